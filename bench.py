@@ -1,7 +1,12 @@
 #!/usr/bin/env python3
 """bench.py -- throughput of the IQ->bursts hot path on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config 2|3|4]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config 2|3|4] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times K steps and prints the JSON line (value, ms_per_step, the kernel intervals of the timed
+region).  `--full` adds everything else the line can carry, each of which costs runs or checks of its own: the parity check
+against the oracle, the isolated pushes of roofline.alone, the host ring passes, cpu_baseline and the `configs` legs.
+`--dump-outputs DIR` writes the bursts the timed path handed over for its last step as DIR/bursts_*.npy (see dump_outputs).
 
 Workloads (BASELINE.json `configs`; config.workload carries the string):
   --config 2 (default)  configs[1]: 8 channels @ 2 MS/s, one wideband cs16 stream per GPU, 67.2 MS per step
@@ -19,7 +24,7 @@ under one (WORLD_SIZE set, as the driver launches it), and fails if fewer than N
 by independent wideband stream (vdlm2dec_amd/shard.py): no data-path collective; RCCL carries the
 timing barrier / max, the parity verdicts and the gather of the packed burst records to rank 0.
 
-Extra objects on the JSON line:
+Extra objects on the JSON line (parity, cpu_baseline, configs, host_ring and roofline.alone with --full only):
   roofline      the channeliser's full-rate kernel (k1_fast at 2 MS/s, k1_pp otherwise -- the only kernel that touches
                 the wideband stream): algorithmic bytes = sample bytes x samples, read once for all 8 channels (SURVEY.md
                 8d), over its mean launch time from HIP events on the library's own stream, inside the timed region.
@@ -311,6 +316,30 @@ def oracle_stream(tiles, fmt: str, rate: int, fos, ntiles: int, order=None):
 def canon(recs: np.ndarray) -> bytes:
     order = np.lexsort((recs["trig_dec"], recs["chn"], recs["stream"]))
     return recs[order].tobytes()
+
+
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(dirname: str, recs: np.ndarray, t_lo: int, t_hi: int, tile_dec: int) -> None:
+    """--dump-outputs: the bursts of the last timed step (packed records, shard.REC_DTYPE, whose instant falls in tiles
+    [t_lo, t_hi) of the stream) in canonical order (stream, channel, instant), one array per field: float64 for the integer
+    fields, float32 for the carrier estimate and the 2040 data bytes.  The inputs are seeded, so two builds run with the
+    same arguments can be compared array for array.  Above DUMP_BYTES a fixed, seeded sample of the records is written."""
+    r = recs[(recs["trig_dec"] // tile_dec >= t_lo) & (recs["trig_dec"] // tile_dec < t_hi)]
+    r = r[np.lexsort((r["trig_dec"], r["chn"], r["stream"]))]
+    total = len(r)
+    row_bytes = 6 * 8 + 4 + r.dtype["data"].shape[0] * 4
+    keep = max(1, (DUMP_BYTES - 4096) // row_bytes)
+    if total > keep:
+        r = r[np.sort(np.random.default_rng(0).choice(total, keep, replace=False))]
+    os.makedirs(dirname, exist_ok=True)
+    arrays = {f"bursts_{k}": r[k].astype(np.float64) for k in ("stream", "chn", "nbrow", "nlbyte", "trig_dec", "end_dec")}
+    arrays["bursts_df"] = np.ascontiguousarray(r["df_bits"]).view(np.float32)
+    arrays["bursts_data"] = r["data"].astype(np.float32)
+    arrays["bursts_total"] = np.array([total], np.float64)       # records in the step, sampled or not
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
 
 
 def oracle_streams(tiles, fmt, rate, fos, ntiles, order=None):
@@ -617,6 +646,11 @@ def main():
                          "whole N > 1 path run on a box with ONE GPU: RCCL refuses two ranks on one device)")
     ap.add_argument("--share-gpu", action="store_true", help="every rank uses cuda:0 (needs --backend gloo): the multi-rank path on a one-GPU box")
     ap.add_argument("--gather-out", default="", help="rank 0 writes the gathered records of the timed region here (.npy, shard.REC_DTYPE): for tests")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="rank 0 writes the bursts of the last timed step here, one float .npy per field (dump_outputs)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline does not need: parity vs the oracle, roofline.alone, host ring, CPU baselines, "
+                         "the `configs` legs (--no-parity / --no-ring / --no-cpu / --no-extra drop single parts of it)")
     args = ap.parse_args()
     if args.share_gpu and args.backend != "gloo":
         sys.exit("bench.py: --share-gpu needs --backend gloo (RCCL refuses two ranks on one device)")
@@ -751,20 +785,22 @@ def main():
     last_timed_tile = npush[0] * ntiles            # exclusive
     tm = rx.timing(reset=True)
     st = rx.stats()
-    # outside the timed region: the same hand-off a few times with nothing else on the GPU (each push finished before
+    # outside the timed region (--full): the same hand-off a few times with nothing else on the GPU (each push finished before
     # the next starts), to tell what the channeliser does alone from what it does while it shares the GPU with the
     # previous push's demodulator (the timed region above)
-    for _ in range(4):
-        rx.push_device(dbufs[npush[0] % NBUF].data_ptr(), batch, stride_bytes)
-        npush[0] += 1
-        rx.sync()
-        drain(False)
-    tm_iso = rx.timing(reset=True)
+    tm_iso = {"channelise_fast_ms": 0.0, "fast_pushes": 0}
+    if args.full:
+        for _ in range(4):
+            rx.push_device(dbufs[npush[0] % NBUF].data_ptr(), batch, stride_bytes)
+            npush[0] += 1
+            rx.sync()
+            drain(False)
+        tm_iso = rx.timing(reset=True)
     # also outside the timed region: the same hand-off from page-locked host memory through the ingest ring (SURVEY 8
     # f-2) -- the PCIe-inclusive rate.  Reported beside `value`, never as `value`.
     host_ring = None
     host_ring_cu8 = None
-    if rank == 0 and world == 1 and not args.no_ring and args.config == 2:
+    if args.full and rank == 0 and world == 1 and not args.no_ring and args.config == 2:
         try:
             if args.fmt == "cs16":      # the reference's native RTL format through the same ring, on a handle of its own (2 bytes per sample)
                 host_ring_cu8 = ring_rate(local, rate, fos, "cu8", batch, [v for v in make_variants([4321 + k for k in range(4)], "cu8", rate, fos, args.bursts_per_s)], ntiles)
@@ -802,9 +838,9 @@ def main():
     parity = None
     ok_local = True
     oracle_time = None
-    if not args.no_parity:
+    if args.full and not args.no_parity:
         # bounded: the oracle handles ~25 MS/s per channel and thread; BENCH_ORACLE_TILES (1200) tiles per stream and at most four streams
-        # per rank keep the check near a minute.  The default run (and the driver's) is covered completely.
+        # per rank keep the check near a minute.  A --full run with the default workload is covered completely.
         ncheck_tiles = min(last_timed_tile, int(os.environ.get("BENCH_ORACLE_TILES", "1200")))
         ncheck_streams = min(nstr, 4)
         packed = shard.pack_records(timed)
@@ -858,8 +894,11 @@ def main():
         ok_all = ok_local
         total_bursts = int(len(timed))
         gathered = None
+        allrecs = shard.pack_records(timed) if (args.gather_out or args.dump_outputs) else None
         if args.gather_out:
-            np.save(args.gather_out, shard.pack_records(timed))
+            np.save(args.gather_out, allrecs)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, allrecs, last_timed_tile - ntiles, last_timed_tile, tile_dec)
 
     rc = 0
     if rank == 0:
@@ -986,7 +1025,8 @@ def main():
                          "valu_issue": valu,
                          "alone": {"avg_launch_ms": iso_ms, "achieved": alg_bytes / (iso_ms * 1e-3) / 1e9 if iso_ms > 0 else 0.0,
                                    "frac": (alg_bytes / (iso_ms * 1e-3) / 1e9 / HBM_PEAK_GBS) if iso_ms > 0 else 0.0,
-                                   "how": "4 pushes after the timed region, each synchronised before the next: no other kernel on the GPU"},
+                                   "how": "4 pushes after the timed region, each synchronised before the next: no other kernel on the GPU"}
+                                  if args.full else None,
                          "note": "live: HIP events around the one full-rate launch of each push inside the timed region (every fourth push "
                                  "carries them), where it runs beside the PREVIOUS push's back stage -- its cluster kernel or verify pass, "
                                  "both of which fill the GPU by themselves: three pushes are in the pipeline (DESIGN.md 4, Host side), so the "
@@ -1022,7 +1062,7 @@ def main():
             out["host_ring_cu8"] = host_ring_cu8
         if os.environ.get("VDL2GPU_DEBUG_COUNTERS") or os.environ.get("VDL2GPU_K1_PROF"):
             out["dbg"] = rx.debug_counters(64)
-        if not args.no_cpu and world == 1:
+        if args.full and not args.no_cpu and world == 1:
             port = cpu_baseline(tiles_np[0], args.fmt, fos, rate)
             ref = cpu_baseline_reference(tiles_np[0], args.fmt, fos, rate)
             if ref is not None:
@@ -1035,7 +1075,7 @@ def main():
             rc = 1
     rx.close()
     leg4 = None
-    if world > 1 and args.config == 2 and not args.no_extra and not (args.rate or args.streams):
+    if args.full and world > 1 and args.config == 2 and not args.no_extra and not (args.rate or args.streams):
         # configs[3] across ALL ranks: 8 streams x 8 channels per rank (64 streams = 512 channels on 8 GPUs), every stream its own
         # recordings, the timed region fenced across the ranks, results collected as SURVEY 8e says.  (The headline above stays the
         # config-2 workload per GPU, so that an N = 1 line and BENCH agree.)
@@ -1069,7 +1109,7 @@ def main():
             out.setdefault("configs", {})["config4_512ch"] = leg4
             if leg4["value"] is None:
                 rc = 1
-        if world == 1 and not args.no_extra and args.config == 2 and not (args.rate or args.streams or args.tiles):
+        if args.full and world == 1 and not args.no_extra and args.config == 2 and not (args.rate or args.streams or args.tiles):
             del dbufs
             torch.cuda.empty_cache()
             out["configs"] = extra_legs(local)

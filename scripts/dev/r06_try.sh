@@ -10,7 +10,7 @@ tail -3 gpurun_out/r06_${tag}_tests.txt
 fi
 for rep in 1 2; do
 for e in "$@"; do
-  env $e timeout 300 python bench.py --no-cpu --no-extra --no-ring 2>/dev/null | tail -1 > /tmp/line.json
+  env $e timeout 300 python bench.py --full --no-cpu --no-extra --no-ring 2>/dev/null | tail -1 > /tmp/line.json
   python - "$e" <<'P'
 import json,sys
 d=json.load(open('/tmp/line.json'))

@@ -3,7 +3,7 @@
 cd "$(dirname "$0")/.."
 export TMPDIR=/tmp
 rm -rf /tmp/prof_ks
-( cd /tmp && rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_ks -- python "$OLDPWD/bench.py" --no-cpu --no-parity --steps 6 --warmup 2 "$@" > /tmp/prof_ks.log 2>&1 )
+( cd /tmp && rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_ks -- python "$OLDPWD/bench.py" --full --no-cpu --no-parity --steps 6 --warmup 2 "$@" > /tmp/prof_ks.log 2>&1 )
 python - <<'PY'
 import glob, csv
 f = glob.glob("/tmp/prof_ks/**/*kernel_stats.csv", recursive=True)[0]

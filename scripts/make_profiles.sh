@@ -1,5 +1,5 @@
 #!/bin/bash
-# Regenerates profiles/rNN_* on a GPU box (gpurun):  R=r04 scripts/make_profiles.sh   (copy gpurun_out/profiles/* to profiles/ afterwards)
+# Regenerates profiles/rNN_* on a GPU box:  R=r04 scripts/make_profiles.sh   (copy $OUT/profiles/* to profiles/ afterwards; OUT defaults to out)
 #   ${R}_bench_line.json         the bench line of the default command
 #   ${R}_bench_kernel_stats.csv  rocprofv3 --kernel-trace --stats summary of the same command
 #   ${R}_bench_pmc_hbm.json      FETCH_SIZE / WRITE_SIZE per kernel launch (separate --pmc passes)
@@ -10,11 +10,11 @@
 cd "$(dirname "$0")/.."
 R=${R:-r05}
 export TMPDIR=/tmp
-OUT=gpurun_out/profiles
+OUT=${OUT:-out}/profiles
 mkdir -p $OUT
 rm -rf /tmp/pr_stats /tmp/pr_f /tmp/pr_w /tmp/pr_s1 /tmp/pr_s2 /tmp/pr_s3
 here=$(pwd)
-B="python $here/bench.py --no-cpu --no-ring --no-extra"
+B="python $here/bench.py --full --no-cpu --no-ring --no-extra"
 ( cd /tmp && rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/pr_stats -- $B > /tmp/pr_stats.log 2>&1 )
 cp $(find /tmp/pr_stats -name "*kernel_stats.csv" | head -1) $OUT/${R}_bench_kernel_stats.csv
 S="--no-parity --steps 4 --warmup 2"
@@ -77,8 +77,8 @@ json.dump({"per_launch": sq, "per_step": {k: {"SQ_INSTS_VALU": v.get("SQ_INSTS_V
            "three --pmc passes of the command above"}, open(out + "/" + R + "_bench_pmc_sq.json", "w"), indent=1)
 PY
 $B 2>/dev/null | tail -1 > $OUT/${R}_bench_line.json
-# the bench line WITH the `configs` object and the CPU baseline (what the driver runs)
-python $here/bench.py --steps 20 --warmup 5 2>/dev/null | tail -1 > $OUT/${R}_bench_line_full.json
+# the bench line WITH the `configs` object and the CPU baseline (--full)
+python $here/bench.py --steps 20 --warmup 5 --full 2>/dev/null | tail -1 > $OUT/${R}_bench_line_full.json
 if [ -n "$WITH_BER" ]; then timeout 900 python scripts/ber_curve.py --out $OUT/${R}_ber_curve.json > $OUT/${R}_ber_curve.txt 2>&1; fi
 python - "$OUT" "$R" <<'PY'
 import sys, json, csv

@@ -1,11 +1,11 @@
 #!/bin/bash
 # profiles/${R}_<leg>_kernel_stats.csv + ${R}_<leg>_pmc.json: rocprofv3 kernel stats and counters (HBM traffic, vector / scalar
 # instructions, LDS conflicts; separate --pmc passes) of bench.py's `configs` legs, each run alone through scripts/dev/legs.py:
-#   R=r04 scripts/make_profiles_configs.sh [c3 c4 busy15 busy30]      (copy gpurun_out/profiles/* to profiles/ afterwards)
+#   R=r04 scripts/make_profiles_configs.sh [c3 c4 busy15 busy30]      (copy $OUT/profiles/* to profiles/ afterwards; OUT defaults to out)
 cd "$(dirname "$0")/.."
 export TMPDIR=/tmp
 R=${R:-r05}
-OUT=gpurun_out/profiles
+OUT=${OUT:-out}/profiles
 mkdir -p $OUT
 here=$(pwd)
 legs=${@:-c3 c4 busy15 busy30}

@@ -15,7 +15,7 @@ for round in 1 2; do
     i=$((i+1))
     [ -f /tmp/libvariant_$i.so ] || continue
     cp /tmp/libvariant_$i.so vdlm2dec_amd/libvdl2gpu.so
-    timeout 300 python bench.py --steps ${STEPS:-12} --warmup 3 --no-cpu 2>&1 | grep "^{" > /tmp/kv.json
+    timeout 300 python bench.py --steps ${STEPS:-12} --warmup 3 --full --no-cpu 2>&1 | grep "^{" > /tmp/kv.json
     python -c "import json; d=json.load(open('/tmp/kv.json')); print('variant $v', round(d['value']), round(d['ms_per_step'],4), {k: round(x,4) for k,x in d['kernels_ms'].items() if k != 'note'}, d['parity']['equal'])"
   done
 done

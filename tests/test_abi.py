@@ -135,12 +135,37 @@ def test_test_handicaps_exist_only_in_the_test_build(built):
     assert "getenv" not in push                                             # every knob is read once, in create_impl
 
 
+def _layout_check_source(lay: dict) -> str:
+    """the checks of oracle/ref_layout_check.c with the reference's offsetof()/sizeof() replaced by their recorded values"""
+    m, t = lay["msgblk_t"], lay["thread_param_t"]
+    checks = [(f"VDL2GPU_MSGBLK_OFF_{k.upper()} == {m[k]}", f"msgblk_t.{k}") for k in ("chn", "Fr", "tv", "ppm", "nbrow", "nlbyte", "data")]
+    checks += [(f"VDL2GPU_MSGBLK_SIZE == {m['size']}", "sizeof(msgblk_t)"),
+               (" && ".join(f"{m['widths'][k]} == 4" for k in ("chn", "Fr", "ppm", "nbrow", "nlbyte")), "msgblk_t field widths"),
+               (f"VDL2GPU_ROWLEN == {m['row_len']} && {m['data_bytes']} >= VDL2GPU_MAXROWS * VDL2GPU_ROWLEN", "msgblk_t.data rows"),
+               (f"sizeof(vdl2gpu_chan_t) == {t['size']} && offsetof(vdl2gpu_chan_t, Fr) == {t['Fr']} && offsetof(vdl2gpu_chan_t, Fo) == {t['Fo']}",
+                "thread_param_t"),
+               (f"VDL2GPU_MAXCH == {lay['MAXNBCHANNELS']}", "MAXNBCHANNELS")]
+    return "#include <stddef.h>\n#include \"vdl2gpu.h\"\n" + "".join(f"_Static_assert({c}, \"{msg}\");\n" for c, msg in checks)
+
+
 def test_msgblk_offsets_are_checked_against_the_reference_header(tmp_path):
     """oracle/ref_layout_check.c (_Static_assert against the reference's own vdlm2.h) is part of `make -C oracle ref`;
-    with one constant of include/vdl2gpu.h changed it must refuse to compile."""
+    with one constant of include/vdl2gpu.h changed it must refuse to compile.  The same checks run everywhere against the
+    reference's layout as recorded in tests/golden/layout/msgblk_layout.json; against its vdlm2.h itself where its sources are at hand."""
+    import json
     import subprocess
+    lay = json.load(open(os.path.join(ROOT, "tests", "golden", "layout", "msgblk_layout.json")))
+    chk = tmp_path / "layout_check.c"
+    chk.write_text(_layout_check_source(lay))
+    hdr = open(os.path.join(ROOT, "include", "vdl2gpu.h")).read()
+    (tmp_path / "changed").mkdir()
+    (tmp_path / "changed" / "vdl2gpu.h").write_text(hdr.replace("VDL2GPU_MSGBLK_OFF_NBROW 36", "VDL2GPU_MSGBLK_OFF_NBROW 40"))
+    for inc, good in ((os.path.join(ROOT, "include"), True), (str(tmp_path / "changed"), False)):
+        r = subprocess.run(["gcc", "-std=c11", "-I" + inc, "-w", "-c", "-o", str(tmp_path / "l.o"), str(chk)], capture_output=True, text=True)
+        assert (r.returncode == 0) == good, r.stderr
+        assert good or "msgblk_t.nbrow" in r.stderr
     if not os.path.isdir("/root/reference"):
-        pytest.skip("needs /root/reference")
+        return
     src = os.path.join(ROOT, "oracle", "ref_layout_check.c")
     ok = subprocess.run(["gcc", "-std=c11", "-DWITH_RTL", "-I/root/reference", "-I" + os.path.join(ROOT, "include"), "-w",
                          "-c", "-o", str(tmp_path / "a.o"), src], capture_output=True, text=True)

@@ -68,7 +68,7 @@ def test_bench_multi_rank_path_on_one_gpu(built, tmp_path):
     records on rank 0 are the records ONE process decodes from the same two streams, their digest of digests is what
     shard.combined_digest() says a two-rank run must produce, and the 512-channel leg (8 streams per rank) ran across both."""
     tiles, steps, warmup = 2, 3, 1
-    common = ["--steps", str(steps), "--warmup", str(warmup), "--tiles", str(tiles), "--no-cpu", "--no-ring"]
+    common = ["--steps", str(steps), "--warmup", str(warmup), "--tiles", str(tiles), "--full", "--no-cpu", "--no-ring"]
     g2 = str(tmp_path / "g2.npy")
     two = _bench_line(["--gpus", "2", "--backend", "gloo", "--share-gpu", "--gather-out", g2] + common)
     assert two["n_gpus"] == 2 and two["value"] and two["parity"]["equal"]
