@@ -111,6 +111,7 @@ typedef struct {
 				 * then be a whole number of 32768-sample blocks (RTLINBUFSZ/2, vdlm2.h:35). */
 
 #define VDL2GPU_F_DEBUG_HEADS 64u	/* diagnostics: keep the header soft bits of every sync trigger of the last push (vdl2gpu_debug_heads) */
+#define VDL2GPU_F_LEVELS 128u	/* measure every burst's signal and noise level on the GPU: vdl2gpu_poll_levels() (see vdl2gpu_level_t) */
 
 /* One decoded burst = the msgblk_t fields the DSP fills (vdlm2.h:39-47). */
 typedef struct {
@@ -127,6 +128,43 @@ typedef struct {
 	int64_t end_sample;
 	uint8_t data[VDL2GPU_MAXROWS][VDL2GPU_ROWLEN];	/* msgblk_t.data rows 0..7 */
 } vdl2gpu_burst_t;
+
+/* ---- link quality (VDL2GPU_F_LEVELS; announced by VDL2GPU_HAVE_LEVELS, the ABI version is unchanged) ----
+ * The reference keeps only the argument of the channel-filtered value S (filteredphase(), d8psk.c:219-229); with
+ * VDL2GPU_F_LEVELS the demodulator also measures |S|^2 while it decodes a burst's payload.  For one channel of one stream,
+ * x[n] = the 84 kS/s sample at stream time n (what vdl2gpu_debug_dec returns), mflt[0..64] the channel filter's taps:
+ *     S(n, c) = sum_j x[n - 16 + j] * mflt[c + 4j]   over j >= 0 with c + 4j <= 64      (newest sample n, sub-phase c = 0..3)
+ *   signal: the burst's symbol evaluations n_k = sym_first_dec + 8k, k = 0 .. nsym-1, all at sub-phase `subphase`:
+ *           sig_power = mean_k |S(n_k, subphase)|^2.  The last of them is end_dec (end_dec = sym_first_dec + 8 (nsym - 1));
+ *           the first lies trig_dec + 1 .. trig_dec + 8 (the first symbol after the reference's P1, d8psk.c:306, which is taken at
+ *           trig_dec with the trigger's own sub-phase 4..12 and is not counted).
+ *   noise:  256 evaluations at sub-phase 0 before the burst, m_i = sym_first_dec - 512 - 8i (i = 0..255; the guard of 512 clears the
+ *           ramp, the sync word and the filter memory), in 8 blocks of 32 (block b: i in [32b, 32b + 32)).  A block is valid if its
+ *           oldest sample m_{32b+31} - 16 >= 0 (the stream's start clips it).  noise_power = the MEDIAN of the valid blocks' mean
+ *           |S|^2 (the mean of the two middle ones for an even count); noise_blocks = the number of valid blocks (0..8); with 0
+ *           blocks noise_power and noise_dbfs are NaN.  The median tolerates the tail of a preceding burst in up to 3 of the 8
+ *           blocks; on a saturated channel (bursts back to back) the value is an upper bound of the noise floor.
+ *   scale:  K = (FS * sum_{j=0..16} mflt[4j])^2, FS = 128 (cu8), 32768 (cs16), 1 (cf32, f32r): the channeliser AVERAGES the
+ *           input samples of each 84 kS/s output (D /= nf, d8psk.c:378), so a full-scale complex tone at the channel centre
+ *           leaves it at FS; sig_dbfs = 10 log10(sig_power / K), noise_dbfs likewise, and that tone reads about 0 dBFS.  White
+ *           noise of sigma per component reads 10 log10(2 sigma^2 / M * sum_j mflt[4j]^2 / K), M = sdrinrate / 84000.  A real
+ *           f32 (VDL2GPU_FMT_F32R) tone reads about 6 dB lower: the real stream's image half is not in the channel.
+ * The sums run in a fixed order over the symbol index (64 strided partial sums in ascending k, then a fixed pairwise tree; each
+ * noise block: a fixed pairwise tree of its 32 values): a burst gets bit-identical levels whatever kernel, path or repair round
+ * decoded it and however the stream was cut into pushes.  Levels need no extra input: the noise window lies inside the carried
+ * planes even for the longest burst decoded in the push after its trigger. */
+#define VDL2GPU_HAVE_LEVELS 1
+typedef struct {
+	float sig_dbfs;		/* @0  10 log10(sig_power / K) */
+	float noise_dbfs;	/* @4  10 log10(noise_power / K); NaN with noise_blocks == 0 */
+	float sig_power;	/* @8  mean |S|^2 over the burst's symbols */
+	float noise_power;	/* @12 median of the valid noise blocks' mean |S|^2; NaN with noise_blocks == 0 */
+	int64_t sym_first_dec;	/* @16 stream time (84 kS/s) of the first symbol evaluation */
+	int32_t nsym;		/* @24 symbol evaluations averaged */
+	int32_t subphase;	/* @28 their FIR sub-phase, 0..3 */
+	int32_t noise_blocks;	/* @32 valid noise blocks, 0..8 */
+	int32_t reserved;	/* @36 0 */
+} vdl2gpu_level_t;		/* sizeof 40, alignment 8 */
 
 typedef struct {
 	uint64_t samples_in;	/* per stream */
@@ -225,6 +263,11 @@ int vdl2gpu_poll(vdl2gpu_t *h, vdl2gpu_burst_t *out, int max);
  * a caller keep the next pushes running while it consumes the earlier ones (three pushes can be in the pipeline;
  * a fourth first collects the oldest). */
 int vdl2gpu_poll_ready(vdl2gpu_t *h, vdl2gpu_burst_t *out, int max);
+/* vdl2gpu_poll / vdl2gpu_poll_ready with the bursts' levels: lv[i] belongs to out[i].  Same queue, order, waiting and threading:
+ * each burst is handed out once, whichever of the four calls takes it.  lv == NULL: exactly the plain call.  lv != NULL on a handle
+ * created without VDL2GPU_F_LEVELS: VDL2GPU_EINVAL, and nothing is consumed. */
+int vdl2gpu_poll_levels(vdl2gpu_t *h, vdl2gpu_burst_t *out, vdl2gpu_level_t *lv, int max);
+int vdl2gpu_poll_levels_ready(vdl2gpu_t *h, vdl2gpu_burst_t *out, vdl2gpu_level_t *lv, int max);
 /* Number of bursts a poll would currently return (implies vdl2gpu_sync). */
 int vdl2gpu_pending(vdl2gpu_t *h);
 /* Pushes the GPU has not finished yet (0..3); never waits.  For a producer that is not bound to real time and wants to

@@ -206,6 +206,12 @@ struct vdl2gpu {
 	size_t fready_pos = 0;
 	uint64_t frames_dropped = 0;
 	vdl2gpu_burst_t *h_pin = nullptr;	/* pinned bounce buffer for record read-back */
+	/* VDL2GPU_F_LEVELS: a level record beside every burst record, at the same index -- in the device rings, the slabs and `ready` */
+	bool levels_on = false;
+	double lev_k = 1.0;	/* K of vdl2gpu.h: power of a full-scale tone at the channel centre */
+	vdl2gpu_level_t *d_levels[VDL2_NRING] = {};
+	vdl2gpu_level_t *h_lslab[VDL2_NSLAB] = {}, *d_lslab[VDL2_NSLAB] = {};
+	std::vector<vdl2gpu_level_t> lready;	/* parallel to `ready` */
 	unsigned *h_pin_cnt = nullptr;	/* pinned, written by k3_rebase: [32*ring + {0..6}] counters, [7] overflowed channels, [8..23] redo mask, [24] most candidates of any channel */
 	unsigned *d_pin_cnt = nullptr;	/* its device address */
 	unsigned pin_recs = 0;
@@ -578,6 +584,7 @@ extern "C" void vdl2gpu_destroy(vdl2gpu_t *h)
 	(void)hipFree(h->d_pn8);
 	for (int r = 0; r < VDL2_NRING; ++r) {
 		(void)hipFree(h->d_recs[r]);
+		(void)hipFree(h->d_levels[r]);
 		(void)hipFree(h->d_frames[r]);
 	}
 	(void)hipFree(h->d_fcnt);
@@ -672,6 +679,9 @@ extern "C" void vdl2gpu_destroy(vdl2gpu_t *h)
 	for (int r = 0; r < VDL2_NSLAB; ++r)
 		if (h->h_slab[r])
 			(void)hipHostFree(h->h_slab[r]);
+	for (int r = 0; r < VDL2_NSLAB; ++r)
+		if (h->h_lslab[r])
+			(void)hipHostFree(h->h_lslab[r]);
 	if (h->h_pin_cnt)
 		(void)hipHostFree(h->h_pin_cnt);
 	if (h->stream)
@@ -881,6 +891,26 @@ static int create_impl(vdl2gpu_t *h)
 	for (int r = 0; r < VDL2_NSLAB; ++r) {
 		HIPCHK(h, hipHostMalloc(&h->h_slab[r], (size_t)h->slab_cap * sizeof(vdl2gpu_burst_t), hipHostMallocMapped));
 		HIPCHK(h, hipHostGetDevicePointer((void **)&h->d_slab[r], h->h_slab[r], 0));
+	}
+	h->levels_on = (cfg.flags & VDL2GPU_F_LEVELS) != 0;
+	if (h->levels_on) {
+		for (int r = 0; r < VDL2_NRING; ++r)
+			HIPCHK(h, hipMalloc(&h->d_levels[r], (size_t)h->rec_cap * sizeof(vdl2gpu_level_t)));
+		for (int r = 0; r < VDL2_NSLAB; ++r) {
+			HIPCHK(h, hipHostMalloc(&h->h_lslab[r], (size_t)h->slab_cap * sizeof(vdl2gpu_level_t), hipHostMallocMapped));
+			HIPCHK(h, hipHostGetDevicePointer((void **)&h->d_lslab[r], h->h_lslab[r], 0));
+		}
+		/* K = (FS * sum_j mflt[4j])^2: the channeliser's integrate-and-dump AVERAGES the input samples of an output (D /= nf,
+		 * d8psk.c:378), so a full-scale tone at the channel centre leaves it at FS, and the filter's gain there is the sum of the
+		 * taps of one sub-phase */
+		float mf[65];
+		HIPCHK(h, hipMemcpyFromSymbol(mf, HIP_SYMBOL(c_mflt), sizeof mf));
+		double g = 0.0;
+		for (int j = 0; j <= 16; ++j)
+			g += (double)mf[4 * j];
+		const double fs = cfg.fmt == VDL2GPU_FMT_CU8 ? 128.0 : (cfg.fmt == VDL2GPU_FMT_CS16 ? 32768.0 : 1.0);
+		const double a = fs * g;
+		h->lev_k = a * a;
 	}
 	HIPCHK(h, hipHostMalloc(&h->h_pin_cnt, 32 * VDL2_NRING * sizeof(unsigned), hipHostMallocMapped));
 	memset(h->h_pin_cnt, 0, 32 * VDL2_NRING * sizeof(unsigned));
@@ -1314,7 +1344,7 @@ static int enqueue_back(vdl2gpu_t *h)
 	hipStream_t ps = h->copy_stream;	/* (four hardware queues: the copy stream has one job) */
 	if (spec) {
 		HIPCHK(h, hipStreamWaitEvent(ps, h->k2c_done, 0));
-		hipLaunchKernelGGL(k2d_payload, dim3((unsigned)h->k2d_grid, (unsigned)(VDL2_CS * GS)), dim3(K2D_NT), 0, ps, k2);
+		hipLaunchKernelGGL(h->levels_on ? k2d_payload_lev : k2d_payload, dim3((unsigned)h->k2d_grid, (unsigned)(VDL2_CS * GS)), dim3(K2D_NT), 0, ps, k2);
 		HIPCHK(h, hipEventRecord(h->pay_done, ps));
 	}
 	if (staged)
@@ -1422,12 +1452,12 @@ static int enqueue_back(vdl2gpu_t *h)
 		if (!h->full_scan && !serial) {
 			K2Params k2p = k2;	/* what the repair rounds (or K2f's serial redo) made void of the first selection is tagged now, what they selected is decoded */
 			k2p.sel_mode = 1;
-			hipLaunchKernelGGL(k2d_payload, dim3((unsigned)h->k2d_grid, (unsigned)(VDL2_CS * GS)), dim3(K2D_NT), 0, ts, k2p);
+			hipLaunchKernelGGL(h->levels_on ? k2d_payload_lev : k2d_payload, dim3((unsigned)h->k2d_grid, (unsigned)(VDL2_CS * GS)), dim3(K2D_NT), 0, ts, k2p);
 		}
 	} else {
 		K2Params k2p = k2;	/* one pass behind the commit: the repaired selection where there is one */
 		k2p.sel_mode = 2;
-		hipLaunchKernelGGL(k2d_payload, dim3((unsigned)h->k2d_grid, (unsigned)(VDL2_CS * GS)), dim3(K2D_NT), 0, ts, k2p);
+		hipLaunchKernelGGL(h->levels_on ? k2d_payload_lev : k2d_payload, dim3((unsigned)h->k2d_grid, (unsigned)(VDL2_CS * GS)), dim3(K2D_NT), 0, ts, k2p);
 	}
 	HIPCHK(h, hipGetLastError());
 	if (staged && h->stage_dump)
@@ -1475,6 +1505,8 @@ static int enqueue_back(vdl2gpu_t *h)
 			ke.count = h->d_outc + 2 * ring;
 			ke.dst = h->d_slab[h->back.slab];
 			ke.cap = std::min(h->slab_cap, h->rec_cap);
+			ke.lev = h->d_levels[ring];	/* (nullptr without VDL2GPU_F_LEVELS) */
+			ke.ldst = h->d_lslab[h->back.slab];
 			hipLaunchKernelGGL(k_export_records, dim3((unsigned)h->n_cu), dim3(256), 0, ts, ke);
 			HIPCHK(h, hipGetLastError());
 			if (staged && h->stage_dump)
@@ -1870,6 +1902,7 @@ static int push_impl(vdl2gpu_t *h, const void *iq, size_t nsamples, size_t strea
 		k2.sel_mode = 0;
 		k2.stage_cap = h->stage_cap;
 		k2.recs = h->d_recs[ring];
+		k2.levels = h->d_levels[ring];	/* (nullptr without VDL2GPU_F_LEVELS: nothing is measured) */
 		k2.outc = h->d_outc + 2 * ring;
 		k2.outc_total_redo = h->d_outc + 8;
 		k2.fmask = h->d_fmask[par];
@@ -2043,6 +2076,13 @@ static inline vdl2gpu_burst_t *rec_of(vdl2gpu_t *h, uint64_t hd)
 	return (src ? h->h_slab[src - 1] : h->ready.data()) + (uint32_t)hd;
 }
 
+/* the level record beside it (VDL2GPU_F_LEVELS) */
+static inline vdl2gpu_level_t *lev_of(vdl2gpu_t *h, uint64_t hd)
+{
+	const unsigned src = (unsigned)(hd >> 32) & 7u;
+	return (src ? h->h_lslab[src - 1] : h->lready.data()) + (uint32_t)hd;
+}
+
 /* A ring's slab is about to be written again (its push's back stage is being enqueued): whatever of it has not been
  * handed out yet moves to the pageable queue.  A consumer that polls after every push never gets here with anything. */
 static void spill_slab(vdl2gpu_t *h, int slab)
@@ -2055,6 +2095,8 @@ static void spill_slab(vdl2gpu_t *h, int slab)
 		if (((h->ready_idx[i] >> 32) & 7u) == (unsigned)(1 + slab)) {
 			h->ready.emplace_back();
 			rec_copy(&h->ready.back(), &h->h_slab[slab][(uint32_t)h->ready_idx[i]], true);
+			if (h->levels_on)
+				h->lready.push_back(h->h_lslab[slab][(uint32_t)h->ready_idx[i]]);
 			h->ready_idx[i] = (uint64_t)(h->ready.size() - 1);
 		}
 }
@@ -2131,6 +2173,7 @@ static int harvest_ring(vdl2gpu_t *h, int ring, bool blocking)
 		}
 		if (h->ready_pos == h->ready_idx.size()) {	/* everything handed out: recycle storage */
 			h->ready.clear();
+			h->lready.clear();
 			h->ready_idx.clear();
 			h->ready_pos = 0;
 			for (int k = 0; k < VDL2_NSLAB; ++k)
@@ -2138,12 +2181,16 @@ static int harvest_ring(vdl2gpu_t *h, int ring, bool blocking)
 		} else if (h->ready_pos > 1024 && h->ready_pos > h->ready_idx.size() / 2) {	/* the handed-out prefix is the larger part of the storage: drop it
 											 * (so the storage never exceeds 2 x the unread records + one push: <= (8 + 1) x max_bursts records) */
 			std::vector<vdl2gpu_burst_t> keep;
+			std::vector<vdl2gpu_level_t> lkeep;
 			keep.reserve(h->ready_idx.size() - h->ready_pos);
 			for (size_t i = h->ready_pos; i < h->ready_idx.size(); ++i) {
 				keep.emplace_back();
 				rec_copy(&keep.back(), rec_of(h, h->ready_idx[i]), ((h->ready_idx[i] >> 32) & 7u) != 0);
+				if (h->levels_on)
+					lkeep.push_back(*lev_of(h, h->ready_idx[i]));
 			}
 			h->ready.swap(keep);
+			h->lready.swap(lkeep);
 			h->ready_idx.resize(h->ready.size());
 			for (size_t i = 0; i < h->ready_idx.size(); ++i)
 				h->ready_idx[i] = (uint64_t)i;
@@ -2162,6 +2209,11 @@ static int harvest_ring(vdl2gpu_t *h, int ring, bool blocking)
 			HIPCHK(h, hipStreamSynchronize(h->copy_stream));
 			const vdl2gpu_burst_t *pin = reinterpret_cast<const vdl2gpu_burst_t *>(h->h_pin);
 			h->ready.insert(h->ready.end(), pin, pin + m);
+			if (h->levels_on) {	/* (40 bytes a record: a pageable copy) */
+				const size_t at = h->lready.size();
+				h->lready.resize(at + m);
+				HIPCHK(h, hipMemcpy(h->lready.data() + at, h->d_levels[ring] + done, (size_t)m * sizeof(vdl2gpu_level_t), hipMemcpyDeviceToHost));
+			}
 		}
 		/* K2d ran ahead of the verify pass: what a repair round (or K2f's serial redo) made void of the first selection
 		 * K2d's second pass has tagged (trig_sample == 2 on the device); everything else is a burst of the chain */
@@ -2174,6 +2226,11 @@ static int harvest_ring(vdl2gpu_t *h, int ring, bool blocking)
 			b.end_sample = dec_to_sample(b.end_dec, (unsigned)h->sdrclk);
 			/* d8psk.c:302, same mixed float/double expression */
 			b.ppm = (float)((double)(10500.0f * b.df) / (2.0 * M_PI * (double)b.Fr) * 1e6);
+			if (h->levels_on) {
+				vdl2gpu_level_t &l = *lev_of(h, handle);
+				l.sig_dbfs = (float)(10.0 * log10((double)l.sig_power / h->lev_k));
+				l.noise_dbfs = (float)(10.0 * log10((double)l.noise_power / h->lev_k));	/* (NaN stays NaN) */
+			}
 			h->ready_idx.push_back(handle);
 		};
 		for (unsigned i = 0; i < ns; ++i)
@@ -2327,12 +2384,14 @@ static int wait_harvest(vdl2gpu_t *h, std::unique_lock<std::recursive_mutex> &lk
 	}
 }
 
-static int hand_out(vdl2gpu_t *h, vdl2gpu_burst_t *out, int max)
+static int hand_out(vdl2gpu_t *h, vdl2gpu_burst_t *out, int max, vdl2gpu_level_t *lv = nullptr)
 {
 	const int n = std::min<int>(max, (int)(h->ready_idx.size() - h->ready_pos));
 	for (int i = 0; i < n; ++i) {
 		const uint64_t hd = h->ready_idx[h->ready_pos + i];
 		rec_copy(out + i, rec_of(h, hd), ((hd >> 32) & 7u) != 0);
+		if (lv)
+			lv[i] = *lev_of(h, hd);
 	}
 	h->ready_pos += (size_t)n;
 	return n;
@@ -2504,6 +2563,46 @@ extern "C" int vdl2gpu_poll_ready(vdl2gpu_t *h, vdl2gpu_burst_t *out, int max)
 	if (rc)
 		return rc;
 	return hand_out(h, out, max);
+}
+
+extern "C" int vdl2gpu_poll_levels(vdl2gpu_t *h, vdl2gpu_burst_t *out, vdl2gpu_level_t *lv, int max)
+{
+	if (!lv)
+		return vdl2gpu_poll(h, out, max);
+	if (!h || (max > 0 && !out) || max < 0)
+		return VDL2GPU_EINVAL;
+	HLOCK(h);
+	if (!h->levels_on) {
+		h->err = "vdl2gpu_poll_levels needs VDL2GPU_F_LEVELS";
+		return VDL2GPU_EINVAL;
+	}
+	if (h->failed)
+		return VDL2GPU_EHIP;
+	HIPCHK(h, hipSetDevice(h->cfg.device));
+	int rc = wait_harvest(h, hlock_);
+	if (rc)
+		return rc;
+	return hand_out(h, out, max, lv);
+}
+
+extern "C" int vdl2gpu_poll_levels_ready(vdl2gpu_t *h, vdl2gpu_burst_t *out, vdl2gpu_level_t *lv, int max)
+{
+	if (!lv)
+		return vdl2gpu_poll_ready(h, out, max);
+	if (!h || (max > 0 && !out) || max < 0)
+		return VDL2GPU_EINVAL;
+	HLOCK(h);
+	if (!h->levels_on) {
+		h->err = "vdl2gpu_poll_levels_ready needs VDL2GPU_F_LEVELS";
+		return VDL2GPU_EINVAL;
+	}
+	if (h->failed)
+		return VDL2GPU_EHIP;
+	HIPCHK(h, hipSetDevice(h->cfg.device));
+	int rc = harvest_all(h, false);
+	if (rc)
+		return rc;
+	return hand_out(h, out, max, lv);
 }
 
 extern "C" int vdl2gpu_get_stats(vdl2gpu_t *h, vdl2gpu_stats_t *out)

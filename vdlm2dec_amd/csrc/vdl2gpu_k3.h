@@ -96,6 +96,8 @@ struct KExportParams {
 	const unsigned *count;	/* records written (device counter of this push's ring) */
 	vdl2gpu_burst_t *dst;	/* device address of the ring's slab */
 	unsigned cap;		/* records the slab holds */
+	const vdl2gpu_level_t *lev;	/* VDL2GPU_F_LEVELS: the ring's level records, else nullptr ... */
+	vdl2gpu_level_t *ldst;	/* ... and the slab's */
 };
 /* Only what a record uses travels: the header and the rows of the burst (a record is eight rows of 255 bytes; a typical
  * burst fills one or two) -- a sixth of the PCIe traffic and of what the collecting thread reads; the host zero-fills the
@@ -104,6 +106,7 @@ __global__ __launch_bounds__(256)
 void k_export_records(KExportParams p)
 {
 	static_assert(sizeof(vdl2gpu_burst_t) % 8 == 0 && offsetof(vdl2gpu_burst_t, data) % 8 == 0, "records are copied as 8-byte words");
+	static_assert(sizeof(vdl2gpu_level_t) % 8 == 0 && sizeof(vdl2gpu_level_t) / 8 <= 64, "level records too");
 	unsigned n = *p.count;
 	n = n < p.cap ? n : p.cap;
 	const unsigned lane = threadIdx.x & 63u;
@@ -115,6 +118,8 @@ void k_export_records(KExportParams p)
 		unsigned long long *dst = reinterpret_cast<unsigned long long *>(p.dst + r);
 		for (unsigned i = lane; i < words; i += 64u)
 			dst[i] = src[i];
+		if (p.lev && lane < sizeof(vdl2gpu_level_t) / 8)	/* (uniform) the level record beside it */
+			reinterpret_cast<unsigned long long *>(p.ldst + r)[lane] = reinterpret_cast<const unsigned long long *>(p.lev + r)[lane];
 	}
 }
 

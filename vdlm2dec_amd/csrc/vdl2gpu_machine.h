@@ -54,6 +54,89 @@ __device__ __forceinline__ void burst_timing(int clk0, int *j0, int *rb)
 	*rb = clk0 + 4 * j - 32;	/* sub-phase during and after the burst */
 }
 
+/* VDL2GPU_F_LEVELS: |S|^2 of one evaluation, S formed exactly as k2_fir_phase_tab forms it before its atan2f (x[0..16] ends at the
+ * newest sample; smf = mflt[] in LDS, zero padded to 72) */
+__device__ __forceinline__ float lev_pow(const float2 *x, int tap0, const float *smf)
+{
+	float sr = 0.0f, si = 0.0f;
+#pragma unroll
+	for (int j = 0; j < 16; ++j) {
+		const float2 v = x[j];
+		const float m = smf[tap0 + 4 * j];
+		sr += v.x * m;
+		si += v.y * m;
+	}
+	if (tap0 == 0) {
+		const float2 v = x[16];
+		const float m = smf[64];
+		sr += v.x * m;
+		si += v.y * m;
+	}
+	return sr * sr + si * si;
+}
+
+/* VDL2GPU_F_LEVELS: the signal and noise level of one burst (vdl2gpu.h, vdl2gpu_level_t), by the first wavefront of the workgroup
+ * alone, in an order that depends on nothing but the symbol index -- so that every kernel and path that decodes the burst (K2d, the
+ * serial machine, a repair round; any NT >= 64) writes the same bits:
+ *   signal  lane l sums |S|^2 of symbols l, l + 64, l + 128, ... in ascending order, then the xor butterfly 32, 16, .., 1 (every lane
+ *           ends with the same sum: float addition commutes), divided by nsym;
+ *   noise   lane l takes evaluations i = l + 64 r (r = 0..3): block 2r + l / 32; each block is summed by the butterfly 16, .., 1 over
+ *           its 32 lanes and multiplied by 1/32 (exact); lanes 0..7 hold the block means, and their ranks among the valid ones pick
+ *           the median (with an even count: (lower + upper) * 0.5).
+ * lo: stream time of frame 0 of the planes.  The noise window of any burst the planes hold lies at or above it (VDL2_LEV_GUARD's
+ * static_assert); the test only keeps a broken invariant from reading outside the planes. */
+__device__ __forceinline__ void burst_levels(vdl2gpu_level_t *lev, const float2 *x0, long long first, int nsym, int rb, const float *smf, long long lo)
+{
+	const int lane = (int)threadIdx.x;	/* (callers: threadIdx.x < 64) */
+	float acc = 0.0f;
+	for (int k = lane; k < nsym; k += 64)
+		acc += lev_pow(x0 + (first - 16 + 8LL * k), rb, smf);
+#pragma unroll
+	for (int d = 32; d >= 1; d >>= 1)
+		acc += __shfl_xor(acc, d, 64);
+	/* a block is valid if its oldest sample is (the block of lane b < 8 is block b) */
+	const long long oldest = first - VDL2_LEV_GUARD - 8LL * (VDL2_LEV_BLOCK * (lane & 7) + VDL2_LEV_BLOCK - 1) - 16;
+	const bool myv = lane < 8 && oldest >= 0 && oldest >= lo;
+	const unsigned long long vmask = __ballot(myv);
+	float mym = 0.0f;	/* lane b < 8: mean |S|^2 of block b */
+#pragma unroll 1
+	for (int r = 0; r < VDL2_LEV_NEVAL / 64; ++r) {
+		const int i = lane + 64 * r;
+		const int b = i / VDL2_LEV_BLOCK;	/* uniform over each half-wavefront */
+		float v = ((vmask >> b) & 1u) ? lev_pow(x0 + (first - VDL2_LEV_GUARD - 8LL * i - 16), 0, smf) : 0.0f;
+#pragma unroll
+		for (int d = VDL2_LEV_BLOCK / 2; d >= 1; d >>= 1)
+			v += __shfl_xor(v, d, 64);
+		v = v * (1.0f / VDL2_LEV_BLOCK);
+		const float v0 = __shfl(v, 0, 64), v1 = __shfl(v, 32, 64);
+		mym = lane == 2 * r ? v0 : (lane == 2 * r + 1 ? v1 : mym);
+	}
+	/* median of the valid block means: rank of each among them (ties broken by the block index), then the middle one(s) */
+	int rank = 0;
+#pragma unroll
+	for (int c = 0; c < VDL2_LEV_NEVAL / VDL2_LEV_BLOCK; ++c) {
+		const float mc = __shfl(mym, c, 64);
+		rank += ((vmask >> c) & 1u) && (mc < mym || (mc == mym && c < lane)) ? 1 : 0;
+	}
+	const int nb = __popcll(vmask);
+	const int hi = nb / 2, lo2 = (nb & 1) ? hi : hi - 1;
+	const unsigned long long bh = __ballot(myv && rank == hi), bl = __ballot(myv && rank == lo2);
+	const float mh = __shfl(mym, bh ? __ffsll((long long)bh) - 1 : 0, 64), ml = __shfl(mym, bl ? __ffsll((long long)bl) - 1 : 0, 64);
+	if (lane == 0) {
+		vdl2gpu_level_t L;
+		L.sig_dbfs = 0.0f;	/* the host converts (it knows K) */
+		L.noise_dbfs = 0.0f;
+		L.sig_power = acc / (float)nsym;
+		L.noise_power = nb == 0 ? __uint_as_float(0x7fc00000u) : ((nb & 1) ? mh : (ml + mh) * 0.5f);
+		L.sym_first_dec = first;
+		L.nsym = nsym;
+		L.subphase = rb;
+		L.noise_blocks = nb;
+		L.reserved = 0;
+		*lev = L;
+	}
+}
+
 /* Payload of one accepted burst -> output record (all NT threads of the workgroup).
  * One lane per transmitted byte: its 8 bits sit in 3 or 4 consecutive symbols; the lane takes
  * their phases itself (and the one before, for the differential slice): differential slice +
@@ -167,6 +250,16 @@ template <int NT, bool TAB = false> __device__ __forceinline__ void burst_payloa
 	}
 }
 
+/* VDL2GPU_F_LEVELS: the levels of the burst burst_payload has just decoded (called behind it, not inside: the payload decode's
+ * registers are free again by then) */
+__device__ __forceinline__ void burst_payload_levels(vdl2gpu_level_t *lev, const float2 *x0, long long nstar, int clk0, int nbrow, int nlbyte,
+						     const float *smf, long long lo)
+{
+	int j0, rb;
+	burst_timing(clk0, &j0, &rb);
+	burst_levels(lev, x0, nstar + j0, burst_geom(nbrow, nlbyte).nsym, rb, smf, lo);
+}
+
 template <int NT> struct MachSharedT {
 	float pbuf[VDL2_NPH + NT];	/* phases: [0,68) = history ring */
 	float errs[NT + 2];		/* errs[t+2] = err of eval t; [0],[1] = p2err, perr */
@@ -188,6 +281,7 @@ struct MachCtx {
 	long long dec_base, avail_end;
 	const uint8_t *pn;
 	vdl2gpu_burst_t *recs;	/* sink: output ring, payload decoded at once (K2c serial stretches) ... */
+	vdl2gpu_level_t *levels;	/* ... with its level records (VDL2GPU_F_LEVELS), or nullptr */
 	BurstDesc *desc;	/* ... or descriptor pool, payload decoded by K2d if selected (K2b, K2c) */
 	unsigned *sel, *nsel;	/* K2c: descriptors made by its serial stretches are on the real chain */
 	unsigned dyn_base;	/* first dynamic descriptor slot */
@@ -593,6 +687,8 @@ template <int NT, bool XL> __device__ __forceinline__ long long mach_commit_trig
 		const unsigned slot = (unsigned)sh.ctl[6];
 		if (!XL && !cx.desc && slot != 0xffffffffu)
 			burst_payload<NT>(cx.recs + slot, x0, cx.pn, nstar, clk0, df, nbrow, nlbyte, cx.stream, cx.cfg, nullptr, 1, 0, nullptr, nullptr, sh.smf);
+		if (!XL && !cx.desc && slot != 0xffffffffu && cx.levels && threadIdx.x < 64)
+			burst_payload_levels(cx.levels + slot, x0, nstar, clk0, nbrow, nlbyte, sh.smf, cx.dec_base);
 		if (slot == 0xffffffffu)
 			out.badslot = 1;
 		out.nslots++;
@@ -710,6 +806,7 @@ __device__ __forceinline__ void mach_ctx(MachCtx &cx, const K2Params &p, int s, 
 	cx.desc_static = -1;
 	if (to_stage) {
 		cx.recs = nullptr;
+		cx.levels = nullptr;
 		cx.dyn_base = (unsigned)p.nstreams * VDL2_CS * VDL2_CAND_CAP * VDL2_CL_MAXB;
 		cx.desc = p.stage;
 		cx.rec_count = p.ctl + CTL_STAGE;
@@ -717,6 +814,7 @@ __device__ __forceinline__ void mach_ctx(MachCtx &cx, const K2Params &p, int s, 
 		cx.rec_cap = p.stage_cap;
 	} else {
 		cx.recs = p.recs;
+		cx.levels = p.levels;
 		cx.dyn_base = 0;
 		cx.desc = nullptr;
 		cx.rec_count = p.outc;

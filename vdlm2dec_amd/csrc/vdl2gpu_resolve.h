@@ -1274,8 +1274,10 @@ void k2f_commit(K2Params p)
 #define K2D_WAVES 5	/* 91 registers, no spill (round 4: 119 / four wavefronts -- with the table paths a run-time choice the kernel carried the
 			 * code and the scalar registers of the paths it never takes: burst_payload<NT, TAB>) */
 #endif
-__global__ __launch_bounds__(K2D_NT) __attribute__((amdgpu_waves_per_eu(K2D_WAVES, 8)))
-void k2d_payload(K2Params p)
+/* LEV (VDL2GPU_F_LEVELS): behind every burst its first wavefront measures the levels (burst_payload_levels) -- a kernel of its own,
+ * k2d_payload_lev, with the registers it needs (four wavefronts): k2d_payload sits at the edge of its five and spilled with the pass
+ * inlined; it carries none of it */
+template <bool LEV> __device__ __forceinline__ void k2d_run(const K2Params &p)
 {
 	__shared__ unsigned s_slot;
 	__shared__ float sph[VDL2_MAXSYM];
@@ -1364,9 +1366,23 @@ void k2d_payload(K2Params p)
 			const int s = d.sc / VDL2_CS;
 			const float2 *x0 = p.dec + (size_t)d.sc * p.cap - p.dec_base;
 			burst_payload<K2D_NT, true>(p.recs + slot, x0, p.pn, d.nstar, d.clk0, d.df, d.nbrow, d.nlbyte, s, p.cfg[d.sc], sph, p.sel_mode == 0 ? 0 : 1, d.sc, s_tabs, p.pn8);
+			if (LEV && threadIdx.x < 64)
+				burst_payload_levels(p.levels + slot, x0, d.nstar, d.clk0, d.nbrow, d.nlbyte, s_tabs, p.dec_base);
 		}
 		__syncthreads();
 	}
+}
+
+__global__ __launch_bounds__(K2D_NT) __attribute__((amdgpu_waves_per_eu(K2D_WAVES, 8)))
+void k2d_payload(K2Params p)
+{
+	k2d_run<false>(p);
+}
+
+__global__ __launch_bounds__(K2D_NT) __attribute__((amdgpu_waves_per_eu(4, 8)))
+void k2d_payload_lev(K2Params p)
+{
+	k2d_run<true>(p);
 }
 
 #endif

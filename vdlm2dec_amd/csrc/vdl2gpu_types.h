@@ -21,6 +21,16 @@ static_assert(VDL2_NSET >= 3 && VDL2_NSET <= 4, "d_outc[] has the per-ring count
 #define VDL2_MAXSYM 5456	/* >= ceil((25 + 8*8*255)/3) symbols of the longest burst */
 #define VDL2_SERIAL_BELOW 4096	/* pushes of at most this many 84 kS/s frames go to the serial machine directly */
 #define VDL2_CARRY_FRAMES 49152	/* >= longest burst (43592 frames) + history + slack */
+#define VDL2_LONGEST_BURST 43592	/* trigger .. last symbol of the longest burst, frames: j0 + 8 (nsym - 1) <= 7 + 8 * 5448 (+ 1 of slack) */
+/* VDL2GPU_F_LEVELS (vdl2gpu.h, vdl2gpu_level_t): the noise window reaches VDL2_LEV_GUARD + 8 * (VDL2_LEV_NEVAL - 1) + 16 frames in
+ * front of a burst's first symbol.  A burst decoded in the push after its trigger (deferred) lies in the carried frames, and so must
+ * its noise window: otherwise its levels would read stale planes and depend on where the stream was cut. */
+#define VDL2_LEV_GUARD 512
+#define VDL2_LEV_NEVAL 256
+#define VDL2_LEV_BLOCK 32
+static_assert(VDL2_LONGEST_BURST + VDL2_LEV_GUARD + 8 * VDL2_LEV_NEVAL + 16 <= VDL2_CARRY_FRAMES,
+	      "the levels' noise window of a deferred burst must lie inside the carried planes");
+static_assert(VDL2_LONGEST_BURST >= 7 + 8 * ((25 + 8 * VDL2GPU_MAXROWS * VDL2GPU_ROWLEN + 2) / 3 - 1), "VDL2_LONGEST_BURST covers the longest burst (burst_geom, burst_timing)");
 #define VDL2_PN_BITS (16384 + 64)
 #define VDL2_CAND_CAP 6144	/* trigger candidates per channel per push (round 5: 4096 -> 6144, what the resolver's 23 bytes of LDS per candidate allow) */
 #define VDL2_CL_MAXB 4		/* bursts per cluster before the resolver takes over */
@@ -172,6 +182,7 @@ struct K2Params {
 				 * 2 = one pass behind the commit: the repaired selection for masked channels, the first for the others */
 	unsigned stage_cap;
 	vdl2gpu_burst_t *recs;	/* output ring of this push */
+	vdl2gpu_level_t *levels;	/* VDL2GPU_F_LEVELS: one level record per record slot of `recs`, else nullptr (nothing is measured) */
 	unsigned *outc;		/* [0] = records written, [1] = records dropped (ring full) */
 	unsigned *outc_total_redo;	/* running count of serial redos (host adapts the number of repair rounds) */
 	unsigned *fmask;	/* [16] bit per (stream, channel slot) that a repair round re-resolved or K2f redid serially in this push */

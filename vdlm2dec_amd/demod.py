@@ -29,6 +29,23 @@ class ThreadParam:
     Fo: int
 
 
+@dataclass(frozen=True)
+class Level:
+    """vdl2gpu_level_t: the burst's signal and noise level (Receiver(levels=True); definitions in include/vdl2gpu.h)."""
+    sig_dbfs: float
+    noise_dbfs: float          # NaN with noise_blocks == 0
+    sig_power: float
+    noise_power: float         # NaN with noise_blocks == 0
+    sym_first_dec: int
+    nsym: int
+    subphase: int
+    noise_blocks: int
+
+    @classmethod
+    def from_c(cls, v) -> "Level":
+        return cls(v.sig_dbfs, v.noise_dbfs, v.sig_power, v.noise_power, v.sym_first_dec, v.nsym, v.subphase, v.noise_blocks)
+
+
 @dataclass
 class Burst:
     """The msgblk_t fields the DSP fills (vdlm2.h:39-47) plus stream-time stamps."""
@@ -44,6 +61,7 @@ class Burst:
     trig_sample: int
     end_sample: int
     data: bytes            # 8 rows x 255 bytes, row-major
+    level: Optional[Level] = None   # Receiver(levels=True) only; not part of key()
 
     def key(self):
         return (self.stream, self.chn, self.nbrow, self.nlbyte, self.data)
@@ -58,7 +76,8 @@ class Receiver:
     def __init__(self, sdrinrate: int, channels: Sequence[ThreadParam] | Sequence[Sequence[ThreadParam]],
                  fmt: str = "cu8", max_push: int = 1 << 22, device: int = 0, sdrclk: int = 0,
                  max_bursts: int = 0, keep_dec: bool = False, serial: bool = False, full_scan: bool = False,
-                 frames: bool = False, rtl_quirk: bool = False, flags: int = 0, testhooks: bool = False):
+                 frames: bool = False, rtl_quirk: bool = False, flags: int = 0, testhooks: bool = False,
+                 levels: bool = False):
         # testhooks: load libvdl2gpu_test.so, the build that honours F_TEST_NOREGION / VDL2GPU_PRIM_DROP / VDL2GPU_SPLIT_SAMPLES
         self.L = _lib.load(testhooks=testhooks or bool(flags & _lib.F_TEST_NOREGION))
         if channels and isinstance(channels[0], ThreadParam):
@@ -85,8 +104,9 @@ class Receiver:
         cfg.max_push = max_push
         cfg.device = device
         cfg.max_bursts = max_bursts
-        cfg.flags = (_lib.F_KEEP_DEC if keep_dec else 0) | (_lib.F_SERIAL if serial else 0) | (_lib.F_FULLSCAN if full_scan else 0) | (_lib.F_FRAMES if frames else 0) | (_lib.F_RTL_QUIRK if rtl_quirk else 0) | flags
+        cfg.flags = (_lib.F_KEEP_DEC if keep_dec else 0) | (_lib.F_SERIAL if serial else 0) | (_lib.F_FULLSCAN if full_scan else 0) | (_lib.F_FRAMES if frames else 0) | (_lib.F_RTL_QUIRK if rtl_quirk else 0) | (_lib.F_LEVELS if levels else 0) | flags
         self.max_push = max_push
+        self.levels = bool(cfg.flags & _lib.F_LEVELS)
         self.h = C.c_void_p()
         rc = self.L.vdl2gpu_create(C.byref(cfg), C.byref(self.h))
         if rc != 0:
@@ -137,30 +157,36 @@ class Receiver:
     def sync(self):
         self._check(self.L.vdl2gpu_sync(self.h))
 
-    def poll(self, max_bursts: int = 4096) -> List[Burst]:
+    def _collect(self, ready: bool, max_bursts: int) -> List[Burst]:
         out: List[Burst] = []
         buf = (_lib.BurstT * max_bursts)()
+        lv = (_lib.LevelT * max_bursts)() if self.levels else None
         while True:
-            n = self._check(self.L.vdl2gpu_poll(self.h, buf, max_bursts))
+            if lv is not None:
+                fn = self.L.vdl2gpu_poll_levels_ready if ready else self.L.vdl2gpu_poll_levels
+                n = self._check(fn(self.h, buf, lv, max_bursts))
+            else:
+                fn = self.L.vdl2gpu_poll_ready if ready else self.L.vdl2gpu_poll
+                n = self._check(fn(self.h, buf, max_bursts))
             for i in range(n):
                 b = buf[i]
                 out.append(Burst(b.stream, b.chn, b.Fr, b.nbrow, b.nlbyte, b.df, b.ppm, b.trig_dec, b.end_dec,
-                                 b.trig_sample, b.end_sample, bytes(b.data)))
+                                 b.trig_sample, b.end_sample, bytes(b.data), Level.from_c(lv[i]) if lv is not None else None))
             if n < max_bursts:
                 return out
 
+    def poll(self, max_bursts: int = 4096) -> List[Burst]:
+        """Every burst of everything pushed so far (with its Level on a levels=True receiver)."""
+        return self._collect(False, max_bursts)
+
     def poll_ready(self, max_bursts: int = 4096) -> List[Burst]:
         """Bursts of pushes the GPU has already finished; never waits."""
-        out: List[Burst] = []
-        buf = (_lib.BurstT * max_bursts)()
-        while True:
-            n = self.poll_ready_raw(buf, max_bursts)
-            for i in range(n):
-                b = buf[i]
-                out.append(Burst(b.stream, b.chn, b.Fr, b.nbrow, b.nlbyte, b.df, b.ppm, b.trig_dec, b.end_dec,
-                                 b.trig_sample, b.end_sample, bytes(b.data)))
-            if n < max_bursts:
-                return out
+        return self._collect(True, max_bursts)
+
+    def poll_levels_raw(self, buf, lv, max_bursts: int, ready: bool = False) -> int:
+        """vdl2gpu_poll_levels(_ready) into caller-owned (lib.BurstT * n) / (lib.LevelT * n) arrays; lv may be None."""
+        fn = self.L.vdl2gpu_poll_levels_ready if ready else self.L.vdl2gpu_poll_levels
+        return self._check(fn(self.h, buf, lv, max_bursts))
 
     def poll_ready_raw(self, buf, max_bursts: int) -> int:
         """vdl2gpu_poll_ready: bursts of pushes that have already finished; never waits."""

@@ -23,12 +23,13 @@ F_TEST_NOREGION = 8
 F_FRAMES = 16
 F_RTL_QUIRK = 32
 F_DEBUG_HEADS = 64
+F_LEVELS = 128
 
 # every symbol include/vdl2gpu.h declares
 EXPORTS = (
     "vdl2gpu_abi_version", "vdl2gpu_create", "vdl2gpu_destroy", "vdl2gpu_push", "vdl2gpu_sync",
     "vdl2gpu_ring_init", "vdl2gpu_ring_acquire", "vdl2gpu_ring_commit",
-    "vdl2gpu_poll", "vdl2gpu_poll_ready", "vdl2gpu_pending", "vdl2gpu_inflight", "vdl2gpu_get_stats", "vdl2gpu_get_timing", "vdl2gpu_get_host_profile", "vdl2gpu_last_error",
+    "vdl2gpu_poll", "vdl2gpu_poll_ready", "vdl2gpu_poll_levels", "vdl2gpu_poll_levels_ready", "vdl2gpu_pending", "vdl2gpu_inflight", "vdl2gpu_get_stats", "vdl2gpu_get_timing", "vdl2gpu_get_host_profile", "vdl2gpu_last_error",
     "vdl2gpu_strerror", "vdl2gpu_burst_to_msgblk", "vdl2gpu_decode_blocks", "vdl2gpu_poll_frames", "vdl2gpu_poll_frames_ready", "reversebits", "vdl2gpu_lo_table", "vdl2gpu_plan",
     "vdl2gpu_choose_fc_rtl", "vdl2gpu_choose_fc_air",
     "vdl2gpu_debug_dec", "vdl2gpu_debug_lo", "vdl2gpu_debug_atan2f", "vdl2gpu_debug_counters", "vdl2gpu_debug_cands", "vdl2gpu_debug_clheads", "vdl2gpu_debug_fail", "vdl2gpu_debug_segs", "vdl2gpu_debug_heads",
@@ -51,6 +52,13 @@ class BurstT(C.Structure):
                 ("nlbyte", C.c_int32), ("df", C.c_float), ("ppm", C.c_float),
                 ("trig_dec", C.c_int64), ("end_dec", C.c_int64), ("trig_sample", C.c_int64),
                 ("end_sample", C.c_int64), ("data", (C.c_uint8 * 255) * 8)]
+
+
+class LevelT(C.Structure):
+    """vdl2gpu_level_t (VDL2GPU_F_LEVELS): 40 bytes, see include/vdl2gpu.h for the definitions."""
+    _fields_ = [("sig_dbfs", C.c_float), ("noise_dbfs", C.c_float), ("sig_power", C.c_float), ("noise_power", C.c_float),
+                ("sym_first_dec", C.c_int64), ("nsym", C.c_int32), ("subphase", C.c_int32), ("noise_blocks", C.c_int32),
+                ("reserved", C.c_int32)]
 
 
 class FrameT(C.Structure):
@@ -123,6 +131,10 @@ def load(testhooks: bool = False):
     L.vdl2gpu_poll_ready.restype = C.c_int
     L.vdl2gpu_poll_ready.argtypes = [C.c_void_p, C.POINTER(BurstT), C.c_int]
     L.vdl2gpu_pending.restype = C.c_int
+    L.vdl2gpu_poll_levels.restype = C.c_int
+    L.vdl2gpu_poll_levels.argtypes = [C.c_void_p, C.POINTER(BurstT), C.POINTER(LevelT), C.c_int]
+    L.vdl2gpu_poll_levels_ready.restype = C.c_int
+    L.vdl2gpu_poll_levels_ready.argtypes = [C.c_void_p, C.POINTER(BurstT), C.POINTER(LevelT), C.c_int]
     L.vdl2gpu_pending.argtypes = [C.c_void_p]
     L.vdl2gpu_get_stats.restype = C.c_int
     L.vdl2gpu_get_stats.argtypes = [C.c_void_p, C.POINTER(StatsT)]
