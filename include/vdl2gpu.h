@@ -91,7 +91,10 @@ typedef struct {
 				 * slower; stats.serial_samples shows it).  Long pushes are therefore cut into equal parts inside the
 				 * library -- the bursts are the same for any cut --: 8.4 s of air time until the first pushes have
 				 * been collected, then as long as fills 90 % of the tables at the candidate density of the busiest
-				 * channel over the last four parts, at most 36 s (72 MS at 2 MS/s). */
+				 * channel over the last four parts, at most 36 s (72 MS at 2 MS/s).
+				 * Limit: every stream holds 8 planes of cap = ceil16(49152 + 21 * max_push / sdrclk + 66) decimated
+				 * samples (8 bytes each) for max_push; vdl2gpu_create returns VDL2GPU_EINVAL when 8 * cap * 8 bytes
+				 * reach 4 GiB (max_push >= 1 596 657 881 at 2 MS/s with the default sdrclk, >= 70 252 947 at sdrclk 22). */
 	int32_t device;		/* HIP device ordinal */
 	uint32_t max_bursts;	/* burst-record ring capacity (0 = default 65536) */
 	uint32_t flags;		/* VDL2GPU_F_* */

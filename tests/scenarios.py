@@ -106,3 +106,19 @@ def corrupted(rate=2_000_000, fo=(200_000,), seed=44):
         t += b.duration() + 0.002
     return synth.StreamSpec(rate=rate, fo=tuple(fo), nsamples=_pad(int((t + 0.005) * rate)), bursts=bursts, noise=1.2,
                             seed=seed)
+
+
+def distinct_streams(n, nsamples=1 << 20, nbase=8, seed=600, bursts_per_s=12.0, info_max=120):
+    """n different cs16 streams of 8 channels, for handles of many streams: ``nbase`` seeded recordings, and for the others one of
+    them shifted circularly by a whole number of IQ pairs (a different shift for every stream that shares a base).  Every stream
+    has its own channel plan: its own order of the 8 offsets over the channel slots and its own tuner frequency (so its own ppm).
+    Returns [(raw, fo, fc)] -- what Receiver(plan_channels(fc, fo)) and the oracle's run_oracle(raw, "cs16", ..., fo, fc) take."""
+    base = [synth.synth_stream(synth.random_scenario(2_000_000, FO8, nsamples, seed=seed + b, bursts_per_s=bursts_per_s,
+                                                     info_max=info_max), "cs16") for b in range(min(n, nbase))]
+    step = nsamples // ((n + nbase - 1) // nbase)
+    out = []
+    for k in range(n):
+        shift = (k // nbase) * (step + 7)
+        perm = np.random.default_rng(seed + 1000 + k).permutation(len(FO8))
+        out.append((np.roll(base[k % nbase], 2 * shift), tuple(FO8[i] for i in perm), FC + 25_000 * k))
+    return out

@@ -175,3 +175,44 @@ def test_msgblk_offsets_are_checked_against_the_reference_header(tmp_path):
     bad = subprocess.run(["gcc", "-std=c11", "-DWITH_RTL", "-I/root/reference", "-I" + str(tmp_path), "-w",
                           "-c", "-o", str(tmp_path / "b.o"), src], capture_output=True, text=True)
     assert bad.returncode != 0 and "msgblk_t.nbrow" in bad.stderr
+
+
+def _plane_frames(max_push, sdrclk):
+    """create_impl's frames per channel plane (vdl2gpu.hip: plane_frames)"""
+    return (49152 + 21 * max_push // sdrclk + 2 + 64 + 15) // 16 * 16
+
+
+@pytest.mark.parametrize("sdrclk", [0, 22])
+def test_create_rejects_planes_of_4_gib(built, sdrclk):
+    """k1_fast addresses a stream's 8 planes with 32-bit byte offsets, so vdl2gpu_create refuses a max_push whose planes would
+    reach 4 GiB -- before any device call.  The largest max_push below the limit passes that check (a handle on a GPU, ENODEV
+    without one); one more sample, which adds a frame, is VDL2GPU_EINVAL on any machine.  With a GPU present only the rejected
+    half runs: a handle just below the limit would allocate more than 12 GB for nothing."""
+    import torch
+    from vdlm2dec_amd import lib
+    clk = sdrclk or 2_000_000 // 4000
+    lo, hi = 1, 1 << 40                  # the smallest max_push whose planes reach 4 GiB
+    while lo < hi:
+        m = (lo + hi) // 2
+        if _plane_frames(m, clk) * 8 * 8 >= 1 << 32:
+            hi = m
+        else:
+            lo = m + 1
+    assert _plane_frames(lo - 1, clk) == (1 << 26) - 16 and _plane_frames(lo, clk) == 1 << 26
+    assert lo == {500: 1_596_657_881, 22: 70_252_947}[clk]     # the values include/vdl2gpu.h states
+    L = lib.load()
+    chan = (lib.ChanT * 1)(lib.ChanT(0, 136_975_000, -50_000))
+
+    def create(max_push):
+        cfg = lib.ConfigT(struct_size=C.sizeof(lib.ConfigT), sdrinrate=2_000_000, sdrclk=sdrclk, fmt=1, nbch=1, nstreams=1,
+                          chan=chan, max_push=max_push)
+        h = C.c_void_p()
+        rc = L.vdl2gpu_create(C.byref(cfg), C.byref(h))
+        if rc == 0:
+            L.vdl2gpu_destroy(h)
+        return rc
+
+    for mp in (lo, lo + 12345, 1 << 27 if sdrclk == 22 else 1 << 31, (1 << 64) - 1):
+        assert create(mp) == -1, mp                                         # VDL2GPU_EINVAL
+    if not torch.cuda.is_available():
+        assert create(lo - 1) == -5                                         # VDL2GPU_ENODEV: past the check, at the device

@@ -585,22 +585,25 @@ def test_more_than_512_channel_slots_take_the_repaired_selection(built, oracle):
     """A handle with more than 64 streams has channel slots the 16-word repair mask does not reach (slot = stream * 8 + channel):
     the payload decode there is one pass behind the commit and must still take the selection a repair round re-resolved, and
     nothing of the resolver's for a channel K2f redid serially (round 4's build decoded the stale first selection for slots >= 512:
-    ADVICE r4).  66 streams of one channel each, region scan dropped so that nearly every burst needs a repair; streams 0, 63, 64,
-    65 against the oracle."""
+    ADVICE r4).  66 different streams of one channel each (each its own recording, channel and tuner frequency), region scan
+    dropped so that nearly every burst needs a repair; every stream against its own oracle run."""
+    from concurrent.futures import ThreadPoolExecutor
     from vdlm2dec_amd import lib
     from vdlm2dec_amd.demod import Receiver, plan_channels
-    spec = synth.random_scenario(2_000_000, S.FO8[:1], 1 << 20, seed=93, bursts_per_s=25.0, info_max=60)
-    raw1 = synth.synth_stream(spec, "cs16")
-    want = sorted(b.key() for b in oracle.run_oracle(raw1, "cs16", spec.rate, spec.fo, S.FC))
     nstr = 66
-    raw = np.stack([raw1] * nstr)
-    with Receiver(spec.rate, [plan_channels(S.FC, spec.fo)] * nstr, fmt="cs16", max_push=1 << 19, flags=lib.F_TEST_NOREGION) as rx:
+    ins = [(raw, fo[:1], fc) for raw, fo, fc in S.distinct_streams(nstr, bursts_per_s=25.0, info_max=60)]
+    with ThreadPoolExecutor(16) as ex:
+        want = list(ex.map(lambda x: sorted(b.key() for b in oracle.run_oracle(x[0], "cs16", 2_000_000, x[1], x[2])), ins))
+    raw = np.stack([r for r, _, _ in ins])
+    with Receiver(2_000_000, [plan_channels(fc, fo) for _, fo, fc in ins], fmt="cs16", max_push=1 << 19, flags=lib.F_TEST_NOREGION) as rx:
         got = rx.run(raw)
         st = rx.stats()
-    assert st["repairs"] + st["serial_redos"] > 0 and len(want) >= 8
-    for s in (0, 63, 64, 65):
+    assert st["repairs"] + st["serial_redos"] > 0
+    assert min(len(w) for w in want) >= 5 and len(want[64]) >= 8 and len(want[65]) >= 8 and sum(map(len, want)) >= 8 * nstr
+    assert {b.stream for b in got} == set(range(nstr)) and len(got) == sum(map(len, want))
+    for s in range(nstr):
         mine = sorted((b.chn, b.nbrow, b.nlbyte, b.data) for b in got if b.stream == s)
-        assert mine == want, s
+        assert mine == want[s], s
 
 
 def test_ingest_ring_equals_push(built, oracle):

@@ -689,6 +689,21 @@ extern "C" void vdl2gpu_destroy(vdl2gpu_t *h)
 	delete h;
 }
 
+/* Frames of one channel plane: the carry, the longest push (max_push at SDRCLK, 21 frames per SDRCLK samples) and slack, on whole
+ * 128-byte lines.  vdl2gpu_create refuses a handle whose 8 planes of a stream reach VDL2_PLANES_MAX bytes; 0 = max_push so large
+ * that the count itself would overflow. */
+static long long plane_frames(uint64_t max_push, unsigned sdrclk)
+{
+	if (max_push > ~0ull / 21)
+		return 0;
+	const long long jmax = (long long)((21ull * max_push) / sdrclk) + 2;
+	return (VDL2_CARRY_FRAMES + jmax + 64 + 15) / 16 * 16;
+}
+
+/* k1_fast addresses the planes of a stream with 32-bit byte offsets from the stream's first plane; every other kernel uses 64-bit
+ * ones.  The limit is part of the ABI (include/vdl2gpu.h, max_push). */
+#define VDL2_PLANES_MAX (1ull << 32)
+
 static int create_impl(vdl2gpu_t *h)
 {
 	const vdl2gpu_config_t &cfg = h->cfg;
@@ -714,7 +729,7 @@ static int create_impl(vdl2gpu_t *h)
 	const int S = h->S, L = h->L;
 	h->k1_tbase.assign((size_t)S * 8, 0u);
 	const long long jmax = (long long)((21ull * cfg.max_push) / (unsigned)h->sdrclk) + 2;
-	h->cap = (VDL2_CARRY_FRAMES + jmax + 64 + 15) / 16 * 16;	/* planes start on 128-byte lines */
+	h->cap = plane_frames(cfg.max_push, (unsigned)h->sdrclk);	/* planes start on 128-byte lines */
 	{
 		/* The item lists (what passes a scan's first screen: 80 bytes an item, three sets) by the longest PART the handle can be given
 		 * -- max_push, or what push_checked cuts longer pushes into (36 s of air time, a third more in a test build): 64 items of private
@@ -1010,6 +1025,9 @@ extern "C" int vdl2gpu_create(const vdl2gpu_config_t *cfg, vdl2gpu_t **out)
 	const unsigned sdrclk = cfg->sdrclk ? cfg->sdrclk : cfg->sdrinrate / 4000;
 	if (sdrclk <= 21 || sdrclk > 1000000)
 		return VDL2GPU_EINVAL;
+	const long long cap = plane_frames(cfg->max_push, sdrclk);
+	if (cap == 0 || (unsigned long long)cap * VDL2_CS * sizeof(float2) >= VDL2_PLANES_MAX)
+		return VDL2GPU_EINVAL;	/* a stream's planes must stay below 4 GiB (k1_fast's 32-bit offsets) */
 	vdl2gpu_t *h = new(std::nothrow) vdl2gpu;
 	if (!h)
 		return VDL2GPU_ENOMEM;
@@ -1711,7 +1729,7 @@ static int push_impl(vdl2gpu_t *h, const void *iq, size_t nsamples, size_t strea
 		}
 		const long long nsp = periods / 4;	/* superperiods of 4 periods = 336 outputs = 21 lines of the planes */
 		const bool fast2m = fast && h->sdrclk == 500 && h->L == 80 && nsp >= 3 && !h->knob.k1_pp &&
-				    (size_t)h->cap * VDL2_CS * sizeof(float2) < (1ull << 32);	/* k1_fast addresses a stream's planes with 32-bit offsets */
+				    (size_t)h->cap * VDL2_CS * sizeof(float2) < VDL2_PLANES_MAX;	/* k1_fast addresses a stream's planes with 32-bit offsets (vdl2gpu_create holds every handle to it) */
 		if (fast2m) {
 			/* 2 MS/s: the LO values of a window fit a lane's registers (lane = window x channel).  Whole superperiods in
 			 * the middle; the first one (carried partial window) and the tail on the general kernel -- unless the push

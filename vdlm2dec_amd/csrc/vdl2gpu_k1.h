@@ -864,7 +864,7 @@ void k1_fast(K1Params p)
 	const float fn = (float)nwin;
 	const float rfn = 1.0f / fn;	/* RN(1/nf) for the exact FMA division below */
 	const float2 *dec = p.dec + (size_t)s * VDL2_CS * p.cap + VDL2_CARRY_FRAMES + (p.per_lo + x) * K1F_PER_OUT + g * 16;	/* workgroup-uniform */
-	const unsigned dvo = (unsigned)(((size_t)(active ? c : 0) * p.cap + kk) * sizeof(float2));	/* planes are < 4 GB apart */
+	const unsigned dvo = (unsigned)(((size_t)(active ? c : 0) * p.cap + kk) * sizeof(float2));	/* a stream's planes span < 4 GiB (VDL2_PLANES_MAX, vdl2gpu_create) */
 	asm volatile("s_waitcnt vmcnt(0)" ::: "memory");	/* from here on the only memory operations are the counted ones below */
 #pragma unroll
 	for (int t = 0; t < 24; ++t)
