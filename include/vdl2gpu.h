@@ -115,6 +115,8 @@ typedef struct {
 
 #define VDL2GPU_F_DEBUG_HEADS 64u	/* diagnostics: keep the header soft bits of every sync trigger of the last push (vdl2gpu_debug_heads) */
 #define VDL2GPU_F_LEVELS 128u	/* measure every burst's signal and noise level on the GPU: vdl2gpu_poll_levels() (see vdl2gpu_level_t) */
+#define VDL2GPU_F_SOFT_RS 256u	/* keep every payload byte's reliability (vdl2gpu_soft_t, vdl2gpu_poll_soft()); with VDL2GPU_F_FRAMES the
+				 * block path then rescues rows the reference cannot decode by erasing their least reliable bytes */
 
 /* One decoded burst = the msgblk_t fields the DSP fills (vdlm2.h:39-47). */
 typedef struct {
@@ -168,6 +170,33 @@ typedef struct {
 	int32_t noise_blocks;	/* @32 valid noise blocks, 0..8 */
 	int32_t reserved;	/* @36 0 */
 } vdl2gpu_level_t;		/* sizeof 40, alignment 8 */
+
+/* ---- soft-decision RS erasures (VDL2GPU_F_SOFT_RS; announced by VDL2GPU_HAVE_SOFT_RS, the ABI version is unchanged) ----
+ * The reference slices the payload hard (V > 0.5, d8psk.c:119, 168) and erases only the padding of a short last row (vdlm2.c:63-82).
+ * With VDL2GPU_F_SOFT_RS the demodulator keeps how sure it was of every payload byte:
+ *   bit reliability   for Grey table w = 0..2 (Grey1/2/3, d8psk.h:47ff) and table index idx = 0..256 (the differential slice):
+ *                     R(w, idx) = min(255, (int)floor(fabs((double)Grey_w[idx] - 0.5) * 512)); the descrambler does not enter.
+ *   byte reliability  payload byte b (bits q = 25 + 8b + i, i = 0..7, counted from the first header bit): the minimum of R over its
+ *                     8 bits, stored at the byte's (row, col) -- the same de-interleave the record's data[] uses.  Every position
+ *                     of rel[][] that carries no transmitted byte (zero fill, rows >= nbrow, parity that is not sent) is 255.
+ * Row rule of the block path in soft mode (vdl2gpu_decode_blocks_soft; the pipeline's block path with VDL2GPU_F_FRAMES).  Row r has
+ * by data bytes and e0 fixed erasures (0, 2 or 4) as in the reference; p_r parity bytes were sent (6 for r < nf_rows - 1, nf_last
+ * for r == nf_rows - 1, 0 beyond; nf_rows = nbrow - 1 and nf_last = 6 when nlbyte <= 2, else nf_rows = nbrow and nf_last = 2, 4, 6
+ * for nlbyte <= 30, <= 67, above):
+ *   1. the reference's rs() runs as always; a row it decodes (count >= 0) is kept as it decoded it;
+ *   2. otherwise the candidates [0, by) and [249, 249 + p_r) are ordered by (reliability, position), both ascending;
+ *   3. for s = 2, then 4, as long as e0 + s <= 4: rs() of the received row with the e0 fixed erasures followed by the first s
+ *      candidates; the first trial that returns >= 0 and leaves all six syndromes zero replaces the row (two parity roots always
+ *      stay for detection);
+ *   4. if none does, the row is what the reference left (its partial corrections included).
+ * HDLC, the flag hunt and the FCS follow unchanged, so a rescued row only ever adds frames that pass the FCS.
+ * Memory: 2048 bytes per record slot in each of the device output rings and each host slab, and in the host queue beside every
+ * burst record it holds. */
+#define VDL2GPU_HAVE_SOFT_RS 1
+typedef struct {
+	uint8_t rel[VDL2GPU_MAXROWS][VDL2GPU_ROWLEN];	/* @0    byte reliability, 0 (on a decision boundary) .. 255 */
+	uint8_t reserved[8];				/* @2040 0 */
+} vdl2gpu_soft_t;		/* sizeof 2048 */
 
 typedef struct {
 	uint64_t samples_in;	/* per stream */
@@ -271,6 +300,11 @@ int vdl2gpu_poll_ready(vdl2gpu_t *h, vdl2gpu_burst_t *out, int max);
  * created without VDL2GPU_F_LEVELS: VDL2GPU_EINVAL, and nothing is consumed. */
 int vdl2gpu_poll_levels(vdl2gpu_t *h, vdl2gpu_burst_t *out, vdl2gpu_level_t *lv, int max);
 int vdl2gpu_poll_levels_ready(vdl2gpu_t *h, vdl2gpu_burst_t *out, vdl2gpu_level_t *lv, int max);
+/* The same with the bursts' reliability maps as well: soft[i] belongs to out[i] (VDL2GPU_F_SOFT_RS).  lv and soft may each be NULL;
+ * lv != NULL without VDL2GPU_F_LEVELS or soft != NULL without VDL2GPU_F_SOFT_RS: VDL2GPU_EINVAL, and nothing is consumed.  The
+ * host queue holds a map beside every unread burst: with the flag, 2048 more bytes per record of the bound above. */
+int vdl2gpu_poll_soft(vdl2gpu_t *h, vdl2gpu_burst_t *out, vdl2gpu_level_t *lv, vdl2gpu_soft_t *soft, int max);
+int vdl2gpu_poll_soft_ready(vdl2gpu_t *h, vdl2gpu_burst_t *out, vdl2gpu_level_t *lv, vdl2gpu_soft_t *soft, int max);
 /* Number of bursts a poll would currently return (implies vdl2gpu_sync). */
 int vdl2gpu_pending(vdl2gpu_t *h);
 /* Pushes the GPU has not finished yet (0..3); never waits.  For a producer that is not bound to real time and wants to
@@ -328,6 +362,10 @@ typedef struct {
  * or a negative error. */
 int vdl2gpu_decode_blocks(vdl2gpu_t *h, const vdl2gpu_burst_t *blocks, int n,
 			  vdl2gpu_frame_t *frames, int max_frames, int *dropped);
+/* The same in soft mode: soft[i] is the reliability map of blocks[i] (vdl2gpu_poll_soft), and rows the reference cannot decode go
+ * through the row rule of vdl2gpu_soft_t.  Works on any handle; soft == NULL: exactly vdl2gpu_decode_blocks. */
+int vdl2gpu_decode_blocks_soft(vdl2gpu_t *h, const vdl2gpu_burst_t *blocks, const vdl2gpu_soft_t *soft, int n,
+			       vdl2gpu_frame_t *frames, int max_frames, int *dropped);
 /* With VDL2GPU_F_FRAMES the same kernel runs on every push's burst records where they lie in device
  * memory, right behind the demodulator.  Collect the frames of everything pushed so far (waits like
  * vdl2gpu_poll; the bursts themselves stay available through vdl2gpu_poll).  Frames come out ordered

@@ -3,12 +3,16 @@
 
     python scripts/ber_curve.py [--esn0 14 16 18 20 22 24 27 30 35] [--bursts 160] [--out profiles/r02_ber_curve.json]
     python scripts/ber_curve.py --oracle-only ...        (no GPU: the curve of the CPU restatement alone)
+    python scripts/ber_curve.py --soft ...               (and soft-decision RS erasures, VDL2GPU_F_SOFT_RS)
 
 Every point: `--bursts` bursts (random AVLC info 1..120 bytes, +-400 Hz carrier offset, random fractional start) on 4
 channels of a 2 MS/s cs16 stream at fixed amplitude, AWGN set for the requested Es/N0 = A^2 * SDRINRATE / (2 sigma^2 *
 10500).  Reported per point: headers accepted (msgblk_t records with the sent nbrow/nlbyte), frames that pass RS + FCS
 and equal the sent frame, mean byte errors per 100 sliced bytes before RS -- and, the point of the exercise, that the
-GPU's records are the oracle's records, byte for byte, at every noise level (decisions near their thresholds included)."""
+GPU's records are the oracle's records, byte for byte, at every noise level (decisions near their thresholds included).
+With --soft every point also counts, over distinct (channel, frame) pairs: the frames of the GPU pipeline in soft mode
+(frames=True, soft_rs=True), the CPU model's soft frames (tests/soft_ref.py), the hard frames (the reference's block path on
+the same records), and the frames that pass the FCS but were never sent (model and GPU)."""
 import argparse
 import json
 import os
@@ -73,11 +77,38 @@ def score(spec, recs):
                 byte_errors_per_100=(100.0 * byte_err / byte_n) if byte_n else None)
 
 
+def soft_point(spec, raw, gpu):
+    """--soft: hard / model soft / GPU soft frames and frames that were never sent"""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import soft_ref as R
+    sent = {}
+    for b in spec.bursts:
+        nbrow, nlbyte, rows = synth.received_rows(b.payload())
+        sent.setdefault(b.chan, set()).update(O.frames_of_block(nbrow, nlbyte, rows))
+    hard, model = set(), set()
+    for c, fo in enumerate(FO):
+        for b, h, rel in R.channel_maps(raw, "cs16", RATE, fo, FC, c):
+            hard.update((c, f) for f in O.frames_of_block(b.nbrow, b.nlbyte, b.data))
+            model.update((c, f) for f in R.soft_frames(h, rel, b.nbrow, b.nlbyte))
+    ok = lambda s: sum(f in sent[c] for c, f in s)          # noqa: E731
+    out = dict(hard_frames=ok(hard), model_soft_frames=ok(model), model_never_sent=len(model) - ok(model),
+               hard_never_sent=len(hard) - ok(hard))
+    if gpu:
+        from vdlm2dec_amd.demod import Receiver, plan_channels
+        with Receiver(RATE, plan_channels(FC, FO), fmt="cs16", max_push=spec.nsamples, frames=True, soft_rs=True) as rx:
+            rx.push(raw)
+            rx.poll()
+            g = {(c, f) for _, c, f in rx.poll_frames()}
+        out.update(gpu_soft_frames=ok(g), gpu_never_sent=len(g) - ok(g), gpu_equals_model=g == model)
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--esn0", type=float, nargs="+", default=[14, 16, 18, 20, 22, 24, 27, 30, 35])
     ap.add_argument("--bursts", type=int, default=160)
     ap.add_argument("--oracle-only", action="store_true")
+    ap.add_argument("--soft", action="store_true", help="add soft-decision RS erasures (VDL2GPU_F_SOFT_RS) to every point")
     ap.add_argument("--out", default="")
     a = ap.parse_args()
     pts = []
@@ -97,16 +128,25 @@ def main():
             pt["gpu_equals_oracle"] = grec == orec and \
                 sorted((b.chn, b.trig_dec, int(np.float32(b.df).view(np.uint32))) for b in gb) == \
                 sorted((b.chn, b.trig_dec, int(np.float32(b.df).view(np.uint32))) for b in ob)
+        if a.soft:
+            pt["soft"] = soft_point(spec, raw, not a.oracle_only)
         pts.append(pt)
         s = pt.get("gpu", pt["oracle"])
         print(f"Es/N0 {e:5.1f} dB  sigma {sigma:6.2f}  sent {s['sent']:4d}  headers {s['headers_ok']:4d}  frames {s['frames_ok']:4d}  "
               f"byte errors/100 {s['byte_errors_per_100'] if s['byte_errors_per_100'] is not None else float('nan'):6.3f}"
               + ("" if a.oracle_only else f"  GPU==oracle {pt['gpu_equals_oracle']}"))
+        if a.soft:
+            q = pt["soft"]
+            print(f"        soft: hard frames {q['hard_frames']:4d}  model soft frames {q['model_soft_frames']:4d}  never sent (model) "
+                  f"{q['model_never_sent']}" + ("" if a.oracle_only else f"  GPU soft frames {q['gpu_soft_frames']:4d}  never sent (GPU) "
+                                                                      f"{q['gpu_never_sent']}  GPU==model {q['gpu_equals_model']}"))
     res = dict(rate=RATE, fo=list(FO), amp=AMP, bursts_per_point=a.bursts, points=pts)
     if a.out:
         json.dump(res, open(a.out, "w"), indent=1)
     if not a.oracle_only and not all(p["gpu_equals_oracle"] for p in pts):
         sys.exit("GPU and oracle differ")
+    if a.soft and not a.oracle_only and not all(p["soft"]["gpu_equals_model"] for p in pts):
+        sys.exit("GPU soft frames and the CPU model differ")
 
 
 if __name__ == "__main__":

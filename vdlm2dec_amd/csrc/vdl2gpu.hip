@@ -212,6 +212,12 @@ struct vdl2gpu {
 	vdl2gpu_level_t *d_levels[VDL2_NRING] = {};
 	vdl2gpu_level_t *h_lslab[VDL2_NSLAB] = {}, *d_lslab[VDL2_NSLAB] = {};
 	std::vector<vdl2gpu_level_t> lready;	/* parallel to `ready` */
+	/* VDL2GPU_F_SOFT_RS: a reliability map beside every burst record, at the same index -- in the device rings, the slabs and `ready`
+	 * (2048 bytes per record slot in each) */
+	bool soft_on = false;
+	vdl2gpu_soft_t *d_soft[VDL2_NRING] = {};
+	vdl2gpu_soft_t *h_sslab[VDL2_NSLAB] = {}, *d_sslab[VDL2_NSLAB] = {};
+	std::vector<vdl2gpu_soft_t> sready;	/* parallel to `ready` */
 	unsigned *h_pin_cnt = nullptr;	/* pinned, written by k3_rebase: [32*ring + {0..6}] counters, [7] overflowed channels, [8..23] redo mask, [24] most candidates of any channel */
 	unsigned *d_pin_cnt = nullptr;	/* its device address */
 	unsigned pin_recs = 0;
@@ -585,6 +591,7 @@ extern "C" void vdl2gpu_destroy(vdl2gpu_t *h)
 	for (int r = 0; r < VDL2_NRING; ++r) {
 		(void)hipFree(h->d_recs[r]);
 		(void)hipFree(h->d_levels[r]);
+		(void)hipFree(h->d_soft[r]);
 		(void)hipFree(h->d_frames[r]);
 	}
 	(void)hipFree(h->d_fcnt);
@@ -682,6 +689,9 @@ extern "C" void vdl2gpu_destroy(vdl2gpu_t *h)
 	for (int r = 0; r < VDL2_NSLAB; ++r)
 		if (h->h_lslab[r])
 			(void)hipHostFree(h->h_lslab[r]);
+	for (int r = 0; r < VDL2_NSLAB; ++r)
+		if (h->h_sslab[r])
+			(void)hipHostFree(h->h_sslab[r]);
 	if (h->h_pin_cnt)
 		(void)hipHostFree(h->h_pin_cnt);
 	if (h->stream)
@@ -906,6 +916,15 @@ static int create_impl(vdl2gpu_t *h)
 	for (int r = 0; r < VDL2_NSLAB; ++r) {
 		HIPCHK(h, hipHostMalloc(&h->h_slab[r], (size_t)h->slab_cap * sizeof(vdl2gpu_burst_t), hipHostMallocMapped));
 		HIPCHK(h, hipHostGetDevicePointer((void **)&h->d_slab[r], h->h_slab[r], 0));
+	}
+	h->soft_on = (cfg.flags & VDL2GPU_F_SOFT_RS) != 0;
+	if (h->soft_on) {
+		for (int r = 0; r < VDL2_NRING; ++r)
+			HIPCHK(h, hipMalloc(&h->d_soft[r], (size_t)h->rec_cap * sizeof(vdl2gpu_soft_t)));
+		for (int r = 0; r < VDL2_NSLAB; ++r) {
+			HIPCHK(h, hipHostMalloc(&h->h_sslab[r], (size_t)h->slab_cap * sizeof(vdl2gpu_soft_t), hipHostMallocMapped));
+			HIPCHK(h, hipHostGetDevicePointer((void **)&h->d_sslab[r], h->h_sslab[r], 0));
+		}
 	}
 	h->levels_on = (cfg.flags & VDL2GPU_F_LEVELS) != 0;
 	if (h->levels_on) {
@@ -1308,6 +1327,12 @@ extern "C" int vdl2gpu_ring_commit(vdl2gpu_t *h, size_t nsamples)
 
 /* The BACK stage of a push (see vdl2gpu::Back): resolver, payload decode beside the verify pass, repair rounds, commit,
  * block path, counters -- on the main stream, behind the previous push's back stage and behind this push's front. */
+/* the payload kernel of the handle's flags: each optional pass is a kernel variant of its own (register pressure) */
+static inline void (*k2d_kernel(const vdl2gpu_t *h))(K2Params)
+{
+	return h->soft_on ? (h->levels_on ? k2d_payload_lev_soft : k2d_payload_soft) : (h->levels_on ? k2d_payload_lev : k2d_payload);
+}
+
 static int enqueue_back(vdl2gpu_t *h)
 {
 	if (!h->back.valid)
@@ -1362,7 +1387,7 @@ static int enqueue_back(vdl2gpu_t *h)
 	hipStream_t ps = h->copy_stream;	/* (four hardware queues: the copy stream has one job) */
 	if (spec) {
 		HIPCHK(h, hipStreamWaitEvent(ps, h->k2c_done, 0));
-		hipLaunchKernelGGL(h->levels_on ? k2d_payload_lev : k2d_payload, dim3((unsigned)h->k2d_grid, (unsigned)(VDL2_CS * GS)), dim3(K2D_NT), 0, ps, k2);
+		hipLaunchKernelGGL(k2d_kernel(h), dim3((unsigned)h->k2d_grid, (unsigned)(VDL2_CS * GS)), dim3(K2D_NT), 0, ps, k2);
 		HIPCHK(h, hipEventRecord(h->pay_done, ps));
 	}
 	if (staged)
@@ -1470,12 +1495,12 @@ static int enqueue_back(vdl2gpu_t *h)
 		if (!h->full_scan && !serial) {
 			K2Params k2p = k2;	/* what the repair rounds (or K2f's serial redo) made void of the first selection is tagged now, what they selected is decoded */
 			k2p.sel_mode = 1;
-			hipLaunchKernelGGL(h->levels_on ? k2d_payload_lev : k2d_payload, dim3((unsigned)h->k2d_grid, (unsigned)(VDL2_CS * GS)), dim3(K2D_NT), 0, ts, k2p);
+			hipLaunchKernelGGL(k2d_kernel(h), dim3((unsigned)h->k2d_grid, (unsigned)(VDL2_CS * GS)), dim3(K2D_NT), 0, ts, k2p);
 		}
 	} else {
 		K2Params k2p = k2;	/* one pass behind the commit: the repaired selection where there is one */
 		k2p.sel_mode = 2;
-		hipLaunchKernelGGL(h->levels_on ? k2d_payload_lev : k2d_payload, dim3((unsigned)h->k2d_grid, (unsigned)(VDL2_CS * GS)), dim3(K2D_NT), 0, ts, k2p);
+		hipLaunchKernelGGL(k2d_kernel(h), dim3((unsigned)h->k2d_grid, (unsigned)(VDL2_CS * GS)), dim3(K2D_NT), 0, ts, k2p);
 	}
 	HIPCHK(h, hipGetLastError());
 	if (staged && h->stage_dump)
@@ -1495,6 +1520,7 @@ static int enqueue_back(vdl2gpu_t *h)
 		k4.tabs = h->d_k4tab;
 		k4.fmask = h->ring_spec[ring] ? h->d_fmask[par] : nullptr;
 		k4.dbg = h->knob.debug_counters ? h->d_dbg : nullptr;
+		k4.soft = h->d_soft[ring];	/* (nullptr without VDL2GPU_F_SOFT_RS: the reference's block path) */
 		hipLaunchKernelGGL(k4_frames, dim3((unsigned)h->n_cu * 16), dim3(K4_NT), 0, ts, k4);
 		HIPCHK(h, hipGetLastError());
 	}
@@ -1525,6 +1551,8 @@ static int enqueue_back(vdl2gpu_t *h)
 			ke.cap = std::min(h->slab_cap, h->rec_cap);
 			ke.lev = h->d_levels[ring];	/* (nullptr without VDL2GPU_F_LEVELS) */
 			ke.ldst = h->d_lslab[h->back.slab];
+			ke.soft = h->d_soft[ring];	/* (nullptr without VDL2GPU_F_SOFT_RS) */
+			ke.sdst = h->d_sslab[h->back.slab];
 			hipLaunchKernelGGL(k_export_records, dim3((unsigned)h->n_cu), dim3(256), 0, ts, ke);
 			HIPCHK(h, hipGetLastError());
 			if (staged && h->stage_dump)
@@ -1921,6 +1949,7 @@ static int push_impl(vdl2gpu_t *h, const void *iq, size_t nsamples, size_t strea
 		k2.stage_cap = h->stage_cap;
 		k2.recs = h->d_recs[ring];
 		k2.levels = h->d_levels[ring];	/* (nullptr without VDL2GPU_F_LEVELS: nothing is measured) */
+		k2.soft = h->d_soft[ring];	/* (nullptr without VDL2GPU_F_SOFT_RS) */
 		k2.outc = h->d_outc + 2 * ring;
 		k2.outc_total_redo = h->d_outc + 8;
 		k2.fmask = h->d_fmask[par];
@@ -2101,6 +2130,13 @@ static inline vdl2gpu_level_t *lev_of(vdl2gpu_t *h, uint64_t hd)
 	return (src ? h->h_lslab[src - 1] : h->lready.data()) + (uint32_t)hd;
 }
 
+/* the reliability map beside it (VDL2GPU_F_SOFT_RS) */
+static inline vdl2gpu_soft_t *soft_of(vdl2gpu_t *h, uint64_t hd)
+{
+	const unsigned src = (unsigned)(hd >> 32) & 7u;
+	return (src ? h->h_sslab[src - 1] : h->sready.data()) + (uint32_t)hd;
+}
+
 /* A ring's slab is about to be written again (its push's back stage is being enqueued): whatever of it has not been
  * handed out yet moves to the pageable queue.  A consumer that polls after every push never gets here with anything. */
 static void spill_slab(vdl2gpu_t *h, int slab)
@@ -2115,6 +2151,8 @@ static void spill_slab(vdl2gpu_t *h, int slab)
 			rec_copy(&h->ready.back(), &h->h_slab[slab][(uint32_t)h->ready_idx[i]], true);
 			if (h->levels_on)
 				h->lready.push_back(h->h_lslab[slab][(uint32_t)h->ready_idx[i]]);
+			if (h->soft_on)
+				h->sready.push_back(h->h_sslab[slab][(uint32_t)h->ready_idx[i]]);
 			h->ready_idx[i] = (uint64_t)(h->ready.size() - 1);
 		}
 }
@@ -2192,6 +2230,7 @@ static int harvest_ring(vdl2gpu_t *h, int ring, bool blocking)
 		if (h->ready_pos == h->ready_idx.size()) {	/* everything handed out: recycle storage */
 			h->ready.clear();
 			h->lready.clear();
+			h->sready.clear();
 			h->ready_idx.clear();
 			h->ready_pos = 0;
 			for (int k = 0; k < VDL2_NSLAB; ++k)
@@ -2200,15 +2239,19 @@ static int harvest_ring(vdl2gpu_t *h, int ring, bool blocking)
 											 * (so the storage never exceeds 2 x the unread records + one push: <= (8 + 1) x max_bursts records) */
 			std::vector<vdl2gpu_burst_t> keep;
 			std::vector<vdl2gpu_level_t> lkeep;
+			std::vector<vdl2gpu_soft_t> skeep;
 			keep.reserve(h->ready_idx.size() - h->ready_pos);
 			for (size_t i = h->ready_pos; i < h->ready_idx.size(); ++i) {
 				keep.emplace_back();
 				rec_copy(&keep.back(), rec_of(h, h->ready_idx[i]), ((h->ready_idx[i] >> 32) & 7u) != 0);
 				if (h->levels_on)
 					lkeep.push_back(*lev_of(h, h->ready_idx[i]));
+				if (h->soft_on)
+					skeep.push_back(*soft_of(h, h->ready_idx[i]));
 			}
 			h->ready.swap(keep);
 			h->lready.swap(lkeep);
+			h->sready.swap(skeep);
 			h->ready_idx.resize(h->ready.size());
 			for (size_t i = 0; i < h->ready_idx.size(); ++i)
 				h->ready_idx[i] = (uint64_t)i;
@@ -2231,6 +2274,11 @@ static int harvest_ring(vdl2gpu_t *h, int ring, bool blocking)
 				const size_t at = h->lready.size();
 				h->lready.resize(at + m);
 				HIPCHK(h, hipMemcpy(h->lready.data() + at, h->d_levels[ring] + done, (size_t)m * sizeof(vdl2gpu_level_t), hipMemcpyDeviceToHost));
+			}
+			if (h->soft_on) {
+				const size_t at = h->sready.size();
+				h->sready.resize(at + m);
+				HIPCHK(h, hipMemcpy(h->sready.data() + at, h->d_soft[ring] + done, (size_t)m * sizeof(vdl2gpu_soft_t), hipMemcpyDeviceToHost));
 			}
 		}
 		/* K2d ran ahead of the verify pass: what a repair round (or K2f's serial redo) made void of the first selection
@@ -2402,7 +2450,7 @@ static int wait_harvest(vdl2gpu_t *h, std::unique_lock<std::recursive_mutex> &lk
 	}
 }
 
-static int hand_out(vdl2gpu_t *h, vdl2gpu_burst_t *out, int max, vdl2gpu_level_t *lv = nullptr)
+static int hand_out(vdl2gpu_t *h, vdl2gpu_burst_t *out, int max, vdl2gpu_level_t *lv = nullptr, vdl2gpu_soft_t *sv = nullptr)
 {
 	const int n = std::min<int>(max, (int)(h->ready_idx.size() - h->ready_pos));
 	for (int i = 0; i < n; ++i) {
@@ -2410,6 +2458,8 @@ static int hand_out(vdl2gpu_t *h, vdl2gpu_burst_t *out, int max, vdl2gpu_level_t
 		rec_copy(out + i, rec_of(h, hd), ((hd >> 32) & 7u) != 0);
 		if (lv)
 			lv[i] = *lev_of(h, hd);
+		if (sv)
+			sv[i] = *soft_of(h, hd);
 	}
 	h->ready_pos += (size_t)n;
 	return n;
@@ -2418,6 +2468,12 @@ static int hand_out(vdl2gpu_t *h, vdl2gpu_burst_t *out, int max, vdl2gpu_level_t
 /* ---------------------------------------------------------------- block path */
 extern "C" int vdl2gpu_decode_blocks(vdl2gpu_t *h, const vdl2gpu_burst_t *blocks, int n,
 				     vdl2gpu_frame_t *frames, int max_frames, int *dropped)
+{
+	return vdl2gpu_decode_blocks_soft(h, blocks, nullptr, n, frames, max_frames, dropped);
+}
+
+extern "C" int vdl2gpu_decode_blocks_soft(vdl2gpu_t *h, const vdl2gpu_burst_t *blocks, const vdl2gpu_soft_t *soft, int n,
+					  vdl2gpu_frame_t *frames, int max_frames, int *dropped)
 {
 	if (!h || n < 0 || max_frames < 0 || (n > 0 && !blocks) || (max_frames > 0 && !frames))
 		return VDL2GPU_EINVAL;
@@ -2428,14 +2484,18 @@ extern "C" int vdl2gpu_decode_blocks(vdl2gpu_t *h, const vdl2gpu_burst_t *blocks
 	HLOCK(h);
 	HIPCHK(h, hipSetDevice(h->cfg.device));
 	vdl2gpu_burst_t *d_blk = nullptr;
+	vdl2gpu_soft_t *d_soft = nullptr;
 	vdl2gpu_frame_t *d_fr = nullptr;
 	unsigned *d_cnt = nullptr;
 	auto cleanup = [&]() {
 		(void)hipFree(d_blk);
+		(void)hipFree(d_soft);
 		(void)hipFree(d_fr);
 		(void)hipFree(d_cnt);
 	};
 	hipError_t e = hipMalloc(&d_blk, (size_t)n * sizeof(vdl2gpu_burst_t));
+	if (e == hipSuccess && soft)
+		e = hipMalloc(&d_soft, (size_t)n * sizeof(vdl2gpu_soft_t));
 	if (e == hipSuccess)
 		e = hipMalloc(&d_fr, (size_t)max_frames * sizeof(vdl2gpu_frame_t));
 	if (e == hipSuccess)
@@ -2444,6 +2504,8 @@ extern "C" int vdl2gpu_decode_blocks(vdl2gpu_t *h, const vdl2gpu_burst_t *blocks
 	 * plain hipMemset() that lands after the kernel's first atomics loses frames */
 	if (e == hipSuccess)
 		e = hipMemcpyAsync(d_blk, blocks, (size_t)n * sizeof(vdl2gpu_burst_t), hipMemcpyHostToDevice, h->copy_stream);
+	if (e == hipSuccess && soft)
+		e = hipMemcpyAsync(d_soft, soft, (size_t)n * sizeof(vdl2gpu_soft_t), hipMemcpyHostToDevice, h->copy_stream);
 	if (e == hipSuccess)
 		e = hipMemsetAsync(d_cnt, 0, 4 * sizeof(unsigned), h->copy_stream);
 	unsigned cnt[2] = {0, 0};
@@ -2458,6 +2520,7 @@ extern "C" int vdl2gpu_decode_blocks(vdl2gpu_t *h, const vdl2gpu_burst_t *blocks
 		k4.frame_cap = (unsigned)max_frames;
 		k4.compact = 0;
 		k4.tabs = h->d_k4tab;
+		k4.soft = d_soft;
 		const unsigned grid = (unsigned)std::min<long long>(n, (long long)h->n_cu * 32);
 		hipLaunchKernelGGL(k4_frames, dim3(grid), dim3(K4_NT), 0, h->copy_stream, k4);
 		e = hipGetLastError();
@@ -2621,6 +2684,34 @@ extern "C" int vdl2gpu_poll_levels_ready(vdl2gpu_t *h, vdl2gpu_burst_t *out, vdl
 	if (rc)
 		return rc;
 	return hand_out(h, out, max, lv);
+}
+
+static int poll_soft_impl(vdl2gpu_t *h, vdl2gpu_burst_t *out, vdl2gpu_level_t *lv, vdl2gpu_soft_t *sv, int max, bool blocking)
+{
+	if (!h || (max > 0 && !out) || max < 0)
+		return VDL2GPU_EINVAL;
+	HLOCK(h);
+	if ((lv && !h->levels_on) || (sv && !h->soft_on)) {
+		h->err = lv && !h->levels_on ? "vdl2gpu_poll_soft: lv needs VDL2GPU_F_LEVELS" : "vdl2gpu_poll_soft: soft needs VDL2GPU_F_SOFT_RS";
+		return VDL2GPU_EINVAL;
+	}
+	if (h->failed)
+		return VDL2GPU_EHIP;
+	HIPCHK(h, hipSetDevice(h->cfg.device));
+	int rc = blocking ? wait_harvest(h, hlock_) : harvest_all(h, false);
+	if (rc)
+		return rc;
+	return hand_out(h, out, max, lv, sv);
+}
+
+extern "C" int vdl2gpu_poll_soft(vdl2gpu_t *h, vdl2gpu_burst_t *out, vdl2gpu_level_t *lv, vdl2gpu_soft_t *soft, int max)
+{
+	return poll_soft_impl(h, out, lv, soft, max, true);
+}
+
+extern "C" int vdl2gpu_poll_soft_ready(vdl2gpu_t *h, vdl2gpu_burst_t *out, vdl2gpu_level_t *lv, vdl2gpu_soft_t *soft, int max)
+{
+	return poll_soft_impl(h, out, lv, soft, max, false);
 }
 
 extern "C" int vdl2gpu_get_stats(vdl2gpu_t *h, vdl2gpu_stats_t *out)

@@ -49,6 +49,8 @@ struct K4Params {
 	const unsigned *fmask;		/* not nullptr: the records come from the pipeline, where K2d's second pass tags the void ones 2 (trig_sample) */
 	unsigned long long *dbg;	/* diagnostics: stage cycle counters, or nullptr */
 	const unsigned *tabs;		/* K4_TABW words from k4_tables: gexp[512], glog[256], crc_tab[256] */
+	const vdl2gpu_soft_t *soft;	/* VDL2GPU_F_SOFT_RS: the records' reliability maps, same index: the row rule of vdl2gpu_soft_t for
+					 * rows the reference cannot decode.  nullptr: the reference's block path and nothing else */
 };
 
 #define K4_TABW ((512 + 256 + 512) / 4)
@@ -73,7 +75,9 @@ struct K4Shared {
 	int ctl[16];
 	/* Berlekamp-Massey work arrays live here, not in (scratch-backed) private arrays */
 	uint8_t lam[8], syn[8], bpoly[8], tpoly[8], omg[8], root[8], reg[8], loc[8];
-	int rs_deg, rs_count;
+	int rs_deg, rs_count, rs_fail;
+	uint8_t save[256];	/* soft mode: the received row, for the trials */
+	int cand[4];		/* soft mode: the least reliable candidate positions, most doubtful first */
 };
 
 /* GF(256)/0x187 (rs.c:17-79) and FCS-16 reflected 0x8408 (crc.c) tables, built once per handle */
@@ -234,8 +238,11 @@ __device__ void k4_rs_forney(K4Shared &sh, uint8_t *data, int lane)
 	const uint8_t *gexp = sh.gexp, *glog = sh.glog;
 	const uint8_t *lam = sh.lam, *syn = sh.syn;
 	const int deg = sh.rs_deg, count = sh.rs_count;
-	if (deg != count)
+	if (deg != count) {
+		if (lane == 0)
+			sh.rs_fail = 1;
 		return;
+	}
 	unsigned tmp = 0;
 	if (lane < NR) {
 		for (int j = (deg < lane) ? deg : lane; j >= 0; j--)
@@ -269,6 +276,121 @@ __device__ void k4_rs_forney(K4Shared &sh, uint8_t *data, int lane)
 		data[loc] ^= gexp[k4_m255(glog[num1] + glog[num2] + NNN - glog[den])];
 	if (!bad && lane < count)
 		sh.eras[lane] = loc;
+	if (lane == 0)
+		sh.rs_fail = bad ? 1 : 0;
+}
+
+/* syndromes S_i = sum_j data[j] alpha^((120+i)(254-j)) of one row, reduced over the lanes: every lane returns all six */
+__device__ __forceinline__ unsigned k4_syndromes(const K4Shared &sh, const uint8_t *row, const unsigned (&sexp)[4][2], unsigned (&syn)[6], int lane)
+{
+#pragma unroll
+	for (int i = 0; i < 6; ++i)
+		syn[i] = 0;
+#pragma unroll
+	for (int b = 0; b < 4; ++b) {
+		const int j = lane * 4 + b;
+		if (j < 255) {
+			const unsigned d = row[j];
+			if (d) {
+				const unsigned lg = sh.glog[d];
+#pragma unroll
+				for (int i = 0; i < 6; ++i)
+					syn[i] ^= sh.gexp[lg + ((sexp[b][i / 4] >> (8 * (i % 4))) & 0xffu)];
+			}
+		}
+	}
+	{	/* field sums: XOR over the lanes, four syndromes to a word */
+		unsigned s03 = syn[0] | (syn[1] << 8) | (syn[2] << 16) | (syn[3] << 24), s45 = syn[4] | (syn[5] << 8);
+		for (int d = 32; d > 0; d >>= 1) {
+			s03 ^= __shfl_xor(s03, d, K4_NT);
+			s45 ^= __shfl_xor(s45, d, K4_NT);
+		}
+		syn[0] = s03 & 0xffu;
+		syn[1] = (s03 >> 8) & 0xffu;
+		syn[2] = (s03 >> 16) & 0xffu;
+		syn[3] = s03 >> 24;
+		syn[4] = s45 & 0xffu;
+		syn[5] = s45 >> 8;
+	}
+	return syn[0] | syn[1] | syn[2] | syn[3] | syn[4] | syn[5];
+}
+
+/* rs() of one row with sh.eras[0..nera) (rs.c:81-291): false when it returns -1 */
+__device__ __forceinline__ bool k4_rs_row(K4Shared &sh, uint8_t *row, int nera, const unsigned (&sexp)[4][2], int lane)
+{
+	unsigned syn[6];
+	const unsigned any = k4_syndromes(sh, row, sexp, syn, lane);
+	K4_SYNC();
+	bool ok = true;
+	if (any) {	/* wave-uniform: every lane holds the reduced syndromes */
+		k4_rs_bm(sh, syn, nera, lane);
+		K4_SYNC();
+		k4_rs_chien(sh, lane);
+		K4_SYNC();
+		k4_rs_forney(sh, row, lane);
+		K4_SYNC();
+		ok = sh.rs_fail == 0;
+	}
+	K4_SYNC();
+	return ok;
+}
+
+/* The soft row rule (vdl2gpu.h, vdl2gpu_soft_t) for a row the reference's rs() has just failed on: `row` holds what it left, sh.save
+ * the received row.  The candidates' keys (rel << 8 | position) go through up to four wave-wide minimum searches; each trial starts
+ * from the received row.  Without a success the reference's result is written back: it is what rs() leaves, computed again from the
+ * same row and erasures. */
+__device__ void k4_soft_row(K4Shared &sh, uint8_t *row, const uint8_t *rel, int by, int e0, int pr, const unsigned (&sexp)[4][2], int lane)
+{
+	const int smax = e0 + 4 <= 4 ? 4 : 2;
+	unsigned key[4];
+#pragma unroll
+	for (int b = 0; b < 4; ++b) {
+		const int j = lane * 4 + b;
+		const bool cand = j < by || (j >= 249 && j < 249 + pr);
+		key[b] = cand ? ((unsigned)rel[j] << 8 | (unsigned)j) : 0xffffffffu;
+	}
+	int ncand = 0;
+	for (int t = 0; t < smax; ++t) {
+		unsigned m = key[0];
+#pragma unroll
+		for (int b = 1; b < 4; ++b)
+			m = key[b] < m ? key[b] : m;
+		for (int d = 32; d > 0; d >>= 1) {
+			const unsigned o = __shfl_xor(m, d, K4_NT);
+			m = o < m ? o : m;
+		}
+		if (m == 0xffffffffu)
+			break;
+#pragma unroll
+		for (int b = 0; b < 4; ++b)
+			key[b] = key[b] == m ? 0xffffffffu : key[b];
+		if (lane == 0)
+			sh.cand[t] = (int)(m & 0xffu);
+		++ncand;
+	}
+	K4_SYNC();
+	for (int s = 2; s <= 4; s += 2) {
+		if (e0 + s > 4 || s > ncand)
+			break;
+		for (int i = lane; i < 255; i += K4_NT)
+			row[i] = sh.save[i];
+		if (lane < e0 + s)
+			sh.eras[lane] = lane < e0 ? 255 - e0 + lane : sh.cand[lane - e0];	/* set_eras()'s positions, then the candidates */
+		K4_SYNC();
+		if (k4_rs_row(sh, row, e0 + s, sexp, lane)) {
+			unsigned syn[6];
+			const unsigned any = k4_syndromes(sh, row, sexp, syn, lane);
+			K4_SYNC();
+			if (!any)
+				return;
+		}
+	}
+	for (int i = lane; i < 255; i += K4_NT)
+		row[i] = sh.save[i];
+	if (lane < e0)
+		sh.eras[lane] = 255 - e0 + lane;
+	K4_SYNC();
+	k4_rs_row(sh, row, e0, sexp, lane);
 }
 
 __global__ __launch_bounds__(K4_NT)
@@ -368,44 +490,20 @@ void k4_frames(K4Params p)
 				}
 				nera = by <= 30 ? 4 : (by <= 67 ? 2 : 0);
 			}
-			/* syndromes S_i = sum_j data[j] alpha^((120+i)(254-j)) */
-			unsigned syn[6] = {0, 0, 0, 0, 0, 0};
-#pragma unroll
-			for (int b = 0; b < 4; ++b) {
-				const int j = lane * 4 + b;
-				if (j < 255) {
-					const unsigned d = rows[r * VDL2GPU_ROWLEN + j];
-					if (d) {
-						const unsigned lg = sh.glog[d];
-#pragma unroll
-						for (int i = 0; i < 6; ++i)
-							syn[i] ^= sh.gexp[lg + ((sexp[b][i / 4] >> (8 * (i % 4))) & 0xffu)];
-					}
-				}
-			}
-			{	/* field sums: XOR over the lanes, four syndromes to a word */
-				unsigned s03 = syn[0] | (syn[1] << 8) | (syn[2] << 16) | (syn[3] << 24), s45 = syn[4] | (syn[5] << 8);
-				for (int d = 32; d > 0; d >>= 1) {
-					s03 ^= __shfl_xor(s03, d, K4_NT);
-					s45 ^= __shfl_xor(s45, d, K4_NT);
-				}
-				syn[0] = s03 & 0xffu;
-				syn[1] = (s03 >> 8) & 0xffu;
-				syn[2] = (s03 >> 16) & 0xffu;
-				syn[3] = s03 >> 24;
-				syn[4] = s45 & 0xffu;
-				syn[5] = s45 >> 8;
-			}
-			const unsigned any = syn[0] | syn[1] | syn[2] | syn[3] | syn[4] | syn[5];
-			K4_SYNC();
-			if (any) {	/* wave-uniform: every lane holds the reduced syndromes */
-				k4_rs_bm(sh, syn, nera, lane);
+			uint8_t *const row = rows + r * VDL2GPU_ROWLEN;
+			if (p.soft) {
+				for (int i = lane; i < 255; i += K4_NT)
+					sh.save[i] = row[i];
 				K4_SYNC();
-				k4_rs_chien(sh, lane);
-				K4_SYNC();
-				k4_rs_forney(sh, rows + r * VDL2GPU_ROWLEN, lane);
 			}
-			K4_SYNC();
+			if (!k4_rs_row(sh, row, nera, sexp, lane) && p.soft) {
+				/* the transmitted parity of row r (burst_geom) */
+				const int nf_rows = nlbyte <= 2 ? nbrow - 1 : nbrow;
+				const int nf_last = nlbyte <= 2 ? 6 : (nlbyte <= 30 ? 2 : (nlbyte <= 67 ? 4 : 6));
+				const int pr = r < nf_rows - 1 ? 6 : (r == nf_rows - 1 ? nf_last : 0);
+				if (nera + 2 <= 4)
+					k4_soft_row(sh, row, &p.soft[ib].rel[r][0], by, nera, pr, sexp, lane);
+			}
 			for (int i = lane; i < by; i += K4_NT)
 				sh.src[nby + i] = rows[r * VDL2GPU_ROWLEN + i];
 			nby += by;

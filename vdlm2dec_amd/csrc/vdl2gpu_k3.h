@@ -98,6 +98,8 @@ struct KExportParams {
 	unsigned cap;		/* records the slab holds */
 	const vdl2gpu_level_t *lev;	/* VDL2GPU_F_LEVELS: the ring's level records, else nullptr ... */
 	vdl2gpu_level_t *ldst;	/* ... and the slab's */
+	const vdl2gpu_soft_t *soft;	/* VDL2GPU_F_SOFT_RS: the ring's reliability maps, else nullptr ... */
+	vdl2gpu_soft_t *sdst;	/* ... and the slab's */
 };
 /* Only what a record uses travels: the header and the rows of the burst (a record is eight rows of 255 bytes; a typical
  * burst fills one or two) -- a sixth of the PCIe traffic and of what the collecting thread reads; the host zero-fills the
@@ -120,6 +122,9 @@ void k_export_records(KExportParams p)
 			dst[i] = src[i];
 		if (p.lev && lane < sizeof(vdl2gpu_level_t) / 8)	/* (uniform) the level record beside it */
 			reinterpret_cast<unsigned long long *>(p.ldst + r)[lane] = reinterpret_cast<const unsigned long long *>(p.lev + r)[lane];
+		if (p.soft)	/* (uniform) the map beside it: the rows of the burst, 255 elsewhere */
+			for (unsigned i = lane; i < sizeof(vdl2gpu_soft_t) / 8; i += 64u)
+				reinterpret_cast<unsigned long long *>(p.sdst + r)[i] = reinterpret_cast<const unsigned long long *>(p.soft + r)[i];
 	}
 }
 

@@ -54,6 +54,34 @@ __device__ __forceinline__ void burst_timing(int clk0, int *j0, int *rb)
 	*rb = clk0 + 4 * j - 32;	/* sub-phase during and after the burst */
 }
 
+/* (row, col) of payload byte b: the column-major de-interleave (d8psk.c:127-147, 176-197) as a closed-form scatter */
+__device__ __forceinline__ void burst_scatter(const BurstGeom &g, int b, int *row, int *col)
+{
+	if (b < g.ND) {
+		const int full = g.nd_last * g.nd_rows;
+		if (b < full) {
+			*col = b / g.nd_rows;
+			*row = b % g.nd_rows;
+		} else {
+			const int bb = b - full;
+			*col = g.nd_last + bb / (g.nd_rows - 1);
+			*row = bb % (g.nd_rows - 1);
+		}
+	} else {
+		const int bf = b - g.ND;
+		const int full = g.nf_last * g.nf_rows;
+		if (bf < full) {
+			*col = bf / g.nf_rows;
+			*row = bf % g.nf_rows;
+		} else {
+			const int bb = bf - full;
+			*col = g.nf_last + bb / (g.nf_rows - 1);
+			*row = bb % (g.nf_rows - 1);
+		}
+		*col += 249;
+	}
+}
+
 /* VDL2GPU_F_LEVELS: |S|^2 of one evaluation, S formed exactly as k2_fir_phase_tab forms it before its atan2f (x[0..16] ends at the
  * newest sample; smf = mflt[] in LDS, zero padded to 72) */
 __device__ __forceinline__ float lev_pow(const float2 *x, int tap0, const float *smf)
@@ -209,29 +237,7 @@ template <int NT, bool TAB = false> __device__ __forceinline__ void burst_payloa
 			}
 		}
 		int row, col;
-		if (b < g.ND) {
-			const int full = g.nd_last * g.nd_rows;
-			if (b < full) {
-				col = b / g.nd_rows;
-				row = b % g.nd_rows;
-			} else {
-				const int bb = b - full;
-				col = g.nd_last + bb / (g.nd_rows - 1);
-				row = bb % (g.nd_rows - 1);
-			}
-		} else {
-			const int bf = b - g.ND;
-			const int full = g.nf_last * g.nf_rows;
-			if (bf < full) {
-				col = bf / g.nf_rows;
-				row = bf % g.nf_rows;
-			} else {
-				const int bb = bf - full;
-				col = g.nf_last + bb / (g.nf_rows - 1);
-				row = bb % (g.nf_rows - 1);
-			}
-			col += 249;
-		}
+		burst_scatter(g, b, &row, &col);
 		rec->data[row][col] = (uint8_t)byte;
 	}
 	if (tid == 0) {
@@ -260,6 +266,51 @@ __device__ __forceinline__ void burst_payload_levels(vdl2gpu_level_t *lev, const
 	burst_levels(lev, x0, nstar + j0, burst_geom(nbrow, nlbyte).nsym, rb, smf, lo);
 }
 
+/* VDL2GPU_F_SOFT_RS: the reliability map of the burst burst_payload has just decoded (vdl2gpu.h, vdl2gpu_soft_t), all NT threads,
+ * called behind it: one lane per transmitted byte takes the same Grey table indices as the payload decode -- from sph when the caller
+ * kept the phases there (K2d), else from phases of its own (k2_fir_phase_tab, same result bits) -- and writes the minimum of R over
+ * the byte's bits where the byte's data lies. */
+__device__ __forceinline__ unsigned soft_rel(int idx, int which, const float *grey)
+{
+	const float v = grey ? grey[which * 257 + idx] : d_tab(which == 0 ? c_grey1 : (which == 1 ? c_grey2 : c_grey3), idx);
+	const double r = floor(fabs((double)v - 0.5) * 512.0);
+	return r >= 255.0 ? 255u : (unsigned)r;
+}
+
+template <int NT> __device__ __forceinline__ void burst_payload_soft(vdl2gpu_soft_t *out, const float2 *x0, long long nstar, int clk0, float df,
+								     int nbrow, int nlbyte, const float *sph, const float *lds_fir, const float *grey)
+{
+	const int tid = threadIdx.x;
+	int j0, rb;
+	burst_timing(clk0, &j0, &rb);
+	const BurstGeom g = burst_geom(nbrow, nlbyte);
+	const float2 *xs0 = x0 + (nstar + j0 - 16);
+	uint32_t *w = reinterpret_cast<uint32_t *>(out);
+	static_assert(sizeof(vdl2gpu_soft_t) == 2048 && offsetof(vdl2gpu_soft_t, reserved) == 2040, "the map is 510 words of 255, then 2 of 0");
+	for (int i = tid; i < 512; i += NT)
+		w[i] = i < 510 ? 0xffffffffu : 0u;
+	__syncthreads();
+	for (int b = tid; b < g.ND + g.NF; b += NT) {
+		const int q0 = 25 + 8 * b;
+		const int k0 = q0 / 3;
+		int q = q0;
+		unsigned rel = 255u;
+		float pprev = sph ? sph[k0 - 8] : k2_fir_phase_tab(xs0 + 8LL * (k0 - 1), rb, lds_fir, lds_fir + 72);
+		for (int k = k0; q < q0 + 8; ++k) {
+			const float pk = sph ? sph[k - 7] : k2_fir_phase_tab(xs0 + 8LL * k, rb, lds_fir, lds_fir + 72);
+			const int idx = k2_grey_index(pk, pprev, df);
+			pprev = pk;
+			for (int i = q - 3 * k; i < 3 && q < q0 + 8; ++i, ++q) {
+				const unsigned r = soft_rel(idx, i, grey);
+				rel = r < rel ? r : rel;
+			}
+		}
+		int row, col;
+		burst_scatter(g, b, &row, &col);
+		out->rel[row][col] = (uint8_t)rel;
+	}
+}
+
 template <int NT> struct MachSharedT {
 	float pbuf[VDL2_NPH + NT];	/* phases: [0,68) = history ring */
 	float errs[NT + 2];		/* errs[t+2] = err of eval t; [0],[1] = p2err, perr */
@@ -282,6 +333,7 @@ struct MachCtx {
 	const uint8_t *pn;
 	vdl2gpu_burst_t *recs;	/* sink: output ring, payload decoded at once (K2c serial stretches) ... */
 	vdl2gpu_level_t *levels;	/* ... with its level records (VDL2GPU_F_LEVELS), or nullptr */
+	vdl2gpu_soft_t *soft;	/* ... and its reliability maps (VDL2GPU_F_SOFT_RS), or nullptr */
 	BurstDesc *desc;	/* ... or descriptor pool, payload decoded by K2d if selected (K2b, K2c) */
 	unsigned *sel, *nsel;	/* K2c: descriptors made by its serial stretches are on the real chain */
 	unsigned dyn_base;	/* first dynamic descriptor slot */
@@ -689,6 +741,10 @@ template <int NT, bool XL> __device__ __forceinline__ long long mach_commit_trig
 			burst_payload<NT>(cx.recs + slot, x0, cx.pn, nstar, clk0, df, nbrow, nlbyte, cx.stream, cx.cfg, nullptr, 1, 0, nullptr, nullptr, sh.smf);
 		if (!XL && !cx.desc && slot != 0xffffffffu && cx.levels && threadIdx.x < 64)
 			burst_payload_levels(cx.levels + slot, x0, nstar, clk0, nbrow, nlbyte, sh.smf, cx.dec_base);
+		if (!XL && !cx.desc && slot != 0xffffffffu && cx.soft) {	/* (block-uniform) */
+			__syncthreads();
+			burst_payload_soft<NT>(cx.soft + slot, x0, nstar, clk0, df, nbrow, nlbyte, nullptr, sh.smf, cx.grey);
+		}
 		if (slot == 0xffffffffu)
 			out.badslot = 1;
 		out.nslots++;
@@ -807,6 +863,7 @@ __device__ __forceinline__ void mach_ctx(MachCtx &cx, const K2Params &p, int s, 
 	if (to_stage) {
 		cx.recs = nullptr;
 		cx.levels = nullptr;
+		cx.soft = nullptr;
 		cx.dyn_base = (unsigned)p.nstreams * VDL2_CS * VDL2_CAND_CAP * VDL2_CL_MAXB;
 		cx.desc = p.stage;
 		cx.rec_count = p.ctl + CTL_STAGE;
@@ -815,6 +872,7 @@ __device__ __forceinline__ void mach_ctx(MachCtx &cx, const K2Params &p, int s, 
 	} else {
 		cx.recs = p.recs;
 		cx.levels = p.levels;
+		cx.soft = p.soft;
 		cx.dyn_base = 0;
 		cx.desc = nullptr;
 		cx.rec_count = p.outc;

@@ -1277,7 +1277,9 @@ void k2f_commit(K2Params p)
 /* LEV (VDL2GPU_F_LEVELS): behind every burst its first wavefront measures the levels (burst_payload_levels) -- a kernel of its own,
  * k2d_payload_lev, with the registers it needs (four wavefronts): k2d_payload sits at the edge of its five and spilled with the pass
  * inlined; it carries none of it */
-template <bool LEV> __device__ __forceinline__ void k2d_run(const K2Params &p)
+/* SOFT (VDL2GPU_F_SOFT_RS): behind every burst all its lanes write the reliability map from the phases still in sph
+ * (burst_payload_soft) -- k2d_payload_soft, and k2d_payload_lev_soft with both flags */
+template <bool LEV, bool SOFT> __device__ __forceinline__ void k2d_run(const K2Params &p)
 {
 	__shared__ unsigned s_slot;
 	__shared__ float sph[VDL2_MAXSYM];
@@ -1368,6 +1370,10 @@ template <bool LEV> __device__ __forceinline__ void k2d_run(const K2Params &p)
 			burst_payload<K2D_NT, true>(p.recs + slot, x0, p.pn, d.nstar, d.clk0, d.df, d.nbrow, d.nlbyte, s, p.cfg[d.sc], sph, p.sel_mode == 0 ? 0 : 1, d.sc, s_tabs, p.pn8);
 			if (LEV && threadIdx.x < 64)
 				burst_payload_levels(p.levels + slot, x0, d.nstar, d.clk0, d.nbrow, d.nlbyte, s_tabs, p.dec_base);
+			if (SOFT) {
+				__syncthreads();
+				burst_payload_soft<K2D_NT>(p.soft + slot, x0, d.nstar, d.clk0, d.df, d.nbrow, d.nlbyte, sph, s_tabs, s_tabs + 72 + VDL2_ATAN_ROWS * VDL2_ATAN_STRIDE);
+			}
 		}
 		__syncthreads();
 	}
@@ -1376,13 +1382,25 @@ template <bool LEV> __device__ __forceinline__ void k2d_run(const K2Params &p)
 __global__ __launch_bounds__(K2D_NT) __attribute__((amdgpu_waves_per_eu(K2D_WAVES, 8)))
 void k2d_payload(K2Params p)
 {
-	k2d_run<false>(p);
+	k2d_run<false, false>(p);
 }
 
 __global__ __launch_bounds__(K2D_NT) __attribute__((amdgpu_waves_per_eu(4, 8)))
 void k2d_payload_lev(K2Params p)
 {
-	k2d_run<true>(p);
+	k2d_run<true, false>(p);
+}
+
+__global__ __launch_bounds__(K2D_NT) __attribute__((amdgpu_waves_per_eu(4, 8)))
+void k2d_payload_soft(K2Params p)
+{
+	k2d_run<false, true>(p);
+}
+
+__global__ __launch_bounds__(K2D_NT) __attribute__((amdgpu_waves_per_eu(4, 8)))
+void k2d_payload_lev_soft(K2Params p)
+{
+	k2d_run<true, true>(p);
 }
 
 #endif

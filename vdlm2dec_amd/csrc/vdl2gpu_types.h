@@ -183,6 +183,7 @@ struct K2Params {
 	unsigned stage_cap;
 	vdl2gpu_burst_t *recs;	/* output ring of this push */
 	vdl2gpu_level_t *levels;	/* VDL2GPU_F_LEVELS: one level record per record slot of `recs`, else nullptr (nothing is measured) */
+	vdl2gpu_soft_t *soft;	/* VDL2GPU_F_SOFT_RS: one reliability map per record slot of `recs`, else nullptr */
 	unsigned *outc;		/* [0] = records written, [1] = records dropped (ring full) */
 	unsigned *outc_total_redo;	/* running count of serial redos (host adapts the number of repair rounds) */
 	unsigned *fmask;	/* [16] bit per (stream, channel slot) that a repair round re-resolved or K2f redid serially in this push */

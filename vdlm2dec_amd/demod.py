@@ -62,6 +62,7 @@ class Burst:
     end_sample: int
     data: bytes            # 8 rows x 255 bytes, row-major
     level: Optional[Level] = None   # Receiver(levels=True) only; not part of key()
+    soft: Optional[np.ndarray] = None   # Receiver(soft_rs=True) only: uint8 (8, 255) byte reliabilities; not part of key()
 
     def key(self):
         return (self.stream, self.chn, self.nbrow, self.nlbyte, self.data)
@@ -77,7 +78,7 @@ class Receiver:
                  fmt: str = "cu8", max_push: int = 1 << 22, device: int = 0, sdrclk: int = 0,
                  max_bursts: int = 0, keep_dec: bool = False, serial: bool = False, full_scan: bool = False,
                  frames: bool = False, rtl_quirk: bool = False, flags: int = 0, testhooks: bool = False,
-                 levels: bool = False):
+                 levels: bool = False, soft_rs: bool = False):
         # testhooks: load libvdl2gpu_test.so, the build that honours F_TEST_NOREGION / VDL2GPU_PRIM_DROP / VDL2GPU_SPLIT_SAMPLES
         self.L = _lib.load(testhooks=testhooks or bool(flags & _lib.F_TEST_NOREGION))
         if channels and isinstance(channels[0], ThreadParam):
@@ -104,9 +105,10 @@ class Receiver:
         cfg.max_push = max_push
         cfg.device = device
         cfg.max_bursts = max_bursts
-        cfg.flags = (_lib.F_KEEP_DEC if keep_dec else 0) | (_lib.F_SERIAL if serial else 0) | (_lib.F_FULLSCAN if full_scan else 0) | (_lib.F_FRAMES if frames else 0) | (_lib.F_RTL_QUIRK if rtl_quirk else 0) | (_lib.F_LEVELS if levels else 0) | flags
+        cfg.flags = (_lib.F_KEEP_DEC if keep_dec else 0) | (_lib.F_SERIAL if serial else 0) | (_lib.F_FULLSCAN if full_scan else 0) | (_lib.F_FRAMES if frames else 0) | (_lib.F_RTL_QUIRK if rtl_quirk else 0) | (_lib.F_LEVELS if levels else 0) | (_lib.F_SOFT_RS if soft_rs else 0) | flags
         self.max_push = max_push
         self.levels = bool(cfg.flags & _lib.F_LEVELS)
+        self.soft_rs = bool(cfg.flags & _lib.F_SOFT_RS)
         self.h = C.c_void_p()
         rc = self.L.vdl2gpu_create(C.byref(cfg), C.byref(self.h))
         if rc != 0:
@@ -161,8 +163,12 @@ class Receiver:
         out: List[Burst] = []
         buf = (_lib.BurstT * max_bursts)()
         lv = (_lib.LevelT * max_bursts)() if self.levels else None
+        sv = (_lib.SoftT * max_bursts)() if self.soft_rs else None
         while True:
-            if lv is not None:
+            if sv is not None:
+                fn = self.L.vdl2gpu_poll_soft_ready if ready else self.L.vdl2gpu_poll_soft
+                n = self._check(fn(self.h, buf, lv, sv, max_bursts))
+            elif lv is not None:
                 fn = self.L.vdl2gpu_poll_levels_ready if ready else self.L.vdl2gpu_poll_levels
                 n = self._check(fn(self.h, buf, lv, max_bursts))
             else:
@@ -171,7 +177,8 @@ class Receiver:
             for i in range(n):
                 b = buf[i]
                 out.append(Burst(b.stream, b.chn, b.Fr, b.nbrow, b.nlbyte, b.df, b.ppm, b.trig_dec, b.end_dec,
-                                 b.trig_sample, b.end_sample, bytes(b.data), Level.from_c(lv[i]) if lv is not None else None))
+                                 b.trig_sample, b.end_sample, bytes(b.data), Level.from_c(lv[i]) if lv is not None else None,
+                                 np.frombuffer(bytes(sv[i].rel), np.uint8).reshape(8, 255).copy() if sv is not None else None))
             if n < max_bursts:
                 return out
 
@@ -187,6 +194,11 @@ class Receiver:
         """vdl2gpu_poll_levels(_ready) into caller-owned (lib.BurstT * n) / (lib.LevelT * n) arrays; lv may be None."""
         fn = self.L.vdl2gpu_poll_levels_ready if ready else self.L.vdl2gpu_poll_levels
         return self._check(fn(self.h, buf, lv, max_bursts))
+
+    def poll_soft_raw(self, buf, lv, sv, max_bursts: int, ready: bool = False) -> int:
+        """vdl2gpu_poll_soft(_ready) into caller-owned (lib.BurstT / lib.LevelT / lib.SoftT * n) arrays; lv and sv may be None."""
+        fn = self.L.vdl2gpu_poll_soft_ready if ready else self.L.vdl2gpu_poll_soft
+        return self._check(fn(self.h, buf, lv, sv, max_bursts))
 
     def poll_ready_raw(self, buf, max_bursts: int) -> int:
         """vdl2gpu_poll_ready: bursts of pushes that have already finished; never waits."""
@@ -212,9 +224,11 @@ class Receiver:
         return out
 
     # ------------------------------------------------------------------ block path
-    def decode_blocks(self, blocks: Sequence, max_frames: int = 0) -> List[Tuple[int, bytes]]:
+    def decode_blocks(self, blocks: Sequence, max_frames: int = 0, soft=None) -> List[Tuple[int, bytes]]:
         """blk_thread for a batch (vdlm2.c:84-161): (index of the block, hdata) of every frame the
-        reference would pass to out().  ``blocks``: Burst objects or (nbrow, nlbyte, data) tuples."""
+        reference would pass to out().  ``blocks``: Burst objects or (nbrow, nlbyte, data) tuples.
+        ``soft``: one (8, 255) uint8 reliability map per block (Burst.soft): the soft row rule of include/vdl2gpu.h
+        (vdl2gpu_decode_blocks_soft); None: the reference's block path."""
         n = len(blocks)
         if n == 0:
             return []
@@ -228,7 +242,16 @@ class Receiver:
         cap = max_frames or 4 * n
         out = (_lib.FrameT * cap)()
         dropped = C.c_int(0)
-        nf = self._check(self.L.vdl2gpu_decode_blocks(self.h, arr, n, out, cap, C.byref(dropped)))
+        if soft is None:
+            nf = self._check(self.L.vdl2gpu_decode_blocks(self.h, arr, n, out, cap, C.byref(dropped)))
+        else:
+            if len(soft) != n:
+                raise ValueError("one reliability map per block")
+            sarr = (_lib.SoftT * n)()
+            for i, m in enumerate(soft):
+                m = np.ascontiguousarray(m, np.uint8).reshape(8, 255)
+                C.memmove(C.addressof(sarr[i].rel), m.ctypes.data, 8 * 255)
+            nf = self._check(self.L.vdl2gpu_decode_blocks_soft(self.h, arr, sarr, n, out, cap, C.byref(dropped)))
         if dropped.value:
             raise _lib.Vdl2GpuError(f"{dropped.value} frames dropped: raise max_frames")
         return [(out[i].block, bytes(out[i].data[:out[i].len])) for i in range(nf)]

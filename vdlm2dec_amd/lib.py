@@ -24,13 +24,14 @@ F_FRAMES = 16
 F_RTL_QUIRK = 32
 F_DEBUG_HEADS = 64
 F_LEVELS = 128
+F_SOFT_RS = 256
 
 # every symbol include/vdl2gpu.h declares
 EXPORTS = (
     "vdl2gpu_abi_version", "vdl2gpu_create", "vdl2gpu_destroy", "vdl2gpu_push", "vdl2gpu_sync",
     "vdl2gpu_ring_init", "vdl2gpu_ring_acquire", "vdl2gpu_ring_commit",
-    "vdl2gpu_poll", "vdl2gpu_poll_ready", "vdl2gpu_poll_levels", "vdl2gpu_poll_levels_ready", "vdl2gpu_pending", "vdl2gpu_inflight", "vdl2gpu_get_stats", "vdl2gpu_get_timing", "vdl2gpu_get_host_profile", "vdl2gpu_last_error",
-    "vdl2gpu_strerror", "vdl2gpu_burst_to_msgblk", "vdl2gpu_decode_blocks", "vdl2gpu_poll_frames", "vdl2gpu_poll_frames_ready", "reversebits", "vdl2gpu_lo_table", "vdl2gpu_plan",
+    "vdl2gpu_poll", "vdl2gpu_poll_ready", "vdl2gpu_poll_levels", "vdl2gpu_poll_levels_ready", "vdl2gpu_poll_soft", "vdl2gpu_poll_soft_ready", "vdl2gpu_pending", "vdl2gpu_inflight", "vdl2gpu_get_stats", "vdl2gpu_get_timing", "vdl2gpu_get_host_profile", "vdl2gpu_last_error",
+    "vdl2gpu_strerror", "vdl2gpu_burst_to_msgblk", "vdl2gpu_decode_blocks", "vdl2gpu_decode_blocks_soft", "vdl2gpu_poll_frames", "vdl2gpu_poll_frames_ready", "reversebits", "vdl2gpu_lo_table", "vdl2gpu_plan",
     "vdl2gpu_choose_fc_rtl", "vdl2gpu_choose_fc_air",
     "vdl2gpu_debug_dec", "vdl2gpu_debug_lo", "vdl2gpu_debug_atan2f", "vdl2gpu_debug_counters", "vdl2gpu_debug_cands", "vdl2gpu_debug_clheads", "vdl2gpu_debug_fail", "vdl2gpu_debug_segs", "vdl2gpu_debug_heads",
 )
@@ -59,6 +60,11 @@ class LevelT(C.Structure):
     _fields_ = [("sig_dbfs", C.c_float), ("noise_dbfs", C.c_float), ("sig_power", C.c_float), ("noise_power", C.c_float),
                 ("sym_first_dec", C.c_int64), ("nsym", C.c_int32), ("subphase", C.c_int32), ("noise_blocks", C.c_int32),
                 ("reserved", C.c_int32)]
+
+
+class SoftT(C.Structure):
+    """vdl2gpu_soft_t (VDL2GPU_F_SOFT_RS): 2048 bytes, the reliability of every payload byte (include/vdl2gpu.h)."""
+    _fields_ = [("rel", (C.c_uint8 * 255) * 8), ("reserved", C.c_uint8 * 8)]
 
 
 class FrameT(C.Structure):
@@ -136,6 +142,10 @@ def load(testhooks: bool = False):
     L.vdl2gpu_poll_levels_ready.restype = C.c_int
     L.vdl2gpu_poll_levels_ready.argtypes = [C.c_void_p, C.POINTER(BurstT), C.POINTER(LevelT), C.c_int]
     L.vdl2gpu_pending.argtypes = [C.c_void_p]
+    L.vdl2gpu_poll_soft.restype = C.c_int
+    L.vdl2gpu_poll_soft.argtypes = [C.c_void_p, C.POINTER(BurstT), C.POINTER(LevelT), C.POINTER(SoftT), C.c_int]
+    L.vdl2gpu_poll_soft_ready.restype = C.c_int
+    L.vdl2gpu_poll_soft_ready.argtypes = [C.c_void_p, C.POINTER(BurstT), C.POINTER(LevelT), C.POINTER(SoftT), C.c_int]
     L.vdl2gpu_get_stats.restype = C.c_int
     L.vdl2gpu_get_stats.argtypes = [C.c_void_p, C.POINTER(StatsT)]
     L.vdl2gpu_get_timing.restype = C.c_int
@@ -151,6 +161,9 @@ def load(testhooks: bool = False):
     L.vdl2gpu_decode_blocks.restype = C.c_int
     L.vdl2gpu_decode_blocks.argtypes = [C.c_void_p, C.POINTER(BurstT), C.c_int, C.POINTER(FrameT), C.c_int,
                                         C.POINTER(C.c_int)]
+    L.vdl2gpu_decode_blocks_soft.restype = C.c_int
+    L.vdl2gpu_decode_blocks_soft.argtypes = [C.c_void_p, C.POINTER(BurstT), C.POINTER(SoftT), C.c_int, C.POINTER(FrameT), C.c_int,
+                                             C.POINTER(C.c_int)]
     L.vdl2gpu_poll_frames.restype = C.c_int
     L.vdl2gpu_poll_frames.argtypes = [C.c_void_p, C.POINTER(FrameT), C.c_int]
     L.vdl2gpu_poll_frames_ready.restype = C.c_int
