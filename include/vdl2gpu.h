@@ -78,8 +78,12 @@ typedef struct {
 
 typedef struct {
 	uint32_t struct_size;	/* sizeof(vdl2gpu_config_t), for ABI growth */
-	uint32_t sdrinrate;	/* SDRINRATE: 2000000 (rtl.c:36), 5/6 MS/s (air.c:134), 10 MS/s */
-	uint32_t sdrclk;	/* SDRCLK; 0 = sdrinrate/4000 (rtl.c:37, air.c:138) */
+	uint32_t sdrinrate;	/* SDRINRATE: any multiple of 25 kHz from 100 kHz on (2 MS/s rtl.c:36, 5/6 MS/s air.c:134, 10 MS/s ...),
+				 * with sdrclk such that the general channeliser's LDS, ((L + maxwin) * 8 + 32 * maxwin) * 8 bytes
+				 * with L = sdrinrate / 25000 and maxwin = (sdrclk + 20) / 21, stays within 160 KiB (gfx950's limit
+				 * per workgroup).  At the default sdrclk that is up to 25.7 MS/s; at 2 MS/s, sdrclk up to 10416.
+				 * Anything else is VDL2GPU_EINVAL from vdl2gpu_create, before any device call. */
+	uint32_t sdrclk;	/* SDRCLK, in (21, 1000000] and within the LDS bound above; 0 = sdrinrate/4000 (rtl.c:37, air.c:138) */
 	int32_t fmt;		/* VDL2GPU_FMT_* */
 	int32_t nbch;		/* channels per wideband stream, 1..8 */
 	int32_t nstreams;	/* independent wideband streams decoded side by side (>=1) */

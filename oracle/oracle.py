@@ -49,6 +49,8 @@ def lib():
         L = C.CDLL(_LIB_PATH)
         L.vo_create.restype = C.c_void_p
         L.vo_create.argtypes = [C.c_uint, C.c_int, C.c_int]
+        L.vo_create_clk.restype = C.c_void_p
+        L.vo_create_clk.argtypes = [C.c_uint, C.c_int, C.c_int, C.c_uint]
         L.vo_destroy.argtypes = [C.c_void_p]
         L.vo_enable_taps.argtypes = [C.c_void_p, C.c_int, C.c_int]
         L.vo_feed.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
@@ -118,9 +120,10 @@ def frames_of_block(nbrow: int, nlbyte: int, data: bytes) -> List[bytes]:
 
 
 class OracleChannel:
-    def __init__(self, rate: int, fo: int, fr: int, chn: int = 0, tap_dec: bool = False, tap_phase: bool = False):
+    def __init__(self, rate: int, fo: int, fr: int, chn: int = 0, tap_dec: bool = False, tap_phase: bool = False,
+                 sdrclk: int = 0):
         self.L = lib()
-        self.h = self.L.vo_create(rate, fo, fr)
+        self.h = self.L.vo_create_clk(rate, fo, fr, sdrclk)     # sdrclk: the SDRCLK global (0 = rate / 4000)
         self.chn = chn
         if tap_dec or tap_phase:
             self.L.vo_enable_taps(self.h, int(tap_dec), int(tap_phase))
@@ -177,11 +180,11 @@ class OracleChannel:
 
 
 def run_oracle(raw: np.ndarray, fmt: str, rate: int, fos: Sequence[int], fc: int = 136975000,
-               chunk: Optional[int] = None) -> List[Block]:
-    """All channels of one wideband stream through the CPU restatement."""
+               chunk: Optional[int] = None, sdrclk: int = 0) -> List[Block]:
+    """All channels of one wideband stream through the CPU restatement (sdrclk: SDRCLK, 0 = rate / 4000)."""
     out: List[Block] = []
     for c, fo in enumerate(fos):
-        ch = OracleChannel(rate, fo, fc + fo, chn=c)
+        ch = OracleChannel(rate, fo, fc + fo, chn=c, sdrclk=sdrclk)
         if chunk:
             per = PER_SAMPLE[fmt]
             for s in range(0, raw.size // per, chunk):
@@ -207,11 +210,11 @@ def build_ref() -> bool:
 
 
 def run_ref(path: str, fmt: str, rate: int, fo: int, fr: int, out_path: str, quirk: int = 0,
-            tap_path: str = "", ofast: bool = False):
+            tap_path: str = "", ofast: bool = False, sdrclk: int = 0):
     """One channel through the REAL reference (oracle/_ref/ref_rtl or ref_air; ofast: the build with the
-    reference's own -Ofast -march=native, CMakeLists.txt:4)."""
+    reference's own -Ofast -march=native, CMakeLists.txt:4; sdrclk: its SDRCLK global, 0 = rate / 4000)."""
     exe = os.path.join(REF_DIR, ("ref_air" if fmt == "f32" else "ref_rtl") + ("_ofast" if ofast else ""))
-    subprocess.check_call([exe, path, fmt, str(rate), str(fo), str(fr), out_path, str(quirk), tap_path])
+    subprocess.check_call([exe, path, fmt, str(rate), str(fo), str(fr), out_path, str(quirk), tap_path, str(sdrclk)])
     blocks, frames = [], []
     with open(out_path) as f:
         for line in f:

@@ -25,7 +25,8 @@
  *   atan2f / roundf     defined here, forward to libm via dlsym(RTLD_NEXT)
  *   out()               every CRC-clean frame (vdlm2.c:61)
  *
- * usage: ref_xxx <iqfile> <fmt:cu8|cs16|cf32|f32> <SDRINRATE> <Fo> <Fr> <outfile> [quirk] [tapfile]
+ * usage: ref_xxx <iqfile> <fmt:cu8|cs16|cf32|f32> <SDRINRATE> <Fo> <Fr> <outfile> [quirk] [tapfile] [SDRCLK]
+ *   (SDRCLK: the global d8psk.c reads; absent or 0 = SDRINRATE / 4000 as air.c:138 sets it)
  */
 #define _GNU_SOURCE
 #include <stdio.h>
@@ -162,13 +163,15 @@ int main(int argc, char **argv)
 {
 	if (argc < 7) {
 		fprintf(stderr,
-			"usage: %s iqfile fmt rate Fo Fr outfile [quirk] [tapfile]\n",
+			"usage: %s iqfile fmt rate Fo Fr outfile [quirk] [tapfile] [sdrclk]\n",
 			argv[0]);
 		return 2;
 	}
 	const char *fmt = argv[2];
 	SDRINRATE = (unsigned)atoi(argv[3]);
 	SDRCLK = SDRINRATE / 4000;	/* air.c:138; 500 at 2 MS/s as rtl.c:37 */
+	if (argc > 9 && atoi(argv[9]) > 0)
+		SDRCLK = (unsigned)atoi(argv[9]);	/* the global as a caller of the decoder may set it */
 	int quirk = argc > 7 ? atoi(argv[7]) : 0;
 	FILE *f = fopen(argv[1], "rb");
 	if (!f) {

@@ -141,9 +141,14 @@ static void lo_table(vo_chan *c)
 
 vo_chan *vo_create(unsigned sdrinrate, int fo_hz, int fr_hz)
 {
+	return vo_create_clk(sdrinrate, fo_hz, fr_hz, 0);
+}
+
+vo_chan *vo_create_clk(unsigned sdrinrate, int fo_hz, int fr_hz, unsigned sdrclk)
+{
 	vo_chan *c = calloc(1, sizeof *c);	/* all-zero = canonical start state */
 	c->rate = sdrinrate;
-	c->sdrclk = sdrinrate / 4000;	/* rtl.c:37, air.c:138 */
+	c->sdrclk = sdrclk ? sdrclk : sdrinrate / 4000;	/* the SDRCLK global: rtl.c:37, air.c:138 (0 = that default) */
 	c->lo_len = (int)(sdrinrate / 25000);	/* STEPRATE vdlm2.h:33 */
 	c->fo = fo_hz;
 	c->fr = fr_hz;

@@ -51,6 +51,7 @@ typedef struct vo_chan vo_chan;
 enum { VO_FMT_CU8 = 0, VO_FMT_CS16 = 1, VO_FMT_CF32 = 2, VO_FMT_F32R = 3, VO_FMT_CU8_QUIRK = 4 };
 
 vo_chan *vo_create(unsigned sdrinrate, int fo_hz, int fr_hz);
+vo_chan *vo_create_clk(unsigned sdrinrate, int fo_hz, int fr_hz, unsigned sdrclk);	/* SDRCLK given (0 = sdrinrate / 4000) */
 void vo_destroy(vo_chan *c);
 /* keep every decimated sample / every WSYNC phase for diagnostics (P3 taps) */
 void vo_enable_taps(vo_chan *c, int dec_samples, int phases);

@@ -2,7 +2,7 @@
 
 Run in the build container (needs /root/reference and `make -C oracle ref`):
 
-    python tests/golden/make_golden.py
+    python tests/golden/make_golden.py [case ...]      (no case: all of them)
 
 For every case it writes
     <case>.npz   the raw IQ recording (data), compressed
@@ -42,13 +42,19 @@ CASES = {
     "short_cf32_2ms": (S.single_short(2_000_000, 100_000, seed=9, info_len=8, blocks=2), "cf32", 0),
     # BASELINE.json configs[2]: 8 channels @ 10 MS/s (SDRCLK 2500)
     "eight_cs16_10ms": (S.eight_channels(rate=10_000_000, seed=10, dur=0.05, info=(3, 9, 5, 12, 7, 4, 6, 8), fo=S.FO8_10MS), "cs16", 0),
+    # rates off the four above: 2.4 MS/s (SDRCLK 600, L 96); 2.025 MS/s (SDRCLK 506.25 truncated to 506, L 81: no whole
+    # period of the dump schedule in L inputs, so the general channeliser takes every push)
+    "regimes_cu8_2400k": (S.regimes(rate=2_400_000, seed=12, infos=(1, 3, 28, 31, 66, 70, 250), gap=0.001), "cu8", 0),
+    "eight_cs16_2025k": (S.eight_channels(rate=2_025_000, seed=13, dur=0.06, info=(4, 11, 6, 14, 3, 9, 7, 5)), "cs16", 0),
 }
 SHARE_IQ = {"regimes_cu8_2ms_quirk": "regimes_cu8_2ms"}
 
 
-def main():
+def main(names):
     assert O.build_ref(), "needs /root/reference"
     for name, (spec, fmt, quirk) in CASES.items():
+        if names and name not in names:
+            continue
         raw = synth.synth_stream(spec, fmt)
         if name not in SHARE_IQ:
             np.savez_compressed(os.path.join(HERE, name + ".npz"), raw=raw)
@@ -76,4 +82,4 @@ def main():
 
 
 if __name__ == "__main__":
-    main()
+    main(sys.argv[1:])

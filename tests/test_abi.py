@@ -70,7 +70,7 @@ def test_burst_to_msgblk_layout(built):
     assert L.vdl2gpu_burst_to_msgblk(C.byref(b), blk, 100) == -1
 
 
-@pytest.mark.parametrize("rate", [2_000_000, 5_000_000, 6_000_000, 10_000_000])
+@pytest.mark.parametrize("rate", [2_000_000, 5_000_000, 6_000_000, 10_000_000, 100_000, 2_025_000, 2_400_000, 2_500_000, 25_700_000])
 def test_lo_table_equals_reference_formula(built, oracle, rate):
     """Host LO table (sincosf) == the oracle's cexpf table (d8psk.c:353-357), bit for bit."""
     from vdlm2dec_amd.demod import lo_table
@@ -216,3 +216,39 @@ def test_create_rejects_planes_of_4_gib(built, sdrclk):
         assert create(mp) == -1, mp                                         # VDL2GPU_EINVAL
     if not torch.cuda.is_available():
         assert create(lo - 1) == -5                                         # VDL2GPU_ENODEV: past the check, at the device
+
+
+def _k1_lds(rate, sdrclk):
+    """dynamic LDS of the general channeliser k1_channelise (vdl2gpu.hip: k1_smem_bytes)"""
+    L, maxwin = rate // 25000, (sdrclk + 20) // 21
+    return ((L + maxwin) * 8 + 32 * maxwin) * 8
+
+
+@pytest.mark.parametrize("rate,sdrclk,ok", [
+    (25_700_000, 0, True), (25_725_000, 0, False),          # the default SDRCLK: the ceiling rate include/vdl2gpu.h states
+    (2_000_000, 10416, True), (2_000_000, 10417, False),    # 2 MS/s with a custom SDRCLK: 10416 takes exactly 160 KiB
+    (100_000, 10731, True), (100_000, 10732, False),
+    (2_000_000, 1_000_000, False), (4_000_000_000, 0, False),
+])
+def test_create_rejects_what_the_channeliser_cannot_launch(built, rate, sdrclk, ok):
+    """k1_channelise holds the LO table and a pass's input windows in dynamic LDS, which grows with the rate and SDRCLK; a
+    gfx950 workgroup may have 160 KiB.  vdl2gpu_create refuses a pair above that before any device call (VDL2GPU_EINVAL on any
+    machine) instead of failing at the first push.  A pair at or below it passes the check: a handle on a GPU, ENODEV without one."""
+    import torch
+    from vdlm2dec_amd import lib
+    clk = sdrclk or rate // 4000
+    assert (_k1_lds(rate, clk) <= 160 * 1024) == ok
+    if ok and rate == 2_000_000:
+        assert _k1_lds(rate, clk) == 160 * 1024
+    L = lib.load()
+    chan = (lib.ChanT * 1)(lib.ChanT(0, 136_975_000, 0))
+    cfg = lib.ConfigT(struct_size=C.sizeof(lib.ConfigT), sdrinrate=rate, sdrclk=sdrclk, fmt=1, nbch=1, nstreams=1,
+                      chan=chan, max_push=1 << 16)
+    h = C.c_void_p()
+    rc = L.vdl2gpu_create(C.byref(cfg), C.byref(h))
+    if rc == 0:
+        L.vdl2gpu_destroy(h)
+    if not ok:
+        assert rc == -1                                                     # VDL2GPU_EINVAL
+    else:
+        assert rc == (0 if torch.cuda.is_available() else -5)               # a handle, or VDL2GPU_ENODEV: past the check

@@ -100,7 +100,10 @@ def test_decimation_schedule_closed_form(built):
     """vdl2gpu_plan() against a brute-force run of the reference's clock loop (d8psk.c:369-381)."""
     from vdlm2dec_amd.demod import plan
     rng = np.random.default_rng(3)
-    for sdrclk, L in ((500, 80), (1250, 200), (1500, 240), (2500, 400)):
+    # the default SDRCLK at 2 / 5 / 6 / 10 MS/s; custom SDRCLK down to 22 (the smallest accepted) at 2 MS/s; 100 kS/s (L = 4),
+    # 2.025 MS/s (506.25 truncated), 2.4 MS/s; the LDS ceiling 25.7 MS/s
+    for sdrclk, L in ((500, 80), (1250, 200), (1500, 240), (2500, 400), (22, 80), (25, 4), (400, 80), (506, 81), (510, 80),
+                      (600, 96), (6425, 1028)):
         clk = nf = no = 0
         total = 0
         for _ in range(40):

@@ -10,14 +10,15 @@ import scenarios as S
 from vdlm2dec_amd import synth
 
 
-def _compare(O, spec, fmt, tmp_path, quirk=0):
+def _compare(O, spec, fmt, tmp_path, quirk=0, sdrclk=0):
     raw = synth.synth_stream(spec, fmt)
     p = str(tmp_path / "iq.raw")
     raw.tofile(p)
     total_blocks = 0
     for c, fo in enumerate(spec.fo):
-        rb, rf, taps = O.run_ref(p, fmt, spec.rate, fo, S.FC + fo, str(tmp_path / "o.txt"), quirk, str(tmp_path / "t.bin"))
-        ch = O.OracleChannel(spec.rate, fo, S.FC + fo, chn=c, tap_phase=True)
+        rb, rf, taps = O.run_ref(p, fmt, spec.rate, fo, S.FC + fo, str(tmp_path / "o.txt"), quirk, str(tmp_path / "t.bin"),
+                                 sdrclk=sdrclk)
+        ch = O.OracleChannel(spec.rate, fo, S.FC + fo, chn=c, tap_phase=True, sdrclk=sdrclk)
         ch.feed(raw, fmt + ("_quirk" if quirk else ""))
         ob = ch.blocks()
         assert len(ob) == len(rb)
@@ -83,6 +84,27 @@ def test_weak_noisy(O, tmp_path):
     # low SNR: sync decisions near threshold, header Viterbi actually corrects, false triggers possible
     spec = S.regimes(seed=106, infos=(20, 50, 90, 30, 10, 77), noise=6.0)
     _compare(O, spec, "cu8", tmp_path)
+
+
+def test_rate_2025k_cs16_sdrclk_truncates(O, tmp_path):
+    """2.025 MS/s: SDRCLK = 2025000 / 4000 = 506.25 truncates to 506, and 4 * 506 is no whole number of L = 81 inputs."""
+    assert _compare(O, S.regimes(rate=2_025_000, seed=121, infos=(3, 28, 60, 200, 497)), "cs16", tmp_path) >= 4
+
+
+def test_rate_2400k_cu8(O, tmp_path):
+    assert _compare(O, S.regimes(rate=2_400_000, seed=122, infos=(2, 31, 66, 250)), "cu8", tmp_path) >= 3
+
+
+def test_rate_100k_cs16_one_channel_at_the_centre(O, tmp_path):
+    """the smallest accepted rate: L = 4 LO values, SDRCLK 25, windows of at most 2 inputs"""
+    assert _compare(O, S.single_short(100_000, 0, seed=123, info_len=20, blocks=3), "cs16", tmp_path) == 1
+
+
+@pytest.mark.parametrize("sdrclk", [400, 510])
+def test_custom_sdrclk_at_2m(O, tmp_path, sdrclk):
+    """SDRCLK given apart from the rate (the global a caller of the decoder may set): a decimated rate of 105 / 82.35 kS/s, so
+    the bursts mostly fail; the phases, triggers and whatever is handed over must still be the reference's."""
+    _compare(O, S.regimes(seed=124 + sdrclk, infos=(5, 40, 90)), "cs16", tmp_path, sdrclk=sdrclk)
 
 
 def test_rs_decoder_against_reference_rs(O):

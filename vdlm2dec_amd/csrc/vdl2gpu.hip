@@ -714,6 +714,16 @@ static long long plane_frames(uint64_t max_push, unsigned sdrclk)
  * ones.  The limit is part of the ABI (include/vdl2gpu.h, max_push). */
 #define VDL2_PLANES_MAX (1ull << 32)
 
+/* k1_channelise keeps the LO table ((L + maxwin) x 8 channels) and a pass's input windows (32 outputs x maxwin) in dynamic LDS; both
+ * grow with SDRINRATE and SDRCLK.  The library is built for gfx950 only, where a workgroup may have 160 KiB
+ * (hipDeviceAttributeMaxSharedMemoryPerBlock on the MI355X); the kernel has no static LDS.  vdl2gpu_create refuses what it could
+ * not launch (include/vdl2gpu.h, sdrinrate). */
+#define VDL2_K1_LDS_MAX (160u * 1024u)
+static size_t k1_smem_bytes(uint64_t L, uint64_t maxwin)
+{
+	return (size_t)(((L + maxwin) * VDL2_CS + (uint64_t)K1_OPB * maxwin) * sizeof(float2));
+}
+
 static int create_impl(vdl2gpu_t *h)
 {
 	const vdl2gpu_config_t &cfg = h->cfg;
@@ -1044,6 +1054,8 @@ extern "C" int vdl2gpu_create(const vdl2gpu_config_t *cfg, vdl2gpu_t **out)
 	const unsigned sdrclk = cfg->sdrclk ? cfg->sdrclk : cfg->sdrinrate / 4000;
 	if (sdrclk <= 21 || sdrclk > 1000000)
 		return VDL2GPU_EINVAL;
+	if (k1_smem_bytes(cfg->sdrinrate / 25000, (sdrclk + 20) / 21) > VDL2_K1_LDS_MAX)
+		return VDL2GPU_EINVAL;	/* the general channeliser's LDS (above 25.7 MS/s at the default SDRCLK) */
 	const long long cap = plane_frames(cfg->max_push, sdrclk);
 	if (cap == 0 || (unsigned long long)cap * VDL2_CS * sizeof(float2) >= VDL2_PLANES_MAX)
 		return VDL2GPU_EINVAL;	/* a stream's planes must stay below 4 GiB (k1_fast's 32-bit offsets) */
@@ -1709,7 +1721,7 @@ static int push_impl(vdl2gpu_t *h, const void *iq, size_t nsamples, size_t strea
 		HIPCHK(h, hipEventRecord(pt.e[0], ks));
 	{
 		const long long per_block = K1_OPB * K1_PASSES;
-		const size_t smem = ((size_t)(h->L + h->maxwin) * VDL2_CS + (size_t)K1_OPB * h->maxwin) * sizeof(float2);
+		const size_t smem = k1_smem_bytes((uint64_t)h->L, (uint64_t)h->maxwin);	/* <= VDL2_K1_LDS_MAX (vdl2gpu_create) */
 		auto generic = [&](long long jbeg, long long jend) {
 			if (jend < jbeg)
 				return;
