@@ -18,7 +18,8 @@
  *     ---------------------------------------  -----------------------------------
  *     rcv_thread() x nbch + Bar1/Bar2           vdl2gpu_create() + vdl2gpu_push()
  *     in_callback() cu8->float, rtl.c:285-292   fused into the channeliser kernel
- *     rx_callback() real f32,  air.c:206-208    VDL2GPU_FMT_F32R
+ *     rx_callback() real f32,  air.c:206-208    VDL2GPU_FMT_F32R (VDL2GPU_FMT_S16R: the same stream before
+ *                                               the vendor library widens it, see the formats below)
  *     thread_param_t            vdlm2.h:49-52   vdl2gpu_chan_t (same three ints)
  *     decodeVdlm2(ch)           vdlm2.c:189     vdl2gpu_poll() -> vdl2gpu_burst_t,
  *                                               vdl2gpu_burst_to_msgblk() fills the
@@ -64,8 +65,17 @@ enum {
 	VDL2GPU_FMT_CU8 = 0,	/* interleaved u8 I,Q; x = (float)b - 127.37f  (rtl.c:287-289) */
 	VDL2GPU_FMT_CS16 = 1,	/* interleaved s16 I,Q; x = (float)v              */
 	VDL2GPU_FMT_CF32 = 2,	/* interleaved f32 I,Q  (what Cbuff holds with WITH_RTL)     */
-	VDL2GPU_FMT_F32R = 3	/* real f32 (Cbuff with WITH_AIR, air.c:190)                 */
+	VDL2GPU_FMT_F32R = 3,	/* real f32 (Cbuff with WITH_AIR, air.c:190)                 */
+	/* Two formats receivers deliver natively that the reference's front ends never hand to Cbuff (announced by
+	 * VDL2GPU_HAVE_FMT_CS8_S16R, the ABI version is unchanged).  An integer converts to float without rounding, so a
+	 * handle fed one of them produces bit for bit what a CF32 / F32R handle produces from the same values -- at 2
+	 * bytes a sample over the bus instead of 8 / 4.  VDL2GPU_F_RTL_QUIRK is VDL2GPU_EINVAL with either. */
+	VDL2GPU_FMT_CS8 = 4,	/* interleaved s8 I,Q (HackRF, "cs8" recordings); x = (float)v, NO offset (the 127.37 is cu8's) */
+	VDL2GPU_FMT_S16R = 5	/* real s16 (libairspy's AIRSPY_SAMPLE_INT16_REAL, which air.c:123 has widened to
+				 * AIRSPY_SAMPLE_FLOAT32_REAL on the host); x = (float)v, imaginary part 0, mixed like
+				 * VDL2GPU_FMT_F32R: D += x * wf (d8psk.c:368 WITH_AIR) */
 };
+#define VDL2GPU_HAVE_FMT_CS8_S16R 1
 
 enum { VDL2GPU_MEM_HOST = 0, VDL2GPU_MEM_DEVICE = 1 };
 
@@ -153,11 +163,12 @@ typedef struct {
  *           |S|^2 (the mean of the two middle ones for an even count); noise_blocks = the number of valid blocks (0..8); with 0
  *           blocks noise_power and noise_dbfs are NaN.  The median tolerates the tail of a preceding burst in up to 3 of the 8
  *           blocks; on a saturated channel (bursts back to back) the value is an upper bound of the noise floor.
- *   scale:  K = (FS * sum_{j=0..16} mflt[4j])^2, FS = 128 (cu8), 32768 (cs16), 1 (cf32, f32r): the channeliser AVERAGES the
+ *   scale:  K = (FS * sum_{j=0..16} mflt[4j])^2, FS = 128 (cu8, cs8), 32768 (cs16, s16r), 1 (cf32, f32r): the channeliser AVERAGES the
  *           input samples of each 84 kS/s output (D /= nf, d8psk.c:378), so a full-scale complex tone at the channel centre
  *           leaves it at FS; sig_dbfs = 10 log10(sig_power / K), noise_dbfs likewise, and that tone reads about 0 dBFS.  White
  *           noise of sigma per component reads 10 log10(2 sigma^2 / M * sum_j mflt[4j]^2 / K), M = sdrinrate / 84000.  A real
- *           f32 (VDL2GPU_FMT_F32R) tone reads about 6 dB lower: the real stream's image half is not in the channel.
+ *           tone (VDL2GPU_FMT_F32R, and VDL2GPU_FMT_S16R against its FS of 32768) reads about 6 dB lower: the real stream's
+ *           image half is not in the channel.
  * The sums run in a fixed order over the symbol index (64 strided partial sums in ascending k, then a fixed pairwise tree; each
  * noise block: a fixed pairwise tree of its 32 values): a burst gets bit-identical levels whatever kernel, path or repair round
  * decoded it and however the stream was cut into pushes.  Levels need no extra input: the noise window lies inside the carried

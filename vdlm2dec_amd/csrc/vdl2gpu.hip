@@ -474,6 +474,8 @@ static size_t fmt_bytes(int fmt)
 	case VDL2GPU_FMT_CS16: return 4;
 	case VDL2GPU_FMT_CF32: return 8;
 	case VDL2GPU_FMT_F32R: return 4;
+	case VDL2GPU_FMT_CS8: return 2;
+	case VDL2GPU_FMT_S16R: return 2;
 	default: return 0;
 	}
 }
@@ -952,7 +954,8 @@ static int create_impl(vdl2gpu_t *h)
 		double g = 0.0;
 		for (int j = 0; j <= 16; ++j)
 			g += (double)mf[4 * j];
-		const double fs = cfg.fmt == VDL2GPU_FMT_CU8 ? 128.0 : (cfg.fmt == VDL2GPU_FMT_CS16 ? 32768.0 : 1.0);
+		const double fs = (cfg.fmt == VDL2GPU_FMT_CU8 || cfg.fmt == VDL2GPU_FMT_CS8) ? 128.0
+			: ((cfg.fmt == VDL2GPU_FMT_CS16 || cfg.fmt == VDL2GPU_FMT_S16R) ? 32768.0 : 1.0);
 		const double a = fs * g;
 		h->lev_k = a * a;
 	}
@@ -1734,6 +1737,8 @@ static int push_impl(vdl2gpu_t *h, const void *iq, size_t nsamples, size_t strea
 			case VDL2GPU_FMT_CU8: launch_k1<VDL2GPU_FMT_CU8>(q, grid, smem, ks); break;
 			case VDL2GPU_FMT_CS16: launch_k1<VDL2GPU_FMT_CS16>(q, grid, smem, ks); break;
 			case VDL2GPU_FMT_CF32: launch_k1<VDL2GPU_FMT_CF32>(q, grid, smem, ks); break;
+			case VDL2GPU_FMT_CS8: launch_k1<VDL2GPU_FMT_CS8>(q, grid, smem, ks); break;
+			case VDL2GPU_FMT_S16R: launch_k1<VDL2GPU_FMT_S16R>(q, grid, smem, ks); break;
 			default: launch_k1<VDL2GPU_FMT_F32R>(q, grid, smem, ks); break;
 			}
 		};
@@ -1822,6 +1827,8 @@ static int push_impl(vdl2gpu_t *h, const void *iq, size_t nsamples, size_t strea
 			case VDL2GPU_FMT_CU8: hipLaunchKernelGGL(k1_fast<VDL2GPU_FMT_CU8>, grid, dim3(K1F_THREADS), 0, ks, k1); break;
 			case VDL2GPU_FMT_CS16: hipLaunchKernelGGL(k1_fast<VDL2GPU_FMT_CS16>, grid, dim3(K1F_THREADS), 0, ks, k1); break;
 			case VDL2GPU_FMT_CF32: hipLaunchKernelGGL(k1_fast<VDL2GPU_FMT_CF32>, grid, dim3(K1F_THREADS), 0, ks, k1); break;
+			case VDL2GPU_FMT_CS8: hipLaunchKernelGGL(k1_fast<VDL2GPU_FMT_CS8>, grid, dim3(K1F_THREADS), 0, ks, k1); break;
+			case VDL2GPU_FMT_S16R: hipLaunchKernelGGL(k1_fast<VDL2GPU_FMT_S16R>, grid, dim3(K1F_THREADS), 0, ks, k1); break;
 			default: hipLaunchKernelGGL(k1_fast<VDL2GPU_FMT_F32R>, grid, dim3(K1F_THREADS), 0, ks, k1); break;
 			}
 			if (staged)
@@ -1892,6 +1899,8 @@ static int push_impl(vdl2gpu_t *h, const void *iq, size_t nsamples, size_t strea
 			case VDL2GPU_FMT_CU8: hipLaunchKernelGGL(k1_pp<VDL2GPU_FMT_CU8>, grid, dim3(K1P_THREADS), 0, ks, kp); break;
 			case VDL2GPU_FMT_CS16: hipLaunchKernelGGL(k1_pp<VDL2GPU_FMT_CS16>, grid, dim3(K1P_THREADS), 0, ks, kp); break;
 			case VDL2GPU_FMT_CF32: hipLaunchKernelGGL(k1_pp<VDL2GPU_FMT_CF32>, grid, dim3(K1P_THREADS), 0, ks, kp); break;
+			case VDL2GPU_FMT_CS8: hipLaunchKernelGGL(k1_pp<VDL2GPU_FMT_CS8>, grid, dim3(K1P_THREADS), 0, ks, kp); break;
+			case VDL2GPU_FMT_S16R: hipLaunchKernelGGL(k1_pp<VDL2GPU_FMT_S16R>, grid, dim3(K1P_THREADS), 0, ks, kp); break;
 			default: hipLaunchKernelGGL(k1_pp<VDL2GPU_FMT_F32R>, grid, dim3(K1P_THREADS), 0, ks, kp); break;
 			}
 			if (staged)

@@ -25,6 +25,9 @@ __device__ __forceinline__ long long k1_win_end(long long j, int sdrclk, int c0)
 	return ((j + 1) * (long long)sdrclk - c0 + 20) / 21 - 1;
 }
 
+/* real input (F32R, S16R): the sample is x + 0i and the mixer is D += x * wf (d8psk.c WITH_AIR), no cross terms */
+#define K1_REAL(FMT_) ((FMT_) == VDL2GPU_FMT_F32R || (FMT_) == VDL2GPU_FMT_S16R)
+
 template <int FMT> __device__ __forceinline__ float2 k1_load(const char *raw, long long i)
 {
 	if (FMT == VDL2GPU_FMT_CU8) {
@@ -35,6 +38,11 @@ template <int FMT> __device__ __forceinline__ float2 k1_load(const char *raw, lo
 		return make_float2((float)v.x, (float)v.y);
 	} else if (FMT == VDL2GPU_FMT_CF32) {
 		return reinterpret_cast<const float2 *>(raw)[i];
+	} else if (FMT == VDL2GPU_FMT_CS8) {
+		const char2 b = reinterpret_cast<const char2 *>(raw)[i];	/* signed: no offset (the 127.37 is cu8's) */
+		return make_float2((float)b.x, (float)b.y);
+	} else if (FMT == VDL2GPU_FMT_S16R) {
+		return make_float2((float)reinterpret_cast<const short *>(raw)[i], 0.0f);
 	} else {
 		return make_float2(reinterpret_cast<const float *>(raw)[i], 0.0f);
 	}
@@ -101,7 +109,7 @@ void k1_channelise(K1Params p)
 				dim = cy.y;
 				nf += p.nf0;
 			}
-			if (FMT == VDL2GPU_FMT_F32R) {
+			if (K1_REAL(FMT)) {
 				for (int t = 0; t < n; ++t) {
 					const float x = xp[t].x;
 					const float2 w = wp[t * VDL2_CS];
@@ -279,6 +287,8 @@ template <> struct K1Fmt<VDL2GPU_FMT_CU8> { enum { BYTES = 2, SPB = 8 }; };	/* S
 template <> struct K1Fmt<VDL2GPU_FMT_CS16> { enum { BYTES = 4, SPB = 4 }; };
 template <> struct K1Fmt<VDL2GPU_FMT_CF32> { enum { BYTES = 8, SPB = 2 }; };
 template <> struct K1Fmt<VDL2GPU_FMT_F32R> { enum { BYTES = 4, SPB = 4 }; };
+template <> struct K1Fmt<VDL2GPU_FMT_CS8> { enum { BYTES = 2, SPB = 8 }; };
+template <> struct K1Fmt<VDL2GPU_FMT_S16R> { enum { BYTES = 2, SPB = 8 }; };	/* eight reals to a piece */
 
 /* one 16-byte piece of raw samples -> SPB converted samples */
 template <int FMT> __device__ __forceinline__ void k1_piece_cvt(const uint4 v, float2 *out)
@@ -297,6 +307,16 @@ template <int FMT> __device__ __forceinline__ void k1_piece_cvt(const uint4 v, f
 	} else if constexpr (FMT == VDL2GPU_FMT_CF32) {
 		out[0] = make_float2(__uint_as_float(w[0]), __uint_as_float(w[1]));
 		out[1] = make_float2(__uint_as_float(w[2]), __uint_as_float(w[3]));
+	} else if constexpr (FMT == VDL2GPU_FMT_CS8) {
+#pragma unroll
+		for (int u = 0; u < 8; ++u) {
+			const unsigned h = w[u >> 1] >> (16 * (u & 1));
+			out[u] = make_float2((float)(signed char)(h & 0xffu), (float)(signed char)((h >> 8) & 0xffu));
+		}
+	} else if constexpr (FMT == VDL2GPU_FMT_S16R) {
+#pragma unroll
+		for (int u = 0; u < 8; ++u)
+			out[u] = make_float2((float)(short)((w[u >> 1] >> (16 * (u & 1))) & 0xffffu), 0.0f);
 	} else {
 #pragma unroll
 		for (int u = 0; u < 4; ++u)
@@ -415,7 +435,7 @@ void k1_pp(K1PParams p)
 					k1_load_block_nol(w, xr, lp, xa);
 				else
 					k1_load_block(w, xr, lp, xa);
-				if constexpr (FMT == VDL2GPU_FMT_F32R) {
+				if constexpr (K1_REAL(FMT)) {
 #pragma unroll
 					for (int u = 0; u < 8; ++u)
 						k1_rmac_s(acc, xr[u].x, (v2f){w[2 * u], w[2 * u + 1]});
@@ -435,7 +455,7 @@ void k1_pp(K1PParams p)
 					k1_load_block_nol(w, xr, lp - (8 - n), xa - (unsigned)(8 - n) * 8u);
 				else
 					k1_load_block(w, xr, lp - (8 - n), xa - (unsigned)(8 - n) * 8u);
-#define K1_TAIL(u) if constexpr (FMT == VDL2GPU_FMT_F32R) k1_rmac_s(acc, xr[u].x, (v2f){w[2 * (u)], w[2 * (u) + 1]}); \
+#define K1_TAIL(u) if constexpr (K1_REAL(FMT)) k1_rmac_s(acc, xr[u].x, (v2f){w[2 * (u)], w[2 * (u) + 1]}); \
 		   else k1_cmac_s(acc, xr[u], (v2f){w[2 * (u)], w[2 * (u) + 1]});
 				switch (n) {
 				case 7: K1_TAIL(1)
@@ -701,8 +721,10 @@ template <int FMT, int OFS = 0> __device__ __forceinline__ void k1_raw_issue(typ
 #else
 #define K1F_LD_MOD ""
 #endif
-	if constexpr (FMT == VDL2GPU_FMT_CU8)
+	if constexpr (FMT == VDL2GPU_FMT_CU8 || FMT == VDL2GPU_FMT_CS8)
 		asm volatile("global_load_ushort %0, %1, %2 offset:%3" K1F_LD_MOD : "=v"(r) : "v"(voff), "s"(sbase), "n"(OFS) : "memory");
+	else if constexpr (FMT == VDL2GPU_FMT_S16R)	/* sign-extended by the load: the register is the sample as an int */
+		asm volatile("global_load_sshort %0, %1, %2 offset:%3" K1F_LD_MOD : "=v"(r) : "v"(voff), "s"(sbase), "n"(OFS) : "memory");
 	else if constexpr (FMT == VDL2GPU_FMT_CF32)
 		asm volatile("global_load_dwordx2 %0, %1, %2 offset:%3" K1F_LD_MOD : "=v"(r) : "v"(voff), "s"(sbase), "n"(OFS) : "memory");
 	else
@@ -717,6 +739,10 @@ template <int FMT> __device__ __forceinline__ float2 k1_raw_cvt(typename K1Raw<F
 		return make_float2((float)(short)(v & 0xffffu), (float)(short)(v >> 16));
 	} else if constexpr (FMT == VDL2GPU_FMT_CF32) {
 		return make_float2(__uint_as_float(v.x), __uint_as_float(v.y));
+	} else if constexpr (FMT == VDL2GPU_FMT_CS8) {
+		return make_float2((float)(signed char)(v & 0xffu), (float)(signed char)((v >> 8) & 0xffu));
+	} else if constexpr (FMT == VDL2GPU_FMT_S16R) {
+		return make_float2((float)(int)v, 0.0f);
 	} else {
 		return make_float2(__uint_as_float(v), 0.0f);
 	}
@@ -745,7 +771,7 @@ template <int FMT> __global__ __launch_bounds__(K1F_THREADS, K1F_WAVES_OF(FMT))
 void k1_fast(K1Params p)
 {
 	typedef typename K1Raw<FMT>::T raw_t;
-	constexpr int B = (FMT == VDL2GPU_FMT_CU8) ? 2 : (FMT == VDL2GPU_FMT_CF32) ? 8 : 4;
+	constexpr int B = (FMT == VDL2GPU_FMT_CU8 || FMT == VDL2GPU_FMT_CS8 || FMT == VDL2GPU_FMT_S16R) ? 2 : (FMT == VDL2GPU_FMT_CF32) ? 8 : 4;
 #ifdef K1F_PROF
 	unsigned pf[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
 	unsigned tl = (unsigned)__builtin_amdgcn_readfirstlane((int)clock64());
@@ -961,7 +987,7 @@ void k1_fast(K1Params p)
 			if (ab == 0 || has_b) {
 #endif
 				v2f acc = {0.0f, 0.0f};
-				if (FMT == VDL2GPU_FMT_F32R) {
+				if (K1_REAL(FMT)) {
 					const v2f *xp = reinterpret_cast<const v2f *>(&xs[buf][ab][kk * 25]);
 #pragma unroll
 					for (int t = 0; t < 23; ++t) {

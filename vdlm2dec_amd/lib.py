@@ -13,8 +13,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libvdl2gpu.so")
 LIB_TEST_PATH = os.path.join(_HERE, "libvdl2gpu_test.so")   # the same sources with -DVDL2GPU_TESTHOOKS (tests only)
 
-FMT = {"cu8": 0, "cs16": 1, "cf32": 2, "f32": 3}
-SAMPLE_BYTES = {"cu8": 2, "cs16": 4, "cf32": 8, "f32": 4}
+FMT = {"cu8": 0, "cs16": 1, "cf32": 2, "f32": 3, "cs8": 4, "s16": 5}
+SAMPLE_BYTES = {"cu8": 2, "cs16": 4, "cf32": 8, "f32": 4, "cs8": 2, "s16": 2}
 MEM_HOST, MEM_DEVICE = 0, 1
 F_KEEP_DEC = 1
 F_SERIAL = 2

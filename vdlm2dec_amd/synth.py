@@ -362,6 +362,13 @@ def quantise(x: np.ndarray, fmt: str) -> np.ndarray:
         return out
     if fmt == "f32":  # real sampling (air.c:190): only the real part exists
         return x.real.astype(np.float32)
+    if fmt == "cs8":  # signed bytes at the cu8 LSB scale, no offset (the 127.37 is cu8's alone)
+        out = np.empty(2 * len(x), dtype=np.int8)
+        out[0::2] = np.clip(np.rint(x.real), -128, 127).astype(np.int8)
+        out[1::2] = np.clip(np.rint(x.imag), -128, 127).astype(np.int8)
+        return out
+    if fmt == "s16":  # real sampling as the ADC's integers: the cs16 scale, real part only
+        return np.clip(np.rint(x.real * 256.0), -32768, 32767).astype(np.int16)
     raise ValueError(fmt)
 
 
@@ -408,8 +415,8 @@ def _cli(argv=None) -> int:
     import argparse
     import json
     ap = argparse.ArgumentParser(prog="python -m vdlm2dec_amd.synth", description=_cli.__doc__)
-    ap.add_argument("out", help="raw IQ file to write (interleaved I,Q in --fmt; real samples for f32)")
-    ap.add_argument("--fmt", default="cu8", choices=["cu8", "cs16", "cf32", "f32"])
+    ap.add_argument("out", help="raw IQ file to write (interleaved I,Q in --fmt; real samples for f32 and s16)")
+    ap.add_argument("--fmt", default="cu8", choices=["cu8", "cs16", "cf32", "f32", "cs8", "s16"])
     ap.add_argument("--rate", type=int, default=2_000_000, help="SDRINRATE (2000000 rtl; 5000000/6000000 airspy; 10000000)")
     ap.add_argument("--fo", type=int, nargs="+", default=list(DEFAULT_FO_8CH), help="channel offsets from the tuner centre, Hz")
     ap.add_argument("--seconds", type=float, default=2.0)
