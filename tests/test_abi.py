@@ -129,10 +129,45 @@ def test_test_handicaps_exist_only_in_the_test_build(built):
     assert b"VDL2GPU_PRIM_DROP" not in blob and b"VDL2GPU_SPLIT_SAMPLES" not in blob and b"VDL2GPU_TEST_ITEM" not in blob
     tblob = open(lib.LIB_TEST_PATH, "rb").read()
     assert b"VDL2GPU_PRIM_DROP" in tblob and b"VDL2GPU_TEST_ITEM_GRID" in tblob and b"VDL2GPU_TEST_ITEM_COMMON" in tblob
-    src = open(os.path.join(ROOT, "vdlm2dec_amd", "csrc", "vdl2gpu.hip")).read()
-    push = src[src.index("static int push_impl(vdl2gpu_t *h, const void *iq, size_t nsamples, size_t stream_stride_bytes, int memkind, bool wait_copy)\n{"):]
-    push = push[:push.index("extern \"C\" int vdl2gpu_sync")]
-    assert "getenv" not in push                                             # every knob is read once, in create_impl
+    assert _getenv_outside_create(_host_sources()) == []                    # every knob is read once, in create_impl
+
+
+def _host_sources() -> dict:
+    """vdl2gpu.hip and every header of its directory that it includes, directly or through another: {file name: text}"""
+    import re
+    csrc = os.path.join(ROOT, "vdlm2dec_amd", "csrc")
+    out, todo = {}, ["vdl2gpu.hip"]
+    while todo:
+        f = todo.pop()
+        if f in out or not os.path.exists(os.path.join(csrc, f)):
+            continue
+        out[f] = open(os.path.join(csrc, f)).read()
+        todo += re.findall(r'#include "([^"]+)"', out[f])
+    return out
+
+
+def _getenv_outside_create(sources: dict) -> list:
+    """Files of the library that call getenv anywhere but in the bodies of create_impl and vdl2gpu_create (vdl2gpu.hip)."""
+    def cut(text, head):
+        a = text.index(head + "\n{\n")
+        return text[:a] + text[text.index("\n}\n", a) + 3:]
+    sources = dict(sources)
+    hip = cut(sources["vdl2gpu.hip"], "static int create_impl(vdl2gpu_t *h)")
+    sources["vdl2gpu.hip"] = cut(hip, 'extern "C" int vdl2gpu_create(const vdl2gpu_config_t *cfg, vdl2gpu_t **out)')
+    return sorted(f for f, text in sources.items() if "getenv" in text)
+
+
+def test_a_getenv_in_a_push_helper_is_caught():
+    """the check above is not vacuous: a getenv in a function push_impl calls, or in a header, is found"""
+    src = _host_sources()
+    assert "vdl2gpu_kernels.h" in src and "vdl2gpu_k1.h" in src
+    a = dict(src)
+    a["vdl2gpu.hip"] = a["vdl2gpu.hip"].replace("static int enqueue_front(vdl2gpu_t *h, hipStream_t fs, long long dec_base, PushTiming &pt)\n{\n",
+                                                  "static int enqueue_front(vdl2gpu_t *h, hipStream_t fs, long long dec_base, PushTiming &pt)\n{\n\tif (getenv(\"X\"))\n\t\treturn 0;\n")
+    assert a["vdl2gpu.hip"] != src["vdl2gpu.hip"] and _getenv_outside_create(a) == ["vdl2gpu.hip"]
+    b = dict(src)
+    b["vdl2gpu_k1.h"] += "\nstatic inline int k1_env() { return getenv(\"X\") != nullptr; }\n"
+    assert _getenv_outside_create(b) == ["vdl2gpu_k1.h"]
 
 
 def _layout_check_source(lay: dict) -> str:

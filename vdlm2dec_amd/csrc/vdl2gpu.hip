@@ -26,6 +26,7 @@
 #include <mutex>
 #include <new>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 extern "C" void sincosf(float, float *, float *);
@@ -43,16 +44,87 @@ extern "C" void sincosf(float, float *, float *);
 static int g_test_item_grid = 0, g_test_item_common = 0, g_test_item_verify = 0;	/* read once per vdl2gpu_create (test build only) */
 #endif
 
-#define NEV 8	/* before K1 | K1 | probe+regions | K2b | K2c | verify | K2f+K2d | K3 */
-#define NEVX 24	/* e[15] = the verify pass (round 0) has ended; + e[8], e[9] bracket the k1_fast launch alone; e[10] = start of the demodulator chain; e[12] = before the verify pass
-			 * (main stream, behind the wait for the resolver); e[13], e[14] = around the resolver (its own stream when hoisted) */
+#define TRY(expr)                        \
+	do {                             \
+		const int rc__ = (expr); \
+		if (rc__)                \
+			return rc__;     \
+	} while (0)
+
+/* The HIP events of a push that carries stage events (vdl2gpu_timing_t, VDL2GPU_STAGE_DUMP).  The stage sums are the intervals
+ * e0..e7 (harvest_timing): e0 before the channeliser | e1 behind it | e2 clusters begin | e3 clusters end | e4 front stage's
+ * scan + sort end | e5 repair rounds end | e6 second payload pass + block path end | e7 tail ends; beside them e8, e9 around
+ * the k1_fast / k1_pp launch alone | e10 scan begins | e11 the first period's general launch ends | e12 verify pass begins |
+ * e13, e14 around the resolver.  VDL2GPU_STAGE_DUMP only: e15 verify ends | e16 tail begins | e18 local repair ends | e20 commit
+ * ends | e21 second payload pass ends | e22 export ends | e23 resolver begins. */
+#define NEV 8
+#define NEVX 24
 struct PushTiming {
-	hipEvent_t e[NEVX];	/* before K1, after K1, after K2a, after K2b, after K2c+K2d, after K3 */
+	hipEvent_t e[NEVX];
 	uint64_t samples;
 	uint64_t index;		/* which push of the handle (VDL2GPU_STAGE_DUMP) */
 	bool fast;
 	bool staged;
-	int fast_parts;		/* fast-kernel launches of this push (e[8]..e[9]); e[11] = end of the first period's general launch */
+	int fast_parts;		/* fast-kernel launches of this push (e[8]..e[9]) */
+};
+
+/* A burst record has side columns: entries at the record's index in the device rings, the slabs and the host queue, present when
+ * the handle's flags ask for them.  A column is one row here and its flag in create_impl. */
+enum { COL_SOFT, COL_LEVEL, VDL2_NCOL };	/* VDL2GPU_F_SOFT_RS: a reliability map (2048 bytes); VDL2GPU_F_LEVELS: a level record */
+static const size_t col_bytes[VDL2_NCOL] = { sizeof(vdl2gpu_soft_t), sizeof(vdl2gpu_level_t) };
+
+/* A table set (push % VDL2_NSET): what a push's demodulator kernels work in, see alloc_sets. */
+struct TableSet {
+	K2Params k2{};		/* the set's 21 tables (cands ... items, ctl, fmask), its plane set, and every parameter that never changes */
+	hipEvent_t k2_done = nullptr;	/* the end of the tail of the push that used the set */
+	hipEvent_t f_done = nullptr;	/* FRONT of the push on the set has been enqueued up to its last kernel */
+	bool k2_rec = false;
+};
+
+/* An output ring (push % VDL2_NRING): the calling thread waits for the ring's previous push only three pushes later -- with two
+ * rings it waited for the tail of the push before last in every call, and the GPU's front stream waited for the calling thread. */
+struct OutRing {
+	vdl2gpu_burst_t *d_recs = nullptr;
+	void *d_side[VDL2_NCOL] = {};
+	vdl2gpu_frame_t *d_frames = nullptr;	/* VDL2GPU_F_FRAMES: a byte buffer of compact entries */
+	bool busy = false;
+	hipEvent_t done2[2] = {};	/* the end of the push's tail: its records and counters are on the host.  Two events, used in turn (ev): a
+					 * collector that waits for one with the handle lock released (wait_harvest) would otherwise wait on an
+					 * event the producer may re-record for the push three later */
+	int ev = 0;			/* which of the two the ring's current push recorded */
+	hipEvent_t in_read = nullptr;	/* its channeliser has read the caller's device buffer */
+	bool in_rec = false;
+	uint64_t push = 0;		/* which push filled the ring */
+	size_t samples = 0;		/* samples (per stream) of that push */
+	int slab = 0;			/* the slab its records were exported to */
+	bool spec = false;		/* its K2d ran ahead of verify: honour the redo mask */
+	hipEvent_t done() const { return done2[ev]; }
+	vdl2gpu_level_t *levels() const { return static_cast<vdl2gpu_level_t *>(d_side[COL_LEVEL]); }
+	vdl2gpu_soft_t *soft() const { return static_cast<vdl2gpu_soft_t *>(d_side[COL_SOFT]); }
+};
+
+/* A slab (push % VDL2_NSLAB) of page-locked host memory, which the GPU itself fills at the end of the push (k_export_records), and
+ * its device addresses.  One more than rings, so that a ring collected at the last moment -- by the call that is about to reuse it
+ * -- still lies untouched in its slab while the caller polls once more, instead of being copied aside at once. */
+struct Slab {
+	vdl2gpu_burst_t *h_recs = nullptr, *d_recs = nullptr;
+	uint8_t *h_side[VDL2_NCOL] = {};
+	void *d_side[VDL2_NCOL] = {};
+	size_t lo = 0, hi = 0;	/* ready_idx[lo, hi): where the handles into the slab lie (a push's are contiguous) */
+	vdl2gpu_level_t *d_levels() const { return static_cast<vdl2gpu_level_t *>(d_side[COL_LEVEL]); }
+	vdl2gpu_soft_t *d_soft() const { return static_cast<vdl2gpu_soft_t *>(d_side[COL_SOFT]); }
+};
+
+/* Records in pageable storage, with their side columns (byte vectors: col_bytes[k] a record). */
+struct RecQueue {
+	std::vector<vdl2gpu_burst_t> recs;
+	std::vector<uint8_t> side[VDL2_NCOL];
+	void clear()
+	{
+		recs.clear();
+		for (auto &s : side)
+			s.clear();
+	}
 };
 
 struct vdl2gpu {
@@ -66,6 +138,10 @@ struct vdl2gpu {
 	int S, C, L, maxwin, sdrclk;
 	size_t sample_bytes;
 	long long cap;		/* frames per stream per ping-pong buffer */
+	/* what the handle owns: see dev_alloc ... release_owned */
+	std::vector<void *> own_dev, own_host;
+	std::vector<hipEvent_t> own_events;
+	std::vector<hipStream_t> own_streams;
 	hipStream_t stream = nullptr;
 	/* host samples: two staging buffers in HBM, filled on a stream of their own, so that the copy of one
 	 * push runs beside the channeliser of the one before */
@@ -94,49 +170,18 @@ struct vdl2gpu {
 	ChanCfg *d_cfg = nullptr;
 	uint8_t *d_pn = nullptr;
 	uint8_t *d_pn8 = nullptr;	/* ... by payload byte (K2Params.pn8) */
-	vdl2gpu_burst_t *d_recs[VDL2_NRING] = {};	/* output rings, used in turn (push % 3): the calling thread waits for the
-									 * ring's previous push only three pushes later -- with two rings it waited for the tail of the push
-									 * before last in every call, and the GPU's front stream waited for the calling thread */
+	TableSet set[VDL2_NSET];
+	OutRing ring[VDL2_NRING];
 	unsigned *d_outc = nullptr;	/* [2*ring + {0,1}] = records written, dropped; [8], [9] running totals: serial redos, repairs */
-	bool ring_busy[VDL2_NRING] = {};
-	hipEvent_t ring_done2[VDL2_NRING][2] = {};	/* the end of the push's tail: its records and counters are on the host.  Two events per ring, used in
-						 * turn (ring_ev[]): a collector that waits for one with the handle lock released (wait_harvest) would
-						 * otherwise wait on an event the producer may re-record for the push three later */
-	int ring_ev[VDL2_NRING] = {};		/* which of the two the ring's current push recorded */
-#define ring_done(r) ring_done2[r][h->ring_ev[r]]
-	hipEvent_t in_read[VDL2_NRING] = {};	/* its channeliser has read the caller's device buffer */
-	bool in_rec[VDL2_NRING] = {};
-	uint64_t ring_push[VDL2_NRING] = {};	/* which push filled the ring */
 	hipStream_t copy_stream = nullptr;
-	unsigned *d_ctl[VDL2_NSET] = {};	/* control words, see CTL_* in vdl2gpu_kernels.h */
 	size_t ctl_words = 0;
 	unsigned rec_cap = 0;
-	Cand *d_cands[VDL2_NSET] = {};
-	Cluster *d_clusters[VDL2_NSET] = {};
-	int2 *d_clhead[VDL2_NSET] = {};
-	BurstDesc *d_stage[VDL2_NSET] = {};
-	unsigned *d_sel_list[VDL2_NSET] = {};
-	unsigned *d_sel_list2[VDL2_NSET] = {};	/* the repair rounds' selection (K2Params.sel_list2) */
-	int2 *d_regs[VDL2_NSET] = {};
-	Seg *d_segs[VDL2_NSET] = {};
-	int *d_fail[VDL2_NSET] = {};
-	int *d_redo[VDL2_NSET] = {};
-	ChanState *d_cs_out[VDL2_NSET] = {};
-	int *d_skey[VDL2_NSET] = {};
-	unsigned short *d_sidx[VDL2_NSET] = {}, *d_prim[VDL2_NSET] = {};
-	int *d_seeds[VDL2_NSET] = {};
-	uint8_t *d_onchain[VDL2_NSET] = {};	/* K2Params.onchain, .slog, .win: what a local repair stands on and what it leaves (k2p_patch) */
-	K2Slog *d_slog[VDL2_NSET] = {};
-	int2 *d_win[VDL2_NSET] = {};
 	unsigned item_cap = VDL2_ITEM_CAP, item_priv = VDL2_ITEM_PRIV;	/* K2Params.item_cap; of which private areas at most (create_impl) */
-	K2aItem *d_items[VDL2_NSET] = {};	/* what passed the scans' first screen (worked off by the scan workgroups themselves; the common area by the next kernel) */
 	int full_scan = 0;
 	unsigned stage_cap = 0;
 	int prim_drop = 0;	/* VDL2GPU_PRIM_DROP (tests) */
 #ifndef VDL2_K2D_GRID
-#ifndef VDL2_K2D_GRID
 #define VDL2_K2D_GRID 64
-#endif
 #endif
 	int k2d_grid = VDL2_K2D_GRID;	/* payload workgroups per channel (VDL2GPU_K2D_GRID): 64 -- half the chip's wavefront slots at the kernel's 119 registers.
 					 * One workgroup per burst is a chain of latencies; 128 per channel held EVERY slot while the verify pass beside it
@@ -151,22 +196,17 @@ struct vdl2gpu {
 	bool stage_dump = false;	/* VDL2GPU_STAGE_DUMP=1: events on every push, their times printed when the push is collected (harvest_timing) */
 	hipEvent_t ev_origin = nullptr;
 	hipEvent_t k1_done[2] = {nullptr, nullptr};	/* per staging buffer (host input) */
-	hipEvent_t k2_done[VDL2_NSET] = {};	/* per table set: the end of the tail of the push that used it */
-	bool k2_rec[VDL2_NSET] = {};
 	hipStream_t pay_stream = nullptr;	/* K2d beside the verify pass; then the push's TAIL (repair rounds, commit, export, counters: see enqueue_back) */
 	hipEvent_t verify_done = nullptr, k2f_done = nullptr;	/* main -> tail: the verify pass has run; tail -> main: the channel states are committed */
 	bool k2f_rec = false;
 	hipStream_t tail_prev = nullptr;	/* the stream the previous push's tail ran on */
 	hipEvent_t k2c_done = nullptr, pay_done = nullptr;
-	unsigned *d_fmask[VDL2_NSET] = {};	/* K2f's redo mask of the push in flight, 16 words */
-	bool ring_spec[VDL2_NRING] = {};	/* that ring's K2d ran ahead of verify: honour the redo mask */
 	int repair_rounds = 0;		/* adapted floor..4 from how often the serial fallback was needed */
 	int rounds_floor = 1;		/* one (resolver-only) repair round is always scheduled, see enqueue_back */
 	size_t split_samples = 0;	/* pushes longer than this are cut into parts (36 s of air time), see push_checked; halved
 					 * whenever a channel's candidate tables overflow */
 	size_t split_default = 0;
 	unsigned long long last_ovf_push = 0;
-	size_t ring_samples[VDL2_NRING] = {};	/* samples (per stream) of the push that filled each output ring */
 	double cand_dens[4] = {0, 0, 0, 0};	/* candidates per input sample of the busiest channel, last four parts collected */
 	unsigned cand_dens_n = 0;
 	size_t split_unit = 32768;	/* parts are multiples of this (k1_fast takes whole superperiods; the RTL quirk needs whole blocks) */
@@ -182,21 +222,16 @@ struct vdl2gpu {
 	std::vector<PushTiming> pending;
 	std::vector<PushTiming> free_ev;
 	vdl2gpu_timing_t tm{};
-	std::vector<vdl2gpu_burst_t> ready;	/* fetched, not yet handed out (storage order) */
-	/* hand-out order, consumed from ready_pos: bits 32-33 = where the record lies (0: `ready`, 1 + ring: that ring's slab of
-	 * page-locked host memory, which the GPU itself fills at the end of the push -- k_export_records -- so that collecting a
-	 * push's bursts is an index sort and ONE copy per record, into the caller's buffer), bits 0-31 = index there */
+	RecQueue ready;		/* fetched, not yet handed out (storage order) */
+	/* hand-out order, consumed from ready_pos: bits 32-33 = where the record lies (0: `ready`, 1 + slab: that slab),
+	 * bits 0-31 = index there -- so that collecting a push's bursts is an index sort and ONE copy per record, into the
+	 * caller's buffer (slot_of decodes a handle) */
 	std::vector<uint64_t> ready_idx;
-	vdl2gpu_burst_t *h_slab[VDL2_NSLAB] = {}, *d_slab[VDL2_NSLAB] = {};	/* the slabs (push % 4) and their device addresses:
-									 * one more than rings, so that a ring collected at the last moment -- by the call that is about to reuse it -- still lies
-									 * untouched in its slab while the caller polls once more, instead of being copied aside at once */
-	int ring_slab[VDL2_NRING] = {};	/* the slab of the push that filled the ring */
-	size_t slab_lo[VDL2_NSLAB] = {}, slab_hi[VDL2_NSLAB] = {};	/* ready_idx[lo, hi): where the handles into each slab lie (a push's are contiguous) */
+	Slab slab[VDL2_NSLAB];
 	unsigned slab_cap = 0;
 	size_t ready_pos = 0;
 	/* block path in the pipeline (VDL2GPU_F_FRAMES) */
 	bool frames_on = false;
-	vdl2gpu_frame_t *d_frames[VDL2_NRING] = {};	/* byte buffers of compact entries */
 	unsigned *d_k4tab = nullptr;	/* GF(256) and FCS tables of the block path */
 	unsigned *d_fcnt = nullptr;	/* [4*ring] frames written, [4*ring+1] dropped, [4*ring+2] bytes used */
 	unsigned frame_cap = 0;	/* bytes of a frame buffer (slots + arena) */
@@ -206,18 +241,8 @@ struct vdl2gpu {
 	size_t fready_pos = 0;
 	uint64_t frames_dropped = 0;
 	vdl2gpu_burst_t *h_pin = nullptr;	/* pinned bounce buffer for record read-back */
-	/* VDL2GPU_F_LEVELS: a level record beside every burst record, at the same index -- in the device rings, the slabs and `ready` */
-	bool levels_on = false;
-	double lev_k = 1.0;	/* K of vdl2gpu.h: power of a full-scale tone at the channel centre */
-	vdl2gpu_level_t *d_levels[VDL2_NRING] = {};
-	vdl2gpu_level_t *h_lslab[VDL2_NSLAB] = {}, *d_lslab[VDL2_NSLAB] = {};
-	std::vector<vdl2gpu_level_t> lready;	/* parallel to `ready` */
-	/* VDL2GPU_F_SOFT_RS: a reliability map beside every burst record, at the same index -- in the device rings, the slabs and `ready`
-	 * (2048 bytes per record slot in each) */
-	bool soft_on = false;
-	vdl2gpu_soft_t *d_soft[VDL2_NRING] = {};
-	vdl2gpu_soft_t *h_sslab[VDL2_NSLAB] = {}, *d_sslab[VDL2_NSLAB] = {};
-	std::vector<vdl2gpu_soft_t> sready;	/* parallel to `ready` */
+	bool col_on[VDL2_NCOL] = {};	/* which side columns the handle has */
+	double lev_k = 1.0;	/* K of vdl2gpu.h: power of a full-scale tone at the channel centre (VDL2GPU_F_LEVELS) */
 	unsigned *h_pin_cnt = nullptr;	/* pinned, written by k3_rebase: [32*ring + {0..6}] counters, [7] overflowed channels, [8..23] redo mask, [24] most candidates of any channel */
 	unsigned *d_pin_cnt = nullptr;	/* its device address */
 	unsigned pin_recs = 0;
@@ -226,7 +251,7 @@ struct vdl2gpu {
 	double hprof[8] = {0, 0, 0, 0, 0, 0, 0, 0};	/* VDL2GPU_HOST_PROF: seconds of the calling thread in the segments of push_impl (printed at destroy) */
 	bool hprof_on = false;
 	uint64_t hprof_push0 = 0;	/* pushes at the last reset of hprof[] */
-	/* Environment knobs, read ONCE in create_impl (INTEGRATION.md lists them): push_impl never calls getenv.
+	/* Environment knobs, read ONCE in create_impl (INTEGRATION.md lists them): no other function reads the environment.
 	 * The test handicaps (VDL2GPU_PRIM_DROP, VDL2GPU_SPLIT_SAMPLES, VDL2GPU_F_TEST_NOREGION) exist only in the
 	 * library built with -DVDL2GPU_TESTHOOKS (libvdl2gpu_test.so, which the tests load). */
 	struct {
@@ -264,7 +289,6 @@ struct vdl2gpu {
 		size_t pt_index = 0;	/* its PushTiming in `pending` */
 	} back;
 	hipStream_t fstream = nullptr;
-	hipEvent_t f_done[VDL2_NSET] = {};	/* FRONT of the push on that plane / table set has been enqueued up to its last kernel */
 	hipEvent_t k1_ev = nullptr;	/* channeliser + carry copy of the latest push that kept to the main stream */
 	hipEvent_t f_tail = nullptr;	/* the end of the latest front stage on fstream (carry copy included) */
 	bool k1_ev_rec = false, last_two_streams = false;
@@ -480,6 +504,149 @@ static size_t fmt_bytes(int fmt)
 	}
 }
 
+/* Everything a handle creates on the device, in page-locked memory, as an event or as a stream is made here and recorded in the
+ * handle; release_owned() is the one place that gives it back.  Callers keep their plain pointers, and use the macros, which
+ * name the object in the error text (vdl2gpu_last_error says WHICH allocation failed). */
+static int hip_failed(vdl2gpu_t *h, const char *what, hipError_t e)
+{
+	h->err = std::string(what) + ": " + hipGetErrorString(e);
+	return VDL2GPU_EHIP;
+}
+
+template <class T> static int dev_alloc(vdl2gpu_t *h, T **p, size_t bytes, const char *what)
+{
+	void *q = nullptr;
+	const hipError_t e = hipMalloc(&q, bytes);
+	if (e != hipSuccess)
+		return hip_failed(h, what, e);
+	h->own_dev.push_back(q);
+	*p = static_cast<T *>(q);
+	return VDL2GPU_OK;
+}
+#define DEV_ALLOC(h, p, bytes) TRY(dev_alloc(h, &(p), bytes, "hipMalloc(&" #p ", " #bytes ")"))
+
+/* give one of them back early (a staging buffer that has to grow) */
+static void dev_release(vdl2gpu_t *h, const void *p)
+{
+	auto it = std::find(h->own_dev.begin(), h->own_dev.end(), p);
+	if (it == h->own_dev.end())
+		return;
+	(void)hipFree(*it);
+	h->own_dev.erase(it);
+}
+
+template <class T> static int host_alloc(vdl2gpu_t *h, T **p, size_t bytes, unsigned flags, const char *what)
+{
+	void *q = nullptr;
+	const hipError_t e = hipHostMalloc(&q, bytes, flags);
+	if (e != hipSuccess)
+		return hip_failed(h, what, e);
+	h->own_host.push_back(q);
+	*p = static_cast<T *>(q);
+	return VDL2GPU_OK;
+}
+#define HOST_ALLOC(h, p, bytes, flags) TRY(host_alloc(h, &(p), bytes, flags, "hipHostMalloc(&" #p ", " #bytes ", " #flags ")"))
+
+static int new_event(vdl2gpu_t *h, hipEvent_t *ev, const char *what, bool timing = false)
+{
+	const hipError_t e = hipEventCreateWithFlags(ev, timing ? hipEventDefault : hipEventDisableTiming);
+	if (e != hipSuccess)
+		return hip_failed(h, what, e);
+	h->own_events.push_back(*ev);
+	return VDL2GPU_OK;
+}
+#define NEW_EVENT(h, ev, ...) TRY(new_event(h, &(ev), "hipEventCreate(&" #ev ")", ##__VA_ARGS__))
+
+/* a non-blocking stream: of priority *prio, or of the default one */
+static int new_stream(vdl2gpu_t *h, hipStream_t *s, const char *what, const int *prio = nullptr)
+{
+	const hipError_t e = prio ? hipStreamCreateWithPriority(s, hipStreamNonBlocking, *prio) : hipStreamCreateWithFlags(s, hipStreamNonBlocking);
+	if (e != hipSuccess)
+		return hip_failed(h, what, e);
+	h->own_streams.push_back(*s);
+	return VDL2GPU_OK;
+}
+#define NEW_STREAM(h, s, ...) TRY(new_stream(h, &(s), "hipStreamCreate(&" #s ")", ##__VA_ARGS__))
+
+static void release_owned(vdl2gpu_t *h)
+{
+	for (hipStream_t s : h->own_streams)
+		(void)hipStreamSynchronize(s);
+	for (hipEvent_t e : h->own_events)
+		(void)hipEventDestroy(e);
+	for (void *p : h->own_dev)
+		(void)hipFree(p);
+	for (void *p : h->own_host)
+		(void)hipHostFree(p);
+	for (hipStream_t s : h->own_streams)
+		(void)hipStreamDestroy(s);
+}
+
+#ifdef K1F_PROF
+static void k1f_prof_report()
+{
+	static unsigned raw[K1F_PROF_SLOTS][12];
+	(void)hipDeviceSynchronize();
+	if (hipMemcpyFromSymbol(raw, HIP_SYMBOL(k1f_prof), sizeof raw) == hipSuccess) {
+		double pf[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+		unsigned first = 0xffffffffu, last_start = 0, last_end = 0;
+		int nwaves = 0;
+		for (int b = 0; b < K1F_PROF_SLOTS; ++b) {
+			if (!raw[b][7])
+				continue;
+			++nwaves;
+			for (int i = 0; i < 9; ++i)
+				pf[i] += raw[b][i];
+			first = std::min(first, raw[b][9]);
+			last_start = std::max(last_start, raw[b][9]);
+			last_end = std::max(last_end, raw[b][9] + raw[b][8]);
+		}
+		const char *nm[7] = {"prologue", "wait samples", "convert+park+issue", "barrier", "mix+divide", "store issue", "drain"};
+		if (pf[7] > 0) {
+			double cyc = 0;
+			for (int i = 0; i < 7; ++i)
+				cyc += pf[i];
+			fprintf(stderr, "k1_fast phases, shader cycles per wavefront-iteration (%.0f wavefront-iterations, %d wavefronts in the last launch):", pf[7], nwaves);
+			for (int i = 0; i < 7; ++i)
+				fprintf(stderr, " %s %.0f;", nm[i], pf[i] / pf[7]);
+			{
+				double a = 0, b = 0;
+				for (int bb = 0; bb < K1F_PROF_SLOTS; ++bb)
+					if (raw[bb][7]) {
+						a += raw[bb][10];
+						b += raw[bb][11];
+					}
+				cyc += a + b;
+				fprintf(stderr, " [prologue per wavefront: window table %.0f, addresses + first loads %.0f, LO values + wait %.0f]", a / nwaves, b / nwaves, pf[0] / nwaves);
+			}
+			fprintf(stderr, " shader clock %.0f MHz; a wavefront lives %.1f us; first start to last start %.1f us, to last end %.1f us\n",
+				cyc / (pf[8] / 100.0), pf[8] / nwaves / 100.0, (last_start - first) / 100.0, (last_end - first) / 100.0);
+			std::vector<unsigned> life;
+			double by_xcd[8] = {0}, by_role[K1F_ROLES] = {0}, by_wv[2] = {0};
+			int n_xcd[8] = {0}, n_role[K1F_ROLES] = {0}, n_wv[2] = {0};
+			for (int b = 0; b < K1F_PROF_SLOTS; ++b) {
+				if (!raw[b][7])
+					continue;
+				life.push_back(raw[b][8]);
+				const int blk = b / 2;
+				by_xcd[blk & 7] += raw[b][8]; ++n_xcd[blk & 7];
+				by_role[(blk >> 3) % K1F_ROLES] += raw[b][8]; ++n_role[(blk >> 3) % K1F_ROLES];
+				by_wv[b & 1] += raw[b][8]; ++n_wv[b & 1];
+			}
+			std::sort(life.begin(), life.end());
+			fprintf(stderr, "   lifetime us: min %.1f p10 %.1f p50 %.1f p90 %.1f p99 %.1f max %.1f\n   by XCD:", life[0] / 100.0, life[life.size() / 10] / 100.0,
+				life[life.size() / 2] / 100.0, life[life.size() * 9 / 10] / 100.0, life[life.size() * 99 / 100] / 100.0, life.back() / 100.0);
+			for (int i = 0; i < 8; ++i)
+				fprintf(stderr, " %.1f", by_xcd[i] / std::max(1, n_xcd[i]) / 100.0);
+			fprintf(stderr, "\n   by role:");
+			for (int i = 0; i < K1F_ROLES; ++i)
+				fprintf(stderr, " %.1f", by_role[i] / std::max(1, n_role[i]) / 100.0);
+			fprintf(stderr, "\n   by wavefront of the workgroup: %.1f %.1f\n", by_wv[0] / std::max(1, n_wv[0]) / 100.0, by_wv[1] / std::max(1, n_wv[1]) / 100.0);
+		}
+	}
+}
+#endif
+
 extern "C" void vdl2gpu_destroy(vdl2gpu_t *h)
 {
 	if (h && h->hprof_on && h->pushes)
@@ -488,216 +655,12 @@ extern "C" void vdl2gpu_destroy(vdl2gpu_t *h)
 			h->hprof[0] / h->pushes * 1e3, h->hprof[1] / h->pushes * 1e3, h->hprof[2] / h->pushes * 1e3, h->hprof[3] / h->pushes * 1e3,
 			h->hprof[4] / h->pushes * 1e3, h->hprof[5] / h->pushes * 1e3, h->hprof[6] / h->pushes * 1e3);
 #ifdef K1F_PROF
-	{
-		static unsigned raw[K1F_PROF_SLOTS][12];
-		(void)hipDeviceSynchronize();
-		if (hipMemcpyFromSymbol(raw, HIP_SYMBOL(k1f_prof), sizeof raw) == hipSuccess) {
-			double pf[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-			unsigned first = 0xffffffffu, last_start = 0, last_end = 0;
-			int nwaves = 0;
-			for (int b = 0; b < K1F_PROF_SLOTS; ++b) {
-				if (!raw[b][7])
-					continue;
-				++nwaves;
-				for (int i = 0; i < 9; ++i)
-					pf[i] += raw[b][i];
-				first = std::min(first, raw[b][9]);
-				last_start = std::max(last_start, raw[b][9]);
-				last_end = std::max(last_end, raw[b][9] + raw[b][8]);
-			}
-			const char *nm[7] = {"prologue", "wait samples", "convert+park+issue", "barrier", "mix+divide", "store issue", "drain"};
-			if (pf[7] > 0) {
-				double cyc = 0;
-				for (int i = 0; i < 7; ++i)
-					cyc += pf[i];
-				fprintf(stderr, "k1_fast phases, shader cycles per wavefront-iteration (%.0f wavefront-iterations, %d wavefronts in the last launch):", pf[7], nwaves);
-				for (int i = 0; i < 7; ++i)
-					fprintf(stderr, " %s %.0f;", nm[i], pf[i] / pf[7]);
-				{
-					double a = 0, b = 0;
-					for (int bb = 0; bb < K1F_PROF_SLOTS; ++bb)
-						if (raw[bb][7]) {
-							a += raw[bb][10];
-							b += raw[bb][11];
-						}
-					cyc += a + b;
-					fprintf(stderr, " [prologue per wavefront: window table %.0f, addresses + first loads %.0f, LO values + wait %.0f]", a / nwaves, b / nwaves, pf[0] / nwaves);
-				}
-				fprintf(stderr, " shader clock %.0f MHz; a wavefront lives %.1f us; first start to last start %.1f us, to last end %.1f us\n",
-					cyc / (pf[8] / 100.0), pf[8] / nwaves / 100.0, (last_start - first) / 100.0, (last_end - first) / 100.0);
-				std::vector<unsigned> life;
-				double by_xcd[8] = {0}, by_role[K1F_ROLES] = {0}, by_wv[2] = {0};
-				int n_xcd[8] = {0}, n_role[K1F_ROLES] = {0}, n_wv[2] = {0};
-				for (int b = 0; b < K1F_PROF_SLOTS; ++b) {
-					if (!raw[b][7])
-						continue;
-					life.push_back(raw[b][8]);
-					const int blk = b / 2;
-					by_xcd[blk & 7] += raw[b][8]; ++n_xcd[blk & 7];
-					by_role[(blk >> 3) % K1F_ROLES] += raw[b][8]; ++n_role[(blk >> 3) % K1F_ROLES];
-					by_wv[b & 1] += raw[b][8]; ++n_wv[b & 1];
-				}
-				std::sort(life.begin(), life.end());
-				fprintf(stderr, "   lifetime us: min %.1f p10 %.1f p50 %.1f p90 %.1f p99 %.1f max %.1f\n   by XCD:", life[0] / 100.0, life[life.size() / 10] / 100.0,
-					life[life.size() / 2] / 100.0, life[life.size() * 9 / 10] / 100.0, life[life.size() * 99 / 100] / 100.0, life.back() / 100.0);
-				for (int i = 0; i < 8; ++i)
-					fprintf(stderr, " %.1f", by_xcd[i] / std::max(1, n_xcd[i]) / 100.0);
-				fprintf(stderr, "\n   by role:");
-				for (int i = 0; i < K1F_ROLES; ++i)
-					fprintf(stderr, " %.1f", by_role[i] / std::max(1, n_role[i]) / 100.0);
-				fprintf(stderr, "\n   by wavefront of the workgroup: %.1f %.1f\n", by_wv[0] / std::max(1, n_wv[0]) / 100.0, by_wv[1] / std::max(1, n_wv[1]) / 100.0);
-			}
-		}
-	}
+	k1f_prof_report();
 #endif
 	if (!h)
 		return;
 	(void)hipSetDevice(h->cfg.device);
-	if (h->in_stream)
-		(void)hipStreamSynchronize(h->in_stream);
-	if (h->fstream)
-		(void)hipStreamSynchronize(h->fstream);
-	if (h->stream)
-		(void)hipStreamSynchronize(h->stream);
-	if (h->pay_stream)
-		(void)hipStreamSynchronize(h->pay_stream);
-	if (h->copy_stream)
-		(void)hipStreamSynchronize(h->copy_stream);
-	for (auto &pt : h->pending)
-		for (auto &e : pt.e)
-			(void)hipEventDestroy(e);
-	for (auto &pt : h->free_ev)
-		for (auto &e : pt.e)
-			(void)hipEventDestroy(e);
-	(void)hipFree(h->d_raw[0]);
-	(void)hipFree(h->d_raw[1]);
-	if (h->ring_host)
-		(void)hipHostFree(h->ring_host);
-	for (hipEvent_t e : h->ring_copied)
-		(void)hipEventDestroy(e);
-	for (int i = 0; i < 2; ++i)
-		if (h->raw_copied[i])
-			(void)hipEventDestroy(h->raw_copied[i]);
-	if (h->in_stream)
-		(void)hipStreamDestroy(h->in_stream);
-	(void)hipFree(h->d_lo);
-	(void)hipFree(h->d_lo_ext);
-	(void)hipFree(h->d_k1_tickets);
-	for (int r = 0; r < VDL2_NSET; ++r)
-		(void)hipFree(h->d_dec[r]);
-	(void)hipFree(h->d_ss);
-	(void)hipFree(h->d_cs);
-	(void)hipFree(h->d_cfg);
-	(void)hipFree(h->d_pn);
-	(void)hipFree(h->d_pn8);
-	for (int r = 0; r < VDL2_NRING; ++r) {
-		(void)hipFree(h->d_recs[r]);
-		(void)hipFree(h->d_levels[r]);
-		(void)hipFree(h->d_soft[r]);
-		(void)hipFree(h->d_frames[r]);
-	}
-	(void)hipFree(h->d_fcnt);
-	(void)hipFree(h->d_k4tab);
-	(void)hipFree(h->d_outc);
-	if (h->copy_stream)
-		(void)hipStreamDestroy(h->copy_stream);
-	for (int r = 0; r < 2; ++r)
-		if (h->k1_done[r])
-			(void)hipEventDestroy(h->k1_done[r]);
-	for (int r = 0; r < VDL2_NSET; ++r)
-		if (h->k2_done[r])
-			(void)hipEventDestroy(h->k2_done[r]);
-	for (int r = 0; r < VDL2_NRING; ++r) {
-		for (int k = 0; k < 2; ++k)
-			if (h->ring_done2[r][k])
-				(void)hipEventDestroy(h->ring_done2[r][k]);
-		if (h->in_read[r])
-			(void)hipEventDestroy(h->in_read[r]);
-	}
-	if (h->fstream) {
-		(void)hipStreamSynchronize(h->fstream);
-		(void)hipStreamDestroy(h->fstream);
-	}
-	for (int r = 0; r < VDL2_NSET; ++r)
-		if (h->f_done[r])
-			(void)hipEventDestroy(h->f_done[r]);
-	if (h->k1_ev)
-		(void)hipEventDestroy(h->k1_ev);
-	if (h->f_tail)
-		(void)hipEventDestroy(h->f_tail);
-	if (h->pay_stream) {
-		(void)hipStreamSynchronize(h->pay_stream);
-		(void)hipStreamDestroy(h->pay_stream);
-	}
-	if (h->k2c_done)
-		(void)hipEventDestroy(h->k2c_done);
-	if (h->pay_done)
-		(void)hipEventDestroy(h->pay_done);
-	if (h->verify_done)
-		(void)hipEventDestroy(h->verify_done);
-	if (h->k2f_done)
-		(void)hipEventDestroy(h->k2f_done);
-
-	if (h->ev_origin)
-		(void)hipEventDestroy(h->ev_origin);
-	for (int r = 0; r < VDL2_NSET; ++r)
-		(void)hipFree(h->d_fmask[r]);
-	for (int r = 0; r < VDL2_NSET; ++r)
-		(void)hipFree(h->d_ctl[r]);
-	for (int r = 0; r < VDL2_NSET; ++r)
-		(void)hipFree(h->d_cands[r]);
-	for (int r = 0; r < VDL2_NSET; ++r)
-		(void)hipFree(h->d_clusters[r]);
-	for (int r = 0; r < VDL2_NSET; ++r)
-		(void)hipFree(h->d_clhead[r]);
-	for (int r = 0; r < VDL2_NSET; ++r)
-		(void)hipFree(h->d_stage[r]);
-	for (int r = 0; r < VDL2_NSET; ++r)
-		(void)hipFree(h->d_sel_list[r]);
-	for (int r = 0; r < VDL2_NSET; ++r)
-		(void)hipFree(h->d_sel_list2[r]);
-	for (int r = 0; r < VDL2_NSET; ++r)
-		(void)hipFree(h->d_regs[r]);
-	for (int r = 0; r < VDL2_NSET; ++r)
-		(void)hipFree(h->d_segs[r]);
-	for (int r = 0; r < VDL2_NSET; ++r)
-		(void)hipFree(h->d_fail[r]);
-	for (int r = 0; r < VDL2_NSET; ++r)
-		(void)hipFree(h->d_redo[r]);
-	for (int r = 0; r < VDL2_NSET; ++r)
-		(void)hipFree(h->d_cs_out[r]);
-	for (int r = 0; r < VDL2_NSET; ++r)
-		(void)hipFree(h->d_skey[r]);
-	for (int r = 0; r < VDL2_NSET; ++r)
-		(void)hipFree(h->d_sidx[r]);
-	for (int r = 0; r < VDL2_NSET; ++r)
-		(void)hipFree(h->d_prim[r]);
-	for (int r = 0; r < VDL2_NSET; ++r) {
-		(void)hipFree(h->d_seeds[r]);
-		(void)hipFree(h->d_onchain[r]);
-		(void)hipFree(h->d_slog[r]);
-		(void)hipFree(h->d_win[r]);
-	}
-	for (int r = 0; r < VDL2_NSET; ++r)
-		(void)hipFree(h->d_items[r]);
-	(void)hipFree(h->d_dbg);
-	(void)hipFree(h->d_headtap);
-	(void)hipFree(h->d_headtap_n);
-	if (h->h_pin)
-		(void)hipHostFree(h->h_pin);
-	for (int r = 0; r < VDL2_NSLAB; ++r)
-		if (h->h_slab[r])
-			(void)hipHostFree(h->h_slab[r]);
-	for (int r = 0; r < VDL2_NSLAB; ++r)
-		if (h->h_lslab[r])
-			(void)hipHostFree(h->h_lslab[r]);
-	for (int r = 0; r < VDL2_NSLAB; ++r)
-		if (h->h_sslab[r])
-			(void)hipHostFree(h->h_sslab[r]);
-	if (h->h_pin_cnt)
-		(void)hipHostFree(h->h_pin_cnt);
-	if (h->stream)
-		(void)hipStreamDestroy(h->stream);
+	release_owned(h);
 	delete h;
 }
 
@@ -726,6 +689,93 @@ static size_t k1_smem_bytes(uint64_t L, uint64_t maxwin)
 	return (size_t)(((L + maxwin) * VDL2_CS + (uint64_t)K1_OPB * maxwin) * sizeof(float2));
 }
 
+/* One kind of table for every set in turn (so the sets' tables lie as they always did: kind by kind). */
+template <class T> static int alloc_table(vdl2gpu_t *h, T *K2Params::*m, size_t bytes, const char *what, bool zero = false)
+{
+	for (TableSet &t : h->set)
+		TRY(dev_alloc(h, &(t.k2.*m), bytes, what));
+	for (TableSet &t : h->set)
+		if (zero)
+			HIPCHK(h, hipMemsetAsync(t.k2.*m, 0, bytes, h->stream));
+	return VDL2GPU_OK;
+}
+
+/* The 21 tables of the table sets: a new table is its member of K2Params and a line here. */
+#define ALLOC_TABLE(h, name, bytes, ...) TRY(alloc_table(h, &K2Params::name, bytes, "hipMalloc(&set[r].k2." #name ", " #bytes ")", ##__VA_ARGS__))
+static int alloc_sets(vdl2gpu_t *h)
+{
+	const size_t SC = (size_t)h->S * VDL2_CS;
+	ALLOC_TABLE(h, fmask, 16 * sizeof(unsigned), true);
+	ALLOC_TABLE(h, ctl, h->ctl_words * sizeof(unsigned), true);
+	ALLOC_TABLE(h, cands, SC * VDL2_CAND_CAP * sizeof(Cand));
+	ALLOC_TABLE(h, clusters, SC * VDL2_CAND_CAP * sizeof(Cluster));
+	ALLOC_TABLE(h, clhead, SC * VDL2_CAND_CAP * sizeof(int2));
+	ALLOC_TABLE(h, stage, (size_t)h->stage_cap * sizeof(BurstDesc));
+	ALLOC_TABLE(h, sel_list, SC * VDL2_SEL_CAP * sizeof(unsigned));
+	ALLOC_TABLE(h, sel_list2, SC * VDL2_SEL_CAP * sizeof(unsigned));
+	ALLOC_TABLE(h, regs, SC * VDL2_REG_CAP * sizeof(int2));
+	ALLOC_TABLE(h, segs, SC * VDL2_SEG_CAP * sizeof(Seg));
+	ALLOC_TABLE(h, fail, SC * sizeof(int));
+	ALLOC_TABLE(h, redo, SC * sizeof(int));
+	ALLOC_TABLE(h, cs_out, SC * sizeof(ChanState));
+	ALLOC_TABLE(h, skey, SC * VDL2_CAND_CAP * sizeof(int));
+	ALLOC_TABLE(h, sidx, SC * VDL2_CAND_CAP * sizeof(unsigned short));
+	ALLOC_TABLE(h, prim, SC * VDL2_CAND_CAP * sizeof(unsigned short));
+	ALLOC_TABLE(h, seeds, SC * VDL2_CAND_CAP * sizeof(int));
+	for (TableSet &t : h->set) {
+		DEV_ALLOC(h, t.k2.onchain, SC * VDL2_CAND_CAP);
+		DEV_ALLOC(h, t.k2.slog, SC * VDL2_SLOG_CAP * sizeof(K2Slog));
+		DEV_ALLOC(h, t.k2.win, SC * VDL2_WIN_CAP * sizeof(int2));
+	}
+	ALLOC_TABLE(h, items, SC * h->item_cap * sizeof(K2aItem));
+	return VDL2GPU_OK;
+}
+
+/* The K2Params every kernel of a push on a set starts from: beside the set's tables (alloc_sets), whatever never changes between
+ * pushes; enqueue_front adds what is the push's.  Called when everything the parameters name exists. */
+static void fill_set_params(vdl2gpu_t *h)
+{
+	for (int r = 0; r < VDL2_NSET; ++r) {
+		K2Params &k = h->set[r].k2;
+		k.dec = h->d_dec[r];
+		k.cap = h->cap;
+		k.nbch = h->C;
+		k.nstreams = h->S;
+		k.ss = h->d_ss;
+		k.cs = h->d_cs;
+		k.cfg = h->d_cfg;
+		k.pn = h->d_pn;
+		k.pn8 = h->d_pn8;
+		k.sel_mode = 0;
+		k.stage_cap = h->stage_cap;
+		k.outc_total_redo = h->d_outc + 8;
+		k.rec_cap = h->rec_cap;
+#if VDL2_PROBE_STRIDE == 2
+		k.probe_r = 0;				/* the one class scanned everywhere: fixed, not the class the channel is in */
+#else
+		k.probe_r = -1;			/* no class is scanned everywhere: the probe only finds the bursts (every fourth sample of sub-phase 0), the
+							 * region scan lists every class around them, the verify pass covers every stretch the chain idles through */
+#endif
+		k.prim_drop = h->prim_drop;
+		k.dbg = h->knob.debug_counters ? h->d_dbg : nullptr;
+		k.headtap = h->d_headtap;
+		k.headtap_n = h->d_headtap_n;
+		k.headtap_cap = h->headtap_cap;
+		k.full_scan = h->full_scan;
+#ifdef VDL2GPU_TESTHOOKS
+		k.test_noregion = (h->cfg.flags & VDL2GPU_F_TEST_NOREGION) ? 1 : 0;
+#endif
+		k.round = 0;
+		k.item_cap = h->item_cap;
+		k.item_priv = h->item_priv;
+		k.drain_slot = -1;
+	}
+}
+
+/* The longest part push_checked makes of a push: 36 s of air time (split_default); a test build may ask for a third more
+ * (VDL2GPU_SPLIT_SAMPLES).  The item lists are sized by the same two numbers. */
+static const int PART_SECONDS = 36, TEST_PART_NUM = 4, TEST_PART_DEN = 3;
+
 static int create_impl(vdl2gpu_t *h)
 {
 	const vdl2gpu_config_t &cfg = h->cfg;
@@ -743,128 +793,10 @@ static int create_impl(vdl2gpu_t *h)
 		if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k2a_probe, K2A_THREADS, 0) == hipSuccess && occ > 0)
 			h->probe_occ = occ;
 	}
-	{
-		int prio_lo = 0, prio_hi = 0;
-		HIPCHK(h, hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi));
-		HIPCHK(h, hipStreamCreateWithPriority(&h->stream, hipStreamNonBlocking, prio_hi));
-	}
+	int prio_lo = 0, prio_hi = 0;
+	HIPCHK(h, hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi));
+	NEW_STREAM(h, h->stream, &prio_hi);
 	const int S = h->S, L = h->L;
-	h->k1_tbase.assign((size_t)S * 8, 0u);
-	const long long jmax = (long long)((21ull * cfg.max_push) / (unsigned)h->sdrclk) + 2;
-	h->cap = plane_frames(cfg.max_push, (unsigned)h->sdrclk);	/* planes start on 128-byte lines */
-	{
-		/* The item lists (what passes a scan's first screen: 80 bytes an item, three sets) by the longest PART the handle can be given
-		 * -- max_push, or what push_checked cuts longer pushes into (36 s of air time, a third more in a test build): 64 items of private
-		 * areas per 1024-instant tile (the verify pass's workgroups take four tiles and an area of 256 each; the probe's 42 a tile), the
-		 * common area half of that again.  A 67 MS push at 2 MS/s keeps round 5's 131 072 + 65 536 items per channel (126 MB a set and
-		 * stream); a handle for pushes of a few MS 32 768 + 32 768 (42 MB). */
-		const long long jcap = 48LL * 84000;
-		const long long tiles_max = (VDL2_CARRY_FRAMES + std::min(jmax, jcap)) / K2A_TS + 2;
-		const unsigned priv = (unsigned)std::min<long long>(VDL2_ITEM_PRIV, std::max<long long>(32768, (64 * tiles_max + 4095) / 4096 * 4096));
-		h->item_priv = priv;
-		h->item_cap = priv + std::max(priv / 2, 32768u);	/* (the common area: what a stretch of sync words or a carrier sends past the private areas) */
-#ifdef VDL2_ITEMS_FULL_VALUES
-		h->item_priv = VDL2_ITEM_PRIV;
-		h->item_cap = VDL2_ITEM_CAP;
-#endif
-	}
-	const size_t dec_bytes = (size_t)S * (size_t)h->cap * VDL2_CS * sizeof(float2);
-	for (int r = 0; r < VDL2_NSET; ++r) {
-		HIPCHK(h, hipMalloc(&h->d_dec[r], dec_bytes));
-		HIPCHK(h, hipMemsetAsync(h->d_dec[r], 0, dec_bytes, h->stream));
-	}
-	HIPCHK(h, hipMalloc(&h->d_lo, (size_t)S * VDL2_CS * L * sizeof(float2)));
-	HIPCHK(h, hipMalloc(&h->d_lo_ext, (size_t)S * VDL2_CS * (L + 48) * sizeof(float2)));
-	HIPCHK(h, hipMalloc(&h->d_k1_tickets, (size_t)S * 21 * 8 * sizeof(unsigned)));
-	HIPCHK(h, hipMemsetAsync(h->d_k1_tickets, 0, (size_t)S * 21 * 8 * sizeof(unsigned), h->stream));
-	HIPCHK(h, hipMalloc(&h->d_ss, (size_t)S * sizeof(StreamState)));
-	HIPCHK(h, hipMalloc(&h->d_cs, (size_t)S * VDL2_CS * sizeof(ChanState)));
-	HIPCHK(h, hipMalloc(&h->d_cfg, (size_t)S * VDL2_CS * sizeof(ChanCfg)));
-	HIPCHK(h, hipMalloc(&h->d_pn, VDL2_PN_BITS));
-	for (int r = 0; r < VDL2_NRING; ++r) {
-		HIPCHK(h, hipMalloc(&h->d_recs[r], (size_t)h->rec_cap * sizeof(vdl2gpu_burst_t)));
-	}
-	HIPCHK(h, hipMalloc(&h->d_outc, 16 * sizeof(unsigned)));
-	HIPCHK(h, hipMemsetAsync(h->d_outc, 0, 16 * sizeof(unsigned), h->stream));
-	HIPCHK(h, hipStreamCreateWithPriority(&h->copy_stream, hipStreamNonBlocking, 0));
-	/* (HIP multiplexes its streams onto four hardware queues: a fifth stream shares one with another, and kernels that
-	 * were meant to run side by side then run one behind the other -- this handle makes exactly main, copy, resolver, payload;
-	 * host input adds one for its copies, which may share a queue with the record read-back) */
-	for (int r = 0; r < 2; ++r)
-		HIPCHK(h, hipEventCreateWithFlags(&h->k1_done[r], hipEventDisableTiming));
-	for (int r = 0; r < VDL2_NSET; ++r)
-		HIPCHK(h, hipEventCreateWithFlags(&h->k2_done[r], hipEventDisableTiming));
-	for (int r = 0; r < VDL2_NRING; ++r) {
-		for (int k = 0; k < 2; ++k)
-			HIPCHK(h, hipEventCreateWithFlags(&h->ring_done2[r][k], hipEventDisableTiming));
-		HIPCHK(h, hipEventCreateWithFlags(&h->in_read[r], hipEventDisableTiming));
-	}
-	{
-		int prio_lo = 0, prio_hi = 0;
-		HIPCHK(h, hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi));
-		HIPCHK(h, hipStreamCreateWithPriority(&h->fstream, hipStreamNonBlocking, prio_lo));	/* the back stage (main stream, high priority) is the shorter one: it goes first */
-	}
-	for (int r = 0; r < VDL2_NSET; ++r)
-		HIPCHK(h, hipEventCreateWithFlags(&h->f_done[r], hipEventDisableTiming));
-	HIPCHK(h, hipEventCreateWithFlags(&h->k1_ev, hipEventDisableTiming));
-	HIPCHK(h, hipEventCreateWithFlags(&h->f_tail, hipEventDisableTiming));
-	HIPCHK(h, hipStreamCreateWithFlags(&h->pay_stream, hipStreamNonBlocking));
-	HIPCHK(h, hipEventCreateWithFlags(&h->k2c_done, hipEventDisableTiming));
-	HIPCHK(h, hipEventCreateWithFlags(&h->pay_done, hipEventDisableTiming));
-	HIPCHK(h, hipEventCreateWithFlags(&h->verify_done, hipEventDisableTiming));
-	HIPCHK(h, hipEventCreateWithFlags(&h->k2f_done, hipEventDisableTiming));
-
-	for (int r = 0; r < VDL2_NSET; ++r)
-		HIPCHK(h, hipMalloc(&h->d_fmask[r], 16 * sizeof(unsigned)));
-	for (int r = 0; r < VDL2_NSET; ++r)
-		HIPCHK(h, hipMemsetAsync(h->d_fmask[r], 0, 16 * sizeof(unsigned), h->stream));
-	h->ctl_words = VDL2_CTL_WORDS((size_t)S * VDL2_CS);
-	for (int r = 0; r < VDL2_NSET; ++r)
-		HIPCHK(h, hipMalloc(&h->d_ctl[r], h->ctl_words * sizeof(unsigned)));
-	for (int r = 0; r < VDL2_NSET; ++r)
-		HIPCHK(h, hipMemsetAsync(h->d_ctl[r], 0, h->ctl_words * sizeof(unsigned), h->stream));
-	for (int r = 0; r < VDL2_NSET; ++r)
-		HIPCHK(h, hipMalloc(&h->d_cands[r], (size_t)S * VDL2_CS * VDL2_CAND_CAP * sizeof(Cand)));
-	for (int r = 0; r < VDL2_NSET; ++r)
-		HIPCHK(h, hipMalloc(&h->d_clusters[r], (size_t)S * VDL2_CS * VDL2_CAND_CAP * sizeof(Cluster)));
-	for (int r = 0; r < VDL2_NSET; ++r)
-		HIPCHK(h, hipMalloc(&h->d_clhead[r], (size_t)S * VDL2_CS * VDL2_CAND_CAP * sizeof(int2)));
-	h->stage_cap = (unsigned)S * VDL2_CS * VDL2_CAND_CAP * VDL2_CL_MAXB + 65536u;	/* static slots + dynamic tail */
-	for (int r = 0; r < VDL2_NSET; ++r)
-		HIPCHK(h, hipMalloc(&h->d_stage[r], (size_t)h->stage_cap * sizeof(BurstDesc)));
-	for (int r = 0; r < VDL2_NSET; ++r)
-		HIPCHK(h, hipMalloc(&h->d_sel_list[r], (size_t)S * VDL2_CS * VDL2_SEL_CAP * sizeof(unsigned)));
-	for (int r = 0; r < VDL2_NSET; ++r)
-		HIPCHK(h, hipMalloc(&h->d_sel_list2[r], (size_t)S * VDL2_CS * VDL2_SEL_CAP * sizeof(unsigned)));
-	for (int r = 0; r < VDL2_NSET; ++r)
-		HIPCHK(h, hipMalloc(&h->d_regs[r], (size_t)S * VDL2_CS * VDL2_REG_CAP * sizeof(int2)));
-	for (int r = 0; r < VDL2_NSET; ++r)
-		HIPCHK(h, hipMalloc(&h->d_segs[r], (size_t)S * VDL2_CS * VDL2_SEG_CAP * sizeof(Seg)));
-	for (int r = 0; r < VDL2_NSET; ++r)
-		HIPCHK(h, hipMalloc(&h->d_fail[r], (size_t)S * VDL2_CS * sizeof(int)));
-	for (int r = 0; r < VDL2_NSET; ++r)
-		HIPCHK(h, hipMalloc(&h->d_redo[r], (size_t)S * VDL2_CS * sizeof(int)));
-	for (int r = 0; r < VDL2_NSET; ++r)
-		HIPCHK(h, hipMalloc(&h->d_cs_out[r], (size_t)S * VDL2_CS * sizeof(ChanState)));
-	for (int r = 0; r < VDL2_NSET; ++r)
-		HIPCHK(h, hipMalloc(&h->d_skey[r], (size_t)S * VDL2_CS * VDL2_CAND_CAP * sizeof(int)));
-	for (int r = 0; r < VDL2_NSET; ++r)
-		HIPCHK(h, hipMalloc(&h->d_sidx[r], (size_t)S * VDL2_CS * VDL2_CAND_CAP * sizeof(unsigned short)));
-	for (int r = 0; r < VDL2_NSET; ++r)
-		HIPCHK(h, hipMalloc(&h->d_prim[r], (size_t)S * VDL2_CS * VDL2_CAND_CAP * sizeof(unsigned short)));
-	for (int r = 0; r < VDL2_NSET; ++r)
-		HIPCHK(h, hipMalloc(&h->d_seeds[r], (size_t)S * VDL2_CS * VDL2_CAND_CAP * sizeof(int)));
-	for (int r = 0; r < VDL2_NSET; ++r) {
-		HIPCHK(h, hipMalloc(&h->d_onchain[r], (size_t)S * VDL2_CS * VDL2_CAND_CAP));
-		HIPCHK(h, hipMalloc(&h->d_slog[r], (size_t)S * VDL2_CS * VDL2_SLOG_CAP * sizeof(K2Slog)));
-		HIPCHK(h, hipMalloc(&h->d_win[r], (size_t)S * VDL2_CS * VDL2_WIN_CAP * sizeof(int2)));
-	}
-	for (int r = 0; r < VDL2_NSET; ++r)
-#ifdef VDL2_ITEMS_ALLOC_FULL
-		HIPCHK(h, hipMalloc(&h->d_items[r], (size_t)S * VDL2_CS * VDL2_ITEM_CAP * sizeof(K2aItem)));
-#else
-		HIPCHK(h, hipMalloc(&h->d_items[r], (size_t)S * VDL2_CS * h->item_cap * sizeof(K2aItem)));
-#endif
 	/* every environment knob is read here, once */
 	auto env_int = [](const char *name, int dflt) { const char *v = getenv(name); return v ? atoi(v) : dflt; };
 	h->full_scan = ((cfg.flags & VDL2GPU_F_FULLSCAN) || getenv("VDL2GPU_FULL_SCAN")) ? 1 : 0;
@@ -897,10 +829,10 @@ static int create_impl(vdl2gpu_t *h)
 	 * density is known, 8.4 s -- a saturated channel (250 candidates a second) fills half of the tables in that long. */
 	h->split_unit = ((cfg.flags & VDL2GPU_F_RTL_QUIRK) || h->sdrclk != 500 || h->L != 80) ? 32768 : K1F_PER_IN;
 	/* other rates: whole periods of the dump schedule (4 * SDRCLK samples), so that a part that starts on a schedule boundary is ONE
-	 * k1_pp launch like a whole push (push_impl: whole_pp) -- unless the quirk wants whole 32768-sample blocks */
+	 * k1_pp launch like a whole push (choose_k1: whole_pp) -- unless the quirk wants whole 32768-sample blocks */
 	if (!(cfg.flags & VDL2GPU_F_RTL_QUIRK) && h->split_unit == 32768 && (4 * h->sdrclk) % h->L == 0 && ((size_t)4 * h->sdrclk * h->sample_bytes) % 16 == 0)
 		h->split_unit = (size_t)4 * h->sdrclk * ((32768 + (size_t)4 * h->sdrclk - 1) / ((size_t)4 * h->sdrclk));	/* (about the block's size) */
-	h->split_default = (size_t)(36.0 * (double)h->cfg.sdrinrate) / h->split_unit * h->split_unit;
+	h->split_default = (size_t)((double)PART_SECONDS * (double)h->cfg.sdrinrate) / h->split_unit * h->split_unit;
 	{
 		/* the verify pass maps one workgroup to K2A_VRUN tiles and the item list has room for VDL2_MAXWG private areas: a part
 		 * must not have more tiles than that covers (36 s of air time are 3003 tiles, the bound is 4088) */
@@ -911,7 +843,7 @@ static int create_impl(vdl2gpu_t *h)
 	h->split_samples = std::max(h->split_unit, (size_t)(8.4 * (double)h->cfg.sdrinrate) / h->split_unit * h->split_unit);
 #ifdef VDL2GPU_TESTHOOKS
 	if (getenv("VDL2GPU_SPLIT_SAMPLES")) {
-		h->split_samples = std::min((size_t)atoll(getenv("VDL2GPU_SPLIT_SAMPLES")), h->split_default * 4 / 3);	/* (still inside the verify grid's bound) */
+		h->split_samples = std::min((size_t)atoll(getenv("VDL2GPU_SPLIT_SAMPLES")), h->split_default * TEST_PART_NUM / TEST_PART_DEN);	/* (still inside the verify grid's bound) */
 		h->knob.split_fixed = true;
 	}
 #endif
@@ -919,33 +851,92 @@ static int create_impl(vdl2gpu_t *h)
 	h->repair_rounds = env_int("VDL2GPU_REPAIR_ROUNDS", h->rounds_floor);
 	h->force_serial = (cfg.flags & VDL2GPU_F_SERIAL) ? 1 : 0;
 	h->quirk = (cfg.flags & VDL2GPU_F_RTL_QUIRK) ? 1 : 0;
+	{
+		/* The item lists (what passes a scan's first screen: 80 bytes an item, three sets) by the longest PART the handle can be given
+		 * -- max_push, or what push_checked cuts longer pushes into (36 s of air time, a third more in a test build): 64 items of private
+		 * areas per 1024-instant tile (the verify pass's workgroups take four tiles and an area of 256 each; the probe's 42 a tile), the
+		 * common area half of that again.  A 67 MS push at 2 MS/s keeps round 5's 131 072 + 65 536 items per channel (126 MB a set and
+		 * stream); a handle for pushes of a few MS 32 768 + 32 768 (42 MB). */
+		const long long jmax = (long long)((21ull * cfg.max_push) / (unsigned)h->sdrclk) + 2;
+		const long long jcap = (long long)PART_SECONDS * 84000 * TEST_PART_NUM / TEST_PART_DEN;	/* (84000 frames a second) */
+		const long long tiles_max = (VDL2_CARRY_FRAMES + std::min(jmax, jcap)) / K2A_TS + 2;
+		const unsigned priv = (unsigned)std::min<long long>(VDL2_ITEM_PRIV, std::max<long long>(32768, (64 * tiles_max + 4095) / 4096 * 4096));
+		h->item_priv = priv;
+		h->item_cap = priv + std::max(priv / 2, 32768u);	/* (the common area: what a stretch of sync words or a carrier sends past the private areas) */
+	}
+	h->k1_tbase.assign((size_t)S * 8, 0u);
+	h->cap = plane_frames(cfg.max_push, (unsigned)h->sdrclk);	/* planes start on 128-byte lines */
+	const size_t dec_bytes = (size_t)S * (size_t)h->cap * VDL2_CS * sizeof(float2);
+	for (int r = 0; r < VDL2_NSET; ++r) {
+		DEV_ALLOC(h, h->d_dec[r], dec_bytes);
+		HIPCHK(h, hipMemsetAsync(h->d_dec[r], 0, dec_bytes, h->stream));
+	}
+	DEV_ALLOC(h, h->d_lo, (size_t)S * VDL2_CS * L * sizeof(float2));
+	DEV_ALLOC(h, h->d_lo_ext, (size_t)S * VDL2_CS * (L + 48) * sizeof(float2));
+	DEV_ALLOC(h, h->d_k1_tickets, (size_t)S * 21 * 8 * sizeof(unsigned));
+	HIPCHK(h, hipMemsetAsync(h->d_k1_tickets, 0, (size_t)S * 21 * 8 * sizeof(unsigned), h->stream));
+	DEV_ALLOC(h, h->d_ss, (size_t)S * sizeof(StreamState));
+	DEV_ALLOC(h, h->d_cs, (size_t)S * VDL2_CS * sizeof(ChanState));
+	DEV_ALLOC(h, h->d_cfg, (size_t)S * VDL2_CS * sizeof(ChanCfg));
+	DEV_ALLOC(h, h->d_pn, VDL2_PN_BITS);
+	for (OutRing &rg : h->ring)
+		DEV_ALLOC(h, rg.d_recs, (size_t)h->rec_cap * sizeof(vdl2gpu_burst_t));
+	DEV_ALLOC(h, h->d_outc, 16 * sizeof(unsigned));
+	HIPCHK(h, hipMemsetAsync(h->d_outc, 0, 16 * sizeof(unsigned), h->stream));
+	/* (HIP multiplexes its streams onto four hardware queues: a fifth stream shares one with another, and kernels that
+	 * were meant to run side by side then run one behind the other -- this handle makes exactly main, copy, resolver, payload;
+	 * host input adds one for its copies, which may share a queue with the record read-back) */
+	const int prio_normal = 0;
+	NEW_STREAM(h, h->copy_stream, &prio_normal);
+	for (int r = 0; r < 2; ++r)
+		NEW_EVENT(h, h->k1_done[r]);
+	for (TableSet &t : h->set)
+		NEW_EVENT(h, t.k2_done);
+	for (OutRing &rg : h->ring) {
+		for (int k = 0; k < 2; ++k)
+			NEW_EVENT(h, rg.done2[k]);
+		NEW_EVENT(h, rg.in_read);
+	}
+	NEW_STREAM(h, h->fstream, &prio_lo);	/* the back stage (main stream, high priority) is the shorter one: it goes first */
+	for (TableSet &t : h->set)
+		NEW_EVENT(h, t.f_done);
+	NEW_EVENT(h, h->k1_ev);
+	NEW_EVENT(h, h->f_tail);
+	NEW_STREAM(h, h->pay_stream);
+	NEW_EVENT(h, h->k2c_done);
+	NEW_EVENT(h, h->pay_done);
+	NEW_EVENT(h, h->verify_done);
+	NEW_EVENT(h, h->k2f_done);
+	h->ctl_words = VDL2_CTL_WORDS((size_t)S * VDL2_CS);
+	h->stage_cap = (unsigned)S * VDL2_CS * VDL2_CAND_CAP * VDL2_CL_MAXB + 65536u;	/* static slots + dynamic tail */
+	TRY(alloc_sets(h));
 	h->pin_recs = std::min<unsigned>(h->rec_cap, 8192u);
-	HIPCHK(h, hipHostMalloc(&h->h_pin, (size_t)h->pin_recs * sizeof(vdl2gpu_burst_t), hipHostMallocDefault));
+	HOST_ALLOC(h, h->h_pin, (size_t)h->pin_recs * sizeof(vdl2gpu_burst_t), hipHostMallocDefault);
 	h->slab_cap = std::min<unsigned>(h->rec_cap, 16384u);	/* 34 MB of page-locked memory per slab at most (four slabs); a push with more bursts takes the bounce buffer for the rest */
 #ifdef VDL2GPU_TESTHOOKS
 	h->slab_cap = std::max(1u, std::min<unsigned>(h->slab_cap, (unsigned)env_int("VDL2GPU_SLAB_CAP", (int)h->slab_cap)));	/* (tests: force the bounce path) */
 #endif
-	for (int r = 0; r < VDL2_NSLAB; ++r) {
-		HIPCHK(h, hipHostMalloc(&h->h_slab[r], (size_t)h->slab_cap * sizeof(vdl2gpu_burst_t), hipHostMallocMapped));
-		HIPCHK(h, hipHostGetDevicePointer((void **)&h->d_slab[r], h->h_slab[r], 0));
+	/* the output rings and the slabs: the records, and beside them the side columns the flags ask for */
+	h->col_on[COL_LEVEL] = (cfg.flags & VDL2GPU_F_LEVELS) != 0;
+	h->col_on[COL_SOFT] = (cfg.flags & VDL2GPU_F_SOFT_RS) != 0;
+	h->frames_on = (cfg.flags & VDL2GPU_F_FRAMES) != 0;
+	if (h->frames_on)
+		h->frame_cap = h->rec_cap * K4_SLOT + (4u << 20);	/* bytes: a slot per record, and the arena (see K4Params) */
+	for (Slab &sl : h->slab) {
+		HOST_ALLOC(h, sl.h_recs, (size_t)h->slab_cap * sizeof(vdl2gpu_burst_t), hipHostMallocMapped);
+		HIPCHK(h, hipHostGetDevicePointer((void **)&sl.d_recs, sl.h_recs, 0));
 	}
-	h->soft_on = (cfg.flags & VDL2GPU_F_SOFT_RS) != 0;
-	if (h->soft_on) {
-		for (int r = 0; r < VDL2_NRING; ++r)
-			HIPCHK(h, hipMalloc(&h->d_soft[r], (size_t)h->rec_cap * sizeof(vdl2gpu_soft_t)));
-		for (int r = 0; r < VDL2_NSLAB; ++r) {
-			HIPCHK(h, hipHostMalloc(&h->h_sslab[r], (size_t)h->slab_cap * sizeof(vdl2gpu_soft_t), hipHostMallocMapped));
-			HIPCHK(h, hipHostGetDevicePointer((void **)&h->d_sslab[r], h->h_sslab[r], 0));
+	for (int k = 0; k < VDL2_NCOL; ++k) {
+		if (!h->col_on[k])
+			continue;
+		for (OutRing &rg : h->ring)
+			DEV_ALLOC(h, rg.d_side[k], (size_t)h->rec_cap * col_bytes[k]);
+		for (Slab &sl : h->slab) {
+			HOST_ALLOC(h, sl.h_side[k], (size_t)h->slab_cap * col_bytes[k], hipHostMallocMapped);
+			HIPCHK(h, hipHostGetDevicePointer(&sl.d_side[k], sl.h_side[k], 0));
 		}
 	}
-	h->levels_on = (cfg.flags & VDL2GPU_F_LEVELS) != 0;
-	if (h->levels_on) {
-		for (int r = 0; r < VDL2_NRING; ++r)
-			HIPCHK(h, hipMalloc(&h->d_levels[r], (size_t)h->rec_cap * sizeof(vdl2gpu_level_t)));
-		for (int r = 0; r < VDL2_NSLAB; ++r) {
-			HIPCHK(h, hipHostMalloc(&h->h_lslab[r], (size_t)h->slab_cap * sizeof(vdl2gpu_level_t), hipHostMallocMapped));
-			HIPCHK(h, hipHostGetDevicePointer((void **)&h->d_lslab[r], h->h_lslab[r], 0));
-		}
+	if (h->col_on[COL_LEVEL]) {
 		/* K = (FS * sum_j mflt[4j])^2: the channeliser's integrate-and-dump AVERAGES the input samples of an output (D /= nf,
 		 * d8psk.c:378), so a full-scale tone at the channel centre leaves it at FS, and the filter's gain there is the sum of the
 		 * taps of one sub-phase */
@@ -959,26 +950,24 @@ static int create_impl(vdl2gpu_t *h)
 		const double a = fs * g;
 		h->lev_k = a * a;
 	}
-	HIPCHK(h, hipHostMalloc(&h->h_pin_cnt, 32 * VDL2_NRING * sizeof(unsigned), hipHostMallocMapped));
+	HOST_ALLOC(h, h->h_pin_cnt, 32 * VDL2_NRING * sizeof(unsigned), hipHostMallocMapped);
 	memset(h->h_pin_cnt, 0, 32 * VDL2_NRING * sizeof(unsigned));
-	h->frames_on = (cfg.flags & VDL2GPU_F_FRAMES) != 0;
-	HIPCHK(h, hipMalloc(&h->d_k4tab, K4_TABW * sizeof(unsigned)));
+	DEV_ALLOC(h, h->d_k4tab, K4_TABW * sizeof(unsigned));
 	hipLaunchKernelGGL(k4_tables, dim3(1), dim3(64), 0, h->stream, h->d_k4tab);
 	HIPCHK(h, hipGetLastError());
 	if (h->frames_on) {
-		h->frame_cap = h->rec_cap * K4_SLOT + (4u << 20);	/* bytes: a slot per record, and the arena (see K4Params) */
-		for (int r = 0; r < VDL2_NRING; ++r)
-			HIPCHK(h, hipMalloc((void **)&h->d_frames[r], (size_t)h->frame_cap));
-		HIPCHK(h, hipMalloc(&h->d_fcnt, 4 * VDL2_NRING * sizeof(unsigned)));
+		for (OutRing &rg : h->ring)
+			DEV_ALLOC(h, rg.d_frames, (size_t)h->frame_cap);
+		DEV_ALLOC(h, h->d_fcnt, 4 * VDL2_NRING * sizeof(unsigned));
 		HIPCHK(h, hipMemsetAsync(h->d_fcnt, 0, 4 * VDL2_NRING * sizeof(unsigned), h->stream));
 	}
 	HIPCHK(h, hipHostGetDevicePointer((void **)&h->d_pin_cnt, h->h_pin_cnt, 0));
-	HIPCHK(h, hipMalloc(&h->d_dbg, 64 * sizeof(unsigned long long)));
+	DEV_ALLOC(h, h->d_dbg, 64 * sizeof(unsigned long long));
 	HIPCHK(h, hipMemsetAsync(h->d_dbg, 0, 64 * sizeof(unsigned long long), h->stream));
 	if (cfg.flags & VDL2GPU_F_DEBUG_HEADS) {
 		h->headtap_cap = 1u << 18;
-		HIPCHK(h, hipMalloc(&h->d_headtap, (size_t)h->headtap_cap * sizeof(HeadTap)));
-		HIPCHK(h, hipMalloc(&h->d_headtap_n, sizeof(unsigned)));
+		DEV_ALLOC(h, h->d_headtap, (size_t)h->headtap_cap * sizeof(HeadTap));
+		DEV_ALLOC(h, h->d_headtap_n, sizeof(unsigned));
 		HIPCHK(h, hipMemsetAsync(h->d_headtap_n, 0, sizeof(unsigned), h->stream));
 	}
 
@@ -1015,8 +1004,10 @@ static int create_impl(vdl2gpu_t *h)
 		for (int i = 0; i < 8; ++i)
 			if (25 + 8 * b + i < pn.size())
 				pn8[b] |= (uint8_t)(pn[25 + 8 * b + i] << i);
-	HIPCHK(h, hipMalloc(&h->d_pn8, pn8.size()));
+	DEV_ALLOC(h, h->d_pn8, pn8.size());
 	HIPCHK(h, hipMemcpyAsync(h->d_pn8, pn8.data(), pn8.size(), hipMemcpyHostToDevice, h->stream));
+
+	fill_set_params(h);
 
 	/* canonical start state: everything zero except initD8psk's perr=100 (d8psk.c:28-37);
 	 * 16 zero frames stand for the empty Inbuff ring */
@@ -1097,7 +1088,7 @@ static int get_events(vdl2gpu_t *h, PushTiming &pt)
 		return VDL2GPU_OK;
 	}
 	for (auto &e : pt.e)
-		HIPCHK(h, hipEventCreate(&e));
+		NEW_EVENT(h, e, true);
 	return VDL2GPU_OK;
 }
 
@@ -1109,11 +1100,12 @@ static int harvest_timing(vdl2gpu_t *h)
 			/* VDL2GPU_STAGE_DUMP=1: where every stage of every push began and ended on the GPU's clock, in us since the handle's
 			 * first push -- a Gantt chart of the pipeline as it runs WITHOUT a profiler (under rocprofv3 the calling thread is
 			 * what the streams wait for).  e0 K1 begins | e1 K1 ends | e10 scan begins | e4 front ends | e2 clusters begin |
-			 * e3 = e13 clusters end | e14 resolver ends | e12 verify begins | e15 verify ends | e5 rounds end | e6 commit..export end | e7 tail ends */
-			/* (VDL2GPU_STAGE_DUMP only) e23 resolver begins (the previous push's commit has been seen) | e16 tail begins (the verify pass has
-			 * been seen on the tail's stream) | e17 merge ends | e18 round's resolver ends | e5 rounds end | e20 commit ends | e21 second
-			 * payload pass ends | e22 export ends */
-			static const int order[] = {0, 1, 10, 4, 2, 13, 23, 14, 12, 15, 16, 17, 18, 5, 20, 21, 22, 6, 7};
+			 * e3 = e13 clusters end | e23 resolver begins (the previous push's commit has been seen) | e14 resolver ends | e12 verify
+			 * begins | e15 verify ends | e16 tail begins (the verify pass has been seen on the tail's stream) | e18 local repair ends |
+			 * e5 rounds end | e20 commit ends | e21 second payload pass ends | e22 export ends | e6 block path ends | e7 tail ends
+			 * (see PushTiming.  An event a push does not record keeps the time of the pooled event's last use: e18 on a push
+			 * that takes the serial path) */
+			static const int order[] = {0, 1, 10, 4, 2, 13, 23, 14, 12, 15, 16, 18, 5, 20, 21, 22, 6, 7};
 			fprintf(stderr, "vdl2gpu stage dump push %llu:", (unsigned long long)pt.index);
 			for (int k : order) {
 				float t = -1.0f;
@@ -1222,9 +1214,18 @@ static ScanDrain launch_scan(int which, const K2Params &k2, dim3 grid, hipStream
 	return d;
 }
 
-template <int FMT> static void launch_k1(const K1Params &p, dim3 grid, size_t smem, hipStream_t st)
+/* A sample format as a kernel instantiation: f is called with std::integral_constant<int, FMT> of the handle's format, and launches
+ * kernel<decltype(F)::value>.  (What else knows the formats: fmt_bytes, and the full scale of a level record in create_impl.) */
+template <class F> static void with_fmt(int fmt, F &&f)
 {
-	hipLaunchKernelGGL(k1_channelise<FMT>, grid, dim3(K1_THREADS), smem, st, p);
+	switch (fmt) {
+	case VDL2GPU_FMT_CU8: f(std::integral_constant<int, VDL2GPU_FMT_CU8>{}); break;
+	case VDL2GPU_FMT_CS16: f(std::integral_constant<int, VDL2GPU_FMT_CS16>{}); break;
+	case VDL2GPU_FMT_CF32: f(std::integral_constant<int, VDL2GPU_FMT_CF32>{}); break;
+	case VDL2GPU_FMT_CS8: f(std::integral_constant<int, VDL2GPU_FMT_CS8>{}); break;
+	case VDL2GPU_FMT_S16R: f(std::integral_constant<int, VDL2GPU_FMT_S16R>{}); break;
+	default: f(std::integral_constant<int, VDL2GPU_FMT_F32R>{}); break;
+	}
 }
 
 static int push_impl(vdl2gpu_t *h, const void *iq, size_t nsamples, size_t stream_stride_bytes, int memkind, bool wait_copy);
@@ -1283,12 +1284,12 @@ extern "C" int vdl2gpu_ring_init(vdl2gpu_t *h, size_t slot_samples, int nslots)
 	HIPCHK(h, hipSetDevice(h->cfg.device));
 	h->ring_slot_samples = slot_samples;
 	h->ring_slot_bytes = slot_samples * h->sample_bytes * (size_t)h->S;
-	HIPCHK(h, hipHostMalloc(&h->ring_host, h->ring_slot_bytes * (size_t)nslots, hipHostMallocDefault));
+	HOST_ALLOC(h, h->ring_host, h->ring_slot_bytes * (size_t)nslots, hipHostMallocDefault);
 	h->ring_nslots = nslots;
 	h->ring_copied.resize((size_t)nslots);
 	h->ring_inflight.assign((size_t)nslots, 0);
 	for (int i = 0; i < nslots; ++i)
-		HIPCHK(h, hipEventCreateWithFlags(&h->ring_copied[(size_t)i], hipEventDisableTiming));
+		NEW_EVENT(h, h->ring_copied[(size_t)i]);
 	return VDL2GPU_OK;
 }
 
@@ -1345,7 +1346,7 @@ extern "C" int vdl2gpu_ring_commit(vdl2gpu_t *h, size_t nsamples)
 /* the payload kernel of the handle's flags: each optional pass is a kernel variant of its own (register pressure) */
 static inline void (*k2d_kernel(const vdl2gpu_t *h))(K2Params)
 {
-	return h->soft_on ? (h->levels_on ? k2d_payload_lev_soft : k2d_payload_soft) : (h->levels_on ? k2d_payload_lev : k2d_payload);
+	return h->col_on[COL_SOFT] ? (h->col_on[COL_LEVEL] ? k2d_payload_lev_soft : k2d_payload_soft) : (h->col_on[COL_LEVEL] ? k2d_payload_lev : k2d_payload);
 }
 
 static int enqueue_back(vdl2gpu_t *h)
@@ -1363,7 +1364,7 @@ static int enqueue_back(vdl2gpu_t *h)
 	const dim3 gch((unsigned)h->C, (unsigned)GS);
 	hipStream_t rs = h->stream;
 	if (h->back.two_streams)
-		HIPCHK(h, hipStreamWaitEvent(rs, h->f_done[par], 0));
+		HIPCHK(h, hipStreamWaitEvent(rs, h->set[par].f_done, 0));
 	/* the cluster kernel needs nothing of the previous push's result either, but it is wide, and the stages are better
 	 * balanced with it here: FRONT = channeliser + scan, BACK = clusters + resolver + verify */
 	if (staged)
@@ -1390,7 +1391,7 @@ static int enqueue_back(vdl2gpu_t *h)
 	 * a repaired selection in a second pass behind the rounds): decode the payloads beside the verify pass
 	 * instead of behind it. */
 	const bool spec = !h->full_scan && !serial && h->S * VDL2_CS <= 512;
-	h->ring_spec[ring] = spec;
+	h->ring[ring].spec = spec;
 	if (spec)
 		HIPCHK(h, hipEventRecord(h->k2c_done, rs));
 	/* The payload decode beside the verify pass: on the copy stream (a hardware queue of its own), so that the push's TAIL on the
@@ -1398,7 +1399,7 @@ static int enqueue_back(vdl2gpu_t *h)
 	 * dependency -- starts when the verify pass ends, not when this latency-bound kernel has found CUs between the verify pass's
 	 * workgroups and finished.  The repair rounds write a selection of their own (K2Params.sel_list2), so nothing the decode
 	 * reads changes under it; the tail waits for it only where it needs its records: in front of the second payload pass and the
-	 * export.  (VDL2GPU_PAY_TAIL=1: on the payload stream in front of the tail, round 3's arrangement.) */
+	 * export. */
 	hipStream_t ps = h->copy_stream;	/* (four hardware queues: the copy stream has one job) */
 	if (spec) {
 		HIPCHK(h, hipStreamWaitEvent(ps, h->k2c_done, 0));
@@ -1424,8 +1425,8 @@ static int enqueue_back(vdl2gpu_t *h)
 		HIPCHK(h, hipEventRecord(h->verify_done, h->stream));
 		HIPCHK(h, hipStreamWaitEvent(ts, h->verify_done, 0));
 	}
-	if (h->tail_prev && h->tail_prev != ts && h->k2_rec[(par + VDL2_NSET - 1) % VDL2_NSET])	/* tails follow each other (running totals, StreamState) */
-		HIPCHK(h, hipStreamWaitEvent(ts, h->k2_done[(par + VDL2_NSET - 1) % VDL2_NSET], 0));
+	if (h->tail_prev && h->tail_prev != ts && h->set[(par + VDL2_NSET - 1) % VDL2_NSET].k2_rec)	/* tails follow each other (running totals, StreamState) */
+		HIPCHK(h, hipStreamWaitEvent(ts, h->set[(par + VDL2_NSET - 1) % VDL2_NSET].k2_done, 0));
 	h->tail_prev = ts;
 	if (staged && h->stage_dump)
 		HIPCHK(h, hipEventRecord(pt.e[16], ts));
@@ -1504,7 +1505,7 @@ static int enqueue_back(vdl2gpu_t *h)
 	h->k2f_rec = true;
 	if (staged && h->stage_dump)
 		HIPCHK(h, hipEventRecord(pt.e[20], ts));
-	if (h->ring_spec[ring]) {
+	if (h->ring[ring].spec) {
 		if (ts != ps)
 			HIPCHK(h, hipStreamWaitEvent(ts, h->pay_done, 0));	/* the export needs the first pass's records, K3 publishes the record count */
 		if (!h->full_scan && !serial) {
@@ -1525,17 +1526,17 @@ static int enqueue_back(vdl2gpu_t *h)
 		 * a latency-bound kernel like this one and the next push's scan slow each other down by
 		 * more than the overlap saves. */
 		K4Params k4{};
-		k4.recs = h->d_recs[ring];
+		k4.recs = h->ring[ring].d_recs;
 		k4.nrecs_dev = h->d_outc + 2 * ring;
 		k4.rec_cap = h->rec_cap;
-		k4.frames = h->d_frames[ring];
+		k4.frames = h->ring[ring].d_frames;
 		k4.nframes = h->d_fcnt + 4 * ring;
 		k4.frame_cap = h->frame_cap;
 		k4.compact = 1;
 		k4.tabs = h->d_k4tab;
-		k4.fmask = h->ring_spec[ring] ? h->d_fmask[par] : nullptr;
+		k4.fmask = h->ring[ring].spec ? h->set[par].k2.fmask : nullptr;
 		k4.dbg = h->knob.debug_counters ? h->d_dbg : nullptr;
-		k4.soft = h->d_soft[ring];	/* (nullptr without VDL2GPU_F_SOFT_RS: the reference's block path) */
+		k4.soft = h->ring[ring].soft();	/* (nullptr without VDL2GPU_F_SOFT_RS: the reference's block path) */
 		hipLaunchKernelGGL(k4_frames, dim3((unsigned)h->n_cu * 16), dim3(K4_NT), 0, ts, k4);
 		HIPCHK(h, hipGetLastError());
 	}
@@ -1551,23 +1552,23 @@ static int enqueue_back(vdl2gpu_t *h)
 		k3.ss = h->d_ss;
 		k3.cs = h->d_cs;
 		k3.outc = h->d_outc;
-		k3.fmask = h->d_fmask[par];
+		k3.fmask = h->set[par].k2.fmask;
 		k3.fcnt = h->frames_on ? h->d_fcnt + 4 * ring : nullptr;
 		k3.host_cnt = h->d_pin_cnt + 32 * ring;
 		k3.ring = ring;
-		k3.ctl = h->d_ctl[par];
+		k3.ctl = h->set[par].k2.ctl;
 		k3.nstreams = h->S;
 		{
 			/* the push's records go to the host by the GPU's own hand: page-locked memory, coalesced 8-byte stores */
 			KExportParams ke{};
-			ke.recs = h->d_recs[ring];
+			ke.recs = h->ring[ring].d_recs;
 			ke.count = h->d_outc + 2 * ring;
-			ke.dst = h->d_slab[h->back.slab];
+			ke.dst = h->slab[h->back.slab].d_recs;
 			ke.cap = std::min(h->slab_cap, h->rec_cap);
-			ke.lev = h->d_levels[ring];	/* (nullptr without VDL2GPU_F_LEVELS) */
-			ke.ldst = h->d_lslab[h->back.slab];
-			ke.soft = h->d_soft[ring];	/* (nullptr without VDL2GPU_F_SOFT_RS) */
-			ke.sdst = h->d_sslab[h->back.slab];
+			ke.lev = h->ring[ring].levels();	/* (nullptr without VDL2GPU_F_LEVELS) */
+			ke.ldst = h->slab[h->back.slab].d_levels();
+			ke.soft = h->ring[ring].soft();	/* (nullptr without VDL2GPU_F_SOFT_RS) */
+			ke.sdst = h->slab[h->back.slab].d_soft();
 			hipLaunchKernelGGL(k_export_records, dim3((unsigned)h->n_cu), dim3(256), 0, ts, ke);
 			HIPCHK(h, hipGetLastError());
 			if (staged && h->stage_dump)
@@ -1578,13 +1579,400 @@ static int enqueue_back(vdl2gpu_t *h)
 	}
 	if (staged)
 		HIPCHK(h, hipEventRecord(pt.e[7], ts));
-	HIPCHK(h, hipEventRecord(h->k2_done[par], ts));
-	h->k2_rec[par] = true;
-	h->ring_ev[ring] ^= 1;
-	HIPCHK(h, hipEventRecord(h->ring_done(ring), ts));
+	HIPCHK(h, hipEventRecord(h->set[par].k2_done, ts));
+	h->set[par].k2_rec = true;
+	h->ring[ring].ev ^= 1;
+	HIPCHK(h, hipEventRecord(h->ring[ring].done(), ts));
 	return VDL2GPU_OK;
 }
 
+/* ---- the stages of a push, in the order push_impl runs them ---- */
+
+/* Where the channeliser reads a push's samples: the caller's device buffer as it is, or -- host samples -- one of the two
+ * staging buffers in HBM, filled on a stream of their own. */
+struct Input {
+	const void *src;
+	size_t stride;
+	bool staged;
+};
+
+static int stage_input(vdl2gpu_t *h, const void *iq, size_t nsamples, size_t stream_stride_bytes, int memkind, bool wait_copy, int stg, Input &in)
+{
+	in = Input{ iq, stream_stride_bytes, false };
+	if (memkind == VDL2GPU_MEM_DEVICE)
+		return VDL2GPU_OK;
+	if (memkind != VDL2GPU_MEM_HOST)
+		return VDL2GPU_EINVAL;
+	const size_t per = nsamples * h->sample_bytes;
+	const size_t need = per * (size_t)h->S;
+	if (!h->in_stream) {
+		NEW_STREAM(h, h->in_stream);
+		for (int i = 0; i < 2; ++i)
+			NEW_EVENT(h, h->raw_copied[i]);
+	}
+	if (need > h->raw_bytes[stg]) {
+		HIPCHK(h, hipStreamSynchronize(h->fstream));
+		HIPCHK(h, hipStreamSynchronize(h->stream));
+		HIPCHK(h, hipStreamSynchronize(h->pay_stream));
+		HIPCHK(h, hipStreamSynchronize(h->in_stream));
+		dev_release(h, h->d_raw[stg]);
+		h->d_raw[stg] = nullptr;
+		h->raw_bytes[stg] = 0;
+		DEV_ALLOC(h, h->d_raw[stg], need);
+		h->raw_bytes[stg] = need;
+	}
+	/* the channeliser of the push before last has read this buffer */
+	if (h->k1_rec[stg])
+		HIPCHK(h, hipStreamWaitEvent(h->in_stream, h->k1_done[stg], 0));
+	for (int s = 0; s < h->S; ++s)
+		HIPCHK(h, hipMemcpyAsync((char *)h->d_raw[stg] + (size_t)s * per,
+					 (const char *)iq + (size_t)s * stream_stride_bytes, per,
+					 hipMemcpyHostToDevice, h->in_stream));
+	HIPCHK(h, hipEventRecord(h->raw_copied[stg], h->in_stream));
+	if (wait_copy)
+		HIPCHK(h, hipEventSynchronize(h->raw_copied[stg]));
+	in = Input{ h->d_raw[stg], per, true };
+	return VDL2GPU_OK;
+}
+
+/* push-relative index of the last input sample of output j of a push that starts at c0 of the 21/SDRCLK clock */
+static inline long long wend_abs(long long j, int sdrclk, int c0)
+{
+	return ((j + 1) * (long long)sdrclk - c0 + 20) / 21 - 1;
+}
+
+/* Which channeliser kernels a push takes -- arithmetic on the handle's constants, the push's place in the schedule and where its
+ * samples lie; nothing is launched here.  K1_FAST at SDRCLK 500 with L = 80 only; K1_PP where whole periods of the dump schedule
+ * are whole LO tables and whole 16-byte pieces; the general kernel for everything else, and for the first and the last
+ * (super)period of a push the other two do not take as a whole. */
+enum { K1_GENERAL, K1_PP, K1_FAST };
+struct K1Choice {
+	int kind;
+	bool whole;		/* the kernel takes all of the push: no general launch at either end */
+	long long per_lo;	/* its first (super)period: 0 if whole, else 1 */
+	long long sbase0;	/* K1_PP: push-relative index of the first sample of period per_lo */
+	int d;			/* K1_PP: samples between the 16-byte boundary below that sample and the sample */
+};
+static K1Choice choose_k1(const vdl2gpu_t *h, int c0, int64_t J, size_t nsamples, const void *src, size_t stride)
+{
+	const K1Choice general{ K1_GENERAL, false, 0, 0, 0 };
+	K1Choice c = general;
+	/* whole periods of the schedule (4*SDRCLK inputs = 84 outputs, the LO table a whole number of times:
+	 * SDRINRATE = 4000*SDRCLK, air.c:138) on the period-parallel kernel; the first period (carried partial
+	 * window) and the tail on the general one */
+	const long long periods = J / K1P_PER_OUT;
+	const int per_in = 4 * h->sdrclk;
+	if (!(per_in % h->L == 0 && periods >= 4 && !h->quirk && !h->knob.no_k1_fast &&
+	      std::min(K1P_CH, h->maxwin) <= h->L))	/* k1_pp steps its LO index by a piece (<= a chunk, <= a window) and wraps it once */
+		return general;
+	/* a push that starts on a window boundary of the schedule (nothing carried in) and is a whole number of periods (nothing
+	 * carried out) needs no general launch at either end: the period-parallel kernel takes all of it (as k1_fast does below) */
+	const bool whole_pp = c0 == 0 && nsamples % (size_t)per_in == 0 && J == periods * K1P_PER_OUT && !h->knob.no_whole_pp;
+	c.per_lo = whole_pp ? 0 : 1;
+	c.sbase0 = wend_abs(K1P_PER_OUT * c.per_lo - 1, h->sdrclk, c0) + 1;
+	/* 16-byte pieces: a period's first sample sits d samples above a 16-byte boundary, the same d for
+	 * every period (a period is a whole number of 16-byte pieces) and every stream */
+	const uintptr_t a0 = (uintptr_t)src + (uintptr_t)c.sbase0 * h->sample_bytes;
+	if ((a0 % 16) % h->sample_bytes || (h->S > 1 && stride % 16) || ((size_t)per_in * h->sample_bytes) % 16)
+		return general;
+	c.d = (int)((a0 % 16) / h->sample_bytes);
+	if (whole_pp && c.d != 0) {	/* (the kernel reads a period from the 16-byte boundary below its first sample: that would lie in front of the buffer) */
+		c.per_lo = 1;
+		c.sbase0 = wend_abs(K1P_PER_OUT * c.per_lo - 1, h->sdrclk, c0) + 1;
+		const uintptr_t a1 = (uintptr_t)src + (uintptr_t)c.sbase0 * h->sample_bytes;
+		if ((a1 % 16) % h->sample_bytes)
+			return general;
+		c.d = (int)((a1 % 16) / h->sample_bytes);
+	}
+	const long long nsp = periods / 4;	/* superperiods of 4 periods = 336 outputs = 21 lines of the planes */
+	if (h->sdrclk == 500 && h->L == 80 && nsp >= 3 && !h->knob.k1_pp &&
+	    (size_t)h->cap * VDL2_CS * sizeof(float2) < VDL2_PLANES_MAX) {	/* k1_fast addresses a stream's planes with 32-bit offsets (vdl2gpu_create holds every handle to it) */
+		/* 2 MS/s: the LO values of a window fit a lane's registers (lane = window x channel).  Whole superperiods in
+		 * the middle; the first one (carried partial window) and the tail on the general kernel -- unless the push
+		 * starts on a window boundary of the schedule (c0 == 0: nothing carried in) and is a whole number of
+		 * superperiods (nothing carried out): then the fast kernel takes all of it and the two general launches
+		 * (36 us each for 0.02 % of the samples: launch and latency, not work) are not made at all. */
+		c.kind = K1_FAST;
+		c.whole = c0 == 0 && nsamples % K1F_PER_IN == 0 && J == nsp * K1F_PER_OUT;
+		c.per_lo = c.whole ? 0 : 1;
+	} else {
+		c.kind = K1_PP;
+		c.whole = c.per_lo == 0;
+	}
+	return c;
+}
+
+/* The channeliser of a push on stream `ks`: k1 comes with the push's place in the schedule (vdl2gpu_plan); what choose_k1 decided
+ * is launched, the general kernel around it where the other one does not take the whole push. */
+static int enqueue_k1(vdl2gpu_t *h, K1Params &k1, const Input &in, size_t nsamples, int par, hipStream_t ks, PushTiming &pt)
+{
+	const int GS = h->S;
+	const int64_t J = k1.J;
+	const bool staged = pt.staged;
+	k1.raw = in.src;
+	k1.stream_stride = in.stride;
+	k1.fmt = h->cfg.fmt;
+	k1.nbch = h->C;
+	k1.sdrclk = h->sdrclk;
+	k1.L = h->L;
+	k1.maxwin = h->maxwin;
+	k1.parity = (int)(h->pushes & 1);	/* the carried partial window is double-buffered in StreamState.acc: read [parity], written [parity ^ 1] */
+	k1.quirk = h->quirk;
+	k1.N = (long long)nsamples;
+	k1.lo = h->d_lo;
+	k1.dec = h->d_dec[par];
+	k1.cap = h->cap;
+	k1.ss = h->d_ss;
+	const long long per_block = K1_OPB * K1_PASSES;
+	const size_t smem = k1_smem_bytes((uint64_t)h->L, (uint64_t)h->maxwin);	/* <= VDL2_K1_LDS_MAX (vdl2gpu_create) */
+	auto generic = [&](long long jbeg, long long jend) {
+		if (jend < jbeg)
+			return;
+		K1Params q = k1;
+		q.jbeg = jbeg;
+		q.jend = jend;
+		const unsigned gx = (unsigned)((jend - jbeg + 1 + per_block - 1) / per_block);
+		const dim3 grid(gx, (unsigned)GS);
+		with_fmt(h->cfg.fmt, [&](auto F) { hipLaunchKernelGGL(k1_channelise<decltype(F)::value>, grid, dim3(K1_THREADS), smem, ks, q); });
+	};
+	const K1Choice ch = choose_k1(h, k1.c0, J, nsamples, in.src, in.stride);
+	const bool whole = ch.whole;
+	const long long periods = J / K1P_PER_OUT;
+	const long long nsp = periods / 4;
+	if (ch.kind == K1_FAST) {
+		if (!whole)
+			generic(0, K1F_PER_OUT - 1);
+		if (staged)
+			(void)hipEventRecord(pt.e[11], ks);	/* the wait for the resolver that follows is not channeliser time */
+		pt.fast = true;
+		k1.per_lo = whole ? 0 : 1;
+		k1.per_n = whole ? nsp : nsp - 2;
+		k1.edge_state = whole ? 1 : 0;
+		k1.lo_ext = h->d_lo_ext;
+		k1.lo_stride = h->L + 48;
+		if (staged)
+			(void)hipEventRecord(pt.e[8], ks);
+		/* The grid is resident as a whole: n_cu * 2 * K1F_WAVES_OF(fmt) workgroups of two wavefronts fit.  Per stream
+		 * 21 roles x 8 XCDs families of `nfam` workgroups each, which take the family's tickets in turn (see k1_fast);
+		 * a family needs no more workgroups than it has tickets.  With several streams the families are many and
+		 * small: rather two workgroups each and a twentieth of them waiting for a slot than one each and half the
+		 * SIMDs' wavefront slots empty. */
+		long long ngrp;
+		{
+			const long long slots = (long long)h->n_cu * 2 * K1F_WAVES_OF(h->cfg.fmt);
+			const long long per_fam = (long long)K1F_ROLES * 8 * GS;
+			long long nfam = slots / per_fam;
+			if (nfam < 4 && (nfam + 1) * per_fam * 100 <= slots * 108)
+				++nfam;
+			if (h->knob.k1f_nfam > 0)
+				nfam = h->knob.k1f_nfam;
+			const long long tickets = ((k1.per_n + 7) / 8 + K1F_CHUNK - 1) / K1F_CHUNK;	/* of the family with the most */
+			nfam = std::max<long long>(1, std::min(nfam, tickets));
+			ngrp = nfam * 8;
+		}
+		/* the counters are never reset: a launch makes exactly one request per ticket of a family (k1_fast), so the
+		 * host knows where each one stands */
+		k1.tickets = h->d_k1_tickets;
+		for (int x = 0; x < 8; ++x) {
+			k1.tbase[x] = h->k1_tbase[x];	/* (every stream stands where the first does: all have seen the same pushes) */
+			const long long n_x = (k1.per_n - x + 7) >> 3;
+			if (n_x > 0)
+				for (int sg = 0; sg < GS; ++sg)
+					h->k1_tbase[(size_t)sg * 8 + x] += (unsigned)((n_x + K1F_CHUNK - 1) / K1F_CHUNK);
+		}
+		const dim3 grid((unsigned)ngrp * K1F_ROLES, (unsigned)GS);
+		with_fmt(h->cfg.fmt, [&](auto F) { hipLaunchKernelGGL(k1_fast<decltype(F)::value>, grid, dim3(K1F_THREADS), 0, ks, k1); });
+		if (staged)
+			(void)hipEventRecord(pt.e[9], ks);
+		pt.fast_parts = 1;
+		if (!whole)
+			generic((nsp - 1) * K1F_PER_OUT, J);
+	} else if (ch.kind == K1_PP) {
+		K1PParams kp{};
+		kp.per_lo = ch.per_lo;
+		kp.sbase0 = ch.sbase0;
+		kp.d = ch.d;
+		const int per_in = 4 * h->sdrclk;
+		if (!whole)
+			generic(0, K1P_PER_OUT - 1);
+		if (staged)
+			(void)hipEventRecord(pt.e[11], ks);
+		pt.fast = true;
+		kp.edge_state = whole ? 1 : 0;
+		kp.parity = k1.parity;
+		kp.J = J;
+		kp.raw = in.src;
+		kp.stream_stride = in.stride;
+		kp.nbch = h->C;
+		kp.per_in = per_in;
+		kp.L = h->L;
+		kp.ph0 = (int)(((long long)k1.no0 + kp.sbase0) % h->L);
+		kp.per_n = (int)(whole ? periods : periods - 2);
+		kp.lo_ext = h->d_lo_ext;
+		kp.lo_stride = h->L + 48;
+		kp.dec = k1.dec;
+		kp.cap = h->cap;
+		kp.ss = h->d_ss;
+		int nfmin = 1 << 30, nfmax = 0;
+		for (int k = 0; k < K1P_PER_OUT; ++k) {
+			kp.wend[k] = (int)(wend_abs(K1P_PER_OUT * kp.per_lo + k, h->sdrclk, k1.c0) - kp.sbase0);
+			const int nf = kp.wend[k] - (k ? kp.wend[k - 1] : -1);
+			nfmin = std::min(nfmin, nf);
+			nfmax = std::max(nfmax, nf);
+		}
+		auto proven = [](int nf) { return nf == 23 || nf == 24 || nf == 59 || nf == 60 || nf == 71 || nf == 72 || nf == 119 || nf == 120; };
+		kp.fast_div = proven(nfmin) && proven(nfmax) && nfmax - nfmin <= 1;
+		kp.nf_lo = nfmin;
+		kp.dbg = h->knob.k1_dbg;
+		kp.rcp_lo = 1.0f / (float)nfmin;
+		kp.rcp_hi = 1.0f / (float)(nfmin + 1);
+		/* tasks = (blocks of 64 periods) x (runs of wpt windows): enough of them that the last round of
+		 * workgroups is a small share of the launch, as long as possible otherwise */
+		const long long blocks = (kp.per_n + 63) / 64;
+		const int divs[] = {1, 2, 3, 4, 6, 7, 12, 14, 21, 28};
+		const long long resident = (long long)h->n_cu * 3;
+		int best = 1;
+		double best_eff = -1;
+		for (int nsub : divs) {
+			const long long tasks = blocks * nsub * GS;
+			const long long rounds = (tasks + resident - 1) / resident;
+			const double eff = (double)tasks / (double)(rounds * resident) - 0.004 * nsub;	/* shorter tasks pay their start-up more often */
+			if (eff > best_eff) {
+				best_eff = eff;
+				best = nsub;
+			}
+		}
+		if (h->knob.k1_nsub > 0)
+			best = h->knob.k1_nsub;
+		kp.nsub = best;
+		kp.wpt = K1P_PER_OUT / best;
+		if (staged)
+			(void)hipEventRecord(pt.e[8], ks);
+		const dim3 grid((unsigned)(blocks * kp.nsub), (unsigned)GS);
+		with_fmt(h->cfg.fmt, [&](auto F) { hipLaunchKernelGGL(k1_pp<decltype(F)::value>, grid, dim3(K1P_THREADS), 0, ks, kp); });
+		if (staged)
+			(void)hipEventRecord(pt.e[9], ks);
+		pt.fast_parts = 1;
+		if (!whole)
+			generic((periods - 1) * K1P_PER_OUT, J);
+	} else
+		generic(0, J);
+	HIPCHK(h, hipGetLastError());
+	return VDL2GPU_OK;
+}
+
+/* The rest of the FRONT stage behind the channeliser: reset of the control words, probe, regions, region scan, sort, the carry
+ * for the next push -- and what enqueue_back needs of this push (h->back). */
+static int enqueue_front(vdl2gpu_t *h, hipStream_t fs, long long dec_base, PushTiming &pt)
+{
+	vdl2gpu::Back &p = h->back;	/* (push_impl has put the push's J, sets and path there) */
+	const int GS = h->S, par = p.par, ring = p.ring;
+	const int64_t J = p.J;
+	const bool staged = pt.staged, serial = p.serial, two_streams = p.two_streams;
+	TableSet &set = h->set[par];
+	{
+		KInitParams ki{};
+		ki.ctl = set.k2.ctl + CTL_STAGE;
+		ki.ctl_words = (int)(h->ctl_words - CTL_STAGE);
+		ki.outc = h->d_outc + 2 * ring;
+		ki.fail = set.k2.fail;
+		ki.redo = set.k2.redo;
+		ki.nsc = h->S * VDL2_CS;
+		ki.fmask = set.k2.fmask;
+		ki.fcnt = h->frames_on ? h->d_fcnt + 4 * ring : nullptr;
+		hipLaunchKernelGGL(k_push_init, dim3(1), dim3(1024), 0, fs, ki);
+	}
+	if (staged)
+		HIPCHK(h, hipEventRecord(pt.e[10], fs));
+	K2Params k2 = set.k2;	/* the set's tables and everything that never changes (fill_set_params); what follows is this push's */
+	k2.J = J;
+	k2.recs = h->ring[ring].d_recs;
+	k2.levels = h->ring[ring].levels();	/* (nullptr without VDL2GPU_F_LEVELS: nothing is measured) */
+	k2.soft = h->ring[ring].soft();	/* (nullptr without VDL2GPU_F_SOFT_RS) */
+	k2.outc = h->d_outc + 2 * ring;
+	k2.dec_base = dec_base;
+	k2.scan_lo = dec_base + VDL2_HIST;	/* the scan starts at the first carried frame that has its history */
+	k2.probe_par = (int)((dec_base + VDL2_HIST) & 1);
+	k2.force_serial = serial ? 1 : 0;
+	k2.sel_reserved = (!h->full_scan && !serial && h->S * VDL2_CS <= 512) ? 1 : 0;	/* (enqueue_back's `spec`) */
+	if (h->d_headtap) {
+		/* VDL2GPU_F_DEBUG_HEADS: one tap buffer for the handle, so the pipeline is drained first -- the back stage and the
+		 * tail of the two pushes before would otherwise still be appending to it ("every trigger of the LAST push") */
+		HIPCHK(h, hipStreamSynchronize(h->stream));
+		HIPCHK(h, hipStreamSynchronize(h->pay_stream));
+		HIPCHK(h, hipStreamSynchronize(h->copy_stream));
+		HIPCHK(h, hipMemsetAsync(h->d_headtap_n, 0, sizeof(unsigned), fs));
+	}
+	const unsigned tiles = (unsigned)((VDL2_CARRY_FRAMES + J) / K2A_TS + 2);
+	const dim3 gch((unsigned)h->C, (unsigned)GS);
+	ScanDrain pdrain, rdrain;
+	if (!serial) {
+		{
+			/* as many workgroups as are resident at once, each walking its share of the channel's tiles */
+			const unsigned want = h->full_scan ? tiles : tiles / 2 + 1;
+			unsigned per = (unsigned)((h->n_cu * h->probe_occ + h->C * GS - 1) / (h->C * GS));
+			per = per < 1 ? 1 : (per > want ? want : per);
+			per = std::min<unsigned>(per, VDL2_MAXWG);
+			/* the probe needs the carry the push before made (the first 49152 frames of this plane set); with the front
+			 * stage on two streams (below) that copy is not on this stream */
+			pdrain = launch_scan(SCAN_PROBE, k2, dim3(per, (unsigned)h->C, (unsigned)GS), fs, VDL2_SURV_PROBE, h->full_scan ? 0 : (VDL2_PROBE_STRIDE == 2 ? 2 : 3), 0, (h->full_scan ? 4 : 1) * ((want + per - 1) / per));
+		}
+		{
+			K2Params k2d = k2;	/* (k2r_regions works the probe's common area off first, k2s_sort the region scan's) */
+			scan_drain(k2d, pdrain);
+			hipLaunchKernelGGL(k2r_regions, gch, dim3(K2R_NT), 0, fs, k2d);
+		}
+		rdrain = launch_scan(SCAN_REGION, k2, dim3(128, (unsigned)h->C, (unsigned)GS), fs, VDL2_SURV_REGION, 0, 1, 2);
+		HIPCHK(h, hipGetLastError());
+	}
+	if (!serial) {
+		K2Params k2d = k2;
+		scan_drain(k2d, rdrain);
+		hipLaunchKernelGGL(k2s_sort, gch, dim3(K2S_NT), 0, fs, k2d);
+	}
+	if (staged)
+		HIPCHK(h, hipEventRecord(pt.e[4], fs));	/* end of the front stage's scan + sort (e[4] is free: the verify pass is timed from e[12]) */
+	HIPCHK(h, hipGetLastError());
+	/* ---- end of the FRONT stage */
+	if (two_streams)
+		HIPCHK(h, hipEventRecord(set.f_done, fs));
+	{
+		/* the carry for the NEXT push: the last 49152 frames of this push's planes (its own carry included if it is
+		 * shorter) go in front of where the next push's output will start, in the other plane set -- a fixed amount,
+		 * so that it does not wait for the resolver to say how much is still unconsumed (3 MB per stream).  Behind
+		 * this push's scan rather than in front of the next push's channeliser: there the copy sat for 100 us
+		 * behind the cluster kernel, which has the higher priority. */
+		/* the next plane set's head was last read by the tail of the push two back (a repaired channel's payloads are
+		 * decoded late: a burst at the very start of that push lies in its head); the next push's channeliser, right
+		 * behind this copy, waits for that same tail anyway */
+		if (two_streams && h->set[(par + 1) % VDL2_NSET].k2_rec)
+			HIPCHK(h, hipStreamWaitEvent(fs, h->set[(par + 1) % VDL2_NSET].k2_done, 0));
+		K3Params k3{};
+		k3.src = h->d_dec[par];
+		k3.dst = h->d_dec[(par + 1) % VDL2_NSET];
+		k3.cap = h->cap;
+		k3.nbch = h->C;
+		k3.J = J;
+		hipLaunchKernelGGL(k3_carry, dim3(24, (unsigned)h->C, (unsigned)GS), dim3(K3_THREADS), 0, fs, k3);
+		HIPCHK(h, hipGetLastError());
+		if (two_streams)	/* a following push that keeps to the main stream must see the carry (and with two front streams: the next probe) */
+			HIPCHK(h, hipEventRecord(h->f_tail, fs));
+		else {	/* ... and a following push's front stage this push's channeliser state and carry, made on the main stream */
+			HIPCHK(h, hipEventRecord(h->k1_ev, fs));
+			h->k1_ev_rec = true;
+		}
+	}
+	p.valid = true;
+	p.k2 = k2;
+	p.staged = staged;
+	p.tiles = tiles;
+	p.pt_index = h->pending.size();
+	return VDL2GPU_OK;
+}
+
+/* One push (a part of at most split_samples, see push_checked): checks -> staging copy -> channeliser -> collect the output ring
+ * this push reuses -> rest of the front stage -> spill the slab -> back stage and tail -> bookkeeping.  hp(k) closes segment k of
+ * the calling thread's time (vdl2gpu_get_host_profile). */
 static int push_impl(vdl2gpu_t *h, const void *iq, size_t nsamples, size_t stream_stride_bytes, int memkind, bool wait_copy)
 {
 	if (!h || (!iq && nsamples))
@@ -1610,84 +1998,31 @@ static int push_impl(vdl2gpu_t *h, const void *iq, size_t nsamples, size_t strea
 	}
 	/* include/vdl2gpu.h: a device buffer must stay unchanged "until the second push after this one has been issued": that push
 	 * is this call, for the buffer of the push before last (with two output rings the wait for that push's ring implied it) */
-	const int GS = h->S;
 	auto hnow = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
 	double hp_t = hnow();	/* (always on: six clock reads a push; vdl2gpu_get_host_profile() hands the sums out, VDL2GPU_HOST_PROF prints them at destroy) */
 	auto hp = [&](int k) { const double t = hnow(); h->hprof[k] += t - hp_t; hp_t = t; };
-	if (h->in_rec[(h->pushes + 1) % VDL2_NRING])
-		HIPCHK(h, hipEventSynchronize(h->in_read[(h->pushes + 1) % VDL2_NRING]));
+	if (h->ring[(h->pushes + 1) % VDL2_NRING].in_rec)
+		HIPCHK(h, hipEventSynchronize(h->ring[(h->pushes + 1) % VDL2_NRING].in_read));
 	hp(0);
-	const int slab = (int)(h->pushes % VDL2_NSLAB);	/* page-locked slab this push's records are exported to */
-	const int ring = (int)(h->pushes % VDL2_NRING);	/* output ring of this push (collected below, once the GPU has been given work to do meanwhile) */
-	const void *src = iq;
-	size_t stride = stream_stride_bytes;
-	bool staged_in = false;
+	vdl2gpu::Back &p = h->back;	/* what the stages share of this push; enqueue_front completes it for enqueue_back */
+	p.slab = (int)(h->pushes % VDL2_NSLAB);	/* page-locked slab this push's records are exported to */
+	p.ring = (int)(h->pushes % VDL2_NRING);	/* output ring of this push (collected below, once the GPU has been given work to do meanwhile) */
+	p.par = (int)(h->pushes % VDL2_NSET);	/* table set and plane set of this push */
 	const int stg = (int)(h->pushes & 1);	/* staging buffer of this push; its channeliser's events are k1_done[stg] */
-	if (memkind == VDL2GPU_MEM_HOST) {
-		const size_t per = nsamples * h->sample_bytes;
-		const size_t need = per * (size_t)h->S;
-		if (!h->in_stream) {
-			HIPCHK(h, hipStreamCreateWithFlags(&h->in_stream, hipStreamNonBlocking));
-			for (int i = 0; i < 2; ++i)
-				HIPCHK(h, hipEventCreateWithFlags(&h->raw_copied[i], hipEventDisableTiming));
-		}
-		if (need > h->raw_bytes[stg]) {
-			HIPCHK(h, hipStreamSynchronize(h->fstream));
-			HIPCHK(h, hipStreamSynchronize(h->stream));
-			HIPCHK(h, hipStreamSynchronize(h->pay_stream));
-			HIPCHK(h, hipStreamSynchronize(h->in_stream));
-			(void)hipFree(h->d_raw[stg]);
-			h->d_raw[stg] = nullptr;
-			h->raw_bytes[stg] = 0;
-			HIPCHK(h, hipMalloc(&h->d_raw[stg], need));
-			h->raw_bytes[stg] = need;
-		}
-		/* the channeliser of the push before last has read this buffer */
-		if (h->k1_rec[stg])
-			HIPCHK(h, hipStreamWaitEvent(h->in_stream, h->k1_done[stg], 0));
-		for (int s = 0; s < GS; ++s)
-			HIPCHK(h, hipMemcpyAsync((char *)h->d_raw[stg] + (size_t)s * per,
-						 (const char *)iq + (size_t)s * stream_stride_bytes, per,
-						 hipMemcpyHostToDevice, h->in_stream));
-		HIPCHK(h, hipEventRecord(h->raw_copied[stg], h->in_stream));
-		if (wait_copy)
-			HIPCHK(h, hipEventSynchronize(h->raw_copied[stg]));
-		staged_in = true;
-		src = h->d_raw[stg];
-		stride = per;
-	} else if (memkind != VDL2GPU_MEM_DEVICE)
-		return VDL2GPU_EINVAL;
+	const int par = p.par;
+	OutRing &rg = h->ring[p.ring];
+	Input in;
+	TRY(stage_input(h, iq, nsamples, stream_stride_bytes, memkind, wait_copy, stg, in));
 
 	K1Params k1{};
-	int64_t J = 0;
-	vdl2gpu_plan(h->total_in, nsamples, (unsigned)h->sdrclk, (unsigned)h->L, &k1.c0, &k1.no0, &k1.nf0, &J);
-	const int par = (int)(h->pushes % VDL2_NSET);	/* table set, plane set and output ring of this push */
-	const int pset = par;
-	k1.raw = src;
-	k1.stream_stride = stride;
-	k1.fmt = h->cfg.fmt;
-	k1.nbch = h->C;
-	k1.sdrclk = h->sdrclk;
-	k1.L = h->L;
-	k1.maxwin = h->maxwin;
-	k1.parity = (int)(h->pushes & 1);	/* the carried partial window is double-buffered in StreamState.acc: read [parity], written [parity ^ 1] */
-	k1.quirk = h->quirk;
-	k1.N = (long long)nsamples;
-	k1.J = J;
-	k1.lo = h->d_lo;
-	k1.dec = h->d_dec[pset];
-	k1.cap = h->cap;
-	k1.ss = h->d_ss;
+	vdl2gpu_plan(h->total_in, nsamples, (unsigned)h->sdrclk, (unsigned)h->L, &k1.c0, &k1.no0, &k1.nf0, &p.J);
+	k1.J = p.J;
 	/* A short push (a live SDR block is 1376 frames per channel) is cheaper on the serial machine alone
 	 * than through the scan's ten launches: the parallel path only pays from a few thousand frames on. */
-#ifdef VDL2GPU_TESTHOOKS
-	const bool noregion = (h->cfg.flags & VDL2GPU_F_TEST_NOREGION) != 0;
-#else
-	const bool noregion = false;
-#endif
-	const bool serial = h->force_serial || (J <= VDL2_SERIAL_BELOW && !h->full_scan && !noregion);
-	const bool two_streams = !serial;	/* see vdl2gpu::Back */
-	hipStream_t fs = two_streams ? h->fstream : h->stream;
+	p.serial = h->force_serial || (p.J <= VDL2_SERIAL_BELOW && !h->full_scan && !h->set[p.par].k2.test_noregion);
+	p.two_streams = !p.serial;	/* see vdl2gpu::Back */
+	const bool two_streams = p.two_streams;
+	hipStream_t fs = two_streams ? h->fstream : h->stream;	/* the front stage's stream */
 	/* stream time of frame 0 of this push's planes: the outputs completed before it, minus the carried frames in front */
 	const long long dec_base = (long long)(((unsigned __int128)h->total_in * 21u) / (unsigned)h->sdrclk) - VDL2_CARRY_FRAMES;
 
@@ -1704,222 +2039,33 @@ static int push_impl(vdl2gpu_t *h, const void *iq, size_t nsamples, size_t strea
 	hipStream_t ks = fs;
 	if (!two_streams && h->last_two_streams)	/* the previous push's channeliser state and carry were written on the front stream */
 		HIPCHK(h, hipStreamWaitEvent(fs, h->f_tail, 0));
-	if (!two_streams && h->k2_rec[(par + VDL2_NSET - 1) % VDL2_NSET])	/* ... and its tail may have run on the payload stream */
-		HIPCHK(h, hipStreamWaitEvent(fs, h->k2_done[(par + VDL2_NSET - 1) % VDL2_NSET], 0));
+	if (!two_streams && h->set[(par + VDL2_NSET - 1) % VDL2_NSET].k2_rec)	/* ... and its tail may have run on the payload stream */
+		HIPCHK(h, hipStreamWaitEvent(fs, h->set[(par + VDL2_NSET - 1) % VDL2_NSET].k2_done, 0));
 	if (two_streams) {
 		/* the plane set this push's channeliser writes, the table set and the output ring were last used by the push three
 		 * back: by its tail (the payload decode of a repaired channel reads the planes to the very end of it) */
-		if (h->k2_rec[par])
-			HIPCHK(h, hipStreamWaitEvent(fs, h->k2_done[par], 0));
+		if (h->set[par].k2_rec)
+			HIPCHK(h, hipStreamWaitEvent(fs, h->set[par].k2_done, 0));
 		if (h->k1_ev_rec && !h->last_two_streams)	/* the previous push's channeliser ran on the main stream */
 			HIPCHK(h, hipStreamWaitEvent(fs, h->k1_ev, 0));
 	}
-	if (staged_in)
+	if (in.staged)
 		HIPCHK(h, hipStreamWaitEvent(ks, h->raw_copied[stg], 0));
 	if (staged && h->stage_dump && !h->ev_origin) {	/* the origin of the dump's times: in front of the first push's first event, on its stream */
-		HIPCHK(h, hipEventCreate(&h->ev_origin));
+		NEW_EVENT(h, h->ev_origin, true);
 		HIPCHK(h, hipEventRecord(h->ev_origin, ks));
 	}
 	if (staged)
 		HIPCHK(h, hipEventRecord(pt.e[0], ks));
-	{
-		const long long per_block = K1_OPB * K1_PASSES;
-		const size_t smem = k1_smem_bytes((uint64_t)h->L, (uint64_t)h->maxwin);	/* <= VDL2_K1_LDS_MAX (vdl2gpu_create) */
-		auto generic = [&](long long jbeg, long long jend) {
-			if (jend < jbeg)
-				return;
-			K1Params q = k1;
-			q.jbeg = jbeg;
-			q.jend = jend;
-			const unsigned gx = (unsigned)((jend - jbeg + 1 + per_block - 1) / per_block);
-			const dim3 grid(gx, (unsigned)GS);
-			switch (h->cfg.fmt) {
-			case VDL2GPU_FMT_CU8: launch_k1<VDL2GPU_FMT_CU8>(q, grid, smem, ks); break;
-			case VDL2GPU_FMT_CS16: launch_k1<VDL2GPU_FMT_CS16>(q, grid, smem, ks); break;
-			case VDL2GPU_FMT_CF32: launch_k1<VDL2GPU_FMT_CF32>(q, grid, smem, ks); break;
-			case VDL2GPU_FMT_CS8: launch_k1<VDL2GPU_FMT_CS8>(q, grid, smem, ks); break;
-			case VDL2GPU_FMT_S16R: launch_k1<VDL2GPU_FMT_S16R>(q, grid, smem, ks); break;
-			default: launch_k1<VDL2GPU_FMT_F32R>(q, grid, smem, ks); break;
-			}
-		};
-		/* whole periods of the schedule (4*SDRCLK inputs = 84 outputs, the LO table a whole number of times:
-		 * SDRINRATE = 4000*SDRCLK, air.c:138) on the period-parallel kernel; the first period (carried partial
-		 * window) and the tail on the general one */
-		const long long periods = J / K1P_PER_OUT;
-		const int per_in = 4 * h->sdrclk;
-		bool fast = (per_in % h->L == 0 && periods >= 4 && !h->quirk && !h->knob.no_k1_fast &&
-			     std::min(K1P_CH, h->maxwin) <= h->L);	/* k1_pp steps its LO index by a piece (<= a chunk, <= a window) and wraps it once */
-		K1PParams kp{};
-		/* a push that starts on a window boundary of the schedule (nothing carried in) and is a whole number of periods (nothing
-		 * carried out) needs no general launch at either end: the period-parallel kernel takes all of it (as k1_fast does below) */
-		const bool whole_pp = k1.c0 == 0 && nsamples % (size_t)per_in == 0 && J == periods * K1P_PER_OUT && !h->knob.no_whole_pp;
-		if (fast) {
-			auto wend_abs = [&](long long j) { return ((j + 1) * (long long)h->sdrclk - k1.c0 + 20) / 21 - 1; };
-			kp.per_lo = whole_pp ? 0 : 1;
-			kp.sbase0 = wend_abs(K1P_PER_OUT * kp.per_lo - 1) + 1;
-			/* 16-byte pieces: a period's first sample sits d samples above a 16-byte boundary, the same d for
-			 * every period (a period is a whole number of 16-byte pieces) and every stream */
-			const uintptr_t a0 = (uintptr_t)src + (uintptr_t)kp.sbase0 * h->sample_bytes;
-			if ((a0 % 16) % h->sample_bytes || (h->S > 1 && stride % 16) || ((size_t)per_in * h->sample_bytes) % 16)
-				fast = false;
-			kp.d = (int)((a0 % 16) / h->sample_bytes);
-			if (whole_pp && kp.d != 0) {	/* (the kernel reads a period from the 16-byte boundary below its first sample: that would lie in front of the buffer) */
-				kp.per_lo = 1;
-				kp.sbase0 = wend_abs(K1P_PER_OUT * kp.per_lo - 1) + 1;
-				const uintptr_t a1 = (uintptr_t)src + (uintptr_t)kp.sbase0 * h->sample_bytes;
-				if ((a1 % 16) % h->sample_bytes)
-					fast = false;
-				kp.d = (int)((a1 % 16) / h->sample_bytes);
-			}
-		}
-		const long long nsp = periods / 4;	/* superperiods of 4 periods = 336 outputs = 21 lines of the planes */
-		const bool fast2m = fast && h->sdrclk == 500 && h->L == 80 && nsp >= 3 && !h->knob.k1_pp &&
-				    (size_t)h->cap * VDL2_CS * sizeof(float2) < VDL2_PLANES_MAX;	/* k1_fast addresses a stream's planes with 32-bit offsets (vdl2gpu_create holds every handle to it) */
-		if (fast2m) {
-			/* 2 MS/s: the LO values of a window fit a lane's registers (lane = window x channel).  Whole superperiods in
-			 * the middle; the first one (carried partial window) and the tail on the general kernel -- unless the push
-			 * starts on a window boundary of the schedule (c0 == 0: nothing carried in) and is a whole number of
-			 * superperiods (nothing carried out): then the fast kernel takes all of it and the two general launches
-			 * (36 us each for 0.02 % of the samples: launch and latency, not work) are not made at all. */
-			const bool whole = k1.c0 == 0 && nsamples % K1F_PER_IN == 0 && J == nsp * K1F_PER_OUT;
-			if (!whole)
-				generic(0, K1F_PER_OUT - 1);
-			if (staged)
-				(void)hipEventRecord(pt.e[11], ks);	/* the wait for the resolver that follows is not channeliser time */
-			pt.fast = true;
-			k1.per_lo = whole ? 0 : 1;
-			k1.per_n = whole ? nsp : nsp - 2;
-			k1.edge_state = whole ? 1 : 0;
-			k1.lo_ext = h->d_lo_ext;
-			k1.lo_stride = h->L + 48;
-			if (staged)
-				(void)hipEventRecord(pt.e[8], ks);
-			/* The grid is resident as a whole: n_cu * 2 * K1F_WAVES_OF(fmt) workgroups of two wavefronts fit.  Per stream
-			 * 21 roles x 8 XCDs families of `nfam` workgroups each, which take the family's tickets in turn (see k1_fast);
-			 * a family needs no more workgroups than it has tickets.  With several streams the families are many and
-			 * small: rather two workgroups each and a twentieth of them waiting for a slot than one each and half the
-			 * SIMDs' wavefront slots empty. */
-			long long ngrp;
-			{
-				const long long slots = (long long)h->n_cu * 2 * K1F_WAVES_OF(h->cfg.fmt);
-				const long long per_fam = (long long)K1F_ROLES * 8 * GS;
-				long long nfam = slots / per_fam;
-				if (nfam < 4 && (nfam + 1) * per_fam * 100 <= slots * 108)
-					++nfam;
-				if (h->knob.k1f_nfam > 0)
-					nfam = h->knob.k1f_nfam;
-				const long long tickets = ((k1.per_n + 7) / 8 + K1F_CHUNK - 1) / K1F_CHUNK;	/* of the family with the most */
-				nfam = std::max<long long>(1, std::min(nfam, tickets));
-				ngrp = nfam * 8;
-			}
-			/* the counters are never reset: a launch makes exactly one request per ticket of a family (k1_fast), so the
-			 * host knows where each one stands */
-			k1.tickets = h->d_k1_tickets;
-			for (int x = 0; x < 8; ++x) {
-				k1.tbase[x] = h->k1_tbase[x];	/* (every stream stands where the first does: all have seen the same pushes) */
-				const long long n_x = (k1.per_n - x + 7) >> 3;
-				if (n_x > 0)
-					for (int sg = 0; sg < GS; ++sg)
-						h->k1_tbase[(size_t)sg * 8 + x] += (unsigned)((n_x + K1F_CHUNK - 1) / K1F_CHUNK);
-			}
-			const dim3 grid((unsigned)ngrp * K1F_ROLES, (unsigned)GS);
-			switch (h->cfg.fmt) {
-			case VDL2GPU_FMT_CU8: hipLaunchKernelGGL(k1_fast<VDL2GPU_FMT_CU8>, grid, dim3(K1F_THREADS), 0, ks, k1); break;
-			case VDL2GPU_FMT_CS16: hipLaunchKernelGGL(k1_fast<VDL2GPU_FMT_CS16>, grid, dim3(K1F_THREADS), 0, ks, k1); break;
-			case VDL2GPU_FMT_CF32: hipLaunchKernelGGL(k1_fast<VDL2GPU_FMT_CF32>, grid, dim3(K1F_THREADS), 0, ks, k1); break;
-			case VDL2GPU_FMT_CS8: hipLaunchKernelGGL(k1_fast<VDL2GPU_FMT_CS8>, grid, dim3(K1F_THREADS), 0, ks, k1); break;
-			case VDL2GPU_FMT_S16R: hipLaunchKernelGGL(k1_fast<VDL2GPU_FMT_S16R>, grid, dim3(K1F_THREADS), 0, ks, k1); break;
-			default: hipLaunchKernelGGL(k1_fast<VDL2GPU_FMT_F32R>, grid, dim3(K1F_THREADS), 0, ks, k1); break;
-			}
-			if (staged)
-				(void)hipEventRecord(pt.e[9], ks);
-			pt.fast_parts = 1;
-			if (!whole)
-				generic((nsp - 1) * K1F_PER_OUT, J);
-		} else if (fast) {
-			const bool whole = kp.per_lo == 0;
-			if (!whole)
-				generic(0, K1P_PER_OUT - 1);
-			if (staged)
-				(void)hipEventRecord(pt.e[11], ks);
-			pt.fast = true;
-			kp.edge_state = whole ? 1 : 0;
-			kp.parity = k1.parity;
-			kp.J = J;
-			kp.raw = src;
-			kp.stream_stride = stride;
-			kp.nbch = h->C;
-			kp.per_in = per_in;
-			kp.L = h->L;
-			kp.ph0 = (int)(((long long)k1.no0 + kp.sbase0) % h->L);
-			kp.per_n = (int)(whole ? periods : periods - 2);
-			kp.lo_ext = h->d_lo_ext;
-			kp.lo_stride = h->L + 48;
-			kp.dec = k1.dec;
-			kp.cap = h->cap;
-			kp.ss = h->d_ss;
-			auto wend_abs = [&](long long j) { return ((j + 1) * (long long)h->sdrclk - k1.c0 + 20) / 21 - 1; };
-			int nfmin = 1 << 30, nfmax = 0;
-			for (int k = 0; k < K1P_PER_OUT; ++k) {
-				kp.wend[k] = (int)(wend_abs(K1P_PER_OUT * kp.per_lo + k) - kp.sbase0);
-				const int nf = kp.wend[k] - (k ? kp.wend[k - 1] : -1);
-				nfmin = std::min(nfmin, nf);
-				nfmax = std::max(nfmax, nf);
-			}
-			auto proven = [](int nf) { return nf == 23 || nf == 24 || nf == 59 || nf == 60 || nf == 71 || nf == 72 || nf == 119 || nf == 120; };
-			kp.fast_div = proven(nfmin) && proven(nfmax) && nfmax - nfmin <= 1;
-			kp.nf_lo = nfmin;
-			kp.dbg = h->knob.k1_dbg;
-			kp.rcp_lo = 1.0f / (float)nfmin;
-			kp.rcp_hi = 1.0f / (float)(nfmin + 1);
-			/* tasks = (blocks of 64 periods) x (runs of wpt windows): enough of them that the last round of
-			 * workgroups is a small share of the launch, as long as possible otherwise */
-			const long long blocks = (kp.per_n + 63) / 64;
-			const int divs[] = {1, 2, 3, 4, 6, 7, 12, 14, 21, 28};
-			const long long resident = (long long)h->n_cu * 3;
-			int best = 1;
-			double best_eff = -1;
-			for (int nsub : divs) {
-				const long long tasks = blocks * nsub * GS;
-				const long long rounds = (tasks + resident - 1) / resident;
-				const double eff = (double)tasks / (double)(rounds * resident) - 0.004 * nsub;	/* shorter tasks pay their start-up more often */
-				if (eff > best_eff) {
-					best_eff = eff;
-					best = nsub;
-				}
-			}
-			if (h->knob.k1_nsub > 0)
-				best = h->knob.k1_nsub;
-			kp.nsub = best;
-			kp.wpt = K1P_PER_OUT / best;
-			if (staged)
-				(void)hipEventRecord(pt.e[8], ks);
-			const dim3 grid((unsigned)(blocks * kp.nsub), (unsigned)GS);
-			switch (h->cfg.fmt) {
-			case VDL2GPU_FMT_CU8: hipLaunchKernelGGL(k1_pp<VDL2GPU_FMT_CU8>, grid, dim3(K1P_THREADS), 0, ks, kp); break;
-			case VDL2GPU_FMT_CS16: hipLaunchKernelGGL(k1_pp<VDL2GPU_FMT_CS16>, grid, dim3(K1P_THREADS), 0, ks, kp); break;
-			case VDL2GPU_FMT_CF32: hipLaunchKernelGGL(k1_pp<VDL2GPU_FMT_CF32>, grid, dim3(K1P_THREADS), 0, ks, kp); break;
-			case VDL2GPU_FMT_CS8: hipLaunchKernelGGL(k1_pp<VDL2GPU_FMT_CS8>, grid, dim3(K1P_THREADS), 0, ks, kp); break;
-			case VDL2GPU_FMT_S16R: hipLaunchKernelGGL(k1_pp<VDL2GPU_FMT_S16R>, grid, dim3(K1P_THREADS), 0, ks, kp); break;
-			default: hipLaunchKernelGGL(k1_pp<VDL2GPU_FMT_F32R>, grid, dim3(K1P_THREADS), 0, ks, kp); break;
-			}
-			if (staged)
-				(void)hipEventRecord(pt.e[9], ks);
-			pt.fast_parts = 1;
-			if (!whole)
-				generic((periods - 1) * K1P_PER_OUT, J);
-		} else
-			generic(0, J);
-		HIPCHK(h, hipGetLastError());
-	}
+	TRY(enqueue_k1(h, k1, in, nsamples, par, ks, pt));
 	if (staged)
 		HIPCHK(h, hipEventRecord(pt.e[1], ks));
 	if (memkind != VDL2GPU_MEM_HOST) {	/* the caller's device buffer has been read: see the wait at the top */
-		HIPCHK(h, hipEventRecord(h->in_read[ring], ks));
-		h->in_rec[ring] = true;
+		HIPCHK(h, hipEventRecord(rg.in_read, ks));
+		rg.in_rec = true;
 	} else
-		h->in_rec[ring] = false;
-	if (staged_in) {	/* (only the staging copy of the push after next waits for it) */
+		rg.in_rec = false;
+	if (in.staged) {	/* (only the staging copy of the push after next waits for it) */
 		HIPCHK(h, hipEventRecord(h->k1_done[stg], ks));
 		h->k1_rec[stg] = true;
 	}
@@ -1927,184 +2073,25 @@ static int push_impl(vdl2gpu_t *h, const void *iq, size_t nsamples, size_t strea
 	 * the GPU has the two pushes in between and this push's channeliser to work on while this thread waits for that push's
 	 * tail. */
 	hp(1);	/* channeliser enqueued */
-	if (h->ring_busy[ring]) {
-		const int rch = harvest_ring(h, ring, true);
+	if (rg.busy) {
+		const int rch = harvest_ring(h, p.ring, true);
 		if (rch < 0)
 			return rch;
 	}
 	hp(2);	/* ring collected */
-	{
-		KInitParams ki{};
-		ki.ctl = h->d_ctl[par] + CTL_STAGE;
-		ki.ctl_words = (int)(h->ctl_words - CTL_STAGE);
-		ki.outc = h->d_outc + 2 * ring;
-		ki.fail = h->d_fail[par];
-		ki.redo = h->d_redo[par];
-		ki.nsc = h->S * VDL2_CS;
-		ki.fmask = h->d_fmask[par];
-		ki.fcnt = h->frames_on ? h->d_fcnt + 4 * ring : nullptr;
-		hipLaunchKernelGGL(k_push_init, dim3(1), dim3(1024), 0, fs, ki);
-	}
-	if (staged)
-		HIPCHK(h, hipEventRecord(pt.e[10], fs));
-	{
-		K2Params k2{};
-		k2.dec = h->d_dec[pset];
-		k2.cap = h->cap;
-		k2.nbch = h->C;
-		k2.nstreams = h->S;
-		k2.J = J;
-		k2.ss = h->d_ss;
-		k2.cs = h->d_cs;
-		k2.cfg = h->d_cfg;
-		k2.pn = h->d_pn;
-		k2.pn8 = h->d_pn8;
-		k2.cands = h->d_cands[par];
-		k2.clusters = h->d_clusters[par];
-		k2.clhead = h->d_clhead[par];
-		k2.ctl = h->d_ctl[par];
-		k2.stage = h->d_stage[par];
-		k2.sel_list = h->d_sel_list[par];
-		k2.sel_list2 = h->d_sel_list2[par];
-		k2.sel_mode = 0;
-		k2.stage_cap = h->stage_cap;
-		k2.recs = h->d_recs[ring];
-		k2.levels = h->d_levels[ring];	/* (nullptr without VDL2GPU_F_LEVELS: nothing is measured) */
-		k2.soft = h->d_soft[ring];	/* (nullptr without VDL2GPU_F_SOFT_RS) */
-		k2.outc = h->d_outc + 2 * ring;
-		k2.outc_total_redo = h->d_outc + 8;
-		k2.fmask = h->d_fmask[par];
-		k2.rec_cap = h->rec_cap;
-		k2.dec_base = dec_base;
-		k2.scan_lo = dec_base + VDL2_HIST;	/* the scan starts at the first carried frame that has its history */
-#if VDL2_PROBE_STRIDE == 2
-		k2.probe_r = 0;				/* the one class scanned everywhere: fixed, not the class the channel is in */
-#else
-		k2.probe_r = -1;			/* no class is scanned everywhere: the probe only finds the bursts (every fourth sample of sub-phase 0), the
-							 * region scan lists every class around them, the verify pass covers every stretch the chain idles through */
-#endif
-		k2.probe_par = (int)((dec_base + VDL2_HIST) & 1);
-		k2.force_serial = serial ? 1 : 0;
-		k2.sel_reserved = (!h->full_scan && !serial && h->S * VDL2_CS <= 512) ? 1 : 0;	/* (enqueue_back's `spec`) */
-		k2.prim_drop = h->prim_drop;
-		k2.dbg = h->knob.debug_counters ? h->d_dbg : nullptr;
-		k2.headtap = h->d_headtap;
-		k2.headtap_n = h->d_headtap_n;
-		k2.headtap_cap = h->headtap_cap;
-		if (h->d_headtap) {
-			/* VDL2GPU_F_DEBUG_HEADS: one tap buffer for the handle, so the pipeline is drained first -- the back stage and the
-			 * tail of the two pushes before would otherwise still be appending to it ("every trigger of the LAST push") */
-			HIPCHK(h, hipStreamSynchronize(h->stream));
-			HIPCHK(h, hipStreamSynchronize(h->pay_stream));
-			HIPCHK(h, hipStreamSynchronize(h->copy_stream));
-			HIPCHK(h, hipMemsetAsync(h->d_headtap_n, 0, sizeof(unsigned), fs));
-		}
-		k2.full_scan = h->full_scan;
-		k2.test_noregion = noregion ? 1 : 0;
-		k2.regs = h->d_regs[par];
-		k2.segs = h->d_segs[par];
-		k2.fail = h->d_fail[par];
-		k2.redo = h->d_redo[par];
-		k2.round = 0;
-		k2.cs_out = h->d_cs_out[par];
-		k2.skey = h->d_skey[par];
-		k2.sidx = h->d_sidx[par];
-		k2.prim = h->d_prim[par];
-		k2.seeds = h->d_seeds[par];
-		k2.onchain = h->d_onchain[par];
-		k2.slog = h->d_slog[par];
-		k2.win = h->d_win[par];
-		k2.items = h->d_items[par];
-		k2.item_cap = h->item_cap;
-		k2.item_priv = h->item_priv;
-		k2.drain_slot = -1;
-		const unsigned tiles = (unsigned)((VDL2_CARRY_FRAMES + J) / K2A_TS + 2);
-		const dim3 gch((unsigned)h->C, (unsigned)GS);
-		ScanDrain pdrain, rdrain;
-		if (!serial) {
-			{
-				/* as many workgroups as are resident at once, each walking its share of the channel's tiles */
-				const unsigned want = h->full_scan ? tiles : tiles / 2 + 1;
-				unsigned per = (unsigned)((h->n_cu * h->probe_occ + h->C * GS - 1) / (h->C * GS));
-				per = per < 1 ? 1 : (per > want ? want : per);
-				per = std::min<unsigned>(per, VDL2_MAXWG);
-				/* the probe needs the carry the push before made (the first 49152 frames of this plane set); with the front
-				 * stage on two streams (below) that copy is not on this stream */
-				pdrain = launch_scan(SCAN_PROBE, k2, dim3(per, (unsigned)h->C, (unsigned)GS), fs, VDL2_SURV_PROBE, h->full_scan ? 0 : (VDL2_PROBE_STRIDE == 2 ? 2 : 3), 0, (h->full_scan ? 4 : 1) * ((want + per - 1) / per));
-			}
-			{
-				K2Params k2d = k2;	/* (k2r_regions works the probe's common area off first, k2s_sort the region scan's) */
-				scan_drain(k2d, pdrain);
-				hipLaunchKernelGGL(k2r_regions, gch, dim3(K2R_NT), 0, fs, k2d);
-			}
-			rdrain = launch_scan(SCAN_REGION, k2, dim3(128, (unsigned)h->C, (unsigned)GS), fs, VDL2_SURV_REGION, 0, 1, 2);
-			HIPCHK(h, hipGetLastError());
-		}
-		if (!serial) {
-			K2Params k2d = k2;
-			scan_drain(k2d, rdrain);
-			hipLaunchKernelGGL(k2s_sort, gch, dim3(K2S_NT), 0, fs, k2d);
-		}
-		if (staged)
-		HIPCHK(h, hipEventRecord(pt.e[4], fs));	/* end of the front stage's scan + sort (e[4] is free: the verify pass is timed from e[12]) */
-		HIPCHK(h, hipGetLastError());
-		/* ---- end of the FRONT stage */
-		if (two_streams)
-			HIPCHK(h, hipEventRecord(h->f_done[par], fs));
-		{
-			/* the carry for the NEXT push: the last 49152 frames of this push's planes (its own carry included if it is
-			 * shorter) go in front of where the next push's output will start, in the other plane set -- a fixed amount,
-			 * so that it does not wait for the resolver to say how much is still unconsumed (3 MB per stream).  Behind
-			 * this push's scan rather than in front of the next push's channeliser: there the copy sat for 100 us
-			 * behind the cluster kernel, which has the higher priority. */
-			/* the next plane set's head was last read by the tail of the push two back (a repaired channel's payloads are
-			 * decoded late: a burst at the very start of that push lies in its head); the next push's channeliser, right
-			 * behind this copy, waits for that same tail anyway */
-			if (two_streams && h->k2_rec[(par + 1) % VDL2_NSET])
-				HIPCHK(h, hipStreamWaitEvent(fs, h->k2_done[(par + 1) % VDL2_NSET], 0));
-			K3Params k3{};
-			k3.src = h->d_dec[pset];
-			k3.dst = h->d_dec[(pset + 1) % VDL2_NSET];
-			k3.cap = h->cap;
-			k3.nbch = h->C;
-			k3.J = J;
-			hipLaunchKernelGGL(k3_carry, dim3(24, (unsigned)h->C, (unsigned)GS), dim3(K3_THREADS), 0, fs, k3);
-			HIPCHK(h, hipGetLastError());
-			if (two_streams)	/* a following push that keeps to the main stream must see the carry (and with two front streams: the next probe) */
-				HIPCHK(h, hipEventRecord(h->f_tail, fs));
-			else {	/* ... and a following push's front stage this push's channeliser state and carry, made on the main stream */
-				HIPCHK(h, hipEventRecord(h->k1_ev, fs));
-				h->k1_ev_rec = true;
-			}
-		}
-		h->back.valid = true;
-		h->back.k2 = k2;
-		h->back.J = J;
-		h->back.par = par;
-		h->back.ring = ring;
-		h->back.slab = slab;
-		h->back.staged = staged;
-		h->back.serial = serial;
-		h->back.two_streams = two_streams;
-		h->back.tiles = tiles;
-		h->back.pt_index = h->pending.size();
-	}
+	TRY(enqueue_front(h, fs, dec_base, pt));
 	h->pending.push_back(pt);
 	hp(3);	/* rest of the front stage enqueued */
-	spill_slab(h, slab);	/* (this push's export will write the slab of the push four back: whatever of it the caller has not taken yet moves aside) */
+	spill_slab(h, p.slab);	/* (this push's export will write the slab of the push four back: whatever of it the caller has not taken yet moves aside) */
 	hp(4);
-	{
-		const int rcb = enqueue_back(h);
-		if (rcb)
-			return rcb;
-	}
+	TRY(enqueue_back(h));
 	hp(5);	/* back stage enqueued */
-	h->last_J = J;
+	h->last_J = p.J;
 	h->last_two_streams = two_streams;
-	h->ring_busy[ring] = true;
-	h->ring_slab[ring] = slab;
-	h->ring_push[ring] = h->pushes;
-	h->ring_samples[ring] = nsamples;
+	rg.busy = true;
+	rg.slab = p.slab;
+	rg.push = h->pushes;
+	rg.samples = nsamples;
 	h->last_set = par;
 	h->total_in += nsamples;
 	h->pushes++;
@@ -2138,24 +2125,48 @@ static inline void rec_copy(vdl2gpu_burst_t *dst, const vdl2gpu_burst_t *src, bo
 	memset(reinterpret_cast<char *>(dst) + used, 0, sizeof *dst - used);
 }
 
-static inline vdl2gpu_burst_t *rec_of(vdl2gpu_t *h, uint64_t hd)
+/* The slot a handle of the hand-out order (ready_idx) names: the record and, for every side column the handle was made with, the
+ * entry beside it -- in a slab or in the pageable queue.  The one place that decodes a handle. */
+struct Slot {
+	vdl2gpu_burst_t *rec;
+	uint8_t *side[VDL2_NCOL];	/* nullptr: the column is off */
+	bool from_slab;
+};
+static inline vdl2gpu_burst_t *rec_at(vdl2gpu_t *h, uint64_t hd)	/* (the record alone: the index sort's comparator) */
 {
 	const unsigned src = (unsigned)(hd >> 32) & 7u;
-	return (src ? h->h_slab[src - 1] : h->ready.data()) + (uint32_t)hd;
+	return (src ? h->slab[src - 1].h_recs : h->ready.recs.data()) + (uint32_t)hd;
+}
+static inline Slot slot_of(vdl2gpu_t *h, uint64_t hd)
+{
+	const unsigned src = (unsigned)(hd >> 32) & 7u;
+	const size_t i = (uint32_t)hd;
+	Slot s{};
+	s.from_slab = src != 0;
+	s.rec = rec_at(h, hd);
+	for (int k = 0; k < VDL2_NCOL; ++k)
+		if (h->col_on[k])
+			s.side[k] = (src ? h->slab[src - 1].h_side[k] : h->ready.side[k].data()) + i * col_bytes[k];
+	return s;
 }
 
-/* the level record beside it (VDL2GPU_F_LEVELS) */
-static inline vdl2gpu_level_t *lev_of(vdl2gpu_t *h, uint64_t hd)
+/* Copy the slot `hd` names to the end of the pageable queue `q` and return its index there.  (`q` is not the storage `hd` points
+ * into: a slab's slot goes to h->ready, h->ready's slots go to a queue of their own.) */
+static uint64_t move_aside(vdl2gpu_t *h, RecQueue &q, uint64_t hd)
 {
-	const unsigned src = (unsigned)(hd >> 32) & 7u;
-	return (src ? h->h_lslab[src - 1] : h->lready.data()) + (uint32_t)hd;
+	const Slot s = slot_of(h, hd);
+	q.recs.emplace_back();
+	rec_copy(&q.recs.back(), s.rec, s.from_slab);
+	for (int k = 0; k < VDL2_NCOL; ++k)
+		if (s.side[k])
+			q.side[k].insert(q.side[k].end(), s.side[k], s.side[k] + col_bytes[k]);
+	return (uint64_t)(q.recs.size() - 1);
 }
 
-/* the reliability map beside it (VDL2GPU_F_SOFT_RS) */
-static inline vdl2gpu_soft_t *soft_of(vdl2gpu_t *h, uint64_t hd)
+static void forget_slabs(vdl2gpu_t *h)	/* (no handle points into a slab any more) */
 {
-	const unsigned src = (unsigned)(hd >> 32) & 7u;
-	return (src ? h->h_sslab[src - 1] : h->sready.data()) + (uint32_t)hd;
+	for (Slab &s : h->slab)
+		s.lo = s.hi = 0;
 }
 
 /* A ring's slab is about to be written again (its push's back stage is being enqueued): whatever of it has not been
@@ -2164,53 +2175,30 @@ static void spill_slab(vdl2gpu_t *h, int slab)
 {
 	/* only the stretch of the hand-out order that the slab's push put there (a consumer that polls rarely may have 4 x max_bursts
 	 * unread entries: walking all of them in every push cost the calling thread more than enqueueing the push) */
-	const size_t lo = std::max(h->slab_lo[slab], h->ready_pos), hi = std::min(h->slab_hi[slab], h->ready_idx.size());
-	h->slab_lo[slab] = h->slab_hi[slab] = 0;
+	Slab &sl = h->slab[slab];
+	const size_t lo = std::max(sl.lo, h->ready_pos), hi = std::min(sl.hi, h->ready_idx.size());
+	sl.lo = sl.hi = 0;
 	for (size_t i = lo; i < hi; ++i)
-		if (((h->ready_idx[i] >> 32) & 7u) == (unsigned)(1 + slab)) {
-			h->ready.emplace_back();
-			rec_copy(&h->ready.back(), &h->h_slab[slab][(uint32_t)h->ready_idx[i]], true);
-			if (h->levels_on)
-				h->lready.push_back(h->h_lslab[slab][(uint32_t)h->ready_idx[i]]);
-			if (h->soft_on)
-				h->sready.push_back(h->h_sslab[slab][(uint32_t)h->ready_idx[i]]);
-			h->ready_idx[i] = (uint64_t)(h->ready.size() - 1);
-		}
+		if (((h->ready_idx[i] >> 32) & 7u) == (unsigned)(1 + slab))
+			h->ready_idx[i] = move_aside(h, h->ready, h->ready_idx[i]);
 }
 
-/* Move the records of the push that filled `ring` to the host queue.  blocking = false: only if
- * that push has finished (returns 1 if it has not).  The copy runs on its own stream, so a later
- * push keeps the GPU busy meanwhile. */
-static int harvest_ring(vdl2gpu_t *h, int ring, bool blocking)
+/* harvest_ring, first part: adapt the part length and the number of repair rounds from the counters the push left. */
+static void adapt_from_counters(vdl2gpu_t *h, int ring)
 {
-	if (!h->ring_busy[ring])
-		return 0;
-	if (!blocking) {
-		const hipError_t q = hipEventQuery(h->ring_done(ring));
-		if (q == hipErrorNotReady)
-			return 1;
-		if (q != hipSuccess) {
-			h->err = std::string("hipEventQuery: ") + hipGetErrorString(q);
-			return VDL2GPU_EHIP;
-		}
-	}
-	const double hq0 = std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
-	HIPCHK(h, hipEventSynchronize(h->ring_done(ring)));
-	h->hprof[6] += std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count() - hq0;
-	const unsigned c0 = h->h_pin_cnt[32 * ring], c1 = h->h_pin_cnt[32 * ring + 1];
-	const unsigned n = std::min(c0, h->rec_cap);
-	h->overflowed += c1;
-	if (!h->knob.split_fixed && h->ring_samples[ring]) {
+	const OutRing &rg = h->ring[ring];
+	const unsigned *cnt = h->h_pin_cnt + 32 * ring;
+	if (!h->knob.split_fixed && rg.samples) {
 		/* How long a part may be follows from how many trigger candidates the busiest channel produced per input sample
 		 * in the parts collected lately (the highest of the last four): parts are sized to fill 90 % of the tables, so
 		 * that traffic may grow by a tenth from one push to the next before a channel overflows them.  A channel that does
 		 * overflow is handled by the serial machine for that part (exact, milliseconds); its density then counts as
 		 * twice what the tables hold.  Round 2 halved the parts on an overflow and doubled them again after 1024 quiet
 		 * pushes: busy channels ended up in parts a quarter full. */
-		const unsigned novf = h->h_pin_cnt[32 * ring + 7];
-		const unsigned maxc = h->h_pin_cnt[32 * ring + 24];
+		const unsigned novf = cnt[7];
+		const unsigned maxc = cnt[24];
 		/* (a part's scan starts at the first carried frame: its count covers the part plus 49152 frames of the one before) */
-		const double span = (double)h->ring_samples[ring] + (double)VDL2_CARRY_FRAMES * (double)h->sdrclk / 21.0;
+		const double span = (double)rg.samples + (double)VDL2_CARRY_FRAMES * (double)h->sdrclk / 21.0;
 		double d = (double)std::min<unsigned>(maxc, VDL2_CAND_CAP) / span;
 		if (novf)
 			d = 2.0 * (double)VDL2_CAND_CAP / span;
@@ -2223,204 +2211,230 @@ static int harvest_ring(vdl2gpu_t *h, int ring, bool blocking)
 			lim = (size_t)std::min((double)h->split_default, std::max(0.0, h->knob.table_fill * (double)VDL2_CAND_CAP / dmax - (double)VDL2_CARRY_FRAMES * (double)h->sdrclk / 21.0));
 		h->split_samples = std::max(h->split_unit, lim / h->split_unit * h->split_unit);
 		if (novf)
-			h->last_ovf_push = h->ring_push[ring];
+			h->last_ovf_push = rg.push;
 	}
-	{
-		/* one round always (enqueue_back); one more after every serial redo -- a repaired chain failed its own verify pass
-		 * as often as rounds were scheduled --, and back down one at a time after 256 pushes without a serial redo (what
-		 * the first round repairs does not count: it is always there) */
-		const unsigned redos = h->h_pin_cnt[32 * ring + 2], repairs = h->h_pin_cnt[32 * ring + 3];
-		if (redos != h->redos_seen) {
-			h->redos_seen = redos;
-			h->last_redo_push = h->ring_push[ring];
-			h->repair_rounds = std::min(4, h->repair_rounds + 1);
-		} else if (h->repair_rounds > h->rounds_floor && h->ring_push[ring] > h->last_redo_push + 256) {
-			h->repair_rounds--;
-			h->last_redo_push = h->ring_push[ring];
-		}
-		h->repairs_seen = repairs;
+	/* one round always (enqueue_back); one more after every serial redo -- a repaired chain failed its own verify pass
+	 * as often as rounds were scheduled --, and back down one at a time after 256 pushes without a serial redo (what
+	 * the first round repairs does not count: it is always there) */
+	const unsigned redos = cnt[2], repairs = cnt[3];
+	if (redos != h->redos_seen) {
+		h->redos_seen = redos;
+		h->last_redo_push = rg.push;
+		h->repair_rounds = std::min(4, h->repair_rounds + 1);
+	} else if (h->repair_rounds > h->rounds_floor && rg.push > h->last_redo_push + 256) {
+		h->repair_rounds--;
+		h->last_redo_push = rg.push;
 	}
-	if (n) {
-		/* bounded: a consumer that never collects bursts (only frames) loses the oldest ones, counted */
-		const size_t qmax = 4 * (size_t)h->rec_cap;
-		if (h->ready_idx.size() - h->ready_pos > qmax) {
-			const size_t drop = h->ready_idx.size() - h->ready_pos - qmax;
-			h->ready_pos += drop;
-			h->overflowed += drop;
-		}
-		if (h->ready_pos == h->ready_idx.size()) {	/* everything handed out: recycle storage */
-			h->ready.clear();
-			h->lready.clear();
-			h->sready.clear();
-			h->ready_idx.clear();
-			h->ready_pos = 0;
-			for (int k = 0; k < VDL2_NSLAB; ++k)
-				h->slab_lo[k] = h->slab_hi[k] = 0;
-		} else if (h->ready_pos > 1024 && h->ready_pos > h->ready_idx.size() / 2) {	/* the handed-out prefix is the larger part of the storage: drop it
+	h->repairs_seen = repairs;
+}
+
+/* harvest_ring, second part: the push's n burst records join the host queue, in stream-time order. */
+static int collect_records(vdl2gpu_t *h, int ring, unsigned n)
+{
+	const OutRing &rg = h->ring[ring];
+	/* bounded: a consumer that never collects bursts (only frames) loses the oldest ones, counted */
+	const size_t qmax = 4 * (size_t)h->rec_cap;
+	if (h->ready_idx.size() - h->ready_pos > qmax) {
+		const size_t drop = h->ready_idx.size() - h->ready_pos - qmax;
+		h->ready_pos += drop;
+		h->overflowed += drop;
+	}
+	if (h->ready_pos == h->ready_idx.size()) {	/* everything handed out: recycle storage */
+		h->ready.clear();
+		h->ready_idx.clear();
+		h->ready_pos = 0;
+		forget_slabs(h);
+	} else if (h->ready_pos > 1024 && h->ready_pos > h->ready_idx.size() / 2) {	/* the handed-out prefix is the larger part of the storage: drop it
 											 * (so the storage never exceeds 2 x the unread records + one push: <= (8 + 1) x max_bursts records) */
-			std::vector<vdl2gpu_burst_t> keep;
-			std::vector<vdl2gpu_level_t> lkeep;
-			std::vector<vdl2gpu_soft_t> skeep;
-			keep.reserve(h->ready_idx.size() - h->ready_pos);
-			for (size_t i = h->ready_pos; i < h->ready_idx.size(); ++i) {
-				keep.emplace_back();
-				rec_copy(&keep.back(), rec_of(h, h->ready_idx[i]), ((h->ready_idx[i] >> 32) & 7u) != 0);
-				if (h->levels_on)
-					lkeep.push_back(*lev_of(h, h->ready_idx[i]));
-				if (h->soft_on)
-					skeep.push_back(*soft_of(h, h->ready_idx[i]));
-			}
-			h->ready.swap(keep);
-			h->lready.swap(lkeep);
-			h->sready.swap(skeep);
-			h->ready_idx.resize(h->ready.size());
-			for (size_t i = 0; i < h->ready_idx.size(); ++i)
-				h->ready_idx[i] = (uint64_t)i;
-			h->ready_pos = 0;
-			for (int k = 0; k < VDL2_NSLAB; ++k)	/* (no handle points into a slab any more) */
-				h->slab_lo[k] = h->slab_hi[k] = 0;
+		RecQueue keep;
+		keep.recs.reserve(h->ready_idx.size() - h->ready_pos);
+		for (size_t i = h->ready_pos; i < h->ready_idx.size(); ++i)
+			move_aside(h, keep, h->ready_idx[i]);
+		h->ready = std::move(keep);
+		h->ready_idx.resize(h->ready.recs.size());
+		for (size_t i = 0; i < h->ready_idx.size(); ++i)
+			h->ready_idx[i] = (uint64_t)i;
+		h->ready_pos = 0;
+		forget_slabs(h);
+	}
+	/* the first slab_cap records are already in this ring's slab (k_export_records ran before the event this call
+	 * waited for); a push with more than that brings the rest through the bounce buffer */
+	const unsigned ns = std::min(n, h->slab_cap);
+	const size_t old = h->ready.recs.size();
+	for (unsigned done = ns; done < n; done += h->pin_recs) {
+		const unsigned m = std::min(h->pin_recs, n - done);
+		HIPCHK(h, hipMemcpyAsync(h->h_pin, rg.d_recs + done, (size_t)m * sizeof(vdl2gpu_burst_t),
+					 hipMemcpyDeviceToHost, h->copy_stream));
+		HIPCHK(h, hipStreamSynchronize(h->copy_stream));
+		const vdl2gpu_burst_t *pin = reinterpret_cast<const vdl2gpu_burst_t *>(h->h_pin);
+		h->ready.recs.insert(h->ready.recs.end(), pin, pin + m);
+		for (int k = 0; k < VDL2_NCOL; ++k) {	/* the side columns present (40 bytes a record, or 2048: a pageable copy) */
+			if (!h->col_on[k])
+				continue;
+			std::vector<uint8_t> &q = h->ready.side[k];
+			const size_t at = q.size();
+			q.resize(at + (size_t)m * col_bytes[k]);
+			HIPCHK(h, hipMemcpy(q.data() + at, (const uint8_t *)rg.d_side[k] + (size_t)done * col_bytes[k], (size_t)m * col_bytes[k], hipMemcpyDeviceToHost));
 		}
-		/* the first slab_cap records are already in this ring's slab (k_export_records ran before the event this call
-		 * waited for); a push with more than that brings the rest through the bounce buffer */
-		const unsigned ns = std::min(n, h->slab_cap);
-		const size_t old = h->ready.size();
-		for (unsigned done = ns; done < n; done += h->pin_recs) {
-			const unsigned m = std::min(h->pin_recs, n - done);
-			HIPCHK(h, hipMemcpyAsync(h->h_pin, h->d_recs[ring] + done, (size_t)m * sizeof(vdl2gpu_burst_t),
-						 hipMemcpyDeviceToHost, h->copy_stream));
+	}
+	/* K2d ran ahead of the verify pass: what a repair round (or K2f's serial redo) made void of the first selection
+	 * K2d's second pass has tagged (trig_sample == 2 on the device); everything else is a burst of the chain */
+	const bool any = rg.spec;
+	const size_t iold = h->ready_idx.size();
+	auto take = [&](vdl2gpu_burst_t &b, uint64_t handle) {
+		if (any && b.trig_sample == 2)
+			return;
+		b.trig_sample = dec_to_sample(b.trig_dec, (unsigned)h->sdrclk);
+		b.end_sample = dec_to_sample(b.end_dec, (unsigned)h->sdrclk);
+		/* d8psk.c:302, same mixed float/double expression */
+		b.ppm = (float)((double)(10500.0f * b.df) / (2.0 * M_PI * (double)b.Fr) * 1e6);
+		if (h->col_on[COL_LEVEL]) {
+			uint8_t *at = slot_of(h, handle).side[COL_LEVEL];
+			vdl2gpu_level_t l;
+			memcpy(&l, at, sizeof l);
+			l.sig_dbfs = (float)(10.0 * log10((double)l.sig_power / h->lev_k));
+			l.noise_dbfs = (float)(10.0 * log10((double)l.noise_power / h->lev_k));	/* (NaN stays NaN) */
+			memcpy(at, &l, sizeof l);
+		}
+		h->ready_idx.push_back(handle);
+	};
+	Slab &sl = h->slab[rg.slab];
+	for (unsigned i = 0; i < ns; ++i)
+		take(sl.h_recs[i], ((uint64_t)(1 + rg.slab) << 32) | i);
+	for (size_t i = old; i < h->ready.recs.size(); ++i)
+		take(h->ready.recs[i], (uint64_t)i);
+	sl.lo = iold;
+	sl.hi = h->ready_idx.size();
+	std::sort(h->ready_idx.begin() + iold, h->ready_idx.end(), [h](uint64_t x, uint64_t y) {
+		const vdl2gpu_burst_t &a = *rec_at(h, x), &b = *rec_at(h, y);
+		if (a.end_dec != b.end_dec)
+			return a.end_dec < b.end_dec;
+		if (a.stream != b.stream)
+			return a.stream < b.stream;
+		return a.chn < b.chn;
+	});
+	return VDL2GPU_OK;
+}
+
+/* harvest_ring, third part (VDL2GPU_F_FRAMES): the frames of the push's n records join the host queue. */
+static int collect_frames(vdl2gpu_t *h, int ring, unsigned n)
+{
+	const OutRing &rg = h->ring[ring];
+	const unsigned arena0 = h->rec_cap * K4_SLOT;
+	const unsigned nbytes = std::min(h->h_pin_cnt[32 * ring + 6], h->frame_cap - arena0);
+	h->frames_dropped += h->h_pin_cnt[32 * ring + 5];
+	if (!n)
+		return VDL2GPU_OK;
+	{	/* bounded like the burst queue: the oldest frames go, counted */
+		const size_t qmax = 4 * (size_t)h->rec_cap;
+		if (h->fready_idx.size() - h->fready_pos > qmax) {
+			const size_t drop = h->fready_idx.size() - h->fready_pos - qmax;
+			h->fready_pos += drop;
+			h->frames_dropped += drop;
+		}
+	}
+	if (h->fready_pos == h->fready_idx.size()) {
+		h->fready.clear();
+		h->fready_idx.clear();
+		h->fready_pos = 0;
+	} else if (h->fready_pos > 1024 && h->fready_pos > h->fready_idx.size() / 2) {	/* compact: entries are self-delimiting */
+		std::vector<uint8_t> keep;
+		std::vector<size_t> kidx;
+		const size_t hdr0 = offsetof(vdl2gpu_frame_t, data);
+		for (size_t i = h->fready_pos; i < h->fready_idx.size(); ++i) {
+			const uint8_t *e = h->fready.data() + h->fready_idx[i];
+			const size_t sz = (hdr0 + (size_t)reinterpret_cast<const vdl2gpu_frame_t *>(e)->len + 7) & ~(size_t)7;
+			kidx.push_back(keep.size());
+			keep.insert(keep.end(), e, e + sz);
+		}
+		h->fready.swap(keep);
+		h->fready_idx.swap(kidx);
+		h->fready_pos = 0;
+	}
+	const size_t old = h->fready.size();
+	const size_t hdr = offsetof(vdl2gpu_frame_t, data);
+	const size_t pin_bytes = (size_t)h->pin_recs * sizeof(vdl2gpu_burst_t);
+	/* the records' slots: keep the occupied ones, packed like arena entries */
+	const size_t slot_bytes = (size_t)n * K4_SLOT;
+	for (size_t done = 0; done < slot_bytes; done += pin_bytes) {
+		const size_t m = std::min(pin_bytes, slot_bytes - done);
+		HIPCHK(h, hipMemcpyAsync(h->h_pin, (const char *)rg.d_frames + done, m, hipMemcpyDeviceToHost, h->copy_stream));
+		HIPCHK(h, hipStreamSynchronize(h->copy_stream));
+		const uint8_t *pin = reinterpret_cast<const uint8_t *>(h->h_pin);
+		for (size_t o = 0; o < m; o += K4_SLOT) {
+			const vdl2gpu_frame_t *f = reinterpret_cast<const vdl2gpu_frame_t *>(pin + o);
+			if (f->len <= 0 || hdr + (size_t)f->len > K4_SLOT)
+				continue;
+			const size_t sz = (hdr + (size_t)f->len + 7) & ~(size_t)7;
+			h->fready.insert(h->fready.end(), pin + o, pin + o + sz);
+		}
+	}
+	if (nbytes) {
+		const size_t at = h->fready.size();
+		h->fready.resize(at + nbytes);
+		for (size_t done = 0; done < nbytes; done += pin_bytes) {
+			const size_t m = std::min(pin_bytes, (size_t)nbytes - done);
+			HIPCHK(h, hipMemcpyAsync(h->h_pin, (const char *)rg.d_frames + arena0 + done, m, hipMemcpyDeviceToHost,
+						 h->copy_stream));
 			HIPCHK(h, hipStreamSynchronize(h->copy_stream));
-			const vdl2gpu_burst_t *pin = reinterpret_cast<const vdl2gpu_burst_t *>(h->h_pin);
-			h->ready.insert(h->ready.end(), pin, pin + m);
-			if (h->levels_on) {	/* (40 bytes a record: a pageable copy) */
-				const size_t at = h->lready.size();
-				h->lready.resize(at + m);
-				HIPCHK(h, hipMemcpy(h->lready.data() + at, h->d_levels[ring] + done, (size_t)m * sizeof(vdl2gpu_level_t), hipMemcpyDeviceToHost));
-			}
-			if (h->soft_on) {
-				const size_t at = h->sready.size();
-				h->sready.resize(at + m);
-				HIPCHK(h, hipMemcpy(h->sready.data() + at, h->d_soft[ring] + done, (size_t)m * sizeof(vdl2gpu_soft_t), hipMemcpyDeviceToHost));
-			}
+			memcpy(h->fready.data() + at + done, h->h_pin, m);
 		}
-		/* K2d ran ahead of the verify pass: what a repair round (or K2f's serial redo) made void of the first selection
-		 * K2d's second pass has tagged (trig_sample == 2 on the device); everything else is a burst of the chain */
-		const bool any = h->ring_spec[ring];
-		const size_t iold = h->ready_idx.size();
-		auto take = [&](vdl2gpu_burst_t &b, uint64_t handle) {
-			if (any && b.trig_sample == 2)
-				return;
-			b.trig_sample = dec_to_sample(b.trig_dec, (unsigned)h->sdrclk);
-			b.end_sample = dec_to_sample(b.end_dec, (unsigned)h->sdrclk);
-			/* d8psk.c:302, same mixed float/double expression */
-			b.ppm = (float)((double)(10500.0f * b.df) / (2.0 * M_PI * (double)b.Fr) * 1e6);
-			if (h->levels_on) {
-				vdl2gpu_level_t &l = *lev_of(h, handle);
-				l.sig_dbfs = (float)(10.0 * log10((double)l.sig_power / h->lev_k));
-				l.noise_dbfs = (float)(10.0 * log10((double)l.noise_power / h->lev_k));	/* (NaN stays NaN) */
-			}
-			h->ready_idx.push_back(handle);
-		};
-		for (unsigned i = 0; i < ns; ++i)
-			take(h->h_slab[h->ring_slab[ring]][i], ((uint64_t)(1 + h->ring_slab[ring]) << 32) | i);
-		for (size_t i = old; i < h->ready.size(); ++i)
-			take(h->ready[i], (uint64_t)i);
-		h->slab_lo[h->ring_slab[ring]] = iold;
-		h->slab_hi[h->ring_slab[ring]] = h->ready_idx.size();
-		std::sort(h->ready_idx.begin() + iold, h->ready_idx.end(), [h](uint64_t x, uint64_t y) {
-			const vdl2gpu_burst_t &a = *rec_of(h, x), &b = *rec_of(h, y);
-			if (a.end_dec != b.end_dec)
-				return a.end_dec < b.end_dec;
-			if (a.stream != b.stream)
-				return a.stream < b.stream;
+	}
+	/* walk the entries (56 header bytes + len data bytes, rounded up to 8) */
+	const size_t iold = h->fready_idx.size();
+	for (size_t off = old; off + hdr <= h->fready.size();) {
+		vdl2gpu_frame_t *f = reinterpret_cast<vdl2gpu_frame_t *>(h->fready.data() + off);
+		if (f->len < 0 || f->len > VDL2GPU_MAXFRAME || off + hdr + (size_t)f->len > h->fready.size())
+			break;
+		f->ppm = (float)((double)(10500.0f * f->df) / (2.0 * M_PI * (double)f->Fr) * 1e6);	/* d8psk.c:302 */
+		f->block = -1;
+		h->fready_idx.push_back((uint32_t)off);
+		off += (hdr + (size_t)f->len + 7) & ~(size_t)7;
+	}
+	const uint8_t *fd = h->fready.data();
+	std::sort(h->fready_idx.begin() + iold, h->fready_idx.end(), [fd](size_t x, size_t y) {
+		const vdl2gpu_frame_t &a = *reinterpret_cast<const vdl2gpu_frame_t *>(fd + x);
+		const vdl2gpu_frame_t &b = *reinterpret_cast<const vdl2gpu_frame_t *>(fd + y);
+		if (a.end_dec != b.end_dec)
+			return a.end_dec < b.end_dec;
+		if (a.stream != b.stream)
+			return a.stream < b.stream;
+		if (a.chn != b.chn)
 			return a.chn < b.chn;
-		});
-	}
-	if (h->frames_on) {
-		const unsigned arena0 = h->rec_cap * K4_SLOT;
-		const unsigned nbytes = std::min(h->h_pin_cnt[32 * ring + 6], h->frame_cap - arena0);
-		h->frames_dropped += h->h_pin_cnt[32 * ring + 5];
-		if (n) {
-			{	/* bounded like the burst queue: the oldest frames go, counted */
-				const size_t qmax = 4 * (size_t)h->rec_cap;
-				if (h->fready_idx.size() - h->fready_pos > qmax) {
-					const size_t drop = h->fready_idx.size() - h->fready_pos - qmax;
-					h->fready_pos += drop;
-					h->frames_dropped += drop;
-				}
-			}
-			if (h->fready_pos == h->fready_idx.size()) {
-				h->fready.clear();
-				h->fready_idx.clear();
-				h->fready_pos = 0;
-			} else if (h->fready_pos > 1024 && h->fready_pos > h->fready_idx.size() / 2) {	/* compact: entries are self-delimiting */
-				std::vector<uint8_t> keep;
-				std::vector<size_t> kidx;
-				const size_t hdr0 = offsetof(vdl2gpu_frame_t, data);
-				for (size_t i = h->fready_pos; i < h->fready_idx.size(); ++i) {
-					const uint8_t *e = h->fready.data() + h->fready_idx[i];
-					const size_t sz = (hdr0 + (size_t)reinterpret_cast<const vdl2gpu_frame_t *>(e)->len + 7) & ~(size_t)7;
-					kidx.push_back(keep.size());
-					keep.insert(keep.end(), e, e + sz);
-				}
-				h->fready.swap(keep);
-				h->fready_idx.swap(kidx);
-				h->fready_pos = 0;
-			}
-			const size_t old = h->fready.size();
-			const size_t hdr = offsetof(vdl2gpu_frame_t, data);
-			const size_t pin_bytes = (size_t)h->pin_recs * sizeof(vdl2gpu_burst_t);
-			/* the records' slots: keep the occupied ones, packed like arena entries */
-			const size_t slot_bytes = (size_t)n * K4_SLOT;
-			for (size_t done = 0; done < slot_bytes; done += pin_bytes) {
-				const size_t m = std::min(pin_bytes, slot_bytes - done);
-				HIPCHK(h, hipMemcpyAsync(h->h_pin, (const char *)h->d_frames[ring] + done, m, hipMemcpyDeviceToHost, h->copy_stream));
-				HIPCHK(h, hipStreamSynchronize(h->copy_stream));
-				const uint8_t *pin = reinterpret_cast<const uint8_t *>(h->h_pin);
-				for (size_t o = 0; o < m; o += K4_SLOT) {
-					const vdl2gpu_frame_t *f = reinterpret_cast<const vdl2gpu_frame_t *>(pin + o);
-					if (f->len <= 0 || hdr + (size_t)f->len > K4_SLOT)
-						continue;
-					const size_t sz = (hdr + (size_t)f->len + 7) & ~(size_t)7;
-					h->fready.insert(h->fready.end(), pin + o, pin + o + sz);
-				}
-			}
-			if (nbytes) {
-				const size_t at = h->fready.size();
-				h->fready.resize(at + nbytes);
-				for (size_t done = 0; done < nbytes; done += pin_bytes) {
-					const size_t m = std::min(pin_bytes, (size_t)nbytes - done);
-					HIPCHK(h, hipMemcpyAsync(h->h_pin, (const char *)h->d_frames[ring] + arena0 + done, m, hipMemcpyDeviceToHost,
-								 h->copy_stream));
-					HIPCHK(h, hipStreamSynchronize(h->copy_stream));
-					memcpy(h->fready.data() + at + done, h->h_pin, m);
-				}
-			}
-			/* walk the entries (56 header bytes + len data bytes, rounded up to 8) */
-			const size_t iold = h->fready_idx.size();
-			for (size_t off = old; off + hdr <= h->fready.size();) {
-				vdl2gpu_frame_t *f = reinterpret_cast<vdl2gpu_frame_t *>(h->fready.data() + off);
-				if (f->len < 0 || f->len > VDL2GPU_MAXFRAME || off + hdr + (size_t)f->len > h->fready.size())
-					break;
-				f->ppm = (float)((double)(10500.0f * f->df) / (2.0 * M_PI * (double)f->Fr) * 1e6);	/* d8psk.c:302 */
-				f->block = -1;
-				h->fready_idx.push_back((uint32_t)off);
-				off += (hdr + (size_t)f->len + 7) & ~(size_t)7;
-			}
-			const uint8_t *fd = h->fready.data();
-			std::sort(h->fready_idx.begin() + iold, h->fready_idx.end(), [fd](size_t x, size_t y) {
-				const vdl2gpu_frame_t &a = *reinterpret_cast<const vdl2gpu_frame_t *>(fd + x);
-				const vdl2gpu_frame_t &b = *reinterpret_cast<const vdl2gpu_frame_t *>(fd + y);
-				if (a.end_dec != b.end_dec)
-					return a.end_dec < b.end_dec;
-				if (a.stream != b.stream)
-					return a.stream < b.stream;
-				if (a.chn != b.chn)
-					return a.chn < b.chn;
-				return a.seq < b.seq;
-			});
+		return a.seq < b.seq;
+	});
+	return VDL2GPU_OK;
+}
+
+/* Move the records of the push that filled `ring` to the host queue.  blocking = false: only if
+ * that push has finished (returns 1 if it has not).  The copy runs on its own stream, so a later
+ * push keeps the GPU busy meanwhile. */
+static int harvest_ring(vdl2gpu_t *h, int ring, bool blocking)
+{
+	OutRing &rg = h->ring[ring];
+	if (!rg.busy)
+		return 0;
+	if (!blocking) {
+		const hipError_t q = hipEventQuery(rg.done());
+		if (q == hipErrorNotReady)
+			return 1;
+		if (q != hipSuccess) {
+			h->err = std::string("hipEventQuery: ") + hipGetErrorString(q);
+			return VDL2GPU_EHIP;
 		}
 	}
-	h->ring_busy[ring] = false;
+	const double hq0 = std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
+	HIPCHK(h, hipEventSynchronize(rg.done()));
+	h->hprof[6] += std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count() - hq0;
+	const unsigned c0 = h->h_pin_cnt[32 * ring], c1 = h->h_pin_cnt[32 * ring + 1];
+	const unsigned n = std::min(c0, h->rec_cap);
+	h->overflowed += c1;
+	adapt_from_counters(h, ring);
+	if (n)
+		TRY(collect_records(h, ring, n));
+	if (h->frames_on)
+		TRY(collect_frames(h, ring, n));
+	rg.busy = false;
 	return 0;
 }
 
@@ -2429,9 +2443,9 @@ static int harvest_all(vdl2gpu_t *h, bool blocking)
 	/* oldest push first */
 	int order[VDL2_NRING], n = 0;
 	for (int r = 0; r < VDL2_NRING; ++r)
-		if (h->ring_busy[r])
+		if (h->ring[r].busy)
 			order[n++] = r;
-	std::sort(order, order + n, [&](int a, int b) { return h->ring_push[a] < h->ring_push[b]; });
+	std::sort(order, order + n, [&](int a, int b) { return h->ring[a].push < h->ring[b].push; });
 	for (int k = 0; k < n; ++k) {
 		const int rc = harvest_ring(h, order[k], blocking);
 		if (rc < 0)
@@ -2451,7 +2465,7 @@ static int wait_harvest(vdl2gpu_t *h, std::unique_lock<std::recursive_mutex> &lk
 	for (;;) {
 		int r = -1;
 		for (int k = 0; k < VDL2_NRING; ++k)
-			if (h->ring_busy[k] && h->ring_push[k] < upto && (r < 0 || h->ring_push[k] < h->ring_push[r]))
+			if (h->ring[k].busy && h->ring[k].push < upto && (r < 0 || h->ring[k].push < h->ring[r].push))
 				r = k;
 		if (r < 0)
 			return 0;
@@ -2459,7 +2473,7 @@ static int wait_harvest(vdl2gpu_t *h, std::unique_lock<std::recursive_mutex> &lk
 		if (rc < 0)
 			return rc;
 		if (rc == 1) {
-			hipEvent_t ev = h->ring_done(r);
+			hipEvent_t ev = h->ring[r].done();
 			lk.unlock();
 			const hipError_t e = hipEventSynchronize(ev);
 			lk.lock();
@@ -2471,16 +2485,16 @@ static int wait_harvest(vdl2gpu_t *h, std::unique_lock<std::recursive_mutex> &lk
 	}
 }
 
-static int hand_out(vdl2gpu_t *h, vdl2gpu_burst_t *out, int max, vdl2gpu_level_t *lv = nullptr, vdl2gpu_soft_t *sv = nullptr)
+/* side[k]: where the caller wants column k of the records handed out (nullptr: not; only columns the handle has are asked for) */
+static int hand_out(vdl2gpu_t *h, vdl2gpu_burst_t *out, int max, void *const side[VDL2_NCOL])
 {
 	const int n = std::min<int>(max, (int)(h->ready_idx.size() - h->ready_pos));
 	for (int i = 0; i < n; ++i) {
-		const uint64_t hd = h->ready_idx[h->ready_pos + i];
-		rec_copy(out + i, rec_of(h, hd), ((hd >> 32) & 7u) != 0);
-		if (lv)
-			lv[i] = *lev_of(h, hd);
-		if (sv)
-			sv[i] = *soft_of(h, hd);
+		const Slot s = slot_of(h, h->ready_idx[h->ready_pos + i]);
+		rec_copy(out + i, s.rec, s.from_slab);
+		for (int k = 0; k < VDL2_NCOL; ++k)
+			if (side[k])
+				memcpy((uint8_t *)side[k] + (size_t)i * col_bytes[k], s.side[k], col_bytes[k]);
 	}
 	h->ready_pos += (size_t)n;
 	return n;
@@ -2627,8 +2641,8 @@ extern "C" int vdl2gpu_inflight(vdl2gpu_t *h)
 	HIPCHK(h, hipSetDevice(h->cfg.device));
 	int n = 0;
 	for (int r = 0; r < VDL2_NRING; ++r)
-		if (h->ring_busy[r]) {
-			const hipError_t q = hipEventQuery(h->ring_done(r));
+		if (h->ring[r].busy) {
+			const hipError_t q = hipEventQuery(h->ring[r].done());
 			if (q == hipErrorNotReady)
 				++n;
 			else if (q != hipSuccess) {
@@ -2639,81 +2653,16 @@ extern "C" int vdl2gpu_inflight(vdl2gpu_t *h)
 	return n;
 }
 
-extern "C" int vdl2gpu_poll(vdl2gpu_t *h, vdl2gpu_burst_t *out, int max)
+/* The six collectors.  lv / sv: the side columns the caller wants beside the records (nullptr: not); lv_err / sv_err: what the entry
+ * point says when the handle was made without that column. */
+static int poll_impl(vdl2gpu_t *h, vdl2gpu_burst_t *out, vdl2gpu_level_t *lv, vdl2gpu_soft_t *sv, int max, bool blocking,
+		     const char *lv_err = nullptr, const char *sv_err = nullptr)
 {
 	if (!h || (max > 0 && !out) || max < 0)
 		return VDL2GPU_EINVAL;
 	HLOCK(h);
-	if (h->failed)
-		return VDL2GPU_EHIP;
-	HIPCHK(h, hipSetDevice(h->cfg.device));
-	int rc = wait_harvest(h, hlock_);
-	if (rc)
-		return rc;
-	return hand_out(h, out, max);
-}
-
-extern "C" int vdl2gpu_poll_ready(vdl2gpu_t *h, vdl2gpu_burst_t *out, int max)
-{
-	if (!h || (max > 0 && !out) || max < 0)
-		return VDL2GPU_EINVAL;
-	HLOCK(h);
-	if (h->failed)
-		return VDL2GPU_EHIP;
-	HIPCHK(h, hipSetDevice(h->cfg.device));
-	int rc = harvest_all(h, false);
-	if (rc)
-		return rc;
-	return hand_out(h, out, max);
-}
-
-extern "C" int vdl2gpu_poll_levels(vdl2gpu_t *h, vdl2gpu_burst_t *out, vdl2gpu_level_t *lv, int max)
-{
-	if (!lv)
-		return vdl2gpu_poll(h, out, max);
-	if (!h || (max > 0 && !out) || max < 0)
-		return VDL2GPU_EINVAL;
-	HLOCK(h);
-	if (!h->levels_on) {
-		h->err = "vdl2gpu_poll_levels needs VDL2GPU_F_LEVELS";
-		return VDL2GPU_EINVAL;
-	}
-	if (h->failed)
-		return VDL2GPU_EHIP;
-	HIPCHK(h, hipSetDevice(h->cfg.device));
-	int rc = wait_harvest(h, hlock_);
-	if (rc)
-		return rc;
-	return hand_out(h, out, max, lv);
-}
-
-extern "C" int vdl2gpu_poll_levels_ready(vdl2gpu_t *h, vdl2gpu_burst_t *out, vdl2gpu_level_t *lv, int max)
-{
-	if (!lv)
-		return vdl2gpu_poll_ready(h, out, max);
-	if (!h || (max > 0 && !out) || max < 0)
-		return VDL2GPU_EINVAL;
-	HLOCK(h);
-	if (!h->levels_on) {
-		h->err = "vdl2gpu_poll_levels_ready needs VDL2GPU_F_LEVELS";
-		return VDL2GPU_EINVAL;
-	}
-	if (h->failed)
-		return VDL2GPU_EHIP;
-	HIPCHK(h, hipSetDevice(h->cfg.device));
-	int rc = harvest_all(h, false);
-	if (rc)
-		return rc;
-	return hand_out(h, out, max, lv);
-}
-
-static int poll_soft_impl(vdl2gpu_t *h, vdl2gpu_burst_t *out, vdl2gpu_level_t *lv, vdl2gpu_soft_t *sv, int max, bool blocking)
-{
-	if (!h || (max > 0 && !out) || max < 0)
-		return VDL2GPU_EINVAL;
-	HLOCK(h);
-	if ((lv && !h->levels_on) || (sv && !h->soft_on)) {
-		h->err = lv && !h->levels_on ? "vdl2gpu_poll_soft: lv needs VDL2GPU_F_LEVELS" : "vdl2gpu_poll_soft: soft needs VDL2GPU_F_SOFT_RS";
+	if ((lv && !h->col_on[COL_LEVEL]) || (sv && !h->col_on[COL_SOFT])) {
+		h->err = lv && !h->col_on[COL_LEVEL] ? lv_err : sv_err;
 		return VDL2GPU_EINVAL;
 	}
 	if (h->failed)
@@ -2722,17 +2671,40 @@ static int poll_soft_impl(vdl2gpu_t *h, vdl2gpu_burst_t *out, vdl2gpu_level_t *l
 	int rc = blocking ? wait_harvest(h, hlock_) : harvest_all(h, false);
 	if (rc)
 		return rc;
-	return hand_out(h, out, max, lv, sv);
+	void *side[VDL2_NCOL] = {};
+	side[COL_LEVEL] = lv;
+	side[COL_SOFT] = sv;
+	return hand_out(h, out, max, side);
+}
+
+extern "C" int vdl2gpu_poll(vdl2gpu_t *h, vdl2gpu_burst_t *out, int max)
+{
+	return poll_impl(h, out, nullptr, nullptr, max, true);
+}
+
+extern "C" int vdl2gpu_poll_ready(vdl2gpu_t *h, vdl2gpu_burst_t *out, int max)
+{
+	return poll_impl(h, out, nullptr, nullptr, max, false);
+}
+
+extern "C" int vdl2gpu_poll_levels(vdl2gpu_t *h, vdl2gpu_burst_t *out, vdl2gpu_level_t *lv, int max)
+{
+	return poll_impl(h, out, lv, nullptr, max, true, "vdl2gpu_poll_levels needs VDL2GPU_F_LEVELS");	/* (lv = NULL: vdl2gpu_poll) */
+}
+
+extern "C" int vdl2gpu_poll_levels_ready(vdl2gpu_t *h, vdl2gpu_burst_t *out, vdl2gpu_level_t *lv, int max)
+{
+	return poll_impl(h, out, lv, nullptr, max, false, "vdl2gpu_poll_levels_ready needs VDL2GPU_F_LEVELS");
 }
 
 extern "C" int vdl2gpu_poll_soft(vdl2gpu_t *h, vdl2gpu_burst_t *out, vdl2gpu_level_t *lv, vdl2gpu_soft_t *soft, int max)
 {
-	return poll_soft_impl(h, out, lv, soft, max, true);
+	return poll_impl(h, out, lv, soft, max, true, "vdl2gpu_poll_soft: lv needs VDL2GPU_F_LEVELS", "vdl2gpu_poll_soft: soft needs VDL2GPU_F_SOFT_RS");
 }
 
 extern "C" int vdl2gpu_poll_soft_ready(vdl2gpu_t *h, vdl2gpu_burst_t *out, vdl2gpu_level_t *lv, vdl2gpu_soft_t *soft, int max)
 {
-	return poll_soft_impl(h, out, lv, soft, max, false);
+	return poll_impl(h, out, lv, soft, max, false, "vdl2gpu_poll_soft: lv needs VDL2GPU_F_LEVELS", "vdl2gpu_poll_soft: soft needs VDL2GPU_F_SOFT_RS");
 }
 
 extern "C" int vdl2gpu_get_stats(vdl2gpu_t *h, vdl2gpu_stats_t *out)
@@ -2872,7 +2844,7 @@ extern "C" int vdl2gpu_debug_atan2f(vdl2gpu_t *h, const float *y, const float *x
 	}
 	if (e == hipSuccess)
 		e = hipMemcpy(out, d + 2 * n, n * sizeof(float), hipMemcpyDeviceToHost);
-	(void)hipFree(d);
+	(void)hipFree(d);	/* (a call's temporary, explicit like vdl2gpu_decode_blocks_soft's) */
 	if (e != hipSuccess) {
 		h->err = hipGetErrorString(e);
 		return VDL2GPU_EHIP;
@@ -2908,11 +2880,11 @@ extern "C" int vdl2gpu_debug_cands(vdl2gpu_t *h, int stream, int ch, int *out, i
 		return rc;
 	const int sc = stream * VDL2_CS + ch;
 	unsigned n = 0;
-	HIPCHK(h, hipMemcpy(&n, h->d_ctl[h->last_set] + CTL_CAND0 + sc, sizeof n, hipMemcpyDeviceToHost));
+	HIPCHK(h, hipMemcpy(&n, h->set[h->last_set].k2.ctl + CTL_CAND0 + sc, sizeof n, hipMemcpyDeviceToHost));
 	n = std::min<unsigned>(n, VDL2_CAND_CAP);
 	n = std::min<unsigned>(n, (unsigned)max_cands);
 	if (n)
-		HIPCHK(h, hipMemcpy(out, h->d_cands[h->last_set] + (size_t)sc * VDL2_CAND_CAP, (size_t)n * sizeof(Cand), hipMemcpyDeviceToHost));
+		HIPCHK(h, hipMemcpy(out, h->set[h->last_set].k2.cands + (size_t)sc * VDL2_CAND_CAP, (size_t)n * sizeof(Cand), hipMemcpyDeviceToHost));
 	return (int)n;
 }
 
@@ -2929,11 +2901,11 @@ extern "C" int vdl2gpu_debug_clheads(vdl2gpu_t *h, int stream, int ch, int *out,
 		return rc;
 	const int sc = stream * VDL2_CS + ch;
 	unsigned n = 0;
-	HIPCHK(h, hipMemcpy(&n, h->d_ctl[h->last_set] + CTL_CAND0 + sc, sizeof n, hipMemcpyDeviceToHost));
+	HIPCHK(h, hipMemcpy(&n, h->set[h->last_set].k2.ctl + CTL_CAND0 + sc, sizeof n, hipMemcpyDeviceToHost));
 	n = std::min<unsigned>(n, VDL2_CAND_CAP);
 	n = std::min<unsigned>(n, (unsigned)max_cands);
 	if (n)
-		HIPCHK(h, hipMemcpy(out, h->d_clhead[h->last_set] + (size_t)sc * VDL2_CAND_CAP, (size_t)n * sizeof(int2), hipMemcpyDeviceToHost));
+		HIPCHK(h, hipMemcpy(out, h->set[h->last_set].k2.clhead + (size_t)sc * VDL2_CAND_CAP, (size_t)n * sizeof(int2), hipMemcpyDeviceToHost));
 	return (int)n;
 }
 
@@ -2946,7 +2918,7 @@ extern "C" int vdl2gpu_debug_fail(vdl2gpu_t *h, int *out, int n)
 	if (rc)
 		return rc;
 	for (int st = 0; st < h->S; ++st)	/* (every stream from the set of its last pass) */
-		HIPCHK(h, hipMemcpy(out + (size_t)st * VDL2_CS, h->d_fail[h->last_set] + (size_t)st * VDL2_CS, VDL2_CS * sizeof(int), hipMemcpyDeviceToHost));
+		HIPCHK(h, hipMemcpy(out + (size_t)st * VDL2_CS, h->set[h->last_set].k2.fail + (size_t)st * VDL2_CS, VDL2_CS * sizeof(int), hipMemcpyDeviceToHost));
 	return h->S * VDL2_CS;
 }
 
@@ -2960,10 +2932,10 @@ extern "C" int vdl2gpu_debug_segs(vdl2gpu_t *h, int stream, int ch, int *out, in
 		return rc;
 	const int sc = stream * VDL2_CS + ch;
 	unsigned n = 0;
-	HIPCHK(h, hipMemcpy(&n, h->d_ctl[h->last_set] + CTL_CAND0 + 3 * (size_t)h->S * VDL2_CS + sc, sizeof n, hipMemcpyDeviceToHost));
+	HIPCHK(h, hipMemcpy(&n, h->set[h->last_set].k2.ctl + CTL_CAND0 + 3 * (size_t)h->S * VDL2_CS + sc, sizeof n, hipMemcpyDeviceToHost));
 	n = std::min<unsigned>(n, (unsigned)std::min(max_segs, VDL2_SEG_CAP));
 	if (n)
-		HIPCHK(h, hipMemcpy(out, h->d_segs[h->last_set] + (size_t)sc * VDL2_SEG_CAP, (size_t)n * sizeof(Seg), hipMemcpyDeviceToHost));
+		HIPCHK(h, hipMemcpy(out, h->set[h->last_set].k2.segs + (size_t)sc * VDL2_SEG_CAP, (size_t)n * sizeof(Seg), hipMemcpyDeviceToHost));
 	return (int)n;
 }
 
