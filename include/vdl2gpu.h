@@ -92,6 +92,15 @@ typedef struct {
 				 * with sdrclk such that the general channeliser's LDS, ((L + maxwin) * 8 + 32 * maxwin) * 8 bytes
 				 * with L = sdrinrate / 25000 and maxwin = (sdrclk + 20) / 21, stays within 160 KiB (gfx950's limit
 				 * per workgroup).  At the default sdrclk that is up to 25.7 MS/s; at 2 MS/s, sdrclk up to 10416.
+				 * Off the 25 kHz grid (announced by VDL2GPU_HAVE_OFFGRID_RATES, the ABI version is unchanged:
+				 * 2.048 MS/s of rtl_sdr, 1.024 / 1.92 / 2.56 / 2.88 MS/s, the 61.44/n family 1.92 .. 30.72 MS/s):
+				 * any multiple of 1 kHz from 100 kHz on whose LO table, L = vdl2gpu_lo_len(sdrinrate) =
+				 * sdrinrate / gcd(sdrinrate, 25000) entries, divides a period of the dump schedule
+				 * (4 * sdrclk % L == 0; at the default sdrclk every multiple of 4 kHz) and whose window part of
+				 * that LDS, (maxwin * 8 + 32 * maxwin) * 8 bytes, stays within 160 KiB (the table itself need
+				 * not): at the default sdrclk maxwin <= 512, up to 43.0 MS/s, so 30.72 MS/s is accepted and 61.44 MS/s is not.
+				 * The table is a whole period of the local oscillator only for channel offsets Fo on the 25 kHz
+				 * grid, where VDL channels lie, as before.  VDL2GPU_F_RTL_QUIRK is VDL2GPU_EINVAL off the grid.
 				 * Anything else is VDL2GPU_EINVAL from vdl2gpu_create, before any device call. */
 	uint32_t sdrclk;	/* SDRCLK, in (21, 1000000] and within the LDS bound above; 0 = sdrinrate/4000 (rtl.c:37, air.c:138) */
 	int32_t fmt;		/* VDL2GPU_FMT_* */
@@ -394,8 +403,14 @@ int vdl2gpu_poll_frames_ready(vdl2gpu_t *h, vdl2gpu_frame_t *out, int max);
 unsigned int reversebits(const unsigned int bits, const int n);
 
 /* ---- pure host helpers (usable without a GPU) ---- */
+/* Length of a channel's local-oscillator table: sdrinrate / gcd(sdrinrate, 25000), the period of the oscillator for
+ * an offset on the 25 kHz grid.  SDRINRATE/25000 (d8psk.c:348) where 25 kHz divides the rate; 2048 at 2.048 MS/s,
+ * 6144 at 30.72 MS/s.  0 for a rate of 0. */
+#define VDL2GPU_HAVE_OFFGRID_RATES 1
+int vdl2gpu_lo_len(unsigned sdrinrate);
 /* Local-oscillator table of one channel, d8psk.c:353-357 (libm sincosf of the
- * float-narrowed phase step).  Returns the table length SDRINRATE/25000. */
+ * float-narrowed phase step) for n = 0 .. vdl2gpu_lo_len(sdrinrate) - 1.  Returns that length, or
+ * VDL2GPU_EINVAL if max_complex is smaller. */
 int vdl2gpu_lo_table(unsigned sdrinrate, int fo_hz, float *out_re_im, int max_complex);
 /* Integrate-and-dump schedule of one push (d8psk.c:374-381 in closed form). */
 int vdl2gpu_plan(uint64_t total_in, uint64_t n, unsigned sdrclk, unsigned lo_len,
@@ -422,6 +437,10 @@ int vdl2gpu_choose_fc_air(const unsigned *fr, int nbch, unsigned sdrinrate, unsi
 int64_t vdl2gpu_debug_dec(vdl2gpu_t *h, int stream, int ch, float *out, int64_t max_complex);
 /* Local-oscillator table of (stream, channel index): len complex values. */
 int vdl2gpu_debug_lo(vdl2gpu_t *h, int stream, int ch, float *out, int max_complex);
+/* Channeliser launches since vdl2gpu_create, by kernel (announced by VDL2GPU_HAVE_OFFGRID_RATES): out[0] k1_channelise with the
+ * LO table in LDS, out[1] k1_channelise with the table in global memory (off-grid rates whose table does not fit LDS),
+ * out[2] k1_pp, out[3] k1_fast.  Writes min(n, 4) counters and returns that number. */
+int vdl2gpu_debug_k1(vdl2gpu_t *h, unsigned long long *out, int n);
 /* Trigger candidates of the last push's sync scan, 6 x int32 each {nrel, r, p2err, perr, err, pfr bits}. */
 int vdl2gpu_debug_cands(vdl2gpu_t *h, int stream, int ch, int *out, int max_cands);
 /* ... and what follows each of them (one int2 per candidate: where the idle search resumes, relative to the push's planes; status |

@@ -136,6 +136,8 @@ struct vdl2gpu {
 	vdl2gpu_config_t cfg;
 	std::vector<vdl2gpu_chan_t> chans;
 	int S, C, L, maxwin, sdrclk;
+	unsigned long long k1_launches[4] = {0, 0, 0, 0};	/* vdl2gpu_debug_k1: k1_channelise (table in LDS), k1_channelise (table in global memory), k1_pp, k1_fast */
+	bool k1_glo = false;	/* k1_channelise reads the LO table from global memory (off-grid rates whose table does not fit LDS) */
 	size_t sample_bytes;
 	long long cap;		/* frames per stream per ping-pong buffer */
 	/* what the handle owns: see dev_alloc ... release_owned */
@@ -307,11 +309,26 @@ extern "C" unsigned int reversebits(const unsigned int bits, const int n)
 	return r;
 }
 
+/* Length of the LO table: the period of cexpf(-n*Fo*I) in n for a channel offset on the 25 kHz grid,
+ * SDRINRATE / gcd(SDRINRATE, 25000).  Where 25 kHz divides the rate that is the reference's SDRINRATE/STEPRATE
+ * (d8psk.c:348); off that grid the reference's table is no whole period (a phase jump every 81 samples at
+ * 2.048 MS/s), and the formula is carried over its true period instead: 2048 entries there. */
+extern "C" int vdl2gpu_lo_len(unsigned sdrinrate)
+{
+	unsigned a = sdrinrate, b = 25000u;
+	while (b) {
+		const unsigned t = a % b;
+		a = b;
+		b = t;
+	}
+	return a ? (int)(sdrinrate / a) : 0;
+}
+
 /* d8psk.c:353-357: wf[n] = cexpf(-n*Fo*I) with Fo narrowed to float.  cexpf of a
  * purely imaginary argument is (cos, sin) from libm's sincosf. */
 extern "C" int vdl2gpu_lo_table(unsigned sdrinrate, int fo_hz, float *out_re_im, int max_complex)
 {
-	const int L = (int)(sdrinrate / 25000u);
+	const int L = vdl2gpu_lo_len(sdrinrate);
 	if (L <= 0 || L > max_complex)
 		return VDL2GPU_EINVAL;
 	const float w = (float)((double)((float)fo_hz / (float)sdrinrate) * 2.0 * M_PI);
@@ -688,6 +705,20 @@ static size_t k1_smem_bytes(uint64_t L, uint64_t maxwin)
 {
 	return (size_t)(((L + maxwin) * VDL2_CS + (uint64_t)K1_OPB * maxwin) * sizeof(float2));
 }
+/* Rates off the 25 kHz grid have LO tables of thousands of entries (vdl2gpu_lo_len), which need not fit beside the windows:
+ * what must fit is the window part of the bound above (the table's maxwin rows of wrap-around and the pass's windows); where the
+ * whole does not, the handle runs the variant of k1_channelise that leaves the table in global memory (k1_glo_table). */
+static size_t k1_win_bytes(uint64_t maxwin)
+{
+	return k1_smem_bytes(0, maxwin);
+}
+/* dynamic LDS of that variant: the pass's windows and the staging tile of LO values, 256 * maxwin + 32 KiB.  Within the limit
+ * wherever k1_win_bytes (320 * maxwin) is: both reach 160 KiB at maxwin = 512 */
+static size_t k1_glo_smem_bytes(uint64_t maxwin)
+{
+	return (size_t)(((uint64_t)K1_OPB * maxwin + (uint64_t)K1G_T * K1_THREADS) * sizeof(float2));
+}
+static_assert(((size_t)K1_OPB * 512 + (size_t)K1G_T * K1_THREADS) * sizeof(float2) <= VDL2_K1_LDS_MAX, "k1_channelise<.., true>: windows of 512 and the staging tile");
 
 /* One kind of table for every set in turn (so the sets' tables lie as they always did: kind by kind). */
 template <class T> static int alloc_table(vdl2gpu_t *h, T *K2Params::*m, size_t bytes, const char *what, bool zero = false)
@@ -1037,8 +1068,11 @@ extern "C" int vdl2gpu_create(const vdl2gpu_config_t *cfg, vdl2gpu_t **out)
 		return VDL2GPU_EINVAL;
 	if (cfg->nbch < 1 || cfg->nbch > VDL2GPU_MAXCH || cfg->nstreams < 1 || !cfg->chan || !cfg->max_push)
 		return VDL2GPU_EINVAL;
-	if (fmt_bytes(cfg->fmt) == 0 || cfg->sdrinrate < 100000 || cfg->sdrinrate % 25000)
+	if (fmt_bytes(cfg->fmt) == 0 || cfg->sdrinrate < 100000)
 		return VDL2GPU_EINVAL;
+	const bool offgrid = cfg->sdrinrate % 25000 != 0;	/* include/vdl2gpu.h, sdrinrate: "off the 25 kHz grid" */
+	if (offgrid && (cfg->sdrinrate % 1000 || (cfg->flags & VDL2GPU_F_RTL_QUIRK)))
+		return VDL2GPU_EINVAL;	/* (the quirk is the reference's RTL front end at its own rates) */
 	if ((cfg->flags & VDL2GPU_F_RTL_QUIRK) && cfg->fmt != VDL2GPU_FMT_CU8)
 		return VDL2GPU_EINVAL;	/* the quirk is in_callback()'s, and that only ever sees cu8 */
 #ifndef VDL2GPU_TESTHOOKS
@@ -1048,7 +1082,13 @@ extern "C" int vdl2gpu_create(const vdl2gpu_config_t *cfg, vdl2gpu_t **out)
 	const unsigned sdrclk = cfg->sdrclk ? cfg->sdrclk : cfg->sdrinrate / 4000;
 	if (sdrclk <= 21 || sdrclk > 1000000)
 		return VDL2GPU_EINVAL;
-	if (k1_smem_bytes(cfg->sdrinrate / 25000, (sdrclk + 20) / 21) > VDL2_K1_LDS_MAX)
+	const unsigned lo_len = (unsigned)vdl2gpu_lo_len(cfg->sdrinrate);
+	if (offgrid) {
+		/* the table is a whole period of the LO only for offsets on the 25 kHz grid, and a period of the dump schedule
+		 * (4 * SDRCLK inputs) must be whole tables: SDRINRATE = 4000 * SDRCLK */
+		if ((4ull * sdrclk) % lo_len || k1_win_bytes((sdrclk + 20) / 21) > VDL2_K1_LDS_MAX)
+			return VDL2GPU_EINVAL;	/* (above 43.0 MS/s at the default SDRCLK) */
+	} else if (k1_smem_bytes(lo_len, (sdrclk + 20) / 21) > VDL2_K1_LDS_MAX)
 		return VDL2GPU_EINVAL;	/* the general channeliser's LDS (above 25.7 MS/s at the default SDRCLK) */
 	const long long cap = plane_frames(cfg->max_push, sdrclk);
 	if (cap == 0 || (unsigned long long)cap * VDL2_CS * sizeof(float2) >= VDL2_PLANES_MAX)
@@ -1059,9 +1099,10 @@ extern "C" int vdl2gpu_create(const vdl2gpu_config_t *cfg, vdl2gpu_t **out)
 	h->cfg = *cfg;
 	h->S = cfg->nstreams;
 	h->C = cfg->nbch;
-	h->L = (int)(cfg->sdrinrate / 25000);	/* SDRINRATE/STEPRATE, d8psk.c:348 */
+	h->L = (int)lo_len;	/* SDRINRATE/STEPRATE, d8psk.c:348; off the 25 kHz grid the LO's true period */
 	h->sdrclk = (int)sdrclk;
 	h->maxwin = (h->sdrclk + 20) / 21;
+	h->k1_glo = offgrid && k1_smem_bytes((uint64_t)h->L, (uint64_t)h->maxwin) > VDL2_K1_LDS_MAX;
 	h->sample_bytes = fmt_bytes(cfg->fmt);
 	h->rec_cap = cfg->max_bursts ? cfg->max_bursts : 65536u;
 	h->chans.assign(cfg->chan, cfg->chan + (size_t)cfg->nstreams * cfg->nbch);
@@ -1724,7 +1765,8 @@ static int enqueue_k1(vdl2gpu_t *h, K1Params &k1, const Input &in, size_t nsampl
 	k1.cap = h->cap;
 	k1.ss = h->d_ss;
 	const long long per_block = K1_OPB * K1_PASSES;
-	const size_t smem = k1_smem_bytes((uint64_t)h->L, (uint64_t)h->maxwin);	/* <= VDL2_K1_LDS_MAX (vdl2gpu_create) */
+	/* <= VDL2_K1_LDS_MAX either way (vdl2gpu_create) */
+	const size_t smem = h->k1_glo ? k1_glo_smem_bytes((uint64_t)h->maxwin) : k1_smem_bytes((uint64_t)h->L, (uint64_t)h->maxwin);
 	auto generic = [&](long long jbeg, long long jend) {
 		if (jend < jbeg)
 			return;
@@ -1733,7 +1775,11 @@ static int enqueue_k1(vdl2gpu_t *h, K1Params &k1, const Input &in, size_t nsampl
 		q.jend = jend;
 		const unsigned gx = (unsigned)((jend - jbeg + 1 + per_block - 1) / per_block);
 		const dim3 grid(gx, (unsigned)GS);
-		with_fmt(h->cfg.fmt, [&](auto F) { hipLaunchKernelGGL(k1_channelise<decltype(F)::value>, grid, dim3(K1_THREADS), smem, ks, q); });
+		++h->k1_launches[h->k1_glo ? 1 : 0];
+		if (h->k1_glo)
+			with_fmt(h->cfg.fmt, [&](auto F) { hipLaunchKernelGGL((k1_channelise<decltype(F)::value, true>), grid, dim3(K1_THREADS), smem, ks, q); });
+		else
+			with_fmt(h->cfg.fmt, [&](auto F) { hipLaunchKernelGGL(k1_channelise<decltype(F)::value>, grid, dim3(K1_THREADS), smem, ks, q); });
 	};
 	const K1Choice ch = choose_k1(h, k1.c0, J, nsamples, in.src, in.stride);
 	const bool whole = ch.whole;
@@ -1781,6 +1827,7 @@ static int enqueue_k1(vdl2gpu_t *h, K1Params &k1, const Input &in, size_t nsampl
 					h->k1_tbase[(size_t)sg * 8 + x] += (unsigned)((n_x + K1F_CHUNK - 1) / K1F_CHUNK);
 		}
 		const dim3 grid((unsigned)ngrp * K1F_ROLES, (unsigned)GS);
+		++h->k1_launches[3];
 		with_fmt(h->cfg.fmt, [&](auto F) { hipLaunchKernelGGL(k1_fast<decltype(F)::value>, grid, dim3(K1F_THREADS), 0, ks, k1); });
 		if (staged)
 			(void)hipEventRecord(pt.e[9], ks);
@@ -1849,6 +1896,7 @@ static int enqueue_k1(vdl2gpu_t *h, K1Params &k1, const Input &in, size_t nsampl
 		if (staged)
 			(void)hipEventRecord(pt.e[8], ks);
 		const dim3 grid((unsigned)(blocks * kp.nsub), (unsigned)GS);
+		++h->k1_launches[2];
 		with_fmt(h->cfg.fmt, [&](auto F) { hipLaunchKernelGGL(k1_pp<decltype(F)::value>, grid, dim3(K1P_THREADS), 0, ks, kp); });
 		if (staged)
 			(void)hipEventRecord(pt.e[9], ks);
@@ -2866,6 +2914,19 @@ extern "C" int vdl2gpu_debug_counters(vdl2gpu_t *h, unsigned long long *out, int
 		HIPCHK(h, hipStreamSynchronize(h->stream));
 	}
 	return VDL2GPU_OK;
+}
+
+/* channeliser launches since the handle was created: {k1_channelise with the LO table in LDS, k1_channelise with the table in
+ * global memory, k1_pp, k1_fast}; returns how many of the four were written */
+extern "C" int vdl2gpu_debug_k1(vdl2gpu_t *h, unsigned long long *out, int n)
+{
+	if (!h || !out || n < 0)
+		return VDL2GPU_EINVAL;
+	HLOCK(h);
+	n = std::min(n, 4);
+	for (int i = 0; i < n; ++i)
+		out[i] = h->k1_launches[i];
+	return n;
 }
 
 /* candidates of (stream, channel index) found by the last push's sync scan: 6 ints per candidate

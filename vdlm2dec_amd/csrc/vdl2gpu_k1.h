@@ -48,15 +48,29 @@ template <int FMT> __device__ __forceinline__ float2 k1_load(const char *raw, lo
 	}
 }
 
-template <int FMT> __global__ __launch_bounds__(K1_THREADS)
-void k1_channelise(K1Params p)
+/* GLO (rates off the 25 kHz grid whose LO table does not fit LDS beside the windows: 3072 entries x 8 channels at 15.36 MS/s,
+ * 6144 at 30.72): the table stays in global memory -- a few hundred KB per stream, L2-resident -- and LDS holds the windows
+ * and a tile of LO values, K1G_T steps of every lane's window at a time.  A wavefront (2 channels x 32 windows) fills its own
+ * rows of the tile: 16 consecutive lanes load 16 consecutive table entries of a window's channel (8 bytes a lane, a 128-byte
+ * run; the index wraps at L), and every lane then takes its K1G_T values of step t from row t -- the same values in the same
+ * order as from the table in LDS, so the sums are the same floats. */
+#define K1G_T 16
+/* entry (step tt of the tile, lane row): rows rotated by tt, so that the 16 steps a loader writes side by side and the 64 lanes
+ * that read one step both spread over the banks */
+__device__ __forceinline__ int k1g_slot(int tt, int row)
+{
+	return tt * K1_THREADS + ((row + tt) & (K1_THREADS - 1));
+}
+
+template <int FMT, bool GLO> __device__ __forceinline__ void k1_channelise_body(const K1Params &p)
 {
 	extern __shared__ float2 k1_smem[];
-	float2 *lo_s = k1_smem;					/* [(L+maxwin)][8] */
-	float2 *xs = k1_smem + (size_t)(p.L + p.maxwin) * VDL2_CS;	/* [32*maxwin] */
+	float2 *lo_s = k1_smem;					/* [(L+maxwin)][8]; GLO: the tile [K1G_T][256] */
+	float2 *xs = k1_smem + (GLO ? (size_t)K1G_T * K1_THREADS : (size_t)(p.L + p.maxwin) * VDL2_CS);	/* [32*maxwin] */
 	const int tid = threadIdx.x;
 	const int s = (int)blockIdx.y;
 	const float2 *lo = p.lo + (size_t)s * VDL2_CS * p.L;
+	if (!GLO)
 	for (int idx = tid; idx < (p.L + p.maxwin) * VDL2_CS; idx += K1_THREADS) {
 		const int n = idx >> 3, c = idx & 7;
 		lo_s[idx] = lo[c * p.L + (n % p.L)];
@@ -95,6 +109,66 @@ void k1_channelise(K1Params p)
 			xs[i] = k1_load<FMT>(raw, in_lo + i);
 		__syncthreads();
 		const long long j = jp + o;
+		/* (the two branches share their set-up and their mixer loops in text only: with them factored out the compiler allots
+		 * the LDS kernels other registers, and those kernels are to stay instruction for instruction what they were) */
+		if constexpr (GLO) {
+			const bool on = j <= p.jend && c < p.nbch;
+			long long a = 0;
+			int n = 0;
+			if (on) {
+				a = (j == 0) ? 0 : k1_win_end(j - 1, p.sdrclk, p.c0) + 1;
+				n = (int)(((j == p.J) ? p.N - 1 : k1_win_end(j, p.sdrclk, p.c0)) - a + 1);
+			}
+			const float2 *xp = xs + (int)(a - in_lo);
+			const int w0 = (int)((p.no0 + a) % p.L);	/* table index of the window's first step */
+			float dre = 0.0f, dim = 0.0f;
+			int nf = n;
+			if (on && j == 0) {
+				const float2 cy = ss->acc[p.parity][c];
+				dre = cy.x;
+				dim = cy.y;
+				nf += p.nf0;
+			}
+			const int lane = tid & 63, wrow = tid & ~63;
+			for (int t0 = 0; t0 < p.maxwin; t0 += K1G_T) {	/* (uniform: every window is maxwin steps at most) */
+				__syncthreads();	/* the previous tile has been read */
+#pragma unroll 4
+				for (int it = 0; it < K1G_T; ++it) {
+					const int e = it * 64 + lane;
+					const int rr = e / K1G_T, tt = e % K1G_T;	/* the wavefront's lane rr, step t0 + tt of its window */
+					const int rw = __shfl(w0, rr), rn = __shfl(n, rr);
+					if (t0 + tt < rn)	/* a true modulo: with a custom SDRCLK a window can be many tables long (L = 128, maxwin = 512) */
+						lo_s[k1g_slot(tt, wrow + rr)] = lo[((wrow + rr) >> 5) * p.L + (rw + t0 + tt) % p.L];
+				}
+				__syncthreads();
+				const int te = (n - t0 < K1G_T) ? n - t0 : K1G_T;
+				if (K1_REAL(FMT)) {
+					for (int t = 0; t < te; ++t) {
+						const float x = xp[t0 + t].x;
+						const float2 w = lo_s[k1g_slot(t, tid)];
+						dre += x * w.x;
+						dim += x * w.y;
+					}
+				} else {
+					for (int t = 0; t < te; ++t) {
+						const float2 x = xp[t0 + t];
+						const float2 w = lo_s[k1g_slot(t, tid)];
+						const float pr = x.x * w.x - x.y * w.y;
+						const float pi = x.x * w.y + x.y * w.x;
+						dre += pr;
+						dim += pi;
+					}
+				}
+			}
+			if (on) {
+				if (j == p.J) {
+					ss->acc[p.parity ^ 1][c] = make_float2(dre, dim);
+				} else {
+					const float fn = (float)nf;
+					dec[j] = make_float2(dre / fn, dim / fn);
+				}
+			}
+		} else
 		if (j <= p.jend && c < p.nbch) {
 			const long long a = (j == 0) ? 0 : k1_win_end(j - 1, p.sdrclk, p.c0) + 1;
 			const long long b = (j == p.J) ? p.N - 1 : k1_win_end(j, p.sdrclk, p.c0);
@@ -136,6 +210,19 @@ void k1_channelise(K1Params p)
 	}
 }
 
+template <int FMT> __global__ __launch_bounds__(K1_THREADS)
+void k1_channelise(K1Params p)
+{
+	k1_channelise_body<FMT, false>(p);
+}
+
+/* the variant with the LO table in global memory: the second template parameter, so that the kernels above keep their names */
+template <int FMT, bool GLO> __global__ __launch_bounds__(K1_THREADS)
+void k1_channelise(K1Params p)
+{
+	static_assert(GLO, "k1_channelise<FMT> is the kernel with the table in LDS");
+	k1_channelise_body<FMT, true>(p);
+}
 
 /* ---- K1 fast path: whole periods of the schedule, any rate ----------------------------
  * The dump schedule and the LO phase repeat every PER = 4*SDRCLK inputs = 84 outputs (1 ms of air

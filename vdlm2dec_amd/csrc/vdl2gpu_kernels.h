@@ -4,8 +4,8 @@
  * Data layout in HBM
  *   raw      wideband IQ exactly as the SDR delivers it (cu8 / cs16 / cf32 /
  *            real f32), one contiguous run per stream; read ONCE by K1.
- *   lo       per (stream, channel) local-oscillator table, L = SDRINRATE/25000
- *            complex floats, computed on the host with libm (d8psk.c:353-357).
+ *   lo       per (stream, channel) local-oscillator table, L = vdl2gpu_lo_len(SDRINRATE)
+ *            (SDRINRATE/25000 on the 25 kHz grid, SDRINRATE/gcd(SDRINRATE, 25000) off it) complex floats, computed on the host with libm (d8psk.c:353-357).
  *   dec      84 kS/s channel planes: plane (stream, channel) = `cap` float2,
  *            three sets used in turn.  K1 writes from frame VDL2_CARRY_FRAMES on, K2* read, K3 copies
  *            the last VDL2_CARRY_FRAMES frames below frame VDL2_CARRY_FRAMES of the next

@@ -284,6 +284,13 @@ class Receiver:
         self._check(int(n))
         return buf[:2 * n].view(np.complex64).copy()
 
+    def debug_k1(self) -> dict:
+        """channeliser launches since the handle was created, by kernel: k1_channelise with the LO table in LDS (`general_lds`) or in
+        global memory (`general_global`: rates off the 25 kHz grid whose table does not fit LDS), `k1_pp`, `k1_fast`"""
+        buf = (C.c_ulonglong * 4)()
+        self._check(self.L.vdl2gpu_debug_k1(self.h, buf, 4))
+        return dict(zip(("general_lds", "general_global", "k1_pp", "k1_fast"), (int(v) for v in buf)))
+
     def debug_atan2f(self, y: np.ndarray, x: np.ndarray) -> np.ndarray:
         y = np.ascontiguousarray(y, np.float32)
         x = np.ascontiguousarray(x, np.float32)
@@ -373,7 +380,7 @@ def choose_fc(freqs: Sequence[int], sdrinrate: int = 2_000_000, tuner: str = "rt
 def lo_table(sdrinrate: int, fo: int) -> np.ndarray:
     """Host LO table exactly as the library uploads it (d8psk.c:353-357)."""
     L = _lib.load()
-    n = sdrinrate // STEPRATE
+    n = L.vdl2gpu_lo_len(sdrinrate)       # SDRINRATE / STEPRATE on the 25 kHz grid, the oscillator's true period off it
     buf = np.empty(2 * n, np.float32)
     rc = L.vdl2gpu_lo_table(sdrinrate, fo, buf.ctypes.data_as(C.c_void_p), n)
     if rc < 0:

@@ -31,9 +31,9 @@ EXPORTS = (
     "vdl2gpu_abi_version", "vdl2gpu_create", "vdl2gpu_destroy", "vdl2gpu_push", "vdl2gpu_sync",
     "vdl2gpu_ring_init", "vdl2gpu_ring_acquire", "vdl2gpu_ring_commit",
     "vdl2gpu_poll", "vdl2gpu_poll_ready", "vdl2gpu_poll_levels", "vdl2gpu_poll_levels_ready", "vdl2gpu_poll_soft", "vdl2gpu_poll_soft_ready", "vdl2gpu_pending", "vdl2gpu_inflight", "vdl2gpu_get_stats", "vdl2gpu_get_timing", "vdl2gpu_get_host_profile", "vdl2gpu_last_error",
-    "vdl2gpu_strerror", "vdl2gpu_burst_to_msgblk", "vdl2gpu_decode_blocks", "vdl2gpu_decode_blocks_soft", "vdl2gpu_poll_frames", "vdl2gpu_poll_frames_ready", "reversebits", "vdl2gpu_lo_table", "vdl2gpu_plan",
+    "vdl2gpu_strerror", "vdl2gpu_burst_to_msgblk", "vdl2gpu_decode_blocks", "vdl2gpu_decode_blocks_soft", "vdl2gpu_poll_frames", "vdl2gpu_poll_frames_ready", "reversebits", "vdl2gpu_lo_len", "vdl2gpu_lo_table", "vdl2gpu_plan",
     "vdl2gpu_choose_fc_rtl", "vdl2gpu_choose_fc_air",
-    "vdl2gpu_debug_dec", "vdl2gpu_debug_lo", "vdl2gpu_debug_atan2f", "vdl2gpu_debug_counters", "vdl2gpu_debug_cands", "vdl2gpu_debug_clheads", "vdl2gpu_debug_fail", "vdl2gpu_debug_segs", "vdl2gpu_debug_heads",
+    "vdl2gpu_debug_dec", "vdl2gpu_debug_k1", "vdl2gpu_debug_lo", "vdl2gpu_debug_atan2f", "vdl2gpu_debug_counters", "vdl2gpu_debug_cands", "vdl2gpu_debug_clheads", "vdl2gpu_debug_fail", "vdl2gpu_debug_segs", "vdl2gpu_debug_heads",
 )
 
 
@@ -170,6 +170,8 @@ def load(testhooks: bool = False):
     L.vdl2gpu_poll_frames_ready.argtypes = [C.c_void_p, C.POINTER(FrameT), C.c_int]
     L.reversebits.restype = C.c_uint
     L.reversebits.argtypes = [C.c_uint, C.c_int]
+    L.vdl2gpu_lo_len.restype = C.c_int
+    L.vdl2gpu_lo_len.argtypes = [C.c_uint]
     L.vdl2gpu_lo_table.restype = C.c_int
     L.vdl2gpu_lo_table.argtypes = [C.c_uint, C.c_int, C.c_void_p, C.c_int]
     L.vdl2gpu_plan.restype = C.c_int
@@ -182,6 +184,8 @@ def load(testhooks: bool = False):
                                         C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.vdl2gpu_debug_dec.restype = C.c_int64
     L.vdl2gpu_debug_dec.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int64]
+    L.vdl2gpu_debug_k1.restype = C.c_int
+    L.vdl2gpu_debug_k1.argtypes = [C.c_void_p, C.POINTER(C.c_ulonglong), C.c_int]
     L.vdl2gpu_debug_lo.restype = C.c_int
     L.vdl2gpu_debug_lo.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int]
     L.vdl2gpu_debug_atan2f.restype = C.c_int

@@ -417,7 +417,7 @@ def _cli(argv=None) -> int:
     ap = argparse.ArgumentParser(prog="python -m vdlm2dec_amd.synth", description=_cli.__doc__)
     ap.add_argument("out", help="raw IQ file to write (interleaved I,Q in --fmt; real samples for f32 and s16)")
     ap.add_argument("--fmt", default="cu8", choices=["cu8", "cs16", "cf32", "f32", "cs8", "s16"])
-    ap.add_argument("--rate", type=int, default=2_000_000, help="SDRINRATE (2000000 rtl; 5000000/6000000 airspy; 10000000)")
+    ap.add_argument("--rate", type=int, default=2_000_000, help="SDRINRATE (2000000 rtl; 2048000 rtl_sdr's default; 5000000/6000000 airspy; 10000000; 1920000 .. 30720000)")
     ap.add_argument("--fo", type=int, nargs="+", default=list(DEFAULT_FO_8CH), help="channel offsets from the tuner centre, Hz")
     ap.add_argument("--seconds", type=float, default=2.0)
     ap.add_argument("--bursts-per-s", type=float, default=4.0, help="arrival rate per channel behind each burst")
