@@ -459,6 +459,10 @@ int vdl2gpu_debug_counters(vdl2gpu_t *h, unsigned long long *out, int n, int res
 int vdl2gpu_debug_heads(vdl2gpu_t *h, uint32_t *out, int max_entries);
 /* Device build of the fixed-sequence atan2f, elementwise (host arrays). */
 int vdl2gpu_debug_atan2f(vdl2gpu_t *h, const float *y, const float *x, float *out, size_t n);
+/* rs() (rs.c:81-291) of n rows on the device: rows n x 255 in/out, eras n x 6 in/out, ret[i] = what rs() returns
+ * (-1, or the number of roots with eras[6 i .. 6 i + ret[i]) their positions; 0 with eras untouched for zero syndromes).
+ * VDL2GPU_EINVAL: no_eras[i] outside 0..6, or one of a row's first no_eras[i] positions outside 0..254. */
+int vdl2gpu_debug_rs(vdl2gpu_t *h, uint8_t *rows, int *eras, const int *no_eras, int *ret, size_t n);
 
 #if defined(__GNUC__) || defined(__clang__)
 #pragma GCC visibility pop

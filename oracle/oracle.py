@@ -101,21 +101,24 @@ class Block:
         return f"Block(chn={self.chn}, nbrow={self.nbrow}, nlbyte={self.nlbyte}, trig={self.trig_dec}, end={self.end_dec})"
 
 
-def frames_of_block(nbrow: int, nlbyte: int, data: bytes) -> List[bytes]:
-    """Host block path (RS + HDLC unstuff + FCS) applied to one burst record."""
+def frames_of_block(nbrow: int, nlbyte: int, data: bytes, cap: int = 8192) -> List[bytes]:
+    """Host block path (RS + HDLC unstuff + FCS) applied to one burst record.  cap: room for the frames (2 + length bytes each);
+    vo_block_frames counts a frame that does not fit but does not store it, which is an error here, not a shorter list."""
     L = lib()
     vb = VoBlock()
     vb.nbrow, vb.nlbyte = nbrow, nlbyte
     C.memmove(vb.data, data, 8 * 255)
-    buf = (C.c_uint8 * 8192)()
+    buf = (C.c_uint8 * cap)()
     used = C.c_size_t(0)
     n = L.vo_block_frames(C.byref(vb), buf, len(buf), C.byref(used))
     raw = bytes(buf[:used.value])
     out, p = [], 0
-    for _ in range(n):
+    while p < len(raw):
         ln = raw[p] | (raw[p + 1] << 8)
         out.append(raw[p + 2:p + 2 + ln])
         p += 2 + ln
+    if len(out) != n or p != len(raw):
+        raise ValueError(f"{n} frames, {len(out)} of them in {cap} bytes: raise cap")
     return out
 
 

@@ -55,9 +55,10 @@ def _tx_block(rng, info_len, nerr_rows=()):
 
 
 def test_corrected_uncorrectable_and_random_rows(built, oracle):
-    """Everything rs() can meet: clean rows, 1..3 byte errors (corrected), 4+ (miscorrected or given
-    up half way -- the partially applied corrections must agree too), every FEC-shortening regime,
-    and rows of pure noise."""
+    """Frames of bursts whose rows are clean, carry 1..3 byte errors in their data bytes (corrected: the frame arrives), 4 and more
+    (no frame on either side, whatever rs() left in the row), over burst lengths in the three FEC-shortening regimes, and of
+    records of pure noise and of one repeated byte (no frame either).  What this observes is frames: a row rs() cannot repair, or
+    miscorrects, is compared row by row in test_gpu_rs.py, not here."""
     rng = np.random.default_rng(77)
     blocks = []
     for n in (1, 2, 3, 10, 28, 31, 60, 66, 70, 120, 247, 250, 400, 497, 900, 1500, 1900):
@@ -107,6 +108,49 @@ def test_block_path_in_the_pipeline(built, oracle):
             frames += rx.poll_frames()
             bursts += rx.poll()
     assert sorted(frames) == sorted(want) and len(want) >= 8
+    assert sorted((b.chn, b.nbrow, b.nlbyte, b.data) for b in bursts) == sorted(b.key() for b in ob)
+
+
+def _compact_scenario():
+    """One channel whose bursts reach every way a frame leaves the block kernel in the pipeline: a first frame of 199 and of 200
+    bytes (with its 56-byte head, exactly the record's 256-byte slot) and of 201 (the arena), frames of about 1000 and 1900 bytes,
+    two bursts of three nested frames (the second and third of a burst always go to the arena), ordinary short bursts between."""
+    import blocks_craft as K
+    rng = np.random.default_rng(2024)
+
+    def body(n):
+        return bytes(v if v != 0x7e else 0x7d for v in rng.integers(0, 256, n).tolist())
+
+    payloads = [K.frame(body(195)), None, K.frame(body(196)), K.nested(3, rng, first=20, more=30), K.frame(body(197)), None,
+                K.frame(body(1000)), None, K.nested(3, rng, first=150, more=120), K.frame(body(1900)), None]
+    bursts, t = [], 0.002
+    for i, p in enumerate(payloads):
+        b = synth.Burst(chan=0, t0=t, info=body(int(rng.integers(5, 60))), amp=40.0, cfo=float(rng.uniform(-200, 200)), raw_payload=p)
+        bursts.append(b)
+        t += b.duration() + 0.002
+    ns = (int((t + 0.004) * 2_000_000) + 32767) // 32768 * 32768
+    return synth.StreamSpec(rate=2_000_000, fo=[-50000], nsamples=ns, bursts=bursts, seed=12)
+
+
+def test_compact_slots_and_arena_in_the_pipeline(built, oracle):
+    from vdlm2dec_amd.demod import Receiver, plan_channels
+    spec = _compact_scenario()
+    assert spec.nsamples < 4_000_000
+    raw = synth.synth_stream(spec, "cs16")
+    ob = oracle.run_oracle(raw, "cs16", spec.rate, spec.fo, S.FC)
+    per = [oracle.frames_of_block(b.nbrow, b.nlbyte, b.data, cap=1 << 16) for b in ob]
+    want = sorted((0, b.chn, f) for b, fs in zip(ob, per) for f in fs)
+    assert sorted(len(fs) for fs in per) == [1] * 9 + [3, 3]
+    lens = [len(fs[0]) for fs in per]
+    assert {199, 200, 201} <= set(lens) and any(990 < n < 1100 for n in lens) and max(lens) > 1850
+    step = -(-spec.nsamples // 3)
+    with Receiver(spec.rate, plan_channels(S.FC, spec.fo), fmt="cs16", max_push=step, frames=True) as rx:
+        bursts, frames = [], []
+        for s0 in range(0, spec.nsamples, step):
+            rx.push(raw[2 * s0:2 * (s0 + step)])
+            frames += rx.poll_frames()
+            bursts += rx.poll()
+    assert sorted(frames) == want and len(want) == 15
     assert sorted((b.chn, b.nbrow, b.nlbyte, b.data) for b in bursts) == sorted(b.key() for b in ob)
 
 

@@ -2900,6 +2900,50 @@ extern "C" int vdl2gpu_debug_atan2f(vdl2gpu_t *h, const float *y, const float *x
 	return VDL2GPU_OK;
 }
 
+extern "C" int vdl2gpu_debug_rs(vdl2gpu_t *h, uint8_t *rows, int *eras, const int *no_eras, int *ret, size_t n)
+{
+	if (!h || n > 0x7fffffffu / 255 || (n && (!rows || !eras || !no_eras || !ret)))
+		return VDL2GPU_EINVAL;
+	for (size_t i = 0; i < n; ++i) {	/* rs()'s contract: at most NROOTS erasures, at positions of the row */
+		if (no_eras[i] < 0 || no_eras[i] > 6)
+			return VDL2GPU_EINVAL;
+		for (int k = 0; k < no_eras[i]; ++k)
+			if (eras[i * 6 + k] < 0 || eras[i * 6 + k] > 254)
+				return VDL2GPU_EINVAL;
+	}
+	HLOCK(h);
+	if (!n)
+		return VDL2GPU_OK;
+	HIPCHK(h, hipSetDevice(h->cfg.device));
+	int *d = nullptr;	/* eras[6n], no_eras[n], ret[n], then the rows */
+	HIPCHK(h, hipMalloc(&d, 8 * n * sizeof(int) + 255 * n));
+	int *const d_eras = d, *const d_ne = d + 6 * n, *const d_ret = d + 7 * n;
+	uint8_t *const d_rows = reinterpret_cast<uint8_t *>(d + 8 * n);
+	hipError_t e = hipMemcpyAsync(d_eras, eras, 6 * n * sizeof(int), hipMemcpyHostToDevice, h->stream);
+	if (e == hipSuccess)
+		e = hipMemcpyAsync(d_ne, no_eras, n * sizeof(int), hipMemcpyHostToDevice, h->stream);
+	if (e == hipSuccess)
+		e = hipMemcpyAsync(d_rows, rows, 255 * n, hipMemcpyHostToDevice, h->stream);
+	if (e == hipSuccess) {
+		hipLaunchKernelGGL(k4_rs_debug, dim3((unsigned)n), dim3(K4_NT), 0, h->stream, d_rows, d_eras, d_ne, d_ret, h->d_k4tab, (unsigned)n);
+		e = hipGetLastError();
+		if (e == hipSuccess)
+			e = hipStreamSynchronize(h->stream);
+	}
+	if (e == hipSuccess)
+		e = hipMemcpy(eras, d_eras, 6 * n * sizeof(int), hipMemcpyDeviceToHost);
+	if (e == hipSuccess)
+		e = hipMemcpy(ret, d_ret, n * sizeof(int), hipMemcpyDeviceToHost);
+	if (e == hipSuccess)
+		e = hipMemcpy(rows, d_rows, 255 * n, hipMemcpyDeviceToHost);
+	(void)hipFree(d);	/* (a call's temporary, like vdl2gpu_debug_atan2f's) */
+	if (e != hipSuccess) {
+		h->err = hipGetErrorString(e);
+		return VDL2GPU_EHIP;
+	}
+	return VDL2GPU_OK;
+}
+
 extern "C" int vdl2gpu_debug_counters(vdl2gpu_t *h, unsigned long long *out, int n, int reset)
 {
 	if (!h || !out || n < 0 || n > 64)

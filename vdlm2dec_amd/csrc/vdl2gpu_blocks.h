@@ -789,4 +789,45 @@ void k4_frames(K4Params p)
 #undef K4_STAMP
 }
 
+/* vdl2gpu_debug_rs: k4_rs_row as k4_frames calls it, one wavefront per row, so that a test can hold what it leaves in a row --
+ * repaired, miscorrected, given up half way -- against rs() itself.  ret: -1, or the number of roots (0: zero syndromes, eras untouched);
+ * eras[0..ret) are written back on success like the reference's eras_pos[]. */
+__global__ __launch_bounds__(K4_NT)
+void k4_rs_debug(uint8_t *rows, int *eras, const int *no_eras, int *ret, const unsigned *tabs, unsigned n)
+{
+	__shared__ K4Shared sh;
+	const int lane = threadIdx.x;
+	const unsigned ib = blockIdx.x;
+	if (ib >= n)
+		return;
+	for (int i = lane; i < K4_TABW; i += K4_NT)
+		reinterpret_cast<unsigned *>(sh.gexp)[i] = tabs[i];
+	unsigned sexp[4][2];	/* as in k4_frames */
+#pragma unroll
+	for (int b = 0; b < 4; ++b) {
+		const int j = lane * 4 + b;
+		sexp[b][0] = sexp[b][1] = 0;
+#pragma unroll
+		for (int i = 0; i < 6; ++i)
+			sexp[b][i / 4] |= (unsigned)k4_m255((120 + i) * (254 - (j < 255 ? j : 254))) << (8 * (i % 4));
+	}
+	uint8_t *const row = sh.src;
+	uint8_t *const grow = rows + (size_t)ib * 255;
+	for (int i = lane; i < 255; i += K4_NT)
+		row[i] = grow[i];
+	if (lane < 6)
+		sh.eras[lane] = eras[(size_t)ib * 6 + lane];
+	if (lane == 0)
+		sh.rs_count = 0;	/* zero syndromes: k4_rs_row returns before anything sets it */
+	K4_SYNC();
+	const bool ok = k4_rs_row(sh, row, no_eras[ib], sexp, lane);
+	const int count = ok ? sh.rs_count : -1;
+	for (int i = lane; i < 255; i += K4_NT)
+		grow[i] = row[i];
+	if (lane < count)
+		eras[(size_t)ib * 6 + lane] = sh.eras[lane];
+	if (lane == 0)
+		ret[ib] = count;
+}
+
 #endif

@@ -299,6 +299,18 @@ class Receiver:
                                                 out.ctypes.data_as(C.c_void_p), y.size))
         return out
 
+    def debug_rs(self, rows: np.ndarray, eras: np.ndarray, no_eras: np.ndarray):
+        """rs() (rs.c:81-291) of every row on the device, through the block kernel's own row decoder: rows (n, 255) uint8,
+        eras (n, 6) and no_eras (n,) int32 -> (ret, rows, eras) as rs() leaves them; the arguments are not modified."""
+        rows = np.array(rows, np.uint8, order="C").reshape(-1, 255)
+        n = rows.shape[0]
+        eras = np.array(eras, np.int32, order="C").reshape(n, 6)
+        no_eras = np.ascontiguousarray(no_eras, np.int32).reshape(n)
+        ret = np.zeros(n, np.int32)
+        self._check(self.L.vdl2gpu_debug_rs(self.h, rows.ctypes.data_as(C.c_void_p), eras.ctypes.data_as(C.c_void_p),
+                                            no_eras.ctypes.data_as(C.c_void_p), ret.ctypes.data_as(C.c_void_p), n))
+        return ret, rows, eras
+
     def debug_cands(self, stream: int, ch: int, max_cands: int = 6144) -> np.ndarray:
         buf = np.zeros((max_cands, 6), np.int32)
         n = self._check(self.L.vdl2gpu_debug_cands(self.h, stream, ch, buf.ctypes.data_as(C.c_void_p), max_cands))
