@@ -100,7 +100,8 @@ typedef struct {
 				 * that LDS, (maxwin * 8 + 32 * maxwin) * 8 bytes, stays within 160 KiB (the table itself need
 				 * not): at the default sdrclk maxwin <= 512, up to 43.0 MS/s, so 30.72 MS/s is accepted and 61.44 MS/s is not.
 				 * The table is a whole period of the local oscillator only for channel offsets Fo on the 25 kHz
-				 * grid, where VDL channels lie, as before.  VDL2GPU_F_RTL_QUIRK is VDL2GPU_EINVAL off the grid.
+				 * grid, where VDL channels lie; an offset off that grid gets the reference's phase jump every L
+				 * samples unless the handle has VDL2GPU_F_EXACT_FO.  VDL2GPU_F_RTL_QUIRK is VDL2GPU_EINVAL off the grid.
 				 * Anything else is VDL2GPU_EINVAL from vdl2gpu_create, before any device call. */
 	uint32_t sdrclk;	/* SDRCLK, in (21, 1000000] and within the LDS bound above; 0 = sdrinrate/4000 (rtl.c:37, air.c:138) */
 	int32_t fmt;		/* VDL2GPU_FMT_* */
@@ -140,6 +141,28 @@ typedef struct {
 #define VDL2GPU_F_LEVELS 128u	/* measure every burst's signal and noise level on the GPU: vdl2gpu_poll_levels() (see vdl2gpu_level_t) */
 #define VDL2GPU_F_SOFT_RS 256u	/* keep every payload byte's reliability (vdl2gpu_soft_t, vdl2gpu_poll_soft()); with VDL2GPU_F_FRAMES the
 				 * block path then rescues rows the reference cannot decode by erasing their least reliable bytes */
+
+/* ---- channel offsets off the 25 kHz grid (VDL2GPU_F_EXACT_FO; announced by VDL2GPU_HAVE_EXACT_FO, the ABI version is unchanged) ----
+ * The reference's LO table (d8psk.c:353-357) is indexed modulo L = SDRINRATE / 25000, so an offset Fo that is no multiple of
+ * 25 kHz gets a phase jump every L samples, and a handle without this flag reproduces that.  With the flag Fo
+ * may be any integer Hz with |Fo| < sdrinrate / 2, at every accepted rate, and the oscillator is phase-continuous:
+ *   Fg = 25000 * floor((Fo + 12500) / 25000),  Fd = Fo - Fg in [-12500, 12500).
+ *   1. The mixer runs as without the flag with the table vdl2gpu_lo_table(sdrinrate, Fg) (what vdl2gpu_debug_lo returns).
+ *   2. A channel with Fd == 0 is left alone: its plane has the bits a handle without the flag produces.
+ *   3. Otherwise every output D_m (the value after D /= nf, d8psk.c:377) is rotated by the residual oscillator at the centre
+ *      of its window.  With a_m, e_m the stream indices of the window's first and last input, R = sdrinrate and
+ *      fd = Fd mod 2R (non-negative):
+ *          k_m = (fd * ((a_m + e_m) mod 2R)) mod 2R          the phase index, angle -pi * k_m / R
+ *          r_m = T_hi[k_m >> 12] (x) T_lo[k_m & 4095]
+ *          D'_m = D_m (x) r_m
+ *      where x (x) y = (xr*yr - xi*yi, xr*yi + xi*yr) in float32, each product and the sum or difference rounded on its own.
+ *   4. T_hi[h] = ((float)cos(-pi*(h*4096)/R), (float)sin(..)) for h < ceil(2R/4096), T_lo[l] = ((float)cos(-pi*l/R),
+ *      (float)sin(..)) for l < 4096, computed in double precision on the host and narrowed once.
+ * The rotation happens inside the channeliser kernels where they dump; |r_m| = 1 to within 1e-7, so the scale of
+ * vdl2gpu_level_t is unaffected.  Together with VDL2GPU_F_RTL_QUIRK: VDL2GPU_EINVAL, before any device call (the quirk is for
+ * parity with the reference, jumps included).  vdl2gpu_exact_fo_tables / vdl2gpu_exact_fo_index below state 3. and 4. on the host. */
+#define VDL2GPU_F_EXACT_FO 512u
+#define VDL2GPU_HAVE_EXACT_FO 1
 
 /* One decoded burst = the msgblk_t fields the DSP fills (vdlm2.h:39-47). */
 typedef struct {
@@ -415,6 +438,13 @@ int vdl2gpu_lo_table(unsigned sdrinrate, int fo_hz, float *out_re_im, int max_co
 /* Integrate-and-dump schedule of one push (d8psk.c:374-381 in closed form). */
 int vdl2gpu_plan(uint64_t total_in, uint64_t n, unsigned sdrclk, unsigned lo_len,
 		 int *c0, int *no0, int *nf0, int64_t *nout);
+/* VDL2GPU_F_EXACT_FO: the rotation tables of a rate, interleaved re,im: T_hi into hi_re_im (max_hi complex values of room),
+ * the 4096 entries of T_lo into lo_re_im; either may be NULL.  Returns the length of T_hi, ceil(2 * sdrinrate / 4096), or
+ * VDL2GPU_EINVAL (a rate of 0 or above 2^30, max_hi too small). */
+int vdl2gpu_exact_fo_tables(unsigned sdrinrate, float *hi_re_im, int max_hi, float *lo_re_im);
+/* ... and the phase index k of the window whose first and last inputs are samples a and e of the stream, for a residual
+ * offset of fd_hz: (fd * ((a + e) mod 2R)) mod 2R, fd = fd_hz mod 2R taken non-negative.  VDL2GPU_EINVAL for such a rate. */
+int64_t vdl2gpu_exact_fo_index(uint64_t a, uint64_t e, unsigned sdrinrate, int fd_hz);
 /* Frequency planning: the tuner centre the reference picks for a list of channel
  * frequencies, and the per-channel mixer offsets Fo it derives (thread_param_t.Fo).
  *   rtl: chooseFc() of rtl.c:123-160 -- the highest Fc (1 Hz steps, downwards from max + 50 kHz) that keeps every
@@ -435,7 +465,7 @@ int vdl2gpu_choose_fc_air(const unsigned *fr, int nbch, unsigned sdrinrate, unsi
 /* Decimated samples of the LAST push of (stream, channel index), interleaved
  * re,im; needs VDL2GPU_F_KEEP_DEC.  Returns the number of complex samples. */
 int64_t vdl2gpu_debug_dec(vdl2gpu_t *h, int stream, int ch, float *out, int64_t max_complex);
-/* Local-oscillator table of (stream, channel index): len complex values. */
+/* Local-oscillator table of (stream, channel index): len complex values (with VDL2GPU_F_EXACT_FO: the table of Fg). */
 int vdl2gpu_debug_lo(vdl2gpu_t *h, int stream, int ch, float *out, int max_complex);
 /* Channeliser launches since vdl2gpu_create, by kernel (announced by VDL2GPU_HAVE_OFFGRID_RATES): out[0] k1_channelise with the
  * LO table in LDS, out[1] k1_channelise with the table in global memory (off-grid rates whose table does not fit LDS),

@@ -161,6 +161,10 @@ struct vdl2gpu {
 	std::vector<hipEvent_t> ring_copied;
 	std::vector<char> ring_inflight;
 	float2 *d_lo = nullptr;
+	bool rot = false;		/* VDL2GPU_F_EXACT_FO with a channel off the 25 kHz grid: the rotating instantiations of the K1 kernels run */
+	K1Rot k1rot{};			/* their second argument: the tables (create_impl), and the push's place in the schedule (push) */
+	unsigned *d_rot_tab = nullptr;	/* [S][8][K1R_TAB] */
+	float2 *d_rot_hi = nullptr, *d_rot_lo = nullptr;	/* T_hi, T_lo: one pair for all channels of the handle */
 	unsigned *d_k1_tickets = nullptr;	/* k1_fast's work counters */
 	std::vector<unsigned> k1_tbase;	/* [S][8] what they hold, per stream and XCD (the same for every role; the same for every stream between two calls) */
 	int last_set = 0;		/* the table / plane set of the last push (the debug calls read it) */
@@ -361,6 +365,52 @@ extern "C" int vdl2gpu_plan(uint64_t total_in, uint64_t n, unsigned sdrclk, unsi
 	*nf0 = (int)(total_in - first);
 	*nout = (int64_t)(((uint64_t)*c0 + 21ull * n) / sdrclk);
 	return VDL2GPU_OK;
+}
+
+/* VDL2GPU_F_EXACT_FO (include/vdl2gpu.h): the two tables of the residual oscillator, angle -pi k / R for the phase index k < 2 R
+ * split as k = 4096 h + l; double precision narrowed once.  Either table may be NULL (the call then only returns T_hi's length). */
+extern "C" int vdl2gpu_exact_fo_tables(unsigned sdrinrate, float *hi_re_im, int max_hi, float *lo_re_im)
+{
+	if (!sdrinrate || sdrinrate > (1u << 30))
+		return VDL2GPU_EINVAL;
+	const int nhi = (int)((2ull * sdrinrate + 4095) / 4096);
+	if (hi_re_im && max_hi < nhi)
+		return VDL2GPU_EINVAL;
+	const double R = (double)sdrinrate;
+	if (hi_re_im)
+		for (int h = 0; h < nhi; ++h) {
+			const double th = -M_PI * (double)(4096ull * (unsigned)h) / R;
+			hi_re_im[2 * h] = (float)cos(th);
+			hi_re_im[2 * h + 1] = (float)sin(th);
+		}
+	if (lo_re_im)
+		for (int l = 0; l < 4096; ++l) {
+			const double th = -M_PI * (double)l / R;
+			lo_re_im[2 * l] = (float)cos(th);
+			lo_re_im[2 * l + 1] = (float)sin(th);
+		}
+	return nhi;
+}
+
+/* ... and the phase index of the window whose first and last inputs are samples a and e of the stream:
+ * (fd * ((a + e) mod 2 R)) mod 2 R with fd = fd_hz mod 2 R taken non-negative */
+extern "C" int64_t vdl2gpu_exact_fo_index(uint64_t a, uint64_t e, unsigned sdrinrate, int fd_hz)
+{
+	if (!sdrinrate || sdrinrate > (1u << 30))
+		return VDL2GPU_EINVAL;
+	const uint64_t M = 2ull * sdrinrate;
+	int64_t f = (int64_t)fd_hz % (int64_t)M;
+	if (f < 0)
+		f += (int64_t)M;
+	const uint64_t sum = (a % M + e % M) % M;
+	return (int64_t)(((unsigned __int128)(uint64_t)f * sum) % M);
+}
+
+/* the 25 kHz grid point a channel offset is mixed with under VDL2GPU_F_EXACT_FO: 25000 * floor((Fo + 12500) / 25000) */
+static int exact_fo_grid(int fo)
+{
+	const long long t = (long long)fo + 12500;
+	return (int)(25000 * (t >= 0 ? t / 25000 : -((-t + 24999) / 25000)));
 }
 
 /* chooseFc() of rtl.c:123-160 (the tuner centre for a list of channel frequencies) and the mixer offsets of
@@ -1008,7 +1058,8 @@ static int create_impl(vdl2gpu_t *h)
 	for (int s = 0; s < S; ++s)
 		for (int c = 0; c < h->C; ++c) {
 			const vdl2gpu_chan_t &ch = h->chans[(size_t)s * h->C + c];
-			vdl2gpu_lo_table(cfg.sdrinrate, ch.Fo, tmp.data(), L);
+			/* VDL2GPU_F_EXACT_FO: the mixer takes the grid point next to Fo, the dump the rest (rot_tab below) */
+			vdl2gpu_lo_table(cfg.sdrinrate, (cfg.flags & VDL2GPU_F_EXACT_FO) ? exact_fo_grid(ch.Fo) : ch.Fo, tmp.data(), L);
 			for (int n = 0; n < L; ++n)
 				lo[((size_t)s * VDL2_CS + c) * L + n] = make_float2(tmp[2 * n], tmp[2 * n + 1]);
 			cc[(size_t)s * VDL2_CS + c] = ChanCfg{ ch.chn, ch.Fr, ch.Fo, 0 };
@@ -1020,6 +1071,41 @@ static int create_impl(vdl2gpu_t *h)
 			loe[sc * (L + 48) + n] = lo[sc * L + ((n + L - 8) % L)];
 	HIPCHK(h, hipMemcpyAsync(h->d_lo_ext, loe.data(), loe.size() * sizeof(float2), hipMemcpyHostToDevice, h->stream));
 	HIPCHK(h, hipMemcpyAsync(h->d_cfg, cc.data(), cc.size() * sizeof(ChanCfg), hipMemcpyHostToDevice, h->stream));
+	std::vector<unsigned> rtab;	/* (these outlive the copies below: the stream is synchronised at the end) */
+	std::vector<float> rhi, rlo;
+	if (cfg.flags & VDL2GPU_F_EXACT_FO) {
+		const unsigned R = cfg.sdrinrate, clk = (unsigned)h->sdrclk;
+		const uint64_t M = 2ull * R;
+		rtab.assign((size_t)S * VDL2_CS * K1R_TAB, 0u);
+		for (int s = 0; s < S; ++s)
+			for (int c = 0; c < h->C; ++c) {
+				const int fo = h->chans[(size_t)s * h->C + c].Fo, fd = fo - exact_fo_grid(fo);
+				unsigned *t = &rtab[((size_t)s * VDL2_CS + c) * K1R_TAB];
+				for (unsigned i = 0; i < 21; ++i)	/* window i of the schedule's first period: inputs ceil(i clk / 21) .. ceil((i + 1) clk / 21) - 1 */
+					t[i] = (unsigned)vdl2gpu_exact_fo_index(((uint64_t)i * clk + 20) / 21, ((uint64_t)(i + 1) * clk + 20) / 21 - 1, R, fd);
+				t[21] = (unsigned)vdl2gpu_exact_fo_index(clk, clk, R, fd);	/* a period on: a + e grows by 2 SDRCLK */
+				t[22] = (unsigned)(((int64_t)fd % (int64_t)M + (int64_t)M) % (int64_t)M);
+				t[23] = fd != 0;
+				h->rot = h->rot || fd != 0;
+			}
+	}
+	if (h->rot) {
+		const int nhi = vdl2gpu_exact_fo_tables(cfg.sdrinrate, nullptr, 0, nullptr);
+		rhi.resize(2 * (size_t)nhi);
+		rlo.resize(2 * 4096);
+		vdl2gpu_exact_fo_tables(cfg.sdrinrate, rhi.data(), nhi, rlo.data());
+		DEV_ALLOC(h, h->d_rot_tab, rtab.size() * sizeof(unsigned));
+		DEV_ALLOC(h, h->d_rot_hi, rhi.size() * sizeof(float));
+		DEV_ALLOC(h, h->d_rot_lo, rlo.size() * sizeof(float));
+		HIPCHK(h, hipMemcpyAsync(h->d_rot_tab, rtab.data(), rtab.size() * sizeof(unsigned), hipMemcpyHostToDevice, h->stream));
+		HIPCHK(h, hipMemcpyAsync(h->d_rot_hi, rhi.data(), rhi.size() * sizeof(float), hipMemcpyHostToDevice, h->stream));
+		HIPCHK(h, hipMemcpyAsync(h->d_rot_lo, rlo.data(), rlo.size() * sizeof(float), hipMemcpyHostToDevice, h->stream));
+		h->k1rot.tab = h->d_rot_tab;
+		h->k1rot.hi = h->d_rot_hi;
+		h->k1rot.lo = h->d_rot_lo;
+		h->k1rot.M = 2u * cfg.sdrinrate;
+		h->k1rot.rM = 1.0 / (double)h->k1rot.M;
+	}
 
 	/* scrambler sequence from seed 0x4D4B (d8psk.c:54-65, 299): identical for every burst */
 	std::vector<uint8_t> pn(VDL2_PN_BITS);
@@ -1075,6 +1161,13 @@ extern "C" int vdl2gpu_create(const vdl2gpu_config_t *cfg, vdl2gpu_t **out)
 		return VDL2GPU_EINVAL;	/* (the quirk is the reference's RTL front end at its own rates) */
 	if ((cfg->flags & VDL2GPU_F_RTL_QUIRK) && cfg->fmt != VDL2GPU_FMT_CU8)
 		return VDL2GPU_EINVAL;	/* the quirk is in_callback()'s, and that only ever sees cu8 */
+	if (cfg->flags & VDL2GPU_F_EXACT_FO) {
+		if (cfg->flags & VDL2GPU_F_RTL_QUIRK)
+			return VDL2GPU_EINVAL;	/* (the quirk is for parity with the reference, and that includes its LO's jumps) */
+		for (size_t i = 0; i < (size_t)cfg->nstreams * cfg->nbch; ++i)
+			if (2ll * std::llabs((long long)cfg->chan[i].Fo) >= (long long)cfg->sdrinrate)
+				return VDL2GPU_EINVAL;	/* |Fo| < SDRINRATE / 2 */
+	}
 #ifndef VDL2GPU_TESTHOOKS
 	if (cfg->flags & VDL2GPU_F_TEST_NOREGION)
 		return VDL2GPU_EINVAL;	/* test handicaps are compiled into libvdl2gpu_test.so only */
@@ -1776,7 +1869,11 @@ static int enqueue_k1(vdl2gpu_t *h, K1Params &k1, const Input &in, size_t nsampl
 		const unsigned gx = (unsigned)((jend - jbeg + 1 + per_block - 1) / per_block);
 		const dim3 grid(gx, (unsigned)GS);
 		++h->k1_launches[h->k1_glo ? 1 : 0];
-		if (h->k1_glo)
+		if (h->rot && h->k1_glo)
+			with_fmt(h->cfg.fmt, [&](auto F) { hipLaunchKernelGGL((k1_channelise<decltype(F)::value, true, true>), grid, dim3(K1_THREADS), smem, ks, q, h->k1rot); });
+		else if (h->rot)
+			with_fmt(h->cfg.fmt, [&](auto F) { hipLaunchKernelGGL((k1_channelise<decltype(F)::value, false, true>), grid, dim3(K1_THREADS), smem, ks, q, h->k1rot); });
+		else if (h->k1_glo)
 			with_fmt(h->cfg.fmt, [&](auto F) { hipLaunchKernelGGL((k1_channelise<decltype(F)::value, true>), grid, dim3(K1_THREADS), smem, ks, q); });
 		else
 			with_fmt(h->cfg.fmt, [&](auto F) { hipLaunchKernelGGL(k1_channelise<decltype(F)::value>, grid, dim3(K1_THREADS), smem, ks, q); });
@@ -1805,7 +1902,7 @@ static int enqueue_k1(vdl2gpu_t *h, K1Params &k1, const Input &in, size_t nsampl
 		 * SIMDs' wavefront slots empty. */
 		long long ngrp;
 		{
-			const long long slots = (long long)h->n_cu * 2 * K1F_WAVES_OF(h->cfg.fmt);
+			const long long slots = (long long)h->n_cu * 2 * (h->rot ? K1F_ROT_WAVES : K1F_WAVES_OF(h->cfg.fmt));
 			const long long per_fam = (long long)K1F_ROLES * 8 * GS;
 			long long nfam = slots / per_fam;
 			if (nfam < 4 && (nfam + 1) * per_fam * 100 <= slots * 108)
@@ -1828,7 +1925,10 @@ static int enqueue_k1(vdl2gpu_t *h, K1Params &k1, const Input &in, size_t nsampl
 		}
 		const dim3 grid((unsigned)ngrp * K1F_ROLES, (unsigned)GS);
 		++h->k1_launches[3];
-		with_fmt(h->cfg.fmt, [&](auto F) { hipLaunchKernelGGL(k1_fast<decltype(F)::value>, grid, dim3(K1F_THREADS), 0, ks, k1); });
+		if (h->rot)
+			with_fmt(h->cfg.fmt, [&](auto F) { hipLaunchKernelGGL((k1_fast<decltype(F)::value, true>), grid, dim3(K1F_THREADS), 0, ks, k1, h->k1rot); });
+		else
+			with_fmt(h->cfg.fmt, [&](auto F) { hipLaunchKernelGGL(k1_fast<decltype(F)::value>, grid, dim3(K1F_THREADS), 0, ks, k1); });
 		if (staged)
 			(void)hipEventRecord(pt.e[9], ks);
 		pt.fast_parts = 1;
@@ -1897,7 +1997,10 @@ static int enqueue_k1(vdl2gpu_t *h, K1Params &k1, const Input &in, size_t nsampl
 			(void)hipEventRecord(pt.e[8], ks);
 		const dim3 grid((unsigned)(blocks * kp.nsub), (unsigned)GS);
 		++h->k1_launches[2];
-		with_fmt(h->cfg.fmt, [&](auto F) { hipLaunchKernelGGL(k1_pp<decltype(F)::value>, grid, dim3(K1P_THREADS), 0, ks, kp); });
+		if (h->rot)
+			with_fmt(h->cfg.fmt, [&](auto F) { hipLaunchKernelGGL((k1_pp<decltype(F)::value, true>), grid, dim3(K1P_THREADS), 0, ks, kp, h->k1rot); });
+		else
+			with_fmt(h->cfg.fmt, [&](auto F) { hipLaunchKernelGGL(k1_pp<decltype(F)::value>, grid, dim3(K1P_THREADS), 0, ks, kp); });
 		if (staged)
 			(void)hipEventRecord(pt.e[9], ks);
 		pt.fast_parts = 1;
@@ -2065,6 +2168,14 @@ static int push_impl(vdl2gpu_t *h, const void *iq, size_t nsamples, size_t strea
 	K1Params k1{};
 	vdl2gpu_plan(h->total_in, nsamples, (unsigned)h->sdrclk, (unsigned)h->L, &k1.c0, &k1.no0, &k1.nf0, &p.J);
 	k1.J = p.J;
+	if (h->rot) {
+		/* where the push's output 0 stands in the 21-output schedule, and the phase index (per Hz of Fd) of the schedule period
+		 * it lies in: that period begins at input q * SDRCLK of the stream, and a + e of its windows grows by twice that */
+		const uint64_t done = (uint64_t)(((unsigned __int128)h->total_in * 21u) / (unsigned)h->sdrclk);
+		const uint64_t qin = done / 21 * (uint64_t)h->sdrclk;
+		h->k1rot.i0 = (int)(done % 21);
+		h->k1rot.sq0 = (unsigned)vdl2gpu_exact_fo_index(qin, qin, h->cfg.sdrinrate, 1);
+	}
 	/* A short push (a live SDR block is 1376 frames per channel) is cheaper on the serial machine alone
 	 * than through the scan's ten launches: the parallel path only pays from a few thousand frames on. */
 	p.serial = h->force_serial || (p.J <= VDL2_SERIAL_BELOW && !h->full_scan && !h->set[p.par].k2.test_noregion);

@@ -48,6 +48,49 @@ template <int FMT> __device__ __forceinline__ float2 k1_load(const char *raw, lo
 	}
 }
 
+/* ---- VDL2GPU_F_EXACT_FO: the residual oscillator at the dump (K1Rot, include/vdl2gpu.h) ----
+ * ROT is a template parameter of the three kernels' bodies; the kernels of a handle without the flag are the <.., false>
+ * instantiations under their old names and parameters.  A lane works out the phase index of its first output once (k1r_mod:
+ * no 64-bit division) and steps it from output to output by adding a host-made increment and subtracting M once if need be. */
+
+/* x mod M for x < 2^56: the quotient from one double multiplication by rM = RN(1 / M) -- off by one at most, the relative
+ * error is a few 2^-53 and the quotient below 2^39 -- the remainder in integers, exact */
+__device__ __forceinline__ unsigned k1r_mod(unsigned long long x, unsigned M, double rM)
+{
+	const unsigned long long q = (unsigned long long)((double)x * rM);
+	long long r = (long long)(x - q * M);
+	if (r < 0)
+		r += M;
+	if (r >= (long long)M)
+		r -= M;
+	return (unsigned)r;
+}
+
+__device__ __forceinline__ unsigned k1r_add(unsigned a, unsigned b, unsigned M)	/* a, b < M < 2^31 */
+{
+	const unsigned t = a + b;
+	return t >= M ? t - M : t;
+}
+
+/* (xr yr - xi yi, xr yi + xi yr): every product and the sum or difference rounded on its own (-ffp-contract=off) */
+__device__ __forceinline__ float2 k1r_cmul(float2 x, float2 y)
+{
+	const float a = x.x * y.x, b = x.y * y.y, c = x.x * y.y, d = x.y * y.x;
+	return make_float2(a - b, c + d);
+}
+
+/* D' = D (x) (T_hi[k >> 12] (x) T_lo[k & 4095]) */
+__device__ __forceinline__ float2 k1r_rotate(float2 d, unsigned k, const K1Rot &r)
+{
+	return k1r_cmul(d, k1r_cmul(r.hi[k >> 12], r.lo[k & 4095]));
+}
+
+/* phase index of the channel's output 21 ql + i, ql counted from the period of the push's output 0, without its tab[i] */
+__device__ __forceinline__ unsigned k1r_period(const unsigned *tab, long long ql, const K1Rot &r)
+{
+	return k1r_mod((unsigned long long)tab[22] * r.sq0 + (unsigned long long)tab[21] * (unsigned long long)ql, r.M, r.rM);
+}
+
 /* GLO (rates off the 25 kHz grid whose LO table does not fit LDS beside the windows: 3072 entries x 8 channels at 15.36 MS/s,
  * 6144 at 30.72): the table stays in global memory -- a few hundred KB per stream, L2-resident -- and LDS holds the windows
  * and a tile of LO values, K1G_T steps of every lane's window at a time.  A wavefront (2 channels x 32 windows) fills its own
@@ -62,7 +105,7 @@ __device__ __forceinline__ int k1g_slot(int tt, int row)
 	return tt * K1_THREADS + ((row + tt) & (K1_THREADS - 1));
 }
 
-template <int FMT, bool GLO> __device__ __forceinline__ void k1_channelise_body(const K1Params &p)
+template <int FMT, bool GLO, bool ROT> __device__ __forceinline__ void k1_channelise_body(const K1Params &p, const K1Rot &r)
 {
 	extern __shared__ float2 k1_smem[];
 	float2 *lo_s = k1_smem;					/* [(L+maxwin)][8]; GLO: the tile [K1G_T][256] */
@@ -87,6 +130,19 @@ template <int FMT, bool GLO> __device__ __forceinline__ void k1_channelise_body(
 	 * so a plane store is a 256-byte run */
 	const int o = tid & 31, c = tid >> 5;
 	float2 *dec = p.dec + ((size_t)s * VDL2_CS + c) * p.cap + fill;
+	/* ROT: output jb + o stands at place ri of its schedule period, whose phase index is rq; a pass later it is 32 = 21 + 11 on */
+	const unsigned *rtab = nullptr;
+	int ri = 0;
+	unsigned rq = 0, rP = 0;
+	bool ron = false;
+	if constexpr (ROT) {
+		rtab = r.tab + ((size_t)s * VDL2_CS + c) * K1R_TAB;
+		const long long t = r.i0 + jb + o;
+		ri = (int)(t % 21);
+		rq = k1r_period(rtab, t / 21, r);
+		rP = rtab[21];
+		ron = rtab[23] != 0;
+	}
 	for (int pass = 0; pass < K1_PASSES; ++pass) {
 		const long long jp = jb + (long long)pass * K1_OPB;
 		if (jp > p.jend)
@@ -165,7 +221,11 @@ template <int FMT, bool GLO> __device__ __forceinline__ void k1_channelise_body(
 					ss->acc[p.parity ^ 1][c] = make_float2(dre, dim);
 				} else {
 					const float fn = (float)nf;
-					dec[j] = make_float2(dre / fn, dim / fn);
+					float2 v = make_float2(dre / fn, dim / fn);
+					if constexpr (ROT)
+						if (ron)
+							v = k1r_rotate(v, k1r_add(rq, rtab[ri], r.M), r);
+					dec[j] = v;
 				}
 			}
 		} else
@@ -204,7 +264,19 @@ template <int FMT, bool GLO> __device__ __forceinline__ void k1_channelise_body(
 				ss->acc[p.parity ^ 1][c] = make_float2(dre, dim);
 			} else {
 				const float fn = (float)nf;
-				dec[j] = make_float2(dre / fn, dim / fn);
+				float2 v = make_float2(dre / fn, dim / fn);
+				if constexpr (ROT)
+					if (ron)
+						v = k1r_rotate(v, k1r_add(rq, rtab[ri], r.M), r);
+				dec[j] = v;
+			}
+		}
+		if constexpr (ROT) {
+			rq = k1r_add(rq, rP, r.M);
+			ri += 11;
+			if (ri >= 21) {
+				ri -= 21;
+				rq = k1r_add(rq, rP, r.M);
 			}
 		}
 	}
@@ -213,7 +285,7 @@ template <int FMT, bool GLO> __device__ __forceinline__ void k1_channelise_body(
 template <int FMT> __global__ __launch_bounds__(K1_THREADS)
 void k1_channelise(K1Params p)
 {
-	k1_channelise_body<FMT, false>(p);
+	k1_channelise_body<FMT, false, false>(p, K1Rot{});
 }
 
 /* the variant with the LO table in global memory: the second template parameter, so that the kernels above keep their names */
@@ -221,7 +293,15 @@ template <int FMT, bool GLO> __global__ __launch_bounds__(K1_THREADS)
 void k1_channelise(K1Params p)
 {
 	static_assert(GLO, "k1_channelise<FMT> is the kernel with the table in LDS");
-	k1_channelise_body<FMT, true>(p);
+	k1_channelise_body<FMT, true, false>(p, K1Rot{});
+}
+
+/* VDL2GPU_F_EXACT_FO: either variant with the rotation at its dump (a third template parameter and a second argument) */
+template <int FMT, bool GLO, bool ROT> __global__ __launch_bounds__(K1_THREADS)
+void k1_channelise(K1Params p, K1Rot r)
+{
+	static_assert(ROT, "without the rotation the kernels are k1_channelise<FMT> and k1_channelise<FMT, true>");
+	k1_channelise_body<FMT, GLO, true>(p, r);
 }
 
 /* ---- K1 fast path: whole periods of the schedule, any rate ----------------------------
@@ -411,206 +491,21 @@ template <int FMT> __device__ __forceinline__ void k1_piece_cvt(const uint4 v, f
 	}
 }
 
+
 template <int FMT> __global__ __launch_bounds__(K1P_THREADS, 6)
 void k1_pp(K1PParams p)
 {
-	constexpr int B = K1Fmt<FMT>::BYTES, SPB = K1Fmt<FMT>::SPB;
-#ifdef K1P_DBG
-	const int dbg = p.dbg;	/* development switches (VDL2GPU_K1_DBG): 1 no mixing, 2 no loads after the first chunk, 4 no stores, .. */
-#else
-	constexpr int dbg = 0;	/* (as run-time tests they were seven branches in every block of 8 samples) */
-#endif
-	constexpr int NPIECE = K1P_CH / SPB;			/* 16-byte pieces per period and chunk */
-	constexpr int NPT = (64 * NPIECE + K1P_THREADS - 1) / K1P_THREADS;	/* pieces per thread */
-	__shared__ float2 xs[8 + 64 * K1P_XROW + 8];	/* 8 entries of pad on either side: blocks of 8 are read whole */
-	__shared__ float2 os[8][8 * K1P_OROW];
-	const int tid = threadIdx.x;
-	const int lane = tid & 63;
-	const int c = __builtin_amdgcn_readfirstlane(tid >> 6);
-	const int s = (int)blockIdx.y;
-	const int blk = (int)(blockIdx.x / (unsigned)p.nsub), sub = (int)(blockIdx.x % (unsigned)p.nsub);
-	const int k0 = sub * p.wpt, k1 = k0 + p.wpt;		/* this task's windows of the period */
-	const int pb = blk * 64;				/* its first period, counted from per_lo */
-	const int nper = (p.per_n - pb < 64) ? p.per_n - pb : 64;
-	const long long fill = VDL2_CARRY_FRAMES;
-	const bool active = c < p.nbch;
-	const char *raw = (const char *)p.raw + (size_t)s * p.stream_stride + (size_t)p.sbase0 * B;	/* first sample of period per_lo */
-	if (p.edge_state && blockIdx.x == 0 && tid < VDL2_CS) {	/* what k1_channelise leaves at a push's two ends (see k1_fast) */
-		StreamState *ss = p.ss + s;
-		if (tid == 0) {
-			ss->last_fill = VDL2_CARRY_FRAMES;
-			ss->last_J = p.J;
-		}
-		ss->acc[p.parity ^ 1][tid] = make_float2(0.0f, 0.0f);	/* the push ends on a window boundary: nothing carried */
-	}
+	constexpr bool ROT = false;
+	const K1Rot r{};
+#include "vdl2gpu_k1_pp.inc"
+}
 
-	/* loader role: NPT pieces (period lp, piece lj) */
-	const char *lptr[NPT];
-	int lcol[NPT];
-	bool lval[NPT];
-#pragma unroll
-	for (int j = 0; j < NPT; ++j) {
-		const int q = tid + j * K1P_THREADS;
-		const int lp = q / NPIECE, lj = q % NPIECE;
-		lval[j] = q < 64 * NPIECE;
-		const int pp = lp < nper ? lp : nper - 1;	/* lanes beyond the last period re-read it (and store nothing) */
-		lptr[j] = raw + ((long long)(pb + pp) * p.per_in - p.d) * B + lj * 16;
-		lcol[j] = 8 + (lp < 64 ? lp : 63) * K1P_XROW + lj * SPB;
-	}
-
-	int k = k0;
-	int i = (k0 == 0) ? 0 : p.wend[k0 - 1] + 1;		/* period-relative sample index */
-	int wend = p.wend[k0];
-	int nf = wend - i + 1;
-	const int i_stop = p.wend[k1 - 1] + 1;
-	int wi = (p.ph0 + i) % p.L;
-	int slot = 0, kflush = k0;
-	v2f acc = {0.0f, 0.0f};
-	const float2 *lo = p.lo_ext + ((size_t)s * VDL2_CS + (active ? c : 0)) * p.lo_stride + 8;	/* 8 entries of front pad */
-	const unsigned xrow = (unsigned)(size_t)(__attribute__((address_space(3))) const float2 *)&xs[8 + lane * K1P_XROW];
-	const int m0 = (i + p.d) / K1P_CH, m1 = (i_stop - 1 + p.d) / K1P_CH;
-	float2 *decp = p.dec + ((size_t)s * VDL2_CS + (active ? c : 0)) * p.cap + fill + (p.per_lo + pb) * K1P_PER_OUT;
-
-	uint4 rr[NPT];
-#pragma unroll
-	for (int j = 0; j < NPT; ++j)
-		rr[j] = *reinterpret_cast<const uint4 *>(lptr[j] + (long long)m0 * K1P_CH * B);
-	for (int m = m0; m <= m1; ++m) {
-		if (!(dbg & 8))
-			__syncthreads();	/* the previous chunk has been read by every wave */
-#pragma unroll
-		for (int j = 0; j < NPT; ++j)
-			if (lval[j]) {
-				float2 cv[SPB];
-				k1_piece_cvt<FMT>(rr[j], cv);
-#pragma unroll
-				for (int u = 0; u < SPB; ++u)
-					xs[lcol[j] + u] = cv[u];
-			}
-		if (m < m1 && !(dbg & 2)) {
-#pragma unroll
-			for (int j = 0; j < NPT; ++j)
-				rr[j] = *reinterpret_cast<const uint4 *>(lptr[j] + (long long)(m + 1) * K1P_CH * B);
-		}
-		if (!(dbg & 8))
-			__syncthreads();
-		if (!active || (dbg & 1))
-			continue;
-		const int cb = m * K1P_CH - p.d;	/* period-relative index of the chunk's first sample */
-		const int hi = (i_stop < cb + K1P_CH) ? i_stop : cb + K1P_CH;
-		while (i < hi) {
-			/* a piece: the samples up to the window's or the chunk's end, as blocks of 8 and a tail */
-			const int lim = (hi < wend + 1) ? hi : wend + 1;
-			int n = lim - i;
-			unsigned xa = xrow + (unsigned)(i - cb) * 8u;
-			const float2 *lp = lo + wi;
-			i = lim;
-			wi += n;
-			if (wi >= p.L)
-				wi -= p.L;
-			for (; n >= 8; n -= 8) {
-				v16f w;
-				v2f xr[8];
-				if (dbg & 16) {
-					w = (v16f)(1.0f);
-#pragma unroll
-					for (int u = 0; u < 8; ++u)
-						xr[u] = acc;
-				} else if (dbg & 512)
-					k1_load_block_nos(w, xr, lp, xa);
-				else if (dbg & 1024)
-					k1_load_block_nol(w, xr, lp, xa);
-				else
-					k1_load_block(w, xr, lp, xa);
-				if constexpr (K1_REAL(FMT)) {
-#pragma unroll
-					for (int u = 0; u < 8; ++u)
-						k1_rmac_s(acc, xr[u].x, (v2f){w[2 * u], w[2 * u + 1]});
-				} else if (!(dbg & 64))
-					k1_cmac8_s(acc, xr, w);
-				lp += 8;
-				xa += 64;
-			}
-			if (n && !(dbg & 128)) {
-				/* the tail: read the 8 entries that END with it (what lies before is the row's or the table's
-				 * front pad or earlier samples) and enter the unrolled sequence n steps before its end */
-				v16f w;
-				v2f xr[8];
-				if (dbg & 512)
-					k1_load_block_nos(w, xr, lp - (8 - n), xa - (unsigned)(8 - n) * 8u);
-				else if (dbg & 1024)
-					k1_load_block_nol(w, xr, lp - (8 - n), xa - (unsigned)(8 - n) * 8u);
-				else
-					k1_load_block(w, xr, lp - (8 - n), xa - (unsigned)(8 - n) * 8u);
-#define K1_TAIL(u) if constexpr (K1_REAL(FMT)) k1_rmac_s(acc, xr[u].x, (v2f){w[2 * (u)], w[2 * (u) + 1]}); \
-		   else k1_cmac_s(acc, xr[u], (v2f){w[2 * (u)], w[2 * (u) + 1]});
-				switch (n) {
-				case 7: K1_TAIL(1)
-				case 6: K1_TAIL(2)
-				case 5: K1_TAIL(3)
-				case 4: K1_TAIL(4)
-				case 3: K1_TAIL(5)
-				case 2: K1_TAIL(6)
-				default: K1_TAIL(7)
-				}
-#undef K1_TAIL
-			}
-			if (i > wend && (dbg & 256)) {
-				acc = (v2f){0.0f, 0.0f};
-				++k;
-				if (k < k1) {
-					const int e = p.wend[k];
-					nf = e - wend;
-					wend = e;
-				}
-			} else if (i > wend) {
-				/* D /= nf (d8psk.c:377).  q0 = x*RN(1/nf); q = fma(fma(-q0, nf, x), RN(1/nf), q0) is the
-				 * correctly rounded quotient for every |x| >= 1e-30 and nf in {23,24,59,60,71,72,119,120}
-				 * (exhaustively checked: tests/ctests/div_check.c); otherwise the plain IEEE division */
-				const float fn = (float)nf;
-				float qr, qi;
-				if (p.fast_div && __all(fabsf(acc.x) >= 1e-30f && fabsf(acc.y) >= 1e-30f)) {
-					const float rfn = (nf == p.nf_lo) ? p.rcp_lo : p.rcp_hi;
-					const float q0r = acc.x * rfn, q0i = acc.y * rfn;
-					qr = fmaf(fmaf(-q0r, fn, acc.x), rfn, q0r);
-					qi = fmaf(fmaf(-q0i, fn, acc.y), rfn, q0i);
-				} else {
-					qr = acc.x / fn;
-					qi = acc.y / fn;
-				}
-				os[c][slot * K1P_OROW + lane] = make_float2(qr, qi);
-				acc = (v2f){0.0f, 0.0f};
-				++slot;
-				++k;
-				if (slot == 8 || k == k1) {
-					/* 8 windows x 64 periods -> 64-byte runs of the plane: lane = (period, pair of windows) */
-					__builtin_amdgcn_wave_barrier();
-#pragma unroll
-					for (int it = 0; it < 4; ++it) {
-						const int pp = it * 16 + (lane >> 2), q = lane & 3;
-						if (pp < nper && 2 * q < slot && !(dbg & 4)) {
-							const float2 v0 = os[c][(2 * q) * K1P_OROW + pp];
-							float2 *dst = decp + (long long)pp * K1P_PER_OUT + kflush + 2 * q;
-							if (2 * q + 1 < slot) {
-								const float2 v1 = os[c][(2 * q + 1) * K1P_OROW + pp];
-								typedef float k1_v4a8 __attribute__((ext_vector_type(4), aligned(8)));
-								*reinterpret_cast<k1_v4a8 *>(dst) = (k1_v4a8){v0.x, v0.y, v1.x, v1.y};
-							} else
-								*dst = v0;
-						}
-					}
-					__builtin_amdgcn_wave_barrier();
-					kflush = k;
-					slot = 0;
-				}
-				if (k < k1) {
-					const int e = p.wend[k];
-					nf = e - wend;
-					wend = e;
-				}
-			}
-		}
-	}
+/* VDL2GPU_F_EXACT_FO: the same with the rotation at its dump */
+template <int FMT, bool ROT> __global__ __launch_bounds__(K1P_THREADS, 6)
+void k1_pp(K1PParams p, K1Rot r)
+{
+	static_assert(ROT, "without the rotation the kernel is k1_pp<FMT>");
+#include "vdl2gpu_k1_pp.inc"
 }
 
 /* ---- K1 fast path: SDRINRATE 2 MS/s (SDRCLK 500, LO period 80) ------------------------
@@ -854,312 +749,29 @@ __device__ unsigned k1f_prof[K1F_PROF_SLOTS][12];	/* development: shader cycles 
 #else
 #define K1F_STAMP(I_) do { } while (0)
 #endif
+/* VDL2GPU_F_EXACT_FO: one table entry of the rotation, requested and not waited for (the loop counts it among its loads) */
+__device__ __forceinline__ void k1r_issue(v2f &v, const unsigned voff, const float2 *sbase)
+{
+	asm volatile("global_load_dwordx2 %0, %1, %2" : "=v"(v) : "v"(voff), "s"(sbase) : "memory");
+}
+#define K1F_ROT_WAVES 4		/* wavefronts per SIMD of the rotating instantiations: the phase index and the four table entries in
+				 * flight per pair do not fit the 96 registers of five */
+
+
 template <int FMT> __global__ __launch_bounds__(K1F_THREADS, K1F_WAVES_OF(FMT))
 void k1_fast(K1Params p)
 {
-	typedef typename K1Raw<FMT>::T raw_t;
-	constexpr int B = (FMT == VDL2GPU_FMT_CU8 || FMT == VDL2GPU_FMT_CS8 || FMT == VDL2GPU_FMT_S16R) ? 2 : (FMT == VDL2GPU_FMT_CF32) ? 8 : 4;
-#ifdef K1F_PROF
-	unsigned pf[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-	unsigned tl = (unsigned)__builtin_amdgcn_readfirstlane((int)clock64());
-	const unsigned wall0 = (unsigned)__builtin_amdgcn_readfirstlane((int)wall_clock64());
-#endif
-	/* LDS: every window has its own row of 25 float2 (24 samples + 1 of padding: rows of 50 dwords put the 8 windows of
-	 * a half-wave read on 8 different bank pairs; laid end to end, windows 4 apart -- 95 or 96 samples -- shared banks),
-	 * a pair of slices per iteration, two copies of the pair used in turn (one barrier per iteration) */
-	__shared__ float2 xs[2][2][16 * 25 + 8];	/* [copy][half of the pair] */
-	__shared__ int s_next;
-	const int tid = threadIdx.x;
-	const int lane = tid & 63, wv = tid >> 6;
-	const int s = (int)blockIdx.y;
-	/* A workgroup owns 16 consecutive outputs -- ONE 128-byte line of every channel plane -- of a superperiod (4
-	 * periods of the schedule: 8000 inputs, 336 outputs, 21 lines) for many superperiods: lane = (window, channel),
-	 * 16 windows x 4 channels to a wavefront, the two wavefronts share the windows' ~381 samples through LDS.  A
-	 * wavefront's store is four whole, aligned lines.  (Runs of 64 bytes -- 8 windows per wavefront -- reached HBM as
-	 * partial lines once the read stream pushed them out of the L2 before their other halves arrived: the same
-	 * traffic moved in 128 us instead of 86, scripts/micro/store_shape.hip.)
-	 *
-	 * The kernel is built around what a SIMD needs to stay busy: one wavefront issues a packed operation every 9 cycles
-	 * at best, four of them together one every 3.5, eight one every 1.5 - 2 (scripts/micro/clock_rate.hip, valu_rate.hip)
-	 * -- three to four wavefronts per SIMD must be mixing at any time.  Hence 96 registers (5 wavefronts per SIMD: the
-	 * 24 LO values of the lane's window take 48 of them, samples come from LDS four at a time), and a grid that is
-	 * resident as a whole (the launch sizes it): a workgroup's start-up -- cold code, LO values, first samples -- is
-	 * paid once per ~70 superperiods. */
-	/* Work is handed out in TICKETS of K1F_CHUNK superperiods.  Workgroup b runs on XCD x = b % 8 and has role
-	 * g = (b / 8) % 21; the workgroups of one (role, XCD) form a family that shares a counter and takes the superperiods
-	 * per_lo + x + 8 i, i = 0, 1, .. in chunks: ticket t = i in [t C, t C + C).  The first ticket of a workgroup is its
-	 * rank in the family, the next one comes from the counter while the current one is being worked on -- a workgroup on
-	 * a SIMD that advances slowly (more wavefronts, a busier CU, another kernel's wavefronts beside it) simply takes
-	 * fewer tickets.  With a fixed share each the launch lasted as long as its slowest SIMD: 104 us for wavefronts that
-	 * lived 88 us on average.  A family's superperiods are neighbours of the other roles' on the same XCD: at any time the
-	 * grid reads one contiguous band of the input and writes one contiguous band of each plane, each L2 its own eighth. */
-	const int x = (int)(blockIdx.x & 7);
-	const int g = (int)((blockIdx.x >> 3) % K1F_ROLES);
-	const int rank = (int)(blockIdx.x / (8 * K1F_ROLES)), nfam = (int)(gridDim.x / (8 * K1F_ROLES));
-	const int n_x = ((int)p.per_n - x + 7) >> 3;			/* superperiods of this XCD */
-	if (rank * K1F_CHUNK >= n_x)	/* its first ticket is empty */
-		return;
-	if (p.edge_state && blockIdx.x == 0 && tid < VDL2_CS) {	/* (rank 0 of XCD 0: never empty) what k1_channelise leaves at a push's two ends */
-		StreamState *ss = p.ss + s;
-		if (tid == 0) {
-			ss->last_fill = VDL2_CARRY_FRAMES;
-			ss->last_J = p.J;
-		}
-		ss->acc[p.parity ^ 1][tid] = make_float2(0.0f, 0.0f);	/* the push ends on a window boundary: nothing carried */
-	}
-	const unsigned *ctr = p.tickets + ((size_t)s * K1F_ROLES + g) * 8 + x;	/* ticket = nfam + (old value - tbase[x]) */
-	const unsigned tbase = p.tbase[x];
-	const int kk = lane >> 2, c = wv * 4 + (lane & 3);
-	const bool active = c < p.nbch;
-	const char *raw = (const char *)p.raw + (size_t)s * p.stream_stride;
-	/* The schedule repeats exactly every superperiod (336 * SDRCLK = 21 * 8000): window jr of ANY superperiod ends
-	 * e(jr) samples behind the superperiod's nominal start pp * 8000, e(jr) = ceil(((jr + 1) * 500 - c0) / 21) - 1
-	 * (k1_win_end with the superperiod's 168000 taken out; 21 * 32 keeps the division's numerator positive), and the
-	 * sample at `rel` belongs to window ceil((21 (rel + 1) + c0 - 20) / 500) - 1.  Everything in front of the loop is
-	 * 32-bit arithmetic on these two, no table and no barrier: every instruction here is executed exactly once and
-	 * fetched cold (~330 cycles per 64-byte line of code), so this part is written for size.
-	 * The slice of this workgroup: from the first sample of window 16g to the last of window 16g + 15. */
-	const int c0 = p.c0;
-	auto e_rel = [c0](int jr) { return ((jr + 1) * 500 - c0 + 20 + 21 * 32) / 21 - 32 - 1; };
-	const int e0 = e_rel(g * 16 - 1);
-	const int slen = e_rel(g * 16 + 15) - e0;
-	const int ek = e_rel(g * 16 + kk - 1);
-	const int off = ek - e0, nwin = e_rel(g * 16 + kk) - ek;
-	/* threads fetch samples tid, tid+128, tid+256 of the slice (clamped: the tail re-reads the last sample) and park
-	 * each in the row of the window it belongs to */
-	unsigned vo[3];	/* [1] = [0] + 128 B is never clamped: the loads use [0] with an immediate offset */
-	int xd[3];
-#pragma unroll 1
-	for (int u = 0; u < 3; ++u) {
-		int i = tid + u * K1F_THREADS;
-		i = i < slen ? i : slen - 1;
-		const int rel = e0 + 1 + i;
-		const int jr = (21 * (rel + 1) + c0 - 20 + 499) / 500 - 1;	/* numerator > 0 for every sample of the slice */
-		const int x = (jr - g * 16) * 25 + (rel - e_rel(jr - 1) - 1);
-		if (u == 0) { vo[0] = (unsigned)i * B; xd[0] = x; }
-		else if (u == 1) { vo[1] = (unsigned)i * B; xd[1] = x; }
-		else { vo[2] = (unsigned)i * B; xd[2] = x; }
-	}
-	/* index i of the family: superperiod per_lo + x + 8 i.  An ITERATION takes a pair (2 p, 2 p + 1): two slices in
-	 * flight (one register set each), one wait, one barrier and one turn of the bookkeeping for two superperiods of
-	 * mixing -- with one superperiod per iteration a wavefront spent as long outside the mixer as in it, and a SIMD
-	 * needs three of its five mixing. */
-	constexpr int CP = K1F_CHUNK / 2;	/* pairs per ticket */
-	static_assert(K1F_DEPTH == 2 && K1F_CHUNK % 2 == 0 && CP >= 4, "the loop below is written for pairs and a ticket known at the fourth pair");
-	const char *rbase = raw + ((p.per_lo + x) * K1F_PER_IN + e0 + 1) * B;	/* the slice in the family's first superperiod; workgroup-uniform */
-	constexpr long long pbytes = (long long)K1F_PER_IN * B * 8;
-	int p0 = rank * CP;	/* this iteration's pair */
-	raw_t rr[2][3];
-	{
-		const int ia = 2 * p0, ib = ia + 1 < n_x ? ia + 1 : ia;
-		const char *rb = rbase + pbytes * ia;
-		k1_raw_issue<FMT>(rr[0][0], vo[0], rb);
-		k1_raw_issue<FMT, K1F_THREADS * B>(rr[0][1], vo[0], rb);
-		k1_raw_issue<FMT>(rr[0][2], vo[2], rb);
-		rb = rbase + pbytes * ib;
-		k1_raw_issue<FMT>(rr[1][0], vo[0], rb);
-		k1_raw_issue<FMT, K1F_THREADS * B>(rr[1][1], vo[0], rb);
-		k1_raw_issue<FMT>(rr[1][2], vo[2], rb);
-	}
-	K1F_STAMP(8);	/* prologue: addresses, first loads issued */
-	/* the lane's LO values, behind the first samples' loads (one round trip for both); the table carries its own
-	 * wrap-around (24 loads off one address) */
-	v2f w[24];
-	{
-		const int ph = (p.no0 + e0 + 1 + off + 80) % 80;	/* 8000 = 100 LO periods: the same in every superperiod; e0 + 1 >= -23 */
-		const float2 *lo = p.lo_ext + ((size_t)s * VDL2_CS + (active ? c : 0)) * p.lo_stride + 8 + ph;
-#pragma unroll
-		for (int t = 0; t < 24; ++t) {
-			const float2 q = lo[t];
-			w[t] = (v2f){q.x, q.y};
-		}
-	}
-	const float fn = (float)nwin;
-	const float rfn = 1.0f / fn;	/* RN(1/nf) for the exact FMA division below */
-	const float2 *dec = p.dec + (size_t)s * VDL2_CS * p.cap + VDL2_CARRY_FRAMES + (p.per_lo + x) * K1F_PER_OUT + g * 16;	/* workgroup-uniform */
-	const unsigned dvo = (unsigned)(((size_t)(active ? c : 0) * p.cap + kk) * sizeof(float2));	/* a stream's planes span < 4 GiB (VDL2_PLANES_MAX, vdl2gpu_create) */
-	asm volatile("s_waitcnt vmcnt(0)" ::: "memory");	/* from here on the only memory operations are the counted ones below */
-#pragma unroll
-	for (int t = 0; t < 24; ++t)
-		asm volatile("" : "+v"(w[t]));	/* loaded in front of the loop, once */
-	K1F_STAMP(0);	/* prologue */
-	const unsigned xa = (unsigned)(size_t)(__attribute__((address_space(3))) const float2 *)&xs[0][0][kk * 25];
-	unsigned tkr = 0;	/* lane 0 of wavefront 0: the counter's answer, landing while the chunk is worked on */
-	int nxt = 0x7fffffff;
-	int pos = 0;	/* position in the current chunk */
-	int buf = 0;	/* which copy of the slices this iteration writes and reads */
-#ifdef K1F_PROF
-	int nit = 0;
-#endif
-	while (p0 >= 0) {
-#ifdef K1F_PROF
-		nit += 2;
-#endif
-		/* pair p0: registers -> float -> LDS slices, then refill the registers with the next pair.  Every iteration
-		 * issues exactly 6 loads and then 2 stores per wavefront: only the 2 stores have been issued after the loads
-		 * this iteration waits for (a ticket request is issued BEFORE an iteration's loads, so they see it land). */
-#ifndef K1F_NOPRIO
-		/* the SIMD's arbiter serves its oldest wavefront first: left alone, the five wavefronts of a SIMD advance
-		 * at very different rates.  Rotating priorities keep them together. */
-		switch ((pos + (int)blockIdx.x) & 3) {
-		case 0: __builtin_amdgcn_s_setprio(0); break;
-		case 1: __builtin_amdgcn_s_setprio(1); break;
-		case 2: __builtin_amdgcn_s_setprio(2); break;
-		default: __builtin_amdgcn_s_setprio(3); break;
-		}
-#endif
-#if defined(K1F_NOLOAD) || defined(K1F_NOSTORE)
-		asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#else
-		asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-#endif
-		K1F_STAMP(1);	/* wait for the samples */
-#pragma unroll
-		for (int ab = 0; ab < 2; ++ab)
-#pragma unroll
-			for (int u = 0; u < 3; ++u)
-				asm volatile("" : "+v"(rr[ab][u]));	/* read only behind the wait */
-#pragma unroll
-		for (int ab = 0; ab < 2; ++ab) {
-			float2 *xb = xs[buf][ab];
-#pragma unroll
-			for (int u = 0; u < 3; ++u)
-				xb[xd[u]] = k1_raw_cvt<FMT>(rr[ab][u]);
-		}
-		if (pos == 0) {
-			/* ask for the next ticket: older than the loads issued below, so the next iteration's wait sees it land */
-			const unsigned long long m = __ballot(tid == 0);
-			asm volatile("s_mov_b64 s[2:3], exec\n\t"
-				     "s_mov_b64 exec, %3\n\t"
-				     "global_atomic_add %0, %1, %2, %4 sc0\n\t"
-				     "s_mov_b64 exec, s[2:3]"
-				     : "+v"(tkr) : "v"(0u), "v"(1u), "s"(m), "s"(ctr) : "memory", "s2", "s3");
-		}
-		if (pos == 1) {
-			asm volatile("" : "+v"(tkr));	/* it has landed: the wait above was for loads issued after the request */
-			if (tid == 0)
-				s_next = ((int)(tkr - tbase) + nfam) * CP;
-		}
-		if (pos == 2)
-			nxt = __builtin_amdgcn_readfirstlane(s_next);	/* first pair of the next ticket; written one barrier ago */
-		/* the next pair: in this chunk, the next ticket's first, or none (the loads then fetch this one again) */
-		int p1 = pos < CP - 1 ? p0 + 1 : nxt;
-		p1 = 2 * p1 < n_x ? p1 : -1;
-		{
-			const int ia = 2 * (p1 >= 0 ? p1 : p0), ib = ia + 1 < n_x ? ia + 1 : ia;
-#ifndef K1F_NOLOAD
-			const char *rb = rbase + pbytes * ia;
-			k1_raw_issue<FMT>(rr[0][0], vo[0], rb);
-			k1_raw_issue<FMT, K1F_THREADS * B>(rr[0][1], vo[0], rb);
-			k1_raw_issue<FMT>(rr[0][2], vo[2], rb);
-			rb = rbase + pbytes * ib;
-			k1_raw_issue<FMT>(rr[1][0], vo[0], rb);
-			k1_raw_issue<FMT, K1F_THREADS * B>(rr[1][1], vo[0], rb);
-			k1_raw_issue<FMT>(rr[1][2], vo[2], rb);
-#endif
-		}
-		K1F_STAMP(2);	/* convert, park, issue the next loads */
-#ifndef K1F_NOBARRIER
-		__syncthreads();	/* the slices are written */
-#endif
-		K1F_STAMP(3);	/* barrier */
-		const bool has_b = 2 * p0 + 1 < n_x;
-		const unsigned xc = xa + (unsigned)buf * (unsigned)sizeof(xs[0]);
-#pragma unroll
-		for (int ab = 0; ab < 2; ++ab) {
-			v2f res = {0.0f, 0.0f};
-#ifdef K1F_NOMIX
-			if (p.nbch > 8) {
-#else
-			if (ab == 0 || has_b) {
-#endif
-				v2f acc = {0.0f, 0.0f};
-				if (K1_REAL(FMT)) {
-					const v2f *xp = reinterpret_cast<const v2f *>(&xs[buf][ab][kk * 25]);
-#pragma unroll
-					for (int t = 0; t < 23; ++t) {
-						const float x = xp[t].x;
-						acc += (v2f){x, x} * w[t];
-					}
-					if (nwin == 24) {
-						const float x = xp[23].x;
-						acc += (v2f){x, x} * w[23];
-					}
-				} else {
-					/* six blocks of 4 samples; every block is mixed while the next one's samples are on their way
-					 * from LDS (reads return in order: at most 4 outstanding = the previous block is there); which
-					 * slice of the pair is part of the reads' immediate offsets */
-					auto mix = [&](auto par) {
-						constexpr int XO = (int)sizeof(xs[0][0]) * decltype(par)::value;
-						v2f x0[4], x1[4];
-						asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-						k1_lds_issue4<0 + XO>(x0, xc);
-						k1_lds_issue4<32 + XO>(x1, xc);
-						asm volatile("s_waitcnt lgkmcnt(4)" ::: "memory");
-						k1_cmac4_v(acc, x0, &w[0]);
-						k1_lds_issue4<64 + XO>(x0, xc);
-						asm volatile("s_waitcnt lgkmcnt(4)" ::: "memory");
-						k1_cmac4_v(acc, x1, &w[4]);
-						k1_lds_issue4<96 + XO>(x1, xc);
-						asm volatile("s_waitcnt lgkmcnt(4)" ::: "memory");
-						k1_cmac4_v(acc, x0, &w[8]);
-						k1_lds_issue4<128 + XO>(x0, xc);
-						asm volatile("s_waitcnt lgkmcnt(4)" ::: "memory");
-						k1_cmac4_v(acc, x1, &w[12]);
-						k1_lds_issue4<160 + XO>(x1, xc);
-						asm volatile("s_waitcnt lgkmcnt(4)" ::: "memory");
-						k1_cmac4_v(acc, x0, &w[16]);
-						asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-						k1_cmac3_v(acc, x1, &w[20]);
-						if (nwin == 24)
-							k1_cmac1_v(acc, x1[3], w[23]);
-					};
-					if (ab)
-						mix(std::integral_constant<int, 1>{});
-					else
-						mix(std::integral_constant<int, 0>{});
-				}
-				/* D /= nf (d8psk.c:377).  q0 = x*RN(1/nf); q = fma(fma(-q0, nf, x), RN(1/nf), q0)
-				 * is the correctly rounded quotient for every |x| >= 1e-30 (exhaustively
-				 * checked for nf = 23, 24: tests/ctests/div_check.c); below that, and only
-				 * then, the plain IEEE division is used */
-				if (__all(fabsf(acc.x) >= 1e-30f && fabsf(acc.y) >= 1e-30f)) {
-					const float q0r = acc.x * rfn, q0i = acc.y * rfn;
-					res.x = fmaf(fmaf(-q0r, fn, acc.x), rfn, q0r);
-					res.y = fmaf(fmaf(-q0i, fn, acc.y), rfn, q0i);
-				} else {
-					res.x = acc.x / fn;
-					res.y = acc.y / fn;
-				}
-			}
-			K1F_STAMP(4);	/* mix + divide */
-			/* exactly one store instruction per superperiod and wavefront: four whole lines (channels beyond nbch masked
-			 * off; a wavefront without any channel, or the missing second half of the family's last pair, still issues
-			 * it, with no lane enabled, so that the count above holds) */
-#ifndef K1F_NOSTORE
-			k1_store_masked(dec + (long long)(2 * p0 + ab) * (8 * K1F_PER_OUT), dvo, res, active && (ab == 0 || has_b));
-#endif
-			K1F_STAMP(5);	/* store issue */
-		}
-		/* no second barrier: the next iteration writes the other copy of the slices, and the one after that writes this
-		 * one only behind the next iteration's barrier, which every wave reaches after its reads here */
-		p0 = p1;
-		pos = pos + 1 == CP ? 0 : pos + 1;
-		buf ^= 1;
-	}
-	asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#ifdef K1F_PROF
-	K1F_STAMP(6);	/* drain */
-	if (lane == 0 && blockIdx.y == 0 && blockIdx.x * 2 + wv < K1F_PROF_SLOTS) {
-		for (int i = 0; i < 7; ++i)
-			k1f_prof[blockIdx.x * 2 + wv][i] = pf[i];
-		k1f_prof[blockIdx.x * 2 + wv][7] = (unsigned)nit;
-		k1f_prof[blockIdx.x * 2 + wv][8] = (unsigned)wall_clock64() - wall0;	/* 100 MHz ticks of the wavefront's life */
-		k1f_prof[blockIdx.x * 2 + wv][9] = wall0;
-		k1f_prof[blockIdx.x * 2 + wv][10] = pf[7];
-		k1f_prof[blockIdx.x * 2 + wv][11] = pf[8];
-	}
-#endif
+	constexpr bool ROT = false;
+	const K1Rot r{};
+#include "vdl2gpu_k1_fast.inc"
+}
+
+/* VDL2GPU_F_EXACT_FO: the same with the rotation at its dump */
+template <int FMT, bool ROT> __global__ __launch_bounds__(K1F_THREADS, K1F_ROT_WAVES)
+void k1_fast(K1Params p, K1Rot r)
+{
+	static_assert(ROT, "without the rotation the kernel is k1_fast<FMT>");
+#include "vdl2gpu_k1_fast.inc"
 }
 
 #endif

@@ -151,6 +151,21 @@ struct K1PParams {		/* k1_pp: whole periods (PER = 4*SDRCLK inputs = 84 outputs)
 	int wend[84];		/* last sample of each window, relative to the period's first sample */
 };
 
+/* VDL2GPU_F_EXACT_FO (include/vdl2gpu.h): what the rotating instantiations of the K1 kernels take beside their parameters.  The
+ * phase index of output m is k_m = fd * (a_m + e_m) mod M, M = 2 * SDRINRATE.  The dump schedule repeats every SDRCLK inputs
+ * for 21 outputs, so with m = 21 q + i:  k_m = (fd * (2 SDRCLK q mod M) + tab[i]) mod M, and a step of q adds tab[21]. */
+#define K1R_TAB 24
+struct K1Rot {
+	const unsigned *tab;	/* [S][8][K1R_TAB] per channel: [i < 21] fd * (a_i + e_i) mod M for the schedule's first period,
+				 * [21] fd * 2 SDRCLK mod M, [22] fd = Fd mod M, [23] Fd != 0 (a channel on the grid is left alone) */
+	const float2 *hi;	/* T_hi[ceil(M / 4096)] */
+	const float2 *lo;	/* T_lo[4096] */
+	double rM;		/* 1 / M (k1r_mod) */
+	unsigned M;
+	unsigned sq0;		/* 2 SDRCLK q0 mod M, q0 = the schedule period the push's output 0 lies in */
+	int i0;			/* that output's place in its period: (outputs before the push) mod 21 */
+};
+
 struct K2Slog {			/* a stretch the first resolver pass handled with the serial machine: where it began (stream-relative) and what it counted */
 	int t, ntrig, nrej, nburst;
 };

@@ -78,7 +78,8 @@ class Receiver:
                  fmt: str = "cu8", max_push: int = 1 << 22, device: int = 0, sdrclk: int = 0,
                  max_bursts: int = 0, keep_dec: bool = False, serial: bool = False, full_scan: bool = False,
                  frames: bool = False, rtl_quirk: bool = False, flags: int = 0, testhooks: bool = False,
-                 levels: bool = False, soft_rs: bool = False):
+                 levels: bool = False, soft_rs: bool = False, exact_fo: bool = False):
+        # exact_fo: VDL2GPU_F_EXACT_FO, channel offsets off the 25 kHz grid with a phase-continuous oscillator (include/vdl2gpu.h)
         # testhooks: load libvdl2gpu_test.so, the build that honours F_TEST_NOREGION / VDL2GPU_PRIM_DROP / VDL2GPU_SPLIT_SAMPLES
         self.L = _lib.load(testhooks=testhooks or bool(flags & _lib.F_TEST_NOREGION))
         if channels and isinstance(channels[0], ThreadParam):
@@ -105,7 +106,7 @@ class Receiver:
         cfg.max_push = max_push
         cfg.device = device
         cfg.max_bursts = max_bursts
-        cfg.flags = (_lib.F_KEEP_DEC if keep_dec else 0) | (_lib.F_SERIAL if serial else 0) | (_lib.F_FULLSCAN if full_scan else 0) | (_lib.F_FRAMES if frames else 0) | (_lib.F_RTL_QUIRK if rtl_quirk else 0) | (_lib.F_LEVELS if levels else 0) | (_lib.F_SOFT_RS if soft_rs else 0) | flags
+        cfg.flags = (_lib.F_KEEP_DEC if keep_dec else 0) | (_lib.F_SERIAL if serial else 0) | (_lib.F_FULLSCAN if full_scan else 0) | (_lib.F_FRAMES if frames else 0) | (_lib.F_RTL_QUIRK if rtl_quirk else 0) | (_lib.F_LEVELS if levels else 0) | (_lib.F_SOFT_RS if soft_rs else 0) | (_lib.F_EXACT_FO if exact_fo else 0) | flags
         self.max_push = max_push
         self.levels = bool(cfg.flags & _lib.F_LEVELS)
         self.soft_rs = bool(cfg.flags & _lib.F_SOFT_RS)
@@ -398,6 +399,32 @@ def lo_table(sdrinrate: int, fo: int) -> np.ndarray:
     if rc < 0:
         raise _lib.Vdl2GpuError("vdl2gpu_lo_table failed")
     return buf.view(np.complex64).copy()
+
+
+def exact_fo_split(fo: int) -> Tuple[int, int]:
+    """(Fg, Fd) of VDL2GPU_F_EXACT_FO: the 25 kHz grid point the mixer takes and the rest, -12500 <= Fd < 12500."""
+    fg = STEPRATE * ((fo + STEPRATE // 2) // STEPRATE)
+    return fg, fo - fg
+
+
+def exact_fo_tables(sdrinrate: int) -> Tuple[np.ndarray, np.ndarray]:
+    """(T_hi, T_lo) of VDL2GPU_F_EXACT_FO exactly as the library uploads them, complex64."""
+    L = _lib.load()
+    n = L.vdl2gpu_exact_fo_tables(sdrinrate, None, 0, None)
+    if n < 0:
+        raise _lib.Vdl2GpuError("vdl2gpu_exact_fo_tables failed")
+    hi, lo = np.empty(2 * n, np.float32), np.empty(2 * 4096, np.float32)
+    if L.vdl2gpu_exact_fo_tables(sdrinrate, hi.ctypes.data_as(C.c_void_p), n, lo.ctypes.data_as(C.c_void_p)) != n:
+        raise _lib.Vdl2GpuError("vdl2gpu_exact_fo_tables failed")
+    return hi.view(np.complex64).copy(), lo.view(np.complex64).copy()
+
+
+def exact_fo_index(a: int, e: int, sdrinrate: int, fd_hz: int) -> int:
+    """phase index of the window whose first and last inputs are samples a and e of the stream (vdl2gpu_exact_fo_index)"""
+    k = _lib.load().vdl2gpu_exact_fo_index(a, e, sdrinrate, fd_hz)
+    if k < 0:
+        raise _lib.Vdl2GpuError("vdl2gpu_exact_fo_index failed")
+    return int(k)
 
 
 def plan(total_in: int, n: int, sdrclk: int, lo_len: int) -> Tuple[int, int, int, int]:

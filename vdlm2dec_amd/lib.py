@@ -25,6 +25,7 @@ F_RTL_QUIRK = 32
 F_DEBUG_HEADS = 64
 F_LEVELS = 128
 F_SOFT_RS = 256
+F_EXACT_FO = 512
 
 # every symbol include/vdl2gpu.h declares
 EXPORTS = (
@@ -32,6 +33,7 @@ EXPORTS = (
     "vdl2gpu_ring_init", "vdl2gpu_ring_acquire", "vdl2gpu_ring_commit",
     "vdl2gpu_poll", "vdl2gpu_poll_ready", "vdl2gpu_poll_levels", "vdl2gpu_poll_levels_ready", "vdl2gpu_poll_soft", "vdl2gpu_poll_soft_ready", "vdl2gpu_pending", "vdl2gpu_inflight", "vdl2gpu_get_stats", "vdl2gpu_get_timing", "vdl2gpu_get_host_profile", "vdl2gpu_last_error",
     "vdl2gpu_strerror", "vdl2gpu_burst_to_msgblk", "vdl2gpu_decode_blocks", "vdl2gpu_decode_blocks_soft", "vdl2gpu_poll_frames", "vdl2gpu_poll_frames_ready", "reversebits", "vdl2gpu_lo_len", "vdl2gpu_lo_table", "vdl2gpu_plan",
+    "vdl2gpu_exact_fo_tables", "vdl2gpu_exact_fo_index",
     "vdl2gpu_choose_fc_rtl", "vdl2gpu_choose_fc_air",
     "vdl2gpu_debug_dec", "vdl2gpu_debug_k1", "vdl2gpu_debug_lo", "vdl2gpu_debug_atan2f", "vdl2gpu_debug_rs", "vdl2gpu_debug_counters", "vdl2gpu_debug_cands", "vdl2gpu_debug_clheads", "vdl2gpu_debug_fail", "vdl2gpu_debug_segs", "vdl2gpu_debug_heads",
 )
@@ -177,6 +179,10 @@ def load(testhooks: bool = False):
     L.vdl2gpu_plan.restype = C.c_int
     L.vdl2gpu_plan.argtypes = [C.c_uint64, C.c_uint64, C.c_uint, C.c_uint, C.POINTER(C.c_int),
                                C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int64)]
+    L.vdl2gpu_exact_fo_tables.restype = C.c_int
+    L.vdl2gpu_exact_fo_tables.argtypes = [C.c_uint, C.c_void_p, C.c_int, C.c_void_p]
+    L.vdl2gpu_exact_fo_index.restype = C.c_int64
+    L.vdl2gpu_exact_fo_index.argtypes = [C.c_uint64, C.c_uint64, C.c_uint, C.c_int]
     L.vdl2gpu_choose_fc_rtl.restype = C.c_int
     L.vdl2gpu_choose_fc_rtl.argtypes = [C.POINTER(C.c_uint), C.c_int, C.c_uint, C.POINTER(C.c_uint), C.POINTER(C.c_int)]
     L.vdl2gpu_choose_fc_air.restype = C.c_int
