@@ -333,8 +333,10 @@ int vdl2gpu_sync(vdl2gpu_t *h);
  * (end_sample, stream, chn).  Returns the count (>=0) or a negative error.
  * The host keeps what has been fetched from the GPU and not yet handed out in two bounded queues (bursts;
  * with VDL2GPU_F_FRAMES also frames): a consumer that drains only one of them loses the OLDEST entries of the
- * other once it holds more than 4 x max_bursts unread ones (counted in vdl2gpu_stats_t.overflowed / frames
- * dropped).  Memory: the storage behind a queue is compacted as soon as its handed-out prefix is the larger part,
+ * other (counted in vdl2gpu_stats_t.overflowed / frames_dropped).  The bound is applied when a push is collected, BEFORE
+ * its entries join the queue: what is unread then is cut to the newest 4 x max_bursts, and the push's own entries come on
+ * top -- a queue never holds more than 4 x max_bursts + one push's entries, and never loses an entry while it holds
+ * 4 x max_bursts or fewer.  Memory: the storage behind a queue is compacted as soon as its handed-out prefix is the larger part,
  * so it holds at most 2 x the unread records plus one push's worth -- <= 9 x max_bursts records of 2104 bytes
  * (1.2 GB with the default max_bursts = 65536 and a consumer that never polls; a few MB with one that does). */
 int vdl2gpu_poll(vdl2gpu_t *h, vdl2gpu_burst_t *out, int max);

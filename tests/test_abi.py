@@ -129,6 +129,7 @@ def test_test_handicaps_exist_only_in_the_test_build(built):
     assert b"VDL2GPU_PRIM_DROP" not in blob and b"VDL2GPU_SPLIT_SAMPLES" not in blob and b"VDL2GPU_TEST_ITEM" not in blob
     tblob = open(lib.LIB_TEST_PATH, "rb").read()
     assert b"VDL2GPU_PRIM_DROP" in tblob and b"VDL2GPU_TEST_ITEM_GRID" in tblob and b"VDL2GPU_TEST_ITEM_COMMON" in tblob
+    assert b"VDL2GPU_FRAME_ARENA" not in blob and b"VDL2GPU_FRAME_ARENA" in tblob       # the frame arena's size (tests/test_gpu_full.py)
     assert _getenv_outside_create(_host_sources()) == []                    # every knob is read once, in create_impl
 
 

@@ -239,7 +239,7 @@ struct vdl2gpu {
 	/* block path in the pipeline (VDL2GPU_F_FRAMES) */
 	bool frames_on = false;
 	unsigned *d_k4tab = nullptr;	/* GF(256) and FCS tables of the block path */
-	unsigned *d_fcnt = nullptr;	/* [4*ring] frames written, [4*ring+1] dropped, [4*ring+2] bytes used */
+	unsigned *d_fcnt = nullptr;	/* [4*ring] frames written, [4*ring+1] dropped, [4*ring+2] arena bytes asked for, [4*ring+3] end of the arena's last written entry */
 	unsigned frame_cap = 0;	/* bytes of a frame buffer (slots + arena) */
 
 	std::vector<uint8_t> fready;		/* compact frame entries as k4_frames wrote them, storage order */
@@ -1001,8 +1001,13 @@ static int create_impl(vdl2gpu_t *h)
 	h->col_on[COL_LEVEL] = (cfg.flags & VDL2GPU_F_LEVELS) != 0;
 	h->col_on[COL_SOFT] = (cfg.flags & VDL2GPU_F_SOFT_RS) != 0;
 	h->frames_on = (cfg.flags & VDL2GPU_F_FRAMES) != 0;
-	if (h->frames_on)
-		h->frame_cap = h->rec_cap * K4_SLOT + (4u << 20);	/* bytes: a slot per record, and the arena (see K4Params) */
+	if (h->frames_on) {
+		unsigned arena = 4u << 20;
+#ifdef VDL2GPU_TESTHOOKS
+		arena = (unsigned)std::min(std::max(env_int("VDL2GPU_FRAME_ARENA", (int)arena), 64), (int)arena) & ~7u;	/* (tests: an arena a few entries fill) */
+#endif
+		h->frame_cap = h->rec_cap * K4_SLOT + arena;	/* bytes: a slot per record, and the arena (see K4Params) */
+	}
 	for (Slab &sl : h->slab) {
 		HOST_ALLOC(h, sl.h_recs, (size_t)h->slab_cap * sizeof(vdl2gpu_burst_t), hipHostMallocMapped);
 		HIPCHK(h, hipHostGetDevicePointer((void **)&sl.d_recs, sl.h_recs, 0));
@@ -2480,6 +2485,8 @@ static int collect_frames(vdl2gpu_t *h, int ring, unsigned n)
 {
 	const OutRing &rg = h->ring[ring];
 	const unsigned arena0 = h->rec_cap * K4_SLOT;
+	/* the arena's entries are the bytes up to the end of the last one that found room (k3_rebase publishes that, not the allocation
+	 * counter: an allocation that fails has advanced the counter, and what lies behind the last entry is an earlier push's) */
 	const unsigned nbytes = std::min(h->h_pin_cnt[32 * ring + 6], h->frame_cap - arena0);
 	h->frames_dropped += h->h_pin_cnt[32 * ring + 5];
 	if (!n)

@@ -37,7 +37,8 @@ struct K4Params {
 	unsigned rec_cap;
 	vdl2gpu_frame_t *frames;
 	unsigned *nframes;		/* [0] frames written (compact: to the arena), [1] frames dropped (buffer full),
-					 * [2] arena bytes used (compact) */
+					 * [2] arena bytes asked for (compact; an allocation that fails has advanced it too),
+					 * [3] end of the last entry that found room (compact): the arena's valid bytes */
 	unsigned frame_cap;		/* records, or bytes if compact */
 	int compact;			/* 0: an array of vdl2gpu_frame_t.
 					 * 1: entries of 56 header bytes (the struct's head) + len data bytes.  Record i owns
@@ -730,8 +731,10 @@ void k4_frames(K4Params p)
 						if (slot + sz > p.frame_cap) {
 							atomicAdd(p.nframes + 1, 1u);
 							slot = 0xffffffffu;
-						} else
+						} else {
 							atomicAdd(p.nframes, 1u);
+							atomicMax(p.nframes + 3, slot + sz - base);	/* the counter never goes back: the entries that found room are a prefix of the arena */
+						}
 					} else {
 						slot = atomicAdd(p.nframes, 1u);
 						if (slot >= p.frame_cap) {

@@ -75,8 +75,8 @@ __global__ void k3_rebase(K3Params p)
 		p.host_cnt[1] = p.outc[2 * p.ring + 1];
 		p.host_cnt[2] = p.outc[8];	/* running totals: serial redos, repairs */
 		p.host_cnt[3] = p.outc[9];
-		for (int i = 0; i < 3; ++i)
-			p.host_cnt[4 + i] = p.fcnt ? p.fcnt[i] : 0u;
+		for (int i = 0; i < 3; ++i)	/* frames, dropped, and the arena's valid bytes (fcnt[3]: where its last written entry ends -- not fcnt[2], which failed allocations have advanced as well) */
+			p.host_cnt[4 + i] = p.fcnt ? p.fcnt[i == 2 ? 3 : i] : 0u;
 		for (int i = 0; i < 16; ++i)
 			p.host_cnt[8 + i] = p.fmask[i];
 		p.host_cnt[7] = novf;
