@@ -915,8 +915,9 @@ static int create_impl(vdl2gpu_t *h)
 		h->split_unit = (size_t)4 * h->sdrclk * ((32768 + (size_t)4 * h->sdrclk - 1) / ((size_t)4 * h->sdrclk));	/* (about the block's size) */
 	h->split_default = (size_t)((double)PART_SECONDS * (double)h->cfg.sdrinrate) / h->split_unit * h->split_unit;
 	{
-		/* the verify pass maps one workgroup to K2A_VRUN tiles and the item list has room for VDL2_MAXWG private areas: a part
-		 * must not have more tiles than that covers (36 s of air time are 3003 tiles, the bound is 4088) */
+		/* (until round 10 the verify pass mapped one workgroup to K2A_VRUN tiles and the item list has room for VDL2_MAXWG private areas: a
+		 * part could not have more tiles than that covers -- 36 s of air time are 3003 tiles, the bound is 4088.  The pass covers a part
+		 * with any grid now; the bound stays, it is what the lists were tested to) */
 		const double max_frames = ((double)VDL2_MAXWG * K2A_VRUN - 4.0) * 2.0 * K2A_TS - 2.0 * K2A_TS - (double)VDL2_CARRY_FRAMES;
 		const size_t max_part = (size_t)(max_frames * (double)h->sdrclk / 21.0) / h->split_unit * h->split_unit;
 		h->split_default = std::min(h->split_default, max_part);
@@ -935,7 +936,7 @@ static int create_impl(vdl2gpu_t *h)
 	{
 		/* The item lists (what passes a scan's first screen: 80 bytes an item, three sets) by the longest PART the handle can be given
 		 * -- max_push, or what push_checked cuts longer pushes into (36 s of air time, a third more in a test build): 64 items of private
-		 * areas per 1024-instant tile (the verify pass's workgroups take four tiles and an area of 256 each; the probe's 42 a tile), the
+		 * areas per 1024-instant tile (the verify pass's and the probe's workgroups size theirs at 42 a tile: launch_scan), the
 		 * common area half of that again.  A 67 MS push at 2 MS/s keeps round 5's 131 072 + 65 536 items per channel (126 MB a set and
 		 * stream); a handle for pushes of a few MS 32 768 + 32 768 (42 MB). */
 		const long long jmax = (long long)((21ull * cfg.max_push) / (unsigned)h->sdrclk) + 2;
@@ -1320,8 +1321,9 @@ static ScanDrain launch_scan(int which, const K2Params &k2, dim3 grid, hipStream
 	 * not hold goes to the common area */
 	const unsigned item_priv = k2.item_priv;
 	grid.x = std::min<unsigned>(grid.x, VDL2_MAXWG);
-	if (which != SCAN_VERIFY)	/* (the verify pass's grid IS its map of the part: 256 items x its workgroups fit by construction; the others walk their work with any grid) */
-		grid.x = std::max(1u, std::min<unsigned>(grid.x, item_priv / 256u));
+	/* every scan walks its work with any grid (the verify pass too, since round 10: its workgroups share the part's pieces out among
+	 * however many they are), so one bound holds for all three: a private area of 256 items at least for every workgroup */
+	grid.x = std::max(1u, std::min<unsigned>(grid.x, item_priv / 256u));
 	unsigned want = (tiles_per_wg * (which == SCAN_REGION ? 400u : 42u * (K2A_TS / 1024u)) + 128u + 255u) / 256u * 256u;	/* (42 of a 1024-instant tile pass: 2.7 % x 1.5) */
 	q.surv_common_cap = 0;	/* (0: whatever the list has left behind the private areas) */
 #ifdef VDL2GPU_TESTHOOKS
@@ -1351,6 +1353,15 @@ static ScanDrain launch_scan(int which, const K2Params &k2, dim3 grid, hipStream
 	d.pch = q.surv_pch;
 	d.nwg = q.surv_nwg;
 	return d;
+}
+
+/* tiles' worth of items a verify workgroup's private area is sized for: its share q of the pieces (k2a_verify) when a launch of
+ * nwg workgroups per channel scans all of a part -- the pieces' instants are the part's at most, and a stretch's partial last piece
+ * rounds a share up by one */
+static unsigned verify_share(unsigned pieces, unsigned nwg)
+{
+	nwg = std::max(1u, std::min<unsigned>(nwg, VDL2_MAXWG));
+	return (pieces + nwg - 1) / nwg + 1;
 }
 
 /* A sample format as a kernel instantiation: f is called with std::integral_constant<int, FMT> of the handle's format, and launches
@@ -1515,7 +1526,17 @@ static int enqueue_back(vdl2gpu_t *h)
 		HIPCHK(h, hipEventRecord(pt.e[3], rs));
 	if (staged)
 		HIPCHK(h, hipEventRecord(pt.e[13], rs));
-	const dim3 vgrid0((tiles / 2 + 1 + K2A_VRUN - 1) / K2A_VRUN, (unsigned)h->C, (unsigned)GS);
+	/* The verify pass's pieces (k2a_verify): a part's stretches are disjoint, so at most a piece per tile of 2 * K2A_TS samples and one
+	 * more per stretch.  The first pass's grid is ONE RESIDENT ROUND -- six workgroups a CU, shared out over the (channel, stream)
+	 * slots, about seven pieces each at 8 channels and 67 MS -- and no longer the map of the part (a workgroup per K2A_VRUN tiles: 2 800
+	 * workgroups for 1 536 places; -DK2A_VGRID_RESIDENT=0 is that grid, DESIGN.md section 5 has both). */
+	const unsigned vpieces = tiles / 2 + 1;
+#if K2A_VGRID_RESIDENT
+	const unsigned vwg0 = std::min(vpieces, std::max(1u, (unsigned)h->n_cu * 6u / (unsigned)(h->C * GS)));
+#else
+	const unsigned vwg0 = (vpieces + K2A_VRUN - 1) / K2A_VRUN;
+#endif
+	const dim3 vgrid0(vwg0, (unsigned)h->C, (unsigned)GS);
 	ScanDrain vdrain;	/* the verify pass whose common area the next one-workgroup-per-channel kernel of the tail has to drain */
 	if (h->k2f_rec)		/* the channel states the resolver starts from are committed on the previous push's tail */
 		HIPCHK(h, hipStreamWaitEvent(rs, h->k2f_done, 0));
@@ -1548,7 +1569,7 @@ static int enqueue_back(vdl2gpu_t *h)
 	if (staged)
 		HIPCHK(h, hipEventRecord(pt.e[12], h->stream));
 	if (!serial)
-		vdrain = launch_scan(SCAN_VERIFY, k2, vgrid0, h->stream, VDL2_SURV_VERIFY, 1, 0, K2A_VRUN);
+		vdrain = launch_scan(SCAN_VERIFY, k2, vgrid0, h->stream, VDL2_SURV_VERIFY, 1, 0, verify_share(vpieces, vgrid0.x));
 	HIPCHK(h, hipGetLastError());
 	if (staged && h->stage_dump)
 		HIPCHK(h, hipEventRecord(pt.e[15], h->stream));
@@ -1586,7 +1607,7 @@ static int enqueue_back(vdl2gpu_t *h)
 		 * last round is a complete one: that re-makes the failing channels' clusters, whose descriptors the decode may be reading) */
 		if (spec && h->repair_rounds >= 2 && ts != ps)
 			HIPCHK(h, hipStreamWaitEvent(ts, h->pay_done, 0));
-		const dim3 vgrid((tiles / 2 + 1 + K2A_VRUN - 1) / K2A_VRUN, (unsigned)h->C, (unsigned)GS);
+		const dim3 vgrid(vgrid0);
 		for (int rr = 1; rr <= h->repair_rounds; ++rr) {
 			k2r.round = rr;
 			k2r.full_round = (rr == h->repair_rounds && h->repair_rounds >= 2) ? 1 : 0;
@@ -1614,12 +1635,12 @@ static int enqueue_back(vdl2gpu_t *h)
 					HIPCHK(h, hipEventRecord(pt.e[18], ts));
 				scan_drain(k2r, ScanDrain());
 				{
-					/* a handful of workgroups per channel, each walking its share of the part's runs of tiles (k2a_verify): the stretches a
-					 * local repair changed are a few tiles, and every workgroup of the launch, the 2 800 that find nothing included, has to
-					 * wait for a slot beside the other pushes' wide kernels before it can leave */
-					const unsigned nv = std::min<unsigned>(vgrid.x, (unsigned)h->knob.verify2_wg);
+					/* a handful of workgroups per channel, which share the pieces of the stretches a local repair changed out among
+					 * themselves (k2a_verify: a few tiles as a rule, a piece or two each; at most the part): every workgroup of a launch
+					 * has to wait for a slot beside the other pushes' wide kernels before it can leave */
+					const unsigned nv = std::min<unsigned>(vpieces, (unsigned)h->knob.verify2_wg);
 					const dim3 vnarrow(nv, vgrid.y, vgrid.z);
-					vdrain = launch_scan(SCAN_VERIFY, k2r, vnarrow, ts, VDL2_SURV_VERIFY + rr, 1, 0, K2A_VRUN * ((vgrid.x + nv - 1) / nv));
+					vdrain = launch_scan(SCAN_VERIFY, k2r, vnarrow, ts, VDL2_SURV_VERIFY + rr, 1, 0, verify_share(vpieces, nv));
 				}
 			} else {
 				/* a further round resolves the channels that still fail again from their input state, with everything listed so far */
@@ -1627,7 +1648,7 @@ static int enqueue_back(vdl2gpu_t *h)
 				hipLaunchKernelGGL(k2s_merge, gch, dim3(K2M_NT), 0, ts, k2r);
 				scan_drain(k2r, ScanDrain());
 				hipLaunchKernelGGL(k2c_resolve, gch, dim3(K2_NT), 0, ts, k2r);
-				vdrain = launch_scan(SCAN_VERIFY, k2r, vgrid, ts, VDL2_SURV_VERIFY + rr, 1, 0, K2A_VRUN);
+				vdrain = launch_scan(SCAN_VERIFY, k2r, vgrid, ts, VDL2_SURV_VERIFY + rr, 1, 0, verify_share(vpieces, vgrid.x));
 			}
 		}
 		HIPCHK(h, hipGetLastError());

@@ -1266,17 +1266,105 @@ void k2a_region(K2Params p)
 		atomicAdd(p.dbg + 48 + threadIdx.x, sh.prof[threadIdx.x]);
 }
 
-/* one workgroup = K2A_VRUN tiles of 2*K2A_TS samples; every piece of a verify segment inside a tile
- * is scanned in the segment's class */
+/* The verify pass's work is the ordered list of a channel's PIECES: stretch k (Seg{lo, hi, r}) yields n_k = ceil(evaluations_k /
+ * K2A_TS) of them, aligned at the stretch's own lo -- piece j covers [lo + j * 2 * K2A_TS, min(hi, lo + (j + 1) * 2 * K2A_TS)), in the
+ * stretch's parity, so only a stretch's last piece is a partial tile -- and T = sum n_k.  The launch's workgroups share them out in
+ * chunks of q = ceil(T / gridDim.x) consecutive pieces: workgroup w takes chunks w, w + gridDim.x, ... while they begin below T.  Any
+ * grid covers the part (the host sizes it by what runs at once, not by the part: enqueue_back), no workgroup takes a turn with
+ * nothing to scan, and a chunk of more than K2A_VITEMS pieces is worked off in batches of so many.
+ * [Until round 10 a workgroup took runs of four grid-aligned tiles and looked for the stretches inside: 2 800 workgroups on the
+ * first pass, an eighth of them for nothing; stretches cut at the grid at both ends; the item list built by one lane that read
+ * every listed Seg again; and on a repair round's pass 44 turns of barriers and a device-memory round trip per workgroup to find the
+ * ten tiles of two or three stretches.] */
 #ifndef K2A_VRUN
-#define K2A_VRUN 4
+#define K2A_VRUN 4		/* pieces per workgroup the host sizes the first pass's grid by where it is not the resident round (enqueue_back) */
 #endif
-#define K2A_VITEMS 64
+#ifndef K2A_VGRID_RESIDENT
+#define K2A_VGRID_RESIDENT 1	/* the first pass's grid: one resident round (1) or a workgroup per K2A_VRUN pieces of the part (0) */
+#endif
+#define K2A_VITEMS 64		/* pieces a workgroup lists at once */
+
+/* a stretch as the pass scans it: inside [p_lo, t_end) like the tiles of old (the resolver writes nothing else), lo in the stretch's
+ * parity; returns its pieces */
+__device__ __forceinline__ int k2a_vseg(const Seg *segs, int k, int nseg, int p_lo, int t_end, int &lo, int &hi, int &r)
+{
+	lo = hi = r = 0;
+	if (k >= nseg)
+		return 0;
+	const Seg g = segs[k];
+	lo = g.lo > p_lo ? g.lo : p_lo;
+	lo += (lo ^ g.lo) & 1;
+	hi = g.hi < t_end ? g.hi : t_end;
+	r = g.r & 3;
+	if (g.hi <= g.lo || hi <= lo) {
+		hi = lo;
+		return 0;
+	}
+	return ((hi - lo + 1) / 2 + K2A_TS - 1) / K2A_TS;
+}
+
+/* the workgroup's sum of v, and (exclusive) what the threads below have; two barriers; s_w[] is free again behind it */
+__device__ __forceinline__ int k2a_vscan(int v, int *s_w, int &total)
+{
+	/* (the wavefront's part with DPP shifts: a shuffle's lane addresses and masks are loop invariants the compiler would hold in
+	 * registers through the tile loop, which has none to spare) */
+	int incl = v;
+	incl += __builtin_amdgcn_update_dpp(0, incl, 0x111, 0xf, 0xf, false);	/* row_shr:1 */
+	incl += __builtin_amdgcn_update_dpp(0, incl, 0x112, 0xf, 0xf, false);	/* row_shr:2 */
+	incl += __builtin_amdgcn_update_dpp(0, incl, 0x114, 0xf, 0xf, false);	/* row_shr:4 */
+	incl += __builtin_amdgcn_update_dpp(0, incl, 0x118, 0xf, 0xf, false);	/* row_shr:8 */
+	incl += __builtin_amdgcn_update_dpp(0, incl, 0x142, 0xa, 0xf, false);	/* row_bcast:15 into rows 1 and 3 */
+	incl += __builtin_amdgcn_update_dpp(0, incl, 0x143, 0xc, 0xf, false);	/* row_bcast:31 into rows 2 and 3 */
+	__syncthreads();	/* (s_w[] of the scan before has been read) */
+	if ((threadIdx.x & 63) == 63)
+		s_w[threadIdx.x >> 6] = incl;
+	__syncthreads();
+	int base = 0, tot = 0;
+#pragma unroll
+	for (int w = 0; w < K2A_THREADS / 64; ++w) {
+		const int t = s_w[w];
+		base += (w < (int)(threadIdx.x >> 6)) ? t : 0;
+		tot += t;
+	}
+	total = tot;
+	return base + incl - v;
+}
+
+/* pieces [a, b) of the channel's list (b - a <= K2A_VITEMS) into s_item[]: the exclusive prefix of n_k by a block scan per chunk of
+ * K2A_THREADS stretches with a carried base, and every thread whose stretch has pieces in [a, b) writes them itself.  FIRST: the
+ * stretches of chunk 0 are the ones the thread holds from the count (lo0, hi0, r0, n0): as a rule (at most K2A_THREADS stretches,
+ * one batch per workgroup) no Seg is read twice. */
+template <bool FIRST> __device__ __forceinline__ void k2a_vitems(const Seg *segs, int nseg, int p_lo, int t_end, int a, int b, int lo0, int hi0, int r0,
+								  int n0, int *s_w, int4 *s_item)
+{
+	int carry = 0;
+	for (int k0 = 0; k0 < nseg && carry < b; k0 += K2A_THREADS) {	/* (block-uniform; nseg <= VDL2_SEG_CAP) */
+		int lo, hi, r, n;
+		if (FIRST && k0 == 0) {
+			lo = lo0;
+			hi = hi0;
+			r = r0;
+			n = n0;
+		} else
+			n = k2a_vseg(segs, k0 + (int)threadIdx.x, nseg, p_lo, t_end, lo, hi, r);
+		int tot;
+		const int e = carry + k2a_vscan(n, s_w, tot);
+		carry += tot;
+		int j = a > e ? a - e : 0;
+		const int j1 = (b - e < n) ? b - e : n;
+		for (; j < j1; ++j) {	/* (at most K2A_VITEMS turns) */
+			const int l = lo + j * 2 * K2A_TS;
+			s_item[e + j - a] = make_int4(l, (hi - l > 2 * K2A_TS) ? l + 2 * K2A_TS : hi, r, 0);
+		}
+	}
+	__syncthreads();
+}
+
 __global__ __launch_bounds__(K2A_THREADS) __attribute__((amdgpu_waves_per_eu(K2A_WPE, 8)))
 void k2a_verify(K2Params p)
 {
 	__shared__ K2aShared sh;
-	__shared__ int s_list[64], s_nl, s_ni;
+	__shared__ int s_w[K2A_THREADS / 64];
 	__shared__ int4 s_item[K2A_VITEMS];	/* lo, hi (stream-relative samples), sub-phase */
 	const int tid = threadIdx.x;
 	const int c = blockIdx.y, s = (int)blockIdx.z;
@@ -1287,69 +1375,58 @@ void k2a_verify(K2Params p)
 		return;
 	const long long dec_base = p.dec_base;
 	const int t_end = (int)(VDL2_CARRY_FRAMES + p.J);
-	const int nseg = (int)p.ctl[CTL_NSEG0 + sc];
+	int nseg = (int)p.ctl[CTL_NSEG0 + sc];
+	nseg = nseg < 0 || nseg > VDL2_SEG_CAP ? VDL2_SEG_CAP : nseg;	/* (the resolver counts the stretches the list did not hold as well) */
 	const Seg *segs = p.segs + (size_t)sc * VDL2_SEG_CAP;
-	if (nseg == 0 || (int)(p.cs[sc].pos - dec_base) + (int)blockIdx.x * K2A_VRUN * 2 * K2A_TS >= t_end)	/* (block-uniform) nothing to look at: not even the tables */
+	if (nseg == 0)	/* (block-uniform) nothing to look at: not even the tables */
 		return;
+	const int p_lo = (int)(p.cs[sc].pos - dec_base);
+	/* the count: T, and the thread's stretch of the first K2A_THREADS */
+	int lo0, hi0, r0;
+	const int n0 = k2a_vseg(segs, tid, nseg, p_lo, t_end, lo0, hi0, r0);
+	int T;
+	{
+		int mine = n0;
+		for (int k = K2A_THREADS + tid; k < nseg; k += K2A_THREADS) {
+			int lo, hi, r;
+			mine += k2a_vseg(segs, k, nseg, p_lo, t_end, lo, hi, r);
+		}
+		k2a_vscan(mine, s_w, T);
+	}
+	const int G = (int)gridDim.x;
+	const int q = (T + G - 1) / G;
+	int ch = (int)blockIdx.x;	/* the chunk the workgroup is at, [a, c_end) what is left of it */
+	int a = ch * q;
+	if (a >= T)	/* (block-uniform; T == 0 as well) no share: not even the tables */
+		return;
+	int c_end = a + q < T ? a + q : T;
 	k2a_tables(sh);
 	K2aPre<2> pre;
 	pre.loaded = false;
 	pre.tiles = 0;
-	/* a workgroup's runs of K2A_VRUN tiles: blockIdx.x, blockIdx.x + gridDim.x, ... -- the first pass's grid has a workgroup per run;
-	 * a repair round's pass, which looks at the few stretches a local repair changed, is launched with a handful of workgroups per
-	 * channel (enqueue_back: 2 800 workgroups that find nothing each wait for a slot beside the other pushes' wide kernels) */
-	for (int run = (int)blockIdx.x;; run += (int)gridDim.x) {
-		const int r_lo = (int)(p.cs[sc].pos - dec_base) + run * K2A_VRUN * 2 * K2A_TS;
-		if (r_lo >= t_end)
-			break;
-		const int r_hi = r_lo + K2A_VRUN * 2 * K2A_TS < t_end ? r_lo + K2A_VRUN * 2 * K2A_TS : t_end;
-		__syncthreads();	/* (the lists of the run before have been read) */
-		if (tid == 0)
-			s_nl = 0;
-		__syncthreads();
-		for (int k = tid; k < nseg && k < VDL2_SEG_CAP; k += K2A_THREADS) {
-			const Seg g = segs[k];
-			if (g.lo < r_hi && g.hi > r_lo && g.hi > g.lo) {
-				const int q = atomicAdd(&s_nl, 1);
-				if (q < 64)
-					s_list[q] = k;
-			}
-		}
-		__syncthreads();
-		const int nl = s_nl;
-		if (nl == 0)	/* (block-uniform) */
-			continue;
-		if (tid == 0) {
-			int ni = 0;
-			for (int q = 0; q < nl && q < 64; ++q) {
-				const Seg g = segs[s_list[q]];
-				for (int t_lo = r_lo; t_lo < r_hi; t_lo += 2 * K2A_TS) {
-					const int t_hi = t_lo + 2 * K2A_TS < r_hi ? t_lo + 2 * K2A_TS : r_hi;
-					int lo = g.lo > t_lo ? g.lo : t_lo;
-					const int hi = g.hi < t_hi ? g.hi : t_hi;
-					lo += (lo ^ g.lo) & 1;		/* keep the segment's parity */
-					if (lo >= hi)
-						continue;
-					if (ni < K2A_VITEMS)
-						s_item[ni] = make_int4(lo, hi, g.r, 0);
-					++ni;
-				}
-			}
-			s_ni = ni;
-		}
-		__syncthreads();
-		const int ni = s_ni;
-		if (nl > 64 || ni > K2A_VITEMS) {	/* absurdly fragmented stretch: give up on the tables for this channel */
-			if (tid == 0)
-				atomicMin(p.fail + sc, 0);
-			break;
-		}
-		for (int q = 0; q < ni; ++q) {
-			const int4 it = s_item[q];
-			const int4 nx = (q + 1 < ni) ? s_item[q + 1] : make_int4(0, 0, 0, 0);
+	int b = a + K2A_VITEMS < c_end ? a + K2A_VITEMS : c_end;
+	k2a_vitems<true>(segs, nseg, p_lo, t_end, a, b, lo0, hi0, r0, n0, s_w, s_item);
+	for (;;) {
+		const int ni = b - a;
+		if (p.dbg && tid < ni)	/* slot 30 (free until round 10): evaluation instants of every piece scanned */
+			atomicAdd(p.dbg + 30, (unsigned long long)((s_item[tid].y - s_item[tid].x + 1) / 2));
+		for (int i = 0; i < ni; ++i) {
+			const int4 it = s_item[i];
+			const int4 nx = (i + 1 < ni) ? s_item[i + 1] : make_int4(0, 0, 0, 0);
 			k2a_tile<2>(sh, p, sc, dec_base, dec_base + it.x, (it.y - it.x + 1) / 2, 1u << it.z, 1, dec_base + it.x, dec_base + it.y,
 				    p.fail + sc, pre, dec_base + nx.x, (nx.y - nx.x + 1) / 2);
 		}
+		a = b;
+		if (a >= c_end) {
+			ch += G;
+			a = ch * q;
+			if (a >= T)
+				break;
+			c_end = a + q < T ? a + q : T;
+		}
+		b = a + K2A_VITEMS < c_end ? a + K2A_VITEMS : c_end;
+		__syncthreads();	/* (the batch before has been read) */
+		k2a_vitems<false>(segs, nseg, p_lo, t_end, a, b, 0, 0, 0, 0, s_w, s_item);
 	}
 	k2a_tail(sh, sc);
 }
