@@ -26,6 +26,8 @@ F_DEBUG_HEADS = 64
 F_LEVELS = 128
 F_SOFT_RS = 256
 F_EXACT_FO = 512
+# status of a cluster head (bits 0-1 of vdl2gpu_debug_clheads()'s packed word; nslots in bits 4-7, nburst in bits 24-31)
+CL_STEADY, CL_DEFER_FIRST, CL_NONSTEADY = 0, 1, 2
 
 # every symbol include/vdl2gpu.h declares
 EXPORTS = (
