@@ -129,7 +129,22 @@ typedef struct {
 #define VDL2GPU_F_TEST_NOREGION 8u	/* test hook: drop the region scan; the verify pass must then redo channels serially.  Only
 					 * libvdl2gpu_test.so (the same sources with -DVDL2GPU_TESTHOOKS) honours it, together with the
 					 * VDL2GPU_PRIM_DROP / VDL2GPU_SPLIT_SAMPLES environment handicaps; libvdl2gpu.so rejects the
-					 * flag with VDL2GPU_EINVAL and never reads those variables */
+					 * flag with VDL2GPU_EINVAL and never reads those variables.
+					 * VDL2GPU_TEST_EPOCH=T0 (test build, read once in vdl2gpu_create): the handle begins as if T0 input
+					 * samples per stream had already been pushed and had left the canonical start state behind them --
+					 * total_in = T0, every stream's planes begin at frame D0 - carry with D0 = 21 T0 / SDRCLK, every
+					 * channel's next evaluation is D0 + 1, everything else is the zero / perr = 100 start -- so every
+					 * stamp it hands out (trig_dec, end_dec, sym_first_dec: + D0; trig_sample, end_sample: + T0) and
+					 * samples_in / dec_samples are absolute, the counters start at 0, and whatever the host derives
+					 * from the samples so far (the push's place in the dump schedule and the LO table, the exact-Fo
+					 * base) follows from total_in.  T0 must be one at which the stream is exactly shift-invariant: a
+					 * multiple of 16 SDRCLK (a superperiod of the dump schedule: D0 a multiple of 336), of
+					 * vdl2gpu_lo_len(sdrinrate), and of 32768 with VDL2GPU_F_RTL_QUIRK, at most 2^56; anything else is
+					 * VDL2GPU_EINVAL before any device call.  (With VDL2GPU_F_EXACT_FO the residual oscillator is
+					 * shift-invariant only at multiples of 2 sdrinrate; other admissible T0 are accepted, and the
+					 * rotation is then that of the absolute sample indices.)
+					 * VDL2GPU_TEST_TICKET0=n (test build): k1_fast's work counters, on the device and as the host
+					 * keeps them, start at n instead of 0 (they are 32 bits wide and never reset) */
 #define VDL2GPU_F_FRAMES 16u	/* run the block path (RS, HDLC, FCS) on every push's bursts as well: vdl2gpu_poll_frames() */
 #define VDL2GPU_F_SERIAL 2u	/* diagnostics: skip the parallel sync tables, one serial machine per channel */
 #define VDL2GPU_F_RTL_QUIRK 32u	/* cu8 only: reproduce in_callback() as written (rtl.c:285-292): in every hand-off block of

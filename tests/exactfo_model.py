@@ -42,29 +42,33 @@ def cmul(x, y):
     return out
 
 
-def indices(n, rate, fd, sdrclk=0):
-    """k_m of every output that completes within n inputs from the start of the stream, in Python integers"""
+def indices(n, rate, fd, sdrclk=0, first=0):
+    """k_m of every output that completes within n inputs, in Python integers; the n inputs are samples first .. first + n - 1 of the
+    stream, where `first` is a sample at which the dump schedule begins anew (a multiple of SDRCLK)"""
     sdrclk = sdrclk or rate // 4000
+    assert first % sdrclk == 0
     ends = [int(e) for e in M.window_ends(n, sdrclk, demod._lib.load().vdl2gpu_lo_len(rate))]
     starts = [0] + [e + 1 for e in ends[:-1]]
     m2 = 2 * rate
     f = fd % m2
-    return np.array([(f * ((a + e) % m2)) % m2 for a, e in zip(starts, ends)], np.int64)
+    return np.array([(f * ((a + e + 2 * first) % m2)) % m2 for a, e in zip(starts, ends)], np.int64)
 
 
-def rotate(plane, n, rate, fd, sdrclk=0):
+def rotate(plane, n, rate, fd, sdrclk=0, first=0):
     if fd == 0:
         return plane
     hi, lo = demod.exact_fo_tables(rate)
-    k = indices(n, rate, fd, sdrclk)
+    k = indices(n, rate, fd, sdrclk, first)
     assert len(k) == len(plane)
     return cmul(plane, cmul(hi[k >> 12], lo[k & 4095]))
 
 
-def channelise(raw, fmt, rate, fo, sdrclk=0):
-    """the 84 kS/s plane of one channel of a handle with VDL2GPU_F_EXACT_FO"""
+def channelise(raw, fmt, rate, fo, sdrclk=0, first=0):
+    """the 84 kS/s plane of one channel of a handle with VDL2GPU_F_EXACT_FO; first: the stream index of raw's first sample, a multiple
+    of the schedule's period and of the mixer's table (the mixer and the dump are then those of a stream that begins there)"""
     fg, fd = split(fo)
-    return rotate(M.channelise(raw, fmt, rate, fg, sdrclk), np.asarray(raw).size // PER[fmt], rate, fd, sdrclk)
+    assert first % (sdrclk or rate // 4000) == 0 and first % demod._lib.load().vdl2gpu_lo_len(rate) == 0
+    return rotate(M.channelise(raw, fmt, rate, fg, sdrclk), np.asarray(raw).size // PER[fmt], rate, fd, sdrclk, first)
 
 
 def scenario(rate, fmt, fos, seed=None):

@@ -14,10 +14,10 @@ def _pad(n, q=32768):
 
 
 def regimes(rate=2_000_000, fo=(-50_000, 250_000), seed=3, infos=(1, 2, 3, 28, 31, 60, 66, 70, 200, 247, 250, 497),
-            noise=1.7, gap=0.002):
-    """One burst per FEC-shortening regime / row count, alternating channels."""
+            noise=1.7, gap=0.002, t0=0.003):
+    """One burst per FEC-shortening regime / row count, alternating channels; the first one begins at t0 seconds."""
     rng = np.random.default_rng(seed)
-    bursts, t = [], 0.003
+    bursts, t = [], t0
     for i, n in enumerate(infos):
         b = synth.Burst(chan=i % len(fo), t0=t, info=bytes(rng.integers(0, 256, n, dtype=np.uint8).tolist()),
                         amp=float(rng.uniform(8, 60)), cfo=float(rng.uniform(-400, 400)))
@@ -33,12 +33,12 @@ FO8_10MS = (-2_250_000, -1_750_000, -1_250_000, -300_000, 475_000, 1_000_000, 1_
 FO8_AIR_5MS = (150_000, 425_000, 700_000, 1_000_000, 1_300_000, 1_575_000, 1_850_000, 2_200_000)
 
 
-def eight_channels(rate=2_000_000, seed=8, dur=0.16, info=(3, 17, 40, 64, 90, 130, 5, 75), fo=None):
-    """Config-2 shape: 8 channels, bursts overlapping in time on different channels."""
+def eight_channels(rate=2_000_000, seed=8, dur=0.16, info=(3, 17, 40, 64, 90, 130, 5, 75), fo=None, t0=0.002):
+    """Config-2 shape: 8 channels, bursts overlapping in time on different channels; the first one begins at t0 seconds."""
     rng = np.random.default_rng(seed)
     bursts = []
     for c in range(8):
-        b = synth.Burst(chan=c, t0=0.002 + 0.004 * c + rng.uniform(0, 1e-3),
+        b = synth.Burst(chan=c, t0=t0 + 0.004 * c + rng.uniform(0, 1e-3),
                         info=bytes(rng.integers(0, 256, info[c], dtype=np.uint8).tolist()),
                         amp=float(rng.uniform(10, 40)), cfo=float(rng.uniform(-400, 400)))
         bursts.append(b)
@@ -49,6 +49,21 @@ def eight_channels(rate=2_000_000, seed=8, dur=0.16, info=(3, 17, 40, 64, 90, 13
         if b2.t0 + b2.duration() < dur - 0.002:
             bursts.append(b2)
     return synth.StreamSpec(rate=rate, fo=tuple(fo) if fo else FO8, nsamples=_pad(int(dur * rate)), bursts=bursts, noise=1.6, seed=seed)
+
+
+def placed(rate, fo, seed, plan, tail=0.006, noise=1.7, q=32768, nsamples=None):
+    """Bursts where a test wants them: plan = [(start in seconds, info bytes)], channels in turn; the stream ends `tail` seconds behind the
+    last burst, rounded up to whole q samples (or is nsamples long, which must be that much or more)."""
+    rng = np.random.default_rng(seed)
+    bursts, end = [], 0.0
+    for i, (t, n) in enumerate(plan):
+        b = synth.Burst(chan=i % len(fo), t0=t, info=bytes(rng.integers(0, 256, n, dtype=np.uint8).tolist()),
+                        amp=float(rng.uniform(12, 60)), cfo=float(rng.uniform(-400, 400)))
+        bursts.append(b)
+        end = max(end, t + b.duration())
+    ns = _pad(int((end + tail) * rate), q)
+    assert nsamples is None or nsamples >= ns
+    return synth.StreamSpec(rate=rate, fo=tuple(fo), nsamples=nsamples or ns, bursts=bursts, noise=noise, seed=seed)
 
 
 def single_short(rate, fo, seed=5, info_len=10, amp=40.0, blocks=4, t0=0.002):

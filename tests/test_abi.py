@@ -110,7 +110,7 @@ def test_product_never_imports_the_oracle():
 
 def test_test_handicaps_exist_only_in_the_test_build(built):
     """libvdl2gpu.so (the product) rejects VDL2GPU_F_TEST_NOREGION and has no code for the VDL2GPU_PRIM_DROP /
-    VDL2GPU_SPLIT_SAMPLES handicaps; libvdl2gpu_test.so (-DVDL2GPU_TESTHOOKS) is what the tests load for them.
+    VDL2GPU_SPLIT_SAMPLES / VDL2GPU_TEST_EPOCH / VDL2GPU_TEST_TICKET0 handicaps; libvdl2gpu_test.so (-DVDL2GPU_TESTHOOKS) is what the tests load for them.
     The flag is checked before any device is touched, so this runs without a GPU."""
     from vdlm2dec_amd import lib
     prod, test = lib.load(), lib.load(testhooks=True)
@@ -130,6 +130,8 @@ def test_test_handicaps_exist_only_in_the_test_build(built):
     tblob = open(lib.LIB_TEST_PATH, "rb").read()
     assert b"VDL2GPU_PRIM_DROP" in tblob and b"VDL2GPU_TEST_ITEM_GRID" in tblob and b"VDL2GPU_TEST_ITEM_COMMON" in tblob
     assert b"VDL2GPU_FRAME_ARENA" not in blob and b"VDL2GPU_FRAME_ARENA" in tblob       # the frame arena's size (tests/test_gpu_full.py)
+    for name in (b"VDL2GPU_TEST_EPOCH", b"VDL2GPU_TEST_TICKET0"):       # the stream epoch and k1_fast's first ticket (tests/test_gpu_epoch.py)
+        assert name not in blob and name in tblob, name
     assert _getenv_outside_create(_host_sources()) == []                    # every knob is read once, in create_impl
 
 

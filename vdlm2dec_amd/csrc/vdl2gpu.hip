@@ -18,6 +18,7 @@
 #include "vdl2gpu_blocks.h"
 
 #include <algorithm>
+#include <cerrno>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -223,6 +224,8 @@ struct vdl2gpu {
 	unsigned *d_headtap_n = nullptr;
 	unsigned headtap_cap = 0;
 	uint64_t total_in = 0;		/* samples per stream pushed so far */
+	uint64_t test_epoch = 0;	/* test build (VDL2GPU_TEST_EPOCH): where total_in starts, see include/vdl2gpu.h */
+	unsigned test_ticket0 = 0;	/* test build (VDL2GPU_TEST_TICKET0): where k1_fast's work counters start */
 	uint64_t pushes = 0;
 	uint64_t overflowed = 0;
 	std::vector<PushTiming> pending;
@@ -946,7 +949,7 @@ static int create_impl(vdl2gpu_t *h)
 		h->item_priv = priv;
 		h->item_cap = priv + std::max(priv / 2, 32768u);	/* (the common area: what a stretch of sync words or a carrier sends past the private areas) */
 	}
-	h->k1_tbase.assign((size_t)S * 8, 0u);
+	h->k1_tbase.assign((size_t)S * 8, h->test_ticket0);
 	h->cap = plane_frames(cfg.max_push, (unsigned)h->sdrclk);	/* planes start on 128-byte lines */
 	const size_t dec_bytes = (size_t)S * (size_t)h->cap * VDL2_CS * sizeof(float2);
 	for (int r = 0; r < VDL2_NSET; ++r) {
@@ -957,6 +960,13 @@ static int create_impl(vdl2gpu_t *h)
 	DEV_ALLOC(h, h->d_lo_ext, (size_t)S * VDL2_CS * (L + 48) * sizeof(float2));
 	DEV_ALLOC(h, h->d_k1_tickets, (size_t)S * 21 * 8 * sizeof(unsigned));
 	HIPCHK(h, hipMemsetAsync(h->d_k1_tickets, 0, (size_t)S * 21 * 8 * sizeof(unsigned), h->stream));
+#ifdef VDL2GPU_TESTHOOKS
+	if (h->test_ticket0) {	/* VDL2GPU_TEST_TICKET0: the counters begin where the host's idea of them does (k1_tbase above) */
+		const std::vector<unsigned> tk0((size_t)S * 21 * 8, h->test_ticket0);
+		HIPCHK(h, hipMemcpyAsync(h->d_k1_tickets, tk0.data(), tk0.size() * sizeof(unsigned), hipMemcpyHostToDevice, h->stream));
+		HIPCHK(h, hipStreamSynchronize(h->stream));	/* (tk0 ends with this block) */
+	}
+#endif
 	DEV_ALLOC(h, h->d_ss, (size_t)S * sizeof(StreamState));
 	DEV_ALLOC(h, h->d_cs, (size_t)S * VDL2_CS * sizeof(ChanState));
 	DEV_ALLOC(h, h->d_cfg, (size_t)S * VDL2_CS * sizeof(ChanCfg));
@@ -1133,17 +1143,21 @@ static int create_impl(vdl2gpu_t *h)
 	fill_set_params(h);
 
 	/* canonical start state: everything zero except initD8psk's perr=100 (d8psk.c:28-37);
-	 * 16 zero frames stand for the empty Inbuff ring */
+	 * 16 zero frames stand for the empty Inbuff ring.  A test build's stream epoch (VDL2GPU_TEST_EPOCH) moves the same state
+	 * to the stream time of sample test_epoch: d0 frames on (0 otherwise); everything the host derives from the samples so
+	 * far follows from total_in (vdl2gpu_plan, the exact-Fo base and dec_base in push_impl, vdl2gpu_get_stats). */
+	h->total_in = h->test_epoch;
+	const long long d0 = (long long)(((unsigned __int128)h->test_epoch * 21u) / (unsigned)h->sdrclk);
 	std::vector<StreamState> ss(S);
 	memset(ss.data(), 0, ss.size() * sizeof(StreamState));
 	for (auto &x : ss) {
-		x.dec_base = -VDL2_CARRY_FRAMES;	/* new output always starts at frame VDL2_CARRY_FRAMES; zeros before it */
+		x.dec_base = d0 - VDL2_CARRY_FRAMES;	/* new output always starts at frame VDL2_CARRY_FRAMES; zeros before it */
 		x.dec_fill = VDL2_CARRY_FRAMES;
 	}
 	std::vector<ChanState> cs((size_t)S * VDL2_CS);
 	memset(cs.data(), 0, cs.size() * sizeof(ChanState));
 	for (auto &x : cs) {
-		x.pos = 1;	/* clk: 0 -> 4 (sample 0, idle) -> 8 (sample 1, evaluate) */
+		x.pos = d0 + 1;	/* clk: 0 -> 4 (sample 0, idle) -> 8 (sample 1, evaluate) */
 		x.r = 0;
 		x.fresh = 0;	/* the all-zero start ring counts as history */
 		x.perr = 100.0f;
@@ -1192,6 +1206,32 @@ extern "C" int vdl2gpu_create(const vdl2gpu_config_t *cfg, vdl2gpu_t **out)
 	const long long cap = plane_frames(cfg->max_push, sdrclk);
 	if (cap == 0 || (unsigned long long)cap * VDL2_CS * sizeof(float2) >= VDL2_PLANES_MAX)
 		return VDL2GPU_EINVAL;	/* a stream's planes must stay below 4 GiB (k1_fast's 32-bit offsets) */
+	uint64_t test_epoch = 0;
+	unsigned test_ticket0 = 0;
+#ifdef VDL2GPU_TESTHOOKS
+	/* The stream epoch (include/vdl2gpu.h, beside VDL2GPU_F_TEST_NOREGION): only a T0 at which the stream is exactly shift-invariant
+	 * -- whole superperiods of the dump schedule (16 SDRCLK inputs, 336 outputs), whole LO tables, whole hand-off blocks of the quirk --
+	 * and one whose stamps stay far inside 63 bits.  Refused before any device call. */
+	auto env_u64 = [](const char *name, unsigned long long max, unsigned long long *out) {	/* decimal digits only, at most max; unset: *out stays */
+		const char *v = getenv(name);
+		if (!v)
+			return true;
+		char *end = nullptr;
+		errno = 0;
+		const unsigned long long x = strtoull(v, &end, 10);
+		if (errno || end == v || *end || *v < '0' || *v > '9' || x > max)
+			return false;
+		*out = x;
+		return true;
+	};
+	unsigned long long t0 = 0, tk0 = 0;
+	if (!env_u64("VDL2GPU_TEST_EPOCH", 1ull << 56, &t0) || !env_u64("VDL2GPU_TEST_TICKET0", 0xffffffffull, &tk0))
+		return VDL2GPU_EINVAL;
+	if (t0 % (16ull * sdrclk) || t0 % lo_len || ((cfg->flags & VDL2GPU_F_RTL_QUIRK) && t0 % 32768))
+		return VDL2GPU_EINVAL;
+	test_epoch = t0;
+	test_ticket0 = (unsigned)tk0;
+#endif
 	vdl2gpu_t *h = new(std::nothrow) vdl2gpu;
 	if (!h)
 		return VDL2GPU_ENOMEM;
@@ -1206,6 +1246,8 @@ extern "C" int vdl2gpu_create(const vdl2gpu_config_t *cfg, vdl2gpu_t **out)
 	h->rec_cap = cfg->max_bursts ? cfg->max_bursts : 65536u;
 	h->chans.assign(cfg->chan, cfg->chan + (size_t)cfg->nstreams * cfg->nbch);
 	h->cfg.chan = h->chans.data();
+	h->test_epoch = test_epoch;
+	h->test_ticket0 = test_ticket0;
 	const int rc = create_impl(h);
 	if (rc != VDL2GPU_OK) {
 		std::string e = h->err;
