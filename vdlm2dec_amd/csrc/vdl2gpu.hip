@@ -41,10 +41,6 @@ extern "C" void sincosf(float, float *, float *);
 		}                                                                               \
 	} while (0)
 
-#ifdef VDL2GPU_TESTHOOKS
-static int g_test_item_grid = 0, g_test_item_common = 0, g_test_item_verify = 0;	/* read once per vdl2gpu_create (test build only) */
-#endif
-
 #define TRY(expr)                        \
 	do {                             \
 		const int rc__ = (expr); \
@@ -52,21 +48,48 @@ static int g_test_item_grid = 0, g_test_item_common = 0, g_test_item_verify = 0;
 			return rc__;     \
 	} while (0)
 
-/* The HIP events of a push that carries stage events (vdl2gpu_timing_t, VDL2GPU_STAGE_DUMP).  The stage sums are the intervals
- * e0..e7 (harvest_timing): e0 before the channeliser | e1 behind it | e2 clusters begin | e3 clusters end | e4 front stage's
- * scan + sort end | e5 repair rounds end | e6 second payload pass + block path end | e7 tail ends; beside them e8, e9 around
- * the k1_fast / k1_pp launch alone | e10 scan begins | e11 the first period's general launch ends | e12 verify pass begins |
- * e13, e14 around the resolver.  VDL2GPU_STAGE_DUMP only: e15 verify ends | e16 tail begins | e18 local repair ends | e20 commit
- * ends | e21 second payload pass ends | e22 export ends | e23 resolver begins. */
-#define NEV 8
+/* The HIP events of a push that carries stage events (vdl2gpu_timing_t, VDL2GPU_STAGE_DUMP), recorded by mark().  The numbers are
+ * the eN= labels of the stage dump (scripts/dev/stage_gantt.py reads them): they stay.  17 and 19 are no longer recorded. */
+enum StageEv {
+	E_K1_BEGIN = 0, E_K1_END = 1,			/* in front of the channeliser, behind it */
+	E_CLUSTERS_BEGIN = 2, E_CLUSTERS_END = 3,
+	E_FRONT_END = 4,				/* the front stage's scan + sort end */
+	E_ROUNDS_END = 5,				/* repair rounds end */
+	E_BLOCKS_END = 6,				/* second payload pass + block path end */
+	E_TAIL_END = 7,
+	E_K1_KERNEL_BEGIN = 8, E_K1_KERNEL_END = 9,	/* around the k1_fast / k1_pp launch alone */
+	E_SCAN_BEGIN = 10,
+	E_K1_HEAD_END = 11,				/* the first period's general launch ends */
+	E_VERIFY_BEGIN = 12,
+	E_RESOLVE_QUEUED = 13, E_RESOLVE_END = 14,	/* around the resolver, its wait for the previous push's commit included */
+	/* VDL2GPU_STAGE_DUMP only: */
+	E_VERIFY_END = 15,
+	E_TAIL_BEGIN = 16,				/* the verify pass has been seen on the tail's stream */
+	E_PATCH_END = 18,				/* local repair ends */
+	E_COMMIT_END = 20, E_PAYLOAD2_END = 21, E_EXPORT_END = 22,	/* commit, second payload pass, export end */
+	E_RESOLVE_BEGIN = 23,				/* the previous push's commit has been seen */
+};
 #define NEVX 24
 struct PushTiming {
-	hipEvent_t e[NEVX];
+	hipEvent_t e[NEVX];	/* by StageEv */
 	uint64_t samples;
 	uint64_t index;		/* which push of the handle (VDL2GPU_STAGE_DUMP) */
 	bool fast;
 	bool staged;
-	int fast_parts;		/* fast-kernel launches of this push (e[8]..e[9]) */
+	int fast_parts;		/* fast-kernel launches of this push (E_K1_KERNEL_BEGIN..E_K1_KERNEL_END) */
+};
+
+/* An event that may not have been recorded yet (the first pushes of a handle; a path not taken yet): waiting for it then waits
+ * for nothing.  The rule: an event that something may wait for before any record is a LaterEvent; an event whose record is certain
+ * wherever it is waited for -- earlier in the same call (f_done, k2c_done, pay_done, verify_done, raw_copied), or by the condition
+ * of the wait itself (f_tail: last_two_streams) -- is a plain hipEvent_t. */
+struct LaterEvent {
+	hipEvent_t ev = nullptr;
+	bool recorded = false;
+	int record(vdl2gpu_t *h, hipStream_t s);
+	int wait(vdl2gpu_t *h, hipStream_t s) const;	/* the stream waits */
+	int sync(vdl2gpu_t *h) const;			/* the calling thread waits */
+	void clear() { recorded = false; }
 };
 
 /* A burst record has side columns: entries at the record's index in the device rings, the slabs and the host queue, present when
@@ -77,10 +100,11 @@ static const size_t col_bytes[VDL2_NCOL] = { sizeof(vdl2gpu_soft_t), sizeof(vdl2
 /* A table set (push % VDL2_NSET): what a push's demodulator kernels work in, see alloc_sets. */
 struct TableSet {
 	K2Params k2{};		/* the set's 21 tables (cands ... items, ctl, fmask), its plane set, and every parameter that never changes */
-	hipEvent_t k2_done = nullptr;	/* the end of the tail of the push that used the set */
+	LaterEvent k2_done;		/* the end of the tail of the push that used the set */
 	hipEvent_t f_done = nullptr;	/* FRONT of the push on the set has been enqueued up to its last kernel */
-	bool k2_rec = false;
 };
+static inline int set_before(int par) { return (par + VDL2_NSET - 1) % VDL2_NSET; }	/* the set of the push before the one on set `par` */
+static inline int set_after(int par) { return (par + 1) % VDL2_NSET; }			/* ... of the push after it */
 
 /* An output ring (push % VDL2_NRING): the calling thread waits for the ring's previous push only three pushes later -- with two
  * rings it waited for the tail of the push before last in every call, and the GPU's front stream waited for the calling thread. */
@@ -93,8 +117,7 @@ struct OutRing {
 					 * collector that waits for one with the handle lock released (wait_harvest) would otherwise wait on an
 					 * event the producer may re-record for the push three later */
 	int ev = 0;			/* which of the two the ring's current push recorded */
-	hipEvent_t in_read = nullptr;	/* its channeliser has read the caller's device buffer */
-	bool in_rec = false;
+	LaterEvent in_read;		/* its channeliser has read the caller's device buffer (cleared by a push from host memory) */
 	uint64_t push = 0;		/* which push filled the ring */
 	size_t samples = 0;		/* samples (per stream) of that push */
 	int slab = 0;			/* the slab its records were exported to */
@@ -152,15 +175,13 @@ struct vdl2gpu {
 	hipEvent_t raw_copied[2] = {nullptr, nullptr};
 	void *d_raw[2] = {nullptr, nullptr};
 	size_t raw_bytes[2] = {0, 0};
-	bool k1_rec[2] = {false, false};	/* k1_done[i] has been recorded at least once */
 	/* ingest ring (rtl.c:274-295, air.c:191-217): pinned host slots the producer fills in place */
 	void *ring_host = nullptr;
 	size_t ring_slot_samples = 0, ring_slot_bytes = 0;
 	int ring_nslots = 0;
 	unsigned long long ring_next = 0;
 	bool ring_acquired = false;
-	std::vector<hipEvent_t> ring_copied;
-	std::vector<char> ring_inflight;
+	std::vector<LaterEvent> ring_copied;	/* per slot: its copy to the GPU has left it (cleared once acquire has waited for it) */
 	float2 *d_lo = nullptr;
 	bool rot = false;		/* VDL2GPU_F_EXACT_FO with a channel off the 25 kHz grid: the rotating instantiations of the K1 kernels run */
 	K1Rot k1rot{};			/* their second argument: the tables (create_impl), and the push's place in the schedule (push) */
@@ -202,10 +223,10 @@ struct vdl2gpu {
 	int stage_every = 4;
 	bool stage_dump = false;	/* VDL2GPU_STAGE_DUMP=1: events on every push, their times printed when the push is collected (harvest_timing) */
 	hipEvent_t ev_origin = nullptr;
-	hipEvent_t k1_done[2] = {nullptr, nullptr};	/* per staging buffer (host input) */
+	LaterEvent k1_done[2];		/* per staging buffer (host input): the channeliser has read it */
 	hipStream_t pay_stream = nullptr;	/* K2d beside the verify pass; then the push's TAIL (repair rounds, commit, export, counters: see enqueue_back) */
-	hipEvent_t verify_done = nullptr, k2f_done = nullptr;	/* main -> tail: the verify pass has run; tail -> main: the channel states are committed */
-	bool k2f_rec = false;
+	hipEvent_t verify_done = nullptr;	/* main -> tail: the verify pass has run */
+	LaterEvent k2f_done;			/* tail -> main: the channel states are committed */
 	hipStream_t tail_prev = nullptr;	/* the stream the previous push's tail ran on */
 	hipEvent_t k2c_done = nullptr, pay_done = nullptr;
 	int repair_rounds = 0;		/* adapted floor..4 from how often the serial fallback was needed */
@@ -275,6 +296,11 @@ struct vdl2gpu {
 		int verify2_wg = 8;		/* VDL2GPU_VERIFY2_WG: workgroups per channel of the local repair round's verify pass */
 		int k1_dbg = 0;			/* VDL2GPU_K1_DBG */
 		int k1_nsub = 0;		/* VDL2GPU_K1_NSUB */
+#ifdef VDL2GPU_TESTHOOKS
+		int test_item_grid = 0;		/* VDL2GPU_TEST_ITEM_GRID: few scan workgroups with the smallest private areas -- most items take the common area's path */
+		int test_item_common = 0;	/* VDL2GPU_TEST_ITEM_COMMON: a common area of so many items -- the list overflows */
+		int test_item_verify = 0;	/* VDL2GPU_TEST_ITEM_VERIFY: the two above for the verify passes only */
+#endif
 	} knob;
 	/* A push's work is three stages on three streams, and three pushes are in the pipeline at once -- the planes, the tables
 	 * (candidates, clusters, descriptors, control words ...) and the output rings exist three times:
@@ -293,19 +319,24 @@ struct vdl2gpu {
 		K2Params k2{};
 		int64_t J = 0;
 		int par = 0, ring = 0, slab = 0;
-		bool staged = false, serial = false, two_streams = false;
+		bool serial = false, two_streams = false;
+		bool spec = false;	/* the payloads are decoded beside the verify pass, ahead of its verdict (push_impl decides; K2Params.sel_reserved) */
 		unsigned tiles = 0;
 		size_t pt_index = 0;	/* its PushTiming in `pending` */
 	} back;
 	hipStream_t fstream = nullptr;
-	hipEvent_t k1_ev = nullptr;	/* channeliser + carry copy of the latest push that kept to the main stream */
+	LaterEvent k1_ev;		/* channeliser + carry copy of the latest push that kept to the main stream */
 	hipEvent_t f_tail = nullptr;	/* the end of the latest front stage on fstream (carry copy included) */
-	bool k1_ev_rec = false, last_two_streams = false;
+	bool last_two_streams = false;
 	int64_t last_J = 0;	/* outputs of the previous push: where its last 49152 frames lie */
 	/* stage sums of the pushes that carried stage events, unscaled, and how many those were */
 	double st_scan = 0, st_cluster = 0, st_resolve = 0, st_demod = 0, st_other = 0, st_k1 = 0;
 	uint64_t st_pushes = 0;
 };
+
+int LaterEvent::record(vdl2gpu_t *h, hipStream_t s) { HIPCHK(h, hipEventRecord(ev, s)); recorded = true; return VDL2GPU_OK; }
+int LaterEvent::wait(vdl2gpu_t *h, hipStream_t s) const { if (recorded) HIPCHK(h, hipStreamWaitEvent(s, ev, 0)); return VDL2GPU_OK; }
+int LaterEvent::sync(vdl2gpu_t *h) const { if (recorded) HIPCHK(h, hipEventSynchronize(ev)); return VDL2GPU_OK; }
 
 /* ------------------------------------------------------------ pure host helpers */
 extern "C" unsigned int reversebits(const unsigned int bits, const int n)
@@ -902,9 +933,9 @@ static int create_impl(vdl2gpu_t *h)
 	h->knob.k1_nsub = env_int("VDL2GPU_K1_NSUB", 0);
 #ifdef VDL2GPU_TESTHOOKS
 	h->prim_drop = env_int("VDL2GPU_PRIM_DROP", 0);
-	g_test_item_grid = env_int("VDL2GPU_TEST_ITEM_GRID", 0);
-	g_test_item_common = env_int("VDL2GPU_TEST_ITEM_COMMON", 0);
-	g_test_item_verify = env_int("VDL2GPU_TEST_ITEM_VERIFY", 0);	/* the two above for the verify passes only */
+	h->knob.test_item_grid = env_int("VDL2GPU_TEST_ITEM_GRID", 0);
+	h->knob.test_item_common = env_int("VDL2GPU_TEST_ITEM_COMMON", 0);
+	h->knob.test_item_verify = env_int("VDL2GPU_TEST_ITEM_VERIFY", 0);
 #endif
 	/* A push in which a channel's verify pass fails with no round scheduled costs a serial redo of that channel's whole
 	 * push (milliseconds), an idle round 30 us: with 16 channels or more an event somewhere is frequent enough that one
@@ -981,24 +1012,24 @@ static int create_impl(vdl2gpu_t *h)
 	const int prio_normal = 0;
 	NEW_STREAM(h, h->copy_stream, &prio_normal);
 	for (int r = 0; r < 2; ++r)
-		NEW_EVENT(h, h->k1_done[r]);
+		NEW_EVENT(h, h->k1_done[r].ev);
 	for (TableSet &t : h->set)
-		NEW_EVENT(h, t.k2_done);
+		NEW_EVENT(h, t.k2_done.ev);
 	for (OutRing &rg : h->ring) {
 		for (int k = 0; k < 2; ++k)
 			NEW_EVENT(h, rg.done2[k]);
-		NEW_EVENT(h, rg.in_read);
+		NEW_EVENT(h, rg.in_read.ev);
 	}
 	NEW_STREAM(h, h->fstream, &prio_lo);	/* the back stage (main stream, high priority) is the shorter one: it goes first */
 	for (TableSet &t : h->set)
 		NEW_EVENT(h, t.f_done);
-	NEW_EVENT(h, h->k1_ev);
+	NEW_EVENT(h, h->k1_ev.ev);
 	NEW_EVENT(h, h->f_tail);
 	NEW_STREAM(h, h->pay_stream);
 	NEW_EVENT(h, h->k2c_done);
 	NEW_EVENT(h, h->pay_done);
 	NEW_EVENT(h, h->verify_done);
-	NEW_EVENT(h, h->k2f_done);
+	NEW_EVENT(h, h->k2f_done.ev);
 	h->ctl_words = VDL2_CTL_WORDS((size_t)S * VDL2_CS);
 	h->stage_cap = (unsigned)S * VDL2_CS * VDL2_CAND_CAP * VDL2_CL_MAXB + 65536u;	/* static slots + dynamic tail */
 	TRY(alloc_sets(h));
@@ -1274,59 +1305,68 @@ static int get_events(vdl2gpu_t *h, PushTiming &pt)
 	return VDL2GPU_OK;
 }
 
+/* a mark of a push that carries stage events, on stream s; dump_only: one that only VDL2GPU_STAGE_DUMP wants (an event record
+ * between two kernels of a chain costs the stream ~3 us) */
+static int mark(vdl2gpu_t *h, const PushTiming &pt, StageEv ev, hipStream_t s, bool dump_only = false)
+{
+	if (pt.staged && (!dump_only || h->stage_dump))
+		HIPCHK(h, hipEventRecord(pt.e[ev], s));
+	return VDL2GPU_OK;
+}
+
 static int harvest_timing(vdl2gpu_t *h)
 {
+	/* the intervals the stage sums are made of (the demodulator chain starts at the scan, not where the channeliser ended; the
+	 * resolver alone, since it may have run beside the next push's channeliser) */
+	enum { D_K1, D_SCAN, D_CLUSTER, D_RESOLVE, D_VERIFY /* and the repair rounds */, D_COMMIT /* ... second payload pass, block path */, D_OUT, ND };
+	static const struct { StageEv from, to; } stage[ND] = {
+		{E_K1_BEGIN, E_K1_END}, {E_SCAN_BEGIN, E_FRONT_END}, {E_CLUSTERS_BEGIN, E_CLUSTERS_END}, {E_RESOLVE_QUEUED, E_RESOLVE_END},
+		{E_VERIFY_BEGIN, E_ROUNDS_END}, {E_ROUNDS_END, E_BLOCKS_END}, {E_BLOCKS_END, E_TAIL_END},
+	};
+	/* VDL2GPU_STAGE_DUMP=1: where every stage of every push began and ended on the GPU's clock, in us since the handle's first
+	 * push -- a Gantt chart of the pipeline as it runs WITHOUT a profiler (under rocprofv3 the calling thread is what the streams
+	 * wait for), in the pipeline's order (see StageEv.  An event a push does not record keeps the time of the pooled event's last
+	 * use: E_PATCH_END on a push that takes the serial path) */
+	static const StageEv dump_order[] = {
+		E_K1_BEGIN, E_K1_END, E_SCAN_BEGIN, E_FRONT_END, E_CLUSTERS_BEGIN, E_RESOLVE_QUEUED, E_RESOLVE_BEGIN, E_RESOLVE_END, E_VERIFY_BEGIN,
+		E_VERIFY_END, E_TAIL_BEGIN, E_PATCH_END, E_ROUNDS_END, E_COMMIT_END, E_PAYLOAD2_END, E_EXPORT_END, E_BLOCKS_END, E_TAIL_END,
+	};
 	for (auto &pt : h->pending) {
-		float d[NEV - 1] = {0};
+		float d[ND] = {0};
 		if (h->stage_dump && pt.staged && h->ev_origin) {
-			/* VDL2GPU_STAGE_DUMP=1: where every stage of every push began and ended on the GPU's clock, in us since the handle's
-			 * first push -- a Gantt chart of the pipeline as it runs WITHOUT a profiler (under rocprofv3 the calling thread is
-			 * what the streams wait for).  e0 K1 begins | e1 K1 ends | e10 scan begins | e4 front ends | e2 clusters begin |
-			 * e3 = e13 clusters end | e23 resolver begins (the previous push's commit has been seen) | e14 resolver ends | e12 verify
-			 * begins | e15 verify ends | e16 tail begins (the verify pass has been seen on the tail's stream) | e18 local repair ends |
-			 * e5 rounds end | e20 commit ends | e21 second payload pass ends | e22 export ends | e6 block path ends | e7 tail ends
-			 * (see PushTiming.  An event a push does not record keeps the time of the pooled event's last use: e18 on a push
-			 * that takes the serial path) */
-			static const int order[] = {0, 1, 10, 4, 2, 13, 23, 14, 12, 15, 16, 18, 5, 20, 21, 22, 6, 7};
 			fprintf(stderr, "vdl2gpu stage dump push %llu:", (unsigned long long)pt.index);
-			for (int k : order) {
+			for (StageEv k : dump_order) {
 				float t = -1.0f;
 				if (hipEventElapsedTime(&t, h->ev_origin, pt.e[k]) != hipSuccess) {
 					(void)hipGetLastError();
 					t = -1.0f;
 				}
-				fprintf(stderr, " e%d=%.1f", k, t * 1e3f);
+				fprintf(stderr, " e%d=%.1f", (int)k, t * 1e3f);
 			}
 			fprintf(stderr, "\n");
 		}
-		for (int i = 0; i + 1 < NEV; ++i) {	/* the demodulator chain starts at e[10], not where the channeliser ended */
-			if (!pt.staged)
-				break;
-			if (i == 3)	/* the resolver alone (it may have run on its own stream, the next push's channeliser beside it) */
-				HIPCHK(h, hipEventElapsedTime(&d[i], pt.e[13], pt.e[14]));
-			else
-				HIPCHK(h, hipEventElapsedTime(&d[i], i == 1 ? pt.e[10] : (i == 4 ? pt.e[12] : pt.e[i]), i == 1 ? pt.e[4] : pt.e[i + 1]));
-		}
-		if (pt.fast && pt.staged) {	/* kernel intervals only: first period | fast kernel | tail */
-			float a = 0, b = 0, c = 0;
-			HIPCHK(h, hipEventElapsedTime(&a, pt.e[0], pt.e[11]));
-			HIPCHK(h, hipEventElapsedTime(&b, pt.e[8], pt.e[9]));
-			HIPCHK(h, hipEventElapsedTime(&c, pt.e[9], pt.e[1]));
-			d[0] = a + b + c;
-		}
 		if (pt.staged) {	/* only some pushes carry events (each costs the stream ~3 us, and the channeliser now sits on the main
 					 * stream): their mean stands for all (see vdl2gpu_get_timing) */
-			h->st_k1 += d[0];
-			h->st_scan += d[1] + d[4];
-			h->st_cluster += d[2];
-			h->st_resolve += d[3] + d[5];
-			h->st_demod += d[1] + d[2] + d[3] + d[4] + d[5];
-			h->st_other += d[6];
+			for (int i = 0; i < ND; ++i)
+				HIPCHK(h, hipEventElapsedTime(&d[i], pt.e[stage[i].from], pt.e[stage[i].to]));
+			if (pt.fast) {	/* kernel intervals only: first period | fast kernel | tail */
+				float a = 0, b = 0, c = 0;
+				HIPCHK(h, hipEventElapsedTime(&a, pt.e[E_K1_BEGIN], pt.e[E_K1_HEAD_END]));
+				HIPCHK(h, hipEventElapsedTime(&b, pt.e[E_K1_KERNEL_BEGIN], pt.e[E_K1_KERNEL_END]));
+				HIPCHK(h, hipEventElapsedTime(&c, pt.e[E_K1_KERNEL_END], pt.e[E_K1_END]));
+				d[D_K1] = a + b + c;
+			}
+			h->st_k1 += d[D_K1];
+			h->st_scan += d[D_SCAN] + d[D_VERIFY];
+			h->st_cluster += d[D_CLUSTER];
+			h->st_resolve += d[D_RESOLVE] + d[D_COMMIT];
+			h->st_demod += d[D_SCAN] + d[D_CLUSTER] + d[D_RESOLVE] + d[D_VERIFY] + d[D_COMMIT];
+			h->st_other += d[D_OUT];
 			h->st_pushes++;
 		}
 		if (pt.fast && pt.staged) {
 			float f = 0;
-			HIPCHK(h, hipEventElapsedTime(&f, pt.e[8], pt.e[9]));
+			HIPCHK(h, hipEventElapsedTime(&f, pt.e[E_K1_KERNEL_BEGIN], pt.e[E_K1_KERNEL_END]));
 			h->tm.channelise_fast_ms += f;
 			h->tm.fast_pushes++;	/* counts the fast-kernel launches that were timed */
 		}
@@ -1344,18 +1384,11 @@ static void spill_slab(vdl2gpu_t *h, int slab);
 
 /* A scan kernel.  Its workgroups work what passes their first screen off themselves, behind their last tile (k2a_tail); what
  * their private areas of the item list did not hold is left in the list's common area for the one-workgroup-per-channel kernel
- * that follows on the stream -- `drain` says where that is (put into that kernel's parameters with scan_drain()). */
+ * that follows on the stream -- the scan's ScanDrain says where that is, and goes to that kernel's launch (launch_per_channel). */
 enum { SCAN_PROBE, SCAN_REGION, SCAN_VERIFY };
-struct ScanDrain { int slot = -1, mode = 0, skip = 0, pch = 0, nwg = 0; };
-static void scan_drain(K2Params &q, const ScanDrain &d)
-{
-	q.drain_slot = d.slot;
-	q.drain_mode = d.mode;
-	q.drain_skip = d.skip;
-	q.drain_pch = d.pch;
-	q.drain_nwg = d.nwg;
-}
-static ScanDrain launch_scan(int which, const K2Params &k2, dim3 grid, hipStream_t st, int slot, int mode, int skip, unsigned tiles_per_wg)
+enum { SURV_CANDS = 0, SURV_VERIFY = 1, SURV_PROBE = 2, SURV_SEEDS = 3 };	/* K2Params.surv_mode: what a detector hit among the survivors means */
+struct ScanDrain { int slot = -1, mode = 0, skip = 0, pch = 0, nwg = 0; };	/* (slot -1: nothing to drain) */
+static int launch_scan(vdl2gpu_t *h, int which, const K2Params &k2, dim3 grid, hipStream_t st, int slot, int mode, int skip, unsigned tiles_per_wg, ScanDrain &drain)
 {
 	K2Params q = k2;
 	/* a scan workgroup's private part of the item list: one and a half times what its tiles yield at the first screen's 2.7 %
@@ -1369,16 +1402,25 @@ static ScanDrain launch_scan(int which, const K2Params &k2, dim3 grid, hipStream
 	unsigned want = (tiles_per_wg * (which == SCAN_REGION ? 400u : 42u * (K2A_TS / 1024u)) + 128u + 255u) / 256u * 256u;	/* (42 of a 1024-instant tile pass: 2.7 % x 1.5) */
 	q.surv_common_cap = 0;	/* (0: whatever the list has left behind the private areas) */
 #ifdef VDL2GPU_TESTHOOKS
-	const bool test_items = !g_test_item_verify || which == SCAN_VERIFY;
-	if (test_items && g_test_item_grid > 0) {	/* VDL2GPU_TEST_ITEM_GRID: few scan workgroups with the smallest private areas -- most items take the common area's path */
-		grid.x = std::min<unsigned>(grid.x, (unsigned)g_test_item_grid);
+	const bool test_items = !h->knob.test_item_verify || which == SCAN_VERIFY;
+	if (test_items && h->knob.test_item_grid > 0) {
+		grid.x = std::min<unsigned>(grid.x, (unsigned)h->knob.test_item_grid);
 		want = 256u;
 	}
-	if (test_items && g_test_item_common > 0)	/* VDL2GPU_TEST_ITEM_COMMON: a common area of so many items -- the list overflows */
-		q.surv_common_cap = g_test_item_common;
+	if (test_items && h->knob.test_item_common > 0)
+		q.surv_common_cap = h->knob.test_item_common;
 #endif
 	q.surv_nwg = (int)grid.x;
 	q.surv_pch = (int)std::max(256u, std::min(want, item_priv / grid.x / 256u * 256u));
+	/* The grid is final.  The private areas lie in front of the list's common area: the kernels take `item_cap - surv_nwg * surv_pch`
+	 * for the common area's size, unsigned.  The clamps above guarantee it (grid.x <= item_priv / 256, so item_priv / grid.x / 256 * 256
+	 * is at least 256 and at most item_priv / grid.x), and create_impl makes the common area non-empty; said here so that a change
+	 * to either fails the push instead of wrapping in a kernel. */
+	if ((unsigned)q.surv_nwg * (unsigned)q.surv_pch > item_priv || item_priv >= k2.item_cap) {
+		h->err = "launch_scan: the scan's private areas (" + std::to_string(q.surv_nwg) + " x " + std::to_string(q.surv_pch) +
+			 " items) do not fit the item list (" + std::to_string(item_priv) + " private of " + std::to_string(k2.item_cap) + ")";
+		return VDL2GPU_EINVAL;
+	}
 	q.surv_slot = slot;
 	q.surv_mode = mode;
 	q.surv_skip = skip;
@@ -1388,13 +1430,39 @@ static ScanDrain launch_scan(int which, const K2Params &k2, dim3 grid, hipStream
 	case SCAN_REGION: hipLaunchKernelGGL(k2a_region, grid, dim3(K2A_THREADS), 0, st, q); break;
 	default: hipLaunchKernelGGL(k2a_verify, grid, dim3(K2A_THREADS), 0, st, q); break;
 	}
-	ScanDrain d;
-	d.slot = slot;
-	d.mode = mode;
-	d.skip = skip;
-	d.pch = q.surv_pch;
-	d.nwg = q.surv_nwg;
-	return d;
+	drain = ScanDrain{ slot, mode, skip, q.surv_pch, q.surv_nwg };
+	return VDL2GPU_OK;
+}
+
+/* A one-workgroup-per-channel kernel (k2r_regions, k2s_sort, k2s_merge, k2p_patch, k2c_resolve, k2f_commit) of `nt` threads on
+ * stream s, which first works off the common area of the scan in front of it, if there is one.  Nothing else writes
+ * K2Params.drain_*: a launch without a drain gets none. */
+static void launch_per_channel(const vdl2gpu_t *h, void (*kernel)(K2Params), unsigned nt, hipStream_t s, const K2Params &k2, const ScanDrain &drain = ScanDrain())
+{
+	K2Params q = k2;
+	q.drain_slot = drain.slot;
+	q.drain_mode = drain.mode;
+	q.drain_skip = drain.skip;
+	q.drain_pch = drain.pch;
+	q.drain_nwg = drain.nwg;
+	hipLaunchKernelGGL(kernel, dim3((unsigned)h->C, (unsigned)h->S), dim3(nt), 0, s, q);
+}
+
+/* the cluster kernel: a persistent grid */
+static void launch_clusters(const vdl2gpu_t *h, hipStream_t s, const K2Params &k2)
+{
+	hipLaunchKernelGGL(k2b_clusters, dim3((unsigned)(h->n_cu * 4 * K2B_GRIDW), (unsigned)((h->S * VDL2_CS + 63) / 64)), dim3(K2B_NT), 0, s, k2);
+}
+
+/* The payload kernel of the handle's flags (each optional pass is a kernel variant of its own: register pressure) on the
+ * selection `sel_mode` names (K2Params.sel_mode). */
+enum { SEL_FIRST = 0, SEL_REPAIRED = 1, SEL_FINAL = 2 };
+static void launch_payload(const vdl2gpu_t *h, hipStream_t s, const K2Params &k2, int sel_mode)
+{
+	void (*const kernel)(K2Params) = h->col_on[COL_SOFT] ? (h->col_on[COL_LEVEL] ? k2d_payload_lev_soft : k2d_payload_soft) : (h->col_on[COL_LEVEL] ? k2d_payload_lev : k2d_payload);
+	K2Params q = k2;
+	q.sel_mode = sel_mode;
+	hipLaunchKernelGGL(kernel, dim3((unsigned)h->k2d_grid, (unsigned)(VDL2_CS * h->S)), dim3(K2D_NT), 0, s, q);
 }
 
 /* tiles' worth of items a verify workgroup's private area is sized for: its share q of the pieces (k2a_verify) when a launch of
@@ -1479,9 +1547,8 @@ extern "C" int vdl2gpu_ring_init(vdl2gpu_t *h, size_t slot_samples, int nslots)
 	HOST_ALLOC(h, h->ring_host, h->ring_slot_bytes * (size_t)nslots, hipHostMallocDefault);
 	h->ring_nslots = nslots;
 	h->ring_copied.resize((size_t)nslots);
-	h->ring_inflight.assign((size_t)nslots, 0);
-	for (int i = 0; i < nslots; ++i)
-		NEW_EVENT(h, h->ring_copied[(size_t)i]);
+	for (LaterEvent &e : h->ring_copied)
+		NEW_EVENT(h, e.ev);
 	return VDL2GPU_OK;
 }
 
@@ -1493,12 +1560,12 @@ extern "C" void *vdl2gpu_ring_acquire(vdl2gpu_t *h, size_t *stream_stride_bytes)
 	if (!h->ring_host || h->ring_acquired)
 		return nullptr;
 	const size_t slot = (size_t)(h->ring_next % (unsigned long long)h->ring_nslots);
-	if (h->ring_inflight[slot]) {	/* its copy to the GPU must have left the slot */
-		if (hipSetDevice(h->cfg.device) != hipSuccess || hipEventSynchronize(h->ring_copied[slot]) != hipSuccess) {
+	if (h->ring_copied[slot].recorded) {	/* its copy to the GPU must have left the slot */
+		if (hipSetDevice(h->cfg.device) != hipSuccess || h->ring_copied[slot].sync(h)) {
 			h->err = "vdl2gpu_ring_acquire: waiting for the slot failed";
 			return nullptr;
 		}
-		h->ring_inflight[slot] = 0;
+		h->ring_copied[slot].clear();
 	}
 	if (stream_stride_bytes)
 		*stream_stride_bytes = h->ring_slot_samples * h->sample_bytes;
@@ -1521,12 +1588,13 @@ extern "C" int vdl2gpu_ring_commit(vdl2gpu_t *h, size_t nsamples)
 	const int rc = push_checked(h, (char *)h->ring_host + slot * h->ring_slot_bytes, nsamples,
 				    h->ring_slot_samples * h->sample_bytes, VDL2GPU_MEM_HOST, false);
 	if (h->in_stream) {	/* whatever was enqueued from the slot, its end is marked: acquire() waits for it */
-		if (hipEventRecord(h->ring_copied[slot], h->in_stream) == hipSuccess)
-			h->ring_inflight[slot] = 1;
-		else if (rc == VDL2GPU_OK) {
-			h->err = "hipEventRecord(ring_copied)";
-			h->failed = true;
-			return VDL2GPU_EHIP;
+		const std::string push_err = h->err;
+		if (h->ring_copied[slot].record(h, h->in_stream)) {
+			if (rc == VDL2GPU_OK) {
+				h->failed = true;
+				return VDL2GPU_EHIP;
+			}
+			h->err = push_err;	/* (the push's own error is the one to report) */
 		}
 	}
 	return rc;
@@ -1535,12 +1603,6 @@ extern "C" int vdl2gpu_ring_commit(vdl2gpu_t *h, size_t nsamples)
 
 /* The BACK stage of a push (see vdl2gpu::Back): resolver, payload decode beside the verify pass, repair rounds, commit,
  * block path, counters -- on the main stream, behind the previous push's back stage and behind this push's front. */
-/* the payload kernel of the handle's flags: each optional pass is a kernel variant of its own (register pressure) */
-static inline void (*k2d_kernel(const vdl2gpu_t *h))(K2Params)
-{
-	return h->col_on[COL_SOFT] ? (h->col_on[COL_LEVEL] ? k2d_payload_lev_soft : k2d_payload_soft) : (h->col_on[COL_LEVEL] ? k2d_payload_lev : k2d_payload);
-}
-
 static int enqueue_back(vdl2gpu_t *h)
 {
 	if (!h->back.valid)
@@ -1549,25 +1611,21 @@ static int enqueue_back(vdl2gpu_t *h)
 	const K2Params &k2 = h->back.k2;
 	const int64_t J = h->back.J;
 	const int par = h->back.par, ring = h->back.ring;
-	const bool staged = h->back.staged, serial = h->back.serial;
+	const bool serial = h->back.serial, spec = h->back.spec;
 	const unsigned tiles = h->back.tiles;
 	const int GS = h->S;
-	PushTiming &pt = h->pending[h->back.pt_index];
-	const dim3 gch((unsigned)h->C, (unsigned)GS);
+	const PushTiming &pt = h->pending[h->back.pt_index];
 	hipStream_t rs = h->stream;
 	if (h->back.two_streams)
 		HIPCHK(h, hipStreamWaitEvent(rs, h->set[par].f_done, 0));
 	/* the cluster kernel needs nothing of the previous push's result either, but it is wide, and the stages are better
 	 * balanced with it here: FRONT = channeliser + scan, BACK = clusters + resolver + verify */
-	if (staged)
-		HIPCHK(h, hipEventRecord(pt.e[2], rs));
+	TRY(mark(h, pt, E_CLUSTERS_BEGIN, rs));
 	if (!serial)
-		hipLaunchKernelGGL(k2b_clusters, dim3((unsigned)(h->n_cu * 4 * K2B_GRIDW), (unsigned)((GS * VDL2_CS + 63) / 64)), dim3(K2B_NT), 0, rs, k2);
+		launch_clusters(h, rs, k2);
 	HIPCHK(h, hipGetLastError());
-	if (staged)
-		HIPCHK(h, hipEventRecord(pt.e[3], rs));
-	if (staged)
-		HIPCHK(h, hipEventRecord(pt.e[13], rs));
+	TRY(mark(h, pt, E_CLUSTERS_END, rs));
+	TRY(mark(h, pt, E_RESOLVE_QUEUED, rs));
 	/* The verify pass's pieces (k2a_verify): a part's stretches are disjoint, so at most a piece per tile of 2 * K2A_TS samples and one
 	 * more per stretch.  The first pass's grid is ONE RESIDENT ROUND -- six workgroups a CU, shared out over the (channel, stream)
 	 * slots, about seven pieces each at 8 channels and 67 MS -- and no longer the map of the part (a workgroup per K2A_VRUN tiles: 2 800
@@ -1580,19 +1638,15 @@ static int enqueue_back(vdl2gpu_t *h)
 #endif
 	const dim3 vgrid0(vwg0, (unsigned)h->C, (unsigned)GS);
 	ScanDrain vdrain;	/* the verify pass whose common area the next one-workgroup-per-channel kernel of the tail has to drain */
-	if (h->k2f_rec)		/* the channel states the resolver starts from are committed on the previous push's tail */
-		HIPCHK(h, hipStreamWaitEvent(rs, h->k2f_done, 0));
-	if (staged && h->stage_dump)
-		HIPCHK(h, hipEventRecord(pt.e[23], rs));
-	hipLaunchKernelGGL(k2c_resolve, gch, dim3(K2_NT), 0, rs, k2);
+	TRY(h->k2f_done.wait(h, rs));	/* the channel states the resolver starts from are committed on the previous push's tail */
+	TRY(mark(h, pt, E_RESOLVE_BEGIN, rs, true));
+	launch_per_channel(h, k2c_resolve, K2_NT, rs, k2);
 	HIPCHK(h, hipGetLastError());
-	if (staged)
-		HIPCHK(h, hipEventRecord(pt.e[14], rs));
+	TRY(mark(h, pt, E_RESOLVE_END, rs));
 	/* The resolver's selection is final unless the verify pass fails -- then a repair round re-resolves the
 	 * channel, or K2f redoes it serially, and the host drops what K2d made of it (see harvest_ring; K2d decodes
 	 * a repaired selection in a second pass behind the rounds): decode the payloads beside the verify pass
-	 * instead of behind it. */
-	const bool spec = !h->full_scan && !serial && h->S * VDL2_CS <= 512;
+	 * instead of behind it (`spec`, decided in push_impl). */
 	h->ring[ring].spec = spec;
 	if (spec)
 		HIPCHK(h, hipEventRecord(h->k2c_done, rs));
@@ -1605,16 +1659,14 @@ static int enqueue_back(vdl2gpu_t *h)
 	hipStream_t ps = h->copy_stream;	/* (four hardware queues: the copy stream has one job) */
 	if (spec) {
 		HIPCHK(h, hipStreamWaitEvent(ps, h->k2c_done, 0));
-		hipLaunchKernelGGL(k2d_kernel(h), dim3((unsigned)h->k2d_grid, (unsigned)(VDL2_CS * GS)), dim3(K2D_NT), 0, ps, k2);
+		launch_payload(h, ps, k2, SEL_FIRST);
 		HIPCHK(h, hipEventRecord(h->pay_done, ps));
 	}
-	if (staged)
-		HIPCHK(h, hipEventRecord(pt.e[12], h->stream));
+	TRY(mark(h, pt, E_VERIFY_BEGIN, rs));
 	if (!serial)
-		vdrain = launch_scan(SCAN_VERIFY, k2, vgrid0, h->stream, VDL2_SURV_VERIFY, 1, 0, verify_share(vpieces, vgrid0.x));
+		TRY(launch_scan(h, SCAN_VERIFY, k2, vgrid0, rs, VDL2_SURV_VERIFY, SURV_VERIFY, 0, verify_share(vpieces, vgrid0.x), vdrain));
 	HIPCHK(h, hipGetLastError());
-	if (staged && h->stage_dump)
-		HIPCHK(h, hipEventRecord(pt.e[15], h->stream));
+	TRY(mark(h, pt, E_VERIFY_END, rs, true));
 	/* ---- the TAIL: everything behind the verify pass -- repair rounds, commit, the payloads a round re-resolved, block path,
 	 * export, counters: a chain of one-workgroup-per-channel kernels and a PCIe copy, 0.1 ms while nothing fails and 0.3 ms when
 	 * a channel is repaired (most pushes of ordinary traffic).  On the main stream it stood between this push's verify pass and
@@ -1622,16 +1674,15 @@ static int enqueue_back(vdl2gpu_t *h)
 	 * it would have had to wait for anyway), the main stream goes on with the next push, and only that push's resolver waits --
 	 * for the commit (k2f_done), which the cluster kernel in front of it covers.  k2_done, which frees the plane and table sets
 	 * and tells the host the ring is complete, is recorded at the tail's end. */
-	hipStream_t ts = (spec && h->back.two_streams && !h->knob.no_tail) ? h->pay_stream : h->stream;
-	if (ts != h->stream) {
-		HIPCHK(h, hipEventRecord(h->verify_done, h->stream));
+	hipStream_t ts = (spec && h->back.two_streams && !h->knob.no_tail) ? h->pay_stream : rs;
+	if (ts != rs) {
+		HIPCHK(h, hipEventRecord(h->verify_done, rs));
 		HIPCHK(h, hipStreamWaitEvent(ts, h->verify_done, 0));
 	}
-	if (h->tail_prev && h->tail_prev != ts && h->set[(par + VDL2_NSET - 1) % VDL2_NSET].k2_rec)	/* tails follow each other (running totals, StreamState) */
-		HIPCHK(h, hipStreamWaitEvent(ts, h->set[(par + VDL2_NSET - 1) % VDL2_NSET].k2_done, 0));
+	if (h->tail_prev && h->tail_prev != ts)	/* tails follow each other (running totals, StreamState) */
+		TRY(h->set[set_before(par)].k2_done.wait(h, ts));
 	h->tail_prev = ts;
-	if (staged && h->stage_dump)
-		HIPCHK(h, hipEventRecord(pt.e[16], ts));
+	TRY(mark(h, pt, E_TAIL_BEGIN, ts, true));
 	if (!h->full_scan && !serial) {
 		/* Repair rounds.  The verify pass has appended what it found to the failing channel's table (candidates without
 		 * clusters): a round re-sorts the table, re-resolves the channel -- the resolver replays the new candidates with the
@@ -1644,85 +1695,59 @@ static int enqueue_back(vdl2gpu_t *h)
 		 * still fail are scanned completely -- every class at every instant, like VDL2GPU_F_FULLSCAN but for them alone
 		 * (~0.1 ms for a channel of a 67 MS push) -- their tables rebuilt from nothing, which leaves nothing to verify and
 		 * nothing to cascade.  What still fails after the last round is redone serially by K2f. */
-		K2Params k2r = k2;
+		K2Params k2r = k2;	/* (what a round's launches share: round, full_round, mini_round) */
 		/* (a repair round writes its own selection, sel_list2: the payload decode of the first one goes on beside it -- unless the
 		 * last round is a complete one: that re-makes the failing channels' clusters, whose descriptors the decode may be reading) */
 		if (spec && h->repair_rounds >= 2 && ts != ps)
 			HIPCHK(h, hipStreamWaitEvent(ts, h->pay_done, 0));
-		const dim3 vgrid(vgrid0);
 		for (int rr = 1; rr <= h->repair_rounds; ++rr) {
 			k2r.round = rr;
 			k2r.full_round = (rr == h->repair_rounds && h->repair_rounds >= 2) ? 1 : 0;
 			k2r.mini_round = k2r.full_round ? 0 : 1;
 			if (k2r.full_round) {
-				scan_drain(k2r, vdrain);
-				hipLaunchKernelGGL(k2r_regions, gch, dim3(K2R_NT), 0, ts, k2r);	/* (resets the channel's tables) */
-				scan_drain(k2r, ScanDrain());
+				launch_per_channel(h, k2r_regions, K2R_NT, ts, k2r, vdrain);	/* (resets the channel's tables) */
 				const unsigned want = tiles;
 				unsigned per = (unsigned)h->n_cu;	/* few channels fail: each may use the whole GPU (the others' workgroups leave at once) */
 				per = per > want ? want : per;
-				const ScanDrain pdrain = launch_scan(SCAN_PROBE, k2r, dim3(per, (unsigned)h->C, (unsigned)GS), ts, VDL2_SURV_FULL, 0, 0, 4 * ((want + per - 1) / per));
-				scan_drain(k2r, pdrain);
-				hipLaunchKernelGGL(k2s_sort, gch, dim3(K2S_NT), 0, ts, k2r);
-				scan_drain(k2r, ScanDrain());
-				hipLaunchKernelGGL(k2b_clusters, dim3((unsigned)(h->n_cu * 4 * K2B_GRIDW), (unsigned)((GS * VDL2_CS + 63) / 64)), dim3(K2B_NT), 0, ts, k2r);
-				hipLaunchKernelGGL(k2c_resolve, gch, dim3(K2_NT), 0, ts, k2r);
+				ScanDrain pdrain;
+				TRY(launch_scan(h, SCAN_PROBE, k2r, dim3(per, (unsigned)h->C, (unsigned)GS), ts, VDL2_SURV_FULL, SURV_CANDS, 0, 4 * ((want + per - 1) / per), pdrain));
+				launch_per_channel(h, k2s_sort, K2S_NT, ts, k2r, pdrain);
+				launch_clusters(h, ts, k2r);
+				launch_per_channel(h, k2c_resolve, K2_NT, ts, k2r);
 				vdrain = ScanDrain();	/* (nothing is verified behind a complete round) */
 			} else if (rr == 1) {
 				/* the first round repairs locally: from each event the verify pass listed to where the new chain rejoins the old one
 				 * (k2p_patch: one narrow kernel, tables read where they lie), and the verify pass looks at what changed */
-				scan_drain(k2r, vdrain);
-				hipLaunchKernelGGL(k2p_patch, gch, dim3(K2P_NT), 0, ts, k2r);
-				if (staged && h->stage_dump)
-					HIPCHK(h, hipEventRecord(pt.e[18], ts));
-				scan_drain(k2r, ScanDrain());
-				{
-					/* a handful of workgroups per channel, which share the pieces of the stretches a local repair changed out among
-					 * themselves (k2a_verify: a few tiles as a rule, a piece or two each; at most the part): every workgroup of a launch
-					 * has to wait for a slot beside the other pushes' wide kernels before it can leave */
-					const unsigned nv = std::min<unsigned>(vpieces, (unsigned)h->knob.verify2_wg);
-					const dim3 vnarrow(nv, vgrid.y, vgrid.z);
-					vdrain = launch_scan(SCAN_VERIFY, k2r, vnarrow, ts, VDL2_SURV_VERIFY + rr, 1, 0, verify_share(vpieces, nv));
-				}
+				launch_per_channel(h, k2p_patch, K2P_NT, ts, k2r, vdrain);
+				TRY(mark(h, pt, E_PATCH_END, ts, true));
+				/* a handful of workgroups per channel, which share the pieces of the stretches a local repair changed out among
+				 * themselves (k2a_verify: a few tiles as a rule, a piece or two each; at most the part): every workgroup of a launch
+				 * has to wait for a slot beside the other pushes' wide kernels before it can leave */
+				const unsigned nv = std::min<unsigned>(vpieces, (unsigned)h->knob.verify2_wg);
+				TRY(launch_scan(h, SCAN_VERIFY, k2r, dim3(nv, vgrid0.y, vgrid0.z), ts, VDL2_SURV_VERIFY + rr, SURV_VERIFY, 0, verify_share(vpieces, nv), vdrain));
 			} else {
 				/* a further round resolves the channels that still fail again from their input state, with everything listed so far */
-				scan_drain(k2r, vdrain);
-				hipLaunchKernelGGL(k2s_merge, gch, dim3(K2M_NT), 0, ts, k2r);
-				scan_drain(k2r, ScanDrain());
-				hipLaunchKernelGGL(k2c_resolve, gch, dim3(K2_NT), 0, ts, k2r);
-				vdrain = launch_scan(SCAN_VERIFY, k2r, vgrid, ts, VDL2_SURV_VERIFY + rr, 1, 0, verify_share(vpieces, vgrid.x));
+				launch_per_channel(h, k2s_merge, K2M_NT, ts, k2r, vdrain);
+				launch_per_channel(h, k2c_resolve, K2_NT, ts, k2r);
+				TRY(launch_scan(h, SCAN_VERIFY, k2r, vgrid0, ts, VDL2_SURV_VERIFY + rr, SURV_VERIFY, 0, verify_share(vpieces, vgrid0.x), vdrain));
 			}
 		}
 		HIPCHK(h, hipGetLastError());
 	}
-	if (staged)
-		HIPCHK(h, hipEventRecord(pt.e[5], ts));
-	{
-		K2Params k2f = k2;
-		scan_drain(k2f, vdrain);
-		hipLaunchKernelGGL(k2f_commit, gch, dim3(K2_NT), 0, ts, k2f);
-	}
+	TRY(mark(h, pt, E_ROUNDS_END, ts));
+	launch_per_channel(h, k2f_commit, K2_NT, ts, k2, vdrain);
 
-	HIPCHK(h, hipEventRecord(h->k2f_done, ts));
-	h->k2f_rec = true;
-	if (staged && h->stage_dump)
-		HIPCHK(h, hipEventRecord(pt.e[20], ts));
-	if (h->ring[ring].spec) {
+	TRY(h->k2f_done.record(h, ts));
+	TRY(mark(h, pt, E_COMMIT_END, ts, true));
+	if (spec) {
 		if (ts != ps)
 			HIPCHK(h, hipStreamWaitEvent(ts, h->pay_done, 0));	/* the export needs the first pass's records, K3 publishes the record count */
-		if (!h->full_scan && !serial) {
-			K2Params k2p = k2;	/* what the repair rounds (or K2f's serial redo) made void of the first selection is tagged now, what they selected is decoded */
-			k2p.sel_mode = 1;
-			hipLaunchKernelGGL(k2d_kernel(h), dim3((unsigned)h->k2d_grid, (unsigned)(VDL2_CS * GS)), dim3(K2D_NT), 0, ts, k2p);
-		}
-	} else {
-		K2Params k2p = k2;	/* one pass behind the commit: the repaired selection where there is one */
-		k2p.sel_mode = 2;
-		hipLaunchKernelGGL(k2d_kernel(h), dim3((unsigned)h->k2d_grid, (unsigned)(VDL2_CS * GS)), dim3(K2D_NT), 0, ts, k2p);
-	}
+		if (!h->full_scan && !serial)	/* what the repair rounds (or K2f's serial redo) made void of the first selection is tagged now, what they selected is decoded */
+			launch_payload(h, ts, k2, SEL_REPAIRED);
+	} else
+		launch_payload(h, ts, k2, SEL_FINAL);	/* one pass behind the commit: the repaired selection where there is one */
 	HIPCHK(h, hipGetLastError());
-	if (staged && h->stage_dump)
-		HIPCHK(h, hipEventRecord(pt.e[21], ts));
+	TRY(mark(h, pt, E_PAYLOAD2_END, ts, true));
 	if (h->frames_on) {
 		/* block path on the records where they lie (vdlm2.c:84-161).  In the chain, not beside it:
 		 * a latency-bound kernel like this one and the next push's scan slow each other down by
@@ -1736,15 +1761,27 @@ static int enqueue_back(vdl2gpu_t *h)
 		k4.frame_cap = h->frame_cap;
 		k4.compact = 1;
 		k4.tabs = h->d_k4tab;
-		k4.fmask = h->ring[ring].spec ? h->set[par].k2.fmask : nullptr;
+		k4.fmask = spec ? h->set[par].k2.fmask : nullptr;
 		k4.dbg = h->knob.debug_counters ? h->d_dbg : nullptr;
 		k4.soft = h->ring[ring].soft();	/* (nullptr without VDL2GPU_F_SOFT_RS: the reference's block path) */
 		hipLaunchKernelGGL(k4_frames, dim3((unsigned)h->n_cu * 16), dim3(K4_NT), 0, ts, k4);
 		HIPCHK(h, hipGetLastError());
 	}
-	if (staged)
-		HIPCHK(h, hipEventRecord(pt.e[6], ts));
+	TRY(mark(h, pt, E_BLOCKS_END, ts));
 	{
+		/* the push's records go to the host by the GPU's own hand: page-locked memory, coalesced 8-byte stores */
+		KExportParams ke{};
+		ke.recs = h->ring[ring].d_recs;
+		ke.count = h->d_outc + 2 * ring;
+		ke.dst = h->slab[h->back.slab].d_recs;
+		ke.cap = std::min(h->slab_cap, h->rec_cap);
+		ke.lev = h->ring[ring].levels();	/* (nullptr without VDL2GPU_F_LEVELS) */
+		ke.ldst = h->slab[h->back.slab].d_levels();
+		ke.soft = h->ring[ring].soft();	/* (nullptr without VDL2GPU_F_SOFT_RS) */
+		ke.sdst = h->slab[h->back.slab].d_soft();
+		hipLaunchKernelGGL(k_export_records, dim3((unsigned)h->n_cu), dim3(256), 0, ts, ke);
+		HIPCHK(h, hipGetLastError());
+		TRY(mark(h, pt, E_EXPORT_END, ts, true));
 		K3Params k3{};
 		k3.src = nullptr;	/* (the counters kernel copies nothing) */
 		k3.dst = nullptr;
@@ -1760,29 +1797,11 @@ static int enqueue_back(vdl2gpu_t *h)
 		k3.ring = ring;
 		k3.ctl = h->set[par].k2.ctl;
 		k3.nstreams = h->S;
-		{
-			/* the push's records go to the host by the GPU's own hand: page-locked memory, coalesced 8-byte stores */
-			KExportParams ke{};
-			ke.recs = h->ring[ring].d_recs;
-			ke.count = h->d_outc + 2 * ring;
-			ke.dst = h->slab[h->back.slab].d_recs;
-			ke.cap = std::min(h->slab_cap, h->rec_cap);
-			ke.lev = h->ring[ring].levels();	/* (nullptr without VDL2GPU_F_LEVELS) */
-			ke.ldst = h->slab[h->back.slab].d_levels();
-			ke.soft = h->ring[ring].soft();	/* (nullptr without VDL2GPU_F_SOFT_RS) */
-			ke.sdst = h->slab[h->back.slab].d_soft();
-			hipLaunchKernelGGL(k_export_records, dim3((unsigned)h->n_cu), dim3(256), 0, ts, ke);
-			HIPCHK(h, hipGetLastError());
-			if (staged && h->stage_dump)
-				HIPCHK(h, hipEventRecord(pt.e[22], ts));
-		}
 		hipLaunchKernelGGL(k3_rebase, dim3((unsigned)GS), dim3(64), 0, ts, k3);
 		HIPCHK(h, hipGetLastError());
 	}
-	if (staged)
-		HIPCHK(h, hipEventRecord(pt.e[7], ts));
-	HIPCHK(h, hipEventRecord(h->set[par].k2_done, ts));
-	h->set[par].k2_rec = true;
+	TRY(mark(h, pt, E_TAIL_END, ts));
+	TRY(h->set[par].k2_done.record(h, ts));
 	h->ring[ring].ev ^= 1;
 	HIPCHK(h, hipEventRecord(h->ring[ring].done(), ts));
 	return VDL2GPU_OK;
@@ -1823,9 +1842,7 @@ static int stage_input(vdl2gpu_t *h, const void *iq, size_t nsamples, size_t str
 		DEV_ALLOC(h, h->d_raw[stg], need);
 		h->raw_bytes[stg] = need;
 	}
-	/* the channeliser of the push before last has read this buffer */
-	if (h->k1_rec[stg])
-		HIPCHK(h, hipStreamWaitEvent(h->in_stream, h->k1_done[stg], 0));
+	TRY(h->k1_done[stg].wait(h, h->in_stream));	/* the channeliser of the push before last has read this buffer */
 	for (int s = 0; s < h->S; ++s)
 		HIPCHK(h, hipMemcpyAsync((char *)h->d_raw[stg] + (size_t)s * per,
 					 (const char *)iq + (size_t)s * stream_stride_bytes, per,
@@ -1904,13 +1921,144 @@ static K1Choice choose_k1(const vdl2gpu_t *h, int c0, int64_t J, size_t nsamples
 	return c;
 }
 
-/* The channeliser of a push on stream `ks`: k1 comes with the push's place in the schedule (vdl2gpu_plan); what choose_k1 decided
- * is launched, the general kernel around it where the other one does not take the whole push. */
-static int enqueue_k1(vdl2gpu_t *h, K1Params &k1, const Input &in, size_t nsamples, int par, hipStream_t ks, PushTiming &pt)
+/* The general channeliser for outputs jbeg..jend of the push. */
+static void launch_k1_general(vdl2gpu_t *h, const K1Params &k1, hipStream_t ks, long long jbeg, long long jend)
+{
+	if (jend < jbeg)
+		return;
+	const long long per_block = K1_OPB * K1_PASSES;
+	/* <= VDL2_K1_LDS_MAX either way (vdl2gpu_create) */
+	const size_t smem = h->k1_glo ? k1_glo_smem_bytes((uint64_t)h->maxwin) : k1_smem_bytes((uint64_t)h->L, (uint64_t)h->maxwin);
+	K1Params q = k1;
+	q.jbeg = jbeg;
+	q.jend = jend;
+	const unsigned gx = (unsigned)((jend - jbeg + 1 + per_block - 1) / per_block);
+	const dim3 grid(gx, (unsigned)h->S);
+	++h->k1_launches[h->k1_glo ? 1 : 0];
+	if (h->rot && h->k1_glo)
+		with_fmt(h->cfg.fmt, [&](auto F) { hipLaunchKernelGGL((k1_channelise<decltype(F)::value, true, true>), grid, dim3(K1_THREADS), smem, ks, q, h->k1rot); });
+	else if (h->rot)
+		with_fmt(h->cfg.fmt, [&](auto F) { hipLaunchKernelGGL((k1_channelise<decltype(F)::value, false, true>), grid, dim3(K1_THREADS), smem, ks, q, h->k1rot); });
+	else if (h->k1_glo)
+		with_fmt(h->cfg.fmt, [&](auto F) { hipLaunchKernelGGL((k1_channelise<decltype(F)::value, true>), grid, dim3(K1_THREADS), smem, ks, q); });
+	else
+		with_fmt(h->cfg.fmt, [&](auto F) { hipLaunchKernelGGL(k1_channelise<decltype(F)::value>, grid, dim3(K1_THREADS), smem, ks, q); });
+}
+
+/* k1_fast on the push's whole superperiods (all of them, or all but the first and the last: `whole`). */
+static void launch_k1_fast(vdl2gpu_t *h, K1Params &k1, bool whole, hipStream_t ks)
 {
 	const int GS = h->S;
-	const int64_t J = k1.J;
-	const bool staged = pt.staged;
+	const long long nsp = k1.J / K1F_PER_OUT;
+	k1.per_lo = whole ? 0 : 1;
+	k1.per_n = whole ? nsp : nsp - 2;
+	k1.edge_state = whole ? 1 : 0;
+	k1.lo_ext = h->d_lo_ext;
+	k1.lo_stride = h->L + 48;
+	/* The grid is resident as a whole: n_cu * 2 * K1F_WAVES_OF(fmt) workgroups of two wavefronts fit.  Per stream
+	 * 21 roles x 8 XCDs families of `nfam` workgroups each, which take the family's tickets in turn (see k1_fast);
+	 * a family needs no more workgroups than it has tickets.  With several streams the families are many and
+	 * small: rather two workgroups each and a twentieth of them waiting for a slot than one each and half the
+	 * SIMDs' wavefront slots empty. */
+	long long ngrp;
+	{
+		const long long slots = (long long)h->n_cu * 2 * (h->rot ? K1F_ROT_WAVES : K1F_WAVES_OF(h->cfg.fmt));
+		const long long per_fam = (long long)K1F_ROLES * 8 * GS;
+		long long nfam = slots / per_fam;
+		if (nfam < 4 && (nfam + 1) * per_fam * 100 <= slots * 108)
+			++nfam;
+		if (h->knob.k1f_nfam > 0)
+			nfam = h->knob.k1f_nfam;
+		const long long tickets = ((k1.per_n + 7) / 8 + K1F_CHUNK - 1) / K1F_CHUNK;	/* of the family with the most */
+		nfam = std::max<long long>(1, std::min(nfam, tickets));
+		ngrp = nfam * 8;
+	}
+	/* the counters are never reset: a launch makes exactly one request per ticket of a family (k1_fast), so the
+	 * host knows where each one stands */
+	k1.tickets = h->d_k1_tickets;
+	for (int x = 0; x < 8; ++x) {
+		k1.tbase[x] = h->k1_tbase[x];	/* (every stream stands where the first does: all have seen the same pushes) */
+		const long long n_x = (k1.per_n - x + 7) >> 3;
+		if (n_x > 0)
+			for (int sg = 0; sg < GS; ++sg)
+				h->k1_tbase[(size_t)sg * 8 + x] += (unsigned)((n_x + K1F_CHUNK - 1) / K1F_CHUNK);
+	}
+	const dim3 grid((unsigned)ngrp * K1F_ROLES, (unsigned)GS);
+	++h->k1_launches[3];
+	if (h->rot)
+		with_fmt(h->cfg.fmt, [&](auto F) { hipLaunchKernelGGL((k1_fast<decltype(F)::value, true>), grid, dim3(K1F_THREADS), 0, ks, k1, h->k1rot); });
+	else
+		with_fmt(h->cfg.fmt, [&](auto F) { hipLaunchKernelGGL(k1_fast<decltype(F)::value>, grid, dim3(K1F_THREADS), 0, ks, k1); });
+}
+
+/* k1_pp on the push's whole periods (all of them, or all but the first and the last: ch.whole). */
+static void launch_k1_pp(vdl2gpu_t *h, const K1Params &k1, const K1Choice &ch, hipStream_t ks)
+{
+	const int GS = h->S;
+	const long long periods = k1.J / K1P_PER_OUT;
+	K1PParams kp{};
+	kp.per_lo = ch.per_lo;
+	kp.sbase0 = ch.sbase0;
+	kp.d = ch.d;
+	kp.edge_state = ch.whole ? 1 : 0;
+	kp.parity = k1.parity;
+	kp.J = k1.J;
+	kp.raw = k1.raw;
+	kp.stream_stride = k1.stream_stride;
+	kp.nbch = h->C;
+	kp.per_in = 4 * h->sdrclk;
+	kp.L = h->L;
+	kp.ph0 = (int)(((long long)k1.no0 + kp.sbase0) % h->L);
+	kp.per_n = (int)(ch.whole ? periods : periods - 2);
+	kp.lo_ext = h->d_lo_ext;
+	kp.lo_stride = h->L + 48;
+	kp.dec = k1.dec;
+	kp.cap = h->cap;
+	kp.ss = h->d_ss;
+	int nfmin = 1 << 30, nfmax = 0;
+	for (int k = 0; k < K1P_PER_OUT; ++k) {
+		kp.wend[k] = (int)(wend_abs(K1P_PER_OUT * kp.per_lo + k, h->sdrclk, k1.c0) - kp.sbase0);
+		const int nf = kp.wend[k] - (k ? kp.wend[k - 1] : -1);
+		nfmin = std::min(nfmin, nf);
+		nfmax = std::max(nfmax, nf);
+	}
+	auto proven = [](int nf) { return nf == 23 || nf == 24 || nf == 59 || nf == 60 || nf == 71 || nf == 72 || nf == 119 || nf == 120; };
+	kp.fast_div = proven(nfmin) && proven(nfmax) && nfmax - nfmin <= 1;
+	kp.nf_lo = nfmin;
+	kp.dbg = h->knob.k1_dbg;
+	kp.rcp_lo = 1.0f / (float)nfmin;
+	kp.rcp_hi = 1.0f / (float)(nfmin + 1);
+	/* tasks = (blocks of 64 periods) x (runs of wpt windows): enough of them that the last round of
+	 * workgroups is a small share of the launch, as long as possible otherwise */
+	const long long blocks = (kp.per_n + 63) / 64;
+	const int divs[] = {1, 2, 3, 4, 6, 7, 12, 14, 21, 28};
+	const long long resident = (long long)h->n_cu * 3;
+	int best = 1;
+	double best_eff = -1;
+	for (int nsub : divs) {
+		const long long tasks = blocks * nsub * GS;
+		const long long rounds = (tasks + resident - 1) / resident;
+		const double eff = (double)tasks / (double)(rounds * resident) - 0.004 * nsub;	/* shorter tasks pay their start-up more often */
+		if (eff > best_eff) {
+			best_eff = eff;
+			best = nsub;
+		}
+	}
+	if (h->knob.k1_nsub > 0)
+		best = h->knob.k1_nsub;
+	kp.nsub = best;
+	kp.wpt = K1P_PER_OUT / best;
+	const dim3 grid((unsigned)(blocks * kp.nsub), (unsigned)GS);
+	++h->k1_launches[2];
+	if (h->rot)
+		with_fmt(h->cfg.fmt, [&](auto F) { hipLaunchKernelGGL((k1_pp<decltype(F)::value, true>), grid, dim3(K1P_THREADS), 0, ks, kp, h->k1rot); });
+	else
+		with_fmt(h->cfg.fmt, [&](auto F) { hipLaunchKernelGGL(k1_pp<decltype(F)::value>, grid, dim3(K1P_THREADS), 0, ks, kp); });
+}
+
+/* what every channeliser kernel is told of the handle and the push, beside the push's place in the schedule (vdl2gpu_plan) */
+static void fill_k1(const vdl2gpu_t *h, K1Params &k1, const Input &in, size_t nsamples, int par)
+{
 	k1.raw = in.src;
 	k1.stream_stride = in.stride;
 	k1.fmt = h->cfg.fmt;
@@ -1925,157 +2073,34 @@ static int enqueue_k1(vdl2gpu_t *h, K1Params &k1, const Input &in, size_t nsampl
 	k1.dec = h->d_dec[par];
 	k1.cap = h->cap;
 	k1.ss = h->d_ss;
-	const long long per_block = K1_OPB * K1_PASSES;
-	/* <= VDL2_K1_LDS_MAX either way (vdl2gpu_create) */
-	const size_t smem = h->k1_glo ? k1_glo_smem_bytes((uint64_t)h->maxwin) : k1_smem_bytes((uint64_t)h->L, (uint64_t)h->maxwin);
-	auto generic = [&](long long jbeg, long long jend) {
-		if (jend < jbeg)
-			return;
-		K1Params q = k1;
-		q.jbeg = jbeg;
-		q.jend = jend;
-		const unsigned gx = (unsigned)((jend - jbeg + 1 + per_block - 1) / per_block);
-		const dim3 grid(gx, (unsigned)GS);
-		++h->k1_launches[h->k1_glo ? 1 : 0];
-		if (h->rot && h->k1_glo)
-			with_fmt(h->cfg.fmt, [&](auto F) { hipLaunchKernelGGL((k1_channelise<decltype(F)::value, true, true>), grid, dim3(K1_THREADS), smem, ks, q, h->k1rot); });
-		else if (h->rot)
-			with_fmt(h->cfg.fmt, [&](auto F) { hipLaunchKernelGGL((k1_channelise<decltype(F)::value, false, true>), grid, dim3(K1_THREADS), smem, ks, q, h->k1rot); });
-		else if (h->k1_glo)
-			with_fmt(h->cfg.fmt, [&](auto F) { hipLaunchKernelGGL((k1_channelise<decltype(F)::value, true>), grid, dim3(K1_THREADS), smem, ks, q); });
-		else
-			with_fmt(h->cfg.fmt, [&](auto F) { hipLaunchKernelGGL(k1_channelise<decltype(F)::value>, grid, dim3(K1_THREADS), smem, ks, q); });
-	};
-	const K1Choice ch = choose_k1(h, k1.c0, J, nsamples, in.src, in.stride);
-	const bool whole = ch.whole;
-	const long long periods = J / K1P_PER_OUT;
-	const long long nsp = periods / 4;
-	if (ch.kind == K1_FAST) {
-		if (!whole)
-			generic(0, K1F_PER_OUT - 1);
-		if (staged)
-			(void)hipEventRecord(pt.e[11], ks);	/* the wait for the resolver that follows is not channeliser time */
+}
+
+/* The channeliser of a push on stream `ks`: k1 comes with the push's place in the schedule; what choose_k1 decided is launched, the
+ * general kernel around it where the other one does not take the whole push. */
+static int enqueue_k1(vdl2gpu_t *h, K1Params &k1, const Input &in, size_t nsamples, int par, hipStream_t ks, PushTiming &pt)
+{
+	fill_k1(h, k1, in, nsamples, par);
+	const K1Choice ch = choose_k1(h, k1.c0, k1.J, nsamples, in.src, in.stride);
+	if (ch.kind == K1_GENERAL)
+		launch_k1_general(h, k1, ks, 0, k1.J);
+	else {
+		/* the kernel takes whole (super)periods of `unit` outputs; unless it takes the whole push, the general kernel takes the
+		 * first one (the carried partial window) and everything from the last one on */
+		const long long unit = ch.kind == K1_FAST ? K1F_PER_OUT : K1P_PER_OUT;
+		if (!ch.whole)
+			launch_k1_general(h, k1, ks, 0, unit - 1);
+		TRY(mark(h, pt, E_K1_HEAD_END, ks));	/* the wait for the resolver that follows is not channeliser time */
 		pt.fast = true;
-		k1.per_lo = whole ? 0 : 1;
-		k1.per_n = whole ? nsp : nsp - 2;
-		k1.edge_state = whole ? 1 : 0;
-		k1.lo_ext = h->d_lo_ext;
-		k1.lo_stride = h->L + 48;
-		if (staged)
-			(void)hipEventRecord(pt.e[8], ks);
-		/* The grid is resident as a whole: n_cu * 2 * K1F_WAVES_OF(fmt) workgroups of two wavefronts fit.  Per stream
-		 * 21 roles x 8 XCDs families of `nfam` workgroups each, which take the family's tickets in turn (see k1_fast);
-		 * a family needs no more workgroups than it has tickets.  With several streams the families are many and
-		 * small: rather two workgroups each and a twentieth of them waiting for a slot than one each and half the
-		 * SIMDs' wavefront slots empty. */
-		long long ngrp;
-		{
-			const long long slots = (long long)h->n_cu * 2 * (h->rot ? K1F_ROT_WAVES : K1F_WAVES_OF(h->cfg.fmt));
-			const long long per_fam = (long long)K1F_ROLES * 8 * GS;
-			long long nfam = slots / per_fam;
-			if (nfam < 4 && (nfam + 1) * per_fam * 100 <= slots * 108)
-				++nfam;
-			if (h->knob.k1f_nfam > 0)
-				nfam = h->knob.k1f_nfam;
-			const long long tickets = ((k1.per_n + 7) / 8 + K1F_CHUNK - 1) / K1F_CHUNK;	/* of the family with the most */
-			nfam = std::max<long long>(1, std::min(nfam, tickets));
-			ngrp = nfam * 8;
-		}
-		/* the counters are never reset: a launch makes exactly one request per ticket of a family (k1_fast), so the
-		 * host knows where each one stands */
-		k1.tickets = h->d_k1_tickets;
-		for (int x = 0; x < 8; ++x) {
-			k1.tbase[x] = h->k1_tbase[x];	/* (every stream stands where the first does: all have seen the same pushes) */
-			const long long n_x = (k1.per_n - x + 7) >> 3;
-			if (n_x > 0)
-				for (int sg = 0; sg < GS; ++sg)
-					h->k1_tbase[(size_t)sg * 8 + x] += (unsigned)((n_x + K1F_CHUNK - 1) / K1F_CHUNK);
-		}
-		const dim3 grid((unsigned)ngrp * K1F_ROLES, (unsigned)GS);
-		++h->k1_launches[3];
-		if (h->rot)
-			with_fmt(h->cfg.fmt, [&](auto F) { hipLaunchKernelGGL((k1_fast<decltype(F)::value, true>), grid, dim3(K1F_THREADS), 0, ks, k1, h->k1rot); });
+		TRY(mark(h, pt, E_K1_KERNEL_BEGIN, ks));
+		if (ch.kind == K1_FAST)
+			launch_k1_fast(h, k1, ch.whole, ks);
 		else
-			with_fmt(h->cfg.fmt, [&](auto F) { hipLaunchKernelGGL(k1_fast<decltype(F)::value>, grid, dim3(K1F_THREADS), 0, ks, k1); });
-		if (staged)
-			(void)hipEventRecord(pt.e[9], ks);
+			launch_k1_pp(h, k1, ch, ks);
+		TRY(mark(h, pt, E_K1_KERNEL_END, ks));
 		pt.fast_parts = 1;
-		if (!whole)
-			generic((nsp - 1) * K1F_PER_OUT, J);
-	} else if (ch.kind == K1_PP) {
-		K1PParams kp{};
-		kp.per_lo = ch.per_lo;
-		kp.sbase0 = ch.sbase0;
-		kp.d = ch.d;
-		const int per_in = 4 * h->sdrclk;
-		if (!whole)
-			generic(0, K1P_PER_OUT - 1);
-		if (staged)
-			(void)hipEventRecord(pt.e[11], ks);
-		pt.fast = true;
-		kp.edge_state = whole ? 1 : 0;
-		kp.parity = k1.parity;
-		kp.J = J;
-		kp.raw = in.src;
-		kp.stream_stride = in.stride;
-		kp.nbch = h->C;
-		kp.per_in = per_in;
-		kp.L = h->L;
-		kp.ph0 = (int)(((long long)k1.no0 + kp.sbase0) % h->L);
-		kp.per_n = (int)(whole ? periods : periods - 2);
-		kp.lo_ext = h->d_lo_ext;
-		kp.lo_stride = h->L + 48;
-		kp.dec = k1.dec;
-		kp.cap = h->cap;
-		kp.ss = h->d_ss;
-		int nfmin = 1 << 30, nfmax = 0;
-		for (int k = 0; k < K1P_PER_OUT; ++k) {
-			kp.wend[k] = (int)(wend_abs(K1P_PER_OUT * kp.per_lo + k, h->sdrclk, k1.c0) - kp.sbase0);
-			const int nf = kp.wend[k] - (k ? kp.wend[k - 1] : -1);
-			nfmin = std::min(nfmin, nf);
-			nfmax = std::max(nfmax, nf);
-		}
-		auto proven = [](int nf) { return nf == 23 || nf == 24 || nf == 59 || nf == 60 || nf == 71 || nf == 72 || nf == 119 || nf == 120; };
-		kp.fast_div = proven(nfmin) && proven(nfmax) && nfmax - nfmin <= 1;
-		kp.nf_lo = nfmin;
-		kp.dbg = h->knob.k1_dbg;
-		kp.rcp_lo = 1.0f / (float)nfmin;
-		kp.rcp_hi = 1.0f / (float)(nfmin + 1);
-		/* tasks = (blocks of 64 periods) x (runs of wpt windows): enough of them that the last round of
-		 * workgroups is a small share of the launch, as long as possible otherwise */
-		const long long blocks = (kp.per_n + 63) / 64;
-		const int divs[] = {1, 2, 3, 4, 6, 7, 12, 14, 21, 28};
-		const long long resident = (long long)h->n_cu * 3;
-		int best = 1;
-		double best_eff = -1;
-		for (int nsub : divs) {
-			const long long tasks = blocks * nsub * GS;
-			const long long rounds = (tasks + resident - 1) / resident;
-			const double eff = (double)tasks / (double)(rounds * resident) - 0.004 * nsub;	/* shorter tasks pay their start-up more often */
-			if (eff > best_eff) {
-				best_eff = eff;
-				best = nsub;
-			}
-		}
-		if (h->knob.k1_nsub > 0)
-			best = h->knob.k1_nsub;
-		kp.nsub = best;
-		kp.wpt = K1P_PER_OUT / best;
-		if (staged)
-			(void)hipEventRecord(pt.e[8], ks);
-		const dim3 grid((unsigned)(blocks * kp.nsub), (unsigned)GS);
-		++h->k1_launches[2];
-		if (h->rot)
-			with_fmt(h->cfg.fmt, [&](auto F) { hipLaunchKernelGGL((k1_pp<decltype(F)::value, true>), grid, dim3(K1P_THREADS), 0, ks, kp, h->k1rot); });
-		else
-			with_fmt(h->cfg.fmt, [&](auto F) { hipLaunchKernelGGL(k1_pp<decltype(F)::value>, grid, dim3(K1P_THREADS), 0, ks, kp); });
-		if (staged)
-			(void)hipEventRecord(pt.e[9], ks);
-		pt.fast_parts = 1;
-		if (!whole)
-			generic((periods - 1) * K1P_PER_OUT, J);
-	} else
-		generic(0, J);
+		if (!ch.whole)
+			launch_k1_general(h, k1, ks, (k1.J / unit - 1) * unit, k1.J);
+	}
 	HIPCHK(h, hipGetLastError());
 	return VDL2GPU_OK;
 }
@@ -2087,7 +2112,7 @@ static int enqueue_front(vdl2gpu_t *h, hipStream_t fs, long long dec_base, PushT
 	vdl2gpu::Back &p = h->back;	/* (push_impl has put the push's J, sets and path there) */
 	const int GS = h->S, par = p.par, ring = p.ring;
 	const int64_t J = p.J;
-	const bool staged = pt.staged, serial = p.serial, two_streams = p.two_streams;
+	const bool serial = p.serial, two_streams = p.two_streams;
 	TableSet &set = h->set[par];
 	{
 		KInitParams ki{};
@@ -2101,8 +2126,7 @@ static int enqueue_front(vdl2gpu_t *h, hipStream_t fs, long long dec_base, PushT
 		ki.fcnt = h->frames_on ? h->d_fcnt + 4 * ring : nullptr;
 		hipLaunchKernelGGL(k_push_init, dim3(1), dim3(1024), 0, fs, ki);
 	}
-	if (staged)
-		HIPCHK(h, hipEventRecord(pt.e[10], fs));
+	TRY(mark(h, pt, E_SCAN_BEGIN, fs));
 	K2Params k2 = set.k2;	/* the set's tables and everything that never changes (fill_set_params); what follows is this push's */
 	k2.J = J;
 	k2.recs = h->ring[ring].d_recs;
@@ -2113,7 +2137,7 @@ static int enqueue_front(vdl2gpu_t *h, hipStream_t fs, long long dec_base, PushT
 	k2.scan_lo = dec_base + VDL2_HIST;	/* the scan starts at the first carried frame that has its history */
 	k2.probe_par = (int)((dec_base + VDL2_HIST) & 1);
 	k2.force_serial = serial ? 1 : 0;
-	k2.sel_reserved = (!h->full_scan && !serial && h->S * VDL2_CS <= 512) ? 1 : 0;	/* (enqueue_back's `spec`) */
+	k2.sel_reserved = p.spec ? 1 : 0;
 	if (h->d_headtap) {
 		/* VDL2GPU_F_DEBUG_HEADS: one tap buffer for the handle, so the pipeline is drained first -- the back stage and the
 		 * tail of the two pushes before would otherwise still be appending to it ("every trigger of the LAST push") */
@@ -2123,9 +2147,8 @@ static int enqueue_front(vdl2gpu_t *h, hipStream_t fs, long long dec_base, PushT
 		HIPCHK(h, hipMemsetAsync(h->d_headtap_n, 0, sizeof(unsigned), fs));
 	}
 	const unsigned tiles = (unsigned)((VDL2_CARRY_FRAMES + J) / K2A_TS + 2);
-	const dim3 gch((unsigned)h->C, (unsigned)GS);
-	ScanDrain pdrain, rdrain;
 	if (!serial) {
+		ScanDrain pdrain, rdrain;
 		{
 			/* as many workgroups as are resident at once, each walking its share of the channel's tiles */
 			const unsigned want = h->full_scan ? tiles : tiles / 2 + 1;
@@ -2134,23 +2157,16 @@ static int enqueue_front(vdl2gpu_t *h, hipStream_t fs, long long dec_base, PushT
 			per = std::min<unsigned>(per, VDL2_MAXWG);
 			/* the probe needs the carry the push before made (the first 49152 frames of this plane set); with the front
 			 * stage on two streams (below) that copy is not on this stream */
-			pdrain = launch_scan(SCAN_PROBE, k2, dim3(per, (unsigned)h->C, (unsigned)GS), fs, VDL2_SURV_PROBE, h->full_scan ? 0 : (VDL2_PROBE_STRIDE == 2 ? 2 : 3), 0, (h->full_scan ? 4 : 1) * ((want + per - 1) / per));
+			TRY(launch_scan(h, SCAN_PROBE, k2, dim3(per, (unsigned)h->C, (unsigned)GS), fs, VDL2_SURV_PROBE,
+					h->full_scan ? SURV_CANDS : (VDL2_PROBE_STRIDE == 2 ? SURV_PROBE : SURV_SEEDS), 0, (h->full_scan ? 4 : 1) * ((want + per - 1) / per), pdrain));
 		}
-		{
-			K2Params k2d = k2;	/* (k2r_regions works the probe's common area off first, k2s_sort the region scan's) */
-			scan_drain(k2d, pdrain);
-			hipLaunchKernelGGL(k2r_regions, gch, dim3(K2R_NT), 0, fs, k2d);
-		}
-		rdrain = launch_scan(SCAN_REGION, k2, dim3(128, (unsigned)h->C, (unsigned)GS), fs, VDL2_SURV_REGION, 0, 1, 2);
+		/* (k2r_regions works the probe's common area off first, k2s_sort the region scan's) */
+		launch_per_channel(h, k2r_regions, K2R_NT, fs, k2, pdrain);
+		TRY(launch_scan(h, SCAN_REGION, k2, dim3(128, (unsigned)h->C, (unsigned)GS), fs, VDL2_SURV_REGION, SURV_CANDS, 1, 2, rdrain));
 		HIPCHK(h, hipGetLastError());
+		launch_per_channel(h, k2s_sort, K2S_NT, fs, k2, rdrain);
 	}
-	if (!serial) {
-		K2Params k2d = k2;
-		scan_drain(k2d, rdrain);
-		hipLaunchKernelGGL(k2s_sort, gch, dim3(K2S_NT), 0, fs, k2d);
-	}
-	if (staged)
-		HIPCHK(h, hipEventRecord(pt.e[4], fs));	/* end of the front stage's scan + sort (e[4] is free: the verify pass is timed from e[12]) */
+	TRY(mark(h, pt, E_FRONT_END, fs));	/* end of the front stage's scan + sort */
 	HIPCHK(h, hipGetLastError());
 	/* ---- end of the FRONT stage */
 	if (two_streams)
@@ -2164,11 +2180,11 @@ static int enqueue_front(vdl2gpu_t *h, hipStream_t fs, long long dec_base, PushT
 		/* the next plane set's head was last read by the tail of the push two back (a repaired channel's payloads are
 		 * decoded late: a burst at the very start of that push lies in its head); the next push's channeliser, right
 		 * behind this copy, waits for that same tail anyway */
-		if (two_streams && h->set[(par + 1) % VDL2_NSET].k2_rec)
-			HIPCHK(h, hipStreamWaitEvent(fs, h->set[(par + 1) % VDL2_NSET].k2_done, 0));
+		if (two_streams)
+			TRY(h->set[set_after(par)].k2_done.wait(h, fs));
 		K3Params k3{};
 		k3.src = h->d_dec[par];
-		k3.dst = h->d_dec[(par + 1) % VDL2_NSET];
+		k3.dst = h->d_dec[set_after(par)];
 		k3.cap = h->cap;
 		k3.nbch = h->C;
 		k3.J = J;
@@ -2176,14 +2192,11 @@ static int enqueue_front(vdl2gpu_t *h, hipStream_t fs, long long dec_base, PushT
 		HIPCHK(h, hipGetLastError());
 		if (two_streams)	/* a following push that keeps to the main stream must see the carry (and with two front streams: the next probe) */
 			HIPCHK(h, hipEventRecord(h->f_tail, fs));
-		else {	/* ... and a following push's front stage this push's channeliser state and carry, made on the main stream */
-			HIPCHK(h, hipEventRecord(h->k1_ev, fs));
-			h->k1_ev_rec = true;
-		}
+		else	/* ... and a following push's front stage this push's channeliser state and carry, made on the main stream */
+			TRY(h->k1_ev.record(h, fs));
 	}
 	p.valid = true;
 	p.k2 = k2;
-	p.staged = staged;
 	p.tiles = tiles;
 	p.pt_index = h->pending.size();
 	return VDL2GPU_OK;
@@ -2220,8 +2233,7 @@ static int push_impl(vdl2gpu_t *h, const void *iq, size_t nsamples, size_t strea
 	auto hnow = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
 	double hp_t = hnow();	/* (always on: six clock reads a push; vdl2gpu_get_host_profile() hands the sums out, VDL2GPU_HOST_PROF prints them at destroy) */
 	auto hp = [&](int k) { const double t = hnow(); h->hprof[k] += t - hp_t; hp_t = t; };
-	if (h->ring[(h->pushes + 1) % VDL2_NRING].in_rec)
-		HIPCHK(h, hipEventSynchronize(h->ring[(h->pushes + 1) % VDL2_NRING].in_read));
+	TRY(h->ring[(h->pushes + 1) % VDL2_NRING].in_read.sync(h));
 	hp(0);
 	vdl2gpu::Back &p = h->back;	/* what the stages share of this push; enqueue_front completes it for enqueue_back */
 	p.slab = (int)(h->pushes % VDL2_NSLAB);	/* page-locked slab this push's records are exported to */
@@ -2248,6 +2260,7 @@ static int push_impl(vdl2gpu_t *h, const void *iq, size_t nsamples, size_t strea
 	 * than through the scan's ten launches: the parallel path only pays from a few thousand frames on. */
 	p.serial = h->force_serial || (p.J <= VDL2_SERIAL_BELOW && !h->full_scan && !h->set[p.par].k2.test_noregion);
 	p.two_streams = !p.serial;	/* see vdl2gpu::Back */
+	p.spec = !h->full_scan && !p.serial && h->S * VDL2_CS <= 512;	/* see enqueue_back */
 	const bool two_streams = p.two_streams;
 	hipStream_t fs = two_streams ? h->fstream : h->stream;	/* the front stage's stream */
 	/* stream time of frame 0 of this push's planes: the outputs completed before it, minus the carried frames in front */
@@ -2261,41 +2274,34 @@ static int push_impl(vdl2gpu_t *h, const void *iq, size_t nsamples, size_t strea
 	pt.fast = false;
 	pt.staged = h->stage_events && (h->pushes % (uint64_t)h->stage_every) == 0;
 	pt.index = h->pushes;
-	const bool staged = pt.staged;
-	/* The channeliser opens the front stage (fstream; the main stream for a push that takes the serial path). */
+	/* The channeliser opens the front stage (fstream; the main stream for a push that takes the serial path).  What its stream waits for: */
 	hipStream_t ks = fs;
-	if (!two_streams && h->last_two_streams)	/* the previous push's channeliser state and carry were written on the front stream */
-		HIPCHK(h, hipStreamWaitEvent(fs, h->f_tail, 0));
-	if (!two_streams && h->set[(par + VDL2_NSET - 1) % VDL2_NSET].k2_rec)	/* ... and its tail may have run on the payload stream */
-		HIPCHK(h, hipStreamWaitEvent(fs, h->set[(par + VDL2_NSET - 1) % VDL2_NSET].k2_done, 0));
 	if (two_streams) {
 		/* the plane set this push's channeliser writes, the table set and the output ring were last used by the push three
 		 * back: by its tail (the payload decode of a repaired channel reads the planes to the very end of it) */
-		if (h->set[par].k2_rec)
-			HIPCHK(h, hipStreamWaitEvent(fs, h->set[par].k2_done, 0));
-		if (h->k1_ev_rec && !h->last_two_streams)	/* the previous push's channeliser ran on the main stream */
-			HIPCHK(h, hipStreamWaitEvent(fs, h->k1_ev, 0));
+		TRY(h->set[par].k2_done.wait(h, fs));
+		if (!h->last_two_streams)	/* the previous push's channeliser ran on the main stream: its state and carry */
+			TRY(h->k1_ev.wait(h, fs));
+	} else {
+		if (h->last_two_streams)	/* the previous push's channeliser state and carry were written on the front stream */
+			HIPCHK(h, hipStreamWaitEvent(fs, h->f_tail, 0));
+		TRY(h->set[set_before(par)].k2_done.wait(h, fs));	/* ... and its tail may have run on the payload stream */
 	}
-	if (in.staged)
+	if (in.staged)	/* host samples: the staging copy */
 		HIPCHK(h, hipStreamWaitEvent(ks, h->raw_copied[stg], 0));
-	if (staged && h->stage_dump && !h->ev_origin) {	/* the origin of the dump's times: in front of the first push's first event, on its stream */
+	if (pt.staged && h->stage_dump && !h->ev_origin) {	/* the origin of the dump's times: in front of the first push's first event, on its stream */
 		NEW_EVENT(h, h->ev_origin, true);
 		HIPCHK(h, hipEventRecord(h->ev_origin, ks));
 	}
-	if (staged)
-		HIPCHK(h, hipEventRecord(pt.e[0], ks));
+	TRY(mark(h, pt, E_K1_BEGIN, ks));
 	TRY(enqueue_k1(h, k1, in, nsamples, par, ks, pt));
-	if (staged)
-		HIPCHK(h, hipEventRecord(pt.e[1], ks));
-	if (memkind != VDL2GPU_MEM_HOST) {	/* the caller's device buffer has been read: see the wait at the top */
-		HIPCHK(h, hipEventRecord(rg.in_read, ks));
-		rg.in_rec = true;
-	} else
-		rg.in_rec = false;
-	if (in.staged) {	/* (only the staging copy of the push after next waits for it) */
-		HIPCHK(h, hipEventRecord(h->k1_done[stg], ks));
-		h->k1_rec[stg] = true;
-	}
+	TRY(mark(h, pt, E_K1_END, ks));
+	if (memkind != VDL2GPU_MEM_HOST)	/* the caller's device buffer has been read: see the wait at the top */
+		TRY(rg.in_read.record(h, ks));
+	else
+		rg.in_read.clear();
+	if (in.staged)	/* (only the staging copy of the push after next waits for it) */
+		TRY(h->k1_done[stg].record(h, ks));
 	/* The output ring of this push: if the push that last used it (three back) has not been collected yet, collect it now --
 	 * the GPU has the two pushes in between and this push's channeliser to work on while this thread waits for that push's
 	 * tail. */
@@ -3154,47 +3160,42 @@ extern "C" int vdl2gpu_debug_k1(vdl2gpu_t *h, unsigned long long *out, int n)
 	return n;
 }
 
+/* rows of one of the last push's per-channel tables (K2Params::*table, `cap` rows a channel): synchronise, read the channel's count
+ * word -- block `count_block` of the [S*8] blocks behind CTL_CAND0 --, copy that many rows; returns the count */
+template <class T> static int debug_rows(vdl2gpu_t *h, int stream, int ch, int *out, int max_rows, T *K2Params::*table, unsigned cap, size_t count_block)
+{
+	if (!h || stream < 0 || stream >= h->S || ch < 0 || ch >= h->C || !out)
+		return VDL2GPU_EINVAL;
+	HLOCK(h);
+	int rc = vdl2gpu_sync(h);
+	if (rc)
+		return rc;
+	const K2Params &k2 = h->set[h->last_set].k2;
+	const int sc = stream * VDL2_CS + ch;
+	unsigned n = 0;
+	HIPCHK(h, hipMemcpy(&n, k2.ctl + CTL_CAND0 + count_block * (size_t)h->S * VDL2_CS + sc, sizeof n, hipMemcpyDeviceToHost));
+	n = std::min(n, cap);
+	n = std::min<unsigned>(n, (unsigned)max_rows);
+	if (n)
+		HIPCHK(h, hipMemcpy(out, k2.*table + (size_t)sc * cap, (size_t)n * sizeof(T), hipMemcpyDeviceToHost));
+	return (int)n;
+}
+
 /* candidates of (stream, channel index) found by the last push's sync scan: 6 ints per candidate
  * {nrel, r, bits(p2err), bits(perr), bits(err), bits(pfr)}; returns the count */
 extern "C" int vdl2gpu_debug_cands(vdl2gpu_t *h, int stream, int ch, int *out, int max_cands)
 {
-	if (!h || stream < 0 || stream >= h->S || ch < 0 || ch >= h->C || !out)
-		return VDL2GPU_EINVAL;
-	HLOCK(h);
-	int rc = vdl2gpu_sync(h);
-	if (rc)
-		return rc;
-	const int sc = stream * VDL2_CS + ch;
-	unsigned n = 0;
-	HIPCHK(h, hipMemcpy(&n, h->set[h->last_set].k2.ctl + CTL_CAND0 + sc, sizeof n, hipMemcpyDeviceToHost));
-	n = std::min<unsigned>(n, VDL2_CAND_CAP);
-	n = std::min<unsigned>(n, (unsigned)max_cands);
-	if (n)
-		HIPCHK(h, hipMemcpy(out, h->set[h->last_set].k2.cands + (size_t)sc * VDL2_CAND_CAP, (size_t)n * sizeof(Cand), hipMemcpyDeviceToHost));
-	return (int)n;
+	return debug_rows(h, stream, ch, out, max_cands, &K2Params::cands, VDL2_CAND_CAP, 0);
+}
+
+/* diagnostics: the cluster heads (cl_pack) of the last push's candidates, in vdl2gpu_debug_cands()'s order */
+extern "C" int vdl2gpu_debug_clheads(vdl2gpu_t *h, int stream, int ch, int *out, int max_cands)
+{
+	return debug_rows(h, stream, ch, out, max_cands, &K2Params::clhead, VDL2_CAND_CAP, 0);
 }
 
 /* verify result of the last push per (stream, channel slot): stream-relative position of the first
  * detector hit the tables lacked, or >= 0x7f000000 when the push verified */
-/* diagnostics: the cluster heads (cl_pack) of the last push's candidates, in vdl2gpu_debug_cands()'s order */
-extern "C" int vdl2gpu_debug_clheads(vdl2gpu_t *h, int stream, int ch, int *out, int max_cands)
-{
-	if (!h || stream < 0 || stream >= h->S || ch < 0 || ch >= h->C || !out)
-		return VDL2GPU_EINVAL;
-	HLOCK(h);
-	int rc = vdl2gpu_sync(h);
-	if (rc)
-		return rc;
-	const int sc = stream * VDL2_CS + ch;
-	unsigned n = 0;
-	HIPCHK(h, hipMemcpy(&n, h->set[h->last_set].k2.ctl + CTL_CAND0 + sc, sizeof n, hipMemcpyDeviceToHost));
-	n = std::min<unsigned>(n, VDL2_CAND_CAP);
-	n = std::min<unsigned>(n, (unsigned)max_cands);
-	if (n)
-		HIPCHK(h, hipMemcpy(out, h->set[h->last_set].k2.clhead + (size_t)sc * VDL2_CAND_CAP, (size_t)n * sizeof(int2), hipMemcpyDeviceToHost));
-	return (int)n;
-}
-
 extern "C" int vdl2gpu_debug_fail(vdl2gpu_t *h, int *out, int n)
 {
 	if (!h || !out || n < h->S * VDL2_CS)
@@ -3208,21 +3209,10 @@ extern "C" int vdl2gpu_debug_fail(vdl2gpu_t *h, int *out, int n)
 	return h->S * VDL2_CS;
 }
 
+/* diagnostics: the idle segments the last push's resolver asked to have verified {lo, hi, r, pad} */
 extern "C" int vdl2gpu_debug_segs(vdl2gpu_t *h, int stream, int ch, int *out, int max_segs)
 {
-	if (!h || stream < 0 || stream >= h->S || ch < 0 || ch >= h->C || !out)
-		return VDL2GPU_EINVAL;
-	HLOCK(h);
-	int rc = vdl2gpu_sync(h);
-	if (rc)
-		return rc;
-	const int sc = stream * VDL2_CS + ch;
-	unsigned n = 0;
-	HIPCHK(h, hipMemcpy(&n, h->set[h->last_set].k2.ctl + CTL_CAND0 + 3 * (size_t)h->S * VDL2_CS + sc, sizeof n, hipMemcpyDeviceToHost));
-	n = std::min<unsigned>(n, (unsigned)std::min(max_segs, VDL2_SEG_CAP));
-	if (n)
-		HIPCHK(h, hipMemcpy(out, h->set[h->last_set].k2.segs + (size_t)sc * VDL2_SEG_CAP, (size_t)n * sizeof(Seg), hipMemcpyDeviceToHost));
-	return (int)n;
+	return debug_rows(h, stream, ch, out, max_segs, &K2Params::segs, VDL2_SEG_CAP, 3);
 }
 
 /* VDL2GPU_F_DEBUG_HEADS: the header soft bits of every sync trigger any kernel of the LAST push handled -- the

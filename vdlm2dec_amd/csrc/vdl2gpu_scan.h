@@ -638,7 +638,7 @@ __device__ __forceinline__ void k2a_tail(K2aShared &sh, int sc)
 /* What the scan workgroups' private areas did not hold lies in the list's common area (k2a_append: a stretch where far more
  * than 2.7 % pass -- a carrier, a run of sync words; a test build's handicaps): the one-workgroup-per-channel kernel that
  * follows the scan on its stream works it off before it looks at the scan's results (a kernel boundary lies between the
- * writes and these reads: no fence).  p.drain_* name the scan (set by the host on the consumer's launch: enqueue_scan_drain);
+ * writes and these reads: no fence).  p.drain_* name the scan (set by the host on the consumer's launch, and nowhere else: launch_per_channel);
  * nothing to do as a rule: one word read. */
 template <int NT> __device__ void k2x_drain(K2xWork &w, const K2Params &p, int sc)
 {

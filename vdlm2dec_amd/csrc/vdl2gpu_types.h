@@ -233,7 +233,7 @@ struct K2Params {
 	int surv_pch, surv_nwg;	/* items a private area holds (a multiple of 256), scan workgroups per channel (= private areas) */
 	int surv_common_cap;	/* test hook: the common area holds only so many items (0: all that is left of the list) */
 	int surv_slot;		/* which of the push's scans this is: its item counters are ctl[CTL_NSURV0 + slot * S*8 ...] (VDL2_SURV_*) */
-	int surv_mode;		/* sparse stages: what a detector hit among the survivors means (k2a_emit: 0 candidates, 1 verify, 2 probe) */
+	int surv_mode;		/* sparse stages: what a detector hit among the survivors means (k2a_emit: 0 candidates, 1 verify, 2 probe, 3 seeds; host side: SURV_*) */
 	int surv_skip;		/* sparse stages: hits in the probe's class are in the table already (region scan) */
 	/* the one-workgroup-per-channel kernel behind a scan drains that scan's common area first (k2x_drain): which scan, and how its list was laid out */
 	int drain_slot;		/* VDL2_SURV_* of the scan in front of this launch, -1: nothing to drain */
