@@ -294,7 +294,6 @@ struct vdl2gpu {
 		bool split_fixed = false;	/* (test hook) the part length was given: do not adapt it */
 		int k1f_nfam = 0;		/* VDL2GPU_K1F_NFAM */
 		int verify2_wg = 8;		/* VDL2GPU_VERIFY2_WG: workgroups per channel of the local repair round's verify pass */
-		int k1_dbg = 0;			/* VDL2GPU_K1_DBG */
 		int k1_nsub = 0;		/* VDL2GPU_K1_NSUB */
 #ifdef VDL2GPU_TESTHOOKS
 		int test_item_grid = 0;		/* VDL2GPU_TEST_ITEM_GRID: few scan workgroups with the smallest private areas -- most items take the common area's path */
@@ -865,12 +864,7 @@ static void fill_set_params(vdl2gpu_t *h)
 		k.stage_cap = h->stage_cap;
 		k.outc_total_redo = h->d_outc + 8;
 		k.rec_cap = h->rec_cap;
-#if VDL2_PROBE_STRIDE == 2
 		k.probe_r = 0;				/* the one class scanned everywhere: fixed, not the class the channel is in */
-#else
-		k.probe_r = -1;			/* no class is scanned everywhere: the probe only finds the bursts (every fourth sample of sub-phase 0), the
-							 * region scan lists every class around them, the verify pass covers every stretch the chain idles through */
-#endif
 		k.prim_drop = h->prim_drop;
 		k.dbg = h->knob.debug_counters ? h->d_dbg : nullptr;
 		k.headtap = h->d_headtap;
@@ -929,7 +923,6 @@ static int create_impl(vdl2gpu_t *h)
 	h->knob.debug_counters = getenv("VDL2GPU_DEBUG_COUNTERS") != nullptr;
 	h->knob.k1f_nfam = env_int("VDL2GPU_K1F_NFAM", 0);
 	h->knob.verify2_wg = std::max(1, env_int("VDL2GPU_VERIFY2_WG", 8));
-	h->knob.k1_dbg = env_int("VDL2GPU_K1_DBG", 0);
 	h->knob.k1_nsub = env_int("VDL2GPU_K1_NSUB", 0);
 #ifdef VDL2GPU_TESTHOOKS
 	h->prim_drop = env_int("VDL2GPU_PRIM_DROP", 0);
@@ -1386,7 +1379,7 @@ static void spill_slab(vdl2gpu_t *h, int slab);
  * their private areas of the item list did not hold is left in the list's common area for the one-workgroup-per-channel kernel
  * that follows on the stream -- the scan's ScanDrain says where that is, and goes to that kernel's launch (launch_per_channel). */
 enum { SCAN_PROBE, SCAN_REGION, SCAN_VERIFY };
-enum { SURV_CANDS = 0, SURV_VERIFY = 1, SURV_PROBE = 2, SURV_SEEDS = 3 };	/* K2Params.surv_mode: what a detector hit among the survivors means */
+enum { SURV_CANDS = 0, SURV_VERIFY = 1, SURV_PROBE = 2 };	/* K2Params.surv_mode: what a detector hit among the survivors means */
 struct ScanDrain { int slot = -1, mode = 0, skip = 0, pch = 0, nwg = 0; };	/* (slot -1: nothing to drain) */
 static int launch_scan(vdl2gpu_t *h, int which, const K2Params &k2, dim3 grid, hipStream_t st, int slot, int mode, int skip, unsigned tiles_per_wg, ScanDrain &drain)
 {
@@ -2025,7 +2018,6 @@ static void launch_k1_pp(vdl2gpu_t *h, const K1Params &k1, const K1Choice &ch, h
 	auto proven = [](int nf) { return nf == 23 || nf == 24 || nf == 59 || nf == 60 || nf == 71 || nf == 72 || nf == 119 || nf == 120; };
 	kp.fast_div = proven(nfmin) && proven(nfmax) && nfmax - nfmin <= 1;
 	kp.nf_lo = nfmin;
-	kp.dbg = h->knob.k1_dbg;
 	kp.rcp_lo = 1.0f / (float)nfmin;
 	kp.rcp_hi = 1.0f / (float)(nfmin + 1);
 	/* tasks = (blocks of 64 periods) x (runs of wpt windows): enough of them that the last round of
@@ -2158,7 +2150,7 @@ static int enqueue_front(vdl2gpu_t *h, hipStream_t fs, long long dec_base, PushT
 			/* the probe needs the carry the push before made (the first 49152 frames of this plane set); with the front
 			 * stage on two streams (below) that copy is not on this stream */
 			TRY(launch_scan(h, SCAN_PROBE, k2, dim3(per, (unsigned)h->C, (unsigned)GS), fs, VDL2_SURV_PROBE,
-					h->full_scan ? SURV_CANDS : (VDL2_PROBE_STRIDE == 2 ? SURV_PROBE : SURV_SEEDS), 0, (h->full_scan ? 4 : 1) * ((want + per - 1) / per), pdrain));
+					h->full_scan ? SURV_CANDS : SURV_PROBE, 0, (h->full_scan ? 4 : 1) * ((want + per - 1) / per), pdrain));
 		}
 		/* (k2r_regions works the probe's common area off first, k2s_sort the region scan's) */
 		launch_per_channel(h, k2r_regions, K2R_NT, fs, k2, pdrain);

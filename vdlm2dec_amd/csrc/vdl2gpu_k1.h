@@ -425,24 +425,6 @@ __device__ __forceinline__ void k1_load_block(v16f &w, v2f (&x)[8], const float2
 		     : "v"(a), "s"(lo)
 		     : "memory");
 }
-
-__device__ __forceinline__ void k1_load_block_nos(v16f &w, v2f (&x)[8], const float2 *lo, const unsigned a)
-{
-	asm volatile("ds_read_b64 %0, %8\n\tds_read_b64 %1, %8 offset:8\n\tds_read_b64 %2, %8 offset:16\n\t"
-		     "ds_read_b64 %3, %8 offset:24\n\tds_read_b64 %4, %8 offset:32\n\tds_read_b64 %5, %8 offset:40\n\t"
-		     "ds_read_b64 %6, %8 offset:48\n\tds_read_b64 %7, %8 offset:56\n\ts_waitcnt lgkmcnt(0)"
-		     : "=&v"(x[0]), "=&v"(x[1]), "=&v"(x[2]), "=&v"(x[3]), "=&v"(x[4]), "=&v"(x[5]), "=&v"(x[6]), "=&v"(x[7])
-		     : "v"(a)
-		     : "memory");
-	w = (v16f)(1.0f);
-}
-__device__ __forceinline__ void k1_load_block_nol(v16f &w, v2f (&x)[8], const float2 *lo, const unsigned a)
-{
-	asm volatile("s_load_dwordx16 %0, %1, 0x0\n\ts_waitcnt lgkmcnt(0)" : "=&s"(w) : "s"(lo) : "memory");
-#pragma unroll
-	for (int u = 0; u < 8; ++u)
-		x[u] = (v2f){1.0f, 2.0f};
-}
 #define K1P_THREADS 512
 #define K1P_CH 32		/* samples of every period per chunk */
 #define K1P_XROW (K1P_CH + 1)	/* LDS row of a period: +1 keeps the lanes' reads on distinct banks */
@@ -679,9 +661,7 @@ __device__ __forceinline__ void k1_cmac3_v(v2f &acc, const v2f (&x)[4], const v2
 #define K1F_WAVES_OF(FMT_) ((FMT_) == VDL2GPU_FMT_CF32 ? 4 : 5)
 #endif	/* wavefronts per SIMD the kernel is built for: 96 registers (cf32 holds its
 								 * raw samples in twice as many: 128, 4 wavefronts) */
-#ifndef K1F_DEPTH
 #define K1F_DEPTH 2		/* superperiods of raw samples in flight per wavefront (registers) */
-#endif
 #define K1F_CHUNK 8		/* superperiods per ticket (even: the two LDS copies and register sets alternate) */
 #define K1F_PER_IN 8000		/* a SUPERPERIOD: 4 periods of the schedule = 336 outputs = 21 lines of 16 */
 #define K1F_PER_OUT 336
@@ -698,19 +678,14 @@ template <> struct K1Raw<VDL2GPU_FMT_CF32> { typedef unsigned T __attribute__((e
  * then costs a full memory round trip, store acknowledgement included, and the kernel is latency-bound. */
 template <int FMT, int OFS = 0> __device__ __forceinline__ void k1_raw_issue(typename K1Raw<FMT>::T &r, const unsigned voff, const char *sbase)
 {
-#ifdef K1F_LOAD_NT
-#define K1F_LD_MOD " nt"
-#else
-#define K1F_LD_MOD ""
-#endif
 	if constexpr (FMT == VDL2GPU_FMT_CU8 || FMT == VDL2GPU_FMT_CS8)
-		asm volatile("global_load_ushort %0, %1, %2 offset:%3" K1F_LD_MOD : "=v"(r) : "v"(voff), "s"(sbase), "n"(OFS) : "memory");
+		asm volatile("global_load_ushort %0, %1, %2 offset:%3" : "=v"(r) : "v"(voff), "s"(sbase), "n"(OFS) : "memory");
 	else if constexpr (FMT == VDL2GPU_FMT_S16R)	/* sign-extended by the load: the register is the sample as an int */
-		asm volatile("global_load_sshort %0, %1, %2 offset:%3" K1F_LD_MOD : "=v"(r) : "v"(voff), "s"(sbase), "n"(OFS) : "memory");
+		asm volatile("global_load_sshort %0, %1, %2 offset:%3" : "=v"(r) : "v"(voff), "s"(sbase), "n"(OFS) : "memory");
 	else if constexpr (FMT == VDL2GPU_FMT_CF32)
-		asm volatile("global_load_dwordx2 %0, %1, %2 offset:%3" K1F_LD_MOD : "=v"(r) : "v"(voff), "s"(sbase), "n"(OFS) : "memory");
+		asm volatile("global_load_dwordx2 %0, %1, %2 offset:%3" : "=v"(r) : "v"(voff), "s"(sbase), "n"(OFS) : "memory");
 	else
-		asm volatile("global_load_dword %0, %1, %2 offset:%3" K1F_LD_MOD : "=v"(r) : "v"(voff), "s"(sbase), "n"(OFS) : "memory");
+		asm volatile("global_load_dword %0, %1, %2 offset:%3" : "=v"(r) : "v"(voff), "s"(sbase), "n"(OFS) : "memory");
 }
 
 template <int FMT> __device__ __forceinline__ float2 k1_raw_cvt(typename K1Raw<FMT>::T v)

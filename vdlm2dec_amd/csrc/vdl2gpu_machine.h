@@ -428,11 +428,7 @@ template <int NT, bool XL> __device__ __forceinline__ float mach_fir(const MachS
 			si += v[j].y * m;
 		}
 	}
-#ifdef VDL2_MACH_ATAN_BRANCHY
-	return vdl2_atan2f(si, sr);
-#else
-	return vdl2_atan2f_tab(si, sr, sh.atab);	/* the same result bits (tests/test_math.py, test_gpu_math.py), no divergence between the lanes */
-#endif
+	return vdl2_atan2f_tab(si, sr, sh.atab);	/* the same result bits as vdl2_atan2f() (tests/test_math.py, test_gpu_math.py), no divergence between the lanes */
 }
 
 template <int NT> __device__ __forceinline__ void mach_load(MachSharedT<NT> &sh, const ChanState *cs)

@@ -28,13 +28,6 @@
 #ifndef K2A_TS
 #define K2A_TS 1024		/* evaluation instants per tile */
 #endif
-#ifndef K2A_PREFETCH
-#define K2A_PREFETCH 0		/* 1: a workgroup loads its next tile's samples into registers behind the current tile's filter pass (twenty
-				 * registers through the screens: the kernels then need more than the 80 that six wavefronts per SIMD leave) */
-#endif
-#ifndef K2A_FLUSH_ATTR
-#define K2A_FLUSH_ATTR
-#endif
 #ifndef K2A_WPE
 #define K2A_WPE 6		/* wavefronts per SIMD the scan kernels are compiled for */
 #endif
@@ -81,7 +74,7 @@ struct K2aDef {			/* an evaluation that needs the exact fit */
 #define K2A_ITEM_WORDS 5
 struct K2aItem { float4 w[K2A_ITEM_WORDS]; };	/* (size only: see above for the layout) */
 
-/* LDS of a scan workgroup: 19.1 KB (the verify pass: 20.4 KB), seven or eight workgroups per CU as far as LDS goes.
+/* LDS of a scan workgroup: 21 168 bytes (the verify pass: 22 208), seven workgroups per CU as far as LDS goes.
  *   xs[]  S = 2 (one class: probe, verify): even samples, then (at K2A_XODD) odd samples, so that both FIR tap parities are
  *         unit-stride across lanes; once the filter pass has read them the SAME memory takes the phase-step phasors
  *         (wu = xs: the filter's results wait in registers for the barrier).
@@ -102,18 +95,6 @@ static_assert(K2A_WU1 % 2 == 0 && K2A_XS_LEN >= K2A_XMAX + 8 && (K2A_XMAX / 2 + 
 static_assert(K2A_TS + K2A_POFF / 2 + 2 <= K2A_XS_LEN && K2A_WU1 >= K2A_TS + K2A_XOFF, "phasor areas");
 static_assert(K2A_TS <= 1024, "pend[] holds an instant within the tile in ten bits");
 #define K2A_XODD (K2A_XMAX / 2 + 4)	/* 8-byte elements: an odd multiple of 64 bytes away, so the two halves use disjoint banks */
-/* S = 4 (the probe since round 5: every FOURTH sample, one sub-phase -- it only has to FIND the bursts, see k2a_probe): a tile is
- * 512 instants (the same 2048 samples as an S = 2 tile), its samples lie de-interleaved by (index mod 4) in four runs of K2A_XQ4
- * elements (tap j = 4 m + t of instant q is element q + m of run t: unit stride across lanes for every tap), 64 bytes apart
- * modulo the banks' 256. */
-#define K2A_TS4 (K2A_TS / 2)
-#ifndef VDL2_PROBE_STRIDE
-#define VDL2_PROBE_STRIDE 2	/* samples between the probe's instants: 2 = one class completely (round 4), 4 = every second instant of it, seeds only */
-#endif
-#define K2A_XQ4 552
-static_assert(4 * K2A_XQ4 <= K2A_XS_LEN && K2A_XQ4 % 32 == 8 && (4 * (K2A_TS4 - 1) + 1 + K2A_XOFF + 3) / 4 <= K2A_XQ4 &&
-	      K2A_TS4 + K2A_POFF / 4 - 2 + 6 <= K2A_XQ4, "S = 4 sample runs: a tile's samples, and the six elements a lane pair reads of each run");
-template <int S> struct K2aTs { static constexpr int v = (S == 4) ? K2A_TS4 : K2A_TS; };
 
 /* Screens for the 17-point fit (the expensive part of the scan).
  * With Pr[] the unwrapped, template-corrected phases the reference fits a line to (d8psk.c:257-289)
@@ -184,7 +165,7 @@ template <class PR> __device__ __forceinline__ void k2a_emit(PR p, int sc, long 
 		if (kk < VDL2_CAND_CAP)	/* surplus seeds are simply dropped: K2a-verify covers what they would have */
 			p.seeds[(size_t)sc * VDL2_CAND_CAP + kk] = (int)(n - dec_base);
 	}
-	if (mode == 3)	/* the probe: it finds the bursts, it lists no candidates (it looks at every second instant of its class only) */
+	if (mode == 3)	/* (no scan runs in this mode: see the legend above k2a_append) */
 		return;
 	if (!(perr < 4.0f && err > perr))
 		return;
@@ -237,16 +218,6 @@ template <class PR> __device__ __forceinline__ void k2a_emit(PR p, int sc, long 
 		*ovf = 1u;
 }
 
-/* The samples of a tile travel HBM -> registers -> LDS.  The registers of the *next* tile of the
- * same workgroup are loaded once the current tile's filter pass is through (its sample registers are free then), so that
- * the memory latency (several thousand cycles under load) is hidden behind the current tile's screens. */
-template <int S> struct K2aPre {
-	static constexpr int NL = (S * (K2aTs<S>::v - 1) + 1 + K2A_XOFF + K2A_THREADS - 1) / K2A_THREADS;
-	float2 v[NL];
-	bool loaded;
-	int tiles;		/* tiles this workgroup has done: which of its wavefronts takes the sparse pass rotates */
-};
-
 /* once per workgroup, before its first tile */
 __device__ __forceinline__ void k2a_tables(K2aShared &sh)
 {
@@ -259,19 +230,6 @@ __device__ __forceinline__ void k2a_tables(K2aShared &sh)
 	__syncthreads();
 }
 
-template <int S> __device__ __forceinline__ void k2a_fetch(K2aPre<S> &pre, const K2Params &p, int sc, long long dec_base, long long nbase, int cnt)
-{
-	const float2 *x = p.dec + (size_t)sc * p.cap + (nbase - K2A_XOFF - dec_base);
-	const int nx = S * (cnt - 1) + 1 + K2A_XOFF;
-#pragma unroll
-	for (int k = 0; k < K2aPre<S>::NL; ++k) {
-		const int i = (int)threadIdx.x + k * K2A_THREADS;
-		if (i < nx)
-			pre.v[k] = x[i];
-	}
-	pre.loaded = true;
-}
-
 /* The tile loop of a scan kernel does the DENSE part only: filter, phasors and the first screen at every instant of a tile, all
  * four wavefronts of a workgroup in step.  What passes the first screen (2.7 % of the instants) is put aside as an item --
  * instant, class and the sixteen phase-step phasors it was screened on -- in the workgroup's private area of the channel's item
@@ -281,7 +239,12 @@ template <int S> __device__ __forceinline__ void k2a_fetch(K2aPre<S> &pre, const
  * the other three waited at the barrier -- a third of the probe's time -- and the exact work's live registers on top of the
  * tile loop's capped the scan kernels at four wavefronts per SIMD; round 4 ran them as a kernel of its own behind every scan:
  * four more launches a push, 30 us each as they ran.  Behind the tile loop the exact work has the registers to itself.]
- * mode 0: append candidates; mode 1: report hits in [chk_lo, chk_hi) to *fail and append them; mode 2: probe (candidates + seeds). */
+ * The scan modes (K2Params.surv_mode; host side: SURV_*) -- 0: append candidates (region scan, complete scan); 1: verify pass, report
+ * hits in [chk_lo, chk_hi) to *fail and append them; 2: probe, candidates of its class and seeds for the region scan.
+ * [Mode 3, seeds without candidates, was the probe at every fourth sample's (measured twice and dropped: DESIGN.md section 8.4).  No
+ * host code sets it any more; k2a_emit's test for it and the `mode >= 2` there and in k2x_chunk are what is left, because `mode` is
+ * a run-time value in the sparse stages and the compiler allots the registers of all eight kernels that hold them differently
+ * without the tests: taking them out is a change to measure, not a tidying.] */
 
 /* The lanes of a wavefront whose evaluation passed the first screen append their items: one atomic per wavefront and pass,
  * the items in lane order (= time order: k2x_chunk finds an evaluation's neighbours next to it). */
@@ -509,9 +472,6 @@ __device__ __forceinline__ void k2x_chunk(K2xWork &sh, PR p, int sc, int mode, i
 		sh.dl[atomicAdd(&sh.ns, 1)] = d;
 	__syncthreads();
 	const int nd = sh.ns;
-#ifdef K2X_NO_EXACT
-	return;
-#endif
 	if (nd == 0)	/* (block-uniform) */
 		return;
 	if (!sh.tabs) {	/* (block-uniform; the tables of the exact stage: only now, one chunk in ten gets here) */
@@ -674,25 +634,7 @@ template <int S> __device__ __forceinline__ void k2a_fir2(const K2aShared &sh, i
 	typedef float v4f __attribute__((ext_vector_type(4)));
 	acc0 = (v2f){0.0f, 0.0f};
 	acc1 = (v2f){0.0f, 0.0f};
-	if (S == 4) {
-		/* instant q, tap j = 4 m + t: element q + m of run t; the neighbouring instant q + 1 one element on (q0 is even: 16-byte reads) */
-		v2f x[4][6];
-#pragma unroll
-		for (int t = 0; t < 4; ++t) {
-			const v4f *pt = reinterpret_cast<const v4f *>(&sh.xs[t * K2A_XQ4 + q0]);
-#pragma unroll
-			for (int i = 0; i < 3; ++i) {
-				const v4f e = pt[i];
-				x[t][2 * i] = e.xy;
-				x[t][2 * i + 1] = e.zw;
-			}
-		}
-#pragma unroll
-		for (int j = 0; j < 17; ++j) {
-			acc0 = __builtin_elementwise_fma(x[j & 3][j >> 2], (v2f){mf[j], mf[j]}, acc0);
-			acc1 = __builtin_elementwise_fma(x[j & 3][(j >> 2) + 1], (v2f){mf[j], mf[j]}, acc1);
-		}
-	} else if (S == 2) {
+	if (S == 2) {
 		/* instant q, tap j: even j = 2m -> even sample q + m, odd j = 2m + 1 -> odd sample q + m */
 		const v4f *pe = reinterpret_cast<const v4f *>(&sh.xs[q0]);
 		const v4f *po = reinterpret_cast<const v4f *>(&sh.xs[K2A_XODD + q0]);
@@ -756,14 +698,9 @@ __device__ __forceinline__ float k2a_lane_from(int byte_addr, float v)
 	return __int_as_float(__builtin_amdgcn_ds_bpermute(byte_addr, __float_as_int(v)));
 }
 
-#ifdef K2A_NOBAR
-#define K2A_SYNC() __builtin_amdgcn_wave_barrier()
-#else
-#define K2A_SYNC() __syncthreads()
-#endif
 template <int S> __device__ void k2a_tile(K2aShared &sh, const K2Params &p, int sc, long long dec_base, long long nbase,
 					   int cnt, unsigned rmask, int mode, long long chk_lo, long long chk_hi, int *fail,
-					   K2aPre<S> &pre, long long next_nbase, int next_cnt, int skip_r = -1, int skip_par = 0)
+					   int skip_r = -1, int skip_par = 0)
 {
 	const int tid = threadIdx.x;
 	constexpr int PH = K2A_POFF / S;	/* phase instants of history */
@@ -774,54 +711,35 @@ template <int S> __device__ void k2a_tile(K2aShared &sh, const K2Params &p, int 
 	constexpr int KH = LSTR / 2;
 	constexpr int PPW = 64 - KH;				/* pairs a wavefront owns per round */
 	constexpr int PPI = (K2A_THREADS / 64) * PPW;		/* ... the workgroup */
-	constexpr int TSS = K2aTs<S>::v;	/* instants of a full tile */
-	constexpr int NIT = ((TSS + PH + 1) / 2 + PPI - 1) / PPI;
+	constexpr int NIT = ((K2A_TS + PH + 1) / 2 + PPI - 1) / PPI;
+	constexpr int NL = (S * (K2A_TS - 1) + 1 + K2A_XOFF + K2A_THREADS - 1) / K2A_THREADS;	/* samples of a full tile per thread */
 	static_assert(K2A_POFF == S * PH, "phase history must be a whole number of instants");
 	float2 *const wu = (S != 1) ? sh.xs : sh.xs + K2A_WU1;	/* phase-step phasors (see K2aShared) */
-	/* exp(-j (SW[l] - SW[l-1])), l = 1..16: the template steps are 1,7,5,-7,1,3,-3,-7,3,-1,5,-5,-3,-5,-1,7 (x pi/8) */
-#ifdef K2A_SCREEN_FMA
-	constexpr float C1 = 0.92387953251128674f, S1 = 0.38268343236508977f;
-	constexpr float rc[16] = {C1, -C1, -S1, -C1, C1, S1, S1, -C1, S1, C1, -S1, -S1, S1, -S1, C1, -C1};
-	constexpr float rs[16] = {-S1, -S1, -C1, S1, -S1, -C1, C1, S1, -C1, S1, -C1, C1, C1, C1, S1, -S1};
-#endif
 	const int nx = S * (cnt - 1) + 1 + K2A_XOFF;
-	const bool prof = p.dbg && (mode >= 2 || (mode == 0 && S == 1 && !p.full_scan && !p.full_round)) && tid == 0 && (blockIdx.x & 7) == 0;	/* probe, region scan */
+	const bool prof = p.dbg && (mode == 2 || (mode == 0 && S == 1 && !p.full_scan && !p.full_round)) && tid == 0 && (blockIdx.x & 7) == 0;	/* probe, region scan */
 	long long tq = prof ? clock64() : 0;
 #define K2A_STAMP(slot) do { if (prof) { const long long tn = clock64(); sh.prof[slot] += (unsigned long long)(tn - tq); tq = tn; } } while (0)
 	/* park slots: sample i = tid + k * K2A_THREADS of the tile goes to xs[pbase + k * pstep] */
-	const int pbase = (S == 4) ? (tid & 3) * K2A_XQ4 + (tid >> 2) : ((S == 2) ? (tid & 1) * K2A_XODD + (tid >> 1) : tid);
+	const int pbase = (S == 2) ? (tid & 1) * K2A_XODD + (tid >> 1) : tid;
 	constexpr int pstep = K2A_THREADS / S;
-#if K2A_PREFETCH
-	if (!pre.loaded)
-		k2a_fetch<S>(pre, p, sc, dec_base, nbase, cnt);
-	K2A_SYNC();
-	K2A_STAMP(12);
-#pragma unroll
-	for (int k = 0; k < K2aPre<S>::NL; ++k)
-		if (tid + k * K2A_THREADS < nx)
-			sh.xs[pbase + k * pstep] = pre.v[k];
-	pre.loaded = false;
-#else
 	{
-		/* no software prefetch: six workgroups per CU are in different phases of their tiles, one's wait for its samples is
-		 * another's filter pass (the twenty registers a prefetch holds through the screens are what six wavefronts per SIMD
-		 * do not leave) */
+		/* The samples of a tile travel HBM -> registers -> LDS.  No software prefetch of the next tile's: six workgroups per CU
+		 * are in different phases of their tiles, one's wait for its samples is another's filter pass (the twenty registers a
+		 * prefetch holds through the screens are what six wavefronts per SIMD do not leave) */
 		const float2 *x = p.dec + (size_t)sc * p.cap + (nbase - K2A_XOFF - dec_base);
-		float2 v[K2aPre<S>::NL];
+		float2 v[NL];
 #pragma unroll
-		for (int k = 0; k < K2aPre<S>::NL; ++k)
+		for (int k = 0; k < NL; ++k)
 			if (tid + k * K2A_THREADS < nx)
 				v[k] = x[tid + k * K2A_THREADS];
 		K2A_STAMP(12);
 #pragma unroll
-		for (int k = 0; k < K2aPre<S>::NL; ++k)
+		for (int k = 0; k < NL; ++k)
 			if (tid + k * K2A_THREADS < nx)
 				sh.xs[pbase + k * pstep] = v[k];
 	}
-#endif
-	pre.tiles++;
 	K2A_STAMP(13);
-	K2A_SYNC();
+	__syncthreads();
 	K2A_STAMP(0);
 	const int npairs = (cnt + PH + 1) / 2;
 	const int wv = tid >> 6, ln = tid & 63;
@@ -845,7 +763,7 @@ template <int S> __device__ void k2a_tile(K2aShared &sh, const K2Params &p, int 
 				continue;
 			}
 			int q0 = 2 * (pw + ln - KH);
-			q0 = q0 < 0 ? 0 : (q0 > TSS + PH - 2 ? TSS + PH - 2 : q0);	/* keeps the reads inside xs[]; what a clamped lane computes is not stored */
+			q0 = q0 < 0 ? 0 : (q0 > K2A_TS + PH - 2 ? K2A_TS + PH - 2 : q0);	/* keeps the reads inside xs[]; what a clamped lane computes is not stored */
 			v2f acc[2];
 			k2a_fir2<S>(sh, q0, mf, acc[0], acc[1]);
 			const v2f w0 = k2a_unit(acc[0]), w1 = k2a_unit(acc[1]);
@@ -856,12 +774,8 @@ template <int S> __device__ void k2a_tile(K2aShared &sh, const K2Params &p, int 
 			__builtin_amdgcn_sched_barrier(0);	/* one round's nineteen samples in registers at a time */
 		}
 		K2A_STAMP(1);
-#if K2A_PREFETCH
-		if (next_cnt > 0 && !pre.loaded)	/* the next tile's samples: in flight during this tile's screens */
-			k2a_fetch<S>(pre, p, sc, dec_base, next_nbase, next_cnt);
-#endif
 		if (S != 1)
-			K2A_SYNC();	/* wu[] is xs[]: every wavefront is through with the samples */
+			__syncthreads();	/* wu[] is xs[]: every wavefront is through with the samples */
 		K2A_STAMP(2);
 #pragma unroll
 		for (int it = 0; it < NIT; ++it) {
@@ -870,7 +784,7 @@ template <int S> __device__ void k2a_tile(K2aShared &sh, const K2Params &p, int 
 				*reinterpret_cast<float4 *>(&wu[q0]) = hold[it];
 		}
 		K2A_STAMP(3);
-		K2A_SYNC();
+		__syncthreads();
 		/* ---- first screen, of the evaluation that is the `perr` of instant i: j = i + E2.  What passes (2.7 % on noise: seven of a
 		 *      wavefront's 256 evaluations) is only NOTED here, two bytes in the wavefront's own queue; the items -- sixteen phasors
 		 *      re-read from wu[], packed, five 16-byte stores, one LDS atomic -- are written behind the passes as one group per
@@ -886,15 +800,6 @@ template <int S> __device__ void k2a_tile(K2aShared &sh, const K2Params &p, int 
 #pragma unroll
 			for (int l = 0; l < 16; ++l)	/* all sixteen LDS reads in flight before the arithmetic */
 				uu[l] = uq[l * LSTR];
-#ifdef K2A_SCREEN_FMA
-			v2f acc = {0.0f, 0.0f}, acc1 = {0.0f, 0.0f};
-#pragma unroll
-			for (int l = 0; l < 16; l += 2) {
-				acc = k2_rot(acc, (v2f){uu[l].x, uu[l].y}, rc[l], rs[l]);
-				acc1 = k2_rot(acc1, (v2f){uu[l + 1].x, uu[l + 1].y}, rc[l + 1], rs[l + 1]);
-			}
-			acc += acc1;
-#else
 			/* The sixteen template rotations are e^(j pi/8) e^(j k pi/4) with k = 7,4,5,3,7,6,1,3,6,0,5,2,1,2,0,4: the common factor
 			 * does not change |R|, even k are quarter turns (+-1, +-j) and odd k the same times e^(j pi/4) -- so the phasors are
 			 * ADDED into four sums (+-1 and +-j, with and without the eighth turn) and turned once at the end: 16 packed additions
@@ -914,7 +819,6 @@ template <int S> __device__ void k2a_tile(K2aShared &sh, const K2Params &p, int 
 			const v2f qa = {s4[2].x - s4[3].y, s4[2].y + s4[3].x};
 			constexpr float RH = 0.70710678118654752f;
 			const v2f acc = {__fmaf_rn(qa.x - qa.y, RH, pa.x), __fmaf_rn(qa.x + qa.y, RH, pa.y)};
-#endif
 			const float r2 = __fmaf_rn(acc.x, acc.x, acc.y * acc.y);
 			bool pass = i < cnt && !(r2 <= VDL2_SCREEN_R2);
 			if (mode == 0 && r == skip_r && (int)((nbase + S * (j - E4)) & 1) == skip_par)
@@ -942,7 +846,7 @@ template <int S> __device__ void k2a_tile(K2aShared &sh, const K2Params &p, int 
 		}
 		K2A_STAMP(4);
 		K2A_STAMP(8);
-		K2A_SYNC();
+		__syncthreads();
 		K2A_STAMP(9);
 		if (prof)
 			sh.prof[11] += 1ull;
@@ -967,57 +871,24 @@ void k2a_probe(K2Params p)
 	k2a_tables(sh);
 	/* each workgroup walks tiles blockIdx.x, blockIdx.x + gridDim.x, ... of its channel */
 	if (p.full_scan || p.full_round) {
-		K2aPre<1> pre;
-		pre.loaded = false;
-		pre.tiles = 0;
 		const long long step = (long long)gridDim.x * K2A_TS;
 		for (long long n0 = p.scan_lo + (long long)blockIdx.x * K2A_TS; n0 < avail_end; n0 += step) {
 			const int nt = (int)((avail_end - n0 < K2A_TS) ? (avail_end - n0) : K2A_TS);
-			const long long n1 = n0 + step;
-			const int nt1 = n1 < avail_end ? (int)((avail_end - n1 < K2A_TS) ? (avail_end - n1) : K2A_TS) : 0;
-			k2a_tile<1>(sh, p, sc, dec_base, n0, nt, 0xfu, 0, 0, 0, nullptr, pre, n1, nt1);
+			k2a_tile<1>(sh, p, sc, dec_base, n0, nt, 0xfu, 0, 0, 0, nullptr);
 		}
 		k2a_tail(sh, sc);
 		return;
 	}
-#if VDL2_PROBE_STRIDE == 2
 	/* ONE class everywhere: sub-phase probe_r at the instants of scan_lo's parity -- any class finds the bursts; which
 	 * stretches the chain relied on in OTHER classes is what the verify pass re-scans (round 4's probe: its class is a complete
 	 * table, the region scan skips it and the verify pass the stretches the chain idles through in it) */
-	K2aPre<2> pre;
-	pre.loaded = false;
-	pre.tiles = 0;
 	const unsigned rmask = 1u << p.probe_r;
 	const long long step = 2LL * gridDim.x * K2A_TS;
 	for (long long n0 = p.scan_lo + 2LL * blockIdx.x * K2A_TS; n0 < avail_end; n0 += step) {
 		const long long left = (avail_end - n0 + 1) / 2;
 		const int nt = (int)(left < K2A_TS ? left : K2A_TS);
-		const long long n1 = n0 + step;
-		const long long left1 = (avail_end - n1 + 1) / 2;
-		const int nt1 = n1 < avail_end ? (int)(left1 < K2A_TS ? left1 : K2A_TS) : 0;
-		k2a_tile<2>(sh, p, sc, dec_base, n0, nt, rmask, 2, 0, 0, nullptr, pre, n1, nt1);
+		k2a_tile<2>(sh, p, sc, dec_base, n0, nt, rmask, 2, 0, 0, nullptr);
 	}
-#else
-	/* The probe FINDS the bursts: sub-phase 0 at every FOURTH sample from scan_lo on, and what it hands on are seeds -- where the
-	 * fit error of that class dips below VDL2_SEED_ERR (k2a_emit, mode 3) --, around which the region scan looks at every class
-	 * at every instant.  A burst fires the detector in all eight classes within a few samples and its screen sum stays within
-	 * 0.5 of the maximum two samples off (scripts/dev/probe_rate.py), so half the instants of one class find it as well as all of
-	 * them did: half the filter and screen work of round 4's probe, which looked at every second sample and whose class was a
-	 * complete table in exchange -- now the region scan lists the probe's class too and the verify pass covers the stretches
-	 * the chain idles through in it (an eighth more of either).  What the probe misses the verify pass finds, as ever. */
-	K2aPre<4> pre;
-	pre.loaded = false;
-	pre.tiles = 0;
-	const long long step = 4LL * gridDim.x * K2A_TS4;
-	for (long long n0 = p.scan_lo + 4LL * blockIdx.x * K2A_TS4; n0 < avail_end; n0 += step) {
-		const long long left = (avail_end - n0 + 3) / 4;
-		const int nt = (int)(left < K2A_TS4 ? left : K2A_TS4);
-		const long long n1 = n0 + step;
-		const long long left1 = (avail_end - n1 + 3) / 4;
-		const int nt1 = n1 < avail_end ? (int)(left1 < K2A_TS4 ? left1 : K2A_TS4) : 0;
-		k2a_tile<4>(sh, p, sc, dec_base, n0, nt, 1u, 3, 0, 0, nullptr, pre, n1, nt1);
-	}
-#endif
 	k2a_tail(sh, sc);
 	if (p.dbg && threadIdx.x < 16 && sh.prof[threadIdx.x])
 		atomicAdd(p.dbg + 32 + threadIdx.x, sh.prof[threadIdx.x]);
@@ -1246,15 +1117,11 @@ void k2a_region(K2Params p)
 	if (threadIdx.x < 16)
 		sh.prof[threadIdx.x] = 0;
 	k2a_tables(sh);
-	K2aPre<1> pre;
-	pre.loaded = false;
-	pre.tiles = 0;
 	const bool prof = p.dbg && threadIdx.x == 0 && (blockIdx.x & 7) == 0;
 	const long long t0 = prof ? clock64() : 0;
 	for (unsigned k = blockIdx.x; k < nreg; k += gridDim.x) {
 		const int2 rg = regs[k];
-		const int2 rn = (k + gridDim.x < nreg) ? regs[k + gridDim.x] : make_int2(0, 0);
-		k2a_tile<1>(sh, p, sc, dec_base, dec_base + rg.x, rg.y, 0xfu, 0, 0, 0, nullptr, pre, dec_base + rn.x, rn.y, skip_r, skip_par);
+		k2a_tile<1>(sh, p, sc, dec_base, dec_base + rg.x, rg.y, 0xfu, 0, 0, 0, nullptr, skip_r, skip_par);
 		if (prof)
 			sh.prof[15] += (unsigned long long)rg.y;	/* instants */
 	}
@@ -1401,9 +1268,6 @@ void k2a_verify(K2Params p)
 		return;
 	int c_end = a + q < T ? a + q : T;
 	k2a_tables(sh);
-	K2aPre<2> pre;
-	pre.loaded = false;
-	pre.tiles = 0;
 	int b = a + K2A_VITEMS < c_end ? a + K2A_VITEMS : c_end;
 	k2a_vitems<true>(segs, nseg, p_lo, t_end, a, b, lo0, hi0, r0, n0, s_w, s_item);
 	for (;;) {
@@ -1412,9 +1276,8 @@ void k2a_verify(K2Params p)
 			atomicAdd(p.dbg + 30, (unsigned long long)((s_item[tid].y - s_item[tid].x + 1) / 2));
 		for (int i = 0; i < ni; ++i) {
 			const int4 it = s_item[i];
-			const int4 nx = (i + 1 < ni) ? s_item[i + 1] : make_int4(0, 0, 0, 0);
 			k2a_tile<2>(sh, p, sc, dec_base, dec_base + it.x, (it.y - it.x + 1) / 2, 1u << it.z, 1, dec_base + it.x, dec_base + it.y,
-				    p.fail + sc, pre, dec_base + nx.x, (nx.y - nx.x + 1) / 2);
+				    p.fail + sc);
 		}
 		a = b;
 		if (a >= c_end) {

@@ -132,7 +132,8 @@ struct K1PParams {		/* k1_pp: whole periods (PER = 4*SDRCLK inputs = 84 outputs)
 	int ph0;		/* LO index of a period's first sample */
 	int d;			/* samples between the 16-byte boundary below a period's first sample and that sample */
 	int fast_div;		/* both window lengths are in the set the reciprocal division is proven exact for */
-	int dbg;		/* development: 1 = no mixing, 2 = no sample loads after the first chunk, 4 = no stores */
+	int unused0;		/* (0; held development switches.  It keeps its place: with the members behind it four or eight bytes lower the
+				 * compiler groups the k1_pp kernels' kernarg loads differently and allots them other registers) */
 	int nf_lo;		/* the shorter of the two window lengths; rcp_lo = RN(1/nf_lo), rcp_hi = RN(1/(nf_lo+1)) */
 	float rcp_lo, rcp_hi;
 	int per_n;
@@ -233,7 +234,7 @@ struct K2Params {
 	int surv_pch, surv_nwg;	/* items a private area holds (a multiple of 256), scan workgroups per channel (= private areas) */
 	int surv_common_cap;	/* test hook: the common area holds only so many items (0: all that is left of the list) */
 	int surv_slot;		/* which of the push's scans this is: its item counters are ctl[CTL_NSURV0 + slot * S*8 ...] (VDL2_SURV_*) */
-	int surv_mode;		/* sparse stages: what a detector hit among the survivors means (k2a_emit: 0 candidates, 1 verify, 2 probe, 3 seeds; host side: SURV_*) */
+	int surv_mode;		/* sparse stages: what a detector hit among the survivors means (k2a_emit: 0 candidates, 1 verify, 2 probe; host side: SURV_*) */
 	int surv_skip;		/* sparse stages: hits in the probe's class are in the table already (region scan) */
 	/* the one-workgroup-per-channel kernel behind a scan drains that scan's common area first (k2x_drain): which scan, and how its list was laid out */
 	int drain_slot;		/* VDL2_SURV_* of the scan in front of this launch, -1: nothing to drain */
