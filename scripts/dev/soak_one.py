@@ -73,10 +73,10 @@ with Receiver(rate, plan_channels(FC, fos), fmt=fmt, max_push=max(block, 1 << 16
                 base = 84000 * (s0 // 1) // rate * 0      # (printed relative: nrel is relative to the push's dec_base)
                 print("   cands of chn", ch, "after push", i, ":", len(cd))
                 for k in range(len(cd)):
-                    print("      #%d nrel %d r %d  p2err/perr/err bits %08x %08x %08x  head x %d y %08x (status %d r_s %d ns %d)" % (
+                    print("      #%d nrel %d r %d  p2err/perr/err bits %08x %08x %08x  head x %d y %08x (status %d r_s %d ns %d)" % ((
                         k, cd[k][0], cd[k][1], int(cd[k][2]) & 0xffffffff, int(cd[k][3]) & 0xffffffff, int(cd[k][4]) & 0xffffffff,
-                        hd[k][0] if k < len(hd) else -1, (int(hd[k][1]) & 0xffffffff) if k < len(hd) else 0,
-                        (int(hd[k][1]) & 3) if k < len(hd) else -1, ((int(hd[k][1]) >> 2) & 3) if k < len(hd) else -1, ((int(hd[k][1]) >> 4) & 15) if k < len(hd) else -1))
+                        hd[k][0] if k < len(hd) else -1, (int(hd[k][1]) & 0xffffffff) if k < len(hd) else 0)
+                        + (_lib.cl_unpack(hd[k][1])[:3] if k < len(hd) else (-1, -1, -1))))
     else:
         bl = list(rx.run(raw, block=block))
     st = rx.stats()

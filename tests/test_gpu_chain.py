@@ -36,8 +36,8 @@ def _env(monkeypatch, path):
 
 def _heads(rx):
     """[(status, slots, bursts)] of the last push's clusters"""
-    packed = rx.debug_clheads(0, 0)[:, 1].astype(np.int64) & 0xffffffff
-    return [(int(p & 3), int(p >> 4 & 15), int(p >> 24 & 255)) for p in packed]
+    heads = [lib.cl_unpack(p) for p in rx.debug_clheads(0, 0)[:, 1]]
+    return [(status, nslots, nburst) for status, _, nslots, _, _, nburst in heads]
 
 
 def _check_heads(name, heads):

@@ -173,7 +173,6 @@ __device__ __forceinline__ void burst_levels(vdl2gpu_level_t *lev, const float2 
 /* sph: optional LDS buffer of VDL2_MAXSYM floats.  With it every symbol phase is computed once by
  * one lane and the byte lanes read them from LDS; without it (serial stretches of the resolver, which
  * have no LDS to spare) each byte lane computes the four or five phases it needs itself. */
-#define VDL2_MAXSYM 5456	/* symbols 7 .. (25 + 8 * 2040 - 1) / 3 */
 /* (inlined: as a call it costs the resolver and the gather kernel 8 % -- callee-saved registers through scratch) */
 /* TAB (K2d): sph, lds_tabs and pn8 are all there -- a compile-time fact, so that the kernel does not carry the other paths' code and
  * their scalar-register appetite (with run-time tests the compiler loaded all of mflt[] into 65 scalar registers for the path K2d never
@@ -339,7 +338,6 @@ struct MachCtx {
 	unsigned dyn_base;	/* first dynamic descriptor slot */
 	long long desc_static;	/* >= 0: descriptor slots are desc_static + burst index (K2b: no atomics) */
 	int sc;
-	unsigned long long *dbg;
 	HeadTap *headtap;	/* diagnostics, see K2Params */
 	unsigned *headtap_n;
 	unsigned headtap_cap;
@@ -457,6 +455,32 @@ template <int NT> __device__ __forceinline__ void mach_store(const MachSharedT<N
 		cs->perr = sh.errs[1];
 		cs->pfr = sh.frs[0];
 	}
+}
+
+__device__ __forceinline__ void mach_out_clear(MachOut &out)
+{
+	out.nslots = out.ntrig = out.nrej = out.nburst = out.ndefer = 0;
+	out.badslot = 0;
+	out.neval = 0;
+}
+
+/* where a channel state stands (its ring and errors: mach_load) */
+__device__ __forceinline__ MachState mach_state(const ChanState *cs) { return MachState{cs->pos, cs->r, cs->fresh}; }
+
+/* go on from the explicit state a CL_NONSTEADY cluster stopped in: history-dependent whatever it says, the serial machine takes it from here */
+template <int NT> __device__ __forceinline__ void mach_resume(MachSharedT<NT> &sh, MachState &st, const ChanState *saved)
+{
+	mach_load(sh, saved);
+	st = mach_state(saved);
+	st.fresh = st.fresh < VDL2_STEADY ? st.fresh : VDL2_STEADY - 1;
+}
+
+/* idle to the end of the data: next evaluation is the first one past it */
+__device__ __forceinline__ void mach_idle_to_end(const MachCtx &cx, MachState &st)
+{
+	const long long rem = (cx.avail_end - st.pos + 1) / 2;
+	if (rem > 0)
+		st.pos += 2 * rem;
 }
 
 /* shift the phase ring: new ring = pbuf[from .. from+67] (all threads call) */
@@ -668,17 +692,7 @@ template <int NT, bool XL> __device__ __forceinline__ MachTrig mach_trigger(Mach
 				defer = true;
 		}
 	}
-	MachTrig tg;
-	tg.nsym0 = nsym0;
-	tg.df = df;
-	tg.clk0 = clk0;
-	tg.rb = rb;
-	tg.accepted = accepted;
-	tg.nbrow = nbrow;
-	tg.nlbyte = nlbyte;
-	tg.nsym = nsym;
-	tg.defer = defer;
-	return tg;
+	return MachTrig{nsym0, df, clk0, rb, accepted, nbrow, nlbyte, nsym, defer};
 }
 
 /* What a trigger that is not deferred leaves behind: counters and, for an accepted header, the burst's
@@ -712,15 +726,7 @@ template <int NT, bool XL> __device__ __forceinline__ long long mach_commit_trig
 				atomicAdd(cx.rec_ovf, 1u);
 				slot = 0xffffffffu;
 			} else if (cx.desc) {
-				BurstDesc d;
-				d.nstar = nstar;
-				d.sc = cx.sc;
-				d.clk0 = clk0;
-				d.df = df;
-				d.nbrow = nbrow;
-				d.nlbyte = nlbyte;
-				d.pad = 0;
-				cx.desc[slot] = d;
+				cx.desc[slot] = BurstDesc{nstar, cx.sc, clk0, df, nbrow, nlbyte, 0};
 				if (cx.sel) {
 					const unsigned q = atomicAdd(cx.nsel, 1u);
 					if (q < VDL2_SEL_CAP)
@@ -848,7 +854,6 @@ __device__ __forceinline__ void mach_ctx(MachCtx &cx, const K2Params &p, int s, 
 	cx.avail_end = p.dec_base + VDL2_CARRY_FRAMES + p.J;
 	cx.pn = p.pn;
 	cx.sc = s * VDL2_CS + c;
-	cx.dbg = to_stage ? p.dbg : nullptr;
 	cx.headtap = p.headtap;
 	cx.headtap_n = p.headtap_n;
 	cx.headtap_cap = p.headtap_cap;

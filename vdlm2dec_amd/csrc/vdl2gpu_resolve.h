@@ -227,16 +227,11 @@ void k2b_clusters(K2Params p)
 		mach_ctx(cx, p, s, c, true);
 		const Cand cd = p.cands[(size_t)sc * VDL2_CAND_CAP + idx];
 		Cluster *cl = p.clusters + (size_t)sc * VDL2_CAND_CAP + idx;
-		MachState st;
-		st.pos = cx.dec_base + cd.nrel;
-		st.r = cd.r;
-		st.fresh = VDL2_STEADY;
+		MachState st = {cx.dec_base + cd.nrel, cd.r, VDL2_STEADY};
 		cx.grey = sgrey;
 		cx.desc_static = ((long long)sc * VDL2_CAND_CAP + idx) * VDL2_CL_MAXB;
 		MachOut out;
-		out.nslots = out.ntrig = out.nrej = out.nburst = out.ndefer = 0;
-		out.neval = 0;
-		out.badslot = 0;
+		mach_out_clear(out);
 		/* The candidate record holds what the detector saw when it fired -- the three fit errors and
 		 * the slope (the scan computed them with the detector's own arithmetic) --, so the trigger is
 		 * handled from those; what has to be rebuilt is the phase ring the detector returns to after
@@ -305,18 +300,14 @@ void k2b_clusters(K2Params p)
 }
 
 /* ====================================================================== K2c
- * Resolver: one workgroup per VDL channel follows the real chain of events.
- * While the detector is history-free the next event is simply the first
- * candidate of the current (sub-phase, sample parity) at or after `pos`, and
- * its consequences were precomputed by K2b; otherwise the serial machine runs
- * until the detector is history-free again.
- *   1. rank-sort the channel's candidates by time                 (parallel)
- *   2. for every candidate: status + index of the candidate that  (parallel)
- *      follows its cluster  -> successor table in LDS
- *   3. walk the chain through the successor table                 (one lane, LDS only)
- *   4. mark the staged bursts of the visited clusters, add counters (parallel)
+ * Resolver: one workgroup per VDL channel follows the real chain of events.  While the detector is history-free the next event is
+ * simply the first candidate of the current (sub-phase, sample parity) at or after `pos`, and its consequences were precomputed by
+ * K2b; otherwise the serial machine runs until the detector is history-free again.
+ *   1.  the candidates as K2s sorted them, their ranks class by class (k2c_class_lists)                            (parallel)
+ *   2.  for every candidate the one that follows its cluster, then four hops deep (k2c_successors, k2c_four_hops)  (parallel)
+ *   3.  walk the chain through that table (k2c_walk)                                                  (one lane, LDS only)
+ *   4.  list the bursts of the visited clusters, add their counters (k2c_publish)                                  (parallel)
  */
-#define K2C_NOCAND 0xffffu
 
 /* first sorted candidate at/after stream-relative time `want` of class (r, parity of want): a binary
  * search in that class's own list (ranks in time order, ascending), -1 if there is none.  (Scanning
@@ -350,184 +341,170 @@ __device__ __forceinline__ int k2c_next(const int *skey, const unsigned short *c
 #define K2C_J_SPECIAL 0x40000000u
 static_assert(VDL2_CAND_CAP <= 8191, "a hop holds a 13-bit rank");
 
-__global__ __launch_bounds__(K2_NT)
-void k2c_resolve(K2Params p)
+/* ---- steps of following the chain that K2c, K2p, K2f and K2d share */
+/* The push's mask of channels a repair round re-resolved or K2f redid serially (K2Params.fmask, a bit per channel slot below 512).
+ * If K2d ran ahead on the first pass's selection, what it made of such a channel is void (K2d's second pass tags those records 2:
+ * the host and K4 drop them) and K2d decodes the repaired selection in that second pass. */
+__device__ __forceinline__ void k2_fmask_set(const K2Params &p, int sc)
 {
-	__shared__ MachSharedT<K2_NT> sh;
-	__shared__ int skey[VDL2_CAND_CAP];		/* sorted keys: nrel*4 + r */
-	/* (sorted rank -> candidate index is read from device memory where it is needed -- publishing: a lane each --, and the rank of the
-	 * candidate that follows a cluster is the first hop of swalk[]: 23 bytes of LDS per candidate, the tables hold 6144) */
-	__shared__ uint8_t sstat[VDL2_CAND_CAP];	/* cluster status | sub-phase the idle search resumes in << 2 (bits 0-3 of the cluster's head) */
-	__shared__ unsigned short svis[K2C_VIS];	/* what the real chain visited: rank | 0x8000 = that cluster; rank = the steady
-							 * hops of swalk[rank] */
-	__shared__ unsigned sjump[VDL2_CAND_CAP];	/* the walk's view of swalk[]: see K2C_J_* */
-	__shared__ int sx[VDL2_CAND_CAP];		/* where the idle search resumes behind every candidate's cluster (cl_pack().x), by sorted rank; the
-							 * rest of the head is read from device memory where it is needed (publishing: every lane its own) --
-							 * together with the notes at the top: 23 bytes of LDS per candidate instead of 35 */
-	__shared__ int s_walk[4];
-	__shared__ int s_cnt[4];
-	__shared__ unsigned short clist[VDL2_CAND_CAP];	/* ranks of the candidates, class by class, time order within */
-	__shared__ unsigned long long swalk[VDL2_CAND_CAP];	/* the next four hops from a steady cluster: what the walk reads */
-	unsigned short *const sw16 = reinterpret_cast<unsigned short *>(swalk);	/* (hop i of rank j: sw16[4 j + i]) */
-	__shared__ int coff[9];				/* where each class (r * 2 + time parity) starts in clist */
-	__shared__ int s_wcnt[K2_NT / 64][8];
-#ifndef K2C_PRIO
-#define K2C_PRIO 3
-#endif
-	__builtin_amdgcn_s_setprio(K2C_PRIO);	/* one workgroup per channel beside the channeliser's thousands of waves */
-	const int tid = threadIdx.x;
-	const int c = blockIdx.x, s = (int)blockIdx.y;
-	const int sc = s * VDL2_CS + c;
-	int seg_from = -0x7fffffff;	/* repair round: stretches that end at or before the earliest event the verify pass found lie on the unchanged
-					 * part of the chain and have been verified -- only what lies behind is listed again */
-	if (p.round > 0) {
-		const int fail_in = p.fail[sc];
-		if (fail_in >= VDL2_VERIFIED)
-			return;		/* verified in the first pass: nothing to repair */
-		seg_from = fail_in;
-		__syncthreads();
-		if (tid == 0) {
-			p.redo[sc] = 1;
-			atomicAdd(p.outc_total_redo + 1, 1u);	/* channel-pushes that went through a repair round */
-			if (p.dbg)
-				atomicAdd(p.dbg + 24, 1ull);
-			p.fail[sc] = 0x7f7f7f7f;	/* the repair pass is verified afresh */
-			p.ctl[CTL_NSEL1 + sc] = 0;	/* (the repair rounds' own selection: see CTL_NSEL1) */
-			p.ctl[CTL_NSEG0 + sc] = 0;
-			p.ctl[CTL_NWIN0 + sc] = VDL2_WIN_ALL;	/* resolved again from the input state: nothing of the first selection stands */
-			/* if K2d ran ahead on the first pass's selection, what it made of this channel is void (K2d's second pass tags
-			 * those records 2: the host and K4 drop them) and K2d decodes the repaired selection in that second pass */
-			if (p.fmask && sc < 512)
-				atomicOr(p.fmask + (sc >> 5), 1u << (sc & 31));
-		}
-		__syncthreads();
+	if (p.fmask && sc < 512)
+		atomicOr(p.fmask + (sc >> 5), 1u << (sc & 31));
+}
+
+__device__ __forceinline__ bool k2_fmask_test(const K2Params &p, int sc) { return sc < 512 && (p.fmask[sc >> 5] >> (sc & 31) & 1u); }
+
+/* thread 0 of a repair round's workgroup: channel sc is resolved again.  nwin0 (CTL_NWIN0): what that makes void of the first selection
+ * before the round has listed any window -- all of it where the channel is resolved again from its input state, nothing in a local repair */
+__device__ __forceinline__ void k2_begin_repair(const K2Params &p, int sc, unsigned nwin0)
+{
+	p.redo[sc] = 1;
+	atomicAdd(p.outc_total_redo + 1, 1u);	/* channel-pushes that went through a repair round */
+	if (p.dbg)
+		atomicAdd(p.dbg + 24, 1ull);
+	p.ctl[CTL_NSEL1 + sc] = 0;	/* (the repair rounds' own selection: see CTL_NSEL1) */
+	p.ctl[CTL_NSEG0 + sc] = 0;
+	p.ctl[CTL_NWIN0 + sc] = nwin0;
+	k2_fmask_set(p, sc);
+}
+
+/* is stream-relative time t inside one of the nwin windows a local repair listed (K2Params.win) */
+__device__ __forceinline__ bool k2_in_windows(const int2 *win, unsigned nwin, long long t)
+{
+	bool in = false;
+	for (unsigned w = 0; w < nwin && w < VDL2_WIN_CAP; ++w)
+		in = in || (t >= win[w].x && t < win[w].y);
+	return in;
+}
+
+/* the chain idles in class (r, parity of lo) over stream-relative [lo, hi) and the probe did not scan that class: entry q of the
+ * channel's list of stretches the verify pass must confirm empty.  false: the list is full and the caller fails the channel.
+ * (K2c's two lists; k2p_patch, whose every lane counts the entries and lane 0 stores them, has the same lines written out: as a
+ * call of this the kernel spills three scalar registers fewer, and its resource line is held where it was measured.) */
+__device__ __forceinline__ bool k2_emit_seg(Seg *segs, unsigned q, int lo, int hi, int r)
+{
+	if (q >= VDL2_SEG_CAP)
+		return false;
+	segs[q] = Seg{lo, hi, r, 0};
+	return true;
+}
+
+/* the ns > 0 bursts of a cluster K2b made go to the end of a selection list of length *nsel (K2c publishing: an LDS copy of it): static
+ * descriptor slots, slot0 = (channel * VDL2_CAND_CAP + candidate index) * VDL2_CL_MAXB onwards; what the list does not hold is counted as dropped */
+template <class T> __device__ __forceinline__ void k2_select_slots(const K2Params &p, unsigned *sel, T *nsel, unsigned slot0, int ns)
+{
+	const unsigned q = (unsigned)atomicAdd(nsel, (T)ns);
+	for (int i = 0; i < ns; ++i) {
+		if (q + i < VDL2_SEL_CAP)
+			sel[q + i] = slot0 + i;
+		else
+			atomicAdd(p.outc + 1, 1u);
 	}
-	const ChanState *cs = p.cs + sc;	/* input state: left untouched until K2f commits */
-	ChanState *cs_out = p.cs_out + sc;
-	unsigned *sel = (p.round > 0 ? p.sel_list2 : p.sel_list) + (size_t)sc * VDL2_SEL_CAP;
-	unsigned *nsel = p.ctl + (p.round > 0 ? CTL_NSEL1 : CTL_NSEL0) + sc;
-	Seg *segs = p.segs + (size_t)sc * VDL2_SEG_CAP;
-	unsigned *nseg = p.ctl + CTL_NSEG0 + sc;
-	MachCtx cx;
-	mach_ctx(cx, p, s, c, true);	/* bursts of serial stretches become descriptors too */
-	cx.sel = sel;
-	cx.nsel = nsel;
-	cx.dbg = nullptr;
-	MachState st;
-	st.pos = cs->pos;
-	st.r = cs->r;
-	st.fresh = cs->fresh;
-	const int r_probe = p.probe_r, par_probe = p.probe_par;	/* the probe scanned class (r_probe, instants of parity par_probe) everywhere */
-	const int t_end = (int)(cx.avail_end - cx.dec_base);
-	const bool lazy = !p.full_scan && !p.full_round;	/* (a full round's tables hold every class: nothing is left to verify) */
-	mach_init_taps(sh);
-	mach_load(sh, cs);
-	MachOut out;
-	out.nslots = out.ntrig = out.nrej = out.nburst = out.ndefer = 0;
-	out.badslot = 0;
-	out.neval = 0;
-	unsigned long long n_slow = 0;
-	int ncand = (int)p.ctl[CTL_CAND0 + sc];
-	const bool tables_ok = !p.force_serial && ncand <= VDL2_CAND_CAP && p.ctl[CTL_CAND0 + p.nstreams * VDL2_CS + sc] == 0;
-	if (!tables_ok)
-		ncand = 0;
-	const Cluster *clusters = p.clusters + (size_t)sc * VDL2_CAND_CAP;
-	/* What a local repair (k2p_patch) needs of this pass: which candidates the chain met in the history-free state (a repaired
-	 * stretch that arrives at one of them has rejoined this chain), and what the serial stretches counted (no cluster head has it). */
-	uint8_t *const onchain = p.onchain + (size_t)sc * VDL2_CAND_CAP;
-	K2Slog *const slog = p.slog + (size_t)sc * VDL2_SLOG_CAP;
-	int nslog = 0;
-	const bool first_pass = p.round == 0;
-	if (first_pass)
-		for (int i = tid; i < (ncand + 3) / 4; i += K2_NT)
-			reinterpret_cast<uint32_t *>(onchain)[i] = 0u;
-	/* 1. candidates sorted by time (K2s) */
-	const long long pos_in = st.pos;
-	const long long tk0 = wall_clock64();
-	{
-		const int2 *head = p.clhead + (size_t)sc * VDL2_CAND_CAP;
-		for (int i = tid; i < ncand; i += K2_NT) {
-			const int idx = p.sidx[(size_t)sc * VDL2_CAND_CAP + i];
-			skey[i] = p.skey[(size_t)sc * VDL2_CAND_CAP + i];
-			const int2 hd = head[idx];
-			sx[i] = hd.x;
-			sstat[i] = (uint8_t)(hd.y & 15);
-		}
-	}
-	__syncthreads();
-	/* 1b. the class lists, a counting sort that keeps the time order: every thread counts the classes in
-	 *     its own contiguous stretch of the sorted list, an exclusive scan over (class, thread) turns the
-	 *     counts into positions, and the thread places its stretch */
-	{
-		const int per = (ncand + K2_NT - 1) / K2_NT;
-		const int j0 = tid * per < ncand ? tid * per : ncand, j1 = j0 + per < ncand ? j0 + per : ncand;
-		int cnt[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-		for (int j = j0; j < j1; ++j) {
-			const int k = skey[j], cls = (k & 3) * 2 + ((k >> 2) & 1);
-#pragma unroll
-			for (int q = 0; q < 8; ++q)
-				cnt[q] += (cls == q);
-		}
-		const int wave = tid >> 6, lane = tid & 63;
-		int excl[8];
-#pragma unroll
-		for (int q = 0; q < 8; ++q) {
-			int v = cnt[q];
-			for (int d = 1; d < 64; d <<= 1) {
-				const int o = __shfl_up(v, d, 64);
-				if (lane >= d)
-					v += o;
-			}
-			excl[q] = v - cnt[q];
-			if (lane == 63)
-				s_wcnt[wave][q] = v;
-		}
-		__syncthreads();
-		if (tid == 0) {
-			int acc = 0;
-			for (int q = 0; q < 8; ++q) {
-				coff[q] = acc;
-				for (int w = 0; w < K2_NT / 64; ++w) {
-					const int v = s_wcnt[w][q];
-					s_wcnt[w][q] = acc;	/* where wave w's share of class q starts */
-					acc += v;
-				}
-			}
-			coff[8] = acc;
-		}
-		__syncthreads();
+}
+
+/* the class (r, parity of STREAM time pos: a push's time base may be odd) is one the probe did not scan everywhere */
+__device__ __forceinline__ bool k2_unprobed(const K2Params &p, int r, long long pos) { return r != p.probe_r || (int)(pos & 1) != p.probe_par; }
+
+/* The resolver's tables in LDS: 23 bytes per candidate, the tables hold 6144.  (Sorted rank -> candidate index is read from device
+ * memory where it is needed -- publishing: a lane each --, and the rank of the candidate that follows a cluster is the first hop of
+ * swalk[].)  The arrays are __shared__ variables of k2c_resolve, each one of its own, and this struct refers to them: as members of
+ * one LDS struct the compiler aligns them to their element and unrolls the loops over them less (fewer registers, other
+ * instruction counts than the kernel has been measured with: DESIGN.md 8). */
+struct K2cShared {
+	int (&skey)[VDL2_CAND_CAP];		/* sorted keys: nrel*4 + r */
+	uint8_t (&sstat)[VDL2_CAND_CAP];	/* cl_stat4() of every cluster's head */
+	unsigned short (&svis)[K2C_VIS];	/* what the real chain visited: rank | 0x8000 = that cluster; rank = the steady hops of swalk[rank] */
+	unsigned (&sjump)[VDL2_CAND_CAP];	/* the walk's view of swalk[]: see K2C_J_* */
+	int (&sx)[VDL2_CAND_CAP];		/* where the idle search resumes behind every candidate's cluster (cl_pack().x), by sorted rank; the rest
+						 * of the head is read from device memory where it is needed (publishing: every lane its own) */
+	int (&walk)[4];				/* lane 0's walk to everybody: see k2c_walk; publishing: list positions, visited entries */
+	int (&cnt)[4];				/* what the visited clusters counted: triggers, rejects, bursts */
+	unsigned short (&clist)[VDL2_CAND_CAP];	/* ranks of the candidates, class by class, time order within */
+	unsigned long long (&swalk)[VDL2_CAND_CAP];	/* the next four hops from a steady cluster: what the walk reads */
+	int (&coff)[9];				/* where each class (r * 2 + time parity) starts in clist */
+	int (&wcnt)[K2_NT / 64][8];
+};
+
+/* 1b. the class lists, a counting sort that keeps the time order: every thread counts the classes in
+ *     its own contiguous stretch of the sorted list, an exclusive scan over (class, thread) turns the
+ *     counts into positions, and the thread places its stretch */
+__device__ __forceinline__ void k2c_class_lists(const K2cShared &ks, int tid, int ncand)
+{
+	const int per = (ncand + K2_NT - 1) / K2_NT;
+	const int j0 = tid * per < ncand ? tid * per : ncand, j1 = j0 + per < ncand ? j0 + per : ncand;
+	int cnt[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+	for (int j = j0; j < j1; ++j) {
+		const int k = ks.skey[j], cls = (k & 3) * 2 + ((k >> 2) & 1);
 #pragma unroll
 		for (int q = 0; q < 8; ++q)
-			excl[q] += s_wcnt[wave][q];
-		for (int j = j0; j < j1; ++j) {
-			const int k = skey[j], cls = (k & 3) * 2 + ((k >> 2) & 1);
-			int at = 0;
-#pragma unroll
-			for (int q = 0; q < 8; ++q)
-				if (cls == q)
-					at = excl[q]++;
-			clist[at] = (unsigned short)j;
-		}
-		__syncthreads();
+			cnt[q] += (cls == q);
 	}
-	const long long tk1 = wall_clock64();
-	/* 2. successor table.  (Interleaving several searches per thread to overlap their LDS round trips
-	 *    was slower: this kernel, with two serial machines inlined, has no registers to spare.) */
-	for (int j = tid; j < ncand; j += K2_NT) {
-		const int status = sstat[j] & 3;
-		int nx = -1;
-		if (status == CL_STEADY)
-			nx = k2c_next(skey, clist, coff, sx[j], (sstat[j] >> 2) & 3);	/* sx[j] lies behind the candidate's own time */
-		/* the first hop: rank of the candidate that follows the cluster | that one's status (the other three: 2b) */
-		sw16[4 * j] = (nx < 0) ? (unsigned short)K2C_HOP_NONE : (unsigned short)((unsigned)nx | ((sstat[nx] & 3u) << K2C_RBITS));
+	const int wave = tid >> 6, lane = tid & 63;
+	int excl[8];
+#pragma unroll
+	for (int q = 0; q < 8; ++q) {
+		int v = cnt[q];
+		for (int d = 1; d < 64; d <<= 1) {
+			const int o = __shfl_up(v, d, 64);
+			if (lane >= d)
+				v += o;
+		}
+		excl[q] = v - cnt[q];
+		if (lane == 63)
+			ks.wcnt[wave][q] = v;
 	}
 	__syncthreads();
-	/* 2b. four hops per table entry: the walk below is one lane chasing pointers through LDS, a round
-	 *     trip per read, so it reads as rarely as possible */
+	if (tid == 0) {
+		int acc = 0;
+		for (int q = 0; q < 8; ++q) {
+			ks.coff[q] = acc;
+			for (int w = 0; w < K2_NT / 64; ++w) {
+				const int v = ks.wcnt[w][q];
+				ks.wcnt[w][q] = acc;	/* where wave w's share of class q starts */
+				acc += v;
+			}
+		}
+		ks.coff[8] = acc;
+	}
+	__syncthreads();
+#pragma unroll
+	for (int q = 0; q < 8; ++q)
+		excl[q] += ks.wcnt[wave][q];
+	for (int j = j0; j < j1; ++j) {
+		const int k = ks.skey[j], cls = (k & 3) * 2 + ((k >> 2) & 1);
+		int at = 0;
+#pragma unroll
+		for (int q = 0; q < 8; ++q)
+			if (cls == q)
+				at = excl[q]++;
+		ks.clist[at] = (unsigned short)j;
+	}
+	__syncthreads();
+}
+
+/* 2. successor table.  (Interleaving several searches per thread to overlap their LDS round trips
+ *    was slower: this kernel, with two serial machines inlined, has no registers to spare.) */
+__device__ __forceinline__ void k2c_successors(const K2cShared &ks, int tid, int ncand)
+{
+	unsigned short *const sw16 = reinterpret_cast<unsigned short *>(ks.swalk);	/* (hop i of rank j: sw16[4 j + i]) */
+	for (int j = tid; j < ncand; j += K2_NT) {
+		int nx = -1;
+		if (stat4_status(ks.sstat[j]) == CL_STEADY)
+			nx = k2c_next(ks.skey, ks.clist, ks.coff, ks.sx[j], stat4_r(ks.sstat[j]));	/* sx[j] lies behind the candidate's own time */
+		/* the first hop: rank of the candidate that follows the cluster | that one's status (the other three: 2b) */
+		sw16[4 * j] = (nx < 0) ? (unsigned short)K2C_HOP_NONE : (unsigned short)((unsigned)nx | ((unsigned)stat4_status(ks.sstat[nx]) << K2C_RBITS));
+	}
+	__syncthreads();
+}
+
+/* 2b. four hops per table entry: the walk is one lane chasing pointers through LDS, a round
+ *     trip per read, so it reads as rarely as possible */
+__device__ __forceinline__ void k2c_four_hops(const K2cShared &ks, int tid, int ncand)
+{
+	unsigned short *const sw16 = reinterpret_cast<unsigned short *>(ks.swalk);	/* (hop i of rank j: sw16[4 j + i]) */
 	for (int j = tid; j < ncand; j += K2_NT) {
 		unsigned jv = 0;
 		int at = j;
-		bool open = ((sstat[j] & 3) == CL_STEADY);
+		bool open = (stat4_status(ks.sstat[j]) == CL_STEADY);
 #pragma unroll
 		for (int i = 0; i < 4; ++i) {
 			unsigned hop = K2C_HOP_NONE;
@@ -545,9 +522,212 @@ void k2c_resolve(K2Params p)
 			if (!open && !(jv & K2C_J_SPECIAL) && hop != K2C_HOP_NONE)
 				jv |= K2C_J_SPECIAL | ((hop & K2C_RANK) << 16);
 		}
-		sjump[j] = jv | (unsigned)at | (open ? K2C_J_CONT : 0u);
+		ks.sjump[j] = jv | (unsigned)at | (open ? K2C_J_CONT : 0u);
 	}
 	__syncthreads();
+}
+
+/* 3. history-free at (st.pos, st.r): lane 0 walks the successor table until something special happens and leaves in ks.walk[]
+ *    [0] the candidate (rank) the chain has arrived at, -1: no more candidates; [1] the last steady cluster it went through, -1: none;
+ *    [2] 1 = the cluster at [0] is not a steady one.  nvis: slots of svis[] in use (lane 0's copy counts). */
+__device__ __forceinline__ void k2c_walk(const K2cShared &ks, const K2Params &p, int sc, const MachCtx &cx, const MachState &st, bool lazy, int seg_from, int &nvis)
+{
+	int cur = k2c_next(ks.skey, ks.clist, ks.coff, (int)(st.pos - cx.dec_base), st.r);
+	int last = -1, why = 0;	/* why: 0 = no more candidates, 1 = special cluster at cur */
+	if (lazy && k2_unprobed(p, st.r, st.pos)) {
+		/* the chain idles from here to the next candidate in a class the probe did not
+		 * scan: K2a-verify must confirm there really is nothing in between */
+		const int g_hi = (cur >= 0) ? (ks.skey[cur] >> 2) : (int)(cx.avail_end - cx.dec_base);
+		if (g_hi > seg_from && !k2_emit_seg(p.segs + (size_t)sc * VDL2_SEG_CAP, atomicAdd(p.ctl + CTL_NSEG0 + sc, 1u), (int)(st.pos - cx.dec_base), g_hi, st.r))
+			atomicMin(p.fail + sc, 0);
+	}
+	if (cur >= 0 && stat4_status(ks.sstat[cur]) != CL_STEADY)
+		why = 1;
+	else if (cur >= 0) {
+		/* A lone lane chasing pointers: a wavefront on its own issues an instruction every ~5
+		 * cycles, so the loop is four instructions and one LDS round trip per four clusters;
+		 * what was visited is worked out from the list afterwards, by everybody. */
+		if (nvis < K2C_VIS)
+			ks.svis[nvis] = (unsigned short)(cur | 0x8000);
+		++nvis;
+		last = cur;
+		unsigned v;
+		for (;;) {
+			v = ks.sjump[last];
+			if (nvis < K2C_VIS)
+				ks.svis[nvis] = (unsigned short)last;
+			++nvis;
+			if (!(v & K2C_J_CONT))
+				break;
+			last = (int)(v & K2C_RANK);
+		}
+		last = (int)(v & K2C_RANK);
+		if (v & K2C_J_SPECIAL) {
+			cur = (int)((v >> 16) & K2C_RANK);
+			why = 1;
+		} else
+			cur = -1;
+		if (nvis > K2C_VIS)
+			atomicMin(p.fail + sc, 0);
+	}
+	ks.walk[0] = cur;
+	ks.walk[1] = last;
+	ks.walk[2] = why;
+}
+
+/* 4. publish the visited clusters: list positions come from LDS counters seeded with what the
+ *    serial stretches and the walk already listed; the global counters are written once.  Behind it ks.cnt[0..2] hold what the
+ *    clusters counted (triggers, rejects, bursts) and ks.walk[3] the entries of the visited list. */
+__device__ __forceinline__ void k2c_publish(const K2cShared &ks, const K2Params &p, int sc, int tid, const MachCtx &cx, bool lazy, int seg_from, int nvis,
+					    bool tables_ok, int nslog)
+{
+	unsigned short *const sw16 = reinterpret_cast<unsigned short *>(ks.swalk);	/* (hop i of rank j: sw16[4 j + i]) */
+	const bool first_pass = p.round == 0;
+	const int t_end = (int)(cx.avail_end - cx.dec_base);
+	uint8_t *const onchain = p.onchain + (size_t)sc * VDL2_CAND_CAP;
+	Seg *segs = p.segs + (size_t)sc * VDL2_SEG_CAP;
+	unsigned *nseg = p.ctl + CTL_NSEG0 + sc;
+	if (tid < 4)
+		ks.cnt[tid] = 0;
+	if (tid == 0) {
+		ks.walk[0] = (int)*cx.nsel;
+		ks.walk[1] = (int)*nseg;
+		ks.walk[3] = nvis < K2C_VIS ? nvis : K2C_VIS;
+	}
+	__syncthreads();
+	int a = 0, b = 0, d = 0;
+	const int nv4 = ks.walk[3] * 4;
+	for (int t = tid; t < nv4; t += K2_NT) {
+		const unsigned ve = ks.svis[t >> 2];
+		int j = -1;
+		if (ve & 0x8000u)
+			j = (t & 3) == 0 ? (int)(ve & K2C_RANK) : -1;
+		else {
+			const unsigned hop = (unsigned)(ks.swalk[ve] >> (16 * (t & 3))) & 0xffffu;
+			if (hop != K2C_HOP_NONE && (hop >> K2C_RBITS) == CL_STEADY)
+				j = (int)(hop & K2C_RANK);
+		}
+		if (j >= 0) {
+			const unsigned gidx = p.sidx[(size_t)sc * VDL2_CAND_CAP + j];	/* (from device memory: a lane each, all in flight together) */
+			const int2 hd = p.clhead[(size_t)sc * VDL2_CAND_CAP + gidx];
+			if (first_pass)
+				onchain[gidx] = 1;	/* invariant (a) at CTL_NWIN0: exactly the clusters selected and counted here (and the k2c_resolve loop's) */
+			const unsigned hop0 = sw16[4 * j];
+			const int next_t = (hop0 == K2C_HOP_NONE) ? t_end : (ks.skey[hop0 & K2C_RANK] >> 2);	/* the successor's trigger, or the end of the data */
+			const int ns = cl_nslots(hd);
+			const unsigned slot0 = (unsigned)(((size_t)sc * VDL2_CAND_CAP + gidx) * VDL2_CL_MAXB);
+			if (ns)
+				k2_select_slots(p, cx.sel, &ks.walk[0], slot0, ns);
+			a += cl_ntrig(hd);
+			b += cl_nrej(hd);
+			d += cl_nburst(hd);
+			/* after a steady cluster the chain idles in class (r_s, parity of n_s) until
+			 * the successor's trigger (or the end of the data) */
+			if (lazy && stat4_status(ks.sstat[j]) == CL_STEADY && k2_unprobed(p, cl_r(hd), cx.dec_base + hd.x) && next_t > seg_from &&
+			    !k2_emit_seg(segs, (unsigned)atomicAdd(&ks.walk[1], 1), hd.x, next_t, cl_r(hd)))
+				atomicMin(p.fail + sc, 0);
+		}
+	}
+	if (a)
+		atomicAdd(&ks.cnt[0], a);
+	if (b)
+		atomicAdd(&ks.cnt[1], b);
+	if (d)
+		atomicAdd(&ks.cnt[2], d);
+	__syncthreads();
+	if (tid == 0) {
+		*cx.nsel = (unsigned)ks.walk[0];
+		*nseg = (unsigned)ks.walk[1];
+		/* the output records of the selected bursts, reserved in one piece: K2d's workgroups (one per burst) then need no
+		 * atomic of their own -- a thousand of them asking one device-scope counter for a slot at the same moment took 80 us,
+		 * more than decoding the bursts (the same effect as in k4_frames) */
+		/* Only the FIRST pass reserves here: every record it reserves is written (K2d's first pass decodes every channel's first
+		 * selection, void or not).  A repair round's selection may be superseded by the next round's or by K2f's serial redo --
+		 * records reserved for it would stay unwritten: whatever an earlier push left in the ring there would be handed out
+		 * as bursts [found by scripts/soak.py's dropped-region-scan modes: two rounds, or a round and a redo].  The repaired
+		 * selection's records are reserved by K2f, when it is final. */
+		if (ks.walk[0] > 0 && p.sel_reserved && p.round == 0)
+			p.ctl[CTL_SELBASE0 + sc] = atomicAdd(p.outc, (unsigned)ks.walk[0]);
+		if (first_pass)
+			p.ctl[CTL_NSLOG0 + sc] = (unsigned)(tables_ok ? nslog : VDL2_SLOG_CAP + 1);	/* (no tables: nothing a local repair could stand on) */
+	}
+	__syncthreads();
+}
+
+__global__ __launch_bounds__(K2_NT)
+void k2c_resolve(K2Params p)
+{
+	__shared__ MachSharedT<K2_NT> sh;
+	__shared__ int skey[VDL2_CAND_CAP], sx[VDL2_CAND_CAP], s_walk[4], s_cnt[4], coff[9], s_wcnt[K2_NT / 64][8];
+	__shared__ unsigned sjump[VDL2_CAND_CAP];
+	__shared__ unsigned long long swalk[VDL2_CAND_CAP];
+	__shared__ unsigned short svis[K2C_VIS], clist[VDL2_CAND_CAP];
+	__shared__ uint8_t sstat[VDL2_CAND_CAP];
+	const K2cShared ks = {skey, sstat, svis, sjump, sx, s_walk, s_cnt, clist, swalk, coff, s_wcnt};
+#ifndef K2C_PRIO
+#define K2C_PRIO 3
+#endif
+	__builtin_amdgcn_s_setprio(K2C_PRIO);	/* one workgroup per channel beside the channeliser's thousands of waves */
+	const int tid = threadIdx.x;
+	const int c = blockIdx.x, s = (int)blockIdx.y;
+	const int sc = s * VDL2_CS + c;
+	int seg_from = -0x7fffffff;	/* repair round: stretches that end at or before the earliest event the verify pass found lie on the unchanged
+					 * part of the chain and have been verified -- only what lies behind is listed again */
+	if (p.round > 0) {
+		const int fail_in = p.fail[sc];
+		if (fail_in >= VDL2_VERIFIED)
+			return;		/* verified in the first pass: nothing to repair */
+		seg_from = fail_in;
+		__syncthreads();
+		if (tid == 0) {
+			p.fail[sc] = 0x7f7f7f7f;	/* the repair pass is verified afresh */
+			k2_begin_repair(p, sc, VDL2_WIN_ALL);	/* resolved again from the input state: nothing of the first selection stands */
+		}
+		__syncthreads();
+	}
+	const ChanState *cs = p.cs + sc;	/* input state: left untouched until K2f commits */
+	ChanState *cs_out = p.cs_out + sc;
+	MachCtx cx;
+	mach_ctx(cx, p, s, c, true);	/* bursts of serial stretches become descriptors too */
+	cx.sel = (p.round > 0 ? p.sel_list2 : p.sel_list) + (size_t)sc * VDL2_SEL_CAP;
+	cx.nsel = p.ctl + (p.round > 0 ? CTL_NSEL1 : CTL_NSEL0) + sc;
+	MachState st = mach_state(cs);
+	const bool lazy = !p.full_scan && !p.full_round;	/* (a full round's tables hold every class: nothing is left to verify) */
+	mach_init_taps(sh);
+	mach_load(sh, cs);
+	MachOut out;
+	mach_out_clear(out);
+	unsigned long long n_slow = 0;
+	int ncand = (int)p.ctl[CTL_CAND0 + sc];
+	const bool tables_ok = !p.force_serial && ncand <= VDL2_CAND_CAP && p.ctl[CTL_CAND0 + p.nstreams * VDL2_CS + sc] == 0;
+	if (!tables_ok)
+		ncand = 0;
+	/* What a local repair (k2p_patch) needs of this pass: which candidates the chain met in the history-free state (a repaired
+	 * stretch that arrives at one of them has rejoined this chain), and what the serial stretches counted (no cluster head has it). */
+	uint8_t *const onchain = p.onchain + (size_t)sc * VDL2_CAND_CAP;
+	K2Slog *const slog = p.slog + (size_t)sc * VDL2_SLOG_CAP;
+	int nslog = 0;
+	const bool first_pass = p.round == 0;
+	if (first_pass)
+		for (int i = tid; i < (ncand + 3) / 4; i += K2_NT)
+			reinterpret_cast<uint32_t *>(onchain)[i] = 0u;
+	const long long pos_in = st.pos;
+	const long long tk0 = wall_clock64();
+	/* 1. the candidates as K2s sorted them by time, and of each one's cluster what the walk reads.  (Written here, on the arrays themselves:
+	 *    as a function on `ks` the compiler picks other induction variables for this loop and the kernel has one LDS store more.) */
+	const int2 *head = p.clhead + (size_t)sc * VDL2_CAND_CAP;
+	for (int i = tid; i < ncand; i += K2_NT) {
+		const int idx = p.sidx[(size_t)sc * VDL2_CAND_CAP + i];
+		skey[i] = p.skey[(size_t)sc * VDL2_CAND_CAP + i];
+		const int2 hd = head[idx];
+		sx[i] = hd.x;
+		sstat[i] = cl_stat4(hd);
+	}
+	__syncthreads();
+	k2c_class_lists(ks, tid, ncand);
+	const long long tk1 = wall_clock64();
+	k2c_successors(ks, tid, ncand);
+	k2c_four_hops(ks, tid, ncand);
 	const long long tk2 = wall_clock64();
 	bool steady_end = false;
 	int nvis = 0;	/* slots of svis[] in use (thread 0's copy counts) */
@@ -565,14 +745,8 @@ void k2c_resolve(K2Params p)
 			if (!replay)
 				n_slow += (unsigned long long)(st.pos - p0);
 			if (first_pass && tables_ok && (out.ntrig != c_trig || out.nrej != c_rej || out.nburst != c_burst)) {
-				if (tid == 0 && nslog < VDL2_SLOG_CAP) {
-					K2Slog g;
-					g.t = (int)(p0 - cx.dec_base);
-					g.ntrig = out.ntrig - c_trig;
-					g.nrej = out.nrej - c_rej;
-					g.nburst = out.nburst - c_burst;
-					slog[nslog] = g;
-				}
+				if (tid == 0 && nslog < VDL2_SLOG_CAP)
+					slog[nslog] = K2Slog{(int)(p0 - cx.dec_base), out.ntrig - c_trig, out.nrej - c_rej, out.nburst - c_burst};
 				++nslog;
 			}
 			replay = false;
@@ -580,78 +754,23 @@ void k2c_resolve(K2Params p)
 				break;
 			continue;
 		}
-		/* 3. history-free: walk the successor table until something special happens */
-		if (tid == 0) {
-			int cur = k2c_next(skey, clist, coff, (int)(st.pos - cx.dec_base), st.r);
-			int last = -1, why = 0;	/* why: 0 = no more candidates, 1 = special cluster at cur */
-			if (lazy && (st.r != r_probe || (int)(st.pos & 1) != par_probe)) {
-				/* the chain idles from here to the next candidate in a class the probe did not
-				 * scan: K2a-verify must confirm there really is nothing in between */
-				const int g_hi = (cur >= 0) ? (skey[cur] >> 2) : t_end;
-				if (g_hi > seg_from) {
-					const unsigned q = atomicAdd(nseg, 1u);
-					if (q < VDL2_SEG_CAP) {
-						Seg g;
-						g.lo = (int)(st.pos - cx.dec_base);
-						g.hi = g_hi;
-						g.r = st.r;
-						g.pad = 0;
-						segs[q] = g;
-					} else
-						atomicMin(p.fail + sc, 0);
-				}
-			}
-			if (cur >= 0 && (sstat[cur] & 3) != CL_STEADY)
-				why = 1;
-			else if (cur >= 0) {
-				/* A lone lane chasing pointers: a wavefront on its own issues an instruction every ~5
-				 * cycles, so the loop is four instructions and one LDS round trip per four clusters;
-				 * what was visited is worked out from the list afterwards, by everybody. */
-				if (nvis < K2C_VIS)
-					svis[nvis] = (unsigned short)(cur | 0x8000);
-				++nvis;
-				last = cur;
-				unsigned v;
-				for (;;) {
-					v = sjump[last];
-					if (nvis < K2C_VIS)
-						svis[nvis] = (unsigned short)last;
-					++nvis;
-					if (!(v & K2C_J_CONT))
-						break;
-					last = (int)(v & K2C_RANK);
-				}
-				last = (int)(v & K2C_RANK);
-				if (v & K2C_J_SPECIAL) {
-					cur = (int)((v >> 16) & K2C_RANK);
-					why = 1;
-				} else
-					cur = -1;
-				if (nvis > K2C_VIS)
-					atomicMin(p.fail + sc, 0);
-			}
-			s_walk[0] = cur;
-			s_walk[1] = last;
-			s_walk[2] = why;
-		}
+		if (tid == 0)	/* history-free */
+			k2c_walk(ks, p, sc, cx, st, lazy, seg_from, nvis);
 		__syncthreads();
-		const int cur = s_walk[0], last = s_walk[1], why = s_walk[2];
+		const int cur = ks.walk[0], last = ks.walk[1], why = ks.walk[2];
 		__syncthreads();
 		if (last >= 0) {
-			st.pos = cx.dec_base + sx[last];
-			st.r = (sstat[last] >> 2) & 3;
+			st.pos = cx.dec_base + ks.sx[last];
+			st.r = stat4_r(ks.sstat[last]);
 		}
 		if (!why) {
-			/* idle to the end of the data: next evaluation is the first one past it */
-			const long long rem = (cx.avail_end - st.pos + 1) / 2;
-			if (rem > 0)
-				st.pos += 2 * rem;
+			mach_idle_to_end(cx, st);
 			steady_end = true;
 			break;
 		}
-		const long long ncand_t = cx.dec_base + (skey[cur] >> 2);
-		const Cluster *cl = clusters + p.sidx[(size_t)sc * VDL2_CAND_CAP + cur];
-		const int status = sstat[cur] & 3;
+		const long long ncand_t = cx.dec_base + (ks.skey[cur] >> 2);
+		const Cluster *cl = p.clusters + (size_t)sc * VDL2_CAND_CAP + p.sidx[(size_t)sc * VDL2_CAND_CAP + cur];
+		const int status = stat4_status(ks.sstat[cur]);
 		if (first_pass && tid == 0)	/* (the chain met this candidate history-free too: whatever its cluster is, what follows is determined) */
 			onchain[p.sidx[(size_t)sc * VDL2_CAND_CAP + cur]] = 1;
 		if (status == CL_DEFER_FIRST) {
@@ -672,109 +791,18 @@ void k2c_resolve(K2Params p)
 		/* CL_NONSTEADY: its bursts count, then continue from the explicit state it stopped in */
 		if (tid == 0) {
 			if (nvis < K2C_VIS)
-				svis[nvis] = (unsigned short)(cur | 0x8000);
+				ks.svis[nvis] = (unsigned short)(cur | 0x8000);
 			else
 				atomicMin(p.fail + sc, 0);
 			++nvis;
 		}
 		if (tid == 0 && p.dbg)
 			atomicAdd(p.dbg + 26, 1ull);	/* non-steady clusters continued serially */
-		mach_load(sh, &cl->saved);
-		st.pos = cl->saved.pos;
-		st.r = cl->saved.r;
-		st.fresh = cl->saved.fresh < VDL2_STEADY ? cl->saved.fresh : VDL2_STEADY - 1;
+		mach_resume(sh, st, &cl->saved);
 	}
 	__syncthreads();
 	const long long tk3 = wall_clock64();
-	/* 4. publish the visited clusters: list positions come from LDS counters seeded with what the
-	 *    serial stretches and the walk already listed; the global counters are written once */
-	if (tid < 4)
-		s_cnt[tid] = 0;
-	if (tid == 0) {
-		s_walk[0] = (int)*nsel;
-		s_walk[1] = (int)*nseg;
-		s_walk[3] = nvis < K2C_VIS ? nvis : K2C_VIS;
-	}
-	__syncthreads();
-	{
-		int a = 0, b = 0, d = 0;
-		const int nv4 = s_walk[3] * 4;
-		for (int t = tid; t < nv4; t += K2_NT) {
-			const unsigned ve = svis[t >> 2];
-			int j = -1;
-			if (ve & 0x8000u)
-				j = (t & 3) == 0 ? (int)(ve & K2C_RANK) : -1;
-			else {
-				const unsigned hop = (unsigned)(swalk[ve] >> (16 * (t & 3))) & 0xffffu;
-				if (hop != K2C_HOP_NONE && (hop >> K2C_RBITS) == CL_STEADY)
-					j = (int)(hop & K2C_RANK);
-			}
-			if (j >= 0) {
-				const unsigned gidx = p.sidx[(size_t)sc * VDL2_CAND_CAP + j];	/* (from device memory: a lane each, all in flight together) */
-				const int2 hd = p.clhead[(size_t)sc * VDL2_CAND_CAP + gidx];
-				if (first_pass)
-					onchain[gidx] = 1;
-				const unsigned hop0 = sw16[4 * j];
-				const int next_t = (hop0 == K2C_HOP_NONE) ? t_end : (skey[hop0 & K2C_RANK] >> 2);	/* the successor's trigger, or the end of the data */
-				const int ns = (hd.y >> 4) & 15;
-				/* K2b's descriptors sit in static slots: (candidate index) * VDL2_CL_MAXB + burst */
-				const unsigned slot0 = (unsigned)(((size_t)sc * VDL2_CAND_CAP + gidx) * VDL2_CL_MAXB);
-				if (ns) {
-					const unsigned q = (unsigned)atomicAdd(&s_walk[0], ns);
-					for (int i = 0; i < ns; ++i) {
-						if (q + i < VDL2_SEL_CAP)
-							sel[q + i] = slot0 + i;
-						else
-							atomicAdd(p.outc + 1, 1u);
-					}
-				}
-				a += (hd.y >> 8) & 255;
-				b += (hd.y >> 16) & 255;
-				d += (hd.y >> 24) & 255;
-				const int r_s = (hd.y >> 2) & 3;
-				const long long n_s = cx.dec_base + hd.x;
-				if (lazy && (sstat[j] & 3) == CL_STEADY && (r_s != r_probe || (int)(n_s & 1) != par_probe) &&
-				    next_t > seg_from) {
-					/* after this cluster the chain idles in class (r_s, parity of n_s) until
-					 * the successor's trigger (or the end of the data) */
-					const unsigned q = (unsigned)atomicAdd(&s_walk[1], 1);
-					if (q < VDL2_SEG_CAP) {
-						Seg g;
-						g.lo = hd.x;
-						g.hi = next_t;
-						g.r = r_s;
-						g.pad = 0;
-						segs[q] = g;
-					} else
-						atomicMin(p.fail + sc, 0);
-				}
-			}
-		}
-		if (a)
-			atomicAdd(&s_cnt[0], a);
-		if (b)
-			atomicAdd(&s_cnt[1], b);
-		if (d)
-			atomicAdd(&s_cnt[2], d);
-	}
-	__syncthreads();
-	if (tid == 0) {
-		*nsel = (unsigned)s_walk[0];
-		*nseg = (unsigned)s_walk[1];
-		/* the output records of the selected bursts, reserved in one piece: K2d's workgroups (one per burst) then need no
-		 * atomic of their own -- a thousand of them asking one device-scope counter for a slot at the same moment took 80 us,
-		 * more than decoding the bursts (the same effect as in k4_frames) */
-		/* Only the FIRST pass reserves here: every record it reserves is written (K2d's first pass decodes every channel's first
-		 * selection, void or not).  A repair round's selection may be superseded by the next round's or by K2f's serial redo --
-		 * records reserved for it would stay unwritten: whatever an earlier push left in the ring there would be handed out
-		 * as bursts [found by scripts/soak.py's dropped-region-scan modes: two rounds, or a round and a redo].  The repaired
-		 * selection's records are reserved by K2f, when it is final. */
-		if (s_walk[0] > 0 && p.sel_reserved && p.round == 0)
-			p.ctl[CTL_SELBASE0 + sc] = atomicAdd(p.outc, (unsigned)s_walk[0]);
-		if (first_pass)
-			p.ctl[CTL_NSLOG0 + sc] = (unsigned)(tables_ok ? nslog : VDL2_SLOG_CAP + 1);	/* (no tables: nothing a local repair could stand on) */
-	}
-	__syncthreads();
+	k2c_publish(ks, p, sc, tid, cx, lazy, seg_from, nvis, tables_ok, nslog);
 	if (steady_end) {
 		mach_materialize<K2_NT, false>(sh, cx, st.pos, st.r);
 		st.fresh = VDL2_STEADY;
@@ -783,9 +811,9 @@ void k2c_resolve(K2Params p)
 	mach_store(sh, st, cs_out);
 	if (tid == 0) {
 		cs_out->n_eval = cs->n_eval + (unsigned long long)((st.pos - pos_in) / 2);	/* evaluation instants covered */
-		cs_out->n_trig = cs->n_trig + (unsigned long long)(out.ntrig + s_cnt[0]);
-		cs_out->n_reject = cs->n_reject + (unsigned long long)(out.nrej + s_cnt[1]);
-		cs_out->n_burst = cs->n_burst + (unsigned long long)(out.nburst + s_cnt[2]);
+		cs_out->n_trig = cs->n_trig + (unsigned long long)(out.ntrig + ks.cnt[0]);
+		cs_out->n_reject = cs->n_reject + (unsigned long long)(out.nrej + ks.cnt[1]);
+		cs_out->n_burst = cs->n_burst + (unsigned long long)(out.nburst + ks.cnt[2]);
 		cs_out->n_defer = cs->n_defer + (unsigned long long)out.ndefer;
 		cs_out->n_slow = cs->n_slow + n_slow;
 		cs_out->n_cand = cs->n_cand + (unsigned long long)ncand;
@@ -798,7 +826,7 @@ void k2c_resolve(K2Params p)
 			atomicAdd(p.dbg + 19, (unsigned long long)(tk4 - tk3));
 			atomicAdd(p.dbg + 20, 1ull);
 			atomicAdd(p.dbg + 27, (unsigned long long)ncand);
-			atomicAdd(p.dbg + 28, (unsigned long long)s_walk[3]);	/* visited-list entries */
+			atomicAdd(p.dbg + 28, (unsigned long long)ks.walk[3]);	/* visited-list entries */
 			atomicAdd(p.dbg + 29, n_slow);
 		}
 	}
@@ -863,13 +891,14 @@ __device__ __forceinline__ int k2p_lower_bound(const int *skey, int n, int key)
 	return lo;
 }
 
-/* first rank >= from of the sorted table with time >= want in class cls (sub-phase * 2 + parity of the time); n if none */
-__device__ __forceinline__ int k2p_next_old(const int *skey, int from, int n, int want, int cls)
+/* first entry >= from of a list of n keys (key_at(j) = nrel * 4 + r, ascending) with time >= want in class cls (sub-phase * 2 + parity
+ * of the time); n if none.  The sorted table in device memory, or the new candidates in LDS */
+template <class KeyAt> __device__ __forceinline__ int k2p_next(KeyAt key_at, int from, int n, int want, int cls)
 {
 	const int lane = threadIdx.x & 63;
 	for (int b = from; b < n; b += 64) {
 		const int j = b + lane;
-		const int k = j < n ? skey[j] : 0;
+		const int k = j < n ? key_at(j) : 0;
 		const int t = k >> 2;
 		const bool hit = j < n && t >= want && ((k & 3) * 2 + (t & 1)) == cls;
 		const unsigned long long m = __ballot(hit);
@@ -879,20 +908,69 @@ __device__ __forceinline__ int k2p_next_old(const int *skey, int from, int n, in
 	return n;
 }
 
-/* the same among the new candidates (LDS, sorted by time) */
-__device__ __forceinline__ int k2p_next_new(const unsigned long long *knew, int n, int want, int cls)
+/* the new candidates (nold .. nold + nnew - 1 of the table) by time into knew[]: every one finds its rank by counting (there are a handful) */
+__device__ __forceinline__ void k2p_rank_new(unsigned long long *knew, const Cand *cands, int nold, int nnew, int tid)
 {
-	const int lane = threadIdx.x & 63;
-	for (int b = 0; b < n; b += 64) {
-		const int j = b + lane;
-		const int k = j < n ? (int)(knew[j] >> 16) : 0;
-		const int t = k >> 2;
-		const bool hit = j < n && t >= want && ((k & 3) * 2 + (t & 1)) == cls;
-		const unsigned long long m = __ballot(hit);
-		if (m)
-			return b + __builtin_ctzll(m);
+	for (int i = tid; i < nnew; i += K2P_NT) {
+		const unsigned long long v = (((unsigned long long)(unsigned)(cands[nold + i].nrel * 4 + cands[nold + i].r)) << 16) | (unsigned)(nold + i);
+		int at = 0;
+		for (int j = 0; j < nnew; ++j) {
+			const unsigned long long w = (((unsigned long long)(unsigned)(cands[nold + j].nrel * 4 + cands[nold + j].r)) << 16) | (unsigned)(nold + j);
+			at += (w < v) ? 1 : 0;
+		}
+		knew[at] = v;
 	}
-	return n;
+}
+
+/* what the OLD chain counted inside the nwin windows of ps.win[]: the clusters it met there (their heads: invariant (a) at CTL_NWIN0), the
+ * serial stretches it began there (K2Params.slog).  Every thread returns the workgroup's sums: x triggers, y rejects, z bursts */
+__device__ __forceinline__ int3 k2p_old_counts(K2pShared &ps, const K2Params &p, int sc, int tid, int nwin, int nold, unsigned nslog_in)
+{
+	const int *skey = p.skey + (size_t)sc * VDL2_CAND_CAP;
+	const unsigned short *sidx = p.sidx + (size_t)sc * VDL2_CAND_CAP;
+	const int2 *heads = p.clhead + (size_t)sc * VDL2_CAND_CAP;
+	const uint8_t *onchain = p.onchain + (size_t)sc * VDL2_CAND_CAP;
+	int sub_trig = 0, sub_rej = 0, sub_burst = 0;
+	for (int w = 0; w < nwin; ++w) {
+		const int2 wn = ps.win[w];
+		const int r_lo = k2p_lower_bound(skey, nold, wn.x * 4);
+		const int r_hi = wn.y == 0x7fffffff ? nold : k2p_lower_bound(skey, nold, wn.y * 4);
+		for (int j = r_lo + tid; j < r_hi; j += K2P_NT) {
+			const int idx = sidx[j];
+			if (onchain[idx]) {
+				const int2 hd = heads[idx];
+				sub_trig += cl_ntrig(hd);
+				sub_rej += cl_nrej(hd);
+				sub_burst += cl_nburst(hd);
+			}
+		}
+		if (tid < (int)nslog_in) {
+			const K2Slog g = p.slog[(size_t)sc * VDL2_SLOG_CAP + tid];
+			if (g.t >= wn.x && g.t < wn.y) {
+				sub_trig += g.ntrig;
+				sub_rej += g.nrej;
+				sub_burst += g.nburst;
+			}
+		}
+	}
+	for (int d = 32; d > 0; d >>= 1) {
+		sub_trig += __shfl_xor(sub_trig, d, 64);
+		sub_rej += __shfl_xor(sub_rej, d, 64);
+		sub_burst += __shfl_xor(sub_burst, d, 64);
+	}
+	if ((tid & 63) == 0) {
+		ps.u.red[0][tid >> 6] = sub_trig;
+		ps.u.red[1][tid >> 6] = sub_rej;
+		ps.u.red[2][tid >> 6] = sub_burst;
+	}
+	__syncthreads();
+	int3 sub = make_int3(0, 0, 0);
+	for (int w = 0; w < K2P_NT / 64; ++w) {
+		sub.x += ps.u.red[0][w];
+		sub.y += ps.u.red[1][w];
+		sub.z += ps.u.red[2][w];
+	}
+	return sub;
 }
 
 __global__ __launch_bounds__(K2P_NT)
@@ -914,17 +992,8 @@ void k2p_patch(K2Params p)
 	const unsigned ovf_in = p.ctl[CTL_CAND0 + p.nstreams * VDL2_CS + sc];
 	const int nold = (int)p.ctl[CTL_NCLUST0 + sc], nnew = ncand - nold;
 	const unsigned nslog_in = p.ctl[CTL_NSLOG0 + sc];
-	if (tid == 0) {
-		p.redo[sc] = 1;
-		atomicAdd(p.outc_total_redo + 1, 1u);	/* channel-pushes that went through a repair round */
-		if (p.dbg)
-			atomicAdd(p.dbg + 24, 1ull);
-		p.ctl[CTL_NSEL1 + sc] = 0;
-		p.ctl[CTL_NSEG0 + sc] = 0;
-		p.ctl[CTL_NWIN0 + sc] = 0;
-		if (p.fmask && sc < 512)
-			atomicOr(p.fmask + (sc >> 5), 1u << (sc & 31));
-	}
+	if (tid == 0)
+		k2_begin_repair(p, sc, 0);	/* (the windows are listed at the end) */
 	/* what cannot be repaired locally stays failed (fail[] keeps its value): the next round, or K2f, takes the channel from its input state */
 	/* fail_in <= 0 is not an event's instant: the verify pass could not vouch for the channel (items refused by a full list, more stretches than
 	 * the lists hold): stretches it was to look at have not been looked at, and a local repair verifies only what IT changes
@@ -946,34 +1015,17 @@ void k2p_patch(K2Params p)
 	unsigned *sel = p.sel_list2 + (size_t)sc * VDL2_SEL_CAP;
 	unsigned *nsel = p.ctl + CTL_NSEL1 + sc;
 	Seg *segs = p.segs + (size_t)sc * VDL2_SEG_CAP;
-	/* the new candidates by time: every one finds its rank by counting (there are a handful) */
-	for (int i = tid; i < nnew; i += K2P_NT) {
-		const unsigned long long v = (((unsigned long long)(unsigned)(cands[nold + i].nrel * 4 + cands[nold + i].r)) << 16) | (unsigned)(nold + i);
-		int at = 0;
-		for (int j = 0; j < nnew; ++j) {
-			const unsigned long long w = (((unsigned long long)(unsigned)(cands[nold + j].nrel * 4 + cands[nold + j].r)) << 16) | (unsigned)(nold + j);
-			at += (w < v) ? 1 : 0;
-		}
-		ps.knew[at] = v;
-	}
+	k2p_rank_new(ps.knew, cands, nold, nnew, tid);
 	MachCtx cx;
 	mach_ctx(cx, p, s, c, true);	/* bursts of serial stretches become descriptors */
 	cx.sel = sel;
 	cx.nsel = nsel;
-	cx.dbg = nullptr;
-	const int r_probe = p.probe_r, par_probe = p.probe_par;
 	const int t_end = (int)(cx.avail_end - cx.dec_base);
 	mach_init_taps(sh);	/* (barriers inside: knew[] is in place behind it) */
 	MachOut out;
-	out.nslots = out.ntrig = out.nrej = out.nburst = out.ndefer = 0;
-	out.badslot = 0;
-	out.neval = 0;
-	MachState st;
-	st.pos = 0;
-	st.r = 0;
-	st.fresh = VDL2_STEADY;
-	int add_trig = 0, add_rej = 0, add_burst = 0;	/* what the table clusters on the new chain count */
-	int add_defer = 0;
+	mach_out_clear(out);
+	MachState st = {0, 0, VDL2_STEADY};
+	int add_trig = 0, add_rej = 0, add_burst = 0, add_defer = 0;	/* what the table clusters on the new chain count */
 	int nwin = 0, nsegs = 0;
 	int rk = 0;		/* rank of the old candidate the walk is looking at */
 	int ev = 0;		/* next new candidate to look at */
@@ -1018,34 +1070,26 @@ void k2p_patch(K2Params p)
 		/* (the search starts at the first entry at or behind `want` whatever its class: the hit of one class says nothing about where the
 		 * candidates of the class the chain is in after the NEXT burst lie -- round 6's first version went on from the hit and, once a class
 		 * had no further candidate, found none of any class: scripts/soak.py seed 6068) */
-		rk = k2p_next_old(skey, k2p_lower_bound(skey, nold, want * 4), nold, want, cls);
-		const int jn = k2p_next_new(ps.knew, nnew, want, cls);
+		rk = k2p_next([&](int j) { return skey[j]; }, k2p_lower_bound(skey, nold, want * 4), nold, want, cls);
+		const int jn = k2p_next([&](int j) { return (int)(ps.knew[j] >> 16); }, 0, nnew, want, cls);
 		const int t_old = rk < nold ? (skey[rk] >> 2) : 0x7fffffff;
 		const int t_new = jn < nnew ? (int)(ps.knew[jn] >> 18) : 0x7fffffff;
 		const int t_next = t_old < t_new ? t_old : t_new;
 		K2P_TR("  walk at %d r %d cls %d: t_old %d (rk %d) t_new %d\n", want, st.r, cls, t_old, rk, t_new);
-		if (st.r != r_probe || (int)(st.pos & 1) != par_probe) {	/* (the probe's parity is one of STREAM time: a push's time base may be odd) */
+		if (k2_unprobed(p, st.r, st.pos)) {
 			/* the new chain idles from here to that candidate in a class the probe did not scan: the round's verify pass looks */
 			const int g_hi = t_next < t_end ? t_next : t_end;
 			if (g_hi > want) {
 				if (nsegs < VDL2_SEG_CAP) {
-					if (tid == 0) {
-						Seg g;
-						g.lo = want;
-						g.hi = g_hi;
-						g.r = st.r;
-						g.pad = 0;
-						segs[nsegs] = g;
-					}
+					if (tid == 0)
+						segs[nsegs] = Seg{want, g_hi, st.r, 0};
 				} else
 					failed = true;
 				++nsegs;
 			}
 		}
-		if (t_next == 0x7fffffff) {	/* idle to the end of the data */
-			const long long rem = (cx.avail_end - st.pos + 1) / 2;
-			if (rem > 0)
-				st.pos += 2 * rem;
+		if (t_next == 0x7fffffff) {
+			mach_idle_to_end(cx, st);
 			steady_end = true;
 			to_end = true;
 			break;
@@ -1070,7 +1114,7 @@ void k2p_patch(K2Params p)
 			continue;
 		}
 		const int2 hd = heads[idx];
-		const int status = hd.y & 3;
+		const int status = cl_status(hd);
 		K2P_TR("  old cand idx %d status %d x %d\n", idx, status, hd.x);
 		if (status == CL_INVALID) {
 			st.pos = cx.dec_base + t_old;
@@ -1084,33 +1128,22 @@ void k2p_patch(K2Params p)
 			to_end = true;
 			break;
 		}
-		{	/* a cluster K2b made: its bursts are on the new chain */
-			const int ns = (hd.y >> 4) & 15;
-			const unsigned slot0 = (unsigned)(((size_t)sc * VDL2_CAND_CAP + idx) * VDL2_CL_MAXB);
-			if (tid == 0 && ns) {
-				const unsigned q = atomicAdd(nsel, (unsigned)ns);	/* (the serial machine appends through the same counter) */
-				for (int i = 0; i < ns; ++i) {
-					if (q + i < VDL2_SEL_CAP)
-						sel[q + i] = slot0 + i;
-					else
-						atomicAdd(p.outc + 1, 1u);
-				}
-			}
-			add_trig += (hd.y >> 8) & 255;
-			add_rej += (hd.y >> 16) & 255;
-			add_burst += (hd.y >> 24) & 255;
-		}
+		/* a cluster K2b made: its bursts are on the new chain */
+		const int ns = cl_nslots(hd);
+		const unsigned slot0 = (unsigned)(((size_t)sc * VDL2_CAND_CAP + idx) * VDL2_CL_MAXB);
+		if (tid == 0 && ns)
+			k2_select_slots(p, sel, nsel, slot0, ns);	/* (the serial machine appends through the same counter) */
+		add_trig += cl_ntrig(hd);
+		add_rej += cl_nrej(hd);
+		add_burst += cl_nburst(hd);
 		if (status == CL_STEADY) {
 			st.pos = cx.dec_base + hd.x;
-			st.r = (hd.y >> 2) & 3;
+			st.r = cl_r(hd);
 			continue;
 		}
-		/* CL_NONSTEADY: go on from the explicit state the cluster stopped in */
+		/* CL_NONSTEADY */
 		__syncthreads();
-		mach_load(sh, &clusters[idx].saved);
-		st.pos = clusters[idx].saved.pos;
-		st.r = clusters[idx].saved.r;
-		st.fresh = clusters[idx].saved.fresh < VDL2_STEADY ? clusters[idx].saved.fresh : VDL2_STEADY - 1;
+		mach_resume(sh, st, &clusters[idx].saved);
 		go = GO_SERIAL;
 	}
 	__syncthreads();
@@ -1134,47 +1167,7 @@ void k2p_patch(K2Params p)
 		return;
 	}
 	__syncthreads();
-	/* what the OLD chain counted inside the windows: the clusters it met there (their heads), the serial stretches it began there */
-	int sub_trig = 0, sub_rej = 0, sub_burst = 0;
-	for (int w = 0; w < nwin; ++w) {
-		const int2 wn = ps.win[w];
-		const int r_lo = k2p_lower_bound(skey, nold, wn.x * 4);
-		const int r_hi = wn.y == 0x7fffffff ? nold : k2p_lower_bound(skey, nold, wn.y * 4);
-		for (int j = r_lo + tid; j < r_hi; j += K2P_NT) {
-			const int idx = sidx[j];
-			if (onchain[idx]) {
-				const int2 hd = heads[idx];
-				sub_trig += (hd.y >> 8) & 255;
-				sub_rej += (hd.y >> 16) & 255;
-				sub_burst += (hd.y >> 24) & 255;
-			}
-		}
-		if (tid < (int)nslog_in) {
-			const K2Slog g = p.slog[(size_t)sc * VDL2_SLOG_CAP + tid];
-			if (g.t >= wn.x && g.t < wn.y) {
-				sub_trig += g.ntrig;
-				sub_rej += g.nrej;
-				sub_burst += g.nburst;
-			}
-		}
-	}
-	for (int d = 32; d > 0; d >>= 1) {
-		sub_trig += __shfl_xor(sub_trig, d, 64);
-		sub_rej += __shfl_xor(sub_rej, d, 64);
-		sub_burst += __shfl_xor(sub_burst, d, 64);
-	}
-	if ((tid & 63) == 0) {
-		ps.u.red[0][tid >> 6] = sub_trig;
-		ps.u.red[1][tid >> 6] = sub_rej;
-		ps.u.red[2][tid >> 6] = sub_burst;
-	}
-	__syncthreads();
-	sub_trig = sub_rej = sub_burst = 0;
-	for (int w = 0; w < K2P_NT / 64; ++w) {
-		sub_trig += ps.u.red[0][w];
-		sub_rej += ps.u.red[1][w];
-		sub_burst += ps.u.red[2][w];
-	}
+	const int3 sub = k2p_old_counts(ps, p, sc, tid, nwin, nold, nslog_in);
 	for (int w = tid; w < nwin; w += K2P_NT)
 		p.win[(size_t)sc * VDL2_WIN_CAP + w] = ps.win[w];
 	/* old counters of the push as the first pass left them in cs_out (read before anything is stored) */
@@ -1191,9 +1184,9 @@ void k2p_patch(K2Params p)
 	if (tid == 0) {
 		p.ctl[CTL_NSEG0 + sc] = (unsigned)nsegs;
 		p.ctl[CTL_NWIN0 + sc] = (unsigned)nwin;
-		cs_out->n_trig = o_trig - (unsigned long long)sub_trig + (unsigned long long)(add_trig + out.ntrig);
-		cs_out->n_reject = o_rej - (unsigned long long)sub_rej + (unsigned long long)(add_rej + out.nrej);
-		cs_out->n_burst = o_burst - (unsigned long long)sub_burst + (unsigned long long)(add_burst + out.nburst);
+		cs_out->n_trig = o_trig - (unsigned long long)sub.x + (unsigned long long)(add_trig + out.ntrig);
+		cs_out->n_reject = o_rej - (unsigned long long)sub.y + (unsigned long long)(add_rej + out.nrej);
+		cs_out->n_burst = o_burst - (unsigned long long)sub.z + (unsigned long long)(add_burst + out.nburst);
 		cs_out->n_cand = o_cand + (unsigned long long)nnew;
 		if (to_end) {
 			cs_out->n_eval = cs->n_eval + (unsigned long long)((st.pos - cs->pos) / 2);
@@ -1224,7 +1217,7 @@ void k2f_commit(K2Params p)
 		for (int i = tid; i < (int)(sizeof(ChanState) / 4); i += K2_NT)
 			dst[i] = src[i];
 		/* a channel the repair rounds re-resolved: its selection is final now -- the records K2d's second pass fills */
-		if (tid == 0 && p.sel_reserved && sc < 512 && (p.fmask[sc >> 5] >> (sc & 31) & 1u)) {
+		if (tid == 0 && p.sel_reserved && k2_fmask_test(p, sc)) {
 			const unsigned n = p.ctl[CTL_NSEL1 + sc];
 			if (n > 0)
 				p.ctl[CTL_SELBASE1 + sc] = atomicAdd(p.outc, n > VDL2_SEL_CAP ? VDL2_SEL_CAP : n);
@@ -1233,18 +1226,12 @@ void k2f_commit(K2Params p)
 	}
 	MachCtx cx;
 	mach_ctx(cx, p, s, c, false);
-	cx.dbg = nullptr;
-	MachState st;
-	st.pos = cs->pos;
-	st.r = cs->r;
-	st.fresh = cs->fresh;
+	MachState st = mach_state(cs);
 	const long long p0 = st.pos;
 	mach_init_taps(sh);
 	mach_load(sh, cs);
 	MachOut out;
-	out.nslots = out.ntrig = out.nrej = out.nburst = out.ndefer = 0;
-	out.badslot = 0;
-	out.neval = 0;
+	mach_out_clear(out);
 	machine_run<K2_NT, false>(sh, cx, st, false, 0, 1 << 30, 0, out);
 	__syncthreads();
 	mach_store(sh, st, cs);
@@ -1260,8 +1247,7 @@ void k2f_commit(K2Params p)
 		p.ctl[CTL_NSEL1 + sc] = 0;	/* K2d: nothing of the resolver's for this channel (it is masked: K2d reads the repair rounds' selection) ... */
 		p.ctl[CTL_NWIN0 + sc] = VDL2_WIN_ALL;
 		p.redo[sc] = 1;			/* (... also where the mask does not reach: K2d's one pass behind the commit asks this word) */
-		if (p.fmask && sc < 512)	/* ... and if K2d ran ahead of the verify pass, the host drops what it made of it */
-			atomicOr(p.fmask + (sc >> 5), 1u << (sc & 31));
+		k2_fmask_set(p, sc);		/* ... and if K2d ran ahead of the verify pass, the host drops what it made of it */
 	}
 }
 
@@ -1294,7 +1280,7 @@ template <bool LEV, bool SOFT> __device__ __forceinline__ void k2d_run(const K2P
 	 *               become void are tagged 2 (the host and K4 drop those), the rounds' selection is decoded (records tagged 1);
 	 *   sel_mode 2: the one pass behind the commit of handles that cannot run the decode ahead (more than 512 channel slots: the 16-word
 	 *               mask does not cover them; complete scans): what stands of the first selection, then the rounds' selection. */
-	const bool touched = p.sel_mode == 2 ? p.redo[sc] != 0 : (sc < 512 && (p.fmask[sc >> 5] >> (sc & 31) & 1u));
+	const bool touched = p.sel_mode == 2 ? p.redo[sc] != 0 : k2_fmask_test(p, sc);
 	if (p.sel_mode == 1 && !touched)
 		return;
 	const unsigned nwin = (p.sel_mode != 0 && touched) ? p.ctl[CTL_NWIN0 + sc] : 0u;
@@ -1310,13 +1296,7 @@ template <bool LEV, bool SOFT> __device__ __forceinline__ void k2d_run(const K2P
 			if (base0 + i >= p.rec_cap)
 				break;
 			vdl2gpu_burst_t *rec = p.recs + base0 + i;
-			bool dead = nwin == VDL2_WIN_ALL;
-			if (!dead) {
-				const long long t = rec->trig_dec - p.dec_base;
-				for (unsigned w = 0; w < nwin && w < VDL2_WIN_CAP; ++w)
-					dead = dead || (t >= win[w].x && t < win[w].y);
-			}
-			if (dead)
+			if (nwin == VDL2_WIN_ALL || k2_in_windows(win, nwin, rec->trig_dec - p.dec_base))	/* invariant (b) at CTL_NWIN0 */
 				rec->trig_sample = 2;
 		}
 	}
@@ -1341,14 +1321,9 @@ template <bool LEV, bool SOFT> __device__ __forceinline__ void k2d_run(const K2P
 	for (unsigned i = blockIdx.x; i < n; i += gridDim.x) {
 		const bool second = i >= na;
 		const BurstDesc d = p.stage[second ? sel1[i - na] : sel0[i]];
-		if (!second && p.sel_mode == 2 && nwin != 0) {	/* (block-uniform) a burst of the first selection inside a repaired window: not on the chain any more */
-			const long long t = d.nstar - p.dec_base;
-			bool dead = false;
-			for (unsigned w = 0; w < nwin && w < VDL2_WIN_CAP; ++w)
-				dead = dead || (t >= win[w].x && t < win[w].y);
-			if (dead)
-				continue;
-		}
+		/* (block-uniform) a burst of the first selection inside a repaired window: not on the chain any more */
+		if (!second && p.sel_mode == 2 && nwin != 0 && k2_in_windows(win, nwin, d.nstar - p.dec_base))
+			continue;
 		unsigned slot;
 		if (p.sel_reserved)
 			slot = (second ? base1 : base0) + (second ? i - na : i);

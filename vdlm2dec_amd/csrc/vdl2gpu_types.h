@@ -79,6 +79,16 @@ __device__ __forceinline__ int2 cl_pack(int n_s_rel, int status, int r_s, int ns
 	nburst = nburst > 255 ? 255 : nburst;
 	return make_int2(n_s_rel, status | (r_s << 2) | (nslots << 4) | (ntrig << 8) | (nrej << 16) | (nburst << 24));
 }
+__device__ __forceinline__ int cl_status(int2 hd) { return hd.y & 3; }	/* ... and the fields of its y again (x is read as it is: hd.x) */
+__device__ __forceinline__ int cl_r(int2 hd) { return (hd.y >> 2) & 3; }	/* sub-phase the idle search resumes in */
+__device__ __forceinline__ int cl_nslots(int2 hd) { return (hd.y >> 4) & 15; }
+__device__ __forceinline__ int cl_ntrig(int2 hd) { return (hd.y >> 8) & 255; }
+__device__ __forceinline__ int cl_nrej(int2 hd) { return (hd.y >> 16) & 255; }
+__device__ __forceinline__ int cl_nburst(int2 hd) { return (hd.y >> 24) & 255; }
+/* status | r_s << 2 in one byte: what the resolver keeps of every head in LDS (K2cShared.sstat) */
+__device__ __forceinline__ uint8_t cl_stat4(int2 hd) { return (uint8_t)(hd.y & 15); }
+__device__ __forceinline__ int stat4_status(unsigned s4) { return (int)(s4 & 3u); }
+__device__ __forceinline__ int stat4_r(unsigned s4) { return (int)((s4 >> 2) & 3u); }
 
 struct BurstDesc {		/* a burst found by a cluster; payload decoded later if it is on the real chain */
 	long long nstar;	/* stream time of the sync trigger */
@@ -272,6 +282,16 @@ enum { VDL2_SURV_PROBE = 0, VDL2_SURV_REGION = 1, VDL2_SURV_VERIFY = 2 /* + repa
 											 * a local repair, k2p_patch), VDL2_WIN_ALL: all of it (the channel was resolved again from its
 											 * input state, or redone serially) */
 #define CTL_NSLOG0 (CTL_CAND0 + (12 + 2 * VDL2_SURV_SLOTS) * p.nstreams * VDL2_CS)	/* [S*8] entries of K2Params.slog the first resolver pass made (VDL2_SLOG_CAP + 1: more than it holds) */
+/* Two invariants the windows of CTL_NWIN0 stand on (both implicit in the code, held by the parity and soak tests alone):
+ * (a) K2Params.onchain[] marks the candidates the first resolver pass met history-free: exactly the clusters whose bursts that pass
+ *     selected and whose head it counted, and the candidates a walk stopped at without counting their head (CL_DEFER_FIRST, CL_INVALID:
+ *     such a head counts nothing, or K2Params.slog has it).  ESTABLISHED by k2c_resolve's first pass (k2c_publish, and the kernel's loop
+ *     for the candidate a walk stops at); RELIED ON by k2p_patch: a repaired stretch that arrives at such a candidate has rejoined the
+ *     old chain, and k2p_old_counts takes the old chain's counts inside a window from these heads;
+ * (b) a burst's trigger instant is the same number everywhere: BurstDesc.nstar of a cluster's first burst = dec_base + its candidate's
+ *     nrel, and a record's trig_dec = its descriptor's nstar.  ESTABLISHED by k2b_clusters (st.pos = dec_base + nrel) and burst_payload;
+ *     RELIED ON by k2_in_windows' callers in k2d_run, which test trig_dec (sel_mode 1) and nstar (sel_mode 2) against windows that
+ *     k2p_patch made of candidate times. */
 #define VDL2_CTL_WORDS(nsc) (CTL_CAND0 + (13 + 2 * VDL2_SURV_SLOTS) * (size_t)(nsc))
 #define VDL2_WIN_CAP 32
 #define VDL2_WIN_ALL 0xffffffffu

@@ -26,8 +26,15 @@ F_DEBUG_HEADS = 64
 F_LEVELS = 128
 F_SOFT_RS = 256
 F_EXACT_FO = 512
-# status of a cluster head (bits 0-1 of vdl2gpu_debug_clheads()'s packed word; nslots in bits 4-7, nburst in bits 24-31)
+# status of a cluster head (vdl2gpu_debug_clheads()'s packed word: cl_pack() in csrc/vdl2gpu_types.h)
 CL_STEADY, CL_DEFER_FIRST, CL_NONSTEADY = 0, 1, 2
+
+
+def cl_unpack(packed):
+    """(status, r_s, nslots, ntrig, nrej, nburst) of a cluster head's packed word, as the device's cl_*() accessors read it"""
+    p = int(packed) & 0xffffffff
+    return p & 3, p >> 2 & 3, p >> 4 & 15, p >> 8 & 255, p >> 16 & 255, p >> 24 & 255
+
 
 # every symbol include/vdl2gpu.h declares
 EXPORTS = (
