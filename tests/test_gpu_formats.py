@@ -290,6 +290,61 @@ def test_rails(built, oracle, monkeypatch, fmt):
             _check(oracle, got, want, rate // 4000)
 
 
+# --------------------------------------------------------------------------------------------------------- windows of zeros
+# rate, format, zero runs as (unit, offset in the unit, length): the unit is what the fast kernel of the rate takes whole, a
+# superperiod of 8000 samples at 2 MS/s (k1_fast) and a period of 4 * SDRCLK samples elsewhere (k1_pp).  The short runs cover
+# a whole window (23/24, 59/60, 119/120 samples) only at some offsets, the long ones several windows at any; one run straddles
+# the end of its unit.  Then 8000 zeros from the start of a unit: at 2 MS/s every window of that superperiod.
+ZERO_ROWS = [
+    (2_000_000, "cs16", 8, [(1, 0, 30), (1, 1011, 200), (2, 2503, 30), (2, 5000, 200), (4, 7990, 30), (5, 3777, 200),
+                            (6, 123, 30), (3, 0, 8000)]),
+    (10_000_000, "cs16", 16, [(1, 0, 130), (2, 1011, 700), (4, 2503, 130), (5, 9990, 130), (7, 3777, 700), (9, 123, 130),
+                              (12, 2222, 700), (10, 0, 8000)]),
+    (5_000_000, "f32", 16, [(1, 0, 130), (2, 1011, 700), (4, 2503, 130), (5, 4990, 130), (7, 3777, 700), (9, 123, 130),
+                            (13, 2222, 700), (10, 0, 8000)]),
+]
+
+
+@pytest.mark.timeout(120)
+@pytest.mark.parametrize("rate,fmt,units,runs", ZERO_ROWS, ids=[f"{r[0] // 1000}k-{r[1]}" for r in ZERO_ROWS])
+def test_zero_windows_beside_live_ones(built, oracle, monkeypatch, rate, fmt, units, runs):
+    """Runs of exact zeros in the input: output windows whose sum is exactly zero beside windows of the same wavefront that
+    are not, and one stretch in which a whole wavefront's are.  k1_fast and k1_pp then leave the reciprocal division for the
+    plain one (k1_div_exact: some lane's |sum| < 1e-30) with live data in the other lanes; the planes must stay the oracle's
+    bit for bit, signs of zero included.  One push of whole units from the first sample: the fast kernel takes all of it.
+    The records are not compared: the runs cut through bursts."""
+    from test_gpu_rates import PER as PER_R
+    clk = rate // 4000
+    unit = 8000 if rate == 2_000_000 else 4 * clk
+    n = units * unit
+    fos = _fos(rate, fmt)
+    spec = S.regimes(rate=rate, fo=fos, seed=rate // 1000 + 3, infos=(3, 40, 120, 17), gap=0.001)
+    p = PER_R[fmt]
+    raw = synth.synth_stream(spec, fmt)[:p * n].copy()
+    assert raw.size == p * n
+    for u, off, ln in runs:
+        a = u * unit + off
+        assert unit <= a and a + ln <= n - unit         # clear of the push's first and last unit
+        raw[p * a:p * (a + ln)] = 0
+    decs = {c: _oracle_dec(oracle, raw, fmt, rate, fos[c], 0) for c in (0, len(fos) - 1)}
+    for d in decs.values():
+        z = (_bits(d).reshape(-1, 2) & 0x7FFFFFFF == 0).all(axis=1)
+        # the 8000 zeros alone hold 8000 * 21 / SDRCLK windows less one, every long run a few more
+        assert z.sum() >= 8000 * 21 // clk and not z[:84].any() and not z[-84:].any(), int(z.sum())
+    monkeypatch.setenv("VDL2GPU_STAGE_EVERY", "1")
+    envs = ((None, True), ("VDL2GPU_K1_PP", True), ("VDL2GPU_NO_K1_FAST", False)) if rate == 2_000_000 else ((None, True),)
+    for env, fast_wanted in envs:
+        for k in ("VDL2GPU_NO_K1_FAST", "VDL2GPU_K1_PP"):
+            monkeypatch.delenv(k, raising=False)
+        if env:
+            monkeypatch.setenv(env, "1")
+        with _rx(rate, fos, fmt, max_push=n, keep_dec=True) as rx:
+            rx.push(raw)
+            _planes_equal(rx, decs, env or "default")
+            rx.poll()
+            assert (rx.timing()["fast_pushes"] > 0) == fast_wanted, env
+
+
 # ---------------------------------------------------------------------------------------------------------------------- ring
 @pytest.mark.timeout(240)
 def test_ingest_ring_cs8(built, oracle):

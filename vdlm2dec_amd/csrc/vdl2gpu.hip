@@ -591,7 +591,8 @@ extern "C" int vdl2gpu_burst_to_msgblk(const vdl2gpu_burst_t *b, void *msgblk, s
 }
 
 /* ------------------------------------------------------------------- lifecycle */
-static size_t fmt_bytes(int fmt)
+/* bytes per sample of a format; 0: no such format.  (The kernels' own table is K1Fmt<FMT>::BYTES: held to this one below.) */
+constexpr static size_t fmt_bytes(int fmt)
 {
 	switch (fmt) {
 	case VDL2GPU_FMT_CU8: return 2;
@@ -603,6 +604,14 @@ static size_t fmt_bytes(int fmt)
 	default: return 0;
 	}
 }
+#define FMT_BYTES_AGREE(F_) static_assert(fmt_bytes(F_) == K1Fmt<F_>::BYTES, "fmt_bytes and K1Fmt disagree on " #F_)
+FMT_BYTES_AGREE(VDL2GPU_FMT_CU8);
+FMT_BYTES_AGREE(VDL2GPU_FMT_CS16);
+FMT_BYTES_AGREE(VDL2GPU_FMT_CF32);
+FMT_BYTES_AGREE(VDL2GPU_FMT_F32R);
+FMT_BYTES_AGREE(VDL2GPU_FMT_CS8);
+FMT_BYTES_AGREE(VDL2GPU_FMT_S16R);
+#undef FMT_BYTES_AGREE
 
 /* Everything a handle creates on the device, in page-locked memory, as an event or as a stream is made here and recorded in the
  * handle; release_owned() is the one place that gives it back.  Callers keep their plain pointers, and use the macros, which
@@ -682,71 +691,6 @@ static void release_owned(vdl2gpu_t *h)
 		(void)hipStreamDestroy(s);
 }
 
-#ifdef K1F_PROF
-static void k1f_prof_report()
-{
-	static unsigned raw[K1F_PROF_SLOTS][12];
-	(void)hipDeviceSynchronize();
-	if (hipMemcpyFromSymbol(raw, HIP_SYMBOL(k1f_prof), sizeof raw) == hipSuccess) {
-		double pf[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-		unsigned first = 0xffffffffu, last_start = 0, last_end = 0;
-		int nwaves = 0;
-		for (int b = 0; b < K1F_PROF_SLOTS; ++b) {
-			if (!raw[b][7])
-				continue;
-			++nwaves;
-			for (int i = 0; i < 9; ++i)
-				pf[i] += raw[b][i];
-			first = std::min(first, raw[b][9]);
-			last_start = std::max(last_start, raw[b][9]);
-			last_end = std::max(last_end, raw[b][9] + raw[b][8]);
-		}
-		const char *nm[7] = {"prologue", "wait samples", "convert+park+issue", "barrier", "mix+divide", "store issue", "drain"};
-		if (pf[7] > 0) {
-			double cyc = 0;
-			for (int i = 0; i < 7; ++i)
-				cyc += pf[i];
-			fprintf(stderr, "k1_fast phases, shader cycles per wavefront-iteration (%.0f wavefront-iterations, %d wavefronts in the last launch):", pf[7], nwaves);
-			for (int i = 0; i < 7; ++i)
-				fprintf(stderr, " %s %.0f;", nm[i], pf[i] / pf[7]);
-			{
-				double a = 0, b = 0;
-				for (int bb = 0; bb < K1F_PROF_SLOTS; ++bb)
-					if (raw[bb][7]) {
-						a += raw[bb][10];
-						b += raw[bb][11];
-					}
-				cyc += a + b;
-				fprintf(stderr, " [prologue per wavefront: window table %.0f, addresses + first loads %.0f, LO values + wait %.0f]", a / nwaves, b / nwaves, pf[0] / nwaves);
-			}
-			fprintf(stderr, " shader clock %.0f MHz; a wavefront lives %.1f us; first start to last start %.1f us, to last end %.1f us\n",
-				cyc / (pf[8] / 100.0), pf[8] / nwaves / 100.0, (last_start - first) / 100.0, (last_end - first) / 100.0);
-			std::vector<unsigned> life;
-			double by_xcd[8] = {0}, by_role[K1F_ROLES] = {0}, by_wv[2] = {0};
-			int n_xcd[8] = {0}, n_role[K1F_ROLES] = {0}, n_wv[2] = {0};
-			for (int b = 0; b < K1F_PROF_SLOTS; ++b) {
-				if (!raw[b][7])
-					continue;
-				life.push_back(raw[b][8]);
-				const int blk = b / 2;
-				by_xcd[blk & 7] += raw[b][8]; ++n_xcd[blk & 7];
-				by_role[(blk >> 3) % K1F_ROLES] += raw[b][8]; ++n_role[(blk >> 3) % K1F_ROLES];
-				by_wv[b & 1] += raw[b][8]; ++n_wv[b & 1];
-			}
-			std::sort(life.begin(), life.end());
-			fprintf(stderr, "   lifetime us: min %.1f p10 %.1f p50 %.1f p90 %.1f p99 %.1f max %.1f\n   by XCD:", life[0] / 100.0, life[life.size() / 10] / 100.0,
-				life[life.size() / 2] / 100.0, life[life.size() * 9 / 10] / 100.0, life[life.size() * 99 / 100] / 100.0, life.back() / 100.0);
-			for (int i = 0; i < 8; ++i)
-				fprintf(stderr, " %.1f", by_xcd[i] / std::max(1, n_xcd[i]) / 100.0);
-			fprintf(stderr, "\n   by role:");
-			for (int i = 0; i < K1F_ROLES; ++i)
-				fprintf(stderr, " %.1f", by_role[i] / std::max(1, n_role[i]) / 100.0);
-			fprintf(stderr, "\n   by wavefront of the workgroup: %.1f %.1f\n", by_wv[0] / std::max(1, n_wv[0]) / 100.0, by_wv[1] / std::max(1, n_wv[1]) / 100.0);
-		}
-	}
-}
-#endif
-
 extern "C" void vdl2gpu_destroy(vdl2gpu_t *h)
 {
 	if (h && h->hprof_on && h->pushes)
@@ -754,9 +698,6 @@ extern "C" void vdl2gpu_destroy(vdl2gpu_t *h)
 				"collect the ring %.3f, front stage enqueue %.3f, spill %.3f, back stage enqueue %.3f; waiting for rings' events (push and poll calls) %.3f\n", (unsigned long long)h->pushes,
 			h->hprof[0] / h->pushes * 1e3, h->hprof[1] / h->pushes * 1e3, h->hprof[2] / h->pushes * 1e3, h->hprof[3] / h->pushes * 1e3,
 			h->hprof[4] / h->pushes * 1e3, h->hprof[5] / h->pushes * 1e3, h->hprof[6] / h->pushes * 1e3);
-#ifdef K1F_PROF
-	k1f_prof_report();
-#endif
 	if (!h)
 		return;
 	(void)hipSetDevice(h->cfg.device);
@@ -1481,6 +1422,16 @@ template <class F> static void with_fmt(int fmt, F &&f)
 	}
 }
 
+/* A channeliser kernel of the handle: `plain`, or with VDL2GPU_F_EXACT_FO `rot`, which takes the rotation behind the parameters. */
+template <class P> static void launch_k1(const vdl2gpu_t *h, void (*plain)(P), void (*rot)(P, K1Rot), dim3 grid, unsigned threads, size_t smem,
+					 hipStream_t ks, const P &p)
+{
+	if (h->rot)
+		hipLaunchKernelGGL(rot, grid, dim3(threads), smem, ks, p, h->k1rot);
+	else
+		hipLaunchKernelGGL(plain, grid, dim3(threads), smem, ks, p);
+}
+
 static int push_impl(vdl2gpu_t *h, const void *iq, size_t nsamples, size_t stream_stride_bytes, int memkind, bool wait_copy);
 
 static int push_checked(vdl2gpu_t *h, const void *iq, size_t nsamples, size_t stream_stride_bytes, int memkind, bool wait_copy)
@@ -1847,12 +1798,6 @@ static int stage_input(vdl2gpu_t *h, const void *iq, size_t nsamples, size_t str
 	return VDL2GPU_OK;
 }
 
-/* push-relative index of the last input sample of output j of a push that starts at c0 of the 21/SDRCLK clock */
-static inline long long wend_abs(long long j, int sdrclk, int c0)
-{
-	return ((j + 1) * (long long)sdrclk - c0 + 20) / 21 - 1;
-}
-
 /* Which channeliser kernels a push takes -- arithmetic on the handle's constants, the push's place in the schedule and where its
  * samples lie; nothing is launched here.  K1_FAST at SDRCLK 500 with L = 80 only; K1_PP where whole periods of the dump schedule
  * are whole LO tables and whole 16-byte pieces; the general kernel for everything else, and for the first and the last
@@ -1881,7 +1826,7 @@ static K1Choice choose_k1(const vdl2gpu_t *h, int c0, int64_t J, size_t nsamples
 	 * carried out) needs no general launch at either end: the period-parallel kernel takes all of it (as k1_fast does below) */
 	const bool whole_pp = c0 == 0 && nsamples % (size_t)per_in == 0 && J == periods * K1P_PER_OUT && !h->knob.no_whole_pp;
 	c.per_lo = whole_pp ? 0 : 1;
-	c.sbase0 = wend_abs(K1P_PER_OUT * c.per_lo - 1, h->sdrclk, c0) + 1;
+	c.sbase0 = k1_win_end(K1P_PER_OUT * c.per_lo - 1, h->sdrclk, c0) + 1;
 	/* 16-byte pieces: a period's first sample sits d samples above a 16-byte boundary, the same d for
 	 * every period (a period is a whole number of 16-byte pieces) and every stream */
 	const uintptr_t a0 = (uintptr_t)src + (uintptr_t)c.sbase0 * h->sample_bytes;
@@ -1890,7 +1835,7 @@ static K1Choice choose_k1(const vdl2gpu_t *h, int c0, int64_t J, size_t nsamples
 	c.d = (int)((a0 % 16) / h->sample_bytes);
 	if (whole_pp && c.d != 0) {	/* (the kernel reads a period from the 16-byte boundary below its first sample: that would lie in front of the buffer) */
 		c.per_lo = 1;
-		c.sbase0 = wend_abs(K1P_PER_OUT * c.per_lo - 1, h->sdrclk, c0) + 1;
+		c.sbase0 = k1_win_end(K1P_PER_OUT * c.per_lo - 1, h->sdrclk, c0) + 1;
 		const uintptr_t a1 = (uintptr_t)src + (uintptr_t)c.sbase0 * h->sample_bytes;
 		if ((a1 % 16) % h->sample_bytes)
 			return general;
@@ -1928,14 +1873,13 @@ static void launch_k1_general(vdl2gpu_t *h, const K1Params &k1, hipStream_t ks, 
 	const unsigned gx = (unsigned)((jend - jbeg + 1 + per_block - 1) / per_block);
 	const dim3 grid(gx, (unsigned)h->S);
 	++h->k1_launches[h->k1_glo ? 1 : 0];
-	if (h->rot && h->k1_glo)
-		with_fmt(h->cfg.fmt, [&](auto F) { hipLaunchKernelGGL((k1_channelise<decltype(F)::value, true, true>), grid, dim3(K1_THREADS), smem, ks, q, h->k1rot); });
-	else if (h->rot)
-		with_fmt(h->cfg.fmt, [&](auto F) { hipLaunchKernelGGL((k1_channelise<decltype(F)::value, false, true>), grid, dim3(K1_THREADS), smem, ks, q, h->k1rot); });
-	else if (h->k1_glo)
-		with_fmt(h->cfg.fmt, [&](auto F) { hipLaunchKernelGGL((k1_channelise<decltype(F)::value, true>), grid, dim3(K1_THREADS), smem, ks, q); });
-	else
-		with_fmt(h->cfg.fmt, [&](auto F) { hipLaunchKernelGGL(k1_channelise<decltype(F)::value>, grid, dim3(K1_THREADS), smem, ks, q); });
+	with_fmt(h->cfg.fmt, [&](auto F) {
+		constexpr int FMT = decltype(F)::value;
+		if (h->k1_glo)
+			launch_k1<K1Params>(h, k1_channelise<FMT, true>, k1_channelise<FMT, true, true>, grid, K1_THREADS, smem, ks, q);
+		else
+			launch_k1<K1Params>(h, k1_channelise<FMT>, k1_channelise<FMT, false, true>, grid, K1_THREADS, smem, ks, q);
+	});
 }
 
 /* k1_fast on the push's whole superperiods (all of them, or all but the first and the last: `whole`). */
@@ -1978,10 +1922,7 @@ static void launch_k1_fast(vdl2gpu_t *h, K1Params &k1, bool whole, hipStream_t k
 	}
 	const dim3 grid((unsigned)ngrp * K1F_ROLES, (unsigned)GS);
 	++h->k1_launches[3];
-	if (h->rot)
-		with_fmt(h->cfg.fmt, [&](auto F) { hipLaunchKernelGGL((k1_fast<decltype(F)::value, true>), grid, dim3(K1F_THREADS), 0, ks, k1, h->k1rot); });
-	else
-		with_fmt(h->cfg.fmt, [&](auto F) { hipLaunchKernelGGL(k1_fast<decltype(F)::value>, grid, dim3(K1F_THREADS), 0, ks, k1); });
+	with_fmt(h->cfg.fmt, [&](auto F) { launch_k1<K1Params>(h, k1_fast<decltype(F)::value>, k1_fast<decltype(F)::value, true>, grid, K1F_THREADS, 0, ks, k1); });
 }
 
 /* k1_pp on the push's whole periods (all of them, or all but the first and the last: ch.whole). */
@@ -2010,7 +1951,7 @@ static void launch_k1_pp(vdl2gpu_t *h, const K1Params &k1, const K1Choice &ch, h
 	kp.ss = h->d_ss;
 	int nfmin = 1 << 30, nfmax = 0;
 	for (int k = 0; k < K1P_PER_OUT; ++k) {
-		kp.wend[k] = (int)(wend_abs(K1P_PER_OUT * kp.per_lo + k, h->sdrclk, k1.c0) - kp.sbase0);
+		kp.wend[k] = (int)(k1_win_end(K1P_PER_OUT * kp.per_lo + k, h->sdrclk, k1.c0) - kp.sbase0);
 		const int nf = kp.wend[k] - (k ? kp.wend[k - 1] : -1);
 		nfmin = std::min(nfmin, nf);
 		nfmax = std::max(nfmax, nf);
@@ -2042,10 +1983,7 @@ static void launch_k1_pp(vdl2gpu_t *h, const K1Params &k1, const K1Choice &ch, h
 	kp.wpt = K1P_PER_OUT / best;
 	const dim3 grid((unsigned)(blocks * kp.nsub), (unsigned)GS);
 	++h->k1_launches[2];
-	if (h->rot)
-		with_fmt(h->cfg.fmt, [&](auto F) { hipLaunchKernelGGL((k1_pp<decltype(F)::value, true>), grid, dim3(K1P_THREADS), 0, ks, kp, h->k1rot); });
-	else
-		with_fmt(h->cfg.fmt, [&](auto F) { hipLaunchKernelGGL(k1_pp<decltype(F)::value>, grid, dim3(K1P_THREADS), 0, ks, kp); });
+	with_fmt(h->cfg.fmt, [&](auto F) { launch_k1<K1PParams>(h, k1_pp<decltype(F)::value>, k1_pp<decltype(F)::value, true>, grid, K1P_THREADS, 0, ks, kp); });
 }
 
 /* what every channeliser kernel is told of the handle and the push, beside the push's place in the schedule (vdl2gpu_plan) */
@@ -2053,7 +1991,6 @@ static void fill_k1(const vdl2gpu_t *h, K1Params &k1, const Input &in, size_t ns
 {
 	k1.raw = in.src;
 	k1.stream_stride = in.stride;
-	k1.fmt = h->cfg.fmt;
 	k1.nbch = h->C;
 	k1.sdrclk = h->sdrclk;
 	k1.L = h->L;

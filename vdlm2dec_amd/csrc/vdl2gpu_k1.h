@@ -20,7 +20,9 @@
 #define K1_OPB 32		/* outputs per pass (256 threads / 8 channel lanes) */
 #define K1_PASSES 8
 
-__device__ __forceinline__ long long k1_win_end(long long j, int sdrclk, int c0)
+/* push-relative index of the last input sample of output j of a push that starts at c0 of the 21/SDRCLK clock (the host lays
+ * out the kernels' periods with the same function) */
+__host__ __device__ __forceinline__ long long k1_win_end(long long j, int sdrclk, int c0)
 {
 	return ((j + 1) * (long long)sdrclk - c0 + 20) / 21 - 1;
 }
@@ -333,7 +335,6 @@ void k1_channelise(K1Params p, K1Rot r)
  * (scripts/micro/valu_rate.hip measures 4.6-4.9 cycles per packed op with all SIMDs busy). */
 typedef float v2f __attribute__((ext_vector_type(2)));
 typedef float v16f __attribute__((ext_vector_type(16)));
-typedef const v16f __attribute__((address_space(4))) *k1_cptr16;	/* constant address space: scalar loads */
 
 /* acc += x * w for complex x (VGPR pair), w (SGPR pair) with the reference's operation order
  *   pr = x.re*w.re - x.im*w.im;  pi = x.re*w.im + x.im*w.re;  acc += (pr, pi)
@@ -425,6 +426,25 @@ __device__ __forceinline__ void k1_load_block(v16f &w, v2f (&x)[8], const float2
 		     : "v"(a), "s"(lo)
 		     : "memory");
 }
+
+/* D /= nf (d8psk.c:377) in k1_pp and k1_fast, fn = (float)nf and rfn = RN(1 / fn).  q0 = x * rfn, q = fma(fma(-q0, fn, x), rfn, q0)
+ * is the correctly rounded quotient for every |x| >= 1e-30 and nf in {23, 24, 59, 60, 71, 72, 119, 120} (exhaustively checked:
+ * tests/ctests/div_check.c).  Where any lane of the wavefront holds a smaller |x| (a window of zeros), or the caller's window
+ * lengths are not of that set (`proven` false), the wavefront takes the plain IEEE division. */
+__device__ __forceinline__ v2f k1_div_exact(v2f acc, float fn, float rfn, bool proven = true)
+{
+	float qr, qi;
+	if (proven && __all(fabsf(acc.x) >= 1e-30f && fabsf(acc.y) >= 1e-30f)) {
+		const float q0r = acc.x * rfn, q0i = acc.y * rfn;
+		qr = fmaf(fmaf(-q0r, fn, acc.x), rfn, q0r);
+		qi = fmaf(fmaf(-q0i, fn, acc.y), rfn, q0i);
+	} else {
+		qr = acc.x / fn;
+		qi = acc.y / fn;
+	}
+	return (v2f){qr, qi};
+}
+
 #define K1P_THREADS 512
 #define K1P_CH 32		/* samples of every period per chunk */
 #define K1P_XROW (K1P_CH + 1)	/* LDS row of a period: +1 keeps the lanes' reads on distinct banks */
@@ -491,98 +511,13 @@ void k1_pp(K1PParams p, K1Rot r)
 }
 
 /* ---- K1 fast path: SDRINRATE 2 MS/s (SDRCLK 500, LO period 80) ------------------------
- * The dump schedule and the LO phase repeat every 2000 inputs = 84 outputs (1 ms of air
- * time).  One WAVEFRONT owns 8 consecutive windows of the period x 8 channels (lane =
- * window*8 + channel) for many periods.  A lane's 23/24 LO values never change, so they
- * live in VGPRs; the ~190 samples the wave's 8 windows cover are fetched by the wave itself
- * (3 coalesced loads per lane), converted once, and parked in a private double-buffered LDS
- * slice, from which each sample is read once per window and broadcast to the 8 channel
- * lanes.  Inner loop: 1 LDS read + 8 VALU ops per sample and channel.  No workgroup
- * barrier anywhere: wavefronts never wait for each other, 16 of them per CU hide HBM latency.
- * 84 = 10*8 + 4, so 11 wave roles cover a period (the last one half empty). */
+ * k1_fast: a workgroup of two wavefronts owns 16 consecutive windows of a superperiod (8000 inputs = 336 outputs) x 8
+ * channels for many superperiods, the lane's 23/24 LO values in VGPRs, the samples shared through LDS, one barrier per pair
+ * of superperiods.  The kernel is described where it is written: vdl2gpu_k1_fast.inc.  Here: its mixers, its counted
+ * loads and stores, its constants.  (The packed complex multiply-add and the A/B/T/S schedule notation: k1_cmac_s and
+ * k1_cmac8_s above.) */
 
-/* (re, im) += x * w for complex x, w with the reference's operation order
- *   pr = x.re*w.re - x.im*w.im;  pi = x.re*w.im + x.im*w.re;  acc += (pr, pi)
- * as four packed-FP32 VALU ops (gfx950 issues plain FP32 at half the packed rate):
- *   a = (x.re*w.re, x.re*w.im)          v_pk_mul_f32, op_sel picks x.re twice
- *   b = (x.im*(-w.im), x.im*w.re)       v_pk_mul_f32, halves of w swapped, low lane negated
- *   acc += (a + b)                      2 x v_pk_add_f32
- * a.lo + b.lo = x.re*w.re + (-(x.im*w.im)) is bit-identical to the subtraction. */
-__device__ __forceinline__ void k1_cmac(v2f &acc, v2f x, v2f w)
-{
-	v2f a, b;
-	asm("v_pk_mul_f32 %0, %2, %3 op_sel_hi:[0,1]\n\t"
-	    "v_pk_mul_f32 %1, %2, %3 op_sel:[1,1] op_sel_hi:[1,0] neg_lo:[0,1]"
-	    : "=&v"(a), "=&v"(b)
-	    : "v"(x), "v"(w));
-	acc += (a + b);
-}
-
-/* Eight (seven) samples with the LO values in VGPRs, ordered so that no instruction reads what the one before it wrote
- * (A/B = the two products of a sample, T = their sum, S = acc += T in sample order; see k1_cmac8_s). */
-__device__ __forceinline__ void k1_cmac8_v(v2f &acc, const v2f (&x)[8], const v2f *w)
-{
-	v2f a0, b0, a1, b1, a2, b2;
-	asm volatile(
-		K1_A("%1", "%7", "%15") K1_B("%2", "%7", "%15")
-		K1_A("%3", "%8", "%16") K1_B("%4", "%8", "%16")
-		K1_T("%1", "%2")
-		K1_A("%5", "%9", "%17") K1_B("%6", "%9", "%17")
-		K1_T("%3", "%4")
-		K1_S("%1")
-		K1_A("%1", "%10", "%18") K1_B("%2", "%10", "%18")
-		K1_T("%5", "%6")
-		K1_S("%3")
-		K1_A("%3", "%11", "%19") K1_B("%4", "%11", "%19")
-		K1_T("%1", "%2")
-		K1_S("%5")
-		K1_A("%5", "%12", "%20") K1_B("%6", "%12", "%20")
-		K1_T("%3", "%4")
-		K1_S("%1")
-		K1_A("%1", "%13", "%21") K1_B("%2", "%13", "%21")
-		K1_T("%5", "%6")
-		K1_S("%3")
-		K1_A("%3", "%14", "%22") K1_B("%4", "%14", "%22")
-		K1_T("%1", "%2")
-		K1_S("%5")
-		K1_T("%3", "%4")
-		K1_S("%1")
-		"s_nop 0\n\t"
-		K1_S("%3")
-		: "+v"(acc), "=&v"(a0), "=&v"(b0), "=&v"(a1), "=&v"(b1), "=&v"(a2), "=&v"(b2)
-		: "v"(x[0]), "v"(x[1]), "v"(x[2]), "v"(x[3]), "v"(x[4]), "v"(x[5]), "v"(x[6]), "v"(x[7]),
-		  "v"(w[0]), "v"(w[1]), "v"(w[2]), "v"(w[3]), "v"(w[4]), "v"(w[5]), "v"(w[6]), "v"(w[7]));
-}
-__device__ __forceinline__ void k1_cmac7_v(v2f &acc, const v2f (&x)[8], const v2f *w)
-{
-	v2f a0, b0, a1, b1, a2, b2;
-	asm volatile(
-		K1_A("%1", "%7", "%14") K1_B("%2", "%7", "%14")
-		K1_A("%3", "%8", "%15") K1_B("%4", "%8", "%15")
-		K1_T("%1", "%2")
-		K1_A("%5", "%9", "%16") K1_B("%6", "%9", "%16")
-		K1_T("%3", "%4")
-		K1_S("%1")
-		K1_A("%1", "%10", "%17") K1_B("%2", "%10", "%17")
-		K1_T("%5", "%6")
-		K1_S("%3")
-		K1_A("%3", "%11", "%18") K1_B("%4", "%11", "%18")
-		K1_T("%1", "%2")
-		K1_S("%5")
-		K1_A("%5", "%12", "%19") K1_B("%6", "%12", "%19")
-		K1_T("%3", "%4")
-		K1_S("%1")
-		K1_A("%1", "%13", "%20") K1_B("%2", "%13", "%20")
-		K1_T("%5", "%6")
-		K1_S("%3")
-		K1_T("%1", "%2")
-		K1_S("%5")
-		"s_nop 0\n\t"
-		K1_S("%1")
-		: "+v"(acc), "=&v"(a0), "=&v"(b0), "=&v"(a1), "=&v"(b1), "=&v"(a2), "=&v"(b2)
-		: "v"(x[0]), "v"(x[1]), "v"(x[2]), "v"(x[3]), "v"(x[4]), "v"(x[5]), "v"(x[6]),
-		  "v"(w[0]), "v"(w[1]), "v"(w[2]), "v"(w[3]), "v"(w[4]), "v"(w[5]), "v"(w[6]));
-}
+/* one sample with its LO value in VGPRs: the 24th of a long window */
 __device__ __forceinline__ void k1_cmac1_v(v2f &acc, v2f x, v2f w)
 {
 	v2f a, b;
@@ -590,18 +525,6 @@ __device__ __forceinline__ void k1_cmac1_v(v2f &acc, v2f x, v2f w)
 		     : "+v"(acc), "=&v"(a), "=&v"(b)
 		     : "v"(x), "v"(w));
 }
-/* eight consecutive float2 from LDS, requested and not waited for (ds_read_b64: 256 bytes a clock; the ds_read2_b64 the
- * compiler merges neighbouring reads into gets half of that) */
-__device__ __forceinline__ void k1_lds_issue8(v2f (&x)[8], const unsigned a)
-{
-	asm volatile("ds_read_b64 %0, %8\n\tds_read_b64 %1, %8 offset:8\n\tds_read_b64 %2, %8 offset:16\n\t"
-		     "ds_read_b64 %3, %8 offset:24\n\tds_read_b64 %4, %8 offset:32\n\tds_read_b64 %5, %8 offset:40\n\t"
-		     "ds_read_b64 %6, %8 offset:48\n\tds_read_b64 %7, %8 offset:56"
-		     : "=&v"(x[0]), "=&v"(x[1]), "=&v"(x[2]), "=&v"(x[3]), "=&v"(x[4]), "=&v"(x[5]), "=&v"(x[6]), "=&v"(x[7])
-		     : "v"(a)
-		     : "memory");
-}
-
 /* four consecutive float2 from LDS at byte offset OFS behind address a, requested and not waited for (the offset is an
  * immediate: as part of the address the compiler keeps one register per block and copy of the slice) */
 template <int OFS> __device__ __forceinline__ void k1_lds_issue4(v2f (&x)[4], const unsigned a)
@@ -655,11 +578,7 @@ __device__ __forceinline__ void k1_cmac3_v(v2f &acc, const v2f (&x)[4], const v2
 }
 
 #define K1F_THREADS 128		/* two wavefronts: channels 0-3 and 4-7 of the same 16 windows */
-#ifdef K1F_PROF
-#define K1F_WAVES_OF(FMT_) 4	/* the stamps need registers of their own */
-#else
-#define K1F_WAVES_OF(FMT_) ((FMT_) == VDL2GPU_FMT_CF32 ? 4 : 5)
-#endif	/* wavefronts per SIMD the kernel is built for: 96 registers (cf32 holds its
+#define K1F_WAVES_OF(FMT_) ((FMT_) == VDL2GPU_FMT_CF32 ? 4 : 5)	/* wavefronts per SIMD the kernel is built for: 96 registers (cf32 holds its
 								 * raw samples in twice as many: 128, 4 wavefronts) */
 #define K1F_DEPTH 2		/* superperiods of raw samples in flight per wavefront (registers) */
 #define K1F_CHUNK 8		/* superperiods per ticket (even: the two LDS copies and register sets alternate) */
@@ -705,25 +624,19 @@ template <int FMT> __device__ __forceinline__ float2 k1_raw_cvt(typename K1Raw<F
 	}
 }
 
-/* one global_store_dwordx2 that is always ISSUED (the waits count it), with only the `on` lanes enabled; the address is
- * a workgroup-uniform base (scalar registers) plus the lane's 32-bit byte offset */
+/* One memory instruction that is always ISSUED (k1_fast's waits count it) with only the lanes of a ballot enabled: the asm
+ * text of INSN_ between the save of exec and its return.  The block names the ballot as operand [m] and clobbers s2, s3.
+ * (k1_store_masked below and k1_fast's ticket request.) */
+#define K1_MASKED_ISSUE(INSN_) "s_mov_b64 s[2:3], exec\n\t" "s_mov_b64 exec, %[m]\n\t" INSN_ "\n\t" "s_mov_b64 exec, s[2:3]"
+
+/* a global_store_dwordx2 of the `on` lanes; the address is a workgroup-uniform base (scalar registers) plus the lane's 32-bit
+ * byte offset */
 __device__ __forceinline__ void k1_store_masked(const float2 *sbase, unsigned voff, v2f v, bool on)
 {
-	const unsigned long long m = __ballot(on);
-	asm volatile("s_mov_b64 s[2:3], exec\n\t"
-		     "s_mov_b64 exec, %3\n\t"
-		     "global_store_dwordx2 %0, %1, %2\n\t"
-		     "s_mov_b64 exec, s[2:3]"
-		     :: "v"(voff), "v"(v), "s"(sbase), "s"(m) : "memory", "s2", "s3");
+	asm volatile(K1_MASKED_ISSUE("global_store_dwordx2 %0, %1, %2")
+		     :: "v"(voff), "v"(v), "s"(sbase), [m] "s"(__ballot(on)) : "memory", "s2", "s3");
 }
 
-#ifdef K1F_PROF
-#define K1F_PROF_SLOTS 32768
-__device__ unsigned k1f_prof[K1F_PROF_SLOTS][12];	/* development: shader cycles a wavefront spends in each phase (last launch) */
-#define K1F_STAMP(I_) do { const unsigned t_ = (unsigned)__builtin_amdgcn_readfirstlane((int)clock64()); pf[I_] += t_ - tl; tl = t_; } while (0)
-#else
-#define K1F_STAMP(I_) do { } while (0)
-#endif
 /* VDL2GPU_F_EXACT_FO: one table entry of the rotation, requested and not waited for (the loop counts it among its loads) */
 __device__ __forceinline__ void k1r_issue(v2f &v, const unsigned voff, const float2 *sbase)
 {

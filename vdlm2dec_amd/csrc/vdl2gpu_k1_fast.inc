@@ -1,14 +1,10 @@
 /* vdl2gpu_k1_fast.inc -- the body of k1_fast, included by vdl2gpu_k1.h once per kernel: into the kernel of a handle without
  * VDL2GPU_F_EXACT_FO with ROT = false and an empty K1Rot r in scope (the text around `if constexpr (ROT)` is then the kernel as
  * it always was, instruction for instruction), and into the rotating kernel with ROT its template parameter and r its
- * second argument.  (As a function shared by the two, the compiler allotted the old kernel other registers.) */
+ * second argument.  (As a function shared by the two, the compiler allotted the old kernel other registers; tried again when the
+ * profiling build and the ablation switches had gone from k1_fast, with the same outcome.) */
 	typedef typename K1Raw<FMT>::T raw_t;
-	constexpr int B = (FMT == VDL2GPU_FMT_CU8 || FMT == VDL2GPU_FMT_CS8 || FMT == VDL2GPU_FMT_S16R) ? 2 : (FMT == VDL2GPU_FMT_CF32) ? 8 : 4;
-#ifdef K1F_PROF
-	unsigned pf[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-	unsigned tl = (unsigned)__builtin_amdgcn_readfirstlane((int)clock64());
-	const unsigned wall0 = (unsigned)__builtin_amdgcn_readfirstlane((int)wall_clock64());
-#endif
+	constexpr int B = K1Fmt<FMT>::BYTES;
 	/* LDS: every window has its own row of 25 float2 (24 samples + 1 of padding: rows of 50 dwords put the 8 windows of
 	 * a half-wave read on 8 different bank pairs; laid end to end, windows 4 apart -- 95 or 96 samples -- shared banks),
 	 * a pair of slices per iteration, two copies of the pair used in turn (one barrier per iteration) */
@@ -95,8 +91,10 @@
 	constexpr long long pbytes = (long long)K1F_PER_IN * B * 8;
 	int p0 = rank * CP;	/* this iteration's pair */
 	raw_t rr[2][3];
-	{
-		const int ia = 2 * p0, ib = ia + 1 < n_x ? ia + 1 : ia;
+	/* the six loads of pair pr: superperiods 2 pr and 2 pr + 1 of the family (the family's last pair may lack its second
+	 * half: the loads then fetch the first again) */
+	auto issue_pair = [&](int pr) {
+		const int ia = 2 * pr, ib = ia + 1 < n_x ? ia + 1 : ia;
 		const char *rb = rbase + pbytes * ia;
 		k1_raw_issue<FMT>(rr[0][0], vo[0], rb);
 		k1_raw_issue<FMT, K1F_THREADS * B>(rr[0][1], vo[0], rb);
@@ -105,8 +103,8 @@
 		k1_raw_issue<FMT>(rr[1][0], vo[0], rb);
 		k1_raw_issue<FMT, K1F_THREADS * B>(rr[1][1], vo[0], rb);
 		k1_raw_issue<FMT>(rr[1][2], vo[2], rb);
-	}
-	K1F_STAMP(8);	/* prologue: addresses, first loads issued */
+	};
+	issue_pair(p0);
 	/* the lane's LO values, behind the first samples' loads (one round trip for both); the table carries its own
 	 * wrap-around (24 loads off one address) */
 	v2f w[24];
@@ -131,7 +129,7 @@
 		ronv = rtab[23];
 	}
 	const float fn = (float)nwin;
-	const float rfn = 1.0f / fn;	/* RN(1/nf) for the exact FMA division below */
+	const float rfn = 1.0f / fn;	/* RN(1/nf) for k1_div_exact */
 	const float2 *dec = p.dec + (size_t)s * VDL2_CS * p.cap + VDL2_CARRY_FRAMES + (p.per_lo + x) * K1F_PER_OUT + g * 16;	/* workgroup-uniform */
 	const unsigned dvo = (unsigned)(((size_t)(active ? c : 0) * p.cap + kk) * sizeof(float2));	/* a stream's planes span < 4 GiB (VDL2_PLANES_MAX, vdl2gpu_create) */
 	asm volatile("s_waitcnt vmcnt(0)" ::: "memory");	/* from here on the only memory operations are the counted ones below */
@@ -141,25 +139,17 @@
 	if constexpr (ROT)
 		asm volatile("" : "+v"(rk0), "+v"(rs1), "+v"(ronv));	/* likewise: the loop's waits are counted */
 	const bool ron = ronv != 0;
-	K1F_STAMP(0);	/* prologue */
 	const unsigned xa = (unsigned)(size_t)(__attribute__((address_space(3))) const float2 *)&xs[0][0][kk * 25];
 	unsigned tkr = 0;	/* lane 0 of wavefront 0: the counter's answer, landing while the chunk is worked on */
 	int nxt = 0x7fffffff;
 	int pos = 0;	/* position in the current chunk */
 	int buf = 0;	/* which copy of the slices this iteration writes and reads */
-#ifdef K1F_PROF
-	int nit = 0;
-#endif
 	if constexpr (ROT)
 		rk = k1r_mod(rk0 + (unsigned long long)(2 * p0) * rs1, r.M, r.rM);	/* of the first superperiod of pair p0 */
 	while (p0 >= 0) {
-#ifdef K1F_PROF
-		nit += 2;
-#endif
 		/* pair p0: registers -> float -> LDS slices, then refill the registers with the next pair.  Every iteration
 		 * issues exactly 6 loads and then 2 stores per wavefront: only the 2 stores have been issued after the loads
 		 * this iteration waits for (a ticket request is issued BEFORE an iteration's loads, so they see it land). */
-#ifndef K1F_NOPRIO
 		/* the SIMD's arbiter serves its oldest wavefront first: left alone, the five wavefronts of a SIMD advance
 		 * at very different rates.  Rotating priorities keep them together. */
 		switch ((pos + (int)blockIdx.x) & 3) {
@@ -168,13 +158,7 @@
 		case 2: __builtin_amdgcn_s_setprio(2); break;
 		default: __builtin_amdgcn_s_setprio(3); break;
 		}
-#endif
-#if defined(K1F_NOLOAD) || defined(K1F_NOSTORE)
-		asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#else
 		asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-#endif
-		K1F_STAMP(1);	/* wait for the samples */
 #pragma unroll
 		for (int ab = 0; ab < 2; ++ab)
 #pragma unroll
@@ -190,11 +174,8 @@
 		if (pos == 0) {
 			/* ask for the next ticket: older than the loads issued below, so the next iteration's wait sees it land */
 			const unsigned long long m = __ballot(tid == 0);
-			asm volatile("s_mov_b64 s[2:3], exec\n\t"
-				     "s_mov_b64 exec, %3\n\t"
-				     "global_atomic_add %0, %1, %2, %4 sc0\n\t"
-				     "s_mov_b64 exec, s[2:3]"
-				     : "+v"(tkr) : "v"(0u), "v"(1u), "s"(m), "s"(ctr) : "memory", "s2", "s3");
+			asm volatile(K1_MASKED_ISSUE("global_atomic_add %0, %1, %2, %4 sc0")
+				     : "+v"(tkr) : "v"(0u), "v"(1u), [m] "s"(m), "s"(ctr) : "memory", "s2", "s3");
 		}
 		if (pos == 1) {
 			asm volatile("" : "+v"(tkr));	/* it has landed: the wait above was for loads issued after the request */
@@ -221,34 +202,14 @@
 			else
 				rk = k1r_mod(rk0 + (unsigned long long)(2 * (p1 >= 0 ? p1 : p0)) * rs1, r.M, r.rM);
 		}
-		{
-			const int ia = 2 * (p1 >= 0 ? p1 : p0), ib = ia + 1 < n_x ? ia + 1 : ia;
-#ifndef K1F_NOLOAD
-			const char *rb = rbase + pbytes * ia;
-			k1_raw_issue<FMT>(rr[0][0], vo[0], rb);
-			k1_raw_issue<FMT, K1F_THREADS * B>(rr[0][1], vo[0], rb);
-			k1_raw_issue<FMT>(rr[0][2], vo[2], rb);
-			rb = rbase + pbytes * ib;
-			k1_raw_issue<FMT>(rr[1][0], vo[0], rb);
-			k1_raw_issue<FMT, K1F_THREADS * B>(rr[1][1], vo[0], rb);
-			k1_raw_issue<FMT>(rr[1][2], vo[2], rb);
-#endif
-		}
-		K1F_STAMP(2);	/* convert, park, issue the next loads */
-#ifndef K1F_NOBARRIER
+		issue_pair(p1 >= 0 ? p1 : p0);
 		__syncthreads();	/* the slices are written */
-#endif
-		K1F_STAMP(3);	/* barrier */
 		const bool has_b = 2 * p0 + 1 < n_x;
 		const unsigned xc = xa + (unsigned)buf * (unsigned)sizeof(xs[0]);
 #pragma unroll
 		for (int ab = 0; ab < 2; ++ab) {
 			v2f res = {0.0f, 0.0f};
-#ifdef K1F_NOMIX
-			if (p.nbch > 8) {
-#else
 			if (ab == 0 || has_b) {
-#endif
 				v2f acc = {0.0f, 0.0f};
 				if (K1_REAL(FMT)) {
 					const v2f *xp = reinterpret_cast<const v2f *>(&xs[buf][ab][kk * 25]);
@@ -295,18 +256,7 @@
 					else
 						mix(std::integral_constant<int, 0>{});
 				}
-				/* D /= nf (d8psk.c:377).  q0 = x*RN(1/nf); q = fma(fma(-q0, nf, x), RN(1/nf), q0)
-				 * is the correctly rounded quotient for every |x| >= 1e-30 (exhaustively
-				 * checked for nf = 23, 24: tests/ctests/div_check.c); below that, and only
-				 * then, the plain IEEE division is used */
-				if (__all(fabsf(acc.x) >= 1e-30f && fabsf(acc.y) >= 1e-30f)) {
-					const float q0r = acc.x * rfn, q0i = acc.y * rfn;
-					res.x = fmaf(fmaf(-q0r, fn, acc.x), rfn, q0r);
-					res.y = fmaf(fmaf(-q0i, fn, acc.y), rfn, q0i);
-				} else {
-					res.x = acc.x / fn;
-					res.y = acc.y / fn;
-				}
+				res = k1_div_exact(acc, fn, rfn);	/* D /= nf (d8psk.c:377) */
 			}
 			if constexpr (ROT) {
 				if (ab == 0)
@@ -319,14 +269,10 @@
 					res.y = q.y;
 				}
 			}
-			K1F_STAMP(4);	/* mix + divide */
 			/* exactly one store instruction per superperiod and wavefront: four whole lines (channels beyond nbch masked
 			 * off; a wavefront without any channel, or the missing second half of the family's last pair, still issues
 			 * it, with no lane enabled, so that the count above holds) */
-#ifndef K1F_NOSTORE
 			k1_store_masked(dec + (long long)(2 * p0 + ab) * (8 * K1F_PER_OUT), dvo, res, active && (ab == 0 || has_b));
-#endif
-			K1F_STAMP(5);	/* store issue */
 		}
 		/* no second barrier: the next iteration writes the other copy of the slices, and the one after that writes this
 		 * one only behind the next iteration's barrier, which every wave reaches after its reads here */
@@ -335,15 +281,3 @@
 		buf ^= 1;
 	}
 	asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#ifdef K1F_PROF
-	K1F_STAMP(6);	/* drain */
-	if (lane == 0 && blockIdx.y == 0 && blockIdx.x * 2 + wv < K1F_PROF_SLOTS) {
-		for (int i = 0; i < 7; ++i)
-			k1f_prof[blockIdx.x * 2 + wv][i] = pf[i];
-		k1f_prof[blockIdx.x * 2 + wv][7] = (unsigned)nit;
-		k1f_prof[blockIdx.x * 2 + wv][8] = (unsigned)wall_clock64() - wall0;	/* 100 MHz ticks of the wavefront's life */
-		k1f_prof[blockIdx.x * 2 + wv][9] = wall0;
-		k1f_prof[blockIdx.x * 2 + wv][10] = pf[7];
-		k1f_prof[blockIdx.x * 2 + wv][11] = pf[8];
-	}
-#endif

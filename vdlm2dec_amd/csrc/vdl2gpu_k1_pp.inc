@@ -1,7 +1,8 @@
 /* vdl2gpu_k1_pp.inc -- the body of k1_pp, included by vdl2gpu_k1.h once per kernel: into the kernel of a handle without
  * VDL2GPU_F_EXACT_FO with ROT = false and an empty K1Rot r in scope (the text around `if constexpr (ROT)` is then the kernel as
  * it always was, instruction for instruction), and into the rotating kernel with ROT its template parameter and r its
- * second argument.  (As a function shared by the two, the compiler allotted the old kernel other registers.) */
+ * second argument.  (As a function shared by the two, the compiler allotted the old kernel other registers; tried again when the
+ * profiling build and the ablation switches had gone from k1_fast, with the same outcome.) */
 	constexpr int B = K1Fmt<FMT>::BYTES, SPB = K1Fmt<FMT>::SPB;
 	constexpr int NPIECE = K1P_CH / SPB;			/* 16-byte pieces per period and chunk */
 	constexpr int NPT = (64 * NPIECE + K1P_THREADS - 1) / K1P_THREADS;	/* pieces per thread */
@@ -143,21 +144,9 @@
 #undef K1_TAIL
 			}
 			if (i > wend) {
-				/* D /= nf (d8psk.c:377).  q0 = x*RN(1/nf); q = fma(fma(-q0, nf, x), RN(1/nf), q0) is the
-				 * correctly rounded quotient for every |x| >= 1e-30 and nf in {23,24,59,60,71,72,119,120}
-				 * (exhaustively checked: tests/ctests/div_check.c); otherwise the plain IEEE division */
-				const float fn = (float)nf;
-				float qr, qi;
-				if (p.fast_div && __all(fabsf(acc.x) >= 1e-30f && fabsf(acc.y) >= 1e-30f)) {
-					const float rfn = (nf == p.nf_lo) ? p.rcp_lo : p.rcp_hi;
-					const float q0r = acc.x * rfn, q0i = acc.y * rfn;
-					qr = fmaf(fmaf(-q0r, fn, acc.x), rfn, q0r);
-					qi = fmaf(fmaf(-q0i, fn, acc.y), rfn, q0i);
-				} else {
-					qr = acc.x / fn;
-					qi = acc.y / fn;
-				}
-				float2 v = make_float2(qr, qi);
+				/* D /= nf (d8psk.c:377); the host says whether this rate's two window lengths are proven (fast_div) */
+				const v2f q = k1_div_exact(acc, (float)nf, (nf == p.nf_lo) ? p.rcp_lo : p.rcp_hi, p.fast_div);
+				float2 v = make_float2(q.x, q.y);
 				if constexpr (ROT)
 					if (ron)
 						v = k1r_cmul(v, k1r_cmul(rh, rl));

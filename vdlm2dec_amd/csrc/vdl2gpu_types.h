@@ -114,7 +114,7 @@ static_assert(sizeof(HeadTap) == 132 || sizeof(HeadTap) == 136, "HeadTap layout"
 struct K1Params {
 	const void *raw;
 	size_t stream_stride;
-	int fmt, nbch;
+	int nbch;
 	int sdrclk, L, maxwin;
 	int c0, no0, nf0, parity;
 	int quirk;		/* cu8 only: the store-index off-by-one of rtl.c:291, per 32768-sample block */
