@@ -260,6 +260,53 @@ typedef struct {
 	uint8_t reserved[8];				/* @2040 0 */
 } vdl2gpu_soft_t;		/* sizeof 2048 */
 
+/* ---- carrier offset and phase-error spread (VDL2GPU_F_CARRIER; announced by VDL2GPU_HAVE_CARRIER, the ABI version is unchanged) ----
+ * A burst record's df / ppm are the reference's one-shot estimate from the 16 sync symbols (d8psk.c:281-302), and stay that.  As a
+ * frequency they carry a convention and a scatter: the reference's sync-word table has a slope of pi/8 per symbol built in, so that
+ * the slicer (d8psk.c:213, 323-327) sees the eight D8PSK increments at the CENTRES of its sectors -- Grey table index 16 + 32 m, not
+ * 32 m -- and 10500 df / 2 pi reads 656.25 Hz below the true offset, give or take some 10 Hz rms.  With VDL2GPU_F_CARRIER the
+ * demodulator adds up, over the whole burst, how far every slice fell from the centre of its sector; that is the carrier offset the
+ * one-shot estimate left behind, and its spread is the burst's modulation quality.
+ * For an accepted burst with header values nbrow, nlbyte, trigger trig_dec, one-shot timing clk0 and carrier estimate df:
+ *   ND, NF       data and FEC bytes transmitted (d8psk.c:117-206): ND = 249 (nbrow - 1) + (nlbyte ? nlbyte : 249); nlbyte <= 2: FEC rows
+ *                nbrow - 1, the last with 6 bytes, else nbrow rows, the last with 2 / 4 / 6 bytes for nlbyte <= 30 / <= 67 / above;
+ *                NF = 6 (FEC rows - 1) + the last row's (0 without FEC rows)
+ *   j0, rb       j0 = max(1, (32 - clk0 + 3) / 4), rb = clk0 + 4 j0 - 32 (d8psk.c:239, 317-319)
+ *   kmax         (25 + 8 (ND + NF) - 1) / 3: the symbol that carries the last transmitted bit
+ *   symbols      k = 8 .. kmax -- exactly the slices the payload decode and the reliability map (vdl2gpu_soft_t) take:
+ *                P_k   = filteredphase() (d8psk.c:219-230) at stream time trig_dec + j0 + 8 k, sub-phase rb
+ *                idx_k = the slicer's Grey table index of (P_k, P_{k-1}, df), 0..256, 32 steps a sector
+ *                e_k   = (idx_k & 31) - 16, in [-16, 15]
+ *   nsym = kmax - 7,  sum_e = sum e_k,  sum_e2 = sum e_k^2 (at most 256 nsym)
+ * The sums are integers, so no order of summation has to be defined: a burst gets the same record whatever kernel, path or repair
+ * round decoded it and however the stream was cut into pushes.  The host derives the rest in double precision, as it does ppm
+ * (vdl2gpu_carrier_from_sums is that arithmetic, and what the library itself calls):
+ *   m       = (double)sum_e / nsym
+ *   dphi_d  = (double)df + M_PI / 8 + m * M_PI / 128        true rotation per symbol beyond the data, rad
+ *   dphi    = (float)dphi_d
+ *   freq_hz = (float)(10500.0 * dphi_d / (2 * M_PI))
+ *   ppm     = (float)(10500.0 * dphi_d / (2 * M_PI * (double)Fr) * 1e6)
+ *   rms_rad = (float)(sqrt(max(0, (double)sum_e2 / nsym - m * m)) * M_PI / 128)
+ * Sign: positive means the carrier lies ABOVE the channel centre as mixed -- above Fo, or above Fg + Fd with VDL2GPU_F_EXACT_FO; a
+ * receiver whose tuner sits low sees its channels high.  freq_hz is what to add to every Fo of an exact-Fo handle.
+ * The estimate is decision-directed: it is as good as the slicer's decisions.  A burst whose rms_rad approaches the half-sector
+ * pi / 8 = 0.39 has symbols in the wrong sectors and is not to be trusted; a clean one reads 0.02 .. 0.1.  It needs no noise window,
+ * so it is a quality figure on a saturated channel too, where vdl2gpu_level_t's noise floor is only an upper bound.
+ * Memory: 32 bytes per record slot wherever a level record has 40 -- each device output ring, each host slab, and the host queue
+ * beside every burst record it holds. */
+#define VDL2GPU_F_CARRIER 1024u
+#define VDL2GPU_HAVE_CARRIER 1
+typedef struct {
+	int32_t nsym;		/* @0  symbols summed, kmax - 7 */
+	int32_t sum_e;		/* @4  sum of e_k */
+	uint32_t sum_e2;	/* @8  sum of e_k^2 */
+	int32_t reserved;	/* @12 0 */
+	float dphi;		/* @16 rotation per symbol beyond the data, rad */
+	float freq_hz;		/* @20 the same as a frequency: 10500 dphi / 2 pi */
+	float ppm;		/* @24 ... relative to the channel frequency Fr (the burst record's own ppm stays the reference's) */
+	float rms_rad;		/* @28 spread of the slices around their mean, rad */
+} vdl2gpu_carrier_t;		/* sizeof 32, alignment 4 */
+
 typedef struct {
 	uint64_t samples_in;	/* per stream */
 	uint64_t dec_samples;	/* 84 kS/s samples produced per channel */
@@ -369,6 +416,11 @@ int vdl2gpu_poll_levels_ready(vdl2gpu_t *h, vdl2gpu_burst_t *out, vdl2gpu_level_
  * host queue holds a map beside every unread burst: with the flag, 2048 more bytes per record of the bound above. */
 int vdl2gpu_poll_soft(vdl2gpu_t *h, vdl2gpu_burst_t *out, vdl2gpu_level_t *lv, vdl2gpu_soft_t *soft, int max);
 int vdl2gpu_poll_soft_ready(vdl2gpu_t *h, vdl2gpu_burst_t *out, vdl2gpu_level_t *lv, vdl2gpu_soft_t *soft, int max);
+/* ... and with the bursts' carrier records: car[i] belongs to out[i] (VDL2GPU_F_CARRIER).  Same queue, order, waiting and threading as
+ * the other collectors; each of lv, soft and car may be NULL (all three: exactly vdl2gpu_poll).  car != NULL on a handle created
+ * without VDL2GPU_F_CARRIER: VDL2GPU_EINVAL, and nothing is consumed; lv and soft as above. */
+int vdl2gpu_poll_carrier(vdl2gpu_t *h, vdl2gpu_burst_t *out, vdl2gpu_level_t *lv, vdl2gpu_soft_t *soft, vdl2gpu_carrier_t *car, int max);
+int vdl2gpu_poll_carrier_ready(vdl2gpu_t *h, vdl2gpu_burst_t *out, vdl2gpu_level_t *lv, vdl2gpu_soft_t *soft, vdl2gpu_carrier_t *car, int max);
 /* Number of bursts a poll would currently return (implies vdl2gpu_sync). */
 int vdl2gpu_pending(vdl2gpu_t *h);
 /* Pushes the GPU has not finished yet (0..3); never waits.  For a producer that is not bound to real time and wants to
@@ -462,6 +514,10 @@ int vdl2gpu_exact_fo_tables(unsigned sdrinrate, float *hi_re_im, int max_hi, flo
 /* ... and the phase index k of the window whose first and last inputs are samples a and e of the stream, for a residual
  * offset of fd_hz: (fd * ((a + e) mod 2R)) mod 2R, fd = fd_hz mod 2R taken non-negative.  VDL2GPU_EINVAL for such a rate. */
 int64_t vdl2gpu_exact_fo_index(uint64_t a, uint64_t e, unsigned sdrinrate, int fd_hz);
+/* VDL2GPU_F_CARRIER: the derived values of a carrier record from its sums, the formulas at vdl2gpu_carrier_t in double precision
+ * (what the library's collector calls for every record).  df, Fr: the burst record's.  Fills all of *out (reserved = 0).
+ * VDL2GPU_EINVAL for nsym <= 0, Fr == 0 or out == NULL. */
+int vdl2gpu_carrier_from_sums(float df, int Fr, int nsym, int sum_e, unsigned sum_e2, vdl2gpu_carrier_t *out);
 /* Frequency planning: the tuner centre the reference picks for a list of channel
  * frequencies, and the per-channel mixer offsets Fo it derives (thread_param_t.Fo).
  *   rtl: chooseFc() of rtl.c:123-160 -- the highest Fc (1 Hz steps, downwards from max + 50 kHz) that keeps every

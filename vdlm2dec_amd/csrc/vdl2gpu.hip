@@ -94,8 +94,8 @@ struct LaterEvent {
 
 /* A burst record has side columns: entries at the record's index in the device rings, the slabs and the host queue, present when
  * the handle's flags ask for them.  A column is one row here and its flag in create_impl. */
-enum { COL_SOFT, COL_LEVEL, VDL2_NCOL };	/* VDL2GPU_F_SOFT_RS: a reliability map (2048 bytes); VDL2GPU_F_LEVELS: a level record */
-static const size_t col_bytes[VDL2_NCOL] = { sizeof(vdl2gpu_soft_t), sizeof(vdl2gpu_level_t) };
+enum { COL_SOFT, COL_LEVEL, COL_CARRIER, VDL2_NCOL };	/* VDL2GPU_F_SOFT_RS: a reliability map (2048 bytes); VDL2GPU_F_LEVELS: a level record; VDL2GPU_F_CARRIER: a carrier record */
+static const size_t col_bytes[VDL2_NCOL] = { sizeof(vdl2gpu_soft_t), sizeof(vdl2gpu_level_t), sizeof(vdl2gpu_carrier_t) };
 
 /* A table set (push % VDL2_NSET): what a push's demodulator kernels work in, see alloc_sets. */
 struct TableSet {
@@ -125,6 +125,7 @@ struct OutRing {
 	hipEvent_t done() const { return done2[ev]; }
 	vdl2gpu_level_t *levels() const { return static_cast<vdl2gpu_level_t *>(d_side[COL_LEVEL]); }
 	vdl2gpu_soft_t *soft() const { return static_cast<vdl2gpu_soft_t *>(d_side[COL_SOFT]); }
+	vdl2gpu_carrier_t *carrier() const { return static_cast<vdl2gpu_carrier_t *>(d_side[COL_CARRIER]); }
 };
 
 /* A slab (push % VDL2_NSLAB) of page-locked host memory, which the GPU itself fills at the end of the push (k_export_records), and
@@ -137,6 +138,7 @@ struct Slab {
 	size_t lo = 0, hi = 0;	/* ready_idx[lo, hi): where the handles into the slab lie (a push's are contiguous) */
 	vdl2gpu_level_t *d_levels() const { return static_cast<vdl2gpu_level_t *>(d_side[COL_LEVEL]); }
 	vdl2gpu_soft_t *d_soft() const { return static_cast<vdl2gpu_soft_t *>(d_side[COL_SOFT]); }
+	vdl2gpu_carrier_t *d_carrier() const { return static_cast<vdl2gpu_carrier_t *>(d_side[COL_CARRIER]); }
 };
 
 /* Records in pageable storage, with their side columns (byte vectors: col_bytes[k] a record). */
@@ -976,6 +978,7 @@ static int create_impl(vdl2gpu_t *h)
 	/* the output rings and the slabs: the records, and beside them the side columns the flags ask for */
 	h->col_on[COL_LEVEL] = (cfg.flags & VDL2GPU_F_LEVELS) != 0;
 	h->col_on[COL_SOFT] = (cfg.flags & VDL2GPU_F_SOFT_RS) != 0;
+	h->col_on[COL_CARRIER] = (cfg.flags & VDL2GPU_F_CARRIER) != 0;
 	h->frames_on = (cfg.flags & VDL2GPU_F_FRAMES) != 0;
 	if (h->frames_on) {
 		unsigned arena = 4u << 20;
@@ -1393,7 +1396,9 @@ static void launch_clusters(const vdl2gpu_t *h, hipStream_t s, const K2Params &k
 enum { SEL_FIRST = 0, SEL_REPAIRED = 1, SEL_FINAL = 2 };
 static void launch_payload(const vdl2gpu_t *h, hipStream_t s, const K2Params &k2, int sel_mode)
 {
-	void (*const kernel)(K2Params) = h->col_on[COL_SOFT] ? (h->col_on[COL_LEVEL] ? k2d_payload_lev_soft : k2d_payload_soft) : (h->col_on[COL_LEVEL] ? k2d_payload_lev : k2d_payload);
+	static void (*const kernels[8])(K2Params) = { k2d_payload, k2d_payload_lev, k2d_payload_soft, k2d_payload_lev_soft,
+						     k2d_payload_car, k2d_payload_lev_car, k2d_payload_soft_car, k2d_payload_lev_soft_car };
+	void (*const kernel)(K2Params) = kernels[(h->col_on[COL_LEVEL] ? 1 : 0) | (h->col_on[COL_SOFT] ? 2 : 0) | (h->col_on[COL_CARRIER] ? 4 : 0)];
 	K2Params q = k2;
 	q.sel_mode = sel_mode;
 	hipLaunchKernelGGL(kernel, dim3((unsigned)h->k2d_grid, (unsigned)(VDL2_CS * h->S)), dim3(K2D_NT), 0, s, q);
@@ -1723,6 +1728,8 @@ static int enqueue_back(vdl2gpu_t *h)
 		ke.ldst = h->slab[h->back.slab].d_levels();
 		ke.soft = h->ring[ring].soft();	/* (nullptr without VDL2GPU_F_SOFT_RS) */
 		ke.sdst = h->slab[h->back.slab].d_soft();
+		ke.car = h->ring[ring].carrier();	/* (nullptr without VDL2GPU_F_CARRIER) */
+		ke.cdst = h->slab[h->back.slab].d_carrier();
 		hipLaunchKernelGGL(k_export_records, dim3((unsigned)h->n_cu), dim3(256), 0, ts, ke);
 		HIPCHK(h, hipGetLastError());
 		TRY(mark(h, pt, E_EXPORT_END, ts, true));
@@ -2061,6 +2068,7 @@ static int enqueue_front(vdl2gpu_t *h, hipStream_t fs, long long dec_base, PushT
 	k2.recs = h->ring[ring].d_recs;
 	k2.levels = h->ring[ring].levels();	/* (nullptr without VDL2GPU_F_LEVELS: nothing is measured) */
 	k2.soft = h->ring[ring].soft();	/* (nullptr without VDL2GPU_F_SOFT_RS) */
+	k2.carrier = h->ring[ring].carrier();	/* (nullptr without VDL2GPU_F_CARRIER) */
 	k2.outc = h->d_outc + 2 * ring;
 	k2.dec_base = dec_base;
 	k2.scan_lo = dec_base + VDL2_HIST;	/* the scan starts at the first carried frame that has its history */
@@ -2430,7 +2438,7 @@ static int collect_records(vdl2gpu_t *h, int ring, unsigned n)
 		HIPCHK(h, hipStreamSynchronize(h->copy_stream));
 		const vdl2gpu_burst_t *pin = reinterpret_cast<const vdl2gpu_burst_t *>(h->h_pin);
 		h->ready.recs.insert(h->ready.recs.end(), pin, pin + m);
-		for (int k = 0; k < VDL2_NCOL; ++k) {	/* the side columns present (40 bytes a record, or 2048: a pageable copy) */
+		for (int k = 0; k < VDL2_NCOL; ++k) {	/* the side columns present (32 or 40 bytes a record, or 2048: a pageable copy) */
 			if (!h->col_on[k])
 				continue;
 			std::vector<uint8_t> &q = h->ready.side[k];
@@ -2457,6 +2465,13 @@ static int collect_records(vdl2gpu_t *h, int ring, unsigned n)
 			l.sig_dbfs = (float)(10.0 * log10((double)l.sig_power / h->lev_k));
 			l.noise_dbfs = (float)(10.0 * log10((double)l.noise_power / h->lev_k));	/* (NaN stays NaN) */
 			memcpy(at, &l, sizeof l);
+		}
+		if (h->col_on[COL_CARRIER]) {
+			uint8_t *at = slot_of(h, handle).side[COL_CARRIER];
+			vdl2gpu_carrier_t c;
+			memcpy(&c, at, sizeof c);
+			if (vdl2gpu_carrier_from_sums(b.df, b.Fr, c.nsym, c.sum_e, c.sum_e2, &c) == VDL2GPU_OK)	/* (a channel with Fr == 0: the sums alone) */
+				memcpy(at, &c, sizeof c);
 		}
 		h->ready_idx.push_back(handle);
 	};
@@ -2817,16 +2832,16 @@ extern "C" int vdl2gpu_inflight(vdl2gpu_t *h)
 	return n;
 }
 
-/* The six collectors.  lv / sv: the side columns the caller wants beside the records (nullptr: not); lv_err / sv_err: what the entry
- * point says when the handle was made without that column. */
+/* The eight collectors.  lv / sv / cv: the side columns the caller wants beside the records (nullptr: not); lv_err / sv_err / cv_err:
+ * what the entry point says when the handle was made without that column. */
 static int poll_impl(vdl2gpu_t *h, vdl2gpu_burst_t *out, vdl2gpu_level_t *lv, vdl2gpu_soft_t *sv, int max, bool blocking,
-		     const char *lv_err = nullptr, const char *sv_err = nullptr)
+		     const char *lv_err = nullptr, const char *sv_err = nullptr, vdl2gpu_carrier_t *cv = nullptr, const char *cv_err = nullptr)
 {
 	if (!h || (max > 0 && !out) || max < 0)
 		return VDL2GPU_EINVAL;
 	HLOCK(h);
-	if ((lv && !h->col_on[COL_LEVEL]) || (sv && !h->col_on[COL_SOFT])) {
-		h->err = lv && !h->col_on[COL_LEVEL] ? lv_err : sv_err;
+	if ((lv && !h->col_on[COL_LEVEL]) || (sv && !h->col_on[COL_SOFT]) || (cv && !h->col_on[COL_CARRIER])) {
+		h->err = lv && !h->col_on[COL_LEVEL] ? lv_err : (sv && !h->col_on[COL_SOFT] ? sv_err : cv_err);
 		return VDL2GPU_EINVAL;
 	}
 	if (h->failed)
@@ -2838,6 +2853,7 @@ static int poll_impl(vdl2gpu_t *h, vdl2gpu_burst_t *out, vdl2gpu_level_t *lv, vd
 	void *side[VDL2_NCOL] = {};
 	side[COL_LEVEL] = lv;
 	side[COL_SOFT] = sv;
+	side[COL_CARRIER] = cv;
 	return hand_out(h, out, max, side);
 }
 
@@ -2869,6 +2885,38 @@ extern "C" int vdl2gpu_poll_soft(vdl2gpu_t *h, vdl2gpu_burst_t *out, vdl2gpu_lev
 extern "C" int vdl2gpu_poll_soft_ready(vdl2gpu_t *h, vdl2gpu_burst_t *out, vdl2gpu_level_t *lv, vdl2gpu_soft_t *soft, int max)
 {
 	return poll_impl(h, out, lv, soft, max, false, "vdl2gpu_poll_soft: lv needs VDL2GPU_F_LEVELS", "vdl2gpu_poll_soft: soft needs VDL2GPU_F_SOFT_RS");
+}
+
+extern "C" int vdl2gpu_poll_carrier(vdl2gpu_t *h, vdl2gpu_burst_t *out, vdl2gpu_level_t *lv, vdl2gpu_soft_t *soft, vdl2gpu_carrier_t *car, int max)
+{
+	return poll_impl(h, out, lv, soft, max, true, "vdl2gpu_poll_carrier: lv needs VDL2GPU_F_LEVELS", "vdl2gpu_poll_carrier: soft needs VDL2GPU_F_SOFT_RS",
+			 car, "vdl2gpu_poll_carrier: car needs VDL2GPU_F_CARRIER");
+}
+
+extern "C" int vdl2gpu_poll_carrier_ready(vdl2gpu_t *h, vdl2gpu_burst_t *out, vdl2gpu_level_t *lv, vdl2gpu_soft_t *soft, vdl2gpu_carrier_t *car, int max)
+{
+	return poll_impl(h, out, lv, soft, max, false, "vdl2gpu_poll_carrier: lv needs VDL2GPU_F_LEVELS", "vdl2gpu_poll_carrier: soft needs VDL2GPU_F_SOFT_RS",
+			 car, "vdl2gpu_poll_carrier: car needs VDL2GPU_F_CARRIER");
+}
+
+/* VDL2GPU_F_CARRIER: the derived values of a carrier record (include/vdl2gpu.h, vdl2gpu_carrier_t) -- the one statement of that
+ * arithmetic: collect_records calls it for every record. */
+extern "C" int vdl2gpu_carrier_from_sums(float df, int Fr, int nsym, int sum_e, unsigned sum_e2, vdl2gpu_carrier_t *out)
+{
+	if (!out || nsym <= 0 || Fr == 0)
+		return VDL2GPU_EINVAL;
+	const double m = (double)sum_e / nsym;
+	const double dphi_d = (double)df + M_PI / 8 + m * M_PI / 128;
+	const double var = (double)sum_e2 / nsym - m * m;
+	out->nsym = nsym;
+	out->sum_e = sum_e;
+	out->sum_e2 = sum_e2;
+	out->reserved = 0;
+	out->dphi = (float)dphi_d;
+	out->freq_hz = (float)(10500.0 * dphi_d / (2 * M_PI));
+	out->ppm = (float)(10500.0 * dphi_d / (2 * M_PI * (double)Fr) * 1e6);
+	out->rms_rad = (float)(sqrt(var > 0.0 ? var : 0.0) * M_PI / 128);
+	return VDL2GPU_OK;
 }
 
 extern "C" int vdl2gpu_get_stats(vdl2gpu_t *h, vdl2gpu_stats_t *out)

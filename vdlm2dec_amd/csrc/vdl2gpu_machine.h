@@ -310,6 +310,55 @@ template <int NT> __device__ __forceinline__ void burst_payload_soft(vdl2gpu_sof
 	}
 }
 
+/* VDL2GPU_F_CARRIER: the phase-error sums of the burst burst_payload has just decoded (vdl2gpu.h, vdl2gpu_carrier_t), all NT threads,
+ * called behind it.  One lane per symbol k = 8 .. kmax -- the slices the payload decode and the reliability map take --: the same Grey
+ * table index, from sph when the caller kept the phases there (K2d), else from two phases of its own (k2_fir_phase_tab, same result
+ * bits), and of it the distance e = (idx & 31) - 16 from the centre of its sector.  Integers only: each wavefront adds its lanes' e
+ * and e * e up (xor butterfly) and its first lane adds the two sums to acc[0], acc[1] in LDS (the caller's, two words nobody else
+ * uses meanwhile); thread 0 writes the record once.  Integer sums have no order: every kernel, path and NT leaves the same words.
+ * (block-uniform call: two barriers inside) */
+template <int NT> __device__ __forceinline__ void burst_payload_carrier(vdl2gpu_carrier_t *out, const float2 *x0, long long nstar, int clk0, float df,
+									int nbrow, int nlbyte, const float *sph, const float *lds_fir, int *acc)
+{
+	static_assert(NT % 64 == 0, "whole wavefronts");
+	const int tid = threadIdx.x;
+	int j0, rb;
+	burst_timing(clk0, &j0, &rb);
+	const BurstGeom g = burst_geom(nbrow, nlbyte);
+	const int kmax = (25 + 8 * (g.ND + g.NF) - 1) / 3;
+	const float2 *xs0 = x0 + (nstar + j0 - 16);
+	if (tid < 2)
+		acc[tid] = 0;
+	__syncthreads();
+	int se = 0, se2 = 0;
+	for (int k = 8 + tid; k <= kmax; k += NT) {
+		const float pprev = sph ? sph[k - 8] : k2_fir_phase_tab(xs0 + 8LL * (k - 1), rb, lds_fir, lds_fir + 72);
+		const float pk = sph ? sph[k - 7] : k2_fir_phase_tab(xs0 + 8LL * k, rb, lds_fir, lds_fir + 72);
+		const int e = (k2_grey_index(pk, pprev, df) & 31) - 16;
+		se += e;
+		se2 += e * e;
+	}
+#pragma unroll
+	for (int d = 32; d >= 1; d >>= 1) {
+		se += __shfl_xor(se, d, 64);
+		se2 += __shfl_xor(se2, d, 64);
+	}
+	if ((tid & 63) == 0) {
+		atomicAdd(&acc[0], se);
+		atomicAdd(&acc[1], se2);
+	}
+	__syncthreads();
+	if (tid == 0) {
+		vdl2gpu_carrier_t c;
+		c.nsym = kmax - 7;
+		c.sum_e = acc[0];
+		c.sum_e2 = (uint32_t)acc[1];	/* <= 256 nsym < 2^31 */
+		c.reserved = 0;
+		c.dphi = c.freq_hz = c.ppm = c.rms_rad = 0.0f;	/* the host derives them (vdl2gpu_carrier_from_sums) */
+		*out = c;
+	}
+}
+
 template <int NT> struct MachSharedT {
 	float pbuf[VDL2_NPH + NT];	/* phases: [0,68) = history ring */
 	float errs[NT + 2];		/* errs[t+2] = err of eval t; [0],[1] = p2err, perr */
@@ -333,6 +382,7 @@ struct MachCtx {
 	vdl2gpu_burst_t *recs;	/* sink: output ring, payload decoded at once (K2c serial stretches) ... */
 	vdl2gpu_level_t *levels;	/* ... with its level records (VDL2GPU_F_LEVELS), or nullptr */
 	vdl2gpu_soft_t *soft;	/* ... and its reliability maps (VDL2GPU_F_SOFT_RS), or nullptr */
+	vdl2gpu_carrier_t *carrier;	/* ... and its phase-error sums (VDL2GPU_F_CARRIER), or nullptr */
 	BurstDesc *desc;	/* ... or descriptor pool, payload decoded by K2d if selected (K2b, K2c) */
 	unsigned *sel, *nsel;	/* K2c: descriptors made by its serial stretches are on the real chain */
 	unsigned dyn_base;	/* first dynamic descriptor slot */
@@ -747,6 +797,8 @@ template <int NT, bool XL> __device__ __forceinline__ long long mach_commit_trig
 			__syncthreads();
 			burst_payload_soft<NT>(cx.soft + slot, x0, nstar, clk0, df, nbrow, nlbyte, nullptr, sh.smf, cx.grey);
 		}
+		if (!XL && !cx.desc && slot != 0xffffffffu && cx.carrier)	/* (block-uniform; sh.ctl[9], [10]: its two sums) */
+			burst_payload_carrier<NT>(cx.carrier + slot, x0, nstar, clk0, df, nbrow, nlbyte, nullptr, sh.smf, &sh.ctl[9]);
 		if (slot == 0xffffffffu)
 			out.badslot = 1;
 		out.nslots++;
@@ -865,6 +917,7 @@ __device__ __forceinline__ void mach_ctx(MachCtx &cx, const K2Params &p, int s, 
 		cx.recs = nullptr;
 		cx.levels = nullptr;
 		cx.soft = nullptr;
+		cx.carrier = nullptr;
 		cx.dyn_base = (unsigned)p.nstreams * VDL2_CS * VDL2_CAND_CAP * VDL2_CL_MAXB;
 		cx.desc = p.stage;
 		cx.rec_count = p.ctl + CTL_STAGE;
@@ -874,6 +927,7 @@ __device__ __forceinline__ void mach_ctx(MachCtx &cx, const K2Params &p, int s, 
 		cx.recs = p.recs;
 		cx.levels = p.levels;
 		cx.soft = p.soft;
+		cx.carrier = p.carrier;
 		cx.dyn_base = 0;
 		cx.desc = nullptr;
 		cx.rec_count = p.outc;

@@ -1265,9 +1265,12 @@ void k2f_commit(K2Params p)
  * inlined; it carries none of it */
 /* SOFT (VDL2GPU_F_SOFT_RS): behind every burst all its lanes write the reliability map from the phases still in sph
  * (burst_payload_soft) -- k2d_payload_soft, and k2d_payload_lev_soft with both flags */
-template <bool LEV, bool SOFT> __device__ __forceinline__ void k2d_run(const K2Params &p)
+/* CAR (VDL2GPU_F_CARRIER): behind every burst one lane per symbol adds up the slices' distance from their sectors' centres, again
+ * from the phases in sph (burst_payload_carrier) -- four kernels more, k2d_payload*_car, so that the four above keep their code */
+template <bool LEV, bool SOFT, bool CAR = false> __device__ __forceinline__ void k2d_run(const K2Params &p)
 {
 	__shared__ unsigned s_slot;
+	__shared__ int s_car[2];	/* (CAR only: the burst's two sums) */
 	__shared__ float sph[VDL2_MAXSYM];
 	__shared__ float s_tabs[72 + VDL2_ATAN_ROWS * VDL2_ATAN_STRIDE + 3 * 257];	/* mflt[], atanf range table, Grey1/2/3 (see burst_payload) */
 	const int sc = (int)blockIdx.y;	/* stream * VDL2_CS + channel slot, like everywhere else: the grid spans all VDL2_CS slots of every stream */
@@ -1349,6 +1352,8 @@ template <bool LEV, bool SOFT> __device__ __forceinline__ void k2d_run(const K2P
 				__syncthreads();
 				burst_payload_soft<K2D_NT>(p.soft + slot, x0, d.nstar, d.clk0, d.df, d.nbrow, d.nlbyte, sph, s_tabs, s_tabs + 72 + VDL2_ATAN_ROWS * VDL2_ATAN_STRIDE);
 			}
+			if (CAR)
+				burst_payload_carrier<K2D_NT>(p.carrier + slot, x0, d.nstar, d.clk0, d.df, d.nbrow, d.nlbyte, sph, s_tabs, s_car);
 		}
 		__syncthreads();
 	}
@@ -1376,6 +1381,30 @@ __global__ __launch_bounds__(K2D_NT) __attribute__((amdgpu_waves_per_eu(4, 8)))
 void k2d_payload_lev_soft(K2Params p)
 {
 	k2d_run<true, true>(p);
+}
+
+__global__ __launch_bounds__(K2D_NT) __attribute__((amdgpu_waves_per_eu(4, 8)))
+void k2d_payload_car(K2Params p)
+{
+	k2d_run<false, false, true>(p);
+}
+
+__global__ __launch_bounds__(K2D_NT) __attribute__((amdgpu_waves_per_eu(4, 8)))
+void k2d_payload_lev_car(K2Params p)
+{
+	k2d_run<true, false, true>(p);
+}
+
+__global__ __launch_bounds__(K2D_NT) __attribute__((amdgpu_waves_per_eu(4, 8)))
+void k2d_payload_soft_car(K2Params p)
+{
+	k2d_run<false, true, true>(p);
+}
+
+__global__ __launch_bounds__(K2D_NT) __attribute__((amdgpu_waves_per_eu(4, 8)))
+void k2d_payload_lev_soft_car(K2Params p)
+{
+	k2d_run<true, true, true>(p);
 }
 
 #endif

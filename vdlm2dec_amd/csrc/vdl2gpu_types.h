@@ -254,6 +254,7 @@ struct K2Params {
 	HeadTap *headtap;	/* diagnostics: every trigger any kernel of the push handled (nullptr: off) */
 	unsigned *headtap_n;
 	unsigned headtap_cap;
+	vdl2gpu_carrier_t *carrier;	/* VDL2GPU_F_CARRIER: one record of phase-error sums per record slot of `recs`, else nullptr (last: the other members keep their place) */
 };
 #define CTL_OUT 0
 #define CTL_OUT_OVF 1

@@ -46,6 +46,31 @@ class Level:
         return cls(v.sig_dbfs, v.noise_dbfs, v.sig_power, v.noise_power, v.sym_first_dec, v.nsym, v.subphase, v.noise_blocks)
 
 
+@dataclass(frozen=True)
+class Carrier:
+    """vdl2gpu_carrier_t: the burst's true carrier offset and phase-error spread (Receiver(carrier=True); definitions in include/vdl2gpu.h)."""
+    nsym: int
+    sum_e: int
+    sum_e2: int
+    dphi: float                # rad per symbol beyond the data
+    freq_hz: float             # positive: the carrier lies above the channel centre as mixed
+    ppm: float
+    rms_rad: float             # near pi/8: not to be trusted
+
+    @classmethod
+    def from_c(cls, v) -> "Carrier":
+        return cls(v.nsym, v.sum_e, v.sum_e2, v.dphi, v.freq_hz, v.ppm, v.rms_rad)
+
+
+def carrier_from_sums(df: float, Fr: int, nsym: int, sum_e: int, sum_e2: int) -> Carrier:
+    """vdl2gpu_carrier_from_sums: the derived values of a carrier record, as the library computes them (no GPU needed)."""
+    c = _lib.CarrierT()
+    rc = _lib.load().vdl2gpu_carrier_from_sums(df, Fr, nsym, sum_e, sum_e2, C.byref(c))
+    if rc < 0:
+        raise _lib.Vdl2GpuError("vdl2gpu_carrier_from_sums failed")
+    return Carrier.from_c(c)
+
+
 @dataclass
 class Burst:
     """The msgblk_t fields the DSP fills (vdlm2.h:39-47) plus stream-time stamps."""
@@ -63,6 +88,7 @@ class Burst:
     data: bytes            # 8 rows x 255 bytes, row-major
     level: Optional[Level] = None   # Receiver(levels=True) only; not part of key()
     soft: Optional[np.ndarray] = None   # Receiver(soft_rs=True) only: uint8 (8, 255) byte reliabilities; not part of key()
+    carrier: Optional[Carrier] = None   # Receiver(carrier=True) only; not part of key()
 
     def key(self):
         return (self.stream, self.chn, self.nbrow, self.nlbyte, self.data)
@@ -78,7 +104,8 @@ class Receiver:
                  fmt: str = "cu8", max_push: int = 1 << 22, device: int = 0, sdrclk: int = 0,
                  max_bursts: int = 0, keep_dec: bool = False, serial: bool = False, full_scan: bool = False,
                  frames: bool = False, rtl_quirk: bool = False, flags: int = 0, testhooks: bool = False,
-                 levels: bool = False, soft_rs: bool = False, exact_fo: bool = False):
+                 levels: bool = False, soft_rs: bool = False, exact_fo: bool = False, carrier: bool = False):
+        # carrier: VDL2GPU_F_CARRIER, every burst's carrier offset and phase-error spread (Burst.carrier)
         # exact_fo: VDL2GPU_F_EXACT_FO, channel offsets off the 25 kHz grid with a phase-continuous oscillator (include/vdl2gpu.h)
         # testhooks: load libvdl2gpu_test.so, the build that honours F_TEST_NOREGION / VDL2GPU_PRIM_DROP / VDL2GPU_SPLIT_SAMPLES
         self.L = _lib.load(testhooks=testhooks or bool(flags & _lib.F_TEST_NOREGION))
@@ -106,10 +133,11 @@ class Receiver:
         cfg.max_push = max_push
         cfg.device = device
         cfg.max_bursts = max_bursts
-        cfg.flags = (_lib.F_KEEP_DEC if keep_dec else 0) | (_lib.F_SERIAL if serial else 0) | (_lib.F_FULLSCAN if full_scan else 0) | (_lib.F_FRAMES if frames else 0) | (_lib.F_RTL_QUIRK if rtl_quirk else 0) | (_lib.F_LEVELS if levels else 0) | (_lib.F_SOFT_RS if soft_rs else 0) | (_lib.F_EXACT_FO if exact_fo else 0) | flags
+        cfg.flags = (_lib.F_KEEP_DEC if keep_dec else 0) | (_lib.F_SERIAL if serial else 0) | (_lib.F_FULLSCAN if full_scan else 0) | (_lib.F_FRAMES if frames else 0) | (_lib.F_RTL_QUIRK if rtl_quirk else 0) | (_lib.F_LEVELS if levels else 0) | (_lib.F_SOFT_RS if soft_rs else 0) | (_lib.F_EXACT_FO if exact_fo else 0) | (_lib.F_CARRIER if carrier else 0) | flags
         self.max_push = max_push
         self.levels = bool(cfg.flags & _lib.F_LEVELS)
         self.soft_rs = bool(cfg.flags & _lib.F_SOFT_RS)
+        self.carrier = bool(cfg.flags & _lib.F_CARRIER)
         self.h = C.c_void_p()
         rc = self.L.vdl2gpu_create(C.byref(cfg), C.byref(self.h))
         if rc != 0:
@@ -165,8 +193,12 @@ class Receiver:
         buf = (_lib.BurstT * max_bursts)()
         lv = (_lib.LevelT * max_bursts)() if self.levels else None
         sv = (_lib.SoftT * max_bursts)() if self.soft_rs else None
+        cv = (_lib.CarrierT * max_bursts)() if self.carrier else None
         while True:
-            if sv is not None:
+            if cv is not None:
+                fn = self.L.vdl2gpu_poll_carrier_ready if ready else self.L.vdl2gpu_poll_carrier
+                n = self._check(fn(self.h, buf, lv, sv, cv, max_bursts))
+            elif sv is not None:
                 fn = self.L.vdl2gpu_poll_soft_ready if ready else self.L.vdl2gpu_poll_soft
                 n = self._check(fn(self.h, buf, lv, sv, max_bursts))
             elif lv is not None:
@@ -179,7 +211,8 @@ class Receiver:
                 b = buf[i]
                 out.append(Burst(b.stream, b.chn, b.Fr, b.nbrow, b.nlbyte, b.df, b.ppm, b.trig_dec, b.end_dec,
                                  b.trig_sample, b.end_sample, bytes(b.data), Level.from_c(lv[i]) if lv is not None else None,
-                                 np.frombuffer(bytes(sv[i].rel), np.uint8).reshape(8, 255).copy() if sv is not None else None))
+                                 np.frombuffer(bytes(sv[i].rel), np.uint8).reshape(8, 255).copy() if sv is not None else None,
+                                 Carrier.from_c(cv[i]) if cv is not None else None))
             if n < max_bursts:
                 return out
 
@@ -200,6 +233,12 @@ class Receiver:
         """vdl2gpu_poll_soft(_ready) into caller-owned (lib.BurstT / lib.LevelT / lib.SoftT * n) arrays; lv and sv may be None."""
         fn = self.L.vdl2gpu_poll_soft_ready if ready else self.L.vdl2gpu_poll_soft
         return self._check(fn(self.h, buf, lv, sv, max_bursts))
+
+    def poll_carrier_raw(self, buf, lv, sv, cv, max_bursts: int, ready: bool = False) -> int:
+        """vdl2gpu_poll_carrier(_ready) into caller-owned (lib.BurstT / lib.LevelT / lib.SoftT / lib.CarrierT * n) arrays; lv, sv and cv may
+        each be None."""
+        fn = self.L.vdl2gpu_poll_carrier_ready if ready else self.L.vdl2gpu_poll_carrier
+        return self._check(fn(self.h, buf, lv, sv, cv, max_bursts))
 
     def poll_ready_raw(self, buf, max_bursts: int) -> int:
         """vdl2gpu_poll_ready: bursts of pushes that have already finished; never waits."""
