@@ -2,7 +2,7 @@
 whole HIP path, judged by the oracle.
 
 burst_geom / burst_scatter replace the reference's byte-by-byte interleaver with divisions, burst_payload strides lanes over the ND + NF
-bytes, burst_payload_soft and burst_payload_levels repeat the geometry, k4_frames restates the last row's parity count: `geom` has one
+bytes, burst_payload_soft and burst_payload_levels repeat the geometry, k4_frames takes a row's parity count from burst_geom for the soft row rule: `geom` has one
 clean burst for nbrow 1 .. 8 x the last row's byte counts either side of every parity threshold, for the byte counts either side of the
 lane strides, and one geometry in every timing class; `geom_frames` the same with a real frame in each and a flipped byte in the last
 row.  `edge_cut` walks a burst's last symbol, header symbol 8 and trigger across the end of a push one frame at a time.

@@ -1549,6 +1549,23 @@ extern "C" int vdl2gpu_ring_commit(vdl2gpu_t *h, size_t nsamples)
 	return rc;
 }
 
+/* k4_frames on the records of output ring `ring` where they lie: compact entries, the record count from the device.  fmask: not
+ * nullptr when K2d's second pass tags void records (see K4Params) */
+static K4Params k4_ring_params(vdl2gpu_t *h, int ring, const unsigned *fmask)
+{
+	K4Params k4{};
+	k4.recs = h->ring[ring].d_recs;
+	k4.nrecs_dev = h->d_outc + 2 * ring;
+	k4.rec_cap = h->rec_cap;
+	k4.frames = h->ring[ring].d_frames;
+	k4.nframes = h->d_fcnt + 4 * ring;
+	k4.frame_cap = h->frame_cap;
+	k4.compact = 1;
+	k4.tabs = h->d_k4tab;
+	k4.fmask = fmask;
+	k4.soft = h->ring[ring].soft();	/* (nullptr without VDL2GPU_F_SOFT_RS: the reference's block path) */
+	return k4;
+}
 
 /* The BACK stage of a push (see vdl2gpu::Back): resolver, payload decode beside the verify pass, repair rounds, commit,
  * block path, counters -- on the main stream, behind the previous push's back stage and behind this push's front. */
@@ -1701,19 +1718,7 @@ static int enqueue_back(vdl2gpu_t *h)
 		/* block path on the records where they lie (vdlm2.c:84-161).  In the chain, not beside it:
 		 * a latency-bound kernel like this one and the next push's scan slow each other down by
 		 * more than the overlap saves. */
-		K4Params k4{};
-		k4.recs = h->ring[ring].d_recs;
-		k4.nrecs_dev = h->d_outc + 2 * ring;
-		k4.rec_cap = h->rec_cap;
-		k4.frames = h->ring[ring].d_frames;
-		k4.nframes = h->d_fcnt + 4 * ring;
-		k4.frame_cap = h->frame_cap;
-		k4.compact = 1;
-		k4.tabs = h->d_k4tab;
-		k4.fmask = spec ? h->set[par].k2.fmask : nullptr;
-		k4.dbg = h->knob.debug_counters ? h->d_dbg : nullptr;
-		k4.soft = h->ring[ring].soft();	/* (nullptr without VDL2GPU_F_SOFT_RS: the reference's block path) */
-		hipLaunchKernelGGL(k4_frames, dim3((unsigned)h->n_cu * 16), dim3(K4_NT), 0, ts, k4);
+		hipLaunchKernelGGL(k4_frames, dim3((unsigned)h->n_cu * 16), dim3(K4_NT), 0, ts, k4_ring_params(h, ring, spec ? h->set[par].k2.fmask : nullptr));
 		HIPCHK(h, hipGetLastError());
 	}
 	TRY(mark(h, pt, E_BLOCKS_END, ts));
@@ -2493,7 +2498,80 @@ static int collect_records(vdl2gpu_t *h, int ring, unsigned n)
 	return VDL2GPU_OK;
 }
 
-/* harvest_ring, third part (VDL2GPU_F_FRAMES): the frames of the push's n records join the host queue. */
+/* harvest_ring, third part (VDL2GPU_F_FRAMES): the frames of the push's n records join the host queue, in four steps.
+ * The queue is bounded like the burst queue: the oldest frames go, counted; and what has been handed out leaves the storage. */
+static void trim_frame_queue(vdl2gpu_t *h)
+{
+	const size_t qmax = 4 * (size_t)h->rec_cap;
+	if (h->fready_idx.size() - h->fready_pos > qmax) {
+		const size_t drop = h->fready_idx.size() - h->fready_pos - qmax;
+		h->fready_pos += drop;
+		h->frames_dropped += drop;
+	}
+	if (h->fready_pos == h->fready_idx.size()) {
+		h->fready.clear();
+		h->fready_idx.clear();
+		h->fready_pos = 0;
+	} else if (h->fready_pos > 1024 && h->fready_pos > h->fready_idx.size() / 2) {	/* compact: entries are self-delimiting */
+		std::vector<uint8_t> keep;
+		std::vector<size_t> kidx;
+		for (size_t i = h->fready_pos; i < h->fready_idx.size(); ++i) {
+			const uint8_t *e = h->fready.data() + h->fready_idx[i];
+			kidx.push_back(keep.size());
+			keep.insert(keep.end(), e, e + k4_entry_bytes(reinterpret_cast<const vdl2gpu_frame_t *>(e)->len));
+		}
+		h->fready.swap(keep);
+		h->fready_idx.swap(kidx);
+		h->fready_pos = 0;
+	}
+}
+
+/* `bytes` of device memory come to the host through the page-locked buffer, a buffer's worth at a time: take(chunk, its bytes) */
+template <class F> static int copy_out(vdl2gpu_t *h, const void *src, size_t bytes, F &&take)
+{
+	const size_t pin_bytes = (size_t)h->pin_recs * sizeof(vdl2gpu_burst_t);
+	for (size_t done = 0; done < bytes; done += pin_bytes) {
+		const size_t m = std::min(pin_bytes, bytes - done);
+		HIPCHK(h, hipMemcpyAsync(h->h_pin, (const char *)src + done, m, hipMemcpyDeviceToHost, h->copy_stream));
+		HIPCHK(h, hipStreamSynchronize(h->copy_stream));
+		take(reinterpret_cast<const uint8_t *>(h->h_pin), m);
+	}
+	return VDL2GPU_OK;
+}
+
+/* walk the entries behind `old` (56 header bytes + len data bytes, rounded up to 8): each joins the index */
+static void index_frames(vdl2gpu_t *h, size_t old)
+{
+	const size_t hdr = offsetof(vdl2gpu_frame_t, data);
+	for (size_t off = old; off + hdr <= h->fready.size();) {
+		vdl2gpu_frame_t *f = reinterpret_cast<vdl2gpu_frame_t *>(h->fready.data() + off);
+		if (f->len < 0 || f->len > VDL2GPU_MAXFRAME || off + hdr + (size_t)f->len > h->fready.size())
+			break;
+		f->ppm = (float)((double)(10500.0f * f->df) / (2.0 * M_PI * (double)f->Fr) * 1e6);	/* d8psk.c:302 */
+		f->block = -1;
+		h->fready_idx.push_back((uint32_t)off);
+		off += k4_entry_bytes(f->len);
+	}
+}
+
+/* the order vdl2gpu_poll_frames hands frames out in: by the burst's end, then stream, channel, place in the burst */
+static bool frame_earlier(const vdl2gpu_frame_t &a, const vdl2gpu_frame_t &b)
+{
+	if (a.end_dec != b.end_dec)
+		return a.end_dec < b.end_dec;
+	if (a.stream != b.stream)
+		return a.stream < b.stream;
+	if (a.chn != b.chn)
+		return a.chn < b.chn;
+	return a.seq < b.seq;
+}
+
+/* the order of vdl2gpu_decode_blocks: by the caller's block, then place in the burst */
+static bool frame_by_block(const vdl2gpu_frame_t &a, const vdl2gpu_frame_t &b)
+{
+	return a.block != b.block ? a.block < b.block : a.seq < b.seq;
+}
+
 static int collect_frames(vdl2gpu_t *h, int ring, unsigned n)
 {
 	const OutRing &rg = h->ring[ring];
@@ -2504,83 +2582,21 @@ static int collect_frames(vdl2gpu_t *h, int ring, unsigned n)
 	h->frames_dropped += h->h_pin_cnt[32 * ring + 5];
 	if (!n)
 		return VDL2GPU_OK;
-	{	/* bounded like the burst queue: the oldest frames go, counted */
-		const size_t qmax = 4 * (size_t)h->rec_cap;
-		if (h->fready_idx.size() - h->fready_pos > qmax) {
-			const size_t drop = h->fready_idx.size() - h->fready_pos - qmax;
-			h->fready_pos += drop;
-			h->frames_dropped += drop;
-		}
-	}
-	if (h->fready_pos == h->fready_idx.size()) {
-		h->fready.clear();
-		h->fready_idx.clear();
-		h->fready_pos = 0;
-	} else if (h->fready_pos > 1024 && h->fready_pos > h->fready_idx.size() / 2) {	/* compact: entries are self-delimiting */
-		std::vector<uint8_t> keep;
-		std::vector<size_t> kidx;
-		const size_t hdr0 = offsetof(vdl2gpu_frame_t, data);
-		for (size_t i = h->fready_pos; i < h->fready_idx.size(); ++i) {
-			const uint8_t *e = h->fready.data() + h->fready_idx[i];
-			const size_t sz = (hdr0 + (size_t)reinterpret_cast<const vdl2gpu_frame_t *>(e)->len + 7) & ~(size_t)7;
-			kidx.push_back(keep.size());
-			keep.insert(keep.end(), e, e + sz);
-		}
-		h->fready.swap(keep);
-		h->fready_idx.swap(kidx);
-		h->fready_pos = 0;
-	}
-	const size_t old = h->fready.size();
-	const size_t hdr = offsetof(vdl2gpu_frame_t, data);
-	const size_t pin_bytes = (size_t)h->pin_recs * sizeof(vdl2gpu_burst_t);
+	trim_frame_queue(h);
+	const size_t old = h->fready.size(), iold = h->fready_idx.size();
 	/* the records' slots: keep the occupied ones, packed like arena entries */
-	const size_t slot_bytes = (size_t)n * K4_SLOT;
-	for (size_t done = 0; done < slot_bytes; done += pin_bytes) {
-		const size_t m = std::min(pin_bytes, slot_bytes - done);
-		HIPCHK(h, hipMemcpyAsync(h->h_pin, (const char *)rg.d_frames + done, m, hipMemcpyDeviceToHost, h->copy_stream));
-		HIPCHK(h, hipStreamSynchronize(h->copy_stream));
-		const uint8_t *pin = reinterpret_cast<const uint8_t *>(h->h_pin);
+	TRY(copy_out(h, rg.d_frames, (size_t)n * K4_SLOT, [h](const uint8_t *pin, size_t m) {
 		for (size_t o = 0; o < m; o += K4_SLOT) {
-			const vdl2gpu_frame_t *f = reinterpret_cast<const vdl2gpu_frame_t *>(pin + o);
-			if (f->len <= 0 || hdr + (size_t)f->len > K4_SLOT)
-				continue;
-			const size_t sz = (hdr + (size_t)f->len + 7) & ~(size_t)7;
-			h->fready.insert(h->fready.end(), pin + o, pin + o + sz);
+			const int len = reinterpret_cast<const vdl2gpu_frame_t *>(pin + o)->len;
+			if (len > 0 && k4_fits_slot(len))
+				h->fready.insert(h->fready.end(), pin + o, pin + o + k4_entry_bytes(len));
 		}
-	}
-	if (nbytes) {
-		const size_t at = h->fready.size();
-		h->fready.resize(at + nbytes);
-		for (size_t done = 0; done < nbytes; done += pin_bytes) {
-			const size_t m = std::min(pin_bytes, (size_t)nbytes - done);
-			HIPCHK(h, hipMemcpyAsync(h->h_pin, (const char *)rg.d_frames + arena0 + done, m, hipMemcpyDeviceToHost,
-						 h->copy_stream));
-			HIPCHK(h, hipStreamSynchronize(h->copy_stream));
-			memcpy(h->fready.data() + at + done, h->h_pin, m);
-		}
-	}
-	/* walk the entries (56 header bytes + len data bytes, rounded up to 8) */
-	const size_t iold = h->fready_idx.size();
-	for (size_t off = old; off + hdr <= h->fready.size();) {
-		vdl2gpu_frame_t *f = reinterpret_cast<vdl2gpu_frame_t *>(h->fready.data() + off);
-		if (f->len < 0 || f->len > VDL2GPU_MAXFRAME || off + hdr + (size_t)f->len > h->fready.size())
-			break;
-		f->ppm = (float)((double)(10500.0f * f->df) / (2.0 * M_PI * (double)f->Fr) * 1e6);	/* d8psk.c:302 */
-		f->block = -1;
-		h->fready_idx.push_back((uint32_t)off);
-		off += (hdr + (size_t)f->len + 7) & ~(size_t)7;
-	}
+	}));
+	TRY(copy_out(h, (const char *)rg.d_frames + arena0, nbytes, [h](const uint8_t *pin, size_t m) { h->fready.insert(h->fready.end(), pin, pin + m); }));
+	index_frames(h, old);
 	const uint8_t *fd = h->fready.data();
 	std::sort(h->fready_idx.begin() + iold, h->fready_idx.end(), [fd](size_t x, size_t y) {
-		const vdl2gpu_frame_t &a = *reinterpret_cast<const vdl2gpu_frame_t *>(fd + x);
-		const vdl2gpu_frame_t &b = *reinterpret_cast<const vdl2gpu_frame_t *>(fd + y);
-		if (a.end_dec != b.end_dec)
-			return a.end_dec < b.end_dec;
-		if (a.stream != b.stream)
-			return a.stream < b.stream;
-		if (a.chn != b.chn)
-			return a.chn < b.chn;
-		return a.seq < b.seq;
+		return frame_earlier(*reinterpret_cast<const vdl2gpu_frame_t *>(fd + x), *reinterpret_cast<const vdl2gpu_frame_t *>(fd + y));
 	});
 	return VDL2GPU_OK;
 }
@@ -2686,6 +2702,37 @@ extern "C" int vdl2gpu_decode_blocks(vdl2gpu_t *h, const vdl2gpu_burst_t *blocks
 	return vdl2gpu_decode_blocks_soft(h, blocks, nullptr, n, frames, max_frames, dropped);
 }
 
+/* the device memory of one vdl2gpu_decode_blocks call: freed on every way out of it */
+struct BlockTemps {
+	vdl2gpu_burst_t *blk = nullptr;
+	vdl2gpu_soft_t *soft = nullptr;
+	vdl2gpu_frame_t *fr = nullptr;
+	unsigned *cnt = nullptr;
+	~BlockTemps()
+	{
+		(void)hipFree(blk);
+		(void)hipFree(soft);
+		(void)hipFree(fr);
+		(void)hipFree(cnt);
+	}
+};
+
+/* k4_frames on n records of the caller's: an array of vdl2gpu_frame_t, the record count by value */
+static K4Params k4_block_params(vdl2gpu_t *h, const BlockTemps &d, int n, int max_frames)
+{
+	K4Params k4{};
+	k4.recs = d.blk;
+	k4.nrecs = (unsigned)n;
+	k4.rec_cap = (unsigned)n;
+	k4.frames = d.fr;
+	k4.nframes = d.cnt;
+	k4.frame_cap = (unsigned)max_frames;
+	k4.compact = 0;
+	k4.tabs = h->d_k4tab;
+	k4.soft = d.soft;
+	return k4;
+}
+
 extern "C" int vdl2gpu_decode_blocks_soft(vdl2gpu_t *h, const vdl2gpu_burst_t *blocks, const vdl2gpu_soft_t *soft, int n,
 					  vdl2gpu_frame_t *frames, int max_frames, int *dropped)
 {
@@ -2697,70 +2744,40 @@ extern "C" int vdl2gpu_decode_blocks_soft(vdl2gpu_t *h, const vdl2gpu_burst_t *b
 		return 0;
 	HLOCK(h);
 	HIPCHK(h, hipSetDevice(h->cfg.device));
-	vdl2gpu_burst_t *d_blk = nullptr;
-	vdl2gpu_soft_t *d_soft = nullptr;
-	vdl2gpu_frame_t *d_fr = nullptr;
-	unsigned *d_cnt = nullptr;
-	auto cleanup = [&]() {
-		(void)hipFree(d_blk);
-		(void)hipFree(d_soft);
-		(void)hipFree(d_fr);
-		(void)hipFree(d_cnt);
-	};
-	hipError_t e = hipMalloc(&d_blk, (size_t)n * sizeof(vdl2gpu_burst_t));
-	if (e == hipSuccess && soft)
-		e = hipMalloc(&d_soft, (size_t)n * sizeof(vdl2gpu_soft_t));
-	if (e == hipSuccess)
-		e = hipMalloc(&d_fr, (size_t)max_frames * sizeof(vdl2gpu_frame_t));
-	if (e == hipSuccess)
-		e = hipMalloc(&d_cnt, 4 * sizeof(unsigned));
+#define BLKCHK(expr)                                                          \
+	do {                                                                  \
+		const hipError_t e__ = (expr);                                \
+		if (e__ != hipSuccess)                                        \
+			return hip_failed(h, "vdl2gpu_decode_blocks", e__);   \
+	} while (0)
+	BlockTemps d;
+	BLKCHK(hipMalloc(&d.blk, (size_t)n * sizeof(vdl2gpu_burst_t)));
+	if (soft)
+		BLKCHK(hipMalloc(&d.soft, (size_t)n * sizeof(vdl2gpu_soft_t)));
+	BLKCHK(hipMalloc(&d.fr, (size_t)max_frames * sizeof(vdl2gpu_frame_t)));
+	BLKCHK(hipMalloc(&d.cnt, 4 * sizeof(unsigned)));
 	/* on the stream the kernel runs on: that stream does not wait for the legacy default stream, and a
 	 * plain hipMemset() that lands after the kernel's first atomics loses frames */
-	if (e == hipSuccess)
-		e = hipMemcpyAsync(d_blk, blocks, (size_t)n * sizeof(vdl2gpu_burst_t), hipMemcpyHostToDevice, h->copy_stream);
-	if (e == hipSuccess && soft)
-		e = hipMemcpyAsync(d_soft, soft, (size_t)n * sizeof(vdl2gpu_soft_t), hipMemcpyHostToDevice, h->copy_stream);
-	if (e == hipSuccess)
-		e = hipMemsetAsync(d_cnt, 0, 4 * sizeof(unsigned), h->copy_stream);
+	BLKCHK(hipMemcpyAsync(d.blk, blocks, (size_t)n * sizeof(vdl2gpu_burst_t), hipMemcpyHostToDevice, h->copy_stream));
+	if (soft)
+		BLKCHK(hipMemcpyAsync(d.soft, soft, (size_t)n * sizeof(vdl2gpu_soft_t), hipMemcpyHostToDevice, h->copy_stream));
+	BLKCHK(hipMemsetAsync(d.cnt, 0, 4 * sizeof(unsigned), h->copy_stream));
+	const unsigned grid = (unsigned)std::min<long long>(n, (long long)h->n_cu * 32);
+	hipLaunchKernelGGL(k4_frames, dim3(grid), dim3(K4_NT), 0, h->copy_stream, k4_block_params(h, d, n, max_frames));
+	BLKCHK(hipGetLastError());
+	BLKCHK(hipStreamSynchronize(h->copy_stream));
 	unsigned cnt[2] = {0, 0};
-	if (e == hipSuccess) {
-		K4Params k4{};
-		k4.recs = d_blk;
-		k4.nrecs_dev = nullptr;
-		k4.nrecs = (unsigned)n;
-		k4.rec_cap = (unsigned)n;
-		k4.frames = d_fr;
-		k4.nframes = d_cnt;
-		k4.frame_cap = (unsigned)max_frames;
-		k4.compact = 0;
-		k4.tabs = h->d_k4tab;
-		k4.soft = d_soft;
-		const unsigned grid = (unsigned)std::min<long long>(n, (long long)h->n_cu * 32);
-		hipLaunchKernelGGL(k4_frames, dim3(grid), dim3(K4_NT), 0, h->copy_stream, k4);
-		e = hipGetLastError();
-		if (e == hipSuccess)
-			e = hipStreamSynchronize(h->copy_stream);
-	}
-	if (e == hipSuccess)
-		e = hipMemcpyAsync(cnt, d_cnt, sizeof cnt, hipMemcpyDeviceToHost, h->copy_stream);
-	if (e == hipSuccess)
-		e = hipStreamSynchronize(h->copy_stream);
+	BLKCHK(hipMemcpyAsync(cnt, d.cnt, sizeof cnt, hipMemcpyDeviceToHost, h->copy_stream));
+	BLKCHK(hipStreamSynchronize(h->copy_stream));
 	const int nf = (int)std::min<unsigned>(cnt[0], (unsigned)max_frames);
-	if (e == hipSuccess && nf > 0) {
-		e = hipMemcpyAsync(frames, d_fr, (size_t)nf * sizeof(vdl2gpu_frame_t), hipMemcpyDeviceToHost, h->copy_stream);
-		if (e == hipSuccess)
-			e = hipStreamSynchronize(h->copy_stream);
+	if (nf > 0) {
+		BLKCHK(hipMemcpyAsync(frames, d.fr, (size_t)nf * sizeof(vdl2gpu_frame_t), hipMemcpyDeviceToHost, h->copy_stream));
+		BLKCHK(hipStreamSynchronize(h->copy_stream));
 	}
-	cleanup();
-	if (e != hipSuccess) {
-		h->err = std::string("vdl2gpu_decode_blocks: ") + hipGetErrorString(e);
-		return VDL2GPU_EHIP;
-	}
+#undef BLKCHK
 	if (dropped)
 		*dropped = (int)cnt[1];
-	std::sort(frames, frames + nf, [](const vdl2gpu_frame_t &a, const vdl2gpu_frame_t &b) {
-		return a.block != b.block ? a.block < b.block : a.seq < b.seq;
-	});
+	std::sort(frames, frames + nf, frame_by_block);
 	return nf;
 }
 
@@ -3056,7 +3073,7 @@ extern "C" int vdl2gpu_debug_atan2f(vdl2gpu_t *h, const float *y, const float *x
 	}
 	if (e == hipSuccess)
 		e = hipMemcpy(out, d + 2 * n, n * sizeof(float), hipMemcpyDeviceToHost);
-	(void)hipFree(d);	/* (a call's temporary, explicit like vdl2gpu_decode_blocks_soft's) */
+	(void)hipFree(d);	/* (a call's temporary) */
 	if (e != hipSuccess) {
 		h->err = hipGetErrorString(e);
 		return VDL2GPU_EHIP;

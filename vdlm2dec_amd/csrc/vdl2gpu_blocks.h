@@ -6,21 +6,13 @@
  *                                  GF(256)/0x187, first root alpha^120
  *   check_frame() vdlm2.c:38-61    length >= 13, FCS-16 (crc.c) residue 0xf0b8
  *
- * One wavefront per burst record.  Integer/byte work, bit-exact by construction:
- *   syndromes      64 lanes x 4 bytes each, XOR-reduced (a syndrome is a field sum: any order)
- *   BM/Chien/Forney  a coefficient (a candidate position, a root) per lane; each step performs the
- *                  reference's field operations on the operands the reference's loops read, so that
- *                  miscorrections, the early exits and the partially applied corrections of an
- *                  uncorrectable row agree
- *   un-stuffing    a stuffed zero is a zero after exactly five ones: the run of ones in front of a
- *                  bit does not depend on what was dropped before, so every lane knows the run it
- *                  starts in from a scan of (all ones?, trailing ones) and drops its own zeros;
- *                  a prefix sum of the kept counts places its bits in the output
- *   flag hunt      the reference ORs bits into hdata[0] until it equals 0x7e (vdlm2.c:124-139): a
- *                  prefix OR over the un-stuffed bytes finds that byte; flags right behind it are
- *                  swallowed; from then on every byte is stored and every 0x7e closes a candidate frame
- *                  that starts at hdata[1] -- all candidates share the start, so one running FCS serves
- * Records come from the output ring of the demodulator (device memory) or from the host.
+ * One wavefront per burst record; records come from the output ring of the demodulator (device memory) or from the host.
+ * Integer/byte work, bit-exact by construction: every step performs the reference's operations on the operands the reference's
+ * loops read, so that miscorrections, early exits and the partially applied corrections of an uncorrectable row agree.
+ * k4_frames is a driver over one function per step of blk_thread(), each on the block's K4Shared and with its own account of how the
+ * step is spread over the lanes: k4_fetch_head / k4_fetch_rows, k4_rs_rows (k4_rs_row: k4_syndromes, k4_rs_bm, k4_rs_chien,
+ * k4_rs_forney; k4_soft_row), k4_unstuff, k4_flag_hunt, k4_fcs_scan, k4_sort_candidates, k4_emit (k4_alloc).  k4_rs_debug runs
+ * k4_rs_row alone.
  */
 #ifndef VDL2GPU_BLOCKS_H
 #define VDL2GPU_BLOCKS_H
@@ -29,6 +21,13 @@
 #define K4_NOLOG 255
 #define K4_MAXBY (VDL2GPU_MAXROWS * 249)
 #define K4_SLOT 256
+#define K4_NCAND 12	/* candidate frames of one burst that the table holds; further ones are counted as dropped */
+#define K4_NONE 0x7fffffff	/* no such byte (k4_flag_hunt) */
+
+/* a compact frame entry: the head of vdl2gpu_frame_t and len data bytes, rounded up to 8 bytes (kernel and host walk the same entries) */
+__host__ __device__ inline unsigned k4_entry_bytes(int len) { return ((unsigned)offsetof(vdl2gpu_frame_t, data) + (unsigned)len + 7u) & ~7u; }
+/* whether a frame of len > 0 bytes fits its record's slot */
+__host__ __device__ inline bool k4_fits_slot(int len) { return (unsigned)offsetof(vdl2gpu_frame_t, data) + (unsigned)len <= K4_SLOT; }
 
 struct K4Params {
 	const vdl2gpu_burst_t *recs;
@@ -47,8 +46,7 @@ struct K4Params {
 					 * device-scope counter for space at the same moment cost more than the whole block
 					 * path; longer and further frames go to the arena behind rec_cap slots, entries
 					 * rounded up to 8 bytes, space taken from nframes[2] */
-	const unsigned *fmask;		/* not nullptr: the records come from the pipeline, where K2d's second pass tags the void ones 2 (trig_sample) */
-	unsigned long long *dbg;	/* diagnostics: stage cycle counters, or nullptr */
+	const unsigned *fmask;		/* not nullptr (it is never read): the records come from the pipeline, where K2d's second pass tags the void ones 2 (trig_sample) */
 	const unsigned *tabs;		/* K4_TABW words from k4_tables: gexp[512], glog[256], crc_tab[256] */
 	const vdl2gpu_soft_t *soft;	/* VDL2GPU_F_SOFT_RS: the records' reliability maps, same index: the row rule of vdl2gpu_soft_t for
 					 * rows the reference cannot decode.  nullptr: the reference's block path and nothing else */
@@ -61,8 +59,8 @@ struct K4Params {
 static_assert(K4_NT == 64, "k4_frames is written for one wavefront per block");
 #define K4_SYNC() do { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); \
 		       __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront"); } while (0)
-#define K4_RECW ((int)(sizeof(vdl2gpu_burst_t) / 4))
 #define K4_RECW0 192	/* words of a record fetched before its header has been looked at: header + two rows */
+#define K4_TABL ((K4_TABW + K4_NT - 1) / K4_NT)	/* table words per lane */
 static_assert(offsetof(vdl2gpu_burst_t, data) % 4 == 0 && sizeof(vdl2gpu_burst_t) % 4 == 0, "rows are fetched as words");
 
 struct K4Shared {
@@ -72,10 +70,13 @@ struct K4Shared {
 	uint8_t src[K4_MAXBY + 8];		/* data bytes of all rows, in order */
 	unsigned dst[(K4_MAXBY + 8) / 4 + 2];	/* un-stuffed bit stream */
 	int eras[6];
-	unsigned fm[16];	/* K4Params.fmask */
-	int ctl[16];
+	int flag0;		/* index in dst[] (bytes) of the first flag, K4_NONE: none */
+	int data0;		/* ... of the first byte behind it that is no flag: hdata[1] */
+	int nfr;		/* candidate frames: found (k4_fcs_scan), then held in ends[] (k4_sort_candidates) */
+	vdl2gpu_frame_t *room;	/* what lane 0 got from k4_alloc */
+	int ends[K4_NCAND];	/* the closing flags of the candidate frames */
 	/* Berlekamp-Massey work arrays live here, not in (scratch-backed) private arrays */
-	uint8_t lam[8], syn[8], bpoly[8], tpoly[8], omg[8], root[8], reg[8], loc[8];
+	uint8_t lam[8], syn[8], omg[8], root[8], loc[8];
 	int rs_deg, rs_count, rs_fail;
 	uint8_t save[256];	/* soft mode: the received row, for the trials */
 	int cand[4];		/* soft mode: the least reliable candidate positions, most doubtful first */
@@ -118,6 +119,67 @@ __device__ __forceinline__ int k4_m255(int x)
 		x = (x >> 8) + (x & 255);
 	}
 	return x;
+}
+
+/* k4_tables' words into registers, and from there into LDS: two steps, so that a kernel can ask for them beside its other loads */
+__device__ __forceinline__ void k4_fetch_tables(const unsigned *tabs, unsigned (&tw)[K4_TABL], int lane)
+{
+#pragma unroll
+	for (int k = 0; k < K4_TABL; ++k)
+		tw[k] = (lane + K4_NT * k < K4_TABW) ? tabs[lane + K4_NT * k] : 0u;
+}
+__device__ __forceinline__ void k4_store_tables(K4Shared &sh, const unsigned (&tw)[K4_TABL], int lane)
+{
+#pragma unroll
+	for (int k = 0; k < K4_TABL; ++k)
+		if (lane + K4_NT * k < K4_TABW)
+			reinterpret_cast<unsigned *>(sh.gexp)[lane + K4_NT * k] = tw[k];
+}
+
+/* exponents of the syndrome sums for this lane's four bytes, (120+i)(254-j) mod 255, a byte each */
+__device__ __forceinline__ void k4_sexp_init(unsigned (&sexp)[4][2], int lane)
+{
+#pragma unroll
+	for (int b = 0; b < 4; ++b) {
+		const int j = lane * 4 + b;
+		sexp[b][0] = sexp[b][1] = 0;
+#pragma unroll
+		for (int i = 0; i < 6; ++i)
+			sexp[b][i / 4] |= (unsigned)k4_m255((120 + i) * (254 - (j < 255 ? j : 254))) << (8 * (i % 4));
+	}
+}
+
+/* n bytes dealt out in runs of `per` = ceil(n / 64): the lane owns [*lo, *hi) */
+__device__ __forceinline__ int k4_lane_span(int n, int lane, int *lo, int *hi)
+{
+	const int per = (n + K4_NT - 1) / K4_NT;
+	*lo = lane * per < n ? lane * per : n;
+	*hi = *lo + per < n ? *lo + per : n;
+	return per;
+}
+
+/* inclusive scan over the lanes: v of lane l becomes op(op(v_0, v_1) ..., v_l) for an associative op(earlier, later) */
+template <class T> __device__ __forceinline__ T k4_shfl_up(T v, int d) { return __shfl_up(v, d, K4_NT); }
+struct K4Run { int all, trail; };	/* a stretch of the bit stream: nothing but ones?  the ones at its end */
+__device__ __forceinline__ K4Run k4_shfl_up(K4Run v, int d) { return {__shfl_up(v.all, d, K4_NT), __shfl_up(v.trail, d, K4_NT)}; }
+template <class T, class Op> __device__ __forceinline__ T k4_scan(T v, int lane, Op op)
+{
+	for (int d = 1; d < K4_NT; d <<= 1) {
+		const T o = k4_shfl_up(v, d);
+		if (lane >= d)
+			v = op(o, v);
+	}
+	return v;
+}
+
+/* set_eras(), vdlm2.c:63-82: a last row of `by` data bytes has had 4 (by <= 30) or 2 (by <= 67) parity bytes less sent: the row's last
+ * bytes, which become its first erasures.  Returns their number. */
+__device__ __forceinline__ int k4_set_eras(K4Shared &sh, int by, int lane)
+{
+	const int n = by <= 30 ? 4 : (by <= 67 ? 2 : 0);
+	if (lane < n)
+		sh.eras[lane] = 255 - n + lane;
+	return n;
 }
 
 /* rs.c:81-291 for one row whose syndromes are not all zero, in three parts, all of them spread over
@@ -375,8 +437,9 @@ __device__ void k4_soft_row(K4Shared &sh, uint8_t *row, const uint8_t *rel, int 
 			break;
 		for (int i = lane; i < 255; i += K4_NT)
 			row[i] = sh.save[i];
-		if (lane < e0 + s)
-			sh.eras[lane] = lane < e0 ? 255 - e0 + lane : sh.cand[lane - e0];	/* set_eras()'s positions, then the candidates */
+		k4_set_eras(sh, by, lane);	/* set_eras()'s positions, then the candidates */
+		if (lane >= e0 && lane < e0 + s)
+			sh.eras[lane] = sh.cand[lane - e0];
 		K4_SYNC();
 		if (k4_rs_row(sh, row, e0 + s, sexp, lane)) {
 			unsigned syn[6];
@@ -388,10 +451,297 @@ __device__ void k4_soft_row(K4Shared &sh, uint8_t *row, const uint8_t *rel, int 
 	}
 	for (int i = lane; i < 255; i += K4_NT)
 		row[i] = sh.save[i];
-	if (lane < e0)
-		sh.eras[lane] = 255 - e0 + lane;
+	k4_set_eras(sh, by, lane);
 	K4_SYNC();
 	k4_rs_row(sh, row, e0, sexp, lane);
+}
+
+/* ---- the record (msgblk_t, vdlm2.c:84-98): its front -- header and two rows -- into registers, and from there into LDS; the
+ * remaining rows follow once the header has been read there */
+__device__ __forceinline__ void k4_fetch_head(const vdl2gpu_burst_t *g, unsigned (&rw)[K4_RECW0 / K4_NT], int lane)
+{
+#pragma unroll
+	for (int k = 0; k < K4_RECW0 / K4_NT; ++k)
+		rw[k] = reinterpret_cast<const unsigned *>(g)[lane + K4_NT * k];
+}
+
+__device__ __forceinline__ void k4_fetch_rows(K4Shared &sh, const vdl2gpu_burst_t *g, int nbrow, int lane)
+{
+	for (int i = K4_RECW0 + lane; i < ((int)offsetof(vdl2gpu_burst_t, data) + nbrow * VDL2GPU_ROWLEN + 3) / 4; i += K4_NT)
+		reinterpret_cast<unsigned *>(sh.recw)[i] = reinterpret_cast<const unsigned *>(g)[i];
+}
+
+/* ---- RS per row (rows in order: eras_pos[] carries over, vdlm2.c:104-113), with the soft row rule behind a row that rs() fails on when
+ * the record has a reliability map (soft: the record's, or nullptr).  The rows' data bytes go to sh.src; returns their number. */
+__device__ __forceinline__ int k4_rs_rows(K4Shared &sh, const vdl2gpu_soft_t *soft, int nbrow, int nlbyte, const unsigned (&sexp)[4][2], int lane)
+{
+	uint8_t *const rows = reinterpret_cast<uint8_t *>(sh.recw) + offsetof(vdl2gpu_burst_t, data);
+	if (lane < 6)
+		sh.eras[lane] = 0;
+	K4_SYNC();
+	int nby = 0;
+	for (int r = 0; r < nbrow; ++r) {
+		const int by = r == nbrow - 1 ? nlbyte : 249;
+		const int nera = k4_set_eras(sh, by, lane);	/* (a full row has none) */
+		uint8_t *const row = rows + r * VDL2GPU_ROWLEN;
+		if (soft) {
+			for (int i = lane; i < 255; i += K4_NT)
+				sh.save[i] = row[i];
+			K4_SYNC();
+		}
+		if (!k4_rs_row(sh, row, nera, sexp, lane) && soft) {
+			const BurstGeom g = burst_geom(nbrow, nlbyte);
+			const int pr = r < g.nf_rows - 1 ? 6 : (r == g.nf_rows - 1 ? g.nf_last : 0);	/* the transmitted parity of row r */
+			if (nera + 2 <= 4)
+				k4_soft_row(sh, row, &soft->rel[r][0], by, nera, pr, sexp, lane);
+		}
+		for (int i = lane; i < by; i += K4_NT)
+			sh.src[nby + i] = rows[r * VDL2GPU_ROWLEN + i];
+		nby += by;
+	}
+	return nby;
+}
+
+/* ---- HDLC bit un-stuffing (vdlm2.c:116-128) of sh.src[0..nby) into sh.dst; returns the number of bits kept.  A stuffed zero is a
+ * zero after exactly five ones: the run of ones in front of a bit does not depend on what was dropped before, so every lane knows the
+ * run it starts in from a scan of (all ones?, trailing ones) and drops its own zeros; a prefix sum of the kept counts places its bits.
+ * A zero is a stuffed one iff exactly five ones stand in front of it.  With the (at most six relevant) bits in front of a byte put
+ * below it, that is a bit pattern test on the whole byte. */
+__device__ __forceinline__ unsigned k4_stuffed(unsigned v, int t)
+{
+	const int tt = t < 6 ? t : 6;
+	const unsigned W = (v << 6) | (((1u << tt) - 1u) << (6 - tt));
+	const unsigned D = ~W & (W << 1) & (W << 2) & (W << 3) & (W << 4) & (W << 5) & ~(W << 6);
+	return (D >> 6) & 0xffu;
+}
+
+/* ones at the end of the stream after byte v, t of them in front of it: those above the byte's highest zero (bit 7 downwards) */
+__device__ __forceinline__ int k4_run_after(unsigned v, int t) { return v == 0xffu ? t + 8 : __clz((int)((~v & 0xffu) << 24)); }
+
+__device__ __forceinline__ int k4_unstuff(K4Shared &sh, int nby, int lane)
+{
+	for (int i = lane; i < nby / 4 + 2; i += K4_NT)
+		sh.dst[i] = 0u;
+	K4_SYNC();
+	int b0, b1;	/* lane owns bytes [b0, b1) */
+	k4_lane_span(nby, lane, &b0, &b1);
+	K4Run run = {1, 0};
+	for (int i = b0; i < b1; ++i) {
+		const unsigned v = sh.src[i];
+		run.all &= v == 0xffu;
+		run.trail = k4_run_after(v, run.trail);
+	}
+	/* run of ones in front of the lane's first bit: scan of t' = all ? t + trail : trail */
+	run = k4_scan(run, lane, [](K4Run a, K4Run b) { return K4Run{a.all & b.all, b.all ? a.trail + b.trail : b.trail}; });
+	int tin = __shfl_up(run.trail, 1, K4_NT);
+	if (lane == 0)
+		tin = 0;
+	int nkeep = 0;
+	for (int i = b0, t = tin; i < b1; ++i) {
+		const unsigned v = sh.src[i];
+		nkeep += 8 - __popc(k4_stuffed(v, t));
+		t = k4_run_after(v, t);
+	}
+	const int kept_incl = k4_scan(nkeep, lane, [](int a, int b) { return a + b; });	/* prefix sum of the kept bits */
+	{
+		int t = tin, o = kept_incl - nkeep;
+		unsigned long long acc = 0;	/* bits of the output word being filled, and what spills over */
+		int w = o >> 5;
+		for (int i = b0; i < b1; ++i) {
+			unsigned v = sh.src[i];
+			unsigned dr = k4_stuffed(v, t);
+			t = k4_run_after(v, t);
+			int nbits = 8;
+			while (dr) {	/* squeeze the dropped zeros out, highest first (there are at most two) */
+				const int d = 31 - __clz((int)dr);
+				v = (v & ((1u << d) - 1u)) | ((v >> (d + 1)) << d);
+				dr &= ~(1u << d);
+				--nbits;
+			}
+			acc |= (unsigned long long)v << (o & 31);
+			o += nbits;
+			if ((o >> 5) != w) {
+				atomicOr(&sh.dst[w], (unsigned)acc);
+				acc >>= 32;
+				++w;
+			}
+		}
+		if ((unsigned)acc)
+			atomicOr(&sh.dst[w], (unsigned)acc);
+	}
+	K4_SYNC();
+	return __shfl(kept_incl, K4_NT - 1, K4_NT);
+}
+
+/* ---- first flag: the byte at which the OR of all bytes so far equals 0x7e (vdlm2.c:129-133); flags right behind the first one are
+ * swallowed (k == 1, vdlm2.c:134-135).  The lane owns the un-stuffed bytes [c0, c1).  Returns the first byte behind the flags,
+ * hdata[1], or K4_NONE: no flag, or nothing but flags behind it. */
+__device__ __forceinline__ int k4_flag_hunt(K4Shared &sh, int c0, int c1, int lane)
+{
+	const uint8_t *B = reinterpret_cast<const uint8_t *>(sh.dst);
+	unsigned lor = 0;	/* OR of all bytes in front of the lane's */
+	for (int i = c0; i < c1; ++i)
+		lor |= B[i];
+	lor = __shfl_up(k4_scan(lor, lane, [](unsigned a, unsigned b) { return a | b; }), 1, K4_NT);
+	if (lane == 0) {
+		lor = 0;
+		sh.flag0 = K4_NONE;
+		sh.data0 = K4_NONE;
+	}
+	K4_SYNC();
+	for (int i = c0; i < c1; ++i) {
+		lor |= B[i];
+		if (lor == 0x7eu) {
+			atomicMin(&sh.flag0, i);
+			break;
+		}
+		if (lor & ~0x7eu)
+			break;	/* a bit outside 0x7e is set for good: no flag will ever be seen */
+	}
+	K4_SYNC();
+	const int m0 = sh.flag0;
+	if (m0 != K4_NONE)
+		for (int i = c0 > m0 + 1 ? c0 : m0 + 1; i < c1; ++i)
+			if (B[i] != 0x7eu) {
+				atomicMin(&sh.data0, i);
+				break;
+			}
+	K4_SYNC();
+	return sh.data0;
+}
+
+/* ---- hdata[] = 0x7e, B[m1], B[m1+1], ...; every later 0x7e closes a candidate frame hdata[0..k] whose FCS runs over hdata[1..k-1]
+ * (check_frame, vdlm2.c:38-61).  All candidates start at m1, so one running FCS serves -- computed lane-parallel: the FCS is linear,
+ * the state at the start of a lane's bytes is (state one lane earlier, advanced over `per` zero bytes) xor (FCS from zero of that
+ * lane's bytes); that recurrence is scanned in log2(64) doubling steps, the advance map (16 columns, one per lane) being squared
+ * alongside.  Leaves the closing flags of the frames that check in sh.ends, in any order, and their number in sh.nfr. */
+__device__ __forceinline__ void k4_fcs_scan(K4Shared &sh, int m1, int per, int c0, int c1, int lane)
+{
+	const uint8_t *B = reinterpret_cast<const uint8_t *>(sh.dst);
+	unsigned col = 0;	/* the advance map, one state bit per lane */
+	if (lane < 16) {
+		col = 1u << lane;
+		for (int i = 0; i < per; ++i)
+			col = (col >> 8) ^ sh.crc_tab[col & 0xffu];
+	}
+	const int L1 = m1 / per;	/* lane that holds m1 (per >= 1 since there are more than m1 bytes) */
+	unsigned x = 0;	/* FCS over the lane's own bytes, from 0xffff at m1, from zero behind it */
+	if (lane >= L1) {
+		x = (lane == L1) ? 0xffffu : 0u;
+		for (int i = (lane == L1) ? m1 : c0; i < c1; ++i)
+			x = (x >> 8) ^ sh.crc_tab[(x ^ B[i]) & 0xffu];
+	}
+	for (int d = 1; d < K4_NT; d <<= 1) {
+		unsigned xl = __shfl_up(x, d, K4_NT);
+		if (lane < d)
+			xl = 0;
+		unsigned y = 0, nc = 0;
+#pragma unroll
+		for (int b = 0; b < 16; ++b) {
+			const unsigned cb = (unsigned)__builtin_amdgcn_readlane((int)col, b);
+			y ^= (0u - ((xl >> b) & 1u)) & cb;
+			nc ^= (0u - ((col >> b) & 1u)) & cb;
+		}
+		x ^= y;	/* exact for whole lanes; the last, partial lane's end state is not needed */
+		col = nc;
+	}
+	const unsigned crc_in = __shfl_up(x, 1, K4_NT);	/* state at the lane's first byte */
+	if (lane == 0)
+		sh.nfr = 0;
+	K4_SYNC();
+	if (lane >= L1) {
+		unsigned c = (lane == L1) ? 0xffffu : crc_in;
+		for (int q = (lane == L1) ? m1 : c0; q < c1; ++q) {
+			const unsigned v = B[q];
+			if (v == 0x7eu && (q - m1 + 2) >= 13 && c == 0xf0b8u) {
+				const int k = atomicAdd(&sh.nfr, 1);
+				if (k < K4_NCAND)
+					sh.ends[k] = q;
+			}
+			c = (c >> 8) ^ sh.crc_tab[(c ^ v) & 0xffu];
+		}
+	}
+	K4_SYNC();
+}
+
+/* ---- frames in stream order (there is almost never more than one); more CRC-clean frames in one burst than the table holds are
+ * counted as dropped, not silent */
+__device__ __forceinline__ void k4_sort_candidates(K4Shared &sh, unsigned *dropped, int lane)
+{
+	if (lane == 0) {
+		const int nf0 = sh.nfr < K4_NCAND ? sh.nfr : K4_NCAND;
+		if (sh.nfr > K4_NCAND)
+			atomicAdd(dropped, (unsigned)(sh.nfr - K4_NCAND));
+		for (int i = 1; i < nf0; ++i)
+			for (int j = i; j > 0 && sh.ends[j] < sh.ends[j - 1]; --j) {
+				const int t = sh.ends[j];
+				sh.ends[j] = sh.ends[j - 1];
+				sh.ends[j - 1] = t;
+			}
+		sh.nfr = nf0;
+	}
+	K4_SYNC();
+}
+
+/* ---- out() (vdlm2.c:140-158).  One lane asks for the room of a frame that does not go to its record's slot: an arena entry (compact)
+ * or the next vdl2gpu_frame_t; nullptr when the buffer is full, and the frame is counted as dropped */
+__device__ __forceinline__ vdl2gpu_frame_t *k4_alloc(const K4Params &p, int len)
+{
+	if (p.compact) {
+		const unsigned sz = k4_entry_bytes(len);
+		const unsigned base = p.rec_cap * K4_SLOT;
+		const unsigned at = base + atomicAdd(p.nframes + 2, sz);	/* byte offset */
+		if (at + sz <= p.frame_cap) {
+			atomicAdd(p.nframes, 1u);
+			atomicMax(p.nframes + 3, at + sz - base);	/* the counter never goes back: the entries that found room are a prefix of the arena */
+			return reinterpret_cast<vdl2gpu_frame_t *>(reinterpret_cast<char *>(p.frames) + at);
+		}
+	} else {
+		const unsigned at = atomicAdd(p.nframes, 1u);
+		if (at < p.frame_cap)
+			return p.frames + at;
+	}
+	atomicAdd(p.nframes + 1, 1u);
+	return nullptr;
+}
+
+/* the burst's frames: the first one into the record's slot when there is one (myslot) and it fits, the others where k4_alloc says */
+__device__ __forceinline__ void k4_emit(K4Shared &sh, const K4Params &p, vdl2gpu_frame_t *myslot, unsigned ib, int m1, int lane)
+{
+	const vdl2gpu_burst_t *const rec = reinterpret_cast<const vdl2gpu_burst_t *>(sh.recw);
+	const uint8_t *B = reinterpret_cast<const uint8_t *>(sh.dst);
+	const int nf = sh.nfr;
+	for (int f = 0; f < nf; ++f) {
+		const int len = sh.ends[f] - m1 + 2;
+		const bool inslot = myslot && f == 0 && k4_fits_slot(len);	/* uniform */
+		if (!inslot) {
+			if (lane == 0)
+				sh.room = k4_alloc(p, len);
+			K4_SYNC();
+		}
+		vdl2gpu_frame_t *const fr = inslot ? myslot : sh.room;
+		if (fr) {
+			if (lane == 0) {
+				fr->stream = rec->stream;
+				fr->chn = rec->chn;
+				fr->Fr = rec->Fr;
+				fr->nbrow = rec->nbrow;
+				fr->nlbyte = rec->nlbyte;
+				fr->len = len;
+				fr->block = (int32_t)ib;
+				fr->seq = f;
+				fr->df = rec->df;
+				fr->ppm = rec->ppm;
+				fr->trig_dec = rec->trig_dec;
+				fr->end_dec = rec->end_dec;
+				fr->data[0] = 0x7e;
+			}
+			for (int i = lane; i < len - 1 && i + 1 < VDL2GPU_MAXFRAME; i += K4_NT)
+				fr->data[i + 1] = B[m1 + i];
+		}
+		K4_SYNC();
+	}
+	K4_SYNC();
 }
 
 __global__ __launch_bounds__(K4_NT)
@@ -399,64 +749,31 @@ void k4_frames(K4Params p)
 {
 	__shared__ K4Shared sh;
 	const int lane = threadIdx.x;
-	const bool prof = p.dbg && lane == 0;
-	long long tq = prof ? clock64() : 0;
 	/* Everything the first record needs from memory is asked for at once -- the tables, the record
 	 * count and the front of record blockIdx.x -- because this kernel runs beside the next push's
 	 * channeliser, which keeps the memory queues full: every dependent round trip costs microseconds. */
-	unsigned tw[(K4_TABW + K4_NT - 1) / K4_NT], rw[K4_RECW0 / K4_NT] = {};
-	const unsigned fmw = (p.fmask && lane < 16) ? p.fmask[lane] : 0u;
-#pragma unroll
-	for (int k = 0; k < (K4_TABW + K4_NT - 1) / K4_NT; ++k)
-		tw[k] = (lane + K4_NT * k < K4_TABW) ? p.tabs[lane + K4_NT * k] : 0u;
-	if (blockIdx.x < p.rec_cap) {
-		const unsigned *w = reinterpret_cast<const unsigned *>(p.recs + blockIdx.x);
-#pragma unroll
-		for (int k = 0; k < K4_RECW0 / K4_NT; ++k)
-			rw[k] = w[lane + K4_NT * k];
-	}
+	unsigned tw[K4_TABL], rw[K4_RECW0 / K4_NT] = {};
+	k4_fetch_tables(p.tabs, tw, lane);
+	if (blockIdx.x < p.rec_cap)
+		k4_fetch_head(p.recs + blockIdx.x, rw, lane);
 	unsigned nrecs = p.nrecs_dev ? *p.nrecs_dev : p.nrecs;
 	nrecs = nrecs > p.rec_cap ? p.rec_cap : nrecs;
 	if (blockIdx.x >= nrecs)
 		return;
-#pragma unroll
-	for (int k = 0; k < (K4_TABW + K4_NT - 1) / K4_NT; ++k)
-		if (lane + K4_NT * k < K4_TABW)
-			reinterpret_cast<unsigned *>(sh.gexp)[lane + K4_NT * k] = tw[k];
-	if (lane < 16)
-		sh.fm[lane] = fmw;
-	unsigned *const recw = reinterpret_cast<unsigned *>(sh.recw);
+	k4_store_tables(sh, tw, lane);
 	const vdl2gpu_burst_t *const rec = reinterpret_cast<const vdl2gpu_burst_t *>(sh.recw);	/* the copy in LDS */
-	uint8_t *const rows = reinterpret_cast<uint8_t *>(sh.recw) + offsetof(vdl2gpu_burst_t, data);
-	/* exponents of the syndrome sums for this lane's four bytes, (120+i)(254-j) mod 255, a byte each */
 	unsigned sexp[4][2];
-#pragma unroll
-	for (int b = 0; b < 4; ++b) {
-		const int j = lane * 4 + b;
-		sexp[b][0] = sexp[b][1] = 0;
-#pragma unroll
-		for (int i = 0; i < 6; ++i)
-			sexp[b][i / 4] |= (unsigned)k4_m255((120 + i) * (254 - (j < 255 ? j : 254))) << (8 * (i % 4));
-	}
-#define K4_STAMP(slot) do { if (prof) { const long long tn = clock64(); atomicAdd(p.dbg + 48 + (slot), (unsigned long long)(tn - tq)); tq = tn; } } while (0)
-	K4_STAMP(0);
+	k4_sexp_init(sexp, lane);
 	for (unsigned ib = blockIdx.x; ib < nrecs; ib += gridDim.x) {
-		const unsigned *gw = reinterpret_cast<const unsigned *>(p.recs + ib);
 		if (ib != blockIdx.x) {
 			K4_SYNC();	/* the previous record's frame bytes have been read */
-#pragma unroll
-			for (int k = 0; k < K4_RECW0 / K4_NT; ++k)
-				rw[k] = gw[lane + K4_NT * k];
+			k4_fetch_head(p.recs + ib, rw, lane);
 		}
 #pragma unroll
 		for (int k = 0; k < K4_RECW0 / K4_NT; ++k)
-			recw[lane + K4_NT * k] = rw[k];
+			reinterpret_cast<unsigned *>(sh.recw)[lane + K4_NT * k] = rw[k];
 		K4_SYNC();
-		const long long tb0 = prof ? clock64() : 0;
-		if (prof)
-			tq = tb0;
 		const int nbrow = rec->nbrow, nlbyte = rec->nlbyte;
-		const unsigned hdr = (unsigned)offsetof(vdl2gpu_frame_t, data);
 		vdl2gpu_frame_t *const myslot = p.compact ? reinterpret_cast<vdl2gpu_frame_t *>(reinterpret_cast<char *>(p.frames) + (size_t)ib * K4_SLOT) : nullptr;
 		if (myslot && lane == 0)
 			myslot->len = 0;
@@ -464,332 +781,20 @@ void k4_frames(K4Params p)
 			continue;
 		if (nbrow < 1 || nbrow > VDL2GPU_MAXROWS || nlbyte < 0 || nlbyte > 249)
 			continue;
-		/* ---- rows to LDS */
-		for (int i = K4_RECW0 + lane; i < ((int)offsetof(vdl2gpu_burst_t, data) + nbrow * VDL2GPU_ROWLEN + 3) / 4; i += K4_NT)
-			recw[i] = gw[i];
-		if (lane < 6)
-			sh.eras[lane] = 0;
-		K4_SYNC();
-		K4_STAMP(1);
-		/* ---- RS per row (rows in order: eras_pos[] carries over, vdlm2.c:104-113) */
-		int nby = 0;
-		for (int r = 0; r < nbrow; ++r) {
-			int by = 249, nera = 0;
-			if (r == nbrow - 1) {
-				by = nlbyte;
-				if (lane == 0) {	/* set_eras(), vdlm2.c:63-82 */
-					if (by <= 67) {
-						sh.eras[0] = 253;
-						sh.eras[1] = 254;
-					}
-					if (by <= 30) {
-						sh.eras[0] = 251;
-						sh.eras[1] = 252;
-						sh.eras[2] = 253;
-						sh.eras[3] = 254;
-					}
-				}
-				nera = by <= 30 ? 4 : (by <= 67 ? 2 : 0);
-			}
-			uint8_t *const row = rows + r * VDL2GPU_ROWLEN;
-			if (p.soft) {
-				for (int i = lane; i < 255; i += K4_NT)
-					sh.save[i] = row[i];
-				K4_SYNC();
-			}
-			if (!k4_rs_row(sh, row, nera, sexp, lane) && p.soft) {
-				/* the transmitted parity of row r (burst_geom) */
-				const int nf_rows = nlbyte <= 2 ? nbrow - 1 : nbrow;
-				const int nf_last = nlbyte <= 2 ? 6 : (nlbyte <= 30 ? 2 : (nlbyte <= 67 ? 4 : 6));
-				const int pr = r < nf_rows - 1 ? 6 : (r == nf_rows - 1 ? nf_last : 0);
-				if (nera + 2 <= 4)
-					k4_soft_row(sh, row, &p.soft[ib].rel[r][0], by, nera, pr, sexp, lane);
-			}
-			for (int i = lane; i < by; i += K4_NT)
-				sh.src[nby + i] = rows[r * VDL2GPU_ROWLEN + i];
-			nby += by;
-		}
-		K4_STAMP(2);
-		for (int i = lane; i < nby / 4 + 2; i += K4_NT)
-			sh.dst[i] = 0u;
-		K4_SYNC();
-		/* ---- HDLC bit un-stuffing (vdlm2.c:116-128): lane owns bytes [b0, b1) */
-		const int per = (nby + K4_NT - 1) / K4_NT;
-		const int b0 = lane * per < nby ? lane * per : nby;
-		const int b1 = b0 + per < nby ? b0 + per : nby;
-		int tin;
-		{
-			int all = 1, trail = 0;
-			for (int i = b0; i < b1; ++i) {
-				const unsigned v = sh.src[i];
-				if (v == 0xffu)
-					trail += 8;
-				else {
-					all = 0;
-					trail = __clz((int)((~v & 0xffu) << 24));	/* ones above the highest zero (bit 7 downwards) */
-				}
-			}
-			/* run of ones in front of the lane's first bit: scan of t' = all ? t + trail : trail */
-			for (int d = 1; d < K4_NT; d <<= 1) {
-				const int la = __shfl_up(all, d, K4_NT), lt = __shfl_up(trail, d, K4_NT);
-				if (lane >= d) {
-					trail = all ? lt + trail : trail;
-					all &= la;
-				}
-			}
-			tin = __shfl_up(trail, 1, K4_NT);
-			if (lane == 0)
-				tin = 0;
-		}
-		/* A zero is a stuffed one iff exactly five ones stand in front of it.  With the (at most six
-		 * relevant) bits in front of a byte put below it, that is a bit pattern test on the whole byte. */
-		auto drops = [](unsigned v, int t) -> unsigned {
-			const int tt = t < 6 ? t : 6;
-			const unsigned W = (v << 6) | (((1u << tt) - 1u) << (6 - tt));
-			const unsigned D = ~W & (W << 1) & (W << 2) & (W << 3) & (W << 4) & (W << 5) & ~(W << 6);
-			return (D >> 6) & 0xffu;
-		};
-		auto run_after = [](unsigned v, int t) -> int {	/* ones at the end of the stream after byte v */
-			return v == 0xffu ? t + 8 : __clz((int)((~v & 0xffu) << 24));
-		};
-		int nkeep = 0;
-		{
-			int t = tin;
-			for (int i = b0; i < b1; ++i) {
-				const unsigned v = sh.src[i];
-				nkeep += 8 - __popc(drops(v, t));
-				t = run_after(v, t);
-			}
-		}
-		int kept_incl = nkeep;	/* prefix sum of the kept bits */
-		for (int d = 1; d < K4_NT; d <<= 1) {
-			const int o = __shfl_up(kept_incl, d, K4_NT);
-			if (lane >= d)
-				kept_incl += o;
-		}
-		const int kept_all = __shfl(kept_incl, K4_NT - 1, K4_NT);
-		{
-			int t = tin, o = kept_incl - nkeep;
-			unsigned long long acc = 0;	/* bits of the output word being filled, and what spills over */
-			int w = o >> 5;
-			for (int i = b0; i < b1; ++i) {
-				unsigned v = sh.src[i];
-				unsigned dr = drops(v, t);
-				t = run_after(v, t);
-				int nbits = 8;
-				while (dr) {	/* squeeze the dropped zeros out, highest first (there are at most two) */
-					const int d = 31 - __clz((int)dr);
-					v = (v & ((1u << d) - 1u)) | ((v >> (d + 1)) << d);
-					dr &= ~(1u << d);
-					--nbits;
-				}
-				acc |= (unsigned long long)v << (o & 31);
-				o += nbits;
-				if ((o >> 5) != w) {
-					atomicOr(&sh.dst[w], (unsigned)acc);
-					acc >>= 32;
-					++w;
-				}
-			}
-			if ((unsigned)acc)
-				atomicOr(&sh.dst[w], (unsigned)acc);
-		}
-		K4_SYNC();
-		K4_STAMP(3);
-		const int nb = kept_all >> 3;	/* whole un-stuffed bytes */
-		const uint8_t *B = reinterpret_cast<const uint8_t *>(sh.dst);
-		/* ---- first flag: the byte at which the OR of all bytes so far equals 0x7e (vdlm2.c:129-133) */
-		const int per2 = (nb + K4_NT - 1) / K4_NT;
-		const int c0 = lane * per2 < nb ? lane * per2 : nb;
-		const int c1 = c0 + per2 < nb ? c0 + per2 : nb;
-		unsigned lor = 0;	/* OR of all bytes in front of the lane's */
-		{
-			for (int i = c0; i < c1; ++i)
-				lor |= B[i];
-			for (int d = 1; d < K4_NT; d <<= 1) {
-				const unsigned o = __shfl_up(lor, d, K4_NT);
-				if (lane >= d)
-					lor |= o;
-			}
-			lor = __shfl_up(lor, 1, K4_NT);
-			if (lane == 0)
-				lor = 0;
-		}
-		if (lane == 0) {
-			sh.ctl[0] = 0x7fffffff;	/* m0 */
-			sh.ctl[1] = 0x7fffffff;	/* m1 */
-		}
-		K4_SYNC();
-		{
-			unsigned o = lor;
-			for (int i = c0; i < c1; ++i) {
-				o |= B[i];
-				if (o == 0x7eu) {
-					atomicMin(&sh.ctl[0], i);
-					break;
-				}
-				if (o & ~0x7eu)
-					break;	/* a bit outside 0x7e is set for good: no flag will ever be seen */
-			}
-		}
-		K4_SYNC();
-		const int m0 = sh.ctl[0];
-		if (m0 != 0x7fffffff) {
-			/* flags right behind the first one are swallowed (k == 1, vdlm2.c:134-135) */
-			for (int i = c0 > m0 + 1 ? c0 : m0 + 1; i < c1; ++i)
-				if (B[i] != 0x7eu) {
-					atomicMin(&sh.ctl[1], i);
-					break;
-				}
-		}
-		K4_SYNC();
-		const int m1 = sh.ctl[1];
-		if (m0 == 0x7fffffff || m1 == 0x7fffffff) {
+		k4_fetch_rows(sh, p.recs + ib, nbrow, lane);
+		const int nby = k4_rs_rows(sh, p.soft ? p.soft + ib : nullptr, nbrow, nlbyte, sexp, lane);
+		const int nb = k4_unstuff(sh, nby, lane) >> 3;	/* whole un-stuffed bytes */
+		int c0, c1;	/* of them, the lane's */
+		const int per = k4_lane_span(nb, lane, &c0, &c1);
+		const int m1 = k4_flag_hunt(sh, c0, c1, lane);
+		if (m1 == K4_NONE) {
 			K4_SYNC();
 			continue;
 		}
-		/* ---- hdata[] = 0x7e, B[m1], B[m1+1], ...; every later 0x7e closes a candidate frame
-		 *      hdata[0..k] whose FCS runs over hdata[1..k-1] (check_frame, vdlm2.c:38-61).  All candidates
-		 *      start at m1, so one running FCS serves -- computed lane-parallel: the FCS is linear, the state
-		 *      at the start of a lane's bytes is (state one lane earlier, advanced over per2 zero bytes)
-		 *      xor (FCS from zero of that lane's bytes); that recurrence is scanned in log2(64) doubling steps,
-		 *      the advance map (16 columns, one per lane) being squared alongside. */
-		K4_STAMP(4);
-		unsigned col = 0;	/* the advance map, one state bit per lane */
-		if (lane < 16) {
-			col = 1u << lane;
-			for (int i = 0; i < per2; ++i)
-				col = (col >> 8) ^ sh.crc_tab[col & 0xffu];
-		}
-		const int L1 = m1 / per2;	/* lane that holds m1 (per2 >= 1 since nb > m1) */
-		unsigned crc_in;
-		{
-			unsigned x = 0;	/* FCS over the lane's own bytes, from 0xffff at m1, from zero behind it */
-			if (lane >= L1) {
-				x = (lane == L1) ? 0xffffu : 0u;
-				for (int i = (lane == L1) ? m1 : c0; i < c1; ++i)
-					x = (x >> 8) ^ sh.crc_tab[(x ^ B[i]) & 0xffu];
-			}
-			for (int d = 1; d < K4_NT; d <<= 1) {
-				unsigned xl = __shfl_up(x, d, K4_NT);
-				if (lane < d)
-					xl = 0;
-				unsigned y = 0, nc = 0;
-#pragma unroll
-				for (int b = 0; b < 16; ++b) {
-					const unsigned cb = (unsigned)__builtin_amdgcn_readlane((int)col, b);
-					y ^= (0u - ((xl >> b) & 1u)) & cb;
-					nc ^= (0u - ((col >> b) & 1u)) & cb;
-				}
-				x ^= y;	/* exact for whole lanes; the last, partial lane's end state is not needed */
-				col = nc;
-			}
-			crc_in = __shfl_up(x, 1, K4_NT);	/* state at the lane's first byte */
-		}
-		if (lane == 0)
-			sh.ctl[1] = 0;	/* number of frames */
-		K4_SYNC();
-		if (lane >= L1) {
-			unsigned c = (lane == L1) ? 0xffffu : crc_in;
-			for (int q = (lane == L1) ? m1 : c0; q < c1; ++q) {
-				const unsigned v = B[q];
-				if (v == 0x7eu && (q - m1 + 2) >= 13 && c == 0xf0b8u) {
-					const int k = atomicAdd(&sh.ctl[1], 1);
-					if (k < 12)
-						sh.ctl[2 + k] = q;
-				}
-				c = (c >> 8) ^ sh.crc_tab[(c ^ v) & 0xffu];
-			}
-		}
-		K4_SYNC();
-		if (lane == 0) {	/* frames in stream order (there is almost never more than one) */
-			int nf0 = sh.ctl[1] < 12 ? sh.ctl[1] : 12;
-			if (sh.ctl[1] > 12)	/* more CRC-clean frames in one burst than the table holds: counted, not silent */
-				atomicAdd(p.nframes + 1, (unsigned)(sh.ctl[1] - 12));
-			for (int i = 1; i < nf0; ++i)
-				for (int j = i; j > 0 && sh.ctl[2 + j] < sh.ctl[1 + j]; --j) {
-					const int t = sh.ctl[2 + j];
-					sh.ctl[2 + j] = sh.ctl[1 + j];
-					sh.ctl[1 + j] = t;
-				}
-			sh.ctl[1] = nf0;
-		}
-		K4_SYNC();
-		K4_STAMP(5);
-		const int nf = sh.ctl[1];
-		for (int f = 0; f < nf; ++f) {
-			const int q = sh.ctl[2 + f];
-			const int len = q - m1 + 2;
-			const bool inslot = myslot && f == 0 && hdr + (unsigned)len <= K4_SLOT;	/* uniform */
-			if (!inslot) {
-				if (lane == 0) {
-					unsigned slot;
-					if (p.compact) {
-						const unsigned sz = (hdr + (unsigned)len + 7u) & ~7u;
-						const unsigned base = p.rec_cap * K4_SLOT;
-						slot = base + atomicAdd(p.nframes + 2, sz);	/* byte offset */
-						if (slot + sz > p.frame_cap) {
-							atomicAdd(p.nframes + 1, 1u);
-							slot = 0xffffffffu;
-						} else {
-							atomicAdd(p.nframes, 1u);
-							atomicMax(p.nframes + 3, slot + sz - base);	/* the counter never goes back: the entries that found room are a prefix of the arena */
-						}
-					} else {
-						slot = atomicAdd(p.nframes, 1u);
-						if (slot >= p.frame_cap) {
-							atomicAdd(p.nframes + 1, 1u);
-							slot = 0xffffffffu;
-						}
-					}
-					sh.ctl[0] = (int)slot;
-				}
-				K4_SYNC();
-			}
-			const unsigned slot = inslot ? 0u : (unsigned)sh.ctl[0];
-			K4_STAMP(12);
-			if (slot != 0xffffffffu) {
-				vdl2gpu_frame_t *fr = inslot ? myslot
-						     : (p.compact ? reinterpret_cast<vdl2gpu_frame_t *>(reinterpret_cast<char *>(p.frames) + slot) : p.frames + slot);
-				if (lane == 0) {
-					fr->stream = rec->stream;
-					fr->chn = rec->chn;
-					fr->Fr = rec->Fr;
-					fr->nbrow = nbrow;
-					fr->nlbyte = nlbyte;
-					fr->len = len;
-					fr->block = (int32_t)ib;
-					fr->seq = f;
-					fr->df = rec->df;
-					fr->ppm = rec->ppm;
-					fr->trig_dec = rec->trig_dec;
-					fr->end_dec = rec->end_dec;
-					fr->data[0] = 0x7e;
-				}
-				for (int i = lane; i < len - 1 && i + 1 < VDL2GPU_MAXFRAME; i += K4_NT)
-					fr->data[i + 1] = B[m1 + i];
-			}
-			K4_SYNC();
-		}
-		K4_SYNC();
-		K4_STAMP(6);
-		if (prof) {
-			atomicAdd(p.dbg + 48 + 7, 1ull);
-			const unsigned long long tot = (unsigned long long)(tq - tb0);
-			atomicMax(p.dbg + 48 + 8, tot);
-			if (nbrow >= 3) {
-				atomicAdd(p.dbg + 48 + 13, tot);
-				atomicAdd(p.dbg + 48 + 14, 1ull);
-			}
-			atomicMax(p.dbg + 48 + 15, (unsigned long long)nbrow);
-			if (tot > 400000ull) {
-				atomicAdd(p.dbg + 48 + 9, 1ull);
-				p.dbg[48 + 10] = ((unsigned long long)nbrow << 32) | (unsigned)nlbyte;
-				p.dbg[48 + 11] = (unsigned long long)kept_all;
-			}
-		}
+		k4_fcs_scan(sh, m1, per, c0, c1, lane);
+		k4_sort_candidates(sh, p.nframes + 1, lane);
+		k4_emit(sh, p, myslot, ib, m1, lane);
 	}
-#undef K4_STAMP
 }
 
 /* vdl2gpu_debug_rs: k4_rs_row as k4_frames calls it, one wavefront per row, so that a test can hold what it leaves in a row --
@@ -803,17 +808,11 @@ void k4_rs_debug(uint8_t *rows, int *eras, const int *no_eras, int *ret, const u
 	const unsigned ib = blockIdx.x;
 	if (ib >= n)
 		return;
-	for (int i = lane; i < K4_TABW; i += K4_NT)
-		reinterpret_cast<unsigned *>(sh.gexp)[i] = tabs[i];
-	unsigned sexp[4][2];	/* as in k4_frames */
-#pragma unroll
-	for (int b = 0; b < 4; ++b) {
-		const int j = lane * 4 + b;
-		sexp[b][0] = sexp[b][1] = 0;
-#pragma unroll
-		for (int i = 0; i < 6; ++i)
-			sexp[b][i / 4] |= (unsigned)k4_m255((120 + i) * (254 - (j < 255 ? j : 254))) << (8 * (i % 4));
-	}
+	unsigned tw[K4_TABL];
+	k4_fetch_tables(tabs, tw, lane);
+	k4_store_tables(sh, tw, lane);
+	unsigned sexp[4][2];
+	k4_sexp_init(sexp, lane);
 	uint8_t *const row = sh.src;
 	uint8_t *const grow = rows + (size_t)ib * 255;
 	for (int i = lane; i < 255; i += K4_NT)
