@@ -301,6 +301,9 @@ struct vdl2gpu {
 		int test_item_grid = 0;		/* VDL2GPU_TEST_ITEM_GRID: few scan workgroups with the smallest private areas -- most items take the common area's path */
 		int test_item_common = 0;	/* VDL2GPU_TEST_ITEM_COMMON: a common area of so many items -- the list overflows */
 		int test_item_verify = 0;	/* VDL2GPU_TEST_ITEM_VERIFY: the two above for the verify passes only */
+		/* VDL2GPU_TEST_{REG,SEG,VIS,WIN,MERGE,SLOG}_CAP: what a list of the back stage holds (K2Params.lim_*; 0 or more than its size: its size);
+		 * VDL2GPU_TEST_STAGE_DYN: dynamic descriptor slots behind the static ones (0 or more than there are: all of them) */
+		int test_reg_cap = 0, test_seg_cap = 0, test_vis_cap = 0, test_win_cap = 0, test_merge_cap = 0, test_slog_cap = 0, test_stage_dyn = 0;
 #endif
 	} knob;
 	/* A push's work is three stages on three streams, and three pushes are in the pipeline at once -- the planes, the tables
@@ -757,6 +760,8 @@ template <class T> static int alloc_table(vdl2gpu_t *h, T *K2Params::*m, size_t 
 	return VDL2GPU_OK;
 }
 
+static const unsigned STAGE_DYN_SLOTS = 65536u;	/* the descriptor pool's dynamic tail behind the clusters' static slots (serial stretches, replays) */
+
 /* The 21 tables of the table sets: a new table is its member of K2Params and a line here. */
 #define ALLOC_TABLE(h, name, bytes, ...) TRY(alloc_table(h, &K2Params::name, bytes, "hipMalloc(&set[r].k2." #name ", " #bytes ")", ##__VA_ARGS__))
 static int alloc_sets(vdl2gpu_t *h)
@@ -816,6 +821,17 @@ static void fill_set_params(vdl2gpu_t *h)
 		k.full_scan = h->full_scan;
 #ifdef VDL2GPU_TESTHOOKS
 		k.test_noregion = (h->cfg.flags & VDL2GPU_F_TEST_NOREGION) ? 1 : 0;
+		{
+			/* a hook may only lower a limit: the lists keep their sizes */
+			auto lim = [](int hook, int size) { return hook > 0 && hook < size ? hook : size; };
+			k.lim_reg = lim(h->knob.test_reg_cap, VDL2_REG_CAP);
+			k.lim_seg = lim(h->knob.test_seg_cap, VDL2_SEG_CAP);
+			k.lim_vis = lim(h->knob.test_vis_cap, K2C_VIS);
+			k.lim_win = lim(h->knob.test_win_cap, VDL2_WIN_CAP);
+			k.lim_merge = lim(h->knob.test_merge_cap, K2S_MERGE);
+			k.lim_slog = lim(h->knob.test_slog_cap, VDL2_SLOG_CAP);
+			k.stage_cap = h->stage_cap - STAGE_DYN_SLOTS + (unsigned)lim(h->knob.test_stage_dyn, (int)STAGE_DYN_SLOTS);	/* (the pool keeps its size) */
+		}
 #endif
 		k.round = 0;
 		k.item_cap = h->item_cap;
@@ -872,6 +888,13 @@ static int create_impl(vdl2gpu_t *h)
 	h->knob.test_item_grid = env_int("VDL2GPU_TEST_ITEM_GRID", 0);
 	h->knob.test_item_common = env_int("VDL2GPU_TEST_ITEM_COMMON", 0);
 	h->knob.test_item_verify = env_int("VDL2GPU_TEST_ITEM_VERIFY", 0);
+	h->knob.test_reg_cap = env_int("VDL2GPU_TEST_REG_CAP", 0);
+	h->knob.test_seg_cap = env_int("VDL2GPU_TEST_SEG_CAP", 0);
+	h->knob.test_vis_cap = env_int("VDL2GPU_TEST_VIS_CAP", 0);
+	h->knob.test_win_cap = env_int("VDL2GPU_TEST_WIN_CAP", 0);
+	h->knob.test_merge_cap = env_int("VDL2GPU_TEST_MERGE_CAP", 0);
+	h->knob.test_slog_cap = env_int("VDL2GPU_TEST_SLOG_CAP", 0);
+	h->knob.test_stage_dyn = env_int("VDL2GPU_TEST_STAGE_DYN", 0);
 #endif
 	/* A push in which a channel's verify pass fails with no round scheduled costs a serial redo of that channel's whole
 	 * push (milliseconds), an idle round 30 us: with 16 channels or more an event somewhere is frequent enough that one
@@ -967,7 +990,7 @@ static int create_impl(vdl2gpu_t *h)
 	NEW_EVENT(h, h->verify_done);
 	NEW_EVENT(h, h->k2f_done.ev);
 	h->ctl_words = VDL2_CTL_WORDS((size_t)S * VDL2_CS);
-	h->stage_cap = (unsigned)S * VDL2_CS * VDL2_CAND_CAP * VDL2_CL_MAXB + 65536u;	/* static slots + dynamic tail */
+	h->stage_cap = (unsigned)S * VDL2_CS * VDL2_CAND_CAP * VDL2_CL_MAXB + STAGE_DYN_SLOTS;	/* static slots + dynamic tail */
 	TRY(alloc_sets(h));
 	h->pin_recs = std::min<unsigned>(h->rec_cap, 8192u);
 	HOST_ALLOC(h, h->h_pin, (size_t)h->pin_recs * sizeof(vdl2gpu_burst_t), hipHostMallocDefault);
@@ -1027,8 +1050,8 @@ static int create_impl(vdl2gpu_t *h)
 		HIPCHK(h, hipMemsetAsync(h->d_fcnt, 0, 4 * VDL2_NRING * sizeof(unsigned), h->stream));
 	}
 	HIPCHK(h, hipHostGetDevicePointer((void **)&h->d_pin_cnt, h->h_pin_cnt, 0));
-	DEV_ALLOC(h, h->d_dbg, 64 * sizeof(unsigned long long));
-	HIPCHK(h, hipMemsetAsync(h->d_dbg, 0, 64 * sizeof(unsigned long long), h->stream));
+	DEV_ALLOC(h, h->d_dbg, VDL2_DBG_WORDS * sizeof(unsigned long long));
+	HIPCHK(h, hipMemsetAsync(h->d_dbg, 0, VDL2_DBG_WORDS * sizeof(unsigned long long), h->stream));
 	if (cfg.flags & VDL2GPU_F_DEBUG_HEADS) {
 		h->headtap_cap = 1u << 18;
 		DEV_ALLOC(h, h->d_headtap, (size_t)h->headtap_cap * sizeof(HeadTap));
@@ -3127,7 +3150,7 @@ extern "C" int vdl2gpu_debug_rs(vdl2gpu_t *h, uint8_t *rows, int *eras, const in
 
 extern "C" int vdl2gpu_debug_counters(vdl2gpu_t *h, unsigned long long *out, int n, int reset)
 {
-	if (!h || !out || n < 0 || n > 64)
+	if (!h || !out || n < 0 || n > VDL2_DBG_WORDS)
 		return VDL2GPU_EINVAL;
 	HLOCK(h);
 	int rc = vdl2gpu_sync(h);
@@ -3135,7 +3158,7 @@ extern "C" int vdl2gpu_debug_counters(vdl2gpu_t *h, unsigned long long *out, int
 		return rc;
 	HIPCHK(h, hipMemcpy(out, h->d_dbg, (size_t)n * sizeof(unsigned long long), hipMemcpyDeviceToHost));
 	if (reset) {
-		HIPCHK(h, hipMemsetAsync(h->d_dbg, 0, 64 * sizeof(unsigned long long), h->stream));
+		HIPCHK(h, hipMemsetAsync(h->d_dbg, 0, VDL2_DBG_WORDS * sizeof(unsigned long long), h->stream));
 		HIPCHK(h, hipStreamSynchronize(h->stream));
 	}
 	return VDL2GPU_OK;

@@ -781,8 +781,10 @@ template <int NT, bool XL> __device__ __forceinline__ long long mach_commit_trig
 					const unsigned q = atomicAdd(cx.nsel, 1u);
 					if (q < VDL2_SEL_CAP)
 						cx.sel[q] = slot;
-					else
+					else {
 						atomicAdd(cx.rec_ovf, 1u);
+						slot = 0xffffffffu;	/* the selection list is full: K2d will not see this burst, and the caller fails the channel (MachOut.badslot) */
+					}
 				}
 			}
 			sh.ctl[6] = (int)slot;

@@ -103,7 +103,11 @@ void k2s_merge(K2Params p)
 	const int nold = (int)p.ctl[CTL_NCLUST0 + sc], nnew = ncand - nold;
 	if (nnew <= 0)
 		return;		/* (a channel that failed for another reason than an unlisted event: the resolver will find nothing new) */
-	if (nnew > K2S_MERGE) {	/* a handicapped test build, a pathological input: not worth a sort kernel's footprint in every push */
+	if (nnew > K2_MERGE_LIM(p)) {	/* a handicapped test build, a pathological input: not worth a sort kernel's footprint in every push */
+		if (tid == 0) {
+			K2_COUNT(p, K2_DBG_ESC_MERGE);
+			K2_COUNT(p, K2_DBG_ESC_MERGE_SORT);
+		}
 		if (tid == 0)
 			atomicOr(ovf, 2u);	/* the resolver takes the channel through the serial machine (a complete round resets this); bit 1, not
 						 * bit 0: the tables were not full, the host must not shorten its parts for this (k3_rebase) */
@@ -256,6 +260,14 @@ void k2b_clusters(K2Params p)
 				rc = MR_DEFER;
 			} else {
 				const long long nlast = mach_commit_trigger<K2B_NT, true>(sh, cx, cx.x - cx.dec_base, nstar, tg, out);
+#ifdef VDL2GPU_TESTHOOKS
+				/* invariant (b) at CTL_NWIN0: the cluster's first descriptor as it lies in the pool (lane 0 wrote it) against the candidate */
+				if (tid == 0 && out.nslots == 1 && !out.badslot) {
+					K2_COUNT(p, K2_DBG_CHK_B_CLUSTER);
+					if (p.stage[cx.desc_static].nstar != p.dec_base + cd.nrel)
+						K2_COUNT(p, K2_DBG_INV_B_CLUSTER);
+				}
+#endif
 				out.neval += 1;
 				st.pos = nlast + 2;
 				st.r = tg.rb;
@@ -289,6 +301,8 @@ void k2b_clusters(K2Params p)
 			status = CL_NONSTEADY;
 		if (out.badslot)	/* descriptor pool full */
 			status = CL_INVALID;
+		if (out.badslot && tid == 0)
+			K2_COUNT(p, K2_DBG_ESC_STAGE);
 		if (status == CL_NONSTEADY)
 			mach_store(sh, st, &cl->saved);
 		if (tid == 0)	/* descriptors sit in static slots desc_static + i: the head only needs their number */
@@ -368,10 +382,10 @@ __device__ __forceinline__ void k2_begin_repair(const K2Params &p, int sc, unsig
 }
 
 /* is stream-relative time t inside one of the nwin windows a local repair listed (K2Params.win) */
-__device__ __forceinline__ bool k2_in_windows(const int2 *win, unsigned nwin, long long t)
+__device__ __forceinline__ bool k2_in_windows(const K2Params &p, const int2 *win, unsigned nwin, long long t)
 {
 	bool in = false;
-	for (unsigned w = 0; w < nwin && w < VDL2_WIN_CAP; ++w)
+	for (unsigned w = 0; w < nwin && w < (unsigned)K2_WIN_LIM(p); ++w)
 		in = in || (t >= win[w].x && t < win[w].y);
 	return in;
 }
@@ -380,10 +394,12 @@ __device__ __forceinline__ bool k2_in_windows(const int2 *win, unsigned nwin, lo
  * channel's list of stretches the verify pass must confirm empty.  false: the list is full and the caller fails the channel.
  * (K2c's two lists; k2p_patch, whose every lane counts the entries and lane 0 stores them, has the same lines written out: as a
  * call of this the kernel spills three scalar registers fewer, and its resource line is held where it was measured.) */
-__device__ __forceinline__ bool k2_emit_seg(Seg *segs, unsigned q, int lo, int hi, int r)
+__device__ __forceinline__ bool k2_emit_seg(const K2Params &p, Seg *segs, unsigned q, int lo, int hi, int r)
 {
-	if (q >= VDL2_SEG_CAP)
+	if (q >= (unsigned)K2_SEG_LIM(p)) {
+		K2_COUNT(p, K2_DBG_ESC_SEG);
 		return false;
+	}
 	segs[q] = Seg{lo, hi, r, 0};
 	return true;
 }
@@ -538,7 +554,7 @@ __device__ __forceinline__ void k2c_walk(const K2cShared &ks, const K2Params &p,
 		/* the chain idles from here to the next candidate in a class the probe did not
 		 * scan: K2a-verify must confirm there really is nothing in between */
 		const int g_hi = (cur >= 0) ? (ks.skey[cur] >> 2) : (int)(cx.avail_end - cx.dec_base);
-		if (g_hi > seg_from && !k2_emit_seg(p.segs + (size_t)sc * VDL2_SEG_CAP, atomicAdd(p.ctl + CTL_NSEG0 + sc, 1u), (int)(st.pos - cx.dec_base), g_hi, st.r))
+		if (g_hi > seg_from && !k2_emit_seg(p, p.segs + (size_t)sc * VDL2_SEG_CAP, atomicAdd(p.ctl + CTL_NSEG0 + sc, 1u), (int)(st.pos - cx.dec_base), g_hi, st.r))
 			atomicMin(p.fail + sc, 0);
 	}
 	if (cur >= 0 && stat4_status(ks.sstat[cur]) != CL_STEADY)
@@ -547,14 +563,14 @@ __device__ __forceinline__ void k2c_walk(const K2cShared &ks, const K2Params &p,
 		/* A lone lane chasing pointers: a wavefront on its own issues an instruction every ~5
 		 * cycles, so the loop is four instructions and one LDS round trip per four clusters;
 		 * what was visited is worked out from the list afterwards, by everybody. */
-		if (nvis < K2C_VIS)
+		if (nvis < K2_VIS_LIM(p))
 			ks.svis[nvis] = (unsigned short)(cur | 0x8000);
 		++nvis;
 		last = cur;
 		unsigned v;
 		for (;;) {
 			v = ks.sjump[last];
-			if (nvis < K2C_VIS)
+			if (nvis < K2_VIS_LIM(p))
 				ks.svis[nvis] = (unsigned short)last;
 			++nvis;
 			if (!(v & K2C_J_CONT))
@@ -567,8 +583,10 @@ __device__ __forceinline__ void k2c_walk(const K2cShared &ks, const K2Params &p,
 			why = 1;
 		} else
 			cur = -1;
-		if (nvis > K2C_VIS)
+		if (nvis > K2_VIS_LIM(p)) {
+			K2_COUNT(p, K2_DBG_ESC_VIS);
 			atomicMin(p.fail + sc, 0);
+		}
 	}
 	ks.walk[0] = cur;
 	ks.walk[1] = last;
@@ -592,7 +610,7 @@ __device__ __forceinline__ void k2c_publish(const K2cShared &ks, const K2Params 
 	if (tid == 0) {
 		ks.walk[0] = (int)*cx.nsel;
 		ks.walk[1] = (int)*nseg;
-		ks.walk[3] = nvis < K2C_VIS ? nvis : K2C_VIS;
+		ks.walk[3] = nvis < K2_VIS_LIM(p) ? nvis : K2_VIS_LIM(p);
 	}
 	__syncthreads();
 	int a = 0, b = 0, d = 0;
@@ -624,7 +642,7 @@ __device__ __forceinline__ void k2c_publish(const K2cShared &ks, const K2Params 
 			/* after a steady cluster the chain idles in class (r_s, parity of n_s) until
 			 * the successor's trigger (or the end of the data) */
 			if (lazy && stat4_status(ks.sstat[j]) == CL_STEADY && k2_unprobed(p, cl_r(hd), cx.dec_base + hd.x) && next_t > seg_from &&
-			    !k2_emit_seg(segs, (unsigned)atomicAdd(&ks.walk[1], 1), hd.x, next_t, cl_r(hd)))
+			    !k2_emit_seg(p, segs, (unsigned)atomicAdd(&ks.walk[1], 1), hd.x, next_t, cl_r(hd)))
 				atomicMin(p.fail + sc, 0);
 		}
 	}
@@ -649,7 +667,9 @@ __device__ __forceinline__ void k2c_publish(const K2cShared &ks, const K2Params 
 		if (ks.walk[0] > 0 && p.sel_reserved && p.round == 0)
 			p.ctl[CTL_SELBASE0 + sc] = atomicAdd(p.outc, (unsigned)ks.walk[0]);
 		if (first_pass)
-			p.ctl[CTL_NSLOG0 + sc] = (unsigned)(tables_ok ? nslog : VDL2_SLOG_CAP + 1);	/* (no tables: nothing a local repair could stand on) */
+			p.ctl[CTL_NSLOG0 + sc] = (unsigned)(tables_ok ? nslog : K2_SLOG_LIM(p) + 1);	/* (no tables: nothing a local repair could stand on) */
+		if (first_pass && tables_ok && nslog > K2_SLOG_LIM(p))
+			K2_COUNT(p, K2_DBG_ESC_SLOG);
 	}
 	__syncthreads();
 }
@@ -745,7 +765,7 @@ void k2c_resolve(K2Params p)
 			if (!replay)
 				n_slow += (unsigned long long)(st.pos - p0);
 			if (first_pass && tables_ok && (out.ntrig != c_trig || out.nrej != c_rej || out.nburst != c_burst)) {
-				if (tid == 0 && nslog < VDL2_SLOG_CAP)
+				if (tid == 0 && nslog < K2_SLOG_LIM(p))
 					slog[nslog] = K2Slog{(int)(p0 - cx.dec_base), out.ntrig - c_trig, out.nrej - c_rej, out.nburst - c_burst};
 				++nslog;
 			}
@@ -790,10 +810,12 @@ void k2c_resolve(K2Params p)
 		}
 		/* CL_NONSTEADY: its bursts count, then continue from the explicit state it stopped in */
 		if (tid == 0) {
-			if (nvis < K2C_VIS)
+			if (nvis < K2_VIS_LIM(p))
 				ks.svis[nvis] = (unsigned short)(cur | 0x8000);
-			else
+			else {
+				K2_COUNT(p, K2_DBG_ESC_VIS);
 				atomicMin(p.fail + sc, 0);
+			}
 			++nvis;
 		}
 		if (tid == 0 && p.dbg)
@@ -801,6 +823,13 @@ void k2c_resolve(K2Params p)
 		mach_resume(sh, st, &cl->saved);
 	}
 	__syncthreads();
+	/* A burst of a serial stretch or a replay that found the descriptor pool or the selection list full is in the counters but has no
+	 * descriptor K2d could decode: the pass cannot stand -- the channel fails (as in k2b_clusters and k2p_patch) and K2f, which writes its
+	 * records itself and needs no descriptor, redoes it.  Counted, never silent. */
+	if (out.badslot && tid == 0) {
+		K2_COUNT(p, K2_DBG_ESC_STAGE);
+		atomicMin(p.fail + sc, 0);
+	}
 	const long long tk3 = wall_clock64();
 	k2c_publish(ks, p, sc, tid, cx, lazy, seg_from, nvis, tables_ok, nslog);
 	if (steady_end) {
@@ -973,6 +1002,31 @@ __device__ __forceinline__ int3 k2p_old_counts(K2pShared &ps, const K2Params &p,
 	return sub;
 }
 
+#ifdef VDL2GPU_TESTHOOKS
+/* test build, invariant (a) at CTL_NWIN0, when a window [x, y) is closed: lane 0 walks the channel's first selection; a burst of a cluster
+ * K2b made (a static descriptor slot) that was triggered inside the window must belong to a candidate marked in onchain[] */
+__device__ __forceinline__ void k2p_check_onchain(const K2Params &p, int sc, int x, int y)
+{
+	if (threadIdx.x != 0 || !p.dbg)
+		return;
+	const unsigned dyn_base = (unsigned)p.nstreams * VDL2_CS * VDL2_CAND_CAP * VDL2_CL_MAXB;
+	const unsigned *sel0 = p.sel_list + (size_t)sc * VDL2_SEL_CAP;
+	unsigned n0 = p.ctl[CTL_NSEL0 + sc];
+	n0 = n0 > VDL2_SEL_CAP ? VDL2_SEL_CAP : n0;
+	for (unsigned i = 0; i < n0; ++i) {
+		const unsigned slot = sel0[i];
+		if (slot >= dyn_base)
+			continue;	/* (a serial stretch's burst: no cluster) */
+		const long long t = p.stage[slot].nstar - p.dec_base;
+		if (t >= x && t < y) {
+			K2_COUNT(p, K2_DBG_CHK_A);
+			if (!p.onchain[slot / VDL2_CL_MAXB])
+				K2_COUNT(p, K2_DBG_INV_A);
+		}
+	}
+}
+#endif
+
 __global__ __launch_bounds__(K2P_NT)
 void k2p_patch(K2Params p)
 {
@@ -999,7 +1053,13 @@ void k2p_patch(K2Params p)
 	 * the lists hold): stretches it was to look at have not been looked at, and a local repair verifies only what IT changes
 	 * [found by scripts/soak.py on handles whose item lists are small: seeds 6064, 6068, 6077] */
 	K2P_TR("k2p sc %d: fail_in %d ncand %d nold %d nslog %u ovf %u dec_base %lld\n", sc, fail_in, ncand, nold, nslog_in, ovf_in, (long long)p.dec_base);
-	if (ncand > VDL2_CAND_CAP || ovf_in != 0 || nnew <= 0 || nnew > K2S_MERGE || nslog_in > VDL2_SLOG_CAP || fail_in <= 0)
+	if (tid == 0 && ncand <= VDL2_CAND_CAP && ovf_in == 0) {	/* (with usable tables: what else refuses the repair) */
+		if (nnew > K2_MERGE_LIM(p))
+			K2_COUNT(p, K2_DBG_ESC_MERGE);
+		if (nslog_in > (unsigned)K2_SLOG_LIM(p))
+			K2_COUNT(p, K2_DBG_ESC_SLOG);
+	}
+	if (ncand > VDL2_CAND_CAP || ovf_in != 0 || nnew <= 0 || nnew > K2_MERGE_LIM(p) || nslog_in > (unsigned)K2_SLOG_LIM(p) || fail_in <= 0)
 		return;
 	__syncthreads();
 	if (tid == 0)
@@ -1080,11 +1140,14 @@ void k2p_patch(K2Params p)
 			/* the new chain idles from here to that candidate in a class the probe did not scan: the round's verify pass looks */
 			const int g_hi = t_next < t_end ? t_next : t_end;
 			if (g_hi > want) {
-				if (nsegs < VDL2_SEG_CAP) {
+				if (nsegs < K2_SEG_LIM(p)) {
 					if (tid == 0)
 						segs[nsegs] = Seg{want, g_hi, st.r, 0};
-				} else
+				} else {
+					if (tid == 0)
+						K2_COUNT(p, K2_DBG_ESC_SEG);
 					failed = true;
+				}
 				++nsegs;
 			}
 		}
@@ -1103,11 +1166,17 @@ void k2p_patch(K2Params p)
 		K2P_TR("  cand idx %d onchain %d\n", idx, (int)onchain[idx]);
 		if (onchain[idx]) {
 			/* the old chain met this candidate history-free as well: the same chain from here on */
-			if (nwin < VDL2_WIN_CAP) {
+			if (nwin < K2_WIN_LIM(p)) {
 				if (tid == 0)
 					ps.win[nwin] = make_int2(win_lo, t_old);
-			} else
+			} else {
+				if (tid == 0)
+					K2_COUNT(p, K2_DBG_ESC_WIN);
 				failed = true;
+			}
+#ifdef VDL2GPU_TESTHOOKS
+			k2p_check_onchain(p, sc, win_lo, t_old);
+#endif
 			++nwin;
 			t_cur = t_old;
 			in_window = false;
@@ -1149,16 +1218,26 @@ void k2p_patch(K2Params p)
 	__syncthreads();
 	K2P_TR(" end: to_end %d steady_end %d failed %d nwin %d nsegs %d pos %lld r %d\n", (int)to_end, (int)steady_end, (int)failed, nwin, nsegs, (long long)(st.pos - cx.dec_base), st.r);
 	if (to_end) {	/* the last window runs to the end of the data */
-		if (nwin < VDL2_WIN_CAP) {
+		if (nwin < K2_WIN_LIM(p)) {
 			if (tid == 0)
 				ps.win[nwin] = make_int2(win_lo, 0x7fffffff);
-		} else
+		} else {
+			if (tid == 0)
+				K2_COUNT(p, K2_DBG_ESC_WIN);
 			failed = true;
+		}
+#ifdef VDL2GPU_TESTHOOKS
+		k2p_check_onchain(p, sc, win_lo, 0x7fffffff);
+#endif
 		++nwin;
 	}
+	if (out.badslot && tid == 0)
+		K2_COUNT(p, K2_DBG_ESC_STAGE);
 	if (out.badslot)
 		failed = true;
 	if (failed) {	/* more windows or stretches than the lists hold: not repaired */
+		if (tid == 0)
+			K2_COUNT(p, K2_DBG_ESC_PATCH_ABANDON);
 		if (tid == 0) {
 			atomicMin(p.fail + sc, 0);
 			p.ctl[CTL_NSEL1 + sc] = 0;
@@ -1299,7 +1378,15 @@ template <bool LEV, bool SOFT, bool CAR = false> __device__ __forceinline__ void
 			if (base0 + i >= p.rec_cap)
 				break;
 			vdl2gpu_burst_t *rec = p.recs + base0 + i;
-			if (nwin == VDL2_WIN_ALL || k2_in_windows(win, nwin, rec->trig_dec - p.dec_base))	/* invariant (b) at CTL_NWIN0 */
+#ifdef VDL2GPU_TESTHOOKS
+			/* record i of the piece was made from entry i of the first selection (where windows are asked: a complete round re-makes the descriptors) */
+			if (nwin != VDL2_WIN_ALL) {
+				K2_COUNT(p, K2_DBG_CHK_B_RECORD);
+				if (p.stage[sel0[i]].nstar != rec->trig_dec)
+					K2_COUNT(p, K2_DBG_INV_B_RECORD);
+			}
+#endif
+			if (nwin == VDL2_WIN_ALL || k2_in_windows(p, win, nwin, rec->trig_dec - p.dec_base))	/* invariant (b) at CTL_NWIN0 */
 				rec->trig_sample = 2;
 		}
 	}
@@ -1325,8 +1412,18 @@ template <bool LEV, bool SOFT, bool CAR = false> __device__ __forceinline__ void
 		const bool second = i >= na;
 		const BurstDesc d = p.stage[second ? sel1[i - na] : sel0[i]];
 		/* (block-uniform) a burst of the first selection inside a repaired window: not on the chain any more */
-		if (!second && p.sel_mode == 2 && nwin != 0 && k2_in_windows(win, nwin, d.nstar - p.dec_base))
+		if (!second && p.sel_mode == 2 && nwin != 0 && k2_in_windows(p, win, nwin, d.nstar - p.dec_base))
 			continue;
+#ifdef VDL2GPU_TESTHOOKS
+		{	/* invariant (b) at CTL_NWIN0: a cluster's first descriptor (static slot, burst 0) against its candidate */
+			const unsigned dslot = second ? sel1[i - na] : sel0[i];
+			if (threadIdx.x == 0 && dslot < (unsigned)p.nstreams * VDL2_CS * VDL2_CAND_CAP * VDL2_CL_MAXB && dslot % VDL2_CL_MAXB == 0) {
+				K2_COUNT(p, K2_DBG_CHK_B_DECODE);
+				if (d.nstar != p.dec_base + p.cands[dslot / VDL2_CL_MAXB].nrel)
+					K2_COUNT(p, K2_DBG_INV_B_DECODE);
+			}
+		}
+#endif
 		unsigned slot;
 		if (p.sel_reserved)
 			slot = (second ? base1 : base0) + (second ? i - na : i);

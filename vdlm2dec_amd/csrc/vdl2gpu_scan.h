@@ -1076,17 +1076,40 @@ void k2r_regions(K2Params p)
 			const int nchunk = (hi - lo + K2A_TS - 1) / K2A_TS;
 			const int base = atomicAdd(&s_nreg, nchunk);
 			for (int k = 0; k < nchunk; ++k)
-				if (base + k < VDL2_REG_CAP) {
+				if (base + k < VDL2_REG_CAP) {	/* (a test build's lower limit is applied below, to the whole list) */
 					const int q = lo + k * K2A_TS;
 					regs[base + k] = make_int2(q, (hi - q < K2A_TS) ? hi - q : K2A_TS);
 				}
 		}
 		__syncthreads();
+#ifdef VDL2GPU_TESTHOOKS
+		/* a lowered limit (VDL2GPU_TEST_REG_CAP) keeps the same regions in every run, spread over the push: of the n listed, in time order,
+		 * numbers floor(k n / lim), k < lim -- so that stretches with regions and stretches without alternate (which ones the list holds
+		 * when it is really full is the order the wavefronts above arrived in).  Every region finds its rank by counting. */
+		if (K2_REG_LIM(p) < VDL2_REG_CAP && s_nreg > K2_REG_LIM(p)) {
+			const int n = s_nreg < VDL2_REG_CAP ? s_nreg : VDL2_REG_CAP, lim = K2_REG_LIM(p);
+			for (int i = tid; i < n; i += K2R_NT)
+				key64[i] = ((unsigned long long)(unsigned)regs[i].x << 32) | (unsigned)regs[i].y;
+			__syncthreads();
+			for (int i = tid; i < n; i += K2R_NT) {
+				const int x = (int)(key64[i] >> 32);
+				int rank = 0;
+				for (int j = 0; j < n; ++j)
+					rank += ((int)(key64[j] >> 32) < x) ? 1 : 0;
+				const int k = (int)(((long long)rank * lim + n - 1) / n);
+				if (k < lim && (int)((long long)k * n / lim) == rank)
+					regs[k] = make_int2(x, (int)(key64[i] & 0xffffffffu));
+			}
+			__syncthreads();
+		}
+#endif
 		if (tid == 0) {
 			const int n = s_nreg;
 			/* more regions than the list holds: the surplus is dropped -- regions are a cost decision, what a
 			 * missing one would have found the verify pass finds (and a repair round scans the channel completely) */
-			p.ctl[CTL_NREG0 + sc] = (unsigned)(n > VDL2_REG_CAP ? VDL2_REG_CAP : n);
+			p.ctl[CTL_NREG0 + sc] = (unsigned)(n > K2_REG_LIM(p) ? K2_REG_LIM(p) : n);
+			if (n > K2_REG_LIM(p))
+				K2_COUNT(p, K2_DBG_ESC_REG);
 			p.ctl[CTL_NSEED0 + sc] = 0;
 		}
 	}
@@ -1243,7 +1266,9 @@ void k2a_verify(K2Params p)
 	const long long dec_base = p.dec_base;
 	const int t_end = (int)(VDL2_CARRY_FRAMES + p.J);
 	int nseg = (int)p.ctl[CTL_NSEG0 + sc];
-	nseg = nseg < 0 || nseg > VDL2_SEG_CAP ? VDL2_SEG_CAP : nseg;	/* (the resolver counts the stretches the list did not hold as well) */
+	if (tid == 0 && blockIdx.x == 0 && (nseg < 0 || nseg > K2_SEG_LIM(p)))
+		K2_COUNT(p, K2_DBG_ESC_SEG);
+	nseg = nseg < 0 || nseg > K2_SEG_LIM(p) ? K2_SEG_LIM(p) : nseg;	/* (the resolver counts the stretches the list did not hold as well) */
 	const Seg *segs = p.segs + (size_t)sc * VDL2_SEG_CAP;
 	if (nseg == 0)	/* (block-uniform) nothing to look at: not even the tables */
 		return;

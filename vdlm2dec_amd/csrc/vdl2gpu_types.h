@@ -255,7 +255,50 @@ struct K2Params {
 	unsigned *headtap_n;
 	unsigned headtap_cap;
 	vdl2gpu_carrier_t *carrier;	/* VDL2GPU_F_CARRIER: one record of phase-error sums per record slot of `recs`, else nullptr (last: the other members keep their place) */
+#ifdef VDL2GPU_TESTHOOKS
+	/* test hooks (VDL2GPU_TEST_*_CAP): what the back stage's lists hold, at most their compile-time sizes (the host fills in the size where
+	 * the hook is unset).  Only the comparisons read these (K2_*_LIM below); strides, LDS arrays and allocations keep the constants.
+	 * (lim_reg also decides WHICH regions a lowered limit keeps: the same ones in every run, evenly spread over the push -- k2r_regions) */
+	int lim_reg, lim_seg, lim_vis, lim_win, lim_merge, lim_slog;
+#endif
 };
+/* What a list of the back stage holds: the compile-time size, in a test build the run-time value beside it (K2Params.lim_*).  Every
+ * comparison against a size goes through its macro, so that a lowered limit is one limit everywhere. */
+#ifdef VDL2GPU_TESTHOOKS
+#define K2_REG_LIM(p) ((p).lim_reg)
+#define K2_SEG_LIM(p) ((p).lim_seg)
+#define K2_VIS_LIM(p) ((p).lim_vis)
+#define K2_WIN_LIM(p) ((p).lim_win)
+#define K2_MERGE_LIM(p) ((p).lim_merge)
+#define K2_SLOG_LIM(p) ((p).lim_slog)
+/* Development counters behind the kernels' cycle counters (K2Params.dbg, vdl2gpu_debug_counters: 96 words in a test build, 64 in the product).
+ * [64 .. 70] escapes: how often a kernel took the branch for a full list --
+ *   64 regions (k2r_regions)  65 verify stretches (k2_emit_seg, k2p_patch, k2a_verify's clamp)  66 visited list (k2c_walk, k2c_resolve)
+ *   67 windows (k2p_patch)  68 merge (k2p_patch, k2s_merge: also in 75)  69 serial-stretch log (k2c_publish, k2p_patch)
+ *   70 descriptor pool or selection list full under a kernel that stages descriptors (k2b_clusters, k2c_resolve, k2p_patch: MachOut.badslot)
+ * [71 .. 74] violations of the two invariants at CTL_NWIN0 (every test reads zero) --
+ *   71 (b) k2b_clusters: a cluster's first descriptor whose nstar is not dec_base + its candidate's nrel
+ *   72 (b) k2d_run: the same, of every first descriptor of a cluster it decodes
+ *   73 (b) k2d_run, sel_mode 1: a record whose trig_dec is not the nstar of the descriptor it was made from
+ *   74 (a) k2p_patch: a burst of the first selection triggered inside a window whose cluster's candidate is not marked in onchain[]
+ * [75] of the merge escapes, those of k2s_merge (a further round: the resolver takes the channel through the serial machine)
+ * [76] k2p_patch gave a repair up that it had begun (k2_begin_repair had run: more windows or stretches than the lists hold, or the pool full)
+ * [77 .. 80] how often the checks behind 71 .. 74 were made (a zero there says something only if these are not) */
+enum { K2_DBG_ESC_REG = 64, K2_DBG_ESC_SEG, K2_DBG_ESC_VIS, K2_DBG_ESC_WIN, K2_DBG_ESC_MERGE, K2_DBG_ESC_SLOG, K2_DBG_ESC_STAGE,
+       K2_DBG_INV_B_CLUSTER, K2_DBG_INV_B_DECODE, K2_DBG_INV_B_RECORD, K2_DBG_INV_A, K2_DBG_ESC_MERGE_SORT,
+       K2_DBG_ESC_PATCH_ABANDON, K2_DBG_CHK_B_CLUSTER, K2_DBG_CHK_B_DECODE, K2_DBG_CHK_B_RECORD, K2_DBG_CHK_A };
+#define VDL2_DBG_WORDS 96
+#define K2_COUNT(p, slot) do { if ((p).dbg) atomicAdd((p).dbg + (slot), 1ull); } while (0)
+#else
+#define K2_REG_LIM(p) VDL2_REG_CAP
+#define K2_SEG_LIM(p) VDL2_SEG_CAP
+#define K2_VIS_LIM(p) K2C_VIS
+#define K2_WIN_LIM(p) VDL2_WIN_CAP
+#define K2_MERGE_LIM(p) K2S_MERGE
+#define K2_SLOG_LIM(p) VDL2_SLOG_CAP
+#define VDL2_DBG_WORDS 64
+#define K2_COUNT(p, slot) do { } while (0)
+#endif
 #define CTL_OUT 0
 #define CTL_OUT_OVF 1
 #define CTL_STAGE 2

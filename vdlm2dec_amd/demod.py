@@ -380,7 +380,7 @@ class Receiver:
         return buf[:n].copy()
 
     def debug_counters(self, n: int = 16, reset: bool = True):
-        buf = (C.c_ulonglong * 64)()
+        buf = (C.c_ulonglong * max(64, n))()     # (64 words; the test library has 96: its escape and invariant counters lie behind)
         self._check(self.L.vdl2gpu_debug_counters(self.h, buf, n, int(reset)))
         return list(buf[:n])
 
