@@ -307,6 +307,71 @@ typedef struct {
 	float rms_rad;		/* @28 spread of the slices around their mean, rad */
 } vdl2gpu_carrier_t;		/* sizeof 32, alignment 4 */
 
+/* ---- block report (VDL2GPU_F_BLOCK_REPORT; announced by VDL2GPU_HAVE_BLOCK_REPORT, the ABI version is unchanged) ----
+ * The block path (vdlm2.c:84-161: RS(255,249) per row, HDLC un-stuffing, flag hunt, check_frame) hands on the frames that pass and
+ * nothing else; the reference says at verbose > 2 why a candidate did not ("#%d error too short", "#%d error crc", vdlm2.c:44-58).
+ * With VDL2GPU_F_BLOCK_REPORT (which needs VDL2GPU_F_FRAMES: without it vdl2gpu_create returns VDL2GPU_EINVAL) every burst record
+ * gets a vdl2gpu_blockrep_t that says what the block path made of it; vdl2gpu_decode_blocks_report gives the same for a batch on
+ * any handle.  For a record with header values nbrow, nlbyte (status 0):
+ *   rows        r < nbrow.  Row r has `by` data bytes (249, the last row nlbyte), e0 fixed erasures from set_eras() (vdlm2.c:63-82:
+ *               the last row's 251..254 for by <= 30, 253..254 for by <= 67) and p_r transmitted parity bytes, all as at
+ *               vdl2gpu_soft_t.  The RECEIVED row is data[r] of the record.
+ *   row_roots   what rs() (rs.c:81) returns for the received row with those erasures: -1, or the number of roots it corrected
+ *               (erasures count); 0 means all six syndromes were zero.  In soft mode too this is the reference's run on the received
+ *               row, not a trial's.
+ *   row_how     (the VDL2GPU_ROW_* names are #defines, below)
+ *               VDL2GPU_ROW_CLEAN  the received row's syndromes are all zero: nothing was touched
+ *               VDL2GPU_ROW_REF    rs() returned >= 0: the row is what the reference decodes (a miscorrection included)
+ *               VDL2GPU_ROW_SOFT2 / _SOFT4  soft mode (the record has a reliability map): rs() returned -1 and the trial with
+ *                                  2 / 4 candidates of the row rule (vdl2gpu_soft_t, step 3) replaced the row
+ *               VDL2GPU_ROW_FAIL   rs() returned -1 and no trial replaced the row (hard mode: none is made; soft mode: e0 + 2 > 4,
+ *                                  or every trial failed): the row is what the reference left, its partial corrections included
+ *               VDL2GPU_ROW_NONE   r >= nbrow
+ *   row_changed the positions j in [0, by) or [249, 249 + p_r) -- the bytes that were transmitted -- at which the row the un-stuffer
+ *               reads differs from the received row: the "octets corrected by FEC" of row r (0..255)
+ *   stuffed     the zeros the un-stuffer dropped (t == 5, vdlm2.c:127-130) over the 249 (nbrow - 1) + nlbyte data bytes of all rows;
+ *               the run of ones carries over from row to row, as in the reference
+ *   nbytes      whole un-stuffed bytes: (8 * data bytes - stuffed) / 8, rounded down; byte i is bits 8i .. 8i + 7 of that stream
+ *   flag_at     the first i at which the OR of bytes 0..i equals 0x7e -- hdata[0] reaching the flag (vdlm2.c:136-139); -1: never
+ *               (no bit was set at all, or a bit outside 0x7e came first)
+ *   cand        calls of check_frame() (vdlm2.c:143): bytes equal to 0x7e behind hdata[1], the first byte behind flag_at that is no
+ *               0x7e.  A candidate's l counts from hdata[0] to that byte, both included.
+ *   too_short   of them l < 13 ("error too short");  bad_fcs  of them l >= 13 with an FCS residue other than 0xf0b8 ("error crc");
+ *   frames      of them handed to out(): cand == too_short + bad_fcs + frames.  This counts every frame that checks, also one the
+ *               library then drops (more than 12 in a burst, arena or caller's buffer full: vdl2gpu_stats_t.frames_dropped, *dropped).
+ * status 1: nbrow outside 1..8 or nlbyte outside 0..249; the block path does not run and every other field is 0.
+ * Each field is a function of the burst record alone -- or, in soft mode (a handle with VDL2GPU_F_SOFT_RS, or soft[i] given to
+ * vdl2gpu_decode_blocks_report), of the record and its reliability map: integers, no order of summation to define.  A burst
+ * therefore gets the same report whatever kernel, path or repair round decoded it and however the stream was cut into pushes, and
+ * vdl2gpu_decode_blocks_report on polled records and maps reproduces it.  The record's data[] stays the received rows, as without
+ * the flag.  Nothing else changes with the flag: records, frames, their order and every other column are what they are without it.
+ * Memory: 48 bytes per record slot in each of the device output rings and each host slab, and in the host queue beside every burst
+ * record it holds. */
+#define VDL2GPU_F_BLOCK_REPORT 2048u
+#define VDL2GPU_HAVE_BLOCK_REPORT 1
+#define VDL2GPU_ROW_NONE 0
+#define VDL2GPU_ROW_CLEAN 1
+#define VDL2GPU_ROW_REF 2
+#define VDL2GPU_ROW_SOFT2 3
+#define VDL2GPU_ROW_SOFT4 4
+#define VDL2GPU_ROW_FAIL 5
+typedef struct {
+	int8_t row_roots[8];	/* @0  rs()'s return value for the received row; rows >= nbrow: 0 */
+	uint8_t row_how[8];	/* @8  VDL2GPU_ROW_* */
+	uint8_t row_changed[8];	/* @16 transmitted positions at which the decoded row differs from the received one */
+	uint16_t bytes_changed;	/* @24 sum of row_changed[] */
+	uint16_t rows_failed;	/* @26 rows with row_how == VDL2GPU_ROW_FAIL */
+	uint16_t rows_rescued;	/* @28 rows with row_how == VDL2GPU_ROW_SOFT2 or _SOFT4 */
+	uint16_t stuffed;	/* @30 zeros the un-stuffer dropped */
+	uint16_t nbytes;	/* @32 whole un-stuffed bytes */
+	int16_t flag_at;	/* @34 index of the un-stuffed byte that completes the first flag, -1: never */
+	uint16_t cand;		/* @36 calls of check_frame() */
+	uint16_t too_short;	/* @38 ... with l < 13 */
+	uint16_t bad_fcs;	/* @40 ... with l >= 13 and the wrong FCS */
+	uint16_t frames;	/* @42 ... that passed */
+	int32_t status;		/* @44 0: the block path ran; 1: header out of range, all other fields 0 */
+} vdl2gpu_blockrep_t;		/* sizeof 48, alignment 4 */
+
 typedef struct {
 	uint64_t samples_in;	/* per stream */
 	uint64_t dec_samples;	/* 84 kS/s samples produced per channel */
@@ -421,6 +486,11 @@ int vdl2gpu_poll_soft_ready(vdl2gpu_t *h, vdl2gpu_burst_t *out, vdl2gpu_level_t 
  * without VDL2GPU_F_CARRIER: VDL2GPU_EINVAL, and nothing is consumed; lv and soft as above. */
 int vdl2gpu_poll_carrier(vdl2gpu_t *h, vdl2gpu_burst_t *out, vdl2gpu_level_t *lv, vdl2gpu_soft_t *soft, vdl2gpu_carrier_t *car, int max);
 int vdl2gpu_poll_carrier_ready(vdl2gpu_t *h, vdl2gpu_burst_t *out, vdl2gpu_level_t *lv, vdl2gpu_soft_t *soft, vdl2gpu_carrier_t *car, int max);
+/* ... and with the bursts' block reports: rep[i] belongs to out[i] (VDL2GPU_F_BLOCK_REPORT).  Same queue, order, waiting and threading
+ * as the other collectors; each of lv, soft, car and rep may be NULL (rep == NULL: exactly vdl2gpu_poll_carrier).  rep != NULL on a
+ * handle created without VDL2GPU_F_BLOCK_REPORT: VDL2GPU_EINVAL, and nothing is consumed; lv, soft and car as above. */
+int vdl2gpu_poll_report(vdl2gpu_t *h, vdl2gpu_burst_t *out, vdl2gpu_level_t *lv, vdl2gpu_soft_t *soft, vdl2gpu_carrier_t *car, vdl2gpu_blockrep_t *rep, int max);
+int vdl2gpu_poll_report_ready(vdl2gpu_t *h, vdl2gpu_burst_t *out, vdl2gpu_level_t *lv, vdl2gpu_soft_t *soft, vdl2gpu_carrier_t *car, vdl2gpu_blockrep_t *rep, int max);
 /* Number of bursts a poll would currently return (implies vdl2gpu_sync). */
 int vdl2gpu_pending(vdl2gpu_t *h);
 /* Pushes the GPU has not finished yet (0..3); never waits.  For a producer that is not bound to real time and wants to
@@ -436,6 +506,8 @@ int vdl2gpu_get_timing(vdl2gpu_t *h, vdl2gpu_timing_t *out, int reset);
  * of the front stage; [4] moving uncollected records out of the slab's way; [5] enqueueing the back stage and the tail; [6] (part of
  * [2] and of the polling calls) waiting for a ring's completion event; [7] the pushes counted.  Replaces nothing of the reference. */
 int vdl2gpu_get_host_profile(vdl2gpu_t *h, double *out8, int reset);
+/* h == NULL: why the calling thread's last vdl2gpu_create refused its configuration, where it says (a static string; today
+ * VDL2GPU_F_BLOCK_REPORT without VDL2GPU_F_FRAMES), else "null handle". */
 const char *vdl2gpu_last_error(vdl2gpu_t *h);
 const char *vdl2gpu_strerror(int code);
 
@@ -482,6 +554,10 @@ int vdl2gpu_decode_blocks(vdl2gpu_t *h, const vdl2gpu_burst_t *blocks, int n,
  * through the row rule of vdl2gpu_soft_t.  Works on any handle; soft == NULL: exactly vdl2gpu_decode_blocks. */
 int vdl2gpu_decode_blocks_soft(vdl2gpu_t *h, const vdl2gpu_burst_t *blocks, const vdl2gpu_soft_t *soft, int n,
 			       vdl2gpu_frame_t *frames, int max_frames, int *dropped);
+/* ... and with the block reports (vdl2gpu_blockrep_t): rep[i] belongs to blocks[i], n of them, whatever becomes of the frames (also
+ * with max_frames == 0).  Works on any handle; soft may be NULL (hard mode); rep == NULL: exactly vdl2gpu_decode_blocks_soft. */
+int vdl2gpu_decode_blocks_report(vdl2gpu_t *h, const vdl2gpu_burst_t *blocks, const vdl2gpu_soft_t *soft, int n,
+				 vdl2gpu_frame_t *frames, int max_frames, int *dropped, vdl2gpu_blockrep_t *rep);
 /* With VDL2GPU_F_FRAMES the same kernel runs on every push's burst records where they lie in device
  * memory, right behind the demodulator.  Collect the frames of everything pushed so far (waits like
  * vdl2gpu_poll; the bursts themselves stay available through vdl2gpu_poll).  Frames come out ordered

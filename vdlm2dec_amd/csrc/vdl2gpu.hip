@@ -94,8 +94,8 @@ struct LaterEvent {
 
 /* A burst record has side columns: entries at the record's index in the device rings, the slabs and the host queue, present when
  * the handle's flags ask for them.  A column is one row here and its flag in create_impl. */
-enum { COL_SOFT, COL_LEVEL, COL_CARRIER, VDL2_NCOL };	/* VDL2GPU_F_SOFT_RS: a reliability map (2048 bytes); VDL2GPU_F_LEVELS: a level record; VDL2GPU_F_CARRIER: a carrier record */
-static const size_t col_bytes[VDL2_NCOL] = { sizeof(vdl2gpu_soft_t), sizeof(vdl2gpu_level_t), sizeof(vdl2gpu_carrier_t) };
+enum { COL_SOFT, COL_LEVEL, COL_CARRIER, COL_REPORT, VDL2_NCOL };	/* VDL2GPU_F_SOFT_RS: a reliability map (2048 bytes); VDL2GPU_F_LEVELS: a level record; VDL2GPU_F_CARRIER: a carrier record; VDL2GPU_F_BLOCK_REPORT: a block report */
+static const size_t col_bytes[VDL2_NCOL] = { sizeof(vdl2gpu_soft_t), sizeof(vdl2gpu_level_t), sizeof(vdl2gpu_carrier_t), sizeof(vdl2gpu_blockrep_t) };
 
 /* A table set (push % VDL2_NSET): what a push's demodulator kernels work in, see alloc_sets. */
 struct TableSet {
@@ -126,6 +126,7 @@ struct OutRing {
 	vdl2gpu_level_t *levels() const { return static_cast<vdl2gpu_level_t *>(d_side[COL_LEVEL]); }
 	vdl2gpu_soft_t *soft() const { return static_cast<vdl2gpu_soft_t *>(d_side[COL_SOFT]); }
 	vdl2gpu_carrier_t *carrier() const { return static_cast<vdl2gpu_carrier_t *>(d_side[COL_CARRIER]); }
+	vdl2gpu_blockrep_t *report() const { return static_cast<vdl2gpu_blockrep_t *>(d_side[COL_REPORT]); }
 };
 
 /* A slab (push % VDL2_NSLAB) of page-locked host memory, which the GPU itself fills at the end of the push (k_export_records), and
@@ -139,6 +140,7 @@ struct Slab {
 	vdl2gpu_level_t *d_levels() const { return static_cast<vdl2gpu_level_t *>(d_side[COL_LEVEL]); }
 	vdl2gpu_soft_t *d_soft() const { return static_cast<vdl2gpu_soft_t *>(d_side[COL_SOFT]); }
 	vdl2gpu_carrier_t *d_carrier() const { return static_cast<vdl2gpu_carrier_t *>(d_side[COL_CARRIER]); }
+	vdl2gpu_blockrep_t *d_report() const { return static_cast<vdl2gpu_blockrep_t *>(d_side[COL_REPORT]); }
 };
 
 /* Records in pageable storage, with their side columns (byte vectors: col_bytes[k] a record). */
@@ -572,10 +574,13 @@ extern "C" const char *vdl2gpu_strerror(int code)
 
 #define HLOCK(h) std::unique_lock<std::recursive_mutex> hlock_((h)->mu)
 
+/* why this thread's last vdl2gpu_create refused its configuration, where it says (there is no handle to keep the text in) */
+static thread_local const char *create_err = nullptr;
+
 extern "C" const char *vdl2gpu_last_error(vdl2gpu_t *h)
 {
 	if (!h)
-		return "null handle";
+		return create_err ? create_err : "null handle";
 	HLOCK(h);
 	return h->err.c_str();	/* (valid until the next call on the handle, from any thread) */
 }
@@ -1002,6 +1007,7 @@ static int create_impl(vdl2gpu_t *h)
 	h->col_on[COL_LEVEL] = (cfg.flags & VDL2GPU_F_LEVELS) != 0;
 	h->col_on[COL_SOFT] = (cfg.flags & VDL2GPU_F_SOFT_RS) != 0;
 	h->col_on[COL_CARRIER] = (cfg.flags & VDL2GPU_F_CARRIER) != 0;
+	h->col_on[COL_REPORT] = (cfg.flags & VDL2GPU_F_BLOCK_REPORT) != 0;	/* (vdl2gpu_create: only with VDL2GPU_F_FRAMES) */
 	h->frames_on = (cfg.flags & VDL2GPU_F_FRAMES) != 0;
 	if (h->frames_on) {
 		unsigned arena = 4u << 20;
@@ -1161,6 +1167,7 @@ static int create_impl(vdl2gpu_t *h)
 
 extern "C" int vdl2gpu_create(const vdl2gpu_config_t *cfg, vdl2gpu_t **out)
 {
+	create_err = nullptr;
 	if (!cfg || !out || cfg->struct_size != sizeof(vdl2gpu_config_t))
 		return VDL2GPU_EINVAL;
 	if (cfg->nbch < 1 || cfg->nbch > VDL2GPU_MAXCH || cfg->nstreams < 1 || !cfg->chan || !cfg->max_push)
@@ -1183,6 +1190,10 @@ extern "C" int vdl2gpu_create(const vdl2gpu_config_t *cfg, vdl2gpu_t **out)
 	if (cfg->flags & VDL2GPU_F_TEST_NOREGION)
 		return VDL2GPU_EINVAL;	/* test handicaps are compiled into libvdl2gpu_test.so only */
 #endif
+	if ((cfg->flags & VDL2GPU_F_BLOCK_REPORT) && !(cfg->flags & VDL2GPU_F_FRAMES)) {
+		create_err = "vdl2gpu_create: VDL2GPU_F_BLOCK_REPORT needs VDL2GPU_F_FRAMES (the pipeline has no block path to report on)";
+		return VDL2GPU_EINVAL;
+	}
 	const unsigned sdrclk = cfg->sdrclk ? cfg->sdrclk : cfg->sdrinrate / 4000;
 	if (sdrclk <= 21 || sdrclk > 1000000)
 		return VDL2GPU_EINVAL;
@@ -1587,6 +1598,7 @@ static K4Params k4_ring_params(vdl2gpu_t *h, int ring, const unsigned *fmask)
 	k4.tabs = h->d_k4tab;
 	k4.fmask = fmask;
 	k4.soft = h->ring[ring].soft();	/* (nullptr without VDL2GPU_F_SOFT_RS: the reference's block path) */
+	k4.rep = h->ring[ring].report();	/* (nullptr without VDL2GPU_F_BLOCK_REPORT, and k4_frames is launched, which does not look at it) */
 	return k4;
 }
 
@@ -1741,7 +1753,8 @@ static int enqueue_back(vdl2gpu_t *h)
 		/* block path on the records where they lie (vdlm2.c:84-161).  In the chain, not beside it:
 		 * a latency-bound kernel like this one and the next push's scan slow each other down by
 		 * more than the overlap saves. */
-		hipLaunchKernelGGL(k4_frames, dim3((unsigned)h->n_cu * 16), dim3(K4_NT), 0, ts, k4_ring_params(h, ring, spec ? h->set[par].k2.fmask : nullptr));
+		hipLaunchKernelGGL(h->col_on[COL_REPORT] ? k4_frames_rep : k4_frames, dim3((unsigned)h->n_cu * 16), dim3(K4_NT), 0, ts,
+				   k4_ring_params(h, ring, spec ? h->set[par].k2.fmask : nullptr));
 		HIPCHK(h, hipGetLastError());
 	}
 	TRY(mark(h, pt, E_BLOCKS_END, ts));
@@ -1758,6 +1771,8 @@ static int enqueue_back(vdl2gpu_t *h)
 		ke.sdst = h->slab[h->back.slab].d_soft();
 		ke.car = h->ring[ring].carrier();	/* (nullptr without VDL2GPU_F_CARRIER) */
 		ke.cdst = h->slab[h->back.slab].d_carrier();
+		ke.rep = h->ring[ring].report();	/* (nullptr without VDL2GPU_F_BLOCK_REPORT) */
+		ke.rdst = h->slab[h->back.slab].d_report();
 		hipLaunchKernelGGL(k_export_records, dim3((unsigned)h->n_cu), dim3(256), 0, ts, ke);
 		HIPCHK(h, hipGetLastError());
 		TRY(mark(h, pt, E_EXPORT_END, ts, true));
@@ -2466,7 +2481,7 @@ static int collect_records(vdl2gpu_t *h, int ring, unsigned n)
 		HIPCHK(h, hipStreamSynchronize(h->copy_stream));
 		const vdl2gpu_burst_t *pin = reinterpret_cast<const vdl2gpu_burst_t *>(h->h_pin);
 		h->ready.recs.insert(h->ready.recs.end(), pin, pin + m);
-		for (int k = 0; k < VDL2_NCOL; ++k) {	/* the side columns present (32 or 40 bytes a record, or 2048: a pageable copy) */
+		for (int k = 0; k < VDL2_NCOL; ++k) {	/* the side columns present (32, 40 or 48 bytes a record, or 2048: a pageable copy) */
 			if (!h->col_on[k])
 				continue;
 			std::vector<uint8_t> &q = h->ready.side[k];
@@ -2731,12 +2746,14 @@ struct BlockTemps {
 	vdl2gpu_soft_t *soft = nullptr;
 	vdl2gpu_frame_t *fr = nullptr;
 	unsigned *cnt = nullptr;
+	vdl2gpu_blockrep_t *rep = nullptr;
 	~BlockTemps()
 	{
 		(void)hipFree(blk);
 		(void)hipFree(soft);
 		(void)hipFree(fr);
 		(void)hipFree(cnt);
+		(void)hipFree(rep);
 	}
 };
 
@@ -2753,17 +2770,25 @@ static K4Params k4_block_params(vdl2gpu_t *h, const BlockTemps &d, int n, int ma
 	k4.compact = 0;
 	k4.tabs = h->d_k4tab;
 	k4.soft = d.soft;
+	k4.rep = d.rep;
 	return k4;
 }
 
 extern "C" int vdl2gpu_decode_blocks_soft(vdl2gpu_t *h, const vdl2gpu_burst_t *blocks, const vdl2gpu_soft_t *soft, int n,
 					  vdl2gpu_frame_t *frames, int max_frames, int *dropped)
 {
+	return vdl2gpu_decode_blocks_report(h, blocks, soft, n, frames, max_frames, dropped, nullptr);
+}
+
+/* rep: k4_frames_rep instead of k4_frames, and its n reports come back beside the frames */
+extern "C" int vdl2gpu_decode_blocks_report(vdl2gpu_t *h, const vdl2gpu_burst_t *blocks, const vdl2gpu_soft_t *soft, int n,
+					    vdl2gpu_frame_t *frames, int max_frames, int *dropped, vdl2gpu_blockrep_t *rep)
+{
 	if (!h || n < 0 || max_frames < 0 || (n > 0 && !blocks) || (max_frames > 0 && !frames))
 		return VDL2GPU_EINVAL;
 	if (dropped)
 		*dropped = 0;
-	if (n == 0 || max_frames == 0)
+	if (n == 0 || (max_frames == 0 && !rep))
 		return 0;
 	HLOCK(h);
 	HIPCHK(h, hipSetDevice(h->cfg.device));
@@ -2777,8 +2802,10 @@ extern "C" int vdl2gpu_decode_blocks_soft(vdl2gpu_t *h, const vdl2gpu_burst_t *b
 	BLKCHK(hipMalloc(&d.blk, (size_t)n * sizeof(vdl2gpu_burst_t)));
 	if (soft)
 		BLKCHK(hipMalloc(&d.soft, (size_t)n * sizeof(vdl2gpu_soft_t)));
-	BLKCHK(hipMalloc(&d.fr, (size_t)max_frames * sizeof(vdl2gpu_frame_t)));
+	BLKCHK(hipMalloc(&d.fr, (size_t)std::max(max_frames, 1) * sizeof(vdl2gpu_frame_t)));
 	BLKCHK(hipMalloc(&d.cnt, 4 * sizeof(unsigned)));
+	if (rep)
+		BLKCHK(hipMalloc(&d.rep, (size_t)n * sizeof(vdl2gpu_blockrep_t)));
 	/* on the stream the kernel runs on: that stream does not wait for the legacy default stream, and a
 	 * plain hipMemset() that lands after the kernel's first atomics loses frames */
 	BLKCHK(hipMemcpyAsync(d.blk, blocks, (size_t)n * sizeof(vdl2gpu_burst_t), hipMemcpyHostToDevice, h->copy_stream));
@@ -2786,8 +2813,10 @@ extern "C" int vdl2gpu_decode_blocks_soft(vdl2gpu_t *h, const vdl2gpu_burst_t *b
 		BLKCHK(hipMemcpyAsync(d.soft, soft, (size_t)n * sizeof(vdl2gpu_soft_t), hipMemcpyHostToDevice, h->copy_stream));
 	BLKCHK(hipMemsetAsync(d.cnt, 0, 4 * sizeof(unsigned), h->copy_stream));
 	const unsigned grid = (unsigned)std::min<long long>(n, (long long)h->n_cu * 32);
-	hipLaunchKernelGGL(k4_frames, dim3(grid), dim3(K4_NT), 0, h->copy_stream, k4_block_params(h, d, n, max_frames));
+	hipLaunchKernelGGL(rep ? k4_frames_rep : k4_frames, dim3(grid), dim3(K4_NT), 0, h->copy_stream, k4_block_params(h, d, n, max_frames));
 	BLKCHK(hipGetLastError());
+	if (rep)	/* (no record is void here: every one of the n has been written) */
+		BLKCHK(hipMemcpyAsync(rep, d.rep, (size_t)n * sizeof(vdl2gpu_blockrep_t), hipMemcpyDeviceToHost, h->copy_stream));
 	BLKCHK(hipStreamSynchronize(h->copy_stream));
 	unsigned cnt[2] = {0, 0};
 	BLKCHK(hipMemcpyAsync(cnt, d.cnt, sizeof cnt, hipMemcpyDeviceToHost, h->copy_stream));
@@ -2872,16 +2901,17 @@ extern "C" int vdl2gpu_inflight(vdl2gpu_t *h)
 	return n;
 }
 
-/* The eight collectors.  lv / sv / cv: the side columns the caller wants beside the records (nullptr: not); lv_err / sv_err / cv_err:
- * what the entry point says when the handle was made without that column. */
+/* The ten collectors.  lv / sv / cv / rv: the side columns the caller wants beside the records (nullptr: not); lv_err / sv_err / cv_err /
+ * rv_err: what the entry point says when the handle was made without that column. */
 static int poll_impl(vdl2gpu_t *h, vdl2gpu_burst_t *out, vdl2gpu_level_t *lv, vdl2gpu_soft_t *sv, int max, bool blocking,
-		     const char *lv_err = nullptr, const char *sv_err = nullptr, vdl2gpu_carrier_t *cv = nullptr, const char *cv_err = nullptr)
+		     const char *lv_err = nullptr, const char *sv_err = nullptr, vdl2gpu_carrier_t *cv = nullptr, const char *cv_err = nullptr,
+		     vdl2gpu_blockrep_t *rv = nullptr, const char *rv_err = nullptr)
 {
 	if (!h || (max > 0 && !out) || max < 0)
 		return VDL2GPU_EINVAL;
 	HLOCK(h);
-	if ((lv && !h->col_on[COL_LEVEL]) || (sv && !h->col_on[COL_SOFT]) || (cv && !h->col_on[COL_CARRIER])) {
-		h->err = lv && !h->col_on[COL_LEVEL] ? lv_err : (sv && !h->col_on[COL_SOFT] ? sv_err : cv_err);
+	if ((lv && !h->col_on[COL_LEVEL]) || (sv && !h->col_on[COL_SOFT]) || (cv && !h->col_on[COL_CARRIER]) || (rv && !h->col_on[COL_REPORT])) {
+		h->err = lv && !h->col_on[COL_LEVEL] ? lv_err : (sv && !h->col_on[COL_SOFT] ? sv_err : (cv && !h->col_on[COL_CARRIER] ? cv_err : rv_err));
 		return VDL2GPU_EINVAL;
 	}
 	if (h->failed)
@@ -2894,6 +2924,7 @@ static int poll_impl(vdl2gpu_t *h, vdl2gpu_burst_t *out, vdl2gpu_level_t *lv, vd
 	side[COL_LEVEL] = lv;
 	side[COL_SOFT] = sv;
 	side[COL_CARRIER] = cv;
+	side[COL_REPORT] = rv;
 	return hand_out(h, out, max, side);
 }
 
@@ -2937,6 +2968,18 @@ extern "C" int vdl2gpu_poll_carrier_ready(vdl2gpu_t *h, vdl2gpu_burst_t *out, vd
 {
 	return poll_impl(h, out, lv, soft, max, false, "vdl2gpu_poll_carrier: lv needs VDL2GPU_F_LEVELS", "vdl2gpu_poll_carrier: soft needs VDL2GPU_F_SOFT_RS",
 			 car, "vdl2gpu_poll_carrier: car needs VDL2GPU_F_CARRIER");
+}
+
+extern "C" int vdl2gpu_poll_report(vdl2gpu_t *h, vdl2gpu_burst_t *out, vdl2gpu_level_t *lv, vdl2gpu_soft_t *soft, vdl2gpu_carrier_t *car, vdl2gpu_blockrep_t *rep, int max)
+{
+	return poll_impl(h, out, lv, soft, max, true, "vdl2gpu_poll_report: lv needs VDL2GPU_F_LEVELS", "vdl2gpu_poll_report: soft needs VDL2GPU_F_SOFT_RS",
+			 car, "vdl2gpu_poll_report: car needs VDL2GPU_F_CARRIER", rep, "vdl2gpu_poll_report: rep needs VDL2GPU_F_BLOCK_REPORT");
+}
+
+extern "C" int vdl2gpu_poll_report_ready(vdl2gpu_t *h, vdl2gpu_burst_t *out, vdl2gpu_level_t *lv, vdl2gpu_soft_t *soft, vdl2gpu_carrier_t *car, vdl2gpu_blockrep_t *rep, int max)
+{
+	return poll_impl(h, out, lv, soft, max, false, "vdl2gpu_poll_report: lv needs VDL2GPU_F_LEVELS", "vdl2gpu_poll_report: soft needs VDL2GPU_F_SOFT_RS",
+			 car, "vdl2gpu_poll_report: car needs VDL2GPU_F_CARRIER", rep, "vdl2gpu_poll_report: rep needs VDL2GPU_F_BLOCK_REPORT");
 }
 
 /* VDL2GPU_F_CARRIER: the derived values of a carrier record (include/vdl2gpu.h, vdl2gpu_carrier_t) -- the one statement of that

@@ -13,6 +13,8 @@
  * step is spread over the lanes: k4_fetch_head / k4_fetch_rows, k4_rs_rows (k4_rs_row: k4_syndromes, k4_rs_bm, k4_rs_chien,
  * k4_rs_forney; k4_soft_row), k4_unstuff, k4_flag_hunt, k4_fcs_scan, k4_sort_candidates, k4_emit (k4_alloc).  k4_rs_debug runs
  * k4_rs_row alone.
+ * The driver is a template over REP: k4_frames is the block path and nothing else; k4_frames_rep also keeps what the steps learn about
+ * the burst (K4Rep, in LDS) and writes it out as the record's vdl2gpu_blockrep_t (VDL2GPU_F_BLOCK_REPORT, include/vdl2gpu.h).
  */
 #ifndef VDL2GPU_BLOCKS_H
 #define VDL2GPU_BLOCKS_H
@@ -50,6 +52,8 @@ struct K4Params {
 	const unsigned *tabs;		/* K4_TABW words from k4_tables: gexp[512], glog[256], crc_tab[256] */
 	const vdl2gpu_soft_t *soft;	/* VDL2GPU_F_SOFT_RS: the records' reliability maps, same index: the row rule of vdl2gpu_soft_t for
 					 * rows the reference cannot decode.  nullptr: the reference's block path and nothing else */
+	vdl2gpu_blockrep_t *rep;	/* k4_frames_rep only (VDL2GPU_F_BLOCK_REPORT): the records' reports, same index.  k4_frames never
+					 * reads it (last: the other members keep their place) */
 };
 
 #define K4_TABW ((512 + 256 + 512) / 4)
@@ -78,7 +82,7 @@ struct K4Shared {
 	/* Berlekamp-Massey work arrays live here, not in (scratch-backed) private arrays */
 	uint8_t lam[8], syn[8], omg[8], root[8], loc[8];
 	int rs_deg, rs_count, rs_fail;
-	uint8_t save[256];	/* soft mode: the received row, for the trials */
+	uint8_t save[256];	/* soft mode and the report: the received row, for the trials and for row_changed */
 	int cand[4];		/* soft mode: the least reliable candidate positions, most doubtful first */
 };
 
@@ -378,11 +382,14 @@ __device__ __forceinline__ unsigned k4_syndromes(const K4Shared &sh, const uint8
 	return syn[0] | syn[1] | syn[2] | syn[3] | syn[4] | syn[5];
 }
 
-/* rs() of one row with sh.eras[0..nera) (rs.c:81-291): false when it returns -1 */
-__device__ __forceinline__ bool k4_rs_row(K4Shared &sh, uint8_t *row, int nera, const unsigned (&sexp)[4][2], int lane)
+/* rs() of one row with sh.eras[0..nera) (rs.c:81-291): false when it returns -1.  anyp: where the caller wants to know whether a
+ * syndrome of the row was non-zero (all zero: rs() returns 0 at once, and sh.rs_count is not written) */
+__device__ __forceinline__ bool k4_rs_row(K4Shared &sh, uint8_t *row, int nera, const unsigned (&sexp)[4][2], int lane, unsigned *anyp = nullptr)
 {
 	unsigned syn[6];
 	const unsigned any = k4_syndromes(sh, row, sexp, syn, lane);
+	if (anyp)
+		*anyp = any;
 	K4_SYNC();
 	bool ok = true;
 	if (any) {	/* wave-uniform: every lane holds the reduced syndromes */
@@ -401,8 +408,8 @@ __device__ __forceinline__ bool k4_rs_row(K4Shared &sh, uint8_t *row, int nera, 
 /* The soft row rule (vdl2gpu.h, vdl2gpu_soft_t) for a row the reference's rs() has just failed on: `row` holds what it left, sh.save
  * the received row.  The candidates' keys (rel << 8 | position) go through up to four wave-wide minimum searches; each trial starts
  * from the received row.  Without a success the reference's result is written back: it is what rs() leaves, computed again from the
- * same row and erasures. */
-__device__ void k4_soft_row(K4Shared &sh, uint8_t *row, const uint8_t *rel, int by, int e0, int pr, const unsigned (&sexp)[4][2], int lane)
+ * same row and erasures.  Returns the number of candidates of the trial that replaced the row (2 or 4), 0: none did. */
+__device__ int k4_soft_row(K4Shared &sh, uint8_t *row, const uint8_t *rel, int by, int e0, int pr, const unsigned (&sexp)[4][2], int lane)
 {
 	const int smax = e0 + 4 <= 4 ? 4 : 2;
 	unsigned key[4];
@@ -446,7 +453,7 @@ __device__ void k4_soft_row(K4Shared &sh, uint8_t *row, const uint8_t *rel, int 
 			const unsigned any = k4_syndromes(sh, row, sexp, syn, lane);
 			K4_SYNC();
 			if (!any)
-				return;
+				return s;
 		}
 	}
 	for (int i = lane; i < 255; i += K4_NT)
@@ -454,6 +461,7 @@ __device__ void k4_soft_row(K4Shared &sh, uint8_t *row, const uint8_t *rel, int 
 	k4_set_eras(sh, by, lane);
 	K4_SYNC();
 	k4_rs_row(sh, row, e0, sexp, lane);
+	return 0;
 }
 
 /* ---- the record (msgblk_t, vdlm2.c:84-98): its front -- header and two rows -- into registers, and from there into LDS; the
@@ -472,24 +480,58 @@ __device__ __forceinline__ void k4_fetch_rows(K4Shared &sh, const vdl2gpu_burst_
 }
 
 /* ---- RS per row (rows in order: eras_pos[] carries over, vdlm2.c:104-113), with the soft row rule behind a row that rs() fails on when
- * the record has a reliability map (soft: the record's, or nullptr).  The rows' data bytes go to sh.src; returns their number. */
-__device__ __forceinline__ int k4_rs_rows(K4Shared &sh, const vdl2gpu_soft_t *soft, int nbrow, int nlbyte, const unsigned (&sexp)[4][2], int lane)
+ * the record has a reliability map (soft: the record's, or nullptr).  The rows' data bytes go to sh.src; returns their number.
+ * REP: rep (in LDS, zeroed) gets the rows' part of the report -- row_roots and row_how from the reference's run on the received row
+ * (k4_rs_row's result, sh.rs_count as k4_rs_debug reads it) and from what k4_soft_row says; row_changed from a comparison of the final
+ * row with the received one in sh.save, four bytes a lane, masked to the transmitted positions and counted over the wave; the three sums
+ * are kept in registers (they are the same in every lane) and stored once. */
+template <bool REP>
+__device__ __forceinline__ int k4_rs_rows(K4Shared &sh, const vdl2gpu_soft_t *soft, int nbrow, int nlbyte, const unsigned (&sexp)[4][2], int lane,
+					  vdl2gpu_blockrep_t *rep)
 {
 	uint8_t *const rows = reinterpret_cast<uint8_t *>(sh.recw) + offsetof(vdl2gpu_burst_t, data);
 	if (lane < 6)
 		sh.eras[lane] = 0;
 	K4_SYNC();
 	int nby = 0;
+	unsigned changed = 0, failed = 0, rescued = 0;	/* (REP) */
 	for (int r = 0; r < nbrow; ++r) {
 		const int by = r == nbrow - 1 ? nlbyte : 249;
 		const int nera = k4_set_eras(sh, by, lane);	/* (a full row has none) */
 		uint8_t *const row = rows + r * VDL2GPU_ROWLEN;
-		if (soft) {
+		if (REP || soft) {
 			for (int i = lane; i < 255; i += K4_NT)
 				sh.save[i] = row[i];
 			K4_SYNC();
 		}
-		if (!k4_rs_row(sh, row, nera, sexp, lane) && soft) {
+		if constexpr (REP) {
+			const BurstGeom g = burst_geom(nbrow, nlbyte);
+			const int pr = r < g.nf_rows - 1 ? 6 : (r == g.nf_rows - 1 ? g.nf_last : 0);	/* the transmitted parity of row r */
+			unsigned any;
+			const bool ok = k4_rs_row(sh, row, nera, sexp, lane, &any);
+			const int roots = !ok ? -1 : (any ? sh.rs_count : 0);
+			unsigned how = !any ? VDL2GPU_ROW_CLEAN : (ok ? VDL2GPU_ROW_REF : VDL2GPU_ROW_FAIL);
+			if (!ok && soft && nera + 2 <= 4) {
+				const int s = k4_soft_row(sh, row, &soft->rel[r][0], by, nera, pr, sexp, lane);
+				how = s == 2 ? VDL2GPU_ROW_SOFT2 : (s == 4 ? VDL2GPU_ROW_SOFT4 : VDL2GPU_ROW_FAIL);
+			}
+			K4_SYNC();	/* the row is final */
+			unsigned nch = 0;
+#pragma unroll
+			for (int b = 0; b < 4; ++b) {
+				const int j = lane * 4 + b;
+				const bool sent = j < by || (j >= 249 && j < 249 + pr);
+				nch += (unsigned)__popcll(__ballot(sent && row[j < 255 ? j : 254] != sh.save[j < 255 ? j : 254]));
+			}
+			if (lane == 0) {
+				rep->row_roots[r] = (int8_t)roots;
+				rep->row_how[r] = (uint8_t)how;
+				rep->row_changed[r] = (uint8_t)nch;
+			}
+			changed += nch;
+			failed += how == VDL2GPU_ROW_FAIL;
+			rescued += how == VDL2GPU_ROW_SOFT2 || how == VDL2GPU_ROW_SOFT4;
+		} else if (!k4_rs_row(sh, row, nera, sexp, lane) && soft) {
 			const BurstGeom g = burst_geom(nbrow, nlbyte);
 			const int pr = r < g.nf_rows - 1 ? 6 : (r == g.nf_rows - 1 ? g.nf_last : 0);	/* the transmitted parity of row r */
 			if (nera + 2 <= 4)
@@ -498,6 +540,11 @@ __device__ __forceinline__ int k4_rs_rows(K4Shared &sh, const vdl2gpu_soft_t *so
 		for (int i = lane; i < by; i += K4_NT)
 			sh.src[nby + i] = rows[r * VDL2GPU_ROWLEN + i];
 		nby += by;
+	}
+	if (REP && lane == 0) {
+		rep->bytes_changed = (uint16_t)changed;
+		rep->rows_failed = (uint16_t)failed;
+		rep->rows_rescued = (uint16_t)rescued;
 	}
 	return nby;
 }
@@ -614,8 +661,12 @@ __device__ __forceinline__ int k4_flag_hunt(K4Shared &sh, int c0, int c1, int la
  * (check_frame, vdlm2.c:38-61).  All candidates start at m1, so one running FCS serves -- computed lane-parallel: the FCS is linear,
  * the state at the start of a lane's bytes is (state one lane earlier, advanced over `per` zero bytes) xor (FCS from zero of that
  * lane's bytes); that recurrence is scanned in log2(64) doubling steps, the advance map (16 columns, one per lane) being squared
- * alongside.  Leaves the closing flags of the frames that check in sh.ends, in any order, and their number in sh.nfr. */
-__device__ __forceinline__ void k4_fcs_scan(K4Shared &sh, int m1, int per, int c0, int c1, int lane)
+ * alongside.  Leaves the closing flags of the frames that check in sh.ends, in any order, and their number in sh.nfr.
+ * REP: every lane also counts the 0x7e bytes it meets (B[m1] is none) and those of them that close a candidate of l < 13; the two
+ * counts (at most K4_MAXBY < 65536 and at most 10: l < 13 ends at m1 + 10) are added up over the wave in one word and returned:
+ * cand | too_short << 16.  The candidates of l >= 13 with the wrong FCS are the rest: cand - too_short - sh.nfr.  Without REP: 0. */
+template <bool REP>
+__device__ __forceinline__ unsigned k4_fcs_scan(K4Shared &sh, int m1, int per, int c0, int c1, int lane)
 {
 	const uint8_t *B = reinterpret_cast<const uint8_t *>(sh.dst);
 	unsigned col = 0;	/* the advance map, one state bit per lane */
@@ -649,6 +700,7 @@ __device__ __forceinline__ void k4_fcs_scan(K4Shared &sh, int m1, int per, int c
 	if (lane == 0)
 		sh.nfr = 0;
 	K4_SYNC();
+	unsigned counts = 0;
 	if (lane >= L1) {
 		unsigned c = (lane == L1) ? 0xffffu : crc_in;
 		for (int q = (lane == L1) ? m1 : c0; q < c1; ++q) {
@@ -658,10 +710,18 @@ __device__ __forceinline__ void k4_fcs_scan(K4Shared &sh, int m1, int per, int c
 				if (k < K4_NCAND)
 					sh.ends[k] = q;
 			}
+			if (REP && v == 0x7eu)
+				counts += 1u + ((q - m1 + 2) < 13 ? 1u << 16 : 0u);
 			c = (c >> 8) ^ sh.crc_tab[(c ^ v) & 0xffu];
 		}
 	}
+	if (REP) {
+		static_assert(K4_MAXBY < 65536, "two counts to a word, 16 bits each");
+		for (int d = 32; d > 0; d >>= 1)
+			counts += __shfl_xor(counts, d, K4_NT);
+	}
 	K4_SYNC();
+	return counts;
 }
 
 /* ---- frames in stream order (there is almost never more than one); more CRC-clean frames in one burst than the table holds are
@@ -744,10 +804,26 @@ __device__ __forceinline__ void k4_emit(K4Shared &sh, const K4Params &p, vdl2gpu
 	K4_SYNC();
 }
 
-__global__ __launch_bounds__(K4_NT)
-void k4_frames(K4Params p)
+/* REP: the record's report goes together in LDS (K4Rep: zeroed, then every step adds what it knows) and leaves as twelve words from
+ * twelve lanes on every way out of the loop body but a void record's, which the host drops. */
+union K4Rep {
+	vdl2gpu_blockrep_t r;
+	unsigned w[sizeof(vdl2gpu_blockrep_t) / 4];
+};
+static_assert(sizeof(vdl2gpu_blockrep_t) == 48 && alignof(vdl2gpu_blockrep_t) == 4, "the report is written as twelve words");
+
+__device__ __forceinline__ void k4_rep_store(const K4Rep &rp, vdl2gpu_blockrep_t *g, int lane)
+{
+	K4_SYNC();
+	if (lane < (int)(sizeof(vdl2gpu_blockrep_t) / 4))
+		reinterpret_cast<unsigned *>(g)[lane] = rp.w[lane];
+}
+
+template <bool REP>
+__device__ __forceinline__ void k4_frames_body(const K4Params &p)
 {
 	__shared__ K4Shared sh;
+	__shared__ K4Rep rp;	/* (REP; never touched without it) */
 	const int lane = threadIdx.x;
 	/* Everything the first record needs from memory is asked for at once -- the tables, the record
 	 * count and the front of record blockIdx.x -- because this kernel runs beside the next push's
@@ -779,22 +855,63 @@ void k4_frames(K4Params p)
 			myslot->len = 0;
 		if (p.fmask && rec->trig_sample == 2)	/* (device-side tag) a burst of the first selection that a repair round made void: K2d's second pass says so */
 			continue;
-		if (nbrow < 1 || nbrow > VDL2GPU_MAXROWS || nlbyte < 0 || nlbyte > 249)
+		const bool badhead = nbrow < 1 || nbrow > VDL2GPU_MAXROWS || nlbyte < 0 || nlbyte > 249;
+		if constexpr (REP) {
+			if (lane < (int)(sizeof(vdl2gpu_blockrep_t) / 4))
+				rp.w[lane] = 0u;
+			K4_SYNC();
+			if (badhead) {
+				if (lane == 0)
+					rp.r.status = 1;
+				k4_rep_store(rp, p.rep + ib, lane);
+			}
+		}
+		if (badhead)
 			continue;
 		k4_fetch_rows(sh, p.recs + ib, nbrow, lane);
-		const int nby = k4_rs_rows(sh, p.soft ? p.soft + ib : nullptr, nbrow, nlbyte, sexp, lane);
-		const int nb = k4_unstuff(sh, nby, lane) >> 3;	/* whole un-stuffed bytes */
+		const int nby = k4_rs_rows<REP>(sh, p.soft ? p.soft + ib : nullptr, nbrow, nlbyte, sexp, lane, &rp.r);
+		const int nbits = k4_unstuff(sh, nby, lane);
+		const int nb = nbits >> 3;	/* whole un-stuffed bytes */
 		int c0, c1;	/* of them, the lane's */
 		const int per = k4_lane_span(nb, lane, &c0, &c1);
 		const int m1 = k4_flag_hunt(sh, c0, c1, lane);
+		if (REP && lane == 0) {
+			rp.r.stuffed = (uint16_t)(8 * nby - nbits);
+			rp.r.nbytes = (uint16_t)nb;
+			rp.r.flag_at = (int16_t)(sh.flag0 == K4_NONE ? -1 : sh.flag0);
+		}
 		if (m1 == K4_NONE) {
+			if constexpr (REP)
+				k4_rep_store(rp, p.rep + ib, lane);
 			K4_SYNC();
 			continue;
 		}
-		k4_fcs_scan(sh, m1, per, c0, c1, lane);
+		const unsigned counts = k4_fcs_scan<REP>(sh, m1, per, c0, c1, lane);
+		if (REP && lane == 0) {
+			const unsigned cand = counts & 0xffffu, too_short = counts >> 16, frames = (unsigned)sh.nfr;	/* (nfr: before k4_sort_candidates caps it) */
+			rp.r.cand = (uint16_t)cand;
+			rp.r.too_short = (uint16_t)too_short;
+			rp.r.bad_fcs = (uint16_t)(cand - too_short - frames);	/* every 0x7e behind hdata[1] is one of the three */
+			rp.r.frames = (uint16_t)frames;
+		}
 		k4_sort_candidates(sh, p.nframes + 1, lane);
 		k4_emit(sh, p, myslot, ib, m1, lane);
+		if constexpr (REP)
+			k4_rep_store(rp, p.rep + ib, lane);
 	}
+}
+
+__global__ __launch_bounds__(K4_NT)
+void k4_frames(K4Params p)
+{
+	k4_frames_body<false>(p);
+}
+
+/* VDL2GPU_F_BLOCK_REPORT and vdl2gpu_decode_blocks_report: the same block path, and p.rep[i] for every record i that is not void */
+__global__ __launch_bounds__(K4_NT)
+void k4_frames_rep(K4Params p)
+{
+	k4_frames_body<true>(p);
 }
 
 /* vdl2gpu_debug_rs: k4_rs_row as k4_frames calls it, one wavefront per row, so that a test can hold what it leaves in a row --

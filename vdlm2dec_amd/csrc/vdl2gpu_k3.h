@@ -102,6 +102,8 @@ struct KExportParams {
 	vdl2gpu_soft_t *sdst;	/* ... and the slab's */
 	const vdl2gpu_carrier_t *car;	/* VDL2GPU_F_CARRIER: the ring's carrier records, else nullptr ... */
 	vdl2gpu_carrier_t *cdst;	/* ... and the slab's */
+	const vdl2gpu_blockrep_t *rep;	/* VDL2GPU_F_BLOCK_REPORT: the ring's block reports (k4_frames_rep has run), else nullptr ... */
+	vdl2gpu_blockrep_t *rdst;	/* ... and the slab's */
 };
 /* Only what a record uses travels: the header and the rows of the burst (a record is eight rows of 255 bytes; a typical
  * burst fills one or two) -- a sixth of the PCIe traffic and of what the collecting thread reads; the host zero-fills the
@@ -112,6 +114,7 @@ void k_export_records(KExportParams p)
 	static_assert(sizeof(vdl2gpu_burst_t) % 8 == 0 && offsetof(vdl2gpu_burst_t, data) % 8 == 0, "records are copied as 8-byte words");
 	static_assert(sizeof(vdl2gpu_level_t) % 8 == 0 && sizeof(vdl2gpu_level_t) / 8 <= 64, "level records too");
 	static_assert(sizeof(vdl2gpu_carrier_t) == 32, "carrier records: four words");
+	static_assert(sizeof(vdl2gpu_blockrep_t) == 48, "block reports: six words");
 	unsigned n = *p.count;
 	n = n < p.cap ? n : p.cap;
 	const unsigned lane = threadIdx.x & 63u;
@@ -127,6 +130,8 @@ void k_export_records(KExportParams p)
 			reinterpret_cast<unsigned long long *>(p.ldst + r)[lane] = reinterpret_cast<const unsigned long long *>(p.lev + r)[lane];
 		if (p.car && lane < sizeof(vdl2gpu_carrier_t) / 8)	/* (uniform) the carrier record beside it */
 			reinterpret_cast<unsigned long long *>(p.cdst + r)[lane] = reinterpret_cast<const unsigned long long *>(p.car + r)[lane];
+		if (p.rep && lane < sizeof(vdl2gpu_blockrep_t) / 8)	/* (uniform) the block report beside it */
+			reinterpret_cast<unsigned long long *>(p.rdst + r)[lane] = reinterpret_cast<const unsigned long long *>(p.rep + r)[lane];
 		if (p.soft)	/* (uniform) the map beside it: the rows of the burst, 255 elsewhere */
 			for (unsigned i = lane; i < sizeof(vdl2gpu_soft_t) / 8; i += 64u)
 				reinterpret_cast<unsigned long long *>(p.sdst + r)[i] = reinterpret_cast<const unsigned long long *>(p.soft + r)[i];

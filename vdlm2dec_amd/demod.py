@@ -62,6 +62,31 @@ class Carrier:
         return cls(v.nsym, v.sum_e, v.sum_e2, v.dphi, v.freq_hz, v.ppm, v.rms_rad)
 
 
+@dataclass(frozen=True)
+class BlockReport:
+    """vdl2gpu_blockrep_t: what the block path made of a burst (Receiver(frames=True, block_report=True), decode_blocks(report=True);
+    definitions in include/vdl2gpu.h)."""
+    row_roots: Tuple[int, ...]     # per row: rs()'s return value for the received row (-1: it failed)
+    row_how: Tuple[int, ...]       # per row: lib.ROW_NONE / CLEAN / REF / SOFT2 / SOFT4 / FAIL
+    row_changed: Tuple[int, ...]   # per row: transmitted bytes the decode changed
+    bytes_changed: int
+    rows_failed: int
+    rows_rescued: int
+    stuffed: int                   # zeros the un-stuffer dropped
+    nbytes: int                    # whole un-stuffed bytes
+    flag_at: int                   # un-stuffed byte that completes the first flag, -1: never
+    cand: int                      # calls of check_frame(): cand == too_short + bad_fcs + frames
+    too_short: int                 # "error too short"
+    bad_fcs: int                   # "error crc"
+    frames: int
+    status: int                    # 1: header out of range, nothing ran
+
+    @classmethod
+    def from_c(cls, v) -> "BlockReport":
+        return cls(tuple(v.row_roots), tuple(v.row_how), tuple(v.row_changed), v.bytes_changed, v.rows_failed, v.rows_rescued,
+                   v.stuffed, v.nbytes, v.flag_at, v.cand, v.too_short, v.bad_fcs, v.frames, v.status)
+
+
 def carrier_from_sums(df: float, Fr: int, nsym: int, sum_e: int, sum_e2: int) -> Carrier:
     """vdl2gpu_carrier_from_sums: the derived values of a carrier record, as the library computes them (no GPU needed)."""
     c = _lib.CarrierT()
@@ -89,6 +114,7 @@ class Burst:
     level: Optional[Level] = None   # Receiver(levels=True) only; not part of key()
     soft: Optional[np.ndarray] = None   # Receiver(soft_rs=True) only: uint8 (8, 255) byte reliabilities; not part of key()
     carrier: Optional[Carrier] = None   # Receiver(carrier=True) only; not part of key()
+    report: Optional[BlockReport] = None   # Receiver(frames=True, block_report=True) only; not part of key()
 
     def key(self):
         return (self.stream, self.chn, self.nbrow, self.nlbyte, self.data)
@@ -104,7 +130,9 @@ class Receiver:
                  fmt: str = "cu8", max_push: int = 1 << 22, device: int = 0, sdrclk: int = 0,
                  max_bursts: int = 0, keep_dec: bool = False, serial: bool = False, full_scan: bool = False,
                  frames: bool = False, rtl_quirk: bool = False, flags: int = 0, testhooks: bool = False,
-                 levels: bool = False, soft_rs: bool = False, exact_fo: bool = False, carrier: bool = False):
+                 levels: bool = False, soft_rs: bool = False, exact_fo: bool = False, carrier: bool = False,
+                 block_report: bool = False):
+        # block_report: VDL2GPU_F_BLOCK_REPORT (needs frames=True), what the block path made of every burst (Burst.report)
         # carrier: VDL2GPU_F_CARRIER, every burst's carrier offset and phase-error spread (Burst.carrier)
         # exact_fo: VDL2GPU_F_EXACT_FO, channel offsets off the 25 kHz grid with a phase-continuous oscillator (include/vdl2gpu.h)
         # testhooks: load libvdl2gpu_test.so, the build that honours F_TEST_NOREGION / VDL2GPU_PRIM_DROP / VDL2GPU_SPLIT_SAMPLES
@@ -133,11 +161,12 @@ class Receiver:
         cfg.max_push = max_push
         cfg.device = device
         cfg.max_bursts = max_bursts
-        cfg.flags = (_lib.F_KEEP_DEC if keep_dec else 0) | (_lib.F_SERIAL if serial else 0) | (_lib.F_FULLSCAN if full_scan else 0) | (_lib.F_FRAMES if frames else 0) | (_lib.F_RTL_QUIRK if rtl_quirk else 0) | (_lib.F_LEVELS if levels else 0) | (_lib.F_SOFT_RS if soft_rs else 0) | (_lib.F_EXACT_FO if exact_fo else 0) | (_lib.F_CARRIER if carrier else 0) | flags
+        cfg.flags = (_lib.F_KEEP_DEC if keep_dec else 0) | (_lib.F_SERIAL if serial else 0) | (_lib.F_FULLSCAN if full_scan else 0) | (_lib.F_FRAMES if frames else 0) | (_lib.F_RTL_QUIRK if rtl_quirk else 0) | (_lib.F_LEVELS if levels else 0) | (_lib.F_SOFT_RS if soft_rs else 0) | (_lib.F_EXACT_FO if exact_fo else 0) | (_lib.F_CARRIER if carrier else 0) | (_lib.F_BLOCK_REPORT if block_report else 0) | flags
         self.max_push = max_push
         self.levels = bool(cfg.flags & _lib.F_LEVELS)
         self.soft_rs = bool(cfg.flags & _lib.F_SOFT_RS)
         self.carrier = bool(cfg.flags & _lib.F_CARRIER)
+        self.block_report = bool(cfg.flags & _lib.F_BLOCK_REPORT)
         self.h = C.c_void_p()
         rc = self.L.vdl2gpu_create(C.byref(cfg), C.byref(self.h))
         if rc != 0:
@@ -194,8 +223,12 @@ class Receiver:
         lv = (_lib.LevelT * max_bursts)() if self.levels else None
         sv = (_lib.SoftT * max_bursts)() if self.soft_rs else None
         cv = (_lib.CarrierT * max_bursts)() if self.carrier else None
+        rv = (_lib.BlockRepT * max_bursts)() if self.block_report else None
         while True:
-            if cv is not None:
+            if rv is not None:
+                fn = self.L.vdl2gpu_poll_report_ready if ready else self.L.vdl2gpu_poll_report
+                n = self._check(fn(self.h, buf, lv, sv, cv, rv, max_bursts))
+            elif cv is not None:
                 fn = self.L.vdl2gpu_poll_carrier_ready if ready else self.L.vdl2gpu_poll_carrier
                 n = self._check(fn(self.h, buf, lv, sv, cv, max_bursts))
             elif sv is not None:
@@ -212,7 +245,8 @@ class Receiver:
                 out.append(Burst(b.stream, b.chn, b.Fr, b.nbrow, b.nlbyte, b.df, b.ppm, b.trig_dec, b.end_dec,
                                  b.trig_sample, b.end_sample, bytes(b.data), Level.from_c(lv[i]) if lv is not None else None,
                                  np.frombuffer(bytes(sv[i].rel), np.uint8).reshape(8, 255).copy() if sv is not None else None,
-                                 Carrier.from_c(cv[i]) if cv is not None else None))
+                                 Carrier.from_c(cv[i]) if cv is not None else None,
+                                 BlockReport.from_c(rv[i]) if rv is not None else None))
             if n < max_bursts:
                 return out
 
@@ -240,6 +274,12 @@ class Receiver:
         fn = self.L.vdl2gpu_poll_carrier_ready if ready else self.L.vdl2gpu_poll_carrier
         return self._check(fn(self.h, buf, lv, sv, cv, max_bursts))
 
+    def poll_report_raw(self, buf, lv, sv, cv, rv, max_bursts: int, ready: bool = False) -> int:
+        """vdl2gpu_poll_report(_ready) into caller-owned (lib.BurstT / LevelT / SoftT / CarrierT / BlockRepT * n) arrays; lv, sv, cv and rv
+        may each be None."""
+        fn = self.L.vdl2gpu_poll_report_ready if ready else self.L.vdl2gpu_poll_report
+        return self._check(fn(self.h, buf, lv, sv, cv, rv, max_bursts))
+
     def poll_ready_raw(self, buf, max_bursts: int) -> int:
         """vdl2gpu_poll_ready: bursts of pushes that have already finished; never waits."""
         return self._check(self.L.vdl2gpu_poll_ready(self.h, buf, max_bursts))
@@ -264,14 +304,15 @@ class Receiver:
         return out
 
     # ------------------------------------------------------------------ block path
-    def decode_blocks(self, blocks: Sequence, max_frames: int = 0, soft=None) -> List[Tuple[int, bytes]]:
+    def decode_blocks(self, blocks: Sequence, max_frames: int = 0, soft=None, report: bool = False):
         """blk_thread for a batch (vdlm2.c:84-161): (index of the block, hdata) of every frame the
         reference would pass to out().  ``blocks``: Burst objects or (nbrow, nlbyte, data) tuples.
         ``soft``: one (8, 255) uint8 reliability map per block (Burst.soft): the soft row rule of include/vdl2gpu.h
-        (vdl2gpu_decode_blocks_soft); None: the reference's block path."""
+        (vdl2gpu_decode_blocks_soft); None: the reference's block path.
+        ``report``: return (frames, [BlockReport of every block]) (vdl2gpu_decode_blocks_report), on any handle."""
         n = len(blocks)
         if n == 0:
-            return []
+            return ([], []) if report else []
         arr = (_lib.BurstT * n)()
         for i, b in enumerate(blocks):
             nbrow, nlbyte, data = (b.nbrow, b.nlbyte, b.data) if hasattr(b, "nbrow") else b
@@ -282,19 +323,21 @@ class Receiver:
         cap = max_frames or 4 * n
         out = (_lib.FrameT * cap)()
         dropped = C.c_int(0)
-        if soft is None:
-            nf = self._check(self.L.vdl2gpu_decode_blocks(self.h, arr, n, out, cap, C.byref(dropped)))
-        else:
+        sarr = None
+        if soft is not None:
             if len(soft) != n:
                 raise ValueError("one reliability map per block")
             sarr = (_lib.SoftT * n)()
             for i, m in enumerate(soft):
                 m = np.ascontiguousarray(m, np.uint8).reshape(8, 255)
                 C.memmove(C.addressof(sarr[i].rel), m.ctypes.data, 8 * 255)
-            nf = self._check(self.L.vdl2gpu_decode_blocks_soft(self.h, arr, sarr, n, out, cap, C.byref(dropped)))
+        rarr = (_lib.BlockRepT * n)() if report else None
+        # (soft NULL: hard mode; rep NULL: exactly vdl2gpu_decode_blocks_soft, and with both exactly vdl2gpu_decode_blocks)
+        nf = self._check(self.L.vdl2gpu_decode_blocks_report(self.h, arr, sarr, n, out, cap, C.byref(dropped), rarr))
         if dropped.value:
             raise _lib.Vdl2GpuError(f"{dropped.value} frames dropped: raise max_frames")
-        return [(out[i].block, bytes(out[i].data[:out[i].len])) for i in range(nf)]
+        frames = [(out[i].block, bytes(out[i].data[:out[i].len])) for i in range(nf)]
+        return (frames, [BlockReport.from_c(r) for r in rarr]) if report else frames
 
     def poll_frames(self, max_frames: int = 4096) -> List[Tuple[int, int, bytes]]:
         """(stream, chn, hdata) of every frame of everything pushed so far (needs frames=True)."""
