@@ -355,13 +355,14 @@ typedef struct {
 #define VDL2GPU_ROW_SOFT2 3
 #define VDL2GPU_ROW_SOFT4 4
 #define VDL2GPU_ROW_FAIL 5
+#define VDL2GPU_ROW_FEEDBACK 6	/* rs() returned -1 and the record's decision-feedback row replaced the row (vdl2gpu_fb_t, below); counted in rows_rescued */
 typedef struct {
 	int8_t row_roots[8];	/* @0  rs()'s return value for the received row; rows >= nbrow: 0 */
 	uint8_t row_how[8];	/* @8  VDL2GPU_ROW_* */
 	uint8_t row_changed[8];	/* @16 transmitted positions at which the decoded row differs from the received one */
 	uint16_t bytes_changed;	/* @24 sum of row_changed[] */
 	uint16_t rows_failed;	/* @26 rows with row_how == VDL2GPU_ROW_FAIL */
-	uint16_t rows_rescued;	/* @28 rows with row_how == VDL2GPU_ROW_SOFT2 or _SOFT4 */
+	uint16_t rows_rescued;	/* @28 rows with row_how == VDL2GPU_ROW_SOFT2, _SOFT4 or _FEEDBACK */
 	uint16_t stuffed;	/* @30 zeros the un-stuffer dropped */
 	uint16_t nbytes;	/* @32 whole un-stuffed bytes */
 	int16_t flag_at;	/* @34 index of the un-stuffed byte that completes the first flag, -1: never */
@@ -371,6 +372,44 @@ typedef struct {
 	uint16_t frames;	/* @42 ... that passed */
 	int32_t status;		/* @44 0: the block path ran; 1: header out of range, all other fields 0 */
 } vdl2gpu_blockrep_t;		/* sizeof 48, alignment 4 */
+
+/* ---- decision-feedback rows (VDL2GPU_F_FEEDBACK; announced by VDL2GPU_HAVE_FEEDBACK, the ABI version is unchanged) ----
+ * The reference slices every payload symbol from P_k - P_{k-1} - df (d8psk.c:213, 323-327): both phases carry their full noise.  How far
+ * a slice fell from the centre of its sector says how far P_{k-1} was off, and the next slice can be told.  With VDL2GPU_F_FEEDBACK the
+ * demodulator slices every payload a second time with the last three of these residuals fed back, and keeps the bytes of that second
+ * slice beside the record: the record's own data[], df and every other field and column stay the reference's.
+ * For an accepted burst take idx_k (0..256) for the symbols k = 8 .. kmax exactly as defined at vdl2gpu_carrier_t, n = kmax - 7:
+ *   e_k  = (idx_k & 31) - 16,  S = sum e_k
+ *   mbar = floor((2 S + n) / (2 n)), floor towards minus infinity: the burst's mean residual, the carrier offset df left behind
+ *   r_k  = 0 for k < 8
+ *   for k = 8 .. kmax in ascending order
+ *          c   = 3 r_{k-1} + 2 r_{k-2} + r_{k-3}
+ *          o_k = (idx_k - mbar + floor((c + 2) / 4)) mod 256, in 0..255 (floor towards minus infinity, mod non-negative)
+ *          r_k = ((idx_k - 16 - 32 (o_k >> 5) - mbar + 128) mod 256) - 128, in -128..127
+ *   payload bit q = 25 + 8 b + i of byte b (symbol k = q / 3, table w = q % 3) is Grey_w[o_k], descrambled and compared with 0.5 exactly as
+ *   the reference path does with Grey_w[idx_k]; the bytes are assembled and scattered to (row, col) exactly as data[].  Positions that
+ *   carry no transmitted byte are 0.
+ * Everything is an integer: a burst gets the same vdl2gpu_fb_t whatever kernel, path or repair round decoded it and however the stream
+ * was cut into pushes.  (Only idx_k mod 256 enters: idx 256, the slice at +pi, is idx 0 one turn on.)
+ * Row rule of the block path when a record has feedback rows (vdl2gpu_decode_blocks_feedback; the pipeline's block path with
+ * VDL2GPU_F_FRAMES | VDL2GPU_F_FEEDBACK).  Row r, its fixed erasures and p_r as at vdl2gpu_soft_t:
+ *   1. the reference's rs() on the received row runs as always; a row it decodes (count >= 0) is kept as it decoded it -- no frame
+ *      the reference gives is ever lost;
+ *   2. otherwise rs() of fb.data[r] with the same fixed erasures; if it returns >= 0 and leaves all six syndromes zero, that row
+ *      replaces the received one (VDL2GPU_ROW_FEEDBACK);
+ *   3. otherwise, in soft mode, the trials of vdl2gpu_soft_t on the received row, unchanged;
+ *   4. otherwise the row is what the reference left.
+ * HDLC, the flag hunt and the FCS follow unchanged: the FCS still decides what is a frame.  In the block report row_roots stays the
+ * reference's run on the received row, row_changed counts against the received row, rows_rescued also counts VDL2GPU_ROW_FEEDBACK.
+ * The flag does not need VDL2GPU_F_FRAMES: a host-side consumer can poll the rows and use them later.
+ * Memory: 2048 bytes per record slot in each of the device output rings and each host slab, and in the host queue beside every
+ * burst record it holds. */
+#define VDL2GPU_F_FEEDBACK 4096u
+#define VDL2GPU_HAVE_FEEDBACK 1
+typedef struct {
+	uint8_t data[VDL2GPU_MAXROWS][VDL2GPU_ROWLEN];	/* @0    the rows of the second slice, laid out as the record's data[] */
+	uint8_t reserved[8];				/* @2040 0 */
+} vdl2gpu_fb_t;		/* sizeof 2048 */
 
 typedef struct {
 	uint64_t samples_in;	/* per stream */
@@ -491,6 +530,13 @@ int vdl2gpu_poll_carrier_ready(vdl2gpu_t *h, vdl2gpu_burst_t *out, vdl2gpu_level
  * handle created without VDL2GPU_F_BLOCK_REPORT: VDL2GPU_EINVAL, and nothing is consumed; lv, soft and car as above. */
 int vdl2gpu_poll_report(vdl2gpu_t *h, vdl2gpu_burst_t *out, vdl2gpu_level_t *lv, vdl2gpu_soft_t *soft, vdl2gpu_carrier_t *car, vdl2gpu_blockrep_t *rep, int max);
 int vdl2gpu_poll_report_ready(vdl2gpu_t *h, vdl2gpu_burst_t *out, vdl2gpu_level_t *lv, vdl2gpu_soft_t *soft, vdl2gpu_carrier_t *car, vdl2gpu_blockrep_t *rep, int max);
+/* ... and with the bursts' decision-feedback rows: fb[i] belongs to out[i] (VDL2GPU_F_FEEDBACK).  Same queue, order, waiting and threading
+ * as the other collectors; each of lv, soft, car, rep and fb may be NULL (fb == NULL: exactly vdl2gpu_poll_report).  fb != NULL on a
+ * handle created without VDL2GPU_F_FEEDBACK: VDL2GPU_EINVAL, and nothing is consumed; lv, soft, car and rep as above. */
+int vdl2gpu_poll_feedback(vdl2gpu_t *h, vdl2gpu_burst_t *out, vdl2gpu_level_t *lv, vdl2gpu_soft_t *soft, vdl2gpu_carrier_t *car, vdl2gpu_blockrep_t *rep,
+			  vdl2gpu_fb_t *fb, int max);
+int vdl2gpu_poll_feedback_ready(vdl2gpu_t *h, vdl2gpu_burst_t *out, vdl2gpu_level_t *lv, vdl2gpu_soft_t *soft, vdl2gpu_carrier_t *car, vdl2gpu_blockrep_t *rep,
+				vdl2gpu_fb_t *fb, int max);
 /* Number of bursts a poll would currently return (implies vdl2gpu_sync). */
 int vdl2gpu_pending(vdl2gpu_t *h);
 /* Pushes the GPU has not finished yet (0..3); never waits.  For a producer that is not bound to real time and wants to
@@ -558,6 +604,10 @@ int vdl2gpu_decode_blocks_soft(vdl2gpu_t *h, const vdl2gpu_burst_t *blocks, cons
  * with max_frames == 0).  Works on any handle; soft may be NULL (hard mode); rep == NULL: exactly vdl2gpu_decode_blocks_soft. */
 int vdl2gpu_decode_blocks_report(vdl2gpu_t *h, const vdl2gpu_burst_t *blocks, const vdl2gpu_soft_t *soft, int n,
 				 vdl2gpu_frame_t *frames, int max_frames, int *dropped, vdl2gpu_blockrep_t *rep);
+/* ... and with decision-feedback rows: fb[i] belongs to blocks[i] (vdl2gpu_poll_feedback), and rows the reference cannot decode go through
+ * the row rule of vdl2gpu_fb_t.  Works on any handle; soft and rep may each be NULL; fb == NULL: exactly vdl2gpu_decode_blocks_report. */
+int vdl2gpu_decode_blocks_feedback(vdl2gpu_t *h, const vdl2gpu_burst_t *blocks, const vdl2gpu_soft_t *soft, const vdl2gpu_fb_t *fb, int n,
+				   vdl2gpu_frame_t *frames, int max_frames, int *dropped, vdl2gpu_blockrep_t *rep);
 /* With VDL2GPU_F_FRAMES the same kernel runs on every push's burst records where they lie in device
  * memory, right behind the demodulator.  Collect the frames of everything pushed so far (waits like
  * vdl2gpu_poll; the bursts themselves stay available through vdl2gpu_poll).  Frames come out ordered

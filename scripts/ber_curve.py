@@ -4,6 +4,7 @@
     python scripts/ber_curve.py [--esn0 14 16 18 20 22 24 27 30 35] [--bursts 160] [--out profiles/r02_ber_curve.json]
     python scripts/ber_curve.py --oracle-only ...        (no GPU: the curve of the CPU restatement alone)
     python scripts/ber_curve.py --soft ...               (and soft-decision RS erasures, VDL2GPU_F_SOFT_RS)
+    python scripts/ber_curve.py --feedback ...           (and decision-feedback rows, VDL2GPU_F_FEEDBACK)
 
 Every point: `--bursts` bursts (random AVLC info 1..120 bytes, +-400 Hz carrier offset, random fractional start) on 4
 channels of a 2 MS/s cs16 stream at fixed amplitude, AWGN set for the requested Es/N0 = A^2 * SDRINRATE / (2 sigma^2 *
@@ -12,7 +13,10 @@ and equal the sent frame, mean byte errors per 100 sliced bytes before RS -- and
 GPU's records are the oracle's records, byte for byte, at every noise level (decisions near their thresholds included).
 With --soft every point also counts, over distinct (channel, frame) pairs: the frames of the GPU pipeline in soft mode
 (frames=True, soft_rs=True), the CPU model's soft frames (tests/soft_ref.py), the hard frames (the reference's block path on
-the same records), and the frames that pass the FCS but were never sent (model and GPU)."""
+the same records), and the frames that pass the FCS but were never sent (model and GPU).
+With --feedback every point counts the same way: the hard frames, the CPU model's frames with the feedback rows in the row rule
+(tests/feedback_ref.py) and the rows it took from them, the frames of the GPU pipeline (frames=True, feedback=True), the frames never
+sent, and whether the GPU's set of frames is the model's."""
 import argparse
 import json
 import os
@@ -103,12 +107,31 @@ def soft_point(spec, raw, gpu):
     return out
 
 
+def feedback_point(spec, raw, gpu):
+    """--feedback: hard / model feedback / GPU feedback frames, rows taken from the feedback rows, frames that were never sent"""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import feedback_ref as F
+    sent, hard, model, taken, _ = F.scenario_frames(spec, raw, FO, FC, RATE)
+    ok = lambda s: len(s & sent)          # noqa: E731
+    out = dict(hard_frames=ok(hard), model_fb_frames=ok(model), model_rows_taken=taken, model_never_sent=len(model - sent),
+               hard_never_sent=len(hard - sent), model_keeps_hard=model >= hard)
+    if gpu:
+        from vdlm2dec_amd.demod import Receiver, plan_channels
+        with Receiver(RATE, plan_channels(FC, FO), fmt="cs16", max_push=spec.nsamples, frames=True, feedback=True) as rx:
+            rx.push(raw)
+            rx.poll()
+            g = {(c, f) for _, c, f in rx.poll_frames()}
+        out.update(gpu_fb_frames=ok(g), gpu_never_sent=len(g - sent), gpu_equals_model=g == model)
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--esn0", type=float, nargs="+", default=[14, 16, 18, 20, 22, 24, 27, 30, 35])
     ap.add_argument("--bursts", type=int, default=160)
     ap.add_argument("--oracle-only", action="store_true")
     ap.add_argument("--soft", action="store_true", help="add soft-decision RS erasures (VDL2GPU_F_SOFT_RS) to every point")
+    ap.add_argument("--feedback", action="store_true", help="add decision-feedback rows (VDL2GPU_F_FEEDBACK) to every point")
     ap.add_argument("--out", default="")
     a = ap.parse_args()
     pts = []
@@ -130,6 +153,8 @@ def main():
                 sorted((b.chn, b.trig_dec, int(np.float32(b.df).view(np.uint32))) for b in ob)
         if a.soft:
             pt["soft"] = soft_point(spec, raw, not a.oracle_only)
+        if a.feedback:
+            pt["feedback"] = feedback_point(spec, raw, not a.oracle_only)
         pts.append(pt)
         s = pt.get("gpu", pt["oracle"])
         print(f"Es/N0 {e:5.1f} dB  sigma {sigma:6.2f}  sent {s['sent']:4d}  headers {s['headers_ok']:4d}  frames {s['frames_ok']:4d}  "
@@ -140,6 +165,12 @@ def main():
             print(f"        soft: hard frames {q['hard_frames']:4d}  model soft frames {q['model_soft_frames']:4d}  never sent (model) "
                   f"{q['model_never_sent']}" + ("" if a.oracle_only else f"  GPU soft frames {q['gpu_soft_frames']:4d}  never sent (GPU) "
                                                                       f"{q['gpu_never_sent']}  GPU==model {q['gpu_equals_model']}"))
+        if a.feedback:
+            q = pt["feedback"]
+            print(f"    feedback: hard frames {q['hard_frames']:4d}  model feedback frames {q['model_fb_frames']:4d}  rows taken "
+                  f"{q['model_rows_taken']:3d}  never sent (model) {q['model_never_sent']}"
+                  + ("" if a.oracle_only else f"  GPU feedback frames {q['gpu_fb_frames']:4d}  never sent (GPU) {q['gpu_never_sent']}  "
+                                              f"GPU==model {q['gpu_equals_model']}"), flush=True)
     res = dict(rate=RATE, fo=list(FO), amp=AMP, bursts_per_point=a.bursts, points=pts)
     if a.out:
         json.dump(res, open(a.out, "w"), indent=1)
@@ -147,6 +178,8 @@ def main():
         sys.exit("GPU and oracle differ")
     if a.soft and not a.oracle_only and not all(p["soft"]["gpu_equals_model"] for p in pts):
         sys.exit("GPU soft frames and the CPU model differ")
+    if a.feedback and not a.oracle_only and not all(p["feedback"]["gpu_equals_model"] for p in pts):
+        sys.exit("GPU feedback frames and the CPU model differ")
 
 
 if __name__ == "__main__":

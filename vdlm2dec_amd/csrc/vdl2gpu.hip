@@ -94,8 +94,8 @@ struct LaterEvent {
 
 /* A burst record has side columns: entries at the record's index in the device rings, the slabs and the host queue, present when
  * the handle's flags ask for them.  A column is one row here and its flag in create_impl. */
-enum { COL_SOFT, COL_LEVEL, COL_CARRIER, COL_REPORT, VDL2_NCOL };	/* VDL2GPU_F_SOFT_RS: a reliability map (2048 bytes); VDL2GPU_F_LEVELS: a level record; VDL2GPU_F_CARRIER: a carrier record; VDL2GPU_F_BLOCK_REPORT: a block report */
-static const size_t col_bytes[VDL2_NCOL] = { sizeof(vdl2gpu_soft_t), sizeof(vdl2gpu_level_t), sizeof(vdl2gpu_carrier_t), sizeof(vdl2gpu_blockrep_t) };
+enum { COL_SOFT, COL_LEVEL, COL_CARRIER, COL_REPORT, COL_FB, VDL2_NCOL };	/* VDL2GPU_F_SOFT_RS: a reliability map (2048 bytes); VDL2GPU_F_LEVELS: a level record; VDL2GPU_F_CARRIER: a carrier record; VDL2GPU_F_BLOCK_REPORT: a block report; VDL2GPU_F_FEEDBACK: decision-feedback rows (2048 bytes) */
+static const size_t col_bytes[VDL2_NCOL] = { sizeof(vdl2gpu_soft_t), sizeof(vdl2gpu_level_t), sizeof(vdl2gpu_carrier_t), sizeof(vdl2gpu_blockrep_t), sizeof(vdl2gpu_fb_t) };
 
 /* A table set (push % VDL2_NSET): what a push's demodulator kernels work in, see alloc_sets. */
 struct TableSet {
@@ -127,6 +127,7 @@ struct OutRing {
 	vdl2gpu_soft_t *soft() const { return static_cast<vdl2gpu_soft_t *>(d_side[COL_SOFT]); }
 	vdl2gpu_carrier_t *carrier() const { return static_cast<vdl2gpu_carrier_t *>(d_side[COL_CARRIER]); }
 	vdl2gpu_blockrep_t *report() const { return static_cast<vdl2gpu_blockrep_t *>(d_side[COL_REPORT]); }
+	vdl2gpu_fb_t *fb() const { return static_cast<vdl2gpu_fb_t *>(d_side[COL_FB]); }
 };
 
 /* A slab (push % VDL2_NSLAB) of page-locked host memory, which the GPU itself fills at the end of the push (k_export_records), and
@@ -141,6 +142,7 @@ struct Slab {
 	vdl2gpu_soft_t *d_soft() const { return static_cast<vdl2gpu_soft_t *>(d_side[COL_SOFT]); }
 	vdl2gpu_carrier_t *d_carrier() const { return static_cast<vdl2gpu_carrier_t *>(d_side[COL_CARRIER]); }
 	vdl2gpu_blockrep_t *d_report() const { return static_cast<vdl2gpu_blockrep_t *>(d_side[COL_REPORT]); }
+	vdl2gpu_fb_t *d_fb() const { return static_cast<vdl2gpu_fb_t *>(d_side[COL_FB]); }
 };
 
 /* Records in pageable storage, with their side columns (byte vectors: col_bytes[k] a record). */
@@ -1008,6 +1010,7 @@ static int create_impl(vdl2gpu_t *h)
 	h->col_on[COL_SOFT] = (cfg.flags & VDL2GPU_F_SOFT_RS) != 0;
 	h->col_on[COL_CARRIER] = (cfg.flags & VDL2GPU_F_CARRIER) != 0;
 	h->col_on[COL_REPORT] = (cfg.flags & VDL2GPU_F_BLOCK_REPORT) != 0;	/* (vdl2gpu_create: only with VDL2GPU_F_FRAMES) */
+	h->col_on[COL_FB] = (cfg.flags & VDL2GPU_F_FEEDBACK) != 0;	/* (with or without VDL2GPU_F_FRAMES) */
 	h->frames_on = (cfg.flags & VDL2GPU_F_FRAMES) != 0;
 	if (h->frames_on) {
 		unsigned arena = 4u << 20;
@@ -1408,7 +1411,9 @@ static int launch_scan(vdl2gpu_t *h, int which, const K2Params &k2, dim3 grid, h
 /* A one-workgroup-per-channel kernel (k2r_regions, k2s_sort, k2s_merge, k2p_patch, k2c_resolve, k2f_commit) of `nt` threads on
  * stream s, which first works off the common area of the scan in front of it, if there is one.  Nothing else writes
  * K2Params.drain_*: a launch without a drain gets none. */
-static void launch_per_channel(const vdl2gpu_t *h, void (*kernel)(K2Params), unsigned nt, hipStream_t s, const K2Params &k2, const ScanDrain &drain = ScanDrain())
+template <class... A>
+static void launch_per_channel(const vdl2gpu_t *h, void (*kernel)(K2Params, A...), unsigned nt, hipStream_t s, const K2Params &k2, const ScanDrain &drain = ScanDrain(),
+			       A... more)	/* (k2f_commit_fb: the feedback rows) */
 {
 	K2Params q = k2;
 	q.drain_slot = drain.slot;
@@ -1416,7 +1421,7 @@ static void launch_per_channel(const vdl2gpu_t *h, void (*kernel)(K2Params), uns
 	q.drain_skip = drain.skip;
 	q.drain_pch = drain.pch;
 	q.drain_nwg = drain.nwg;
-	hipLaunchKernelGGL(kernel, dim3((unsigned)h->C, (unsigned)h->S), dim3(nt), 0, s, q);
+	hipLaunchKernelGGL(kernel, dim3((unsigned)h->C, (unsigned)h->S), dim3(nt), 0, s, q, more...);
 }
 
 /* the cluster kernel: a persistent grid */
@@ -1426,16 +1431,24 @@ static void launch_clusters(const vdl2gpu_t *h, hipStream_t s, const K2Params &k
 }
 
 /* The payload kernel of the handle's flags (each optional pass is a kernel variant of its own: register pressure) on the
- * selection `sel_mode` names (K2Params.sel_mode). */
+ * selection `sel_mode` names (K2Params.sel_mode).  ring: the output ring k2.recs lies in; with VDL2GPU_F_FEEDBACK its feedback rows are
+ * the kernel's second argument (they are no member of K2Params: vdl2gpu_resolve.h, k2d_run). */
 enum { SEL_FIRST = 0, SEL_REPAIRED = 1, SEL_FINAL = 2 };
-static void launch_payload(const vdl2gpu_t *h, hipStream_t s, const K2Params &k2, int sel_mode)
+static void launch_payload(const vdl2gpu_t *h, hipStream_t s, const K2Params &k2, int sel_mode, int ring)
 {
 	static void (*const kernels[8])(K2Params) = { k2d_payload, k2d_payload_lev, k2d_payload_soft, k2d_payload_lev_soft,
 						     k2d_payload_car, k2d_payload_lev_car, k2d_payload_soft_car, k2d_payload_lev_soft_car };
-	void (*const kernel)(K2Params) = kernels[(h->col_on[COL_LEVEL] ? 1 : 0) | (h->col_on[COL_SOFT] ? 2 : 0) | (h->col_on[COL_CARRIER] ? 4 : 0)];
+	/* VDL2GPU_F_FEEDBACK: the same eight with the feedback pass behind them; the rows' ring is their second argument */
+	static void (*const kernels_fb[8])(K2Params, vdl2gpu_fb_t *) = { k2d_payload_fb, k2d_payload_lev_fb, k2d_payload_soft_fb, k2d_payload_lev_soft_fb,
+									  k2d_payload_car_fb, k2d_payload_lev_car_fb, k2d_payload_soft_car_fb, k2d_payload_lev_soft_car_fb };
+	const int which = (h->col_on[COL_LEVEL] ? 1 : 0) | (h->col_on[COL_SOFT] ? 2 : 0) | (h->col_on[COL_CARRIER] ? 4 : 0);
 	K2Params q = k2;
 	q.sel_mode = sel_mode;
-	hipLaunchKernelGGL(kernel, dim3((unsigned)h->k2d_grid, (unsigned)(VDL2_CS * h->S)), dim3(K2D_NT), 0, s, q);
+	const dim3 grid((unsigned)h->k2d_grid, (unsigned)(VDL2_CS * h->S));
+	if (h->col_on[COL_FB])
+		hipLaunchKernelGGL(kernels_fb[which], grid, dim3(K2D_NT), 0, s, q, h->ring[ring].fb());
+	else
+		hipLaunchKernelGGL(kernels[which], grid, dim3(K2D_NT), 0, s, q);
 }
 
 /* tiles' worth of items a verify workgroup's private area is sized for: its share q of the pieces (k2a_verify) when a launch of
@@ -1585,6 +1598,14 @@ extern "C" int vdl2gpu_ring_commit(vdl2gpu_t *h, size_t nsamples)
 
 /* k4_frames on the records of output ring `ring` where they lie: compact entries, the record count from the device.  fmask: not
  * nullptr when K2d's second pass tags void records (see K4Params) */
+/* The block kernel on `grid` workgroups of stream s: with a report or without (rep), with the records' decision-feedback rows in the
+ * row rule (k4.fb is given) or without */
+static void launch_blocks(hipStream_t s, unsigned grid, const K4Params &k4, bool rep)
+{
+	void (*const kernel)(K4Params) = k4.fb ? (rep ? k4_frames_rep_fb : k4_frames_fb) : (rep ? k4_frames_rep : k4_frames);
+	hipLaunchKernelGGL(kernel, dim3(grid), dim3(K4_NT), 0, s, k4);
+}
+
 static K4Params k4_ring_params(vdl2gpu_t *h, int ring, const unsigned *fmask)
 {
 	K4Params k4{};
@@ -1599,6 +1620,7 @@ static K4Params k4_ring_params(vdl2gpu_t *h, int ring, const unsigned *fmask)
 	k4.fmask = fmask;
 	k4.soft = h->ring[ring].soft();	/* (nullptr without VDL2GPU_F_SOFT_RS: the reference's block path) */
 	k4.rep = h->ring[ring].report();	/* (nullptr without VDL2GPU_F_BLOCK_REPORT, and k4_frames is launched, which does not look at it) */
+	k4.fb = h->ring[ring].fb();	/* (nullptr without VDL2GPU_F_FEEDBACK: launch_blocks) */
 	return k4;
 }
 
@@ -1660,7 +1682,7 @@ static int enqueue_back(vdl2gpu_t *h)
 	hipStream_t ps = h->copy_stream;	/* (four hardware queues: the copy stream has one job) */
 	if (spec) {
 		HIPCHK(h, hipStreamWaitEvent(ps, h->k2c_done, 0));
-		launch_payload(h, ps, k2, SEL_FIRST);
+		launch_payload(h, ps, k2, SEL_FIRST, ring);
 		HIPCHK(h, hipEventRecord(h->pay_done, ps));
 	}
 	TRY(mark(h, pt, E_VERIFY_BEGIN, rs));
@@ -1736,7 +1758,10 @@ static int enqueue_back(vdl2gpu_t *h)
 		HIPCHK(h, hipGetLastError());
 	}
 	TRY(mark(h, pt, E_ROUNDS_END, ts));
-	launch_per_channel(h, k2f_commit, K2_NT, ts, k2, vdrain);
+	if (h->col_on[COL_FB])
+		launch_per_channel(h, k2f_commit_fb, K2_NT, ts, k2, vdrain, h->ring[ring].fb());
+	else
+		launch_per_channel(h, k2f_commit, K2_NT, ts, k2, vdrain);
 
 	TRY(h->k2f_done.record(h, ts));
 	TRY(mark(h, pt, E_COMMIT_END, ts, true));
@@ -1744,17 +1769,16 @@ static int enqueue_back(vdl2gpu_t *h)
 		if (ts != ps)
 			HIPCHK(h, hipStreamWaitEvent(ts, h->pay_done, 0));	/* the export needs the first pass's records, K3 publishes the record count */
 		if (!h->full_scan && !serial)	/* what the repair rounds (or K2f's serial redo) made void of the first selection is tagged now, what they selected is decoded */
-			launch_payload(h, ts, k2, SEL_REPAIRED);
+			launch_payload(h, ts, k2, SEL_REPAIRED, ring);
 	} else
-		launch_payload(h, ts, k2, SEL_FINAL);	/* one pass behind the commit: the repaired selection where there is one */
+		launch_payload(h, ts, k2, SEL_FINAL, ring);	/* one pass behind the commit: the repaired selection where there is one */
 	HIPCHK(h, hipGetLastError());
 	TRY(mark(h, pt, E_PAYLOAD2_END, ts, true));
 	if (h->frames_on) {
 		/* block path on the records where they lie (vdlm2.c:84-161).  In the chain, not beside it:
 		 * a latency-bound kernel like this one and the next push's scan slow each other down by
 		 * more than the overlap saves. */
-		hipLaunchKernelGGL(h->col_on[COL_REPORT] ? k4_frames_rep : k4_frames, dim3((unsigned)h->n_cu * 16), dim3(K4_NT), 0, ts,
-				   k4_ring_params(h, ring, spec ? h->set[par].k2.fmask : nullptr));
+		launch_blocks(ts, (unsigned)h->n_cu * 16, k4_ring_params(h, ring, spec ? h->set[par].k2.fmask : nullptr), h->col_on[COL_REPORT]);
 		HIPCHK(h, hipGetLastError());
 	}
 	TRY(mark(h, pt, E_BLOCKS_END, ts));
@@ -1775,6 +1799,11 @@ static int enqueue_back(vdl2gpu_t *h)
 		ke.rdst = h->slab[h->back.slab].d_report();
 		hipLaunchKernelGGL(k_export_records, dim3((unsigned)h->n_cu), dim3(256), 0, ts, ke);
 		HIPCHK(h, hipGetLastError());
+		if (h->col_on[COL_FB]) {	/* the feedback rows beside them: a kernel of its own, k_export_records keeps its registers */
+			hipLaunchKernelGGL(k_export_feedback, dim3((unsigned)h->n_cu), dim3(256), 0, ts, ke.count, ke.cap,
+					   static_cast<const vdl2gpu_fb_t *>(h->ring[ring].fb()), h->slab[h->back.slab].d_fb());
+			HIPCHK(h, hipGetLastError());
+		}
 		TRY(mark(h, pt, E_EXPORT_END, ts, true));
 		K3Params k3{};
 		k3.src = nullptr;	/* (the counters kernel copies nothing) */
@@ -2481,7 +2510,7 @@ static int collect_records(vdl2gpu_t *h, int ring, unsigned n)
 		HIPCHK(h, hipStreamSynchronize(h->copy_stream));
 		const vdl2gpu_burst_t *pin = reinterpret_cast<const vdl2gpu_burst_t *>(h->h_pin);
 		h->ready.recs.insert(h->ready.recs.end(), pin, pin + m);
-		for (int k = 0; k < VDL2_NCOL; ++k) {	/* the side columns present (32, 40 or 48 bytes a record, or 2048: a pageable copy) */
+		for (int k = 0; k < VDL2_NCOL; ++k) {	/* the side columns present (32, 40 or 48 bytes a record, or 2048 for a map or feedback rows: a pageable copy) */
 			if (!h->col_on[k])
 				continue;
 			std::vector<uint8_t> &q = h->ready.side[k];
@@ -2747,6 +2776,7 @@ struct BlockTemps {
 	vdl2gpu_frame_t *fr = nullptr;
 	unsigned *cnt = nullptr;
 	vdl2gpu_blockrep_t *rep = nullptr;
+	vdl2gpu_fb_t *fb = nullptr;
 	~BlockTemps()
 	{
 		(void)hipFree(blk);
@@ -2754,6 +2784,7 @@ struct BlockTemps {
 		(void)hipFree(fr);
 		(void)hipFree(cnt);
 		(void)hipFree(rep);
+		(void)hipFree(fb);
 	}
 };
 
@@ -2771,6 +2802,7 @@ static K4Params k4_block_params(vdl2gpu_t *h, const BlockTemps &d, int n, int ma
 	k4.tabs = h->d_k4tab;
 	k4.soft = d.soft;
 	k4.rep = d.rep;
+	k4.fb = d.fb;
 	return k4;
 }
 
@@ -2780,9 +2812,15 @@ extern "C" int vdl2gpu_decode_blocks_soft(vdl2gpu_t *h, const vdl2gpu_burst_t *b
 	return vdl2gpu_decode_blocks_report(h, blocks, soft, n, frames, max_frames, dropped, nullptr);
 }
 
-/* rep: k4_frames_rep instead of k4_frames, and its n reports come back beside the frames */
 extern "C" int vdl2gpu_decode_blocks_report(vdl2gpu_t *h, const vdl2gpu_burst_t *blocks, const vdl2gpu_soft_t *soft, int n,
 					    vdl2gpu_frame_t *frames, int max_frames, int *dropped, vdl2gpu_blockrep_t *rep)
+{
+	return vdl2gpu_decode_blocks_feedback(h, blocks, soft, nullptr, n, frames, max_frames, dropped, rep);
+}
+
+/* rep: the reporting kernel, and its n reports come back beside the frames; fb: the kernel with the feedback row rule (launch_blocks) */
+extern "C" int vdl2gpu_decode_blocks_feedback(vdl2gpu_t *h, const vdl2gpu_burst_t *blocks, const vdl2gpu_soft_t *soft, const vdl2gpu_fb_t *fb, int n,
+					      vdl2gpu_frame_t *frames, int max_frames, int *dropped, vdl2gpu_blockrep_t *rep)
 {
 	if (!h || n < 0 || max_frames < 0 || (n > 0 && !blocks) || (max_frames > 0 && !frames))
 		return VDL2GPU_EINVAL;
@@ -2806,14 +2844,18 @@ extern "C" int vdl2gpu_decode_blocks_report(vdl2gpu_t *h, const vdl2gpu_burst_t 
 	BLKCHK(hipMalloc(&d.cnt, 4 * sizeof(unsigned)));
 	if (rep)
 		BLKCHK(hipMalloc(&d.rep, (size_t)n * sizeof(vdl2gpu_blockrep_t)));
+	if (fb)
+		BLKCHK(hipMalloc(&d.fb, (size_t)n * sizeof(vdl2gpu_fb_t)));
 	/* on the stream the kernel runs on: that stream does not wait for the legacy default stream, and a
 	 * plain hipMemset() that lands after the kernel's first atomics loses frames */
 	BLKCHK(hipMemcpyAsync(d.blk, blocks, (size_t)n * sizeof(vdl2gpu_burst_t), hipMemcpyHostToDevice, h->copy_stream));
 	if (soft)
 		BLKCHK(hipMemcpyAsync(d.soft, soft, (size_t)n * sizeof(vdl2gpu_soft_t), hipMemcpyHostToDevice, h->copy_stream));
+	if (fb)
+		BLKCHK(hipMemcpyAsync(d.fb, fb, (size_t)n * sizeof(vdl2gpu_fb_t), hipMemcpyHostToDevice, h->copy_stream));
 	BLKCHK(hipMemsetAsync(d.cnt, 0, 4 * sizeof(unsigned), h->copy_stream));
 	const unsigned grid = (unsigned)std::min<long long>(n, (long long)h->n_cu * 32);
-	hipLaunchKernelGGL(rep ? k4_frames_rep : k4_frames, dim3(grid), dim3(K4_NT), 0, h->copy_stream, k4_block_params(h, d, n, max_frames));
+	launch_blocks(h->copy_stream, grid, k4_block_params(h, d, n, max_frames), rep != nullptr);
 	BLKCHK(hipGetLastError());
 	if (rep)	/* (no record is void here: every one of the n has been written) */
 		BLKCHK(hipMemcpyAsync(rep, d.rep, (size_t)n * sizeof(vdl2gpu_blockrep_t), hipMemcpyDeviceToHost, h->copy_stream));
@@ -2901,17 +2943,19 @@ extern "C" int vdl2gpu_inflight(vdl2gpu_t *h)
 	return n;
 }
 
-/* The ten collectors.  lv / sv / cv / rv: the side columns the caller wants beside the records (nullptr: not); lv_err / sv_err / cv_err /
- * rv_err: what the entry point says when the handle was made without that column. */
+/* The twelve collectors.  lv / sv / cv / rv / fv: the side columns the caller wants beside the records (nullptr: not); lv_err / sv_err /
+ * cv_err / rv_err / fv_err: what the entry point says when the handle was made without that column. */
 static int poll_impl(vdl2gpu_t *h, vdl2gpu_burst_t *out, vdl2gpu_level_t *lv, vdl2gpu_soft_t *sv, int max, bool blocking,
 		     const char *lv_err = nullptr, const char *sv_err = nullptr, vdl2gpu_carrier_t *cv = nullptr, const char *cv_err = nullptr,
-		     vdl2gpu_blockrep_t *rv = nullptr, const char *rv_err = nullptr)
+		     vdl2gpu_blockrep_t *rv = nullptr, const char *rv_err = nullptr, vdl2gpu_fb_t *fv = nullptr, const char *fv_err = nullptr)
 {
 	if (!h || (max > 0 && !out) || max < 0)
 		return VDL2GPU_EINVAL;
 	HLOCK(h);
-	if ((lv && !h->col_on[COL_LEVEL]) || (sv && !h->col_on[COL_SOFT]) || (cv && !h->col_on[COL_CARRIER]) || (rv && !h->col_on[COL_REPORT])) {
-		h->err = lv && !h->col_on[COL_LEVEL] ? lv_err : (sv && !h->col_on[COL_SOFT] ? sv_err : (cv && !h->col_on[COL_CARRIER] ? cv_err : rv_err));
+	if ((lv && !h->col_on[COL_LEVEL]) || (sv && !h->col_on[COL_SOFT]) || (cv && !h->col_on[COL_CARRIER]) || (rv && !h->col_on[COL_REPORT]) ||
+	    (fv && !h->col_on[COL_FB])) {
+		h->err = lv && !h->col_on[COL_LEVEL] ? lv_err : (sv && !h->col_on[COL_SOFT] ? sv_err : (cv && !h->col_on[COL_CARRIER] ? cv_err :
+			 (rv && !h->col_on[COL_REPORT] ? rv_err : fv_err)));
 		return VDL2GPU_EINVAL;
 	}
 	if (h->failed)
@@ -2925,6 +2969,7 @@ static int poll_impl(vdl2gpu_t *h, vdl2gpu_burst_t *out, vdl2gpu_level_t *lv, vd
 	side[COL_SOFT] = sv;
 	side[COL_CARRIER] = cv;
 	side[COL_REPORT] = rv;
+	side[COL_FB] = fv;
 	return hand_out(h, out, max, side);
 }
 
@@ -2980,6 +3025,22 @@ extern "C" int vdl2gpu_poll_report_ready(vdl2gpu_t *h, vdl2gpu_burst_t *out, vdl
 {
 	return poll_impl(h, out, lv, soft, max, false, "vdl2gpu_poll_report: lv needs VDL2GPU_F_LEVELS", "vdl2gpu_poll_report: soft needs VDL2GPU_F_SOFT_RS",
 			 car, "vdl2gpu_poll_report: car needs VDL2GPU_F_CARRIER", rep, "vdl2gpu_poll_report: rep needs VDL2GPU_F_BLOCK_REPORT");
+}
+
+extern "C" int vdl2gpu_poll_feedback(vdl2gpu_t *h, vdl2gpu_burst_t *out, vdl2gpu_level_t *lv, vdl2gpu_soft_t *soft, vdl2gpu_carrier_t *car, vdl2gpu_blockrep_t *rep,
+				     vdl2gpu_fb_t *fb, int max)
+{
+	return poll_impl(h, out, lv, soft, max, true, "vdl2gpu_poll_feedback: lv needs VDL2GPU_F_LEVELS", "vdl2gpu_poll_feedback: soft needs VDL2GPU_F_SOFT_RS",
+			 car, "vdl2gpu_poll_feedback: car needs VDL2GPU_F_CARRIER", rep, "vdl2gpu_poll_feedback: rep needs VDL2GPU_F_BLOCK_REPORT",
+			 fb, "vdl2gpu_poll_feedback: fb needs VDL2GPU_F_FEEDBACK");
+}
+
+extern "C" int vdl2gpu_poll_feedback_ready(vdl2gpu_t *h, vdl2gpu_burst_t *out, vdl2gpu_level_t *lv, vdl2gpu_soft_t *soft, vdl2gpu_carrier_t *car,
+					   vdl2gpu_blockrep_t *rep, vdl2gpu_fb_t *fb, int max)
+{
+	return poll_impl(h, out, lv, soft, max, false, "vdl2gpu_poll_feedback: lv needs VDL2GPU_F_LEVELS", "vdl2gpu_poll_feedback: soft needs VDL2GPU_F_SOFT_RS",
+			 car, "vdl2gpu_poll_feedback: car needs VDL2GPU_F_CARRIER", rep, "vdl2gpu_poll_feedback: rep needs VDL2GPU_F_BLOCK_REPORT",
+			 fb, "vdl2gpu_poll_feedback: fb needs VDL2GPU_F_FEEDBACK");
 }
 
 /* VDL2GPU_F_CARRIER: the derived values of a carrier record (include/vdl2gpu.h, vdl2gpu_carrier_t) -- the one statement of that

@@ -15,6 +15,8 @@
  * k4_rs_row alone.
  * The driver is a template over REP: k4_frames is the block path and nothing else; k4_frames_rep also keeps what the steps learn about
  * the burst (K4Rep, in LDS) and writes it out as the record's vdl2gpu_blockrep_t (VDL2GPU_F_BLOCK_REPORT, include/vdl2gpu.h).
+ * ... and over FB: k4_frames_fb / k4_frames_rep_fb try the record's decision-feedback row (K4Params.fb, VDL2GPU_F_FEEDBACK) behind a
+ * row that rs() fails on (k4_fb_row), in front of the soft trials.
  */
 #ifndef VDL2GPU_BLOCKS_H
 #define VDL2GPU_BLOCKS_H
@@ -54,6 +56,8 @@ struct K4Params {
 					 * rows the reference cannot decode.  nullptr: the reference's block path and nothing else */
 	vdl2gpu_blockrep_t *rep;	/* k4_frames_rep only (VDL2GPU_F_BLOCK_REPORT): the records' reports, same index.  k4_frames never
 					 * reads it (last: the other members keep their place) */
+	const vdl2gpu_fb_t *fb;		/* k4_frames_fb / k4_frames_rep_fb only (VDL2GPU_F_FEEDBACK): the records' decision-feedback rows, same
+					 * index: the row rule of vdl2gpu_fb_t.  The other two kernels never read it (last, for the same reason) */
 };
 
 #define K4_TABW ((512 + 256 + 512) / 4)
@@ -409,6 +413,10 @@ __device__ __forceinline__ bool k4_rs_row(K4Shared &sh, uint8_t *row, int nera, 
  * the received row.  The candidates' keys (rel << 8 | position) go through up to four wave-wide minimum searches; each trial starts
  * from the received row.  Without a success the reference's result is written back: it is what rs() leaves, computed again from the
  * same row and erasures.  Returns the number of candidates of the trial that replaced the row (2 or 4), 0: none did. */
+/* COPY: k4_frames and k4_frames_rep call copy 0, the two kernels with feedback rows copy 1 -- the same text twice in the library.  With
+ * all four calling one function k4_frames_rep is allocated other registers (45 scalar spills for 53), and what a handle without
+ * VDL2GPU_F_FEEDBACK runs stays what it was. */
+template <int COPY = 0>
 __device__ int k4_soft_row(K4Shared &sh, uint8_t *row, const uint8_t *rel, int by, int e0, int pr, const unsigned (&sexp)[4][2], int lane)
 {
 	const int smax = e0 + 4 <= 4 ? 4 : 2;
@@ -464,6 +472,33 @@ __device__ int k4_soft_row(K4Shared &sh, uint8_t *row, const uint8_t *rel, int b
 	return 0;
 }
 
+/* The feedback row rule (vdl2gpu.h, vdl2gpu_fb_t, step 2) for a row the reference's rs() has just failed on: the record's feedback row
+ * (global memory) goes where the row was, rs() runs on it with the same fixed erasures, and it stays if that returns >= 0 and leaves
+ * all six syndromes zero. */
+__device__ __forceinline__ bool k4_fb_row(K4Shared &sh, uint8_t *row, const uint8_t *fbrow, int by, int e0, const unsigned (&sexp)[4][2], int lane)
+{
+	for (int i = lane; i < 255; i += K4_NT)
+		row[i] = fbrow[i];
+	k4_set_eras(sh, by, lane);
+	K4_SYNC();
+	if (!k4_rs_row(sh, row, e0, sexp, lane))
+		return false;
+	unsigned syn[6];
+	const unsigned any = k4_syndromes(sh, row, sexp, syn, lane);
+	K4_SYNC();
+	return !any;
+}
+
+/* ... and when neither it nor a soft trial follows: what the reference left, computed again from the received row in sh.save */
+__device__ __forceinline__ void k4_ref_row_again(K4Shared &sh, uint8_t *row, int by, int e0, const unsigned (&sexp)[4][2], int lane)
+{
+	for (int i = lane; i < 255; i += K4_NT)
+		row[i] = sh.save[i];
+	k4_set_eras(sh, by, lane);
+	K4_SYNC();
+	k4_rs_row(sh, row, e0, sexp, lane);
+}
+
 /* ---- the record (msgblk_t, vdlm2.c:84-98): its front -- header and two rows -- into registers, and from there into LDS; the
  * remaining rows follow once the header has been read there */
 __device__ __forceinline__ void k4_fetch_head(const vdl2gpu_burst_t *g, unsigned (&rw)[K4_RECW0 / K4_NT], int lane)
@@ -485,9 +520,11 @@ __device__ __forceinline__ void k4_fetch_rows(K4Shared &sh, const vdl2gpu_burst_
  * (k4_rs_row's result, sh.rs_count as k4_rs_debug reads it) and from what k4_soft_row says; row_changed from a comparison of the final
  * row with the received one in sh.save, four bytes a lane, masked to the transmitted positions and counted over the wave; the three sums
  * are kept in registers (they are the same in every lane) and stored once. */
-template <bool REP>
+/* FB: fb is the record's feedback rows; a row rs() fails on first tries fb->data[r] (k4_fb_row); the soft trials follow only if that
+ * fails too, and without them the reference's result is put back (k4_soft_row does that itself). */
+template <bool REP, bool FB>
 __device__ __forceinline__ int k4_rs_rows(K4Shared &sh, const vdl2gpu_soft_t *soft, int nbrow, int nlbyte, const unsigned (&sexp)[4][2], int lane,
-					  vdl2gpu_blockrep_t *rep)
+					  vdl2gpu_blockrep_t *rep, const vdl2gpu_fb_t *fb)
 {
 	uint8_t *const rows = reinterpret_cast<uint8_t *>(sh.recw) + offsetof(vdl2gpu_burst_t, data);
 	if (lane < 6)
@@ -499,7 +536,7 @@ __device__ __forceinline__ int k4_rs_rows(K4Shared &sh, const vdl2gpu_soft_t *so
 		const int by = r == nbrow - 1 ? nlbyte : 249;
 		const int nera = k4_set_eras(sh, by, lane);	/* (a full row has none) */
 		uint8_t *const row = rows + r * VDL2GPU_ROWLEN;
-		if (REP || soft) {
+		if (REP || FB || soft) {
 			for (int i = lane; i < 255; i += K4_NT)
 				sh.save[i] = row[i];
 			K4_SYNC();
@@ -511,7 +548,17 @@ __device__ __forceinline__ int k4_rs_rows(K4Shared &sh, const vdl2gpu_soft_t *so
 			const bool ok = k4_rs_row(sh, row, nera, sexp, lane, &any);
 			const int roots = !ok ? -1 : (any ? sh.rs_count : 0);
 			unsigned how = !any ? VDL2GPU_ROW_CLEAN : (ok ? VDL2GPU_ROW_REF : VDL2GPU_ROW_FAIL);
-			if (!ok && soft && nera + 2 <= 4) {
+			if constexpr (FB) {
+				if (!ok) {
+					if (k4_fb_row(sh, row, &fb->data[r][0], by, nera, sexp, lane))
+						how = VDL2GPU_ROW_FEEDBACK;
+					else if (soft && nera + 2 <= 4) {
+						const int s = k4_soft_row<1>(sh, row, &soft->rel[r][0], by, nera, pr, sexp, lane);
+						how = s == 2 ? VDL2GPU_ROW_SOFT2 : (s == 4 ? VDL2GPU_ROW_SOFT4 : VDL2GPU_ROW_FAIL);
+					} else
+						k4_ref_row_again(sh, row, by, nera, sexp, lane);
+				}
+			} else if (!ok && soft && nera + 2 <= 4) {
 				const int s = k4_soft_row(sh, row, &soft->rel[r][0], by, nera, pr, sexp, lane);
 				how = s == 2 ? VDL2GPU_ROW_SOFT2 : (s == 4 ? VDL2GPU_ROW_SOFT4 : VDL2GPU_ROW_FAIL);
 			}
@@ -530,7 +577,16 @@ __device__ __forceinline__ int k4_rs_rows(K4Shared &sh, const vdl2gpu_soft_t *so
 			}
 			changed += nch;
 			failed += how == VDL2GPU_ROW_FAIL;
-			rescued += how == VDL2GPU_ROW_SOFT2 || how == VDL2GPU_ROW_SOFT4;
+			rescued += how == VDL2GPU_ROW_SOFT2 || how == VDL2GPU_ROW_SOFT4 || (FB && how == VDL2GPU_ROW_FEEDBACK);
+		} else if constexpr (FB) {
+			if (!k4_rs_row(sh, row, nera, sexp, lane) && !k4_fb_row(sh, row, &fb->data[r][0], by, nera, sexp, lane)) {
+				if (soft && nera + 2 <= 4) {
+					const BurstGeom g = burst_geom(nbrow, nlbyte);
+					const int pr = r < g.nf_rows - 1 ? 6 : (r == g.nf_rows - 1 ? g.nf_last : 0);	/* the transmitted parity of row r */
+					k4_soft_row<1>(sh, row, &soft->rel[r][0], by, nera, pr, sexp, lane);
+				} else
+					k4_ref_row_again(sh, row, by, nera, sexp, lane);
+			}
 		} else if (!k4_rs_row(sh, row, nera, sexp, lane) && soft) {
 			const BurstGeom g = burst_geom(nbrow, nlbyte);
 			const int pr = r < g.nf_rows - 1 ? 6 : (r == g.nf_rows - 1 ? g.nf_last : 0);	/* the transmitted parity of row r */
@@ -819,7 +875,8 @@ __device__ __forceinline__ void k4_rep_store(const K4Rep &rp, vdl2gpu_blockrep_t
 		reinterpret_cast<unsigned *>(g)[lane] = rp.w[lane];
 }
 
-template <bool REP>
+/* FB: p.fb holds the records' decision-feedback rows for the row rule of vdl2gpu_fb_t */
+template <bool REP, bool FB = false>
 __device__ __forceinline__ void k4_frames_body(const K4Params &p)
 {
 	__shared__ K4Shared sh;
@@ -869,7 +926,7 @@ __device__ __forceinline__ void k4_frames_body(const K4Params &p)
 		if (badhead)
 			continue;
 		k4_fetch_rows(sh, p.recs + ib, nbrow, lane);
-		const int nby = k4_rs_rows<REP>(sh, p.soft ? p.soft + ib : nullptr, nbrow, nlbyte, sexp, lane, &rp.r);
+		const int nby = k4_rs_rows<REP, FB>(sh, p.soft ? p.soft + ib : nullptr, nbrow, nlbyte, sexp, lane, &rp.r, FB ? p.fb + ib : nullptr);
 		const int nbits = k4_unstuff(sh, nby, lane);
 		const int nb = nbits >> 3;	/* whole un-stuffed bytes */
 		int c0, c1;	/* of them, the lane's */
@@ -912,6 +969,19 @@ __global__ __launch_bounds__(K4_NT)
 void k4_frames_rep(K4Params p)
 {
 	k4_frames_body<true>(p);
+}
+
+/* VDL2GPU_F_FEEDBACK and vdl2gpu_decode_blocks_feedback: the same two with the records' feedback rows (p.fb) in the row rule */
+__global__ __launch_bounds__(K4_NT)
+void k4_frames_fb(K4Params p)
+{
+	k4_frames_body<false, true>(p);
+}
+
+__global__ __launch_bounds__(K4_NT)
+void k4_frames_rep_fb(K4Params p)
+{
+	k4_frames_body<true, true>(p);
 }
 
 /* vdl2gpu_debug_rs: k4_rs_row as k4_frames calls it, one wavefront per row, so that a test can hold what it leaves in a row --

@@ -138,6 +138,19 @@ void k_export_records(KExportParams p)
 	}
 }
 
+/* VDL2GPU_F_FEEDBACK: the records' decision-feedback rows beside them, launched behind k_export_records with its count / cap -- a
+ * kernel of its own, so that k_export_records keeps its registers --: all 2048 bytes, like a reliability map.  One wavefront per record. */
+__global__ __launch_bounds__(256)
+void k_export_feedback(const unsigned *count, unsigned cap, const vdl2gpu_fb_t *fb, vdl2gpu_fb_t *fdst)
+{
+	unsigned n = *count;
+	n = n < cap ? n : cap;
+	const unsigned lane = threadIdx.x & 63u;
+	for (unsigned r = blockIdx.x * 4u + (threadIdx.x >> 6); r < n; r += gridDim.x * 4u)
+		for (unsigned i = lane; i < sizeof(vdl2gpu_fb_t) / 8; i += 64u)
+			reinterpret_cast<unsigned long long *>(fdst + r)[i] = reinterpret_cast<const unsigned long long *>(fb + r)[i];
+}
+
 /* test hook: both device forms of atan2f; a disagreement between them comes back as NaN */
 __global__ void k_atan2f(const float *y, const float *x, float *out, size_t n)
 {

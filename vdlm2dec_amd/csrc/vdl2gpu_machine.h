@@ -359,6 +359,127 @@ template <int NT> __device__ __forceinline__ void burst_payload_carrier(vdl2gpu_
 	}
 }
 
+/* VDL2GPU_F_FEEDBACK: the decision-feedback rows of the burst burst_payload has just decoded (vdl2gpu.h, vdl2gpu_fb_t), all NT threads,
+ * called behind it.  Three steps over the symbols k = 8 .. kmax, in chunks that `ob` (LDS bytes, 4-byte aligned, cap of them) holds:
+ *   1. one lane per symbol takes the same Grey table index as the payload decode -- from sph when the caller kept the phases there
+ *      (K2d), else from two phases of its own (k2_fir_phase_tab, same result bits) -- and keeps idx & 255, one byte a symbol (only
+ *      idx mod 256 enters the rule, and (256 & 31) == (0 & 31)).  ob may BE sph: pass p reads floats [p NT, (p + 1) NT] and, behind a
+ *      barrier, writes bytes [p NT, (p + 1) NT), which lie in floats below (p + 1) NT / 4 <= p NT that no later pass reads.
+ *      S = sum e_k as in burst_payload_carrier (wave butterfly, one LDS atomic per wavefront into acc[0]); without sph a first pass over
+ *      all symbols forms S alone, because mbar has to be known before the first chunk's recursion.
+ *   2. thread 0 walks the chunk's bytes a word at a time and replaces idx_k by o_k; r_{k-1..k-3} stay in its registers across chunks.
+ *   3. one lane per byte whose bits lie in the chunk builds it from Grey_w[o_k] and scatters it like data[].
+ * A chunk ends where a byte boundary and a symbol boundary meet -- byte 1 + 3 m begins with symbol 11 + 8 m -- so no byte straddles two
+ * chunks: chunk c holds symbols [c ? 11 + 8 M c : 8, 11 + 8 M (c + 1)) and bytes [c ? 1 + 3 M c : 0, 1 + 3 M (c + 1)), M = (cap - 3) / 8.
+ * K2d's sph (VDL2_MAXSYM floats) takes any burst in one chunk -- it has to: with sph, S is added up while the first chunk is filled, and
+ * k2d_run asserts that at compile time --; the serial machine lends 2048 bytes, three chunks for the longest.
+ * Integers only behind step 1: every kernel, path and NT leaves the same rows.  (block-uniform call: barriers inside) */
+template <int NT> __device__ __forceinline__ void burst_payload_feedback(vdl2gpu_fb_t *out, const float2 *x0, const uint8_t *pn, const uint8_t *pn8, long long nstar,
+									 int clk0, float df, int nbrow, int nlbyte, const float *sph, const float *lds_fir,
+									 const float *grey, uint8_t *ob, int cap, int *acc)
+{
+	static_assert(NT % 64 == 0, "whole wavefronts");
+	const int tid = threadIdx.x;
+	int j0, rb;
+	burst_timing(clk0, &j0, &rb);
+	const BurstGeom g = burst_geom(nbrow, nlbyte);
+	const int nbytes = g.ND + g.NF;
+	const int kmax = (25 + 8 * nbytes - 1) / 3;
+	const float2 *xs0 = x0 + (nstar + j0 - 16);
+	const int M = (cap - 3) / 8;
+	const int nchunk = (kmax + 1 - 11 + 8 * M - 1) / (8 * M) > 1 ? (kmax + 1 - 11 + 8 * M - 1) / (8 * M) : 1;	/* (kmax >= 10) */
+	uint32_t *w = reinterpret_cast<uint32_t *>(out);
+	static_assert(sizeof(vdl2gpu_fb_t) == 2048, "the rows are zeroed as 512 words");
+	for (int i = tid; i < 512; i += NT)
+		w[i] = 0u;
+	if (tid == 0)
+		acc[0] = 0;
+	__syncthreads();
+	int se = 0;
+	if (!sph) {	/* (block-uniform) S ahead of the chunks */
+		for (int k = 8 + tid; k <= kmax; k += NT) {
+			const float pprev = k2_fir_phase_tab(xs0 + 8LL * (k - 1), rb, lds_fir, lds_fir + 72);
+			const float pk = k2_fir_phase_tab(xs0 + 8LL * k, rb, lds_fir, lds_fir + 72);
+			se += (k2_grey_index(pk, pprev, df) & 31) - 16;
+		}
+	}
+	int r1 = 0, r2 = 0, r3 = 0, mbar = 0;	/* (thread 0) */
+	for (int c = 0; c < nchunk; ++c) {
+		const int ks = c ? 11 + 8 * M * c : 8;
+		const int ke = 11 + 8 * M * (c + 1) < kmax + 1 ? 11 + 8 * M * (c + 1) : kmax + 1;
+		const int bs = c ? 1 + 3 * M * c : 0;
+		const int be = 1 + 3 * M * (c + 1) < nbytes ? 1 + 3 * M * (c + 1) : nbytes;
+		/* 1. the chunk's indices */
+		for (int k0 = ks; k0 < ke; k0 += NT) {	/* (block-uniform trip count) */
+			const int k = k0 + tid;
+			int idx = 0;
+			if (k < ke) {
+				const float pprev = sph ? sph[k - 8] : k2_fir_phase_tab(xs0 + 8LL * (k - 1), rb, lds_fir, lds_fir + 72);
+				const float pk = sph ? sph[k - 7] : k2_fir_phase_tab(xs0 + 8LL * k, rb, lds_fir, lds_fir + 72);
+				idx = k2_grey_index(pk, pprev, df);
+				if (sph)
+					se += (idx & 31) - 16;
+			}
+			__syncthreads();	/* (ob may be sph: this pass has been read) */
+			if (k < ke)
+				ob[k - ks] = (uint8_t)idx;
+		}
+		if (c == 0) {
+#pragma unroll
+			for (int d = 32; d >= 1; d >>= 1)
+				se += __shfl_xor(se, d, 64);
+			if ((tid & 63) == 0)
+				atomicAdd(&acc[0], se);
+		}
+		__syncthreads();
+		/* 2. the recursion */
+		if (tid == 0) {
+			if (c == 0) {
+				const int n = kmax - 7, num = 2 * acc[0] + n, den = 2 * n;
+				mbar = num / den - (num % den < 0 ? 1 : 0);
+			}
+			uint32_t *ow = reinterpret_cast<uint32_t *>(ob);
+			const int nk = ke - ks;
+			for (int i = 0; i < nk; i += 4) {
+				const uint32_t v = ow[i >> 2];
+				uint32_t u = 0;
+#pragma unroll
+				for (int j = 0; j < 4; ++j) {
+					if (i + j < nk) {
+						const int idx = (int)((v >> (8 * j)) & 0xffu);
+						const int fb = (3 * r1 + 2 * r2 + r3 + 2) >> 2;	/* floor: an arithmetic shift */
+						const int o = (idx - mbar + fb) & 255;
+						const int r = ((idx - 16 - 32 * (o >> 5) - mbar + 128) & 255) - 128;
+						r3 = r2;
+						r2 = r1;
+						r1 = r;
+						u |= (uint32_t)o << (8 * j);
+					}
+				}
+				ow[i >> 2] = u;
+			}
+		}
+		__syncthreads();
+		/* 3. the chunk's bytes */
+		for (int b = bs + tid; b < be; b += NT) {
+			const int q0 = 25 + 8 * b;
+			unsigned byte = 0;
+			const unsigned pnb = pn8 ? pn8[b] : 0u;
+#pragma unroll
+			for (int i = 0; i < 8; ++i) {
+				const int q = q0 + i, k = q / 3;
+				const float v = k2_soft_bit((int)ob[k - ks], q - 3 * k, pn8 ? (int)((pnb >> i) & 1u) : (int)pn[q], grey);
+				if ((double)v > 0.5)
+					byte |= 1u << i;
+			}
+			int row, col;
+			burst_scatter(g, b, &row, &col);
+			out->data[row][col] = (uint8_t)byte;
+		}
+		__syncthreads();	/* (the next chunk overwrites ob) */
+	}
+}
+
 template <int NT> struct MachSharedT {
 	float pbuf[VDL2_NPH + NT];	/* phases: [0,68) = history ring */
 	float errs[NT + 2];		/* errs[t+2] = err of eval t; [0],[1] = p2err, perr */
@@ -748,8 +869,10 @@ template <int NT, bool XL> __device__ __forceinline__ MachTrig mach_trigger(Mach
 /* What a trigger that is not deferred leaves behind: counters and, for an accepted header, the burst's
  * descriptor (or its record, payload decoded at once).  Returns the stream time of the burst's last
  * symbol (of header symbol 8 for a rejected one): the idle search resumes two samples later. */
-template <int NT, bool XL> __device__ __forceinline__ long long mach_commit_trigger(MachSharedT<NT> &sh, MachCtx &cx, const float2 *x0,
-										       long long nstar, const MachTrig &tg, MachOut &out)
+/* FB (k2f_commit_fb, VDL2GPU_F_FEEDBACK): the record's decision-feedback rows as well, into fbrows[slot] -- a compile-time switch and an
+ * argument of its own, so that every other kernel the machine is part of keeps its code. */
+template <int NT, bool XL, bool FB = false> __device__ __forceinline__ long long mach_commit_trigger(MachSharedT<NT> &sh, MachCtx &cx, const float2 *x0,
+										       long long nstar, const MachTrig &tg, MachOut &out, vdl2gpu_fb_t *fbrows = nullptr)
 {
 	const int tid = threadIdx.x;
 	const int clk0 = tg.clk0, accepted = tg.accepted, nbrow = tg.nbrow, nlbyte = tg.nlbyte, nsym = tg.nsym;
@@ -801,6 +924,14 @@ template <int NT, bool XL> __device__ __forceinline__ long long mach_commit_trig
 		}
 		if (!XL && !cx.desc && slot != 0xffffffffu && cx.carrier)	/* (block-uniform; sh.ctl[9], [10]: its two sums) */
 			burst_payload_carrier<NT>(cx.carrier + slot, x0, nstar, clk0, df, nbrow, nlbyte, nullptr, sh.smf, &sh.ctl[9]);
+		if constexpr (FB && !XL) {
+			if (!cx.desc && slot != 0xffffffffu) {	/* (block-uniform; sh.xt is the cluster mode's tile: free here, 2048 bytes for the indices; sh.ctl[11]: S) */
+				static_assert(sizeof sh.xt >= 2048, "burst_payload_feedback's chunk");
+				__syncthreads();
+				burst_payload_feedback<NT>(fbrows + slot, x0, cx.pn, nullptr, nstar, clk0, df, nbrow, nlbyte, nullptr, sh.smf, cx.grey,
+							   reinterpret_cast<uint8_t *>(sh.xt), 2048, &sh.ctl[11]);
+			}
+		}
 		if (slot == 0xffffffffu)
 			out.badslot = 1;
 		out.nslots++;
@@ -811,8 +942,8 @@ template <int NT, bool XL> __device__ __forceinline__ long long mach_commit_trig
 
 /* stop_steady: return MR_STEADY as soon as the detector is history-free and at least
  * `min_trig` triggers were handled.  first_nev: size of the first search window (a hint). */
-template <int NT, bool XL> __device__ __forceinline__ int machine_run(MachSharedT<NT> &sh, MachCtx &cx, MachState &st, bool stop_steady,
-					     int min_trig, int max_bursts, int first_nev, MachOut &out)
+template <int NT, bool XL, bool FB = false> __device__ __forceinline__ int machine_run(MachSharedT<NT> &sh, MachCtx &cx, MachState &st, bool stop_steady,
+					     int min_trig, int max_bursts, int first_nev, MachOut &out, vdl2gpu_fb_t *fbrows = nullptr)
 {
 	const int tid = threadIdx.x;
 	const float2 *x0 = cx.x - cx.dec_base;	/* x0[n] = sample at stream time n */
@@ -885,7 +1016,7 @@ template <int NT, bool XL> __device__ __forceinline__ int machine_run(MachShared
 			rc = MR_DEFER;
 			break;
 		}
-		const long long nlast = mach_commit_trigger<NT, XL>(sh, cx, x0, nstar, tg, out);
+		const long long nlast = mach_commit_trigger<NT, XL, FB>(sh, cx, x0, nstar, tg, out, fbrows);
 		/* back to the idle detector: ring keeps the phases up to the trigger
 		 * evaluation (Ph is not written during a burst), errors re-armed
 		 * (d8psk.c:308), sub-phase sticks at rb */

@@ -1280,6 +1280,7 @@ void k2p_patch(K2Params p)
  * state by the serial machine alone (always exact; it writes its bursts itself) and the
  * resolver's selection for that channel is dropped.
  */
+/* (k2f_commit_fb, below, is this kernel's text once more with the feedback rows: a change here is a change there) */
 __global__ __launch_bounds__(K2_NT)
 void k2f_commit(K2Params p)
 {
@@ -1330,6 +1331,60 @@ void k2f_commit(K2Params p)
 	}
 }
 
+/* VDL2GPU_F_FEEDBACK: k2f_commit again, statement for statement, with the one difference that the serial machine also writes every
+ * record's decision-feedback rows, fb[slot] (machine_run<.., true>, burst_payload_feedback).  A kernel of its own text, not a body the
+ * two share: called through a shared function k2f_commit compiles to other registers (226 VGPRs and 264 scalar spills for 234 and
+ * 258), and what a handle without the flag runs stays what it was.  tests/test_gpu_feedback.py holds the two against each other:
+ * the records and every other column of a redone channel are those of a handle without the flag. */
+__global__ __launch_bounds__(K2_NT)
+void k2f_commit_fb(K2Params p, vdl2gpu_fb_t *fb)
+{
+	__shared__ MachSharedT<K2_NT> sh;
+	__shared__ K2xWork xw;
+	const int tid = threadIdx.x;
+	const int c = blockIdx.x, s = (int)blockIdx.y;
+	const int sc = s * VDL2_CS + c;
+	ChanState *cs = p.cs + sc;
+	k2x_drain<K2_NT>(xw, p, sc);
+	if (p.fail[sc] >= VDL2_VERIFIED) {
+		const uint32_t *src = reinterpret_cast<const uint32_t *>(p.cs_out + sc);
+		uint32_t *dst = reinterpret_cast<uint32_t *>(cs);
+		for (int i = tid; i < (int)(sizeof(ChanState) / 4); i += K2_NT)
+			dst[i] = src[i];
+		if (tid == 0 && p.sel_reserved && k2_fmask_test(p, sc)) {
+			const unsigned n = p.ctl[CTL_NSEL1 + sc];
+			if (n > 0)
+				p.ctl[CTL_SELBASE1 + sc] = atomicAdd(p.outc, n > VDL2_SEL_CAP ? VDL2_SEL_CAP : n);
+		}
+		return;
+	}
+	MachCtx cx;
+	mach_ctx(cx, p, s, c, false);
+	MachState st = mach_state(cs);
+	const long long p0 = st.pos;
+	mach_init_taps(sh);
+	mach_load(sh, cs);
+	MachOut out;
+	mach_out_clear(out);
+	machine_run<K2_NT, false, true>(sh, cx, st, false, 0, 1 << 30, 0, out, fb);
+	__syncthreads();
+	mach_store(sh, st, cs);
+	if (tid == 0) {
+		cs->n_eval += (unsigned long long)out.neval;
+		cs->n_trig += (unsigned long long)out.ntrig;
+		cs->n_reject += (unsigned long long)out.nrej;
+		cs->n_burst += (unsigned long long)out.nburst;
+		cs->n_defer += (unsigned long long)out.ndefer;
+		cs->n_slow += (unsigned long long)(st.pos - p0);
+		cs->n_redo += 1;
+		atomicAdd(p.outc_total_redo, 1u);
+		p.ctl[CTL_NSEL1 + sc] = 0;
+		p.ctl[CTL_NWIN0 + sc] = VDL2_WIN_ALL;
+		p.redo[sc] = 1;
+		k2_fmask_set(p, sc);
+	}
+}
+
 /* ====================================================================== K2d
  * Payload decode of the bursts that lie on the real chain: one workgroup per
  * selected burst descriptor, one lane per byte.
@@ -1346,10 +1401,15 @@ void k2f_commit(K2Params p)
  * (burst_payload_soft) -- k2d_payload_soft, and k2d_payload_lev_soft with both flags */
 /* CAR (VDL2GPU_F_CARRIER): behind every burst one lane per symbol adds up the slices' distance from their sectors' centres, again
  * from the phases in sph (burst_payload_carrier) -- four kernels more, k2d_payload*_car, so that the four above keep their code */
-template <bool LEV, bool SOFT, bool CAR = false> __device__ __forceinline__ void k2d_run(const K2Params &p)
+/* FB (VDL2GPU_F_FEEDBACK): behind every burst its symbols are sliced a second time with the residuals of the last three fed back
+ * (burst_payload_feedback: the indices go where the phases were, one byte a symbol, so it comes last) -- eight kernels more,
+ * k2d_payload*_fb, so that the eight above keep their code.  The rows' ring (fb, one vdl2gpu_fb_t per record slot of p.recs) is a
+ * second kernel argument, not a member of K2Params: the parameter block of every kernel that never reads them stays what it was */
+template <bool LEV, bool SOFT, bool CAR = false, bool FB = false> __device__ __forceinline__ void k2d_run(const K2Params &p, vdl2gpu_fb_t *fb = nullptr)
 {
 	__shared__ unsigned s_slot;
 	__shared__ int s_car[2];	/* (CAR only: the burst's two sums) */
+	__shared__ int s_fb[1];		/* (FB only: the burst's sum of residuals) */
 	__shared__ float sph[VDL2_MAXSYM];
 	__shared__ float s_tabs[72 + VDL2_ATAN_ROWS * VDL2_ATAN_STRIDE + 3 * 257];	/* mflt[], atanf range table, Grey1/2/3 (see burst_payload) */
 	const int sc = (int)blockIdx.y;	/* stream * VDL2_CS + channel slot, like everywhere else: the grid spans all VDL2_CS slots of every stream */
@@ -1451,6 +1511,13 @@ template <bool LEV, bool SOFT, bool CAR = false> __device__ __forceinline__ void
 			}
 			if (CAR)
 				burst_payload_carrier<K2D_NT>(p.carrier + slot, x0, d.nstar, d.clk0, d.df, d.nbrow, d.nlbyte, sph, s_tabs, s_car);
+			if (FB) {
+				/* burst_payload_feedback adds S up while it fills its first chunk from sph: sph has to take the longest burst in one */
+				static_assert(11 + 8 * ((VDL2_MAXSYM - 3) / 8) > (25 + 8 * VDL2GPU_MAXROWS * VDL2GPU_ROWLEN - 1) / 3, "one chunk of indices in sph");
+				__syncthreads();	/* (everybody is done with the phases) */
+				burst_payload_feedback<K2D_NT>(fb + slot, x0, p.pn, p.pn8, d.nstar, d.clk0, d.df, d.nbrow, d.nlbyte, sph, s_tabs,
+							       s_tabs + 72 + VDL2_ATAN_ROWS * VDL2_ATAN_STRIDE, reinterpret_cast<uint8_t *>(sph), VDL2_MAXSYM, s_fb);
+			}
 		}
 		__syncthreads();
 	}
@@ -1502,6 +1569,54 @@ __global__ __launch_bounds__(K2D_NT) __attribute__((amdgpu_waves_per_eu(4, 8)))
 void k2d_payload_lev_soft_car(K2Params p)
 {
 	k2d_run<true, true, true>(p);
+}
+
+__global__ __launch_bounds__(K2D_NT) __attribute__((amdgpu_waves_per_eu(4, 8)))
+void k2d_payload_fb(K2Params p, vdl2gpu_fb_t *fb)
+{
+	k2d_run<false, false, false, true>(p, fb);
+}
+
+__global__ __launch_bounds__(K2D_NT) __attribute__((amdgpu_waves_per_eu(4, 8)))
+void k2d_payload_lev_fb(K2Params p, vdl2gpu_fb_t *fb)
+{
+	k2d_run<true, false, false, true>(p, fb);
+}
+
+__global__ __launch_bounds__(K2D_NT) __attribute__((amdgpu_waves_per_eu(4, 8)))
+void k2d_payload_soft_fb(K2Params p, vdl2gpu_fb_t *fb)
+{
+	k2d_run<false, true, false, true>(p, fb);
+}
+
+__global__ __launch_bounds__(K2D_NT) __attribute__((amdgpu_waves_per_eu(4, 8)))
+void k2d_payload_lev_soft_fb(K2Params p, vdl2gpu_fb_t *fb)
+{
+	k2d_run<true, true, false, true>(p, fb);
+}
+
+__global__ __launch_bounds__(K2D_NT) __attribute__((amdgpu_waves_per_eu(4, 8)))
+void k2d_payload_car_fb(K2Params p, vdl2gpu_fb_t *fb)
+{
+	k2d_run<false, false, true, true>(p, fb);
+}
+
+__global__ __launch_bounds__(K2D_NT) __attribute__((amdgpu_waves_per_eu(4, 8)))
+void k2d_payload_lev_car_fb(K2Params p, vdl2gpu_fb_t *fb)
+{
+	k2d_run<true, false, true, true>(p, fb);
+}
+
+__global__ __launch_bounds__(K2D_NT) __attribute__((amdgpu_waves_per_eu(4, 8)))
+void k2d_payload_soft_car_fb(K2Params p, vdl2gpu_fb_t *fb)
+{
+	k2d_run<false, true, true, true>(p, fb);
+}
+
+__global__ __launch_bounds__(K2D_NT) __attribute__((amdgpu_waves_per_eu(4, 8)))
+void k2d_payload_lev_soft_car_fb(K2Params p, vdl2gpu_fb_t *fb)
+{
+	k2d_run<true, true, true, true>(p, fb);
 }
 
 #endif

@@ -67,7 +67,7 @@ class BlockReport:
     """vdl2gpu_blockrep_t: what the block path made of a burst (Receiver(frames=True, block_report=True), decode_blocks(report=True);
     definitions in include/vdl2gpu.h)."""
     row_roots: Tuple[int, ...]     # per row: rs()'s return value for the received row (-1: it failed)
-    row_how: Tuple[int, ...]       # per row: lib.ROW_NONE / CLEAN / REF / SOFT2 / SOFT4 / FAIL
+    row_how: Tuple[int, ...]       # per row: lib.ROW_NONE / CLEAN / REF / SOFT2 / SOFT4 / FAIL / FEEDBACK
     row_changed: Tuple[int, ...]   # per row: transmitted bytes the decode changed
     bytes_changed: int
     rows_failed: int
@@ -115,6 +115,7 @@ class Burst:
     soft: Optional[np.ndarray] = None   # Receiver(soft_rs=True) only: uint8 (8, 255) byte reliabilities; not part of key()
     carrier: Optional[Carrier] = None   # Receiver(carrier=True) only; not part of key()
     report: Optional[BlockReport] = None   # Receiver(frames=True, block_report=True) only; not part of key()
+    fb: Optional[np.ndarray] = None   # Receiver(feedback=True) only: uint8 (8, 255), the rows sliced with decision feedback; not part of key()
 
     def key(self):
         return (self.stream, self.chn, self.nbrow, self.nlbyte, self.data)
@@ -131,7 +132,9 @@ class Receiver:
                  max_bursts: int = 0, keep_dec: bool = False, serial: bool = False, full_scan: bool = False,
                  frames: bool = False, rtl_quirk: bool = False, flags: int = 0, testhooks: bool = False,
                  levels: bool = False, soft_rs: bool = False, exact_fo: bool = False, carrier: bool = False,
-                 block_report: bool = False):
+                 block_report: bool = False, feedback: bool = False):
+        # feedback: VDL2GPU_F_FEEDBACK, every burst's rows sliced a second time with decision feedback (Burst.fb); with frames=True the
+        # block path takes a row the reference cannot decode from them
         # block_report: VDL2GPU_F_BLOCK_REPORT (needs frames=True), what the block path made of every burst (Burst.report)
         # carrier: VDL2GPU_F_CARRIER, every burst's carrier offset and phase-error spread (Burst.carrier)
         # exact_fo: VDL2GPU_F_EXACT_FO, channel offsets off the 25 kHz grid with a phase-continuous oscillator (include/vdl2gpu.h)
@@ -161,12 +164,13 @@ class Receiver:
         cfg.max_push = max_push
         cfg.device = device
         cfg.max_bursts = max_bursts
-        cfg.flags = (_lib.F_KEEP_DEC if keep_dec else 0) | (_lib.F_SERIAL if serial else 0) | (_lib.F_FULLSCAN if full_scan else 0) | (_lib.F_FRAMES if frames else 0) | (_lib.F_RTL_QUIRK if rtl_quirk else 0) | (_lib.F_LEVELS if levels else 0) | (_lib.F_SOFT_RS if soft_rs else 0) | (_lib.F_EXACT_FO if exact_fo else 0) | (_lib.F_CARRIER if carrier else 0) | (_lib.F_BLOCK_REPORT if block_report else 0) | flags
+        cfg.flags = (_lib.F_KEEP_DEC if keep_dec else 0) | (_lib.F_SERIAL if serial else 0) | (_lib.F_FULLSCAN if full_scan else 0) | (_lib.F_FRAMES if frames else 0) | (_lib.F_RTL_QUIRK if rtl_quirk else 0) | (_lib.F_LEVELS if levels else 0) | (_lib.F_SOFT_RS if soft_rs else 0) | (_lib.F_EXACT_FO if exact_fo else 0) | (_lib.F_CARRIER if carrier else 0) | (_lib.F_BLOCK_REPORT if block_report else 0) | (_lib.F_FEEDBACK if feedback else 0) | flags
         self.max_push = max_push
         self.levels = bool(cfg.flags & _lib.F_LEVELS)
         self.soft_rs = bool(cfg.flags & _lib.F_SOFT_RS)
         self.carrier = bool(cfg.flags & _lib.F_CARRIER)
         self.block_report = bool(cfg.flags & _lib.F_BLOCK_REPORT)
+        self.feedback = bool(cfg.flags & _lib.F_FEEDBACK)
         self.h = C.c_void_p()
         rc = self.L.vdl2gpu_create(C.byref(cfg), C.byref(self.h))
         if rc != 0:
@@ -224,8 +228,12 @@ class Receiver:
         sv = (_lib.SoftT * max_bursts)() if self.soft_rs else None
         cv = (_lib.CarrierT * max_bursts)() if self.carrier else None
         rv = (_lib.BlockRepT * max_bursts)() if self.block_report else None
+        fv = (_lib.FbT * max_bursts)() if self.feedback else None
         while True:
-            if rv is not None:
+            if fv is not None:
+                fn = self.L.vdl2gpu_poll_feedback_ready if ready else self.L.vdl2gpu_poll_feedback
+                n = self._check(fn(self.h, buf, lv, sv, cv, rv, fv, max_bursts))
+            elif rv is not None:
                 fn = self.L.vdl2gpu_poll_report_ready if ready else self.L.vdl2gpu_poll_report
                 n = self._check(fn(self.h, buf, lv, sv, cv, rv, max_bursts))
             elif cv is not None:
@@ -246,7 +254,8 @@ class Receiver:
                                  b.trig_sample, b.end_sample, bytes(b.data), Level.from_c(lv[i]) if lv is not None else None,
                                  np.frombuffer(bytes(sv[i].rel), np.uint8).reshape(8, 255).copy() if sv is not None else None,
                                  Carrier.from_c(cv[i]) if cv is not None else None,
-                                 BlockReport.from_c(rv[i]) if rv is not None else None))
+                                 BlockReport.from_c(rv[i]) if rv is not None else None,
+                                 np.frombuffer(bytes(fv[i].data), np.uint8).reshape(8, 255).copy() if fv is not None else None))
             if n < max_bursts:
                 return out
 
@@ -280,6 +289,12 @@ class Receiver:
         fn = self.L.vdl2gpu_poll_report_ready if ready else self.L.vdl2gpu_poll_report
         return self._check(fn(self.h, buf, lv, sv, cv, rv, max_bursts))
 
+    def poll_feedback_raw(self, buf, lv, sv, cv, rv, fv, max_bursts: int, ready: bool = False) -> int:
+        """vdl2gpu_poll_feedback(_ready) into caller-owned (lib.BurstT / LevelT / SoftT / CarrierT / BlockRepT / FbT * n) arrays; lv, sv, cv,
+        rv and fv may each be None."""
+        fn = self.L.vdl2gpu_poll_feedback_ready if ready else self.L.vdl2gpu_poll_feedback
+        return self._check(fn(self.h, buf, lv, sv, cv, rv, fv, max_bursts))
+
     def poll_ready_raw(self, buf, max_bursts: int) -> int:
         """vdl2gpu_poll_ready: bursts of pushes that have already finished; never waits."""
         return self._check(self.L.vdl2gpu_poll_ready(self.h, buf, max_bursts))
@@ -304,12 +319,14 @@ class Receiver:
         return out
 
     # ------------------------------------------------------------------ block path
-    def decode_blocks(self, blocks: Sequence, max_frames: int = 0, soft=None, report: bool = False):
+    def decode_blocks(self, blocks: Sequence, max_frames: int = 0, soft=None, report: bool = False, fb=None):
         """blk_thread for a batch (vdlm2.c:84-161): (index of the block, hdata) of every frame the
         reference would pass to out().  ``blocks``: Burst objects or (nbrow, nlbyte, data) tuples.
         ``soft``: one (8, 255) uint8 reliability map per block (Burst.soft): the soft row rule of include/vdl2gpu.h
         (vdl2gpu_decode_blocks_soft); None: the reference's block path.
-        ``report``: return (frames, [BlockReport of every block]) (vdl2gpu_decode_blocks_report), on any handle."""
+        ``report``: return (frames, [BlockReport of every block]) (vdl2gpu_decode_blocks_report), on any handle.
+        ``fb``: one (8, 255) uint8 array of decision-feedback rows per block (Burst.fb): a row the reference cannot decode is taken from
+        them if it decodes there (vdl2gpu_decode_blocks_feedback), on any handle; None: not."""
         n = len(blocks)
         if n == 0:
             return ([], []) if report else []
@@ -331,9 +348,21 @@ class Receiver:
             for i, m in enumerate(soft):
                 m = np.ascontiguousarray(m, np.uint8).reshape(8, 255)
                 C.memmove(C.addressof(sarr[i].rel), m.ctypes.data, 8 * 255)
+        farr = None
+        if fb is not None:
+            if len(fb) != n:
+                raise ValueError("one set of feedback rows per block")
+            farr = (_lib.FbT * n)()
+            for i, m in enumerate(fb):
+                m = np.ascontiguousarray(m, np.uint8).reshape(8, 255)
+                C.memmove(C.addressof(farr[i].data), m.ctypes.data, 8 * 255)
         rarr = (_lib.BlockRepT * n)() if report else None
-        # (soft NULL: hard mode; rep NULL: exactly vdl2gpu_decode_blocks_soft, and with both exactly vdl2gpu_decode_blocks)
-        nf = self._check(self.L.vdl2gpu_decode_blocks_report(self.h, arr, sarr, n, out, cap, C.byref(dropped), rarr))
+        # (soft NULL: hard mode; rep NULL: exactly vdl2gpu_decode_blocks_soft, and with both exactly vdl2gpu_decode_blocks; fb NULL: the
+        # library's vdl2gpu_decode_blocks_report, which the older calls go through as well)
+        if farr is None:
+            nf = self._check(self.L.vdl2gpu_decode_blocks_report(self.h, arr, sarr, n, out, cap, C.byref(dropped), rarr))
+        else:
+            nf = self._check(self.L.vdl2gpu_decode_blocks_feedback(self.h, arr, sarr, farr, n, out, cap, C.byref(dropped), rarr))
         if dropped.value:
             raise _lib.Vdl2GpuError(f"{dropped.value} frames dropped: raise max_frames")
         frames = [(out[i].block, bytes(out[i].data[:out[i].len])) for i in range(nf)]

@@ -30,6 +30,8 @@ F_CARRIER = 1024
 F_BLOCK_REPORT = 2048
 # vdl2gpu_blockrep_t.row_how (VDL2GPU_ROW_*)
 ROW_NONE, ROW_CLEAN, ROW_REF, ROW_SOFT2, ROW_SOFT4, ROW_FAIL = range(6)
+ROW_FEEDBACK = 6    # (VDL2GPU_F_FEEDBACK) the record's decision-feedback row replaced the row
+F_FEEDBACK = 4096
 # status of a cluster head (vdl2gpu_debug_clheads()'s packed word: cl_pack() in csrc/vdl2gpu_types.h)
 CL_STEADY, CL_DEFER_FIRST, CL_NONSTEADY = 0, 1, 2
 
@@ -44,8 +46,8 @@ def cl_unpack(packed):
 EXPORTS = (
     "vdl2gpu_abi_version", "vdl2gpu_create", "vdl2gpu_destroy", "vdl2gpu_push", "vdl2gpu_sync",
     "vdl2gpu_ring_init", "vdl2gpu_ring_acquire", "vdl2gpu_ring_commit",
-    "vdl2gpu_poll", "vdl2gpu_poll_ready", "vdl2gpu_poll_levels", "vdl2gpu_poll_levels_ready", "vdl2gpu_poll_soft", "vdl2gpu_poll_soft_ready", "vdl2gpu_poll_carrier", "vdl2gpu_poll_carrier_ready", "vdl2gpu_poll_report", "vdl2gpu_poll_report_ready", "vdl2gpu_pending", "vdl2gpu_inflight", "vdl2gpu_get_stats", "vdl2gpu_get_timing", "vdl2gpu_get_host_profile", "vdl2gpu_last_error",
-    "vdl2gpu_strerror", "vdl2gpu_burst_to_msgblk", "vdl2gpu_decode_blocks", "vdl2gpu_decode_blocks_soft", "vdl2gpu_decode_blocks_report", "vdl2gpu_poll_frames", "vdl2gpu_poll_frames_ready", "reversebits", "vdl2gpu_lo_len", "vdl2gpu_lo_table", "vdl2gpu_plan",
+    "vdl2gpu_poll", "vdl2gpu_poll_ready", "vdl2gpu_poll_levels", "vdl2gpu_poll_levels_ready", "vdl2gpu_poll_soft", "vdl2gpu_poll_soft_ready", "vdl2gpu_poll_carrier", "vdl2gpu_poll_carrier_ready", "vdl2gpu_poll_report", "vdl2gpu_poll_report_ready", "vdl2gpu_poll_feedback", "vdl2gpu_poll_feedback_ready", "vdl2gpu_pending", "vdl2gpu_inflight", "vdl2gpu_get_stats", "vdl2gpu_get_timing", "vdl2gpu_get_host_profile", "vdl2gpu_last_error",
+    "vdl2gpu_strerror", "vdl2gpu_burst_to_msgblk", "vdl2gpu_decode_blocks", "vdl2gpu_decode_blocks_soft", "vdl2gpu_decode_blocks_report", "vdl2gpu_decode_blocks_feedback", "vdl2gpu_poll_frames", "vdl2gpu_poll_frames_ready", "reversebits", "vdl2gpu_lo_len", "vdl2gpu_lo_table", "vdl2gpu_plan",
     "vdl2gpu_exact_fo_tables", "vdl2gpu_exact_fo_index", "vdl2gpu_carrier_from_sums",
     "vdl2gpu_choose_fc_rtl", "vdl2gpu_choose_fc_air",
     "vdl2gpu_debug_dec", "vdl2gpu_debug_k1", "vdl2gpu_debug_lo", "vdl2gpu_debug_atan2f", "vdl2gpu_debug_rs", "vdl2gpu_debug_counters", "vdl2gpu_debug_cands", "vdl2gpu_debug_clheads", "vdl2gpu_debug_fail", "vdl2gpu_debug_segs", "vdl2gpu_debug_heads",
@@ -96,6 +98,12 @@ class BlockRepT(C.Structure):
                 ("bytes_changed", C.c_uint16), ("rows_failed", C.c_uint16), ("rows_rescued", C.c_uint16), ("stuffed", C.c_uint16),
                 ("nbytes", C.c_uint16), ("flag_at", C.c_int16), ("cand", C.c_uint16), ("too_short", C.c_uint16),
                 ("bad_fcs", C.c_uint16), ("frames", C.c_uint16), ("status", C.c_int32)]
+
+
+class FbT(C.Structure):
+    """vdl2gpu_fb_t (VDL2GPU_F_FEEDBACK): 2048 bytes, the rows of the burst sliced a second time with decision feedback, laid out as the
+    record's data[] (include/vdl2gpu.h)."""
+    _fields_ = [("data", (C.c_uint8 * 255) * 8), ("reserved", C.c_uint8 * 8)]
 
 
 class FrameT(C.Structure):
@@ -185,6 +193,10 @@ def load(testhooks: bool = False):
     L.vdl2gpu_poll_report.argtypes = [C.c_void_p, C.POINTER(BurstT), C.POINTER(LevelT), C.POINTER(SoftT), C.POINTER(CarrierT), C.POINTER(BlockRepT), C.c_int]
     L.vdl2gpu_poll_report_ready.restype = C.c_int
     L.vdl2gpu_poll_report_ready.argtypes = [C.c_void_p, C.POINTER(BurstT), C.POINTER(LevelT), C.POINTER(SoftT), C.POINTER(CarrierT), C.POINTER(BlockRepT), C.c_int]
+    L.vdl2gpu_poll_feedback.restype = C.c_int
+    L.vdl2gpu_poll_feedback.argtypes = [C.c_void_p, C.POINTER(BurstT), C.POINTER(LevelT), C.POINTER(SoftT), C.POINTER(CarrierT), C.POINTER(BlockRepT), C.POINTER(FbT), C.c_int]
+    L.vdl2gpu_poll_feedback_ready.restype = C.c_int
+    L.vdl2gpu_poll_feedback_ready.argtypes = [C.c_void_p, C.POINTER(BurstT), C.POINTER(LevelT), C.POINTER(SoftT), C.POINTER(CarrierT), C.POINTER(BlockRepT), C.POINTER(FbT), C.c_int]
     L.vdl2gpu_carrier_from_sums.restype = C.c_int
     L.vdl2gpu_carrier_from_sums.argtypes = [C.c_float, C.c_int, C.c_int, C.c_int, C.c_uint, C.POINTER(CarrierT)]
     L.vdl2gpu_get_stats.restype = C.c_int
@@ -208,6 +220,9 @@ def load(testhooks: bool = False):
     L.vdl2gpu_decode_blocks_report.restype = C.c_int
     L.vdl2gpu_decode_blocks_report.argtypes = [C.c_void_p, C.POINTER(BurstT), C.POINTER(SoftT), C.c_int, C.POINTER(FrameT), C.c_int,
                                                C.POINTER(C.c_int), C.POINTER(BlockRepT)]
+    L.vdl2gpu_decode_blocks_feedback.restype = C.c_int
+    L.vdl2gpu_decode_blocks_feedback.argtypes = [C.c_void_p, C.POINTER(BurstT), C.POINTER(SoftT), C.POINTER(FbT), C.c_int, C.POINTER(FrameT), C.c_int,
+                                                 C.POINTER(C.c_int), C.POINTER(BlockRepT)]
     L.vdl2gpu_poll_frames.restype = C.c_int
     L.vdl2gpu_poll_frames.argtypes = [C.c_void_p, C.POINTER(FrameT), C.c_int]
     L.vdl2gpu_poll_frames_ready.restype = C.c_int
