@@ -93,9 +93,16 @@ struct LaterEvent {
 };
 
 /* A burst record has side columns: entries at the record's index in the device rings, the slabs and the host queue, present when
- * the handle's flags ask for them.  A column is one row here and its flag in create_impl. */
-enum { COL_SOFT, COL_LEVEL, COL_CARRIER, COL_REPORT, COL_FB, VDL2_NCOL };	/* VDL2GPU_F_SOFT_RS: a reliability map (2048 bytes); VDL2GPU_F_LEVELS: a level record; VDL2GPU_F_CARRIER: a carrier record; VDL2GPU_F_BLOCK_REPORT: a block report; VDL2GPU_F_FEEDBACK: decision-feedback rows (2048 bytes) */
-static const size_t col_bytes[VDL2_NCOL] = { sizeof(vdl2gpu_soft_t), sizeof(vdl2gpu_level_t), sizeof(vdl2gpu_carrier_t), sizeof(vdl2gpu_blockrep_t), sizeof(vdl2gpu_fb_t) };
+ * the handle's flags ask for them.  A column is a name in the enum and a row of each of the two tables here. */
+enum { COL_LEVEL, COL_SOFT, COL_CARRIER, COL_REPORT, COL_FB, VDL2_NCOL };	/* (the order of the collectors' arguments: poll_impl) */
+static const size_t col_bytes[VDL2_NCOL] = { sizeof(vdl2gpu_level_t), sizeof(vdl2gpu_soft_t), sizeof(vdl2gpu_carrier_t), sizeof(vdl2gpu_blockrep_t), sizeof(vdl2gpu_fb_t) };
+static const struct { unsigned flag; const char *flag_name, *arg; } col_info[VDL2_NCOL] = {	/* arg: what the collectors' error texts call the column */
+	{ VDL2GPU_F_LEVELS, "VDL2GPU_F_LEVELS", "lv" },			/* a level record */
+	{ VDL2GPU_F_SOFT_RS, "VDL2GPU_F_SOFT_RS", "soft" },		/* a reliability map (2048 bytes) */
+	{ VDL2GPU_F_CARRIER, "VDL2GPU_F_CARRIER", "car" },		/* a carrier record */
+	{ VDL2GPU_F_BLOCK_REPORT, "VDL2GPU_F_BLOCK_REPORT", "rep" },	/* a block report (vdl2gpu_create: only with VDL2GPU_F_FRAMES) */
+	{ VDL2GPU_F_FEEDBACK, "VDL2GPU_F_FEEDBACK", "fb" },		/* decision-feedback rows (2048 bytes; with or without VDL2GPU_F_FRAMES) */
+};
 
 /* A table set (push % VDL2_NSET): what a push's demodulator kernels work in, see alloc_sets. */
 struct TableSet {
@@ -123,11 +130,7 @@ struct OutRing {
 	int slab = 0;			/* the slab its records were exported to */
 	bool spec = false;		/* its K2d ran ahead of verify: honour the redo mask */
 	hipEvent_t done() const { return done2[ev]; }
-	vdl2gpu_level_t *levels() const { return static_cast<vdl2gpu_level_t *>(d_side[COL_LEVEL]); }
-	vdl2gpu_soft_t *soft() const { return static_cast<vdl2gpu_soft_t *>(d_side[COL_SOFT]); }
-	vdl2gpu_carrier_t *carrier() const { return static_cast<vdl2gpu_carrier_t *>(d_side[COL_CARRIER]); }
-	vdl2gpu_blockrep_t *report() const { return static_cast<vdl2gpu_blockrep_t *>(d_side[COL_REPORT]); }
-	vdl2gpu_fb_t *fb() const { return static_cast<vdl2gpu_fb_t *>(d_side[COL_FB]); }
+	template <class T> T *col(int k) const { return static_cast<T *>(d_side[k]); }	/* (nullptr: the handle has no column k) */
 };
 
 /* A slab (push % VDL2_NSLAB) of page-locked host memory, which the GPU itself fills at the end of the push (k_export_records), and
@@ -138,11 +141,7 @@ struct Slab {
 	uint8_t *h_side[VDL2_NCOL] = {};
 	void *d_side[VDL2_NCOL] = {};
 	size_t lo = 0, hi = 0;	/* ready_idx[lo, hi): where the handles into the slab lie (a push's are contiguous) */
-	vdl2gpu_level_t *d_levels() const { return static_cast<vdl2gpu_level_t *>(d_side[COL_LEVEL]); }
-	vdl2gpu_soft_t *d_soft() const { return static_cast<vdl2gpu_soft_t *>(d_side[COL_SOFT]); }
-	vdl2gpu_carrier_t *d_carrier() const { return static_cast<vdl2gpu_carrier_t *>(d_side[COL_CARRIER]); }
-	vdl2gpu_blockrep_t *d_report() const { return static_cast<vdl2gpu_blockrep_t *>(d_side[COL_REPORT]); }
-	vdl2gpu_fb_t *d_fb() const { return static_cast<vdl2gpu_fb_t *>(d_side[COL_FB]); }
+	template <class T> T *col(int k) const { return static_cast<T *>(d_side[k]); }
 };
 
 /* Records in pageable storage, with their side columns (byte vectors: col_bytes[k] a record). */
@@ -1006,11 +1005,8 @@ static int create_impl(vdl2gpu_t *h)
 	h->slab_cap = std::max(1u, std::min<unsigned>(h->slab_cap, (unsigned)env_int("VDL2GPU_SLAB_CAP", (int)h->slab_cap)));	/* (tests: force the bounce path) */
 #endif
 	/* the output rings and the slabs: the records, and beside them the side columns the flags ask for */
-	h->col_on[COL_LEVEL] = (cfg.flags & VDL2GPU_F_LEVELS) != 0;
-	h->col_on[COL_SOFT] = (cfg.flags & VDL2GPU_F_SOFT_RS) != 0;
-	h->col_on[COL_CARRIER] = (cfg.flags & VDL2GPU_F_CARRIER) != 0;
-	h->col_on[COL_REPORT] = (cfg.flags & VDL2GPU_F_BLOCK_REPORT) != 0;	/* (vdl2gpu_create: only with VDL2GPU_F_FRAMES) */
-	h->col_on[COL_FB] = (cfg.flags & VDL2GPU_F_FEEDBACK) != 0;	/* (with or without VDL2GPU_F_FRAMES) */
+	for (int k = 0; k < VDL2_NCOL; ++k)
+		h->col_on[k] = (cfg.flags & col_info[k].flag) != 0;
 	h->frames_on = (cfg.flags & VDL2GPU_F_FRAMES) != 0;
 	if (h->frames_on) {
 		unsigned arena = 4u << 20;
@@ -1432,23 +1428,31 @@ static void launch_clusters(const vdl2gpu_t *h, hipStream_t s, const K2Params &k
 
 /* The payload kernel of the handle's flags (each optional pass is a kernel variant of its own: register pressure) on the
  * selection `sel_mode` names (K2Params.sel_mode).  ring: the output ring k2.recs lies in; with VDL2GPU_F_FEEDBACK its feedback rows are
- * the kernel's second argument (they are no member of K2Params: vdl2gpu_resolve.h, k2d_run). */
+ * the kernel's second argument (they are no member of K2Params: vdl2gpu_resolve.h, k2d_run).  The two tables -- the eight kernels
+ * without the feedback pass, the eight with it -- are filled from K2D_PAYLOAD_KERNELS, each kernel where K2D_INDEX of its own line's
+ * flags says, and asked with K2D_INDEX of the handle's: no order to keep in step by hand. */
 enum { SEL_FIRST = 0, SEL_REPAIRED = 1, SEL_FINAL = 2 };
+struct PayloadKernels {
+	void (*fb0[8])(K2Params);
+	void (*fb1[8])(K2Params, vdl2gpu_fb_t *);
+	PayloadKernels()
+	{
+#define K2D_ENTER(name, waves, LEV, SOFT, CAR, FB) fb##FB[K2D_INDEX(LEV, SOFT, CAR, 0)] = name;
+		K2D_PAYLOAD_KERNELS(K2D_ENTER)
+#undef K2D_ENTER
+	}
+};
 static void launch_payload(const vdl2gpu_t *h, hipStream_t s, const K2Params &k2, int sel_mode, int ring)
 {
-	static void (*const kernels[8])(K2Params) = { k2d_payload, k2d_payload_lev, k2d_payload_soft, k2d_payload_lev_soft,
-						     k2d_payload_car, k2d_payload_lev_car, k2d_payload_soft_car, k2d_payload_lev_soft_car };
-	/* VDL2GPU_F_FEEDBACK: the same eight with the feedback pass behind them; the rows' ring is their second argument */
-	static void (*const kernels_fb[8])(K2Params, vdl2gpu_fb_t *) = { k2d_payload_fb, k2d_payload_lev_fb, k2d_payload_soft_fb, k2d_payload_lev_soft_fb,
-									  k2d_payload_car_fb, k2d_payload_lev_car_fb, k2d_payload_soft_car_fb, k2d_payload_lev_soft_car_fb };
-	const int which = (h->col_on[COL_LEVEL] ? 1 : 0) | (h->col_on[COL_SOFT] ? 2 : 0) | (h->col_on[COL_CARRIER] ? 4 : 0);
+	static const PayloadKernels kernels;
+	const int which = K2D_INDEX(h->col_on[COL_LEVEL] ? 1 : 0, h->col_on[COL_SOFT] ? 1 : 0, h->col_on[COL_CARRIER] ? 1 : 0, 0);
 	K2Params q = k2;
 	q.sel_mode = sel_mode;
 	const dim3 grid((unsigned)h->k2d_grid, (unsigned)(VDL2_CS * h->S));
 	if (h->col_on[COL_FB])
-		hipLaunchKernelGGL(kernels_fb[which], grid, dim3(K2D_NT), 0, s, q, h->ring[ring].fb());
+		hipLaunchKernelGGL(kernels.fb1[which], grid, dim3(K2D_NT), 0, s, q, h->ring[ring].col<vdl2gpu_fb_t>(COL_FB));
 	else
-		hipLaunchKernelGGL(kernels[which], grid, dim3(K2D_NT), 0, s, q);
+		hipLaunchKernelGGL(kernels.fb0[which], grid, dim3(K2D_NT), 0, s, q);
 }
 
 /* tiles' worth of items a verify workgroup's private area is sized for: its share q of the pieces (k2a_verify) when a launch of
@@ -1618,9 +1622,9 @@ static K4Params k4_ring_params(vdl2gpu_t *h, int ring, const unsigned *fmask)
 	k4.compact = 1;
 	k4.tabs = h->d_k4tab;
 	k4.fmask = fmask;
-	k4.soft = h->ring[ring].soft();	/* (nullptr without VDL2GPU_F_SOFT_RS: the reference's block path) */
-	k4.rep = h->ring[ring].report();	/* (nullptr without VDL2GPU_F_BLOCK_REPORT, and k4_frames is launched, which does not look at it) */
-	k4.fb = h->ring[ring].fb();	/* (nullptr without VDL2GPU_F_FEEDBACK: launch_blocks) */
+	k4.soft = h->ring[ring].col<vdl2gpu_soft_t>(COL_SOFT);	/* (nullptr without VDL2GPU_F_SOFT_RS: the reference's block path) */
+	k4.rep = h->ring[ring].col<vdl2gpu_blockrep_t>(COL_REPORT);	/* (nullptr without VDL2GPU_F_BLOCK_REPORT, and k4_frames is launched, which does not look at it) */
+	k4.fb = h->ring[ring].col<vdl2gpu_fb_t>(COL_FB);	/* (nullptr without VDL2GPU_F_FEEDBACK: launch_blocks) */
 	return k4;
 }
 
@@ -1759,7 +1763,7 @@ static int enqueue_back(vdl2gpu_t *h)
 	}
 	TRY(mark(h, pt, E_ROUNDS_END, ts));
 	if (h->col_on[COL_FB])
-		launch_per_channel(h, k2f_commit_fb, K2_NT, ts, k2, vdrain, h->ring[ring].fb());
+		launch_per_channel(h, k2f_commit_fb, K2_NT, ts, k2, vdrain, h->ring[ring].col<vdl2gpu_fb_t>(COL_FB));
 	else
 		launch_per_channel(h, k2f_commit, K2_NT, ts, k2, vdrain);
 
@@ -1789,19 +1793,21 @@ static int enqueue_back(vdl2gpu_t *h)
 		ke.count = h->d_outc + 2 * ring;
 		ke.dst = h->slab[h->back.slab].d_recs;
 		ke.cap = std::min(h->slab_cap, h->rec_cap);
-		ke.lev = h->ring[ring].levels();	/* (nullptr without VDL2GPU_F_LEVELS) */
-		ke.ldst = h->slab[h->back.slab].d_levels();
-		ke.soft = h->ring[ring].soft();	/* (nullptr without VDL2GPU_F_SOFT_RS) */
-		ke.sdst = h->slab[h->back.slab].d_soft();
-		ke.car = h->ring[ring].carrier();	/* (nullptr without VDL2GPU_F_CARRIER) */
-		ke.cdst = h->slab[h->back.slab].d_carrier();
-		ke.rep = h->ring[ring].report();	/* (nullptr without VDL2GPU_F_BLOCK_REPORT) */
-		ke.rdst = h->slab[h->back.slab].d_report();
+		const OutRing &rg = h->ring[ring];
+		const Slab &sl = h->slab[h->back.slab];
+		ke.lev = rg.col<vdl2gpu_level_t>(COL_LEVEL);	/* (nullptr without VDL2GPU_F_LEVELS) */
+		ke.ldst = sl.col<vdl2gpu_level_t>(COL_LEVEL);
+		ke.soft = rg.col<vdl2gpu_soft_t>(COL_SOFT);	/* (nullptr without VDL2GPU_F_SOFT_RS) */
+		ke.sdst = sl.col<vdl2gpu_soft_t>(COL_SOFT);
+		ke.car = rg.col<vdl2gpu_carrier_t>(COL_CARRIER);	/* (nullptr without VDL2GPU_F_CARRIER) */
+		ke.cdst = sl.col<vdl2gpu_carrier_t>(COL_CARRIER);
+		ke.rep = rg.col<vdl2gpu_blockrep_t>(COL_REPORT);	/* (nullptr without VDL2GPU_F_BLOCK_REPORT) */
+		ke.rdst = sl.col<vdl2gpu_blockrep_t>(COL_REPORT);
 		hipLaunchKernelGGL(k_export_records, dim3((unsigned)h->n_cu), dim3(256), 0, ts, ke);
 		HIPCHK(h, hipGetLastError());
 		if (h->col_on[COL_FB]) {	/* the feedback rows beside them: a kernel of its own, k_export_records keeps its registers */
 			hipLaunchKernelGGL(k_export_feedback, dim3((unsigned)h->n_cu), dim3(256), 0, ts, ke.count, ke.cap,
-					   static_cast<const vdl2gpu_fb_t *>(h->ring[ring].fb()), h->slab[h->back.slab].d_fb());
+					   rg.col<const vdl2gpu_fb_t>(COL_FB), sl.col<vdl2gpu_fb_t>(COL_FB));
 			HIPCHK(h, hipGetLastError());
 		}
 		TRY(mark(h, pt, E_EXPORT_END, ts, true));
@@ -2138,9 +2144,9 @@ static int enqueue_front(vdl2gpu_t *h, hipStream_t fs, long long dec_base, PushT
 	K2Params k2 = set.k2;	/* the set's tables and everything that never changes (fill_set_params); what follows is this push's */
 	k2.J = J;
 	k2.recs = h->ring[ring].d_recs;
-	k2.levels = h->ring[ring].levels();	/* (nullptr without VDL2GPU_F_LEVELS: nothing is measured) */
-	k2.soft = h->ring[ring].soft();	/* (nullptr without VDL2GPU_F_SOFT_RS) */
-	k2.carrier = h->ring[ring].carrier();	/* (nullptr without VDL2GPU_F_CARRIER) */
+	k2.levels = h->ring[ring].col<vdl2gpu_level_t>(COL_LEVEL);	/* (nullptr without VDL2GPU_F_LEVELS: nothing is measured) */
+	k2.soft = h->ring[ring].col<vdl2gpu_soft_t>(COL_SOFT);	/* (nullptr without VDL2GPU_F_SOFT_RS) */
+	k2.carrier = h->ring[ring].col<vdl2gpu_carrier_t>(COL_CARRIER);	/* (nullptr without VDL2GPU_F_CARRIER) */
 	k2.outc = h->d_outc + 2 * ring;
 	k2.dec_base = dec_base;
 	k2.scan_lo = dec_base + VDL2_HIST;	/* the scan starts at the first carried frame that has its history */
@@ -2943,105 +2949,43 @@ extern "C" int vdl2gpu_inflight(vdl2gpu_t *h)
 	return n;
 }
 
-/* The twelve collectors.  lv / sv / cv / rv / fv: the side columns the caller wants beside the records (nullptr: not); lv_err / sv_err /
- * cv_err / rv_err / fv_err: what the entry point says when the handle was made without that column. */
-static int poll_impl(vdl2gpu_t *h, vdl2gpu_burst_t *out, vdl2gpu_level_t *lv, vdl2gpu_soft_t *sv, int max, bool blocking,
-		     const char *lv_err = nullptr, const char *sv_err = nullptr, vdl2gpu_carrier_t *cv = nullptr, const char *cv_err = nullptr,
-		     vdl2gpu_blockrep_t *rv = nullptr, const char *rv_err = nullptr, vdl2gpu_fb_t *fv = nullptr, const char *fv_err = nullptr)
+/* The twelve collectors.  side.p[k]: where the caller wants column k beside the records (nullptr: not).  who: the entry point as the
+ * error texts name it.  When the handle was made without a column that is asked for, the first such column in the order of the
+ * arguments is named: "who: arg needs FLAG" (named = false, the two collectors with one column: "who needs FLAG"). */
+struct PollCols {
+	void *p[VDL2_NCOL];
+};
+static int poll_impl(vdl2gpu_t *h, vdl2gpu_burst_t *out, int max, const PollCols &side, bool blocking, const char *who, bool named = true)
 {
 	if (!h || (max > 0 && !out) || max < 0)
 		return VDL2GPU_EINVAL;
 	HLOCK(h);
-	if ((lv && !h->col_on[COL_LEVEL]) || (sv && !h->col_on[COL_SOFT]) || (cv && !h->col_on[COL_CARRIER]) || (rv && !h->col_on[COL_REPORT]) ||
-	    (fv && !h->col_on[COL_FB])) {
-		h->err = lv && !h->col_on[COL_LEVEL] ? lv_err : (sv && !h->col_on[COL_SOFT] ? sv_err : (cv && !h->col_on[COL_CARRIER] ? cv_err :
-			 (rv && !h->col_on[COL_REPORT] ? rv_err : fv_err)));
-		return VDL2GPU_EINVAL;
-	}
+	for (int k = 0; k < VDL2_NCOL; ++k)
+		if (side.p[k] && !h->col_on[k]) {
+			h->err = std::string(who) + (named ? std::string(": ") + col_info[k].arg : std::string()) + " needs " + col_info[k].flag_name;
+			return VDL2GPU_EINVAL;
+		}
 	if (h->failed)
 		return VDL2GPU_EHIP;
 	HIPCHK(h, hipSetDevice(h->cfg.device));
 	int rc = blocking ? wait_harvest(h, hlock_) : harvest_all(h, false);
 	if (rc)
 		return rc;
-	void *side[VDL2_NCOL] = {};
-	side[COL_LEVEL] = lv;
-	side[COL_SOFT] = sv;
-	side[COL_CARRIER] = cv;
-	side[COL_REPORT] = rv;
-	side[COL_FB] = fv;
-	return hand_out(h, out, max, side);
+	return hand_out(h, out, max, side.p);
 }
 
-extern "C" int vdl2gpu_poll(vdl2gpu_t *h, vdl2gpu_burst_t *out, int max)
-{
-	return poll_impl(h, out, nullptr, nullptr, max, true);
-}
-
-extern "C" int vdl2gpu_poll_ready(vdl2gpu_t *h, vdl2gpu_burst_t *out, int max)
-{
-	return poll_impl(h, out, nullptr, nullptr, max, false);
-}
-
-extern "C" int vdl2gpu_poll_levels(vdl2gpu_t *h, vdl2gpu_burst_t *out, vdl2gpu_level_t *lv, int max)
-{
-	return poll_impl(h, out, lv, nullptr, max, true, "vdl2gpu_poll_levels needs VDL2GPU_F_LEVELS");	/* (lv = NULL: vdl2gpu_poll) */
-}
-
-extern "C" int vdl2gpu_poll_levels_ready(vdl2gpu_t *h, vdl2gpu_burst_t *out, vdl2gpu_level_t *lv, int max)
-{
-	return poll_impl(h, out, lv, nullptr, max, false, "vdl2gpu_poll_levels_ready needs VDL2GPU_F_LEVELS");
-}
-
-extern "C" int vdl2gpu_poll_soft(vdl2gpu_t *h, vdl2gpu_burst_t *out, vdl2gpu_level_t *lv, vdl2gpu_soft_t *soft, int max)
-{
-	return poll_impl(h, out, lv, soft, max, true, "vdl2gpu_poll_soft: lv needs VDL2GPU_F_LEVELS", "vdl2gpu_poll_soft: soft needs VDL2GPU_F_SOFT_RS");
-}
-
-extern "C" int vdl2gpu_poll_soft_ready(vdl2gpu_t *h, vdl2gpu_burst_t *out, vdl2gpu_level_t *lv, vdl2gpu_soft_t *soft, int max)
-{
-	return poll_impl(h, out, lv, soft, max, false, "vdl2gpu_poll_soft: lv needs VDL2GPU_F_LEVELS", "vdl2gpu_poll_soft: soft needs VDL2GPU_F_SOFT_RS");
-}
-
-extern "C" int vdl2gpu_poll_carrier(vdl2gpu_t *h, vdl2gpu_burst_t *out, vdl2gpu_level_t *lv, vdl2gpu_soft_t *soft, vdl2gpu_carrier_t *car, int max)
-{
-	return poll_impl(h, out, lv, soft, max, true, "vdl2gpu_poll_carrier: lv needs VDL2GPU_F_LEVELS", "vdl2gpu_poll_carrier: soft needs VDL2GPU_F_SOFT_RS",
-			 car, "vdl2gpu_poll_carrier: car needs VDL2GPU_F_CARRIER");
-}
-
-extern "C" int vdl2gpu_poll_carrier_ready(vdl2gpu_t *h, vdl2gpu_burst_t *out, vdl2gpu_level_t *lv, vdl2gpu_soft_t *soft, vdl2gpu_carrier_t *car, int max)
-{
-	return poll_impl(h, out, lv, soft, max, false, "vdl2gpu_poll_carrier: lv needs VDL2GPU_F_LEVELS", "vdl2gpu_poll_carrier: soft needs VDL2GPU_F_SOFT_RS",
-			 car, "vdl2gpu_poll_carrier: car needs VDL2GPU_F_CARRIER");
-}
-
-extern "C" int vdl2gpu_poll_report(vdl2gpu_t *h, vdl2gpu_burst_t *out, vdl2gpu_level_t *lv, vdl2gpu_soft_t *soft, vdl2gpu_carrier_t *car, vdl2gpu_blockrep_t *rep, int max)
-{
-	return poll_impl(h, out, lv, soft, max, true, "vdl2gpu_poll_report: lv needs VDL2GPU_F_LEVELS", "vdl2gpu_poll_report: soft needs VDL2GPU_F_SOFT_RS",
-			 car, "vdl2gpu_poll_report: car needs VDL2GPU_F_CARRIER", rep, "vdl2gpu_poll_report: rep needs VDL2GPU_F_BLOCK_REPORT");
-}
-
-extern "C" int vdl2gpu_poll_report_ready(vdl2gpu_t *h, vdl2gpu_burst_t *out, vdl2gpu_level_t *lv, vdl2gpu_soft_t *soft, vdl2gpu_carrier_t *car, vdl2gpu_blockrep_t *rep, int max)
-{
-	return poll_impl(h, out, lv, soft, max, false, "vdl2gpu_poll_report: lv needs VDL2GPU_F_LEVELS", "vdl2gpu_poll_report: soft needs VDL2GPU_F_SOFT_RS",
-			 car, "vdl2gpu_poll_report: car needs VDL2GPU_F_CARRIER", rep, "vdl2gpu_poll_report: rep needs VDL2GPU_F_BLOCK_REPORT");
-}
-
-extern "C" int vdl2gpu_poll_feedback(vdl2gpu_t *h, vdl2gpu_burst_t *out, vdl2gpu_level_t *lv, vdl2gpu_soft_t *soft, vdl2gpu_carrier_t *car, vdl2gpu_blockrep_t *rep,
-				     vdl2gpu_fb_t *fb, int max)
-{
-	return poll_impl(h, out, lv, soft, max, true, "vdl2gpu_poll_feedback: lv needs VDL2GPU_F_LEVELS", "vdl2gpu_poll_feedback: soft needs VDL2GPU_F_SOFT_RS",
-			 car, "vdl2gpu_poll_feedback: car needs VDL2GPU_F_CARRIER", rep, "vdl2gpu_poll_feedback: rep needs VDL2GPU_F_BLOCK_REPORT",
-			 fb, "vdl2gpu_poll_feedback: fb needs VDL2GPU_F_FEEDBACK");
-}
-
-extern "C" int vdl2gpu_poll_feedback_ready(vdl2gpu_t *h, vdl2gpu_burst_t *out, vdl2gpu_level_t *lv, vdl2gpu_soft_t *soft, vdl2gpu_carrier_t *car,
-					   vdl2gpu_blockrep_t *rep, vdl2gpu_fb_t *fb, int max)
-{
-	return poll_impl(h, out, lv, soft, max, false, "vdl2gpu_poll_feedback: lv needs VDL2GPU_F_LEVELS", "vdl2gpu_poll_feedback: soft needs VDL2GPU_F_SOFT_RS",
-			 car, "vdl2gpu_poll_feedback: car needs VDL2GPU_F_CARRIER", rep, "vdl2gpu_poll_feedback: rep needs VDL2GPU_F_BLOCK_REPORT",
-			 fb, "vdl2gpu_poll_feedback: fb needs VDL2GPU_F_FEEDBACK");
-}
+extern "C" int vdl2gpu_poll(vdl2gpu_t *h, vdl2gpu_burst_t *out, int max) { return poll_impl(h, out, max, {}, true, "vdl2gpu_poll"); }
+extern "C" int vdl2gpu_poll_ready(vdl2gpu_t *h, vdl2gpu_burst_t *out, int max) { return poll_impl(h, out, max, {}, false, "vdl2gpu_poll"); }
+extern "C" int vdl2gpu_poll_levels(vdl2gpu_t *h, vdl2gpu_burst_t *out, vdl2gpu_level_t *lv, int max) { return poll_impl(h, out, max, {{lv}}, true, "vdl2gpu_poll_levels", false); }	/* (lv = NULL: vdl2gpu_poll) */
+extern "C" int vdl2gpu_poll_levels_ready(vdl2gpu_t *h, vdl2gpu_burst_t *out, vdl2gpu_level_t *lv, int max) { return poll_impl(h, out, max, {{lv}}, false, "vdl2gpu_poll_levels_ready", false); }
+extern "C" int vdl2gpu_poll_soft(vdl2gpu_t *h, vdl2gpu_burst_t *out, vdl2gpu_level_t *lv, vdl2gpu_soft_t *soft, int max) { return poll_impl(h, out, max, {{lv, soft}}, true, "vdl2gpu_poll_soft"); }
+extern "C" int vdl2gpu_poll_soft_ready(vdl2gpu_t *h, vdl2gpu_burst_t *out, vdl2gpu_level_t *lv, vdl2gpu_soft_t *soft, int max) { return poll_impl(h, out, max, {{lv, soft}}, false, "vdl2gpu_poll_soft"); }
+extern "C" int vdl2gpu_poll_carrier(vdl2gpu_t *h, vdl2gpu_burst_t *out, vdl2gpu_level_t *lv, vdl2gpu_soft_t *soft, vdl2gpu_carrier_t *car, int max) { return poll_impl(h, out, max, {{lv, soft, car}}, true, "vdl2gpu_poll_carrier"); }
+extern "C" int vdl2gpu_poll_carrier_ready(vdl2gpu_t *h, vdl2gpu_burst_t *out, vdl2gpu_level_t *lv, vdl2gpu_soft_t *soft, vdl2gpu_carrier_t *car, int max) { return poll_impl(h, out, max, {{lv, soft, car}}, false, "vdl2gpu_poll_carrier"); }
+extern "C" int vdl2gpu_poll_report(vdl2gpu_t *h, vdl2gpu_burst_t *out, vdl2gpu_level_t *lv, vdl2gpu_soft_t *soft, vdl2gpu_carrier_t *car, vdl2gpu_blockrep_t *rep, int max) { return poll_impl(h, out, max, {{lv, soft, car, rep}}, true, "vdl2gpu_poll_report"); }
+extern "C" int vdl2gpu_poll_report_ready(vdl2gpu_t *h, vdl2gpu_burst_t *out, vdl2gpu_level_t *lv, vdl2gpu_soft_t *soft, vdl2gpu_carrier_t *car, vdl2gpu_blockrep_t *rep, int max) { return poll_impl(h, out, max, {{lv, soft, car, rep}}, false, "vdl2gpu_poll_report"); }
+extern "C" int vdl2gpu_poll_feedback(vdl2gpu_t *h, vdl2gpu_burst_t *out, vdl2gpu_level_t *lv, vdl2gpu_soft_t *soft, vdl2gpu_carrier_t *car, vdl2gpu_blockrep_t *rep, vdl2gpu_fb_t *fb, int max) { return poll_impl(h, out, max, {{lv, soft, car, rep, fb}}, true, "vdl2gpu_poll_feedback"); }
+extern "C" int vdl2gpu_poll_feedback_ready(vdl2gpu_t *h, vdl2gpu_burst_t *out, vdl2gpu_level_t *lv, vdl2gpu_soft_t *soft, vdl2gpu_carrier_t *car, vdl2gpu_blockrep_t *rep, vdl2gpu_fb_t *fb, int max) { return poll_impl(h, out, max, {{lv, soft, car, rep, fb}}, false, "vdl2gpu_poll_feedback"); }
 
 /* VDL2GPU_F_CARRIER: the derived values of a carrier record (include/vdl2gpu.h, vdl2gpu_carrier_t) -- the one statement of that
  * arithmetic: collect_records calls it for every record. */

@@ -310,10 +310,34 @@ template <int NT> __device__ __forceinline__ void burst_payload_soft(vdl2gpu_sof
 	}
 }
 
+/* The slices of a burst as the passes behind burst_payload take them: symbol k's phase from sph when the caller kept the phases
+ * there (K2d), else from a filter pass of its own (k2_fir_phase_tab on lds_fir, the same result bits), and the Grey table index of
+ * symbol k against symbol k - 1, k = 8 .. kmax -- the slices the payload decode and the reliability map take.  (burst_payload and
+ * burst_payload_soft state the same themselves: with this in their place the compiler moves registers of kernels on the default path) */
+struct BurstSlices {
+	BurstGeom g;
+	int rb, nbytes, kmax;	/* the filter's sub-phase, the transmitted bytes, the last symbol that carries a bit of them */
+	const float2 *xs0;	/* symbol k's filter window begins at xs0 + 8 k */
+	float df;
+	const float *sph, *lds_fir;
+	__device__ __forceinline__ BurstSlices(const float2 *x0, long long nstar, int clk0, float df_, int nbrow, int nlbyte, const float *sph_, const float *lds_fir_)
+		: g(burst_geom(nbrow, nlbyte)), nbytes(g.ND + g.NF), kmax((25 + 8 * nbytes - 1) / 3), df(df_), sph(sph_), lds_fir(lds_fir_)
+	{
+		int j0;
+		burst_timing(clk0, &j0, &rb);
+		xs0 = x0 + (nstar + j0 - 16);
+	}
+	__device__ __forceinline__ float phase(int k) const { return sph ? sph[k - 7] : k2_fir_phase_tab(xs0 + 8LL * k, rb, lds_fir, lds_fir + 72); }
+	__device__ __forceinline__ int index(int k) const
+	{
+		const float pprev = phase(k - 1);
+		return k2_grey_index(phase(k), pprev, df);
+	}
+};
+
 /* VDL2GPU_F_CARRIER: the phase-error sums of the burst burst_payload has just decoded (vdl2gpu.h, vdl2gpu_carrier_t), all NT threads,
- * called behind it.  One lane per symbol k = 8 .. kmax -- the slices the payload decode and the reliability map take --: the same Grey
- * table index, from sph when the caller kept the phases there (K2d), else from two phases of its own (k2_fir_phase_tab, same result
- * bits), and of it the distance e = (idx & 31) - 16 from the centre of its sector.  Integers only: each wavefront adds its lanes' e
+ * called behind it.  One lane per symbol k = 8 .. kmax takes its Grey table index (BurstSlices) and of it the distance
+ * e = (idx & 31) - 16 from the centre of its sector.  Integers only: each wavefront adds its lanes' e
  * and e * e up (xor butterfly) and its first lane adds the two sums to acc[0], acc[1] in LDS (the caller's, two words nobody else
  * uses meanwhile); thread 0 writes the record once.  Integer sums have no order: every kernel, path and NT leaves the same words.
  * (block-uniform call: two barriers inside) */
@@ -322,19 +346,14 @@ template <int NT> __device__ __forceinline__ void burst_payload_carrier(vdl2gpu_
 {
 	static_assert(NT % 64 == 0, "whole wavefronts");
 	const int tid = threadIdx.x;
-	int j0, rb;
-	burst_timing(clk0, &j0, &rb);
-	const BurstGeom g = burst_geom(nbrow, nlbyte);
-	const int kmax = (25 + 8 * (g.ND + g.NF) - 1) / 3;
-	const float2 *xs0 = x0 + (nstar + j0 - 16);
+	const BurstSlices sl(x0, nstar, clk0, df, nbrow, nlbyte, sph, lds_fir);
+	const int kmax = sl.kmax;
 	if (tid < 2)
 		acc[tid] = 0;
 	__syncthreads();
 	int se = 0, se2 = 0;
 	for (int k = 8 + tid; k <= kmax; k += NT) {
-		const float pprev = sph ? sph[k - 8] : k2_fir_phase_tab(xs0 + 8LL * (k - 1), rb, lds_fir, lds_fir + 72);
-		const float pk = sph ? sph[k - 7] : k2_fir_phase_tab(xs0 + 8LL * k, rb, lds_fir, lds_fir + 72);
-		const int e = (k2_grey_index(pk, pprev, df) & 31) - 16;
+		const int e = (sl.index(k) & 31) - 16;
 		se += e;
 		se2 += e * e;
 	}
@@ -361,8 +380,7 @@ template <int NT> __device__ __forceinline__ void burst_payload_carrier(vdl2gpu_
 
 /* VDL2GPU_F_FEEDBACK: the decision-feedback rows of the burst burst_payload has just decoded (vdl2gpu.h, vdl2gpu_fb_t), all NT threads,
  * called behind it.  Three steps over the symbols k = 8 .. kmax, in chunks that `ob` (LDS bytes, 4-byte aligned, cap of them) holds:
- *   1. one lane per symbol takes the same Grey table index as the payload decode -- from sph when the caller kept the phases there
- *      (K2d), else from two phases of its own (k2_fir_phase_tab, same result bits) -- and keeps idx & 255, one byte a symbol (only
+ *   1. one lane per symbol takes the same Grey table index as the payload decode (BurstSlices) and keeps idx & 255, one byte a symbol (only
  *      idx mod 256 enters the rule, and (256 & 31) == (0 & 31)).  ob may BE sph: pass p reads floats [p NT, (p + 1) NT] and, behind a
  *      barrier, writes bytes [p NT, (p + 1) NT), which lie in floats below (p + 1) NT / 4 <= p NT that no later pass reads.
  *      S = sum e_k as in burst_payload_carrier (wave butterfly, one LDS atomic per wavefront into acc[0]); without sph a first pass over
@@ -380,12 +398,8 @@ template <int NT> __device__ __forceinline__ void burst_payload_feedback(vdl2gpu
 {
 	static_assert(NT % 64 == 0, "whole wavefronts");
 	const int tid = threadIdx.x;
-	int j0, rb;
-	burst_timing(clk0, &j0, &rb);
-	const BurstGeom g = burst_geom(nbrow, nlbyte);
-	const int nbytes = g.ND + g.NF;
-	const int kmax = (25 + 8 * nbytes - 1) / 3;
-	const float2 *xs0 = x0 + (nstar + j0 - 16);
+	const BurstSlices sl(x0, nstar, clk0, df, nbrow, nlbyte, sph, lds_fir);
+	const int nbytes = sl.nbytes, kmax = sl.kmax;
 	const int M = (cap - 3) / 8;
 	const int nchunk = (kmax + 1 - 11 + 8 * M - 1) / (8 * M) > 1 ? (kmax + 1 - 11 + 8 * M - 1) / (8 * M) : 1;	/* (kmax >= 10) */
 	uint32_t *w = reinterpret_cast<uint32_t *>(out);
@@ -397,11 +411,8 @@ template <int NT> __device__ __forceinline__ void burst_payload_feedback(vdl2gpu
 	__syncthreads();
 	int se = 0;
 	if (!sph) {	/* (block-uniform) S ahead of the chunks */
-		for (int k = 8 + tid; k <= kmax; k += NT) {
-			const float pprev = k2_fir_phase_tab(xs0 + 8LL * (k - 1), rb, lds_fir, lds_fir + 72);
-			const float pk = k2_fir_phase_tab(xs0 + 8LL * k, rb, lds_fir, lds_fir + 72);
-			se += (k2_grey_index(pk, pprev, df) & 31) - 16;
-		}
+		for (int k = 8 + tid; k <= kmax; k += NT)
+			se += (sl.index(k) & 31) - 16;
 	}
 	int r1 = 0, r2 = 0, r3 = 0, mbar = 0;	/* (thread 0) */
 	for (int c = 0; c < nchunk; ++c) {
@@ -414,9 +425,7 @@ template <int NT> __device__ __forceinline__ void burst_payload_feedback(vdl2gpu
 			const int k = k0 + tid;
 			int idx = 0;
 			if (k < ke) {
-				const float pprev = sph ? sph[k - 8] : k2_fir_phase_tab(xs0 + 8LL * (k - 1), rb, lds_fir, lds_fir + 72);
-				const float pk = sph ? sph[k - 7] : k2_fir_phase_tab(xs0 + 8LL * k, rb, lds_fir, lds_fir + 72);
-				idx = k2_grey_index(pk, pprev, df);
+				idx = sl.index(k);
 				if (sph)
 					se += (idx & 31) - 16;
 			}
@@ -473,7 +482,7 @@ template <int NT> __device__ __forceinline__ void burst_payload_feedback(vdl2gpu
 					byte |= 1u << i;
 			}
 			int row, col;
-			burst_scatter(g, b, &row, &col);
+			burst_scatter(sl.g, b, &row, &col);
 			out->data[row][col] = (uint8_t)byte;
 		}
 		__syncthreads();	/* (the next chunk overwrites ob) */

@@ -1523,100 +1523,41 @@ template <bool LEV, bool SOFT, bool CAR = false, bool FB = false> __device__ __f
 	}
 }
 
-__global__ __launch_bounds__(K2D_NT) __attribute__((amdgpu_waves_per_eu(K2D_WAVES, 8)))
-void k2d_payload(K2Params p)
-{
-	k2d_run<false, false>(p);
-}
-
-__global__ __launch_bounds__(K2D_NT) __attribute__((amdgpu_waves_per_eu(4, 8)))
-void k2d_payload_lev(K2Params p)
-{
-	k2d_run<true, false>(p);
-}
-
-__global__ __launch_bounds__(K2D_NT) __attribute__((amdgpu_waves_per_eu(4, 8)))
-void k2d_payload_soft(K2Params p)
-{
-	k2d_run<false, true>(p);
-}
-
-__global__ __launch_bounds__(K2D_NT) __attribute__((amdgpu_waves_per_eu(4, 8)))
-void k2d_payload_lev_soft(K2Params p)
-{
-	k2d_run<true, true>(p);
-}
-
-__global__ __launch_bounds__(K2D_NT) __attribute__((amdgpu_waves_per_eu(4, 8)))
-void k2d_payload_car(K2Params p)
-{
-	k2d_run<false, false, true>(p);
-}
-
-__global__ __launch_bounds__(K2D_NT) __attribute__((amdgpu_waves_per_eu(4, 8)))
-void k2d_payload_lev_car(K2Params p)
-{
-	k2d_run<true, false, true>(p);
-}
-
-__global__ __launch_bounds__(K2D_NT) __attribute__((amdgpu_waves_per_eu(4, 8)))
-void k2d_payload_soft_car(K2Params p)
-{
-	k2d_run<false, true, true>(p);
-}
-
-__global__ __launch_bounds__(K2D_NT) __attribute__((amdgpu_waves_per_eu(4, 8)))
-void k2d_payload_lev_soft_car(K2Params p)
-{
-	k2d_run<true, true, true>(p);
-}
-
-__global__ __launch_bounds__(K2D_NT) __attribute__((amdgpu_waves_per_eu(4, 8)))
-void k2d_payload_fb(K2Params p, vdl2gpu_fb_t *fb)
-{
-	k2d_run<false, false, false, true>(p, fb);
-}
-
-__global__ __launch_bounds__(K2D_NT) __attribute__((amdgpu_waves_per_eu(4, 8)))
-void k2d_payload_lev_fb(K2Params p, vdl2gpu_fb_t *fb)
-{
-	k2d_run<true, false, false, true>(p, fb);
-}
-
-__global__ __launch_bounds__(K2D_NT) __attribute__((amdgpu_waves_per_eu(4, 8)))
-void k2d_payload_soft_fb(K2Params p, vdl2gpu_fb_t *fb)
-{
-	k2d_run<false, true, false, true>(p, fb);
-}
-
-__global__ __launch_bounds__(K2D_NT) __attribute__((amdgpu_waves_per_eu(4, 8)))
-void k2d_payload_lev_soft_fb(K2Params p, vdl2gpu_fb_t *fb)
-{
-	k2d_run<true, true, false, true>(p, fb);
-}
-
-__global__ __launch_bounds__(K2D_NT) __attribute__((amdgpu_waves_per_eu(4, 8)))
-void k2d_payload_car_fb(K2Params p, vdl2gpu_fb_t *fb)
-{
-	k2d_run<false, false, true, true>(p, fb);
-}
-
-__global__ __launch_bounds__(K2D_NT) __attribute__((amdgpu_waves_per_eu(4, 8)))
-void k2d_payload_lev_car_fb(K2Params p, vdl2gpu_fb_t *fb)
-{
-	k2d_run<true, false, true, true>(p, fb);
-}
-
-__global__ __launch_bounds__(K2D_NT) __attribute__((amdgpu_waves_per_eu(4, 8)))
-void k2d_payload_soft_car_fb(K2Params p, vdl2gpu_fb_t *fb)
-{
-	k2d_run<false, true, true, true>(p, fb);
-}
-
-__global__ __launch_bounds__(K2D_NT) __attribute__((amdgpu_waves_per_eu(4, 8)))
-void k2d_payload_lev_soft_car_fb(K2Params p, vdl2gpu_fb_t *fb)
-{
-	k2d_run<true, true, true, true>(p, fb);
-}
+/* The sixteen payload kernels, one line each: name, the least wavefronts per SIMD the compiler is held to, LEV, SOFT, CAR, FB.  The
+ * kernels are defined from this list right below and launch_payload (vdl2gpu.hip) builds its tables from it, each kernel at the index
+ * its own flag columns give: the order of the lines means nothing.  Without FB a kernel takes (K2Params), with it (K2Params, the rows'
+ * ring). */
+#define K2D_PAYLOAD_KERNELS(X) \
+	X(k2d_payload, K2D_WAVES, 0, 0, 0, 0) \
+	X(k2d_payload_lev, 4, 1, 0, 0, 0) \
+	X(k2d_payload_soft, 4, 0, 1, 0, 0) \
+	X(k2d_payload_lev_soft, 4, 1, 1, 0, 0) \
+	X(k2d_payload_car, 4, 0, 0, 1, 0) \
+	X(k2d_payload_lev_car, 4, 1, 0, 1, 0) \
+	X(k2d_payload_soft_car, 4, 0, 1, 1, 0) \
+	X(k2d_payload_lev_soft_car, 4, 1, 1, 1, 0) \
+	X(k2d_payload_fb, 4, 0, 0, 0, 1) \
+	X(k2d_payload_lev_fb, 4, 1, 0, 0, 1) \
+	X(k2d_payload_soft_fb, 4, 0, 1, 0, 1) \
+	X(k2d_payload_lev_soft_fb, 4, 1, 1, 0, 1) \
+	X(k2d_payload_car_fb, 4, 0, 0, 1, 1) \
+	X(k2d_payload_lev_car_fb, 4, 1, 0, 1, 1) \
+	X(k2d_payload_soft_car_fb, 4, 0, 1, 1, 1) \
+	X(k2d_payload_lev_soft_car_fb, 4, 1, 1, 1, 1)
+#define K2D_INDEX(LEV, SOFT, CAR, FB) ((LEV) | (SOFT) << 1 | (CAR) << 2 | (FB) << 3)
+#define K2D_BIT(name, waves, LEV, SOFT, CAR, FB) | 1u << K2D_INDEX(LEV, SOFT, CAR, FB)
+static_assert((0u K2D_PAYLOAD_KERNELS(K2D_BIT)) == 0xffffu, "one payload kernel for every set of passes");
+#undef K2D_BIT
+#define K2D_ARGS_0 K2Params p
+#define K2D_ARGS_1 K2Params p, vdl2gpu_fb_t *fb
+#define K2D_PASS_0 p
+#define K2D_PASS_1 p, fb
+#define K2D_DEFINE(name, waves, LEV, SOFT, CAR, FB) \
+	__global__ __launch_bounds__(K2D_NT) __attribute__((amdgpu_waves_per_eu(waves, 8))) void name(K2D_ARGS_##FB) \
+	{ \
+		k2d_run<LEV, SOFT, CAR, FB>(K2D_PASS_##FB); \
+	}
+K2D_PAYLOAD_KERNELS(K2D_DEFINE)
+#undef K2D_DEFINE
 
 #endif

@@ -121,6 +121,21 @@ class Burst:
         return (self.stream, self.chn, self.nbrow, self.nlbyte, self.data)
 
 
+def _rows(v) -> np.ndarray:
+    return np.frombuffer(bytes(v), np.uint8).reshape(8, 255).copy()
+
+
+# The side columns of a burst, in the order of the collectors' arguments: Receiver keyword (and attribute), flag, record type, and the
+# Burst field's value of a record.  (The Burst fields themselves follow `data` in this order.)
+_COLUMNS = (
+    ("levels", _lib.F_LEVELS, _lib.LevelT, Level.from_c),
+    ("soft_rs", _lib.F_SOFT_RS, _lib.SoftT, lambda v: _rows(v.rel)),
+    ("carrier", _lib.F_CARRIER, _lib.CarrierT, Carrier.from_c),
+    ("block_report", _lib.F_BLOCK_REPORT, _lib.BlockRepT, BlockReport.from_c),
+    ("feedback", _lib.F_FEEDBACK, _lib.FbT, lambda v: _rows(v.data)),
+)
+
+
 def plan_channels(fc: int, offsets: Sequence[int]) -> List[ThreadParam]:
     """thread_param_t list the way rtl.c:245-247 fills it: Fo = Fr - Fc."""
     return [ThreadParam(chn=i, Fr=fc + fo, Fo=fo) for i, fo in enumerate(offsets)]
@@ -164,13 +179,13 @@ class Receiver:
         cfg.max_push = max_push
         cfg.device = device
         cfg.max_bursts = max_bursts
-        cfg.flags = (_lib.F_KEEP_DEC if keep_dec else 0) | (_lib.F_SERIAL if serial else 0) | (_lib.F_FULLSCAN if full_scan else 0) | (_lib.F_FRAMES if frames else 0) | (_lib.F_RTL_QUIRK if rtl_quirk else 0) | (_lib.F_LEVELS if levels else 0) | (_lib.F_SOFT_RS if soft_rs else 0) | (_lib.F_EXACT_FO if exact_fo else 0) | (_lib.F_CARRIER if carrier else 0) | (_lib.F_BLOCK_REPORT if block_report else 0) | (_lib.F_FEEDBACK if feedback else 0) | flags
+        asked = dict(levels=levels, soft_rs=soft_rs, carrier=carrier, block_report=block_report, feedback=feedback)
+        switches = [(keep_dec, _lib.F_KEEP_DEC), (serial, _lib.F_SERIAL), (full_scan, _lib.F_FULLSCAN), (frames, _lib.F_FRAMES),
+                    (rtl_quirk, _lib.F_RTL_QUIRK), (exact_fo, _lib.F_EXACT_FO)] + [(asked[kw], flag) for kw, flag, _, _ in _COLUMNS]
+        cfg.flags = flags | sum(flag for on, flag in switches if on)     # (one bit each)
         self.max_push = max_push
-        self.levels = bool(cfg.flags & _lib.F_LEVELS)
-        self.soft_rs = bool(cfg.flags & _lib.F_SOFT_RS)
-        self.carrier = bool(cfg.flags & _lib.F_CARRIER)
-        self.block_report = bool(cfg.flags & _lib.F_BLOCK_REPORT)
-        self.feedback = bool(cfg.flags & _lib.F_FEEDBACK)
+        for kw, flag, _, _ in _COLUMNS:     # self.levels, .soft_rs, .carrier, .block_report, .feedback: by keyword or by `flags`
+            setattr(self, kw, bool(cfg.flags & flag))
         self.h = C.c_void_p()
         rc = self.L.vdl2gpu_create(C.byref(cfg), C.byref(self.h))
         if rc != 0:
@@ -224,38 +239,16 @@ class Receiver:
     def _collect(self, ready: bool, max_bursts: int) -> List[Burst]:
         out: List[Burst] = []
         buf = (_lib.BurstT * max_bursts)()
-        lv = (_lib.LevelT * max_bursts)() if self.levels else None
-        sv = (_lib.SoftT * max_bursts)() if self.soft_rs else None
-        cv = (_lib.CarrierT * max_bursts)() if self.carrier else None
-        rv = (_lib.BlockRepT * max_bursts)() if self.block_report else None
-        fv = (_lib.FbT * max_bursts)() if self.feedback else None
+        cols = [(typ * max_bursts)() if getattr(self, kw) else None for kw, _, typ, _ in _COLUMNS]
+        # the widest collector serves every handle: a column the handle lacks is None, "not wanted" (include/vdl2gpu.h)
+        fn = self.L.vdl2gpu_poll_feedback_ready if ready else self.L.vdl2gpu_poll_feedback
         while True:
-            if fv is not None:
-                fn = self.L.vdl2gpu_poll_feedback_ready if ready else self.L.vdl2gpu_poll_feedback
-                n = self._check(fn(self.h, buf, lv, sv, cv, rv, fv, max_bursts))
-            elif rv is not None:
-                fn = self.L.vdl2gpu_poll_report_ready if ready else self.L.vdl2gpu_poll_report
-                n = self._check(fn(self.h, buf, lv, sv, cv, rv, max_bursts))
-            elif cv is not None:
-                fn = self.L.vdl2gpu_poll_carrier_ready if ready else self.L.vdl2gpu_poll_carrier
-                n = self._check(fn(self.h, buf, lv, sv, cv, max_bursts))
-            elif sv is not None:
-                fn = self.L.vdl2gpu_poll_soft_ready if ready else self.L.vdl2gpu_poll_soft
-                n = self._check(fn(self.h, buf, lv, sv, max_bursts))
-            elif lv is not None:
-                fn = self.L.vdl2gpu_poll_levels_ready if ready else self.L.vdl2gpu_poll_levels
-                n = self._check(fn(self.h, buf, lv, max_bursts))
-            else:
-                fn = self.L.vdl2gpu_poll_ready if ready else self.L.vdl2gpu_poll
-                n = self._check(fn(self.h, buf, max_bursts))
+            n = self._check(fn(self.h, buf, *cols, max_bursts))
             for i in range(n):
                 b = buf[i]
                 out.append(Burst(b.stream, b.chn, b.Fr, b.nbrow, b.nlbyte, b.df, b.ppm, b.trig_dec, b.end_dec,
-                                 b.trig_sample, b.end_sample, bytes(b.data), Level.from_c(lv[i]) if lv is not None else None,
-                                 np.frombuffer(bytes(sv[i].rel), np.uint8).reshape(8, 255).copy() if sv is not None else None,
-                                 Carrier.from_c(cv[i]) if cv is not None else None,
-                                 BlockReport.from_c(rv[i]) if rv is not None else None,
-                                 np.frombuffer(bytes(fv[i].data), np.uint8).reshape(8, 255).copy() if fv is not None else None))
+                                 b.trig_sample, b.end_sample, bytes(b.data),
+                                 *[conv(v[i]) if v is not None else None for v, (_, _, _, conv) in zip(cols, _COLUMNS)]))
             if n < max_bursts:
                 return out
 
@@ -267,33 +260,26 @@ class Receiver:
         """Bursts of pushes the GPU has already finished; never waits."""
         return self._collect(True, max_bursts)
 
+    def _poll_cols_raw(self, name: str, ready: bool, buf, cols, max_bursts: int) -> int:
+        fn = getattr(self.L, name + ("_ready" if ready else ""))
+        return self._check(fn(self.h, buf, *cols, max_bursts))
+
+    # vdl2gpu_poll_levels / _soft / _carrier / _report / _feedback (and their _ready forms) into caller-owned arrays: buf a
+    # (lib.BurstT * n), lv / sv / cv / rv / fv a (lib.LevelT / SoftT / CarrierT / BlockRepT / FbT * n) or None
     def poll_levels_raw(self, buf, lv, max_bursts: int, ready: bool = False) -> int:
-        """vdl2gpu_poll_levels(_ready) into caller-owned (lib.BurstT * n) / (lib.LevelT * n) arrays; lv may be None."""
-        fn = self.L.vdl2gpu_poll_levels_ready if ready else self.L.vdl2gpu_poll_levels
-        return self._check(fn(self.h, buf, lv, max_bursts))
+        return self._poll_cols_raw("vdl2gpu_poll_levels", ready, buf, (lv,), max_bursts)
 
     def poll_soft_raw(self, buf, lv, sv, max_bursts: int, ready: bool = False) -> int:
-        """vdl2gpu_poll_soft(_ready) into caller-owned (lib.BurstT / lib.LevelT / lib.SoftT * n) arrays; lv and sv may be None."""
-        fn = self.L.vdl2gpu_poll_soft_ready if ready else self.L.vdl2gpu_poll_soft
-        return self._check(fn(self.h, buf, lv, sv, max_bursts))
+        return self._poll_cols_raw("vdl2gpu_poll_soft", ready, buf, (lv, sv), max_bursts)
 
     def poll_carrier_raw(self, buf, lv, sv, cv, max_bursts: int, ready: bool = False) -> int:
-        """vdl2gpu_poll_carrier(_ready) into caller-owned (lib.BurstT / lib.LevelT / lib.SoftT / lib.CarrierT * n) arrays; lv, sv and cv may
-        each be None."""
-        fn = self.L.vdl2gpu_poll_carrier_ready if ready else self.L.vdl2gpu_poll_carrier
-        return self._check(fn(self.h, buf, lv, sv, cv, max_bursts))
+        return self._poll_cols_raw("vdl2gpu_poll_carrier", ready, buf, (lv, sv, cv), max_bursts)
 
     def poll_report_raw(self, buf, lv, sv, cv, rv, max_bursts: int, ready: bool = False) -> int:
-        """vdl2gpu_poll_report(_ready) into caller-owned (lib.BurstT / LevelT / SoftT / CarrierT / BlockRepT * n) arrays; lv, sv, cv and rv
-        may each be None."""
-        fn = self.L.vdl2gpu_poll_report_ready if ready else self.L.vdl2gpu_poll_report
-        return self._check(fn(self.h, buf, lv, sv, cv, rv, max_bursts))
+        return self._poll_cols_raw("vdl2gpu_poll_report", ready, buf, (lv, sv, cv, rv), max_bursts)
 
     def poll_feedback_raw(self, buf, lv, sv, cv, rv, fv, max_bursts: int, ready: bool = False) -> int:
-        """vdl2gpu_poll_feedback(_ready) into caller-owned (lib.BurstT / LevelT / SoftT / CarrierT / BlockRepT / FbT * n) arrays; lv, sv, cv,
-        rv and fv may each be None."""
-        fn = self.L.vdl2gpu_poll_feedback_ready if ready else self.L.vdl2gpu_poll_feedback
-        return self._check(fn(self.h, buf, lv, sv, cv, rv, fv, max_bursts))
+        return self._poll_cols_raw("vdl2gpu_poll_feedback", ready, buf, (lv, sv, cv, rv, fv), max_bursts)
 
     def poll_ready_raw(self, buf, max_bursts: int) -> int:
         """vdl2gpu_poll_ready: bursts of pushes that have already finished; never waits."""
