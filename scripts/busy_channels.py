@@ -50,13 +50,14 @@ with Receiver(2_000_000, plan_channels(bench.FC, fos), fmt="cs16", max_push=n, m
     dt = time.perf_counter() - t0
     print("pipelined: %.2f ms per push, %.1f GS/s, %d bursts per push" % (dt / 8 * 1e3, 8 * n / dt / 1e9, tot // 8))
     if os.environ.get("VDL2GPU_DEBUG_COUNTERS"):
-        d = rx.debug_counters(64)
-        n = max(1, d[20])
-        names = ["stage-in", "fir+unit", "barrier", "steps", "screen1", "barrier", "screen2/3", "flush(in tile)", "-", "barrier", "nwl", "passes", "all tiles", "ndl final", "final flush", "instants"]
-        for base, what in ((32, "probe"), (48, "region")):
-            print(what + ": " + ", ".join("%s %d" % (names[i], d[base + i]) for i in range(16) if d[base + i]))
+        raw_d = rx.debug_counters(_lib.DBG_WORDS)
+        d = {k: raw_d[v] for k, v in _lib.DBG.items() if v < _lib.DBG_WORDS}
+        n = max(1, d["K2C_CALLS"])
+        for base, what in (("PROBE_STAGE0", "probe"), ("REGION_STAGE0", "region")):
+            print(what + ": " + _lib.dbg_stages(raw_d, _lib.DBG[base]))
         print("K2c per call (100 MHz ticks -> us): load %.1f tables %.1f walk+serial %.1f publish %.1f; calls %d; per call: cands %.0f visited %.0f "
-              "replays %.2f nonsteady %.2f serial samples %.0f" % (d[16] / n / 100, d[17] / n / 100, d[18] / n / 100, d[19] / n / 100, d[20],
-                                                            d[27] / n, d[28] / n, d[25] / n, d[26] / n, d[29] / n))
+              "replays %.2f nonsteady %.2f serial samples %.0f" % (d["K2C_LOAD_TICKS"] / n / 100, d["K2C_TABLES_TICKS"] / n / 100, d["K2C_WALK_TICKS"] / n / 100, d["K2C_PUBLISH_TICKS"] / n / 100, d["K2C_CALLS"],
+                                                            d["K2C_CANDS"] / n, d["K2C_VISITED"] / n, d["K2C_REPLAYS"] / n, d["K2C_NONSTEADY"] / n, d["K2C_SERIAL_SAMPLES"] / n))
         print("K2b: clusters %d, ring %.1f us, rest %.1f us per sampled cluster; triggers/cluster %.2f evals/cluster %.1f steady %.2f rejects %.2f" % (
-            d[2] * 16, d[0] / max(1, d[2]) / 100, d[1] / max(1, d[2]) / 100, d[3] / max(1, d[2]), d[4] / max(1, d[2]), d[6] / max(1, d[2]), d[7] / max(1, d[2])))
+            d["K2B_SAMPLED"] * 16, d["K2B_RING_TICKS"] / max(1, d["K2B_SAMPLED"]) / 100, d["K2B_REST_TICKS"] / max(1, d["K2B_SAMPLED"]) / 100, d["K2B_TRIG"] / max(1, d["K2B_SAMPLED"]),
+            d["K2B_EVAL"] / max(1, d["K2B_SAMPLED"]), d["K2B_STEADY"] / max(1, d["K2B_SAMPLED"]), d["K2B_REJ"] / max(1, d["K2B_SAMPLED"])))

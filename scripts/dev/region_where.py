@@ -13,15 +13,13 @@ fos = synth.DEFAULT_FO_8CH
 spec, raw = bench.make_tile(1234, "cs16", 2_000_000, fos)
 big = torch.from_numpy(np.tile(raw, 16)).cuda()
 n = big.numel() // 2
-names = ["stage-in", "fir+unit", "barrier", "steps", "screen1", "barrier", "screen2/3", "flush(in tile)", "-", "barrier", "nwl", "passes",
-         "all tiles/wait", "ndl final/park", "final flush", "instants"]
 buf = (_lib.BurstT * (1 << 16))()
 with Receiver(2_000_000, plan_channels(bench.FC, fos), fmt="cs16", max_push=n, max_bursts=1 << 17) as rx:
     for _ in range(4):
         rx.push_device(big.data_ptr(), n, 0)
         rx.poll_raw(buf, 1 << 16)
     for mode in ("synchronous", "pipelined"):
-        rx.debug_counters(64, reset=True)
+        rx.debug_counters(_lib.DBG_WORDS, reset=True)
         for _ in range(8):
             rx.push_device(big.data_ptr(), n, 0)
             if mode == "synchronous":
@@ -29,7 +27,7 @@ with Receiver(2_000_000, plan_channels(bench.FC, fos), fmt="cs16", max_push=n, m
             else:
                 rx.poll_ready_raw(buf, 1 << 16)
         rx.poll_raw(buf, 1 << 16)
-        d = rx.debug_counters(64)
+        d = rx.debug_counters(_lib.DBG_WORDS)
         print(mode)
-        for base, what in ((32, "probe"), (48, "region")):
-            print("  " + what + ": " + ", ".join("%s %d" % (names[i], d[base + i]) for i in range(16) if d[base + i]))
+        for base, what in (("PROBE_STAGE0", "probe"), ("REGION_STAGE0", "region")):
+            print("  " + what + ": " + _lib.dbg_stages(d, _lib.DBG[base]))

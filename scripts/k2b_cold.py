@@ -6,7 +6,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
 import numpy as np
 import scenarios as S
-from vdlm2dec_amd import synth
+from vdlm2dec_amd import lib, synth
 from vdlm2dec_amd.demod import Receiver, plan_channels
 
 n = 16_800_000
@@ -17,5 +17,6 @@ with Receiver(spec.rate, plan_channels(S.FC, spec.fo), fmt="cs16", max_push=n) a
         rx.push(raw)
         got = rx.poll()
         c = rx.debug_counters(16, reset=True)
-        print("push", rep, "bursts", len(got), "clusters", c[12] + c[13] + c[14] + c[15],
-              "mean ticks by ordinal:", [round(c[8 + i] / max(1, c[12 + i]), 1) for i in range(4)], "counts", [int(c[12 + i]) for i in range(4)])
+        ticks, counts = lib.DBG["K2B_ORD_TICKS0"], lib.DBG["K2B_ORD_COUNT0"]     # by a cluster's ordinal in its wavefront: + 0 .. 3
+        print("push", rep, "bursts", len(got), "clusters", sum(c[counts:counts + 4]),
+              "mean ticks by ordinal:", [round(c[ticks + i] / max(1, c[counts + i]), 1) for i in range(4)], "counts", [int(c[counts + i]) for i in range(4)])

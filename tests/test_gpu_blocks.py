@@ -196,7 +196,7 @@ def test_frames_of_channels_repaired_behind_the_payload_decode(built, oracle, mo
             rx.push(raw[2 * s0:2 * (s0 + 600_000)])
             frames += rx.poll_frames()
             bursts += rx.poll()
-        repaired = rx.debug_counters(32, reset=False)[24]      # channel-pushes that went through a repair round
+        repaired = rx.debug_counters(32, reset=False)[lib.DBG["REPAIRED"]]      # channel-pushes that went through a repair round
     assert repaired > 0
     assert sorted(frames) == want and len(want) >= 10
     assert sorted((b.chn, b.nbrow, b.nlbyte, b.data) for b in bursts) == sorted(b.key() for b in ob)

@@ -29,16 +29,19 @@ import test_gpu_levels as TL
 import test_gpu_rates as TR
 from test_gpu_chain import PART, _env, _push_parts
 from test_gpu_planes import _bits, _rx
+from vdlm2dec_amd import lib
 
 pytestmark = pytest.mark.gpu
 
-NDBG = 96                       # VDL2_DBG_WORDS of the test library
-REPAIRED = 24                   # channel-pushes that went through a repair round (k2_begin_repair)
-ESC = {"REG_CAP": 64, "SEG_CAP": 65, "VIS_CAP": 66, "WIN_CAP": 67, "MERGE_CAP": 68, "SLOG_CAP": 69, "STAGE_DYN": 70}
-INVARIANTS = (71, 72, 73, 74)   # (b) k2b_clusters, (b) k2d_run's descriptors, (b) k2d_run's records, (a) k2p_patch
-MERGE_SORT = 75                 # the merge escapes of k2s_merge alone
-ABANDONED = 76                  # k2p_patch gave up a repair it had begun
-CHECKED = (77, 78, 79, 80)      # how often the checks behind INVARIANTS were made
+NDBG = lib.DBG_WORDS_TEST       # VDL2_DBG_WORDS of the test library
+REPAIRED = lib.DBG["REPAIRED"]  # channel-pushes that went through a repair round (k2_begin_repair)
+ESC = {"REG_CAP": lib.DBG["ESC_REG"], "SEG_CAP": lib.DBG["ESC_SEG"], "VIS_CAP": lib.DBG["ESC_VIS"], "WIN_CAP": lib.DBG["ESC_WIN"],
+       "MERGE_CAP": lib.DBG["ESC_MERGE"], "SLOG_CAP": lib.DBG["ESC_SLOG"], "STAGE_DYN": lib.DBG["ESC_STAGE"]}
+# (b) k2b_clusters, (b) k2d_run's descriptors, (b) k2d_run's records, (a) k2p_patch
+INVARIANTS = tuple(lib.DBG[k] for k in ("INV_B_CLUSTER", "INV_B_DECODE", "INV_B_RECORD", "INV_A"))
+MERGE_SORT = lib.DBG["ESC_MERGE_SORT"]          # the merge escapes of k2s_merge alone
+ABANDONED = lib.DBG["ESC_PATCH_ABANDON"]        # k2p_patch gave up a repair it had begun
+CHECKED = tuple(lib.DBG[k] for k in ("CHK_B_CLUSTER", "CHK_B_DECODE", "CHK_B_RECORD", "CHK_A"))   # how often the checks behind INVARIANTS were made
 HOOKS = tuple("VDL2GPU_TEST_" + k for k in ESC)
 SIDE = dict(frames=True, levels=True, soft_rs=True, carrier=True)
 

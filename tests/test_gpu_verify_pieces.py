@@ -9,13 +9,13 @@ import numpy as np
 import pytest
 
 import scenarios as S
-from vdlm2dec_amd import synth
+from vdlm2dec_amd import lib, synth
 
 pytestmark = pytest.mark.gpu
 
 N = 1 << 21
 TILE = 2048         # samples of a full piece: K2A_TS evaluation instants of one parity
-SLOT = 30           # debug counter: evaluation instants of every piece the verify passes scanned
+SLOT = lib.DBG["VERIFY_INSTANTS"]   # debug counter: evaluation instants of every piece the verify passes scanned
 
 
 def _keys(bursts):

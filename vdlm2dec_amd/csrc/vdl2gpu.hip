@@ -205,7 +205,7 @@ struct vdl2gpu {
 	uint8_t *d_pn8 = nullptr;	/* ... by payload byte (K2Params.pn8) */
 	TableSet set[VDL2_NSET];
 	OutRing ring[VDL2_NRING];
-	unsigned *d_outc = nullptr;	/* [2*ring + {0,1}] = records written, dropped; [8], [9] running totals: serial redos, repairs */
+	OutCounters *d_outc = nullptr;
 	hipStream_t copy_stream = nullptr;
 	size_t ctl_words = 0;
 	unsigned rec_cap = 0;
@@ -268,7 +268,7 @@ struct vdl2gpu {
 	/* block path in the pipeline (VDL2GPU_F_FRAMES) */
 	bool frames_on = false;
 	unsigned *d_k4tab = nullptr;	/* GF(256) and FCS tables of the block path */
-	unsigned *d_fcnt = nullptr;	/* [4*ring] frames written, [4*ring+1] dropped, [4*ring+2] arena bytes asked for, [4*ring+3] end of the arena's last written entry */
+	FrameCounters *d_fcnt = nullptr;	/* [VDL2_NRING] */
 	unsigned frame_cap = 0;	/* bytes of a frame buffer (slots + arena) */
 
 	std::vector<uint8_t> fready;		/* compact frame entries as k4_frames wrote them, storage order */
@@ -278,8 +278,8 @@ struct vdl2gpu {
 	vdl2gpu_burst_t *h_pin = nullptr;	/* pinned bounce buffer for record read-back */
 	bool col_on[VDL2_NCOL] = {};	/* which side columns the handle has */
 	double lev_k = 1.0;	/* K of vdl2gpu.h: power of a full-scale tone at the channel centre (VDL2GPU_F_LEVELS) */
-	unsigned *h_pin_cnt = nullptr;	/* pinned, written by k3_rebase: [32*ring + {0..6}] counters, [7] overflowed channels, [8..23] redo mask, [24] most candidates of any channel */
-	unsigned *d_pin_cnt = nullptr;	/* its device address */
+	PushCounters *h_pin_cnt = nullptr;	/* [VDL2_NRING] pinned, written by k3_rebase */
+	PushCounters *d_pin_cnt = nullptr;	/* its device address */
 	unsigned pin_recs = 0;
 	bool failed = false;	/* a HIP call failed while work was being enqueued: device and host state no longer agree */
 	std::string err;
@@ -773,7 +773,7 @@ static const unsigned STAGE_DYN_SLOTS = 65536u;	/* the descriptor pool's dynamic
 static int alloc_sets(vdl2gpu_t *h)
 {
 	const size_t SC = (size_t)h->S * VDL2_CS;
-	ALLOC_TABLE(h, fmask, 16 * sizeof(unsigned), true);
+	ALLOC_TABLE(h, fmask, VDL2_FMASK_WORDS * sizeof(unsigned), true);
 	ALLOC_TABLE(h, ctl, h->ctl_words * sizeof(unsigned), true);
 	ALLOC_TABLE(h, cands, SC * VDL2_CAND_CAP * sizeof(Cand));
 	ALLOC_TABLE(h, clusters, SC * VDL2_CAND_CAP * sizeof(Cluster));
@@ -814,9 +814,9 @@ static void fill_set_params(vdl2gpu_t *h)
 		k.cfg = h->d_cfg;
 		k.pn = h->d_pn;
 		k.pn8 = h->d_pn8;
-		k.sel_mode = 0;
+		k.sel_mode = SEL_FIRST;
 		k.stage_cap = h->stage_cap;
-		k.outc_total_redo = h->d_outc + 8;
+		k.outc_total = &h->d_outc->total;
 		k.rec_cap = h->rec_cap;
 		k.probe_r = 0;				/* the one class scanned everywhere: fixed, not the class the channel is in */
 		k.prim_drop = h->prim_drop;
@@ -969,8 +969,8 @@ static int create_impl(vdl2gpu_t *h)
 	DEV_ALLOC(h, h->d_pn, VDL2_PN_BITS);
 	for (OutRing &rg : h->ring)
 		DEV_ALLOC(h, rg.d_recs, (size_t)h->rec_cap * sizeof(vdl2gpu_burst_t));
-	DEV_ALLOC(h, h->d_outc, 16 * sizeof(unsigned));
-	HIPCHK(h, hipMemsetAsync(h->d_outc, 0, 16 * sizeof(unsigned), h->stream));
+	DEV_ALLOC(h, h->d_outc, sizeof(OutCounters));
+	HIPCHK(h, hipMemsetAsync(h->d_outc, 0, sizeof(OutCounters), h->stream));
 	/* (HIP multiplexes its streams onto four hardware queues: a fifth stream shares one with another, and kernels that
 	 * were meant to run side by side then run one behind the other -- this handle makes exactly main, copy, resolver, payload;
 	 * host input adds one for its copies, which may share a queue with the record read-back) */
@@ -1043,16 +1043,16 @@ static int create_impl(vdl2gpu_t *h)
 		const double a = fs * g;
 		h->lev_k = a * a;
 	}
-	HOST_ALLOC(h, h->h_pin_cnt, 32 * VDL2_NRING * sizeof(unsigned), hipHostMallocMapped);
-	memset(h->h_pin_cnt, 0, 32 * VDL2_NRING * sizeof(unsigned));
+	HOST_ALLOC(h, h->h_pin_cnt, VDL2_NRING * sizeof(PushCounters), hipHostMallocMapped);
+	memset(h->h_pin_cnt, 0, VDL2_NRING * sizeof(PushCounters));
 	DEV_ALLOC(h, h->d_k4tab, K4_TABW * sizeof(unsigned));
 	hipLaunchKernelGGL(k4_tables, dim3(1), dim3(64), 0, h->stream, h->d_k4tab);
 	HIPCHK(h, hipGetLastError());
 	if (h->frames_on) {
 		for (OutRing &rg : h->ring)
 			DEV_ALLOC(h, rg.d_frames, (size_t)h->frame_cap);
-		DEV_ALLOC(h, h->d_fcnt, 4 * VDL2_NRING * sizeof(unsigned));
-		HIPCHK(h, hipMemsetAsync(h->d_fcnt, 0, 4 * VDL2_NRING * sizeof(unsigned), h->stream));
+		DEV_ALLOC(h, h->d_fcnt, VDL2_NRING * sizeof(FrameCounters));
+		HIPCHK(h, hipMemsetAsync(h->d_fcnt, 0, VDL2_NRING * sizeof(FrameCounters), h->stream));
 	}
 	HIPCHK(h, hipHostGetDevicePointer((void **)&h->d_pin_cnt, h->h_pin_cnt, 0));
 	DEV_ALLOC(h, h->d_dbg, VDL2_DBG_WORDS * sizeof(unsigned long long));
@@ -1356,8 +1356,7 @@ static void spill_slab(vdl2gpu_t *h, int slab);
  * their private areas of the item list did not hold is left in the list's common area for the one-workgroup-per-channel kernel
  * that follows on the stream -- the scan's ScanDrain says where that is, and goes to that kernel's launch (launch_per_channel). */
 enum { SCAN_PROBE, SCAN_REGION, SCAN_VERIFY };
-enum { SURV_CANDS = 0, SURV_VERIFY = 1, SURV_PROBE = 2 };	/* K2Params.surv_mode: what a detector hit among the survivors means */
-struct ScanDrain { int slot = -1, mode = 0, skip = 0, pch = 0, nwg = 0; };	/* (slot -1: nothing to drain) */
+struct ScanDrain { int slot = -1, mode = SURV_CANDS, skip = 0, pch = 0, nwg = 0; };	/* (slot -1: nothing to drain) */
 static int launch_scan(vdl2gpu_t *h, int which, const K2Params &k2, dim3 grid, hipStream_t st, int slot, int mode, int skip, unsigned tiles_per_wg, ScanDrain &drain)
 {
 	K2Params q = k2;
@@ -1431,7 +1430,6 @@ static void launch_clusters(const vdl2gpu_t *h, hipStream_t s, const K2Params &k
  * the kernel's second argument (they are no member of K2Params: vdl2gpu_resolve.h, k2d_run).  The two tables -- the eight kernels
  * without the feedback pass, the eight with it -- are filled from K2D_PAYLOAD_KERNELS, each kernel where K2D_INDEX of its own line's
  * flags says, and asked with K2D_INDEX of the handle's: no order to keep in step by hand. */
-enum { SEL_FIRST = 0, SEL_REPAIRED = 1, SEL_FINAL = 2 };
 struct PayloadKernels {
 	void (*fb0[8])(K2Params);
 	void (*fb1[8])(K2Params, vdl2gpu_fb_t *);
@@ -1614,10 +1612,10 @@ static K4Params k4_ring_params(vdl2gpu_t *h, int ring, const unsigned *fmask)
 {
 	K4Params k4{};
 	k4.recs = h->ring[ring].d_recs;
-	k4.nrecs_dev = h->d_outc + 2 * ring;
+	k4.nrecs_dev = &h->d_outc->ring[ring].records;
 	k4.rec_cap = h->rec_cap;
 	k4.frames = h->ring[ring].d_frames;
-	k4.nframes = h->d_fcnt + 4 * ring;
+	k4.nframes = h->d_fcnt + ring;
 	k4.frame_cap = h->frame_cap;
 	k4.compact = 1;
 	k4.tabs = h->d_k4tab;
@@ -1790,7 +1788,7 @@ static int enqueue_back(vdl2gpu_t *h)
 		/* the push's records go to the host by the GPU's own hand: page-locked memory, coalesced 8-byte stores */
 		KExportParams ke{};
 		ke.recs = h->ring[ring].d_recs;
-		ke.count = h->d_outc + 2 * ring;
+		ke.count = &h->d_outc->ring[ring].records;
 		ke.dst = h->slab[h->back.slab].d_recs;
 		ke.cap = std::min(h->slab_cap, h->rec_cap);
 		const OutRing &rg = h->ring[ring];
@@ -1821,8 +1819,8 @@ static int enqueue_back(vdl2gpu_t *h)
 		k3.cs = h->d_cs;
 		k3.outc = h->d_outc;
 		k3.fmask = h->set[par].k2.fmask;
-		k3.fcnt = h->frames_on ? h->d_fcnt + 4 * ring : nullptr;
-		k3.host_cnt = h->d_pin_cnt + 32 * ring;
+		k3.fcnt = h->frames_on ? h->d_fcnt + ring : nullptr;
+		k3.host_cnt = h->d_pin_cnt + ring;
 		k3.ring = ring;
 		k3.ctl = h->set[par].k2.ctl;
 		k3.nstreams = h->S;
@@ -2132,12 +2130,12 @@ static int enqueue_front(vdl2gpu_t *h, hipStream_t fs, long long dec_base, PushT
 		KInitParams ki{};
 		ki.ctl = set.k2.ctl + CTL_STAGE;
 		ki.ctl_words = (int)(h->ctl_words - CTL_STAGE);
-		ki.outc = h->d_outc + 2 * ring;
+		ki.outc = &h->d_outc->ring[ring];
 		ki.fail = set.k2.fail;
 		ki.redo = set.k2.redo;
 		ki.nsc = h->S * VDL2_CS;
 		ki.fmask = set.k2.fmask;
-		ki.fcnt = h->frames_on ? h->d_fcnt + 4 * ring : nullptr;
+		ki.fcnt = h->frames_on ? h->d_fcnt + ring : nullptr;
 		hipLaunchKernelGGL(k_push_init, dim3(1), dim3(1024), 0, fs, ki);
 	}
 	TRY(mark(h, pt, E_SCAN_BEGIN, fs));
@@ -2147,7 +2145,7 @@ static int enqueue_front(vdl2gpu_t *h, hipStream_t fs, long long dec_base, PushT
 	k2.levels = h->ring[ring].col<vdl2gpu_level_t>(COL_LEVEL);	/* (nullptr without VDL2GPU_F_LEVELS: nothing is measured) */
 	k2.soft = h->ring[ring].col<vdl2gpu_soft_t>(COL_SOFT);	/* (nullptr without VDL2GPU_F_SOFT_RS) */
 	k2.carrier = h->ring[ring].col<vdl2gpu_carrier_t>(COL_CARRIER);	/* (nullptr without VDL2GPU_F_CARRIER) */
-	k2.outc = h->d_outc + 2 * ring;
+	k2.outc = &h->d_outc->ring[ring];
 	k2.dec_base = dec_base;
 	k2.scan_lo = dec_base + VDL2_HIST;	/* the scan starts at the first carried frame that has its history */
 	k2.probe_par = (int)((dec_base + VDL2_HIST) & 1);
@@ -2275,7 +2273,7 @@ static int push_impl(vdl2gpu_t *h, const void *iq, size_t nsamples, size_t strea
 	 * than through the scan's ten launches: the parallel path only pays from a few thousand frames on. */
 	p.serial = h->force_serial || (p.J <= VDL2_SERIAL_BELOW && !h->full_scan && !h->set[p.par].k2.test_noregion);
 	p.two_streams = !p.serial;	/* see vdl2gpu::Back */
-	p.spec = !h->full_scan && !p.serial && h->S * VDL2_CS <= 512;	/* see enqueue_back */
+	p.spec = !h->full_scan && !p.serial && h->S * VDL2_CS <= VDL2_FMASK_SLOTS;	/* see enqueue_back */
 	const bool two_streams = p.two_streams;
 	hipStream_t fs = two_streams ? h->fstream : h->stream;	/* the front stage's stream */
 	/* stream time of frame 0 of this push's planes: the outputs completed before it, minus the carried frames in front */
@@ -2435,7 +2433,7 @@ static void spill_slab(vdl2gpu_t *h, int slab)
 static void adapt_from_counters(vdl2gpu_t *h, int ring)
 {
 	const OutRing &rg = h->ring[ring];
-	const unsigned *cnt = h->h_pin_cnt + 32 * ring;
+	const PushCounters &cnt = h->h_pin_cnt[ring];
 	if (!h->knob.split_fixed && rg.samples) {
 		/* How long a part may be follows from how many trigger candidates the busiest channel produced per input sample
 		 * in the parts collected lately (the highest of the last four): parts are sized to fill 90 % of the tables, so
@@ -2443,8 +2441,8 @@ static void adapt_from_counters(vdl2gpu_t *h, int ring)
 		 * overflow is handled by the serial machine for that part (exact, milliseconds); its density then counts as
 		 * twice what the tables hold.  Round 2 halved the parts on an overflow and doubled them again after 1024 quiet
 		 * pushes: busy channels ended up in parts a quarter full. */
-		const unsigned novf = cnt[7];
-		const unsigned maxc = cnt[24];
+		const unsigned novf = cnt.cand_ovf;
+		const unsigned maxc = cnt.cand_max;
 		/* (a part's scan starts at the first carried frame: its count covers the part plus 49152 frames of the one before) */
 		const double span = (double)rg.samples + (double)VDL2_CARRY_FRAMES * (double)h->sdrclk / 21.0;
 		double d = (double)std::min<unsigned>(maxc, VDL2_CAND_CAP) / span;
@@ -2464,7 +2462,7 @@ static void adapt_from_counters(vdl2gpu_t *h, int ring)
 	/* one round always (enqueue_back); one more after every serial redo -- a repaired chain failed its own verify pass
 	 * as often as rounds were scheduled --, and back down one at a time after 256 pushes without a serial redo (what
 	 * the first round repairs does not count: it is always there) */
-	const unsigned redos = cnt[2], repairs = cnt[3];
+	const unsigned redos = cnt.total.redo, repairs = cnt.total.repairs;
 	if (redos != h->redos_seen) {
 		h->redos_seen = redos;
 		h->last_redo_push = rg.push;
@@ -2526,11 +2524,11 @@ static int collect_records(vdl2gpu_t *h, int ring, unsigned n)
 		}
 	}
 	/* K2d ran ahead of the verify pass: what a repair round (or K2f's serial redo) made void of the first selection
-	 * K2d's second pass has tagged (trig_sample == 2 on the device); everything else is a burst of the chain */
+	 * K2d's second pass has tagged (trig_sample == REC_VOID on the device); everything else is a burst of the chain */
 	const bool any = rg.spec;
 	const size_t iold = h->ready_idx.size();
 	auto take = [&](vdl2gpu_burst_t &b, uint64_t handle) {
-		if (any && b.trig_sample == 2)
+		if (any && b.trig_sample == REC_VOID)
 			return;
 		b.trig_sample = dec_to_sample(b.trig_dec, (unsigned)h->sdrclk);
 		b.end_sample = dec_to_sample(b.end_dec, (unsigned)h->sdrclk);
@@ -2651,8 +2649,8 @@ static int collect_frames(vdl2gpu_t *h, int ring, unsigned n)
 	const unsigned arena0 = h->rec_cap * K4_SLOT;
 	/* the arena's entries are the bytes up to the end of the last one that found room (k3_rebase publishes that, not the allocation
 	 * counter: an allocation that fails has advanced the counter, and what lies behind the last entry is an earlier push's) */
-	const unsigned nbytes = std::min(h->h_pin_cnt[32 * ring + 6], h->frame_cap - arena0);
-	h->frames_dropped += h->h_pin_cnt[32 * ring + 5];
+	const unsigned nbytes = std::min(h->h_pin_cnt[ring].arena_end, h->frame_cap - arena0);
+	h->frames_dropped += h->h_pin_cnt[ring].frames_dropped;
 	if (!n)
 		return VDL2GPU_OK;
 	trim_frame_queue(h);
@@ -2694,9 +2692,9 @@ static int harvest_ring(vdl2gpu_t *h, int ring, bool blocking)
 	const double hq0 = std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
 	HIPCHK(h, hipEventSynchronize(rg.done()));
 	h->hprof[6] += std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count() - hq0;
-	const unsigned c0 = h->h_pin_cnt[32 * ring], c1 = h->h_pin_cnt[32 * ring + 1];
-	const unsigned n = std::min(c0, h->rec_cap);
-	h->overflowed += c1;
+	const RingCount &rec = h->h_pin_cnt[ring].rec;
+	const unsigned n = std::min(rec.records, h->rec_cap);
+	h->overflowed += rec.dropped;
 	adapt_from_counters(h, ring);
 	if (n)
 		TRY(collect_records(h, ring, n));
@@ -2780,7 +2778,7 @@ struct BlockTemps {
 	vdl2gpu_burst_t *blk = nullptr;
 	vdl2gpu_soft_t *soft = nullptr;
 	vdl2gpu_frame_t *fr = nullptr;
-	unsigned *cnt = nullptr;
+	FrameCounters *cnt = nullptr;
 	vdl2gpu_blockrep_t *rep = nullptr;
 	vdl2gpu_fb_t *fb = nullptr;
 	~BlockTemps()
@@ -2847,7 +2845,7 @@ extern "C" int vdl2gpu_decode_blocks_feedback(vdl2gpu_t *h, const vdl2gpu_burst_
 	if (soft)
 		BLKCHK(hipMalloc(&d.soft, (size_t)n * sizeof(vdl2gpu_soft_t)));
 	BLKCHK(hipMalloc(&d.fr, (size_t)std::max(max_frames, 1) * sizeof(vdl2gpu_frame_t)));
-	BLKCHK(hipMalloc(&d.cnt, 4 * sizeof(unsigned)));
+	BLKCHK(hipMalloc(&d.cnt, sizeof *d.cnt));
 	if (rep)
 		BLKCHK(hipMalloc(&d.rep, (size_t)n * sizeof(vdl2gpu_blockrep_t)));
 	if (fb)
@@ -2859,24 +2857,24 @@ extern "C" int vdl2gpu_decode_blocks_feedback(vdl2gpu_t *h, const vdl2gpu_burst_
 		BLKCHK(hipMemcpyAsync(d.soft, soft, (size_t)n * sizeof(vdl2gpu_soft_t), hipMemcpyHostToDevice, h->copy_stream));
 	if (fb)
 		BLKCHK(hipMemcpyAsync(d.fb, fb, (size_t)n * sizeof(vdl2gpu_fb_t), hipMemcpyHostToDevice, h->copy_stream));
-	BLKCHK(hipMemsetAsync(d.cnt, 0, 4 * sizeof(unsigned), h->copy_stream));
+	BLKCHK(hipMemsetAsync(d.cnt, 0, sizeof *d.cnt, h->copy_stream));
 	const unsigned grid = (unsigned)std::min<long long>(n, (long long)h->n_cu * 32);
 	launch_blocks(h->copy_stream, grid, k4_block_params(h, d, n, max_frames), rep != nullptr);
 	BLKCHK(hipGetLastError());
 	if (rep)	/* (no record is void here: every one of the n has been written) */
 		BLKCHK(hipMemcpyAsync(rep, d.rep, (size_t)n * sizeof(vdl2gpu_blockrep_t), hipMemcpyDeviceToHost, h->copy_stream));
 	BLKCHK(hipStreamSynchronize(h->copy_stream));
-	unsigned cnt[2] = {0, 0};
-	BLKCHK(hipMemcpyAsync(cnt, d.cnt, sizeof cnt, hipMemcpyDeviceToHost, h->copy_stream));
+	FrameCounters cnt{};
+	BLKCHK(hipMemcpyAsync(&cnt, d.cnt, sizeof cnt, hipMemcpyDeviceToHost, h->copy_stream));
 	BLKCHK(hipStreamSynchronize(h->copy_stream));
-	const int nf = (int)std::min<unsigned>(cnt[0], (unsigned)max_frames);
+	const int nf = (int)std::min<unsigned>(cnt.frames, (unsigned)max_frames);
 	if (nf > 0) {
 		BLKCHK(hipMemcpyAsync(frames, d.fr, (size_t)nf * sizeof(vdl2gpu_frame_t), hipMemcpyDeviceToHost, h->copy_stream));
 		BLKCHK(hipStreamSynchronize(h->copy_stream));
 	}
 #undef BLKCHK
 	if (dropped)
-		*dropped = (int)cnt[1];
+		*dropped = (int)cnt.dropped;
 	std::sort(frames, frames + nf, frame_by_block);
 	return nf;
 }
@@ -3037,7 +3035,7 @@ extern "C" int vdl2gpu_get_stats(vdl2gpu_t *h, vdl2gpu_stats_t *out)
 	{	/* the running total on the device (k2f_commit adds to it), like the channel counters above: current whether or not
 		 * the caller has collected the pushes yet */
 		unsigned rep = 0;
-		HIPCHK(h, hipMemcpy(&rep, h->d_outc + 9, sizeof rep, hipMemcpyDeviceToHost));
+		HIPCHK(h, hipMemcpy(&rep, &h->d_outc->total.repairs, sizeof rep, hipMemcpyDeviceToHost));
 		out->repairs = rep;
 	}
 	return VDL2GPU_OK;
@@ -3226,8 +3224,8 @@ extern "C" int vdl2gpu_debug_k1(vdl2gpu_t *h, unsigned long long *out, int n)
 }
 
 /* rows of one of the last push's per-channel tables (K2Params::*table, `cap` rows a channel): synchronise, read the channel's count
- * word -- block `count_block` of the [S*8] blocks behind CTL_CAND0 --, copy that many rows; returns the count */
-template <class T> static int debug_rows(vdl2gpu_t *h, int stream, int ch, int *out, int max_rows, T *K2Params::*table, unsigned cap, size_t count_block)
+ * word -- in block `count_block` (CTL_B_*) of the control words --, copy that many rows; returns the count */
+template <class T> static int debug_rows(vdl2gpu_t *h, int stream, int ch, int *out, int max_rows, T *K2Params::*table, unsigned cap, int count_block)
 {
 	if (!h || stream < 0 || stream >= h->S || ch < 0 || ch >= h->C || !out)
 		return VDL2GPU_EINVAL;
@@ -3238,7 +3236,7 @@ template <class T> static int debug_rows(vdl2gpu_t *h, int stream, int ch, int *
 	const K2Params &k2 = h->set[h->last_set].k2;
 	const int sc = stream * VDL2_CS + ch;
 	unsigned n = 0;
-	HIPCHK(h, hipMemcpy(&n, k2.ctl + CTL_CAND0 + count_block * (size_t)h->S * VDL2_CS + sc, sizeof n, hipMemcpyDeviceToHost));
+	HIPCHK(h, hipMemcpy(&n, k2.ctl + CTL_BLOCK(k2, count_block) + sc, sizeof n, hipMemcpyDeviceToHost));
 	n = std::min(n, cap);
 	n = std::min<unsigned>(n, (unsigned)max_rows);
 	if (n)
@@ -3250,13 +3248,13 @@ template <class T> static int debug_rows(vdl2gpu_t *h, int stream, int ch, int *
  * {nrel, r, bits(p2err), bits(perr), bits(err), bits(pfr)}; returns the count */
 extern "C" int vdl2gpu_debug_cands(vdl2gpu_t *h, int stream, int ch, int *out, int max_cands)
 {
-	return debug_rows(h, stream, ch, out, max_cands, &K2Params::cands, VDL2_CAND_CAP, 0);
+	return debug_rows(h, stream, ch, out, max_cands, &K2Params::cands, VDL2_CAND_CAP, CTL_B_CAND);
 }
 
 /* diagnostics: the cluster heads (cl_pack) of the last push's candidates, in vdl2gpu_debug_cands()'s order */
 extern "C" int vdl2gpu_debug_clheads(vdl2gpu_t *h, int stream, int ch, int *out, int max_cands)
 {
-	return debug_rows(h, stream, ch, out, max_cands, &K2Params::clhead, VDL2_CAND_CAP, 0);
+	return debug_rows(h, stream, ch, out, max_cands, &K2Params::clhead, VDL2_CAND_CAP, CTL_B_CAND);
 }
 
 /* verify result of the last push per (stream, channel slot): stream-relative position of the first
@@ -3277,7 +3275,7 @@ extern "C" int vdl2gpu_debug_fail(vdl2gpu_t *h, int *out, int n)
 /* diagnostics: the idle segments the last push's resolver asked to have verified {lo, hi, r, pad} */
 extern "C" int vdl2gpu_debug_segs(vdl2gpu_t *h, int stream, int ch, int *out, int max_segs)
 {
-	return debug_rows(h, stream, ch, out, max_segs, &K2Params::segs, VDL2_SEG_CAP, 3);
+	return debug_rows(h, stream, ch, out, max_segs, &K2Params::segs, VDL2_SEG_CAP, CTL_B_NSEG);
 }
 
 /* VDL2GPU_F_DEBUG_HEADS: the header soft bits of every sync trigger any kernel of the LAST push handled -- the

@@ -39,9 +39,8 @@ struct K4Params {
 	unsigned nrecs;
 	unsigned rec_cap;
 	vdl2gpu_frame_t *frames;
-	unsigned *nframes;		/* [0] frames written (compact: to the arena), [1] frames dropped (buffer full),
-					 * [2] arena bytes asked for (compact; an allocation that fails has advanced it too),
-					 * [3] end of the last entry that found room (compact): the arena's valid bytes */
+	FrameCounters *nframes;		/* frames written (compact: to the arena) and dropped (buffer full); compact: arena bytes asked for (an
+					 * allocation that fails has advanced it too) and the end of the last entry that found room */
 	unsigned frame_cap;		/* records, or bytes if compact */
 	int compact;			/* 0: an array of vdl2gpu_frame_t.
 					 * 1: entries of 56 header bytes (the struct's head) + len data bytes.  Record i owns
@@ -49,8 +48,8 @@ struct K4Params {
 					 * fits (len 0: none) -- no allocation, because two thousand waves asking one
 					 * device-scope counter for space at the same moment cost more than the whole block
 					 * path; longer and further frames go to the arena behind rec_cap slots, entries
-					 * rounded up to 8 bytes, space taken from nframes[2] */
-	const unsigned *fmask;		/* not nullptr (it is never read): the records come from the pipeline, where K2d's second pass tags the void ones 2 (trig_sample) */
+					 * rounded up to 8 bytes, space taken from nframes->arena_asked */
+	const unsigned *fmask;		/* not nullptr (it is never read): the records come from the pipeline, where K2d's second pass tags the void ones REC_VOID (trig_sample) */
 	const unsigned *tabs;		/* K4_TABW words from k4_tables: gexp[512], glog[256], crc_tab[256] */
 	const vdl2gpu_soft_t *soft;	/* VDL2GPU_F_SOFT_RS: the records' reliability maps, same index: the row rule of vdl2gpu_soft_t for
 					 * rows the reference cannot decode.  nullptr: the reference's block path and nothing else */
@@ -806,18 +805,18 @@ __device__ __forceinline__ vdl2gpu_frame_t *k4_alloc(const K4Params &p, int len)
 	if (p.compact) {
 		const unsigned sz = k4_entry_bytes(len);
 		const unsigned base = p.rec_cap * K4_SLOT;
-		const unsigned at = base + atomicAdd(p.nframes + 2, sz);	/* byte offset */
+		const unsigned at = base + atomicAdd(&p.nframes->arena_asked, sz);	/* byte offset */
 		if (at + sz <= p.frame_cap) {
-			atomicAdd(p.nframes, 1u);
-			atomicMax(p.nframes + 3, at + sz - base);	/* the counter never goes back: the entries that found room are a prefix of the arena */
+			atomicAdd(&p.nframes->frames, 1u);
+			atomicMax(&p.nframes->arena_end, at + sz - base);	/* the counter never goes back: the entries that found room are a prefix of the arena */
 			return reinterpret_cast<vdl2gpu_frame_t *>(reinterpret_cast<char *>(p.frames) + at);
 		}
 	} else {
-		const unsigned at = atomicAdd(p.nframes, 1u);
+		const unsigned at = atomicAdd(&p.nframes->frames, 1u);
 		if (at < p.frame_cap)
 			return p.frames + at;
 	}
-	atomicAdd(p.nframes + 1, 1u);
+	atomicAdd(&p.nframes->dropped, 1u);
 	return nullptr;
 }
 
@@ -910,7 +909,7 @@ __device__ __forceinline__ void k4_frames_body(const K4Params &p)
 		vdl2gpu_frame_t *const myslot = p.compact ? reinterpret_cast<vdl2gpu_frame_t *>(reinterpret_cast<char *>(p.frames) + (size_t)ib * K4_SLOT) : nullptr;
 		if (myslot && lane == 0)
 			myslot->len = 0;
-		if (p.fmask && rec->trig_sample == 2)	/* (device-side tag) a burst of the first selection that a repair round made void: K2d's second pass says so */
+		if (p.fmask && rec->trig_sample == REC_VOID)	/* (device-side tag) a burst of the first selection that a repair round made void: K2d's second pass says so */
 			continue;
 		const bool badhead = nbrow < 1 || nbrow > VDL2GPU_MAXROWS || nlbyte < 0 || nlbyte > 249;
 		if constexpr (REP) {
@@ -951,7 +950,7 @@ __device__ __forceinline__ void k4_frames_body(const K4Params &p)
 			rp.r.bad_fcs = (uint16_t)(cand - too_short - frames);	/* every 0x7e behind hdata[1] is one of the three */
 			rp.r.frames = (uint16_t)frames;
 		}
-		k4_sort_candidates(sh, p.nframes + 1, lane);
+		k4_sort_candidates(sh, &p.nframes->dropped, lane);
 		k4_emit(sh, p, myslot, ib, m1, lane);
 		if constexpr (REP)
 			k4_rep_store(rp, p.rep + ib, lane);

@@ -40,12 +40,12 @@ __global__ void k_push_init(KInitParams p)
 		p.fail[i] = 0x7f7f7f7f;
 		p.redo[i] = 0;
 	}
-	if (threadIdx.x < 2)
-		p.outc[threadIdx.x] = 0u;
-	if (threadIdx.x < 16)
+	if (threadIdx.x < sizeof *p.outc / sizeof(unsigned))
+		reinterpret_cast<unsigned *>(p.outc)[threadIdx.x] = 0u;
+	if (threadIdx.x < VDL2_FMASK_WORDS)
 		p.fmask[threadIdx.x] = 0u;
-	if (p.fcnt && threadIdx.x < 4)
-		p.fcnt[threadIdx.x] = 0u;
+	if (p.fcnt && threadIdx.x < sizeof *p.fcnt / sizeof(unsigned))
+		reinterpret_cast<unsigned *>(p.fcnt)[threadIdx.x] = 0u;
 }
 
 /* runs after k3_compact (same stream): publish the new time base and hand the push's counters to the host */
@@ -59,7 +59,7 @@ __global__ void k3_rebase(K3Params p)
 		for (int sc = (int)threadIdx.x; sc < (p.nstreams * VDL2_CS + 63) / 64 * 64; sc += 64) {
 			const bool live = sc < p.nstreams * VDL2_CS && sc % VDL2_CS < p.nbch;
 			const unsigned nc = live ? p.ctl[CTL_CAND0 + sc] : 0u;
-			const bool over = live && (nc > VDL2_CAND_CAP || (p.ctl[CTL_CAND0 + p.nstreams * VDL2_CS + sc] & 1u));	/* (bit 1: unusable for another reason than their size) */
+			const bool over = live && (nc > VDL2_CAND_CAP || (p.ctl[CTL_CANDOVF0(p) + sc] & 1u));	/* (bit 1: unusable for another reason than their size) */
 			novf += (unsigned)__popcll(__ballot(over));
 			maxc = nc > maxc ? nc : maxc;
 		}
@@ -71,16 +71,22 @@ __global__ void k3_rebase(K3Params p)
 	if (threadIdx.x != 0)
 		return;
 	if (blockIdx.x == 0) {
-		p.host_cnt[0] = p.outc[2 * p.ring];
-		p.host_cnt[1] = p.outc[2 * p.ring + 1];
-		p.host_cnt[2] = p.outc[8];	/* running totals: serial redos, repairs */
-		p.host_cnt[3] = p.outc[9];
-		for (int i = 0; i < 3; ++i)	/* frames, dropped, and the arena's valid bytes (fcnt[3]: where its last written entry ends -- not fcnt[2], which failed allocations have advanced as well) */
-			p.host_cnt[4 + i] = p.fcnt ? p.fcnt[i == 2 ? 3 : i] : 0u;
-		for (int i = 0; i < 16; ++i)
-			p.host_cnt[8 + i] = p.fmask[i];
-		p.host_cnt[7] = novf;
-		p.host_cnt[24] = maxc;
+		/* The blocks as words, each at its member's place (VDL2_WORD).  Copied member by member the compiler may take it that no
+		 * store to *host_cnt changes *outc or *fcnt, and fetches them in pairs ahead of the stores: other code than this kernel had */
+		const unsigned *outc = reinterpret_cast<const unsigned *>(p.outc), *fcnt = reinterpret_cast<const unsigned *>(p.fcnt);
+		unsigned *h = reinterpret_cast<unsigned *>(p.host_cnt);
+		const int ring0 = VDL2_WORD(OutCounters, ring) + VDL2_WORD(OutCounters, ring[1]) * p.ring;
+		h[VDL2_WORD(PushCounters, rec.records)] = outc[ring0 + VDL2_WORD(RingCount, records)];
+		h[VDL2_WORD(PushCounters, rec.dropped)] = outc[ring0 + VDL2_WORD(RingCount, dropped)];
+		h[VDL2_WORD(PushCounters, total.redo)] = outc[VDL2_WORD(OutCounters, total.redo)];
+		h[VDL2_WORD(PushCounters, total.repairs)] = outc[VDL2_WORD(OutCounters, total.repairs)];
+		h[VDL2_WORD(PushCounters, frames)] = fcnt ? fcnt[VDL2_WORD(FrameCounters, frames)] : 0u;
+		h[VDL2_WORD(PushCounters, frames_dropped)] = fcnt ? fcnt[VDL2_WORD(FrameCounters, dropped)] : 0u;
+		h[VDL2_WORD(PushCounters, arena_end)] = fcnt ? fcnt[VDL2_WORD(FrameCounters, arena_end)] : 0u;	/* (not arena_asked, which failed allocations have advanced as well) */
+		for (int i = 0; i < VDL2_FMASK_WORDS; ++i)
+			h[VDL2_WORD(PushCounters, fmask) + i] = p.fmask[i];
+		h[VDL2_WORD(PushCounters, cand_ovf)] = novf;
+		h[VDL2_WORD(PushCounters, cand_max)] = maxc;
 	}
 	StreamState *ss = p.ss + s;	/* (diagnostics: the kernels take the time base from their parameters) */
 	ss->dec_base = ss->dec_base + ss->dec_fill + p.J - VDL2_CARRY_FRAMES;	/* frame VDL2_CARRY_FRAMES = first output of the next push */

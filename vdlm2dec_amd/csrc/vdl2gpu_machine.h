@@ -179,7 +179,7 @@ __device__ __forceinline__ void burst_levels(vdl2gpu_level_t *lev, const float2 
  * takes and spilled 367 of them: 11 900 lines of ISA, 5 500 without) */
 template <int NT, bool TAB = false> __device__ __forceinline__ void burst_payload(vdl2gpu_burst_t *rec, const float2 *x0, const uint8_t *pn, long long nstar,
 						  int clk0, float df, int nbrow, int nlbyte, int stream, ChanCfg cfg, float *sph_ = nullptr,
-						  int tag = 1, int slot = 0, const float *lds_tabs_ = nullptr, const uint8_t *pn8_ = nullptr,
+						  int tag = REC_FINAL, int slot = 0, const float *lds_tabs_ = nullptr, const uint8_t *pn8_ = nullptr,
 						  const float *lds_fir = nullptr)
 {
 	/* lds_tabs: mflt[72], the atanf range table AND the three soft-bit tables in LDS (K2d); lds_fir: only the first two (the serial
@@ -249,8 +249,8 @@ template <int NT, bool TAB = false> __device__ __forceinline__ void burst_payloa
 		rec->ppm = 0.0f;	/* host: d8psk.c:302 needs libm double math */
 		rec->trig_dec = nstar;
 		rec->end_dec = nsym0 + 8LL * (g.nsym - 1);
-		rec->trig_sample = tag;	/* device-side use of the two host-filled fields: 0 = decoded by K2d from the resolver's
-					 * selection (the host drops these for a channel that K2f then redid), 1 = final */
+		rec->trig_sample = tag;	/* device-side use of the two host-filled fields: REC_FIRST = decoded by K2d from the resolver's
+					 * selection (the host drops these for a channel that K2f then redid), REC_FINAL */
 		rec->end_sample = slot;	/* stream * 8 + channel slot */
 	}
 }
@@ -924,7 +924,7 @@ template <int NT, bool XL, bool FB = false> __device__ __forceinline__ long long
 		__syncthreads();
 		const unsigned slot = (unsigned)sh.ctl[6];
 		if (!XL && !cx.desc && slot != 0xffffffffu)
-			burst_payload<NT>(cx.recs + slot, x0, cx.pn, nstar, clk0, df, nbrow, nlbyte, cx.stream, cx.cfg, nullptr, 1, 0, nullptr, nullptr, sh.smf);
+			burst_payload<NT>(cx.recs + slot, x0, cx.pn, nstar, clk0, df, nbrow, nlbyte, cx.stream, cx.cfg, nullptr, REC_FINAL, 0, nullptr, nullptr, sh.smf);
 		if (!XL && !cx.desc && slot != 0xffffffffu && cx.levels && threadIdx.x < 64)
 			burst_payload_levels(cx.levels + slot, x0, nstar, clk0, nbrow, nlbyte, sh.smf, cx.dec_base);
 		if (!XL && !cx.desc && slot != 0xffffffffu && cx.soft) {	/* (block-uniform) */
@@ -1072,8 +1072,8 @@ __device__ __forceinline__ void mach_ctx(MachCtx &cx, const K2Params &p, int s, 
 		cx.carrier = p.carrier;
 		cx.dyn_base = 0;
 		cx.desc = nullptr;
-		cx.rec_count = p.outc;
-		cx.rec_ovf = p.outc + 1;
+		cx.rec_count = &p.outc->records;
+		cx.rec_ovf = &p.outc->dropped;
 		cx.rec_cap = p.rec_cap;
 	}
 	cx.stream = s;

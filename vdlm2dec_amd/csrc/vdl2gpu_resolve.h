@@ -27,7 +27,7 @@ void k2s_sort(K2Params p)
 	if (p.round > 0 && p.fail[sc] >= VDL2_VERIFIED)
 		return;
 	int ncand = (int)p.ctl[CTL_CAND0 + sc];
-	if (ncand > VDL2_CAND_CAP || p.ctl[CTL_CAND0 + p.nstreams * VDL2_CS + sc] != 0)
+	if (ncand > VDL2_CAND_CAP || p.ctl[CTL_CANDOVF0(p) + sc] != 0)
 		return;		/* tables unusable: the resolver runs serially */
 	const Cand *cands = p.cands + (size_t)sc * VDL2_CAND_CAP;
 	int *skey = p.skey + (size_t)sc * VDL2_CAND_CAP;
@@ -42,7 +42,7 @@ void k2s_sort(K2Params p)
 	/* repair round: candidates are only ever appended and a cluster depends on nothing but its own
 	 * candidate and the samples, so the clusters of the earlier rounds stand -- only primaries that are new
 	 * (or were not primary before) go to K2b */
-	const int nold = (p.round > 0) ? (int)p.ctl[CTL_NCLUST0 + sc] : 0;
+	const int nold = (p.round > 0) ? (int)p.ctl[CTL_NCLUST0(p) + sc] : 0;
 	for (int j = tid; j < ncand; j += K2S_NT) {
 		const unsigned long long v = sbuf[j];
 		const int key = (int)(v >> 16), idx = (int)(v & 0xffffu);
@@ -71,8 +71,8 @@ void k2s_sort(K2Params p)
 	}
 	__syncthreads();
 	if (tid == 0) {
-		p.ctl[CTL_NPRIM0 + sc] = (unsigned)s_np;
-		p.ctl[CTL_NCLUST0 + sc] = (unsigned)ncand;
+		p.ctl[CTL_NPRIM0(p) + sc] = (unsigned)s_np;
+		p.ctl[CTL_NCLUST0(p) + sc] = (unsigned)ncand;
 	}
 }
 
@@ -97,10 +97,10 @@ void k2s_merge(K2Params p)
 	if (p.fail[sc] >= VDL2_VERIFIED)
 		return;
 	const int ncand = (int)p.ctl[CTL_CAND0 + sc];
-	unsigned *ovf = p.ctl + CTL_CAND0 + p.nstreams * VDL2_CS + sc;
+	unsigned *ovf = p.ctl + CTL_CANDOVF0(p) + sc;
 	if (ncand > VDL2_CAND_CAP || *ovf != 0)
 		return;		/* tables unusable: the resolver runs serially */
-	const int nold = (int)p.ctl[CTL_NCLUST0 + sc], nnew = ncand - nold;
+	const int nold = (int)p.ctl[CTL_NCLUST0(p) + sc], nnew = ncand - nold;
 	if (nnew <= 0)
 		return;		/* (a channel that failed for another reason than an unlisted event: the resolver will find nothing new) */
 	if (nnew > K2_MERGE_LIM(p)) {	/* a handicapped test build, a pathological input: not worth a sort kernel's footprint in every push */
@@ -166,8 +166,8 @@ void k2s_merge(K2Params p)
 		sidx[at] = (unsigned short)(vn & 0xffffu);
 	}
 	if (tid == 0) {
-		p.ctl[CTL_NPRIM0 + sc] = 0u;
-		p.ctl[CTL_NCLUST0 + sc] = (unsigned)ncand;
+		p.ctl[CTL_NPRIM0(p) + sc] = 0u;
+		p.ctl[CTL_NCLUST0(p) + sc] = (unsigned)ncand;
 	}
 }
 static_assert(VDL2_CAND_CAP % K2M_NT == 0 && K2S_MERGE <= K2M_NT, "k2s_merge");
@@ -208,7 +208,7 @@ void k2b_clusters(K2Params p)
 	if (tid == 0) {
 		unsigned acc = 0;
 		for (int k = 0; k < nsc64; ++k) {
-			unsigned n = p.ctl[CTL_NPRIM0 + sc0 + k];
+			unsigned n = p.ctl[CTL_NPRIM0(p) + sc0 + k];
 			n = n > VDL2_CAND_CAP ? VDL2_CAND_CAP : n;
 			if (p.round > 0 && p.fail[sc0 + k] >= VDL2_VERIFIED)
 				n = 0;
@@ -277,19 +277,19 @@ void k2b_clusters(K2Params p)
 		}
 		const long long t2 = wall_clock64();
 		if (tid == 0 && p.dbg && (tk & 15u) == 0) {
-			atomicAdd(p.dbg + 0, (unsigned long long)(t1 - t0));
-			atomicAdd(p.dbg + 1, (unsigned long long)(t2 - t1));
-			atomicAdd(p.dbg + 2, 1ull);
-			atomicAdd(p.dbg + 3, (unsigned long long)out.ntrig);
-			atomicAdd(p.dbg + 4, (unsigned long long)out.neval);
-			atomicMax(p.dbg + 5, (unsigned long long)(t2 - t1));
-			atomicAdd(p.dbg + 6, (unsigned long long)(rc == MR_STEADY));
-			atomicAdd(p.dbg + 7, (unsigned long long)out.nrej);
+			atomicAdd(p.dbg + K2_DBG_K2B_RING_TICKS, (unsigned long long)(t1 - t0));
+			atomicAdd(p.dbg + K2_DBG_K2B_REST_TICKS, (unsigned long long)(t2 - t1));
+			atomicAdd(p.dbg + K2_DBG_K2B_SAMPLED, 1ull);
+			atomicAdd(p.dbg + K2_DBG_K2B_TRIG, (unsigned long long)out.ntrig);
+			atomicAdd(p.dbg + K2_DBG_K2B_EVAL, (unsigned long long)out.neval);
+			atomicMax(p.dbg + K2_DBG_K2B_MAX_TICKS, (unsigned long long)(t2 - t1));
+			atomicAdd(p.dbg + K2_DBG_K2B_STEADY, (unsigned long long)(rc == MR_STEADY));
+			atomicAdd(p.dbg + K2_DBG_K2B_REJ, (unsigned long long)out.nrej);
 		}
 		if (tid == 0 && p.dbg) {	/* is a wavefront's first cluster slower than its later ones (code fetched cold)? */
 			const int o = ord < 3 ? ord : 3;
-			atomicAdd(p.dbg + 8 + o, (unsigned long long)(t2 - t0));
-			atomicAdd(p.dbg + 12 + o, 1ull);
+			atomicAdd(p.dbg + K2_DBG_K2B_ORD_TICKS0 + o, (unsigned long long)(t2 - t0));
+			atomicAdd(p.dbg + K2_DBG_K2B_ORD_COUNT0 + o, 1ull);
 		}
 		++ord;
 		int status;
@@ -356,28 +356,28 @@ __device__ __forceinline__ int k2c_next(const int *skey, const unsigned short *c
 static_assert(VDL2_CAND_CAP <= 8191, "a hop holds a 13-bit rank");
 
 /* ---- steps of following the chain that K2c, K2p, K2f and K2d share */
-/* The push's mask of channels a repair round re-resolved or K2f redid serially (K2Params.fmask, a bit per channel slot below 512).
- * If K2d ran ahead on the first pass's selection, what it made of such a channel is void (K2d's second pass tags those records 2:
+/* The push's mask of channels a repair round re-resolved or K2f redid serially (K2Params.fmask, a bit per channel slot below VDL2_FMASK_SLOTS).
+ * If K2d ran ahead on the first pass's selection, what it made of such a channel is void (K2d's second pass tags those records REC_VOID:
  * the host and K4 drop them) and K2d decodes the repaired selection in that second pass. */
 __device__ __forceinline__ void k2_fmask_set(const K2Params &p, int sc)
 {
-	if (p.fmask && sc < 512)
+	if (p.fmask && sc < VDL2_FMASK_SLOTS)
 		atomicOr(p.fmask + (sc >> 5), 1u << (sc & 31));
 }
 
-__device__ __forceinline__ bool k2_fmask_test(const K2Params &p, int sc) { return sc < 512 && (p.fmask[sc >> 5] >> (sc & 31) & 1u); }
+__device__ __forceinline__ bool k2_fmask_test(const K2Params &p, int sc) { return sc < VDL2_FMASK_SLOTS && (p.fmask[sc >> 5] >> (sc & 31) & 1u); }
 
 /* thread 0 of a repair round's workgroup: channel sc is resolved again.  nwin0 (CTL_NWIN0): what that makes void of the first selection
  * before the round has listed any window -- all of it where the channel is resolved again from its input state, nothing in a local repair */
 __device__ __forceinline__ void k2_begin_repair(const K2Params &p, int sc, unsigned nwin0)
 {
 	p.redo[sc] = 1;
-	atomicAdd(p.outc_total_redo + 1, 1u);	/* channel-pushes that went through a repair round */
+	atomicAdd(&p.outc_total->repairs, 1u);	/* channel-pushes that went through a repair round */
 	if (p.dbg)
-		atomicAdd(p.dbg + 24, 1ull);
-	p.ctl[CTL_NSEL1 + sc] = 0;	/* (the repair rounds' own selection: see CTL_NSEL1) */
-	p.ctl[CTL_NSEG0 + sc] = 0;
-	p.ctl[CTL_NWIN0 + sc] = nwin0;
+		atomicAdd(p.dbg + K2_DBG_REPAIRED, 1ull);
+	p.ctl[CTL_NSEL1(p) + sc] = 0;	/* (the repair rounds' own selection: see CTL_NSEL1) */
+	p.ctl[CTL_NSEG0(p) + sc] = 0;
+	p.ctl[CTL_NWIN0(p) + sc] = nwin0;
 	k2_fmask_set(p, sc);
 }
 
@@ -413,7 +413,7 @@ template <class T> __device__ __forceinline__ void k2_select_slots(const K2Param
 		if (q + i < VDL2_SEL_CAP)
 			sel[q + i] = slot0 + i;
 		else
-			atomicAdd(p.outc + 1, 1u);
+			atomicAdd(&p.outc->dropped, 1u);
 	}
 }
 
@@ -554,7 +554,7 @@ __device__ __forceinline__ void k2c_walk(const K2cShared &ks, const K2Params &p,
 		/* the chain idles from here to the next candidate in a class the probe did not
 		 * scan: K2a-verify must confirm there really is nothing in between */
 		const int g_hi = (cur >= 0) ? (ks.skey[cur] >> 2) : (int)(cx.avail_end - cx.dec_base);
-		if (g_hi > seg_from && !k2_emit_seg(p, p.segs + (size_t)sc * VDL2_SEG_CAP, atomicAdd(p.ctl + CTL_NSEG0 + sc, 1u), (int)(st.pos - cx.dec_base), g_hi, st.r))
+		if (g_hi > seg_from && !k2_emit_seg(p, p.segs + (size_t)sc * VDL2_SEG_CAP, atomicAdd(p.ctl + CTL_NSEG0(p) + sc, 1u), (int)(st.pos - cx.dec_base), g_hi, st.r))
 			atomicMin(p.fail + sc, 0);
 	}
 	if (cur >= 0 && stat4_status(ks.sstat[cur]) != CL_STEADY)
@@ -604,7 +604,7 @@ __device__ __forceinline__ void k2c_publish(const K2cShared &ks, const K2Params 
 	const int t_end = (int)(cx.avail_end - cx.dec_base);
 	uint8_t *const onchain = p.onchain + (size_t)sc * VDL2_CAND_CAP;
 	Seg *segs = p.segs + (size_t)sc * VDL2_SEG_CAP;
-	unsigned *nseg = p.ctl + CTL_NSEG0 + sc;
+	unsigned *nseg = p.ctl + CTL_NSEG0(p) + sc;
 	if (tid < 4)
 		ks.cnt[tid] = 0;
 	if (tid == 0) {
@@ -665,9 +665,9 @@ __device__ __forceinline__ void k2c_publish(const K2cShared &ks, const K2Params 
 		 * as bursts [found by scripts/soak.py's dropped-region-scan modes: two rounds, or a round and a redo].  The repaired
 		 * selection's records are reserved by K2f, when it is final. */
 		if (ks.walk[0] > 0 && p.sel_reserved && p.round == 0)
-			p.ctl[CTL_SELBASE0 + sc] = atomicAdd(p.outc, (unsigned)ks.walk[0]);
+			p.ctl[CTL_SELBASE0(p) + sc] = atomicAdd(&p.outc->records, (unsigned)ks.walk[0]);
 		if (first_pass)
-			p.ctl[CTL_NSLOG0 + sc] = (unsigned)(tables_ok ? nslog : K2_SLOG_LIM(p) + 1);	/* (no tables: nothing a local repair could stand on) */
+			p.ctl[CTL_NSLOG0(p) + sc] = (unsigned)(tables_ok ? nslog : K2_SLOG_LIM(p) + 1);	/* (no tables: nothing a local repair could stand on) */
 		if (first_pass && tables_ok && nslog > K2_SLOG_LIM(p))
 			K2_COUNT(p, K2_DBG_ESC_SLOG);
 	}
@@ -710,7 +710,7 @@ void k2c_resolve(K2Params p)
 	MachCtx cx;
 	mach_ctx(cx, p, s, c, true);	/* bursts of serial stretches become descriptors too */
 	cx.sel = (p.round > 0 ? p.sel_list2 : p.sel_list) + (size_t)sc * VDL2_SEL_CAP;
-	cx.nsel = p.ctl + (p.round > 0 ? CTL_NSEL1 : CTL_NSEL0) + sc;
+	cx.nsel = p.ctl + (p.round > 0 ? CTL_NSEL1(p) : CTL_NSEL0(p)) + sc;
 	MachState st = mach_state(cs);
 	const bool lazy = !p.full_scan && !p.full_round;	/* (a full round's tables hold every class: nothing is left to verify) */
 	mach_init_taps(sh);
@@ -719,7 +719,7 @@ void k2c_resolve(K2Params p)
 	mach_out_clear(out);
 	unsigned long long n_slow = 0;
 	int ncand = (int)p.ctl[CTL_CAND0 + sc];
-	const bool tables_ok = !p.force_serial && ncand <= VDL2_CAND_CAP && p.ctl[CTL_CAND0 + p.nstreams * VDL2_CS + sc] == 0;
+	const bool tables_ok = !p.force_serial && ncand <= VDL2_CAND_CAP && p.ctl[CTL_CANDOVF0(p) + sc] == 0;
 	if (!tables_ok)
 		ncand = 0;
 	/* What a local repair (k2p_patch) needs of this pass: which candidates the chain met in the history-free state (a repaired
@@ -805,7 +805,7 @@ void k2c_resolve(K2Params p)
 			mach_materialize<K2_NT, false>(sh, cx, st.pos, st.r);
 			replay = true;
 			if (tid == 0 && p.dbg)
-				atomicAdd(p.dbg + 25, 1ull);	/* replays of clusters K2b did not make */
+				atomicAdd(p.dbg + K2_DBG_K2C_REPLAYS, 1ull);	/* replays of clusters K2b did not make */
 			continue;
 		}
 		/* CL_NONSTEADY: its bursts count, then continue from the explicit state it stopped in */
@@ -819,7 +819,7 @@ void k2c_resolve(K2Params p)
 			++nvis;
 		}
 		if (tid == 0 && p.dbg)
-			atomicAdd(p.dbg + 26, 1ull);	/* non-steady clusters continued serially */
+			atomicAdd(p.dbg + K2_DBG_K2C_NONSTEADY, 1ull);	/* non-steady clusters continued serially */
 		mach_resume(sh, st, &cl->saved);
 	}
 	__syncthreads();
@@ -849,14 +849,14 @@ void k2c_resolve(K2Params p)
 		cs_out->n_redo = cs->n_redo;
 		if (p.dbg) {
 			const long long tk4 = wall_clock64();
-			atomicAdd(p.dbg + 16, (unsigned long long)(tk1 - tk0));
-			atomicAdd(p.dbg + 17, (unsigned long long)(tk2 - tk1));
-			atomicAdd(p.dbg + 18, (unsigned long long)(tk3 - tk2));
-			atomicAdd(p.dbg + 19, (unsigned long long)(tk4 - tk3));
-			atomicAdd(p.dbg + 20, 1ull);
-			atomicAdd(p.dbg + 27, (unsigned long long)ncand);
-			atomicAdd(p.dbg + 28, (unsigned long long)ks.walk[3]);	/* visited-list entries */
-			atomicAdd(p.dbg + 29, n_slow);
+			atomicAdd(p.dbg + K2_DBG_K2C_LOAD_TICKS, (unsigned long long)(tk1 - tk0));
+			atomicAdd(p.dbg + K2_DBG_K2C_TABLES_TICKS, (unsigned long long)(tk2 - tk1));
+			atomicAdd(p.dbg + K2_DBG_K2C_WALK_TICKS, (unsigned long long)(tk3 - tk2));
+			atomicAdd(p.dbg + K2_DBG_K2C_PUBLISH_TICKS, (unsigned long long)(tk4 - tk3));
+			atomicAdd(p.dbg + K2_DBG_K2C_CALLS, 1ull);
+			atomicAdd(p.dbg + K2_DBG_K2C_CANDS, (unsigned long long)ncand);
+			atomicAdd(p.dbg + K2_DBG_K2C_VISITED, (unsigned long long)ks.walk[3]);	/* visited-list entries */
+			atomicAdd(p.dbg + K2_DBG_K2C_SERIAL_SAMPLES, n_slow);
 		}
 	}
 }
@@ -1011,7 +1011,7 @@ __device__ __forceinline__ void k2p_check_onchain(const K2Params &p, int sc, int
 		return;
 	const unsigned dyn_base = (unsigned)p.nstreams * VDL2_CS * VDL2_CAND_CAP * VDL2_CL_MAXB;
 	const unsigned *sel0 = p.sel_list + (size_t)sc * VDL2_SEL_CAP;
-	unsigned n0 = p.ctl[CTL_NSEL0 + sc];
+	unsigned n0 = p.ctl[CTL_NSEL0(p) + sc];
 	n0 = n0 > VDL2_SEL_CAP ? VDL2_SEL_CAP : n0;
 	for (unsigned i = 0; i < n0; ++i) {
 		const unsigned slot = sel0[i];
@@ -1043,9 +1043,9 @@ void k2p_patch(K2Params p)
 		return;		/* verified in the first pass: nothing to repair */
 	__syncthreads();
 	const int ncand = (int)p.ctl[CTL_CAND0 + sc];
-	const unsigned ovf_in = p.ctl[CTL_CAND0 + p.nstreams * VDL2_CS + sc];
-	const int nold = (int)p.ctl[CTL_NCLUST0 + sc], nnew = ncand - nold;
-	const unsigned nslog_in = p.ctl[CTL_NSLOG0 + sc];
+	const unsigned ovf_in = p.ctl[CTL_CANDOVF0(p) + sc];
+	const int nold = (int)p.ctl[CTL_NCLUST0(p) + sc], nnew = ncand - nold;
+	const unsigned nslog_in = p.ctl[CTL_NSLOG0(p) + sc];
 	if (tid == 0)
 		k2_begin_repair(p, sc, 0);	/* (the windows are listed at the end) */
 	/* what cannot be repaired locally stays failed (fail[] keeps its value): the next round, or K2f, takes the channel from its input state */
@@ -1073,7 +1073,7 @@ void k2p_patch(K2Params p)
 	const uint8_t *onchain = p.onchain + (size_t)sc * VDL2_CAND_CAP;
 	const Cluster *clusters = p.clusters + (size_t)sc * VDL2_CAND_CAP;
 	unsigned *sel = p.sel_list2 + (size_t)sc * VDL2_SEL_CAP;
-	unsigned *nsel = p.ctl + CTL_NSEL1 + sc;
+	unsigned *nsel = p.ctl + CTL_NSEL1(p) + sc;
 	Seg *segs = p.segs + (size_t)sc * VDL2_SEG_CAP;
 	k2p_rank_new(ps.knew, cands, nold, nnew, tid);
 	MachCtx cx;
@@ -1240,8 +1240,8 @@ void k2p_patch(K2Params p)
 			K2_COUNT(p, K2_DBG_ESC_PATCH_ABANDON);
 		if (tid == 0) {
 			atomicMin(p.fail + sc, 0);
-			p.ctl[CTL_NSEL1 + sc] = 0;
-			p.ctl[CTL_NSEG0 + sc] = 0;
+			p.ctl[CTL_NSEL1(p) + sc] = 0;
+			p.ctl[CTL_NSEG0(p) + sc] = 0;
 		}
 		return;
 	}
@@ -1261,8 +1261,8 @@ void k2p_patch(K2Params p)
 		mach_store(sh, st, cs_out);
 	}
 	if (tid == 0) {
-		p.ctl[CTL_NSEG0 + sc] = (unsigned)nsegs;
-		p.ctl[CTL_NWIN0 + sc] = (unsigned)nwin;
+		p.ctl[CTL_NSEG0(p) + sc] = (unsigned)nsegs;
+		p.ctl[CTL_NWIN0(p) + sc] = (unsigned)nwin;
 		cs_out->n_trig = o_trig - (unsigned long long)sub.x + (unsigned long long)(add_trig + out.ntrig);
 		cs_out->n_reject = o_rej - (unsigned long long)sub.y + (unsigned long long)(add_rej + out.nrej);
 		cs_out->n_burst = o_burst - (unsigned long long)sub.z + (unsigned long long)(add_burst + out.nburst);
@@ -1298,9 +1298,9 @@ void k2f_commit(K2Params p)
 			dst[i] = src[i];
 		/* a channel the repair rounds re-resolved: its selection is final now -- the records K2d's second pass fills */
 		if (tid == 0 && p.sel_reserved && k2_fmask_test(p, sc)) {
-			const unsigned n = p.ctl[CTL_NSEL1 + sc];
+			const unsigned n = p.ctl[CTL_NSEL1(p) + sc];
 			if (n > 0)
-				p.ctl[CTL_SELBASE1 + sc] = atomicAdd(p.outc, n > VDL2_SEL_CAP ? VDL2_SEL_CAP : n);
+				p.ctl[CTL_SELBASE1(p) + sc] = atomicAdd(&p.outc->records, n > VDL2_SEL_CAP ? VDL2_SEL_CAP : n);
 		}
 		return;
 	}
@@ -1323,9 +1323,9 @@ void k2f_commit(K2Params p)
 		cs->n_defer += (unsigned long long)out.ndefer;
 		cs->n_slow += (unsigned long long)(st.pos - p0);
 		cs->n_redo += 1;
-		atomicAdd(p.outc_total_redo, 1u);
-		p.ctl[CTL_NSEL1 + sc] = 0;	/* K2d: nothing of the resolver's for this channel (it is masked: K2d reads the repair rounds' selection) ... */
-		p.ctl[CTL_NWIN0 + sc] = VDL2_WIN_ALL;
+		atomicAdd(&p.outc_total->redo, 1u);
+		p.ctl[CTL_NSEL1(p) + sc] = 0;	/* K2d: nothing of the resolver's for this channel (it is masked: K2d reads the repair rounds' selection) ... */
+		p.ctl[CTL_NWIN0(p) + sc] = VDL2_WIN_ALL;
 		p.redo[sc] = 1;			/* (... also where the mask does not reach: K2d's one pass behind the commit asks this word) */
 		k2_fmask_set(p, sc);		/* ... and if K2d ran ahead of the verify pass, the host drops what it made of it */
 	}
@@ -1352,9 +1352,9 @@ void k2f_commit_fb(K2Params p, vdl2gpu_fb_t *fb)
 		for (int i = tid; i < (int)(sizeof(ChanState) / 4); i += K2_NT)
 			dst[i] = src[i];
 		if (tid == 0 && p.sel_reserved && k2_fmask_test(p, sc)) {
-			const unsigned n = p.ctl[CTL_NSEL1 + sc];
+			const unsigned n = p.ctl[CTL_NSEL1(p) + sc];
 			if (n > 0)
-				p.ctl[CTL_SELBASE1 + sc] = atomicAdd(p.outc, n > VDL2_SEL_CAP ? VDL2_SEL_CAP : n);
+				p.ctl[CTL_SELBASE1(p) + sc] = atomicAdd(&p.outc->records, n > VDL2_SEL_CAP ? VDL2_SEL_CAP : n);
 		}
 		return;
 	}
@@ -1377,9 +1377,9 @@ void k2f_commit_fb(K2Params p, vdl2gpu_fb_t *fb)
 		cs->n_defer += (unsigned long long)out.ndefer;
 		cs->n_slow += (unsigned long long)(st.pos - p0);
 		cs->n_redo += 1;
-		atomicAdd(p.outc_total_redo, 1u);
-		p.ctl[CTL_NSEL1 + sc] = 0;
-		p.ctl[CTL_NWIN0 + sc] = VDL2_WIN_ALL;
+		atomicAdd(&p.outc_total->redo, 1u);
+		p.ctl[CTL_NSEL1(p) + sc] = 0;
+		p.ctl[CTL_NWIN0(p) + sc] = VDL2_WIN_ALL;
 		p.redo[sc] = 1;
 		k2_fmask_set(p, sc);
 	}
@@ -1417,23 +1417,23 @@ template <bool LEV, bool SOFT, bool CAR = false, bool FB = false> __device__ __f
 		return;
 	/* Which selection.  The first resolver pass's (sel_list) stands but for what the repair rounds made void of it (CTL_NWIN0: the
 	 * bursts triggered inside the windows of a local repair, or all of it), the rounds' own (sel_list2) comes on top.
-	 *   sel_mode 0: the first selection of every channel, beside the verify pass (nothing is known of any repair yet; records tagged 0);
-	 *   sel_mode 1: second pass, behind the commit: only the channels a round touched (masked) -- the first pass's records that have
-	 *               become void are tagged 2 (the host and K4 drop those), the rounds' selection is decoded (records tagged 1);
-	 *   sel_mode 2: the one pass behind the commit of handles that cannot run the decode ahead (more than 512 channel slots: the 16-word
+	 *   SEL_FIRST: the first selection of every channel, beside the verify pass (nothing is known of any repair yet; records tagged REC_FIRST);
+	 *   SEL_REPAIRED: second pass, behind the commit: only the channels a round touched (masked) -- the first pass's records that have
+	 *               become void are tagged REC_VOID (the host and K4 drop those), the rounds' selection is decoded (records tagged REC_FINAL);
+	 *   SEL_FINAL: the one pass behind the commit of handles that cannot run the decode ahead (more than VDL2_FMASK_SLOTS channel slots: the
 	 *               mask does not cover them; complete scans): what stands of the first selection, then the rounds' selection. */
-	const bool touched = p.sel_mode == 2 ? p.redo[sc] != 0 : k2_fmask_test(p, sc);
-	if (p.sel_mode == 1 && !touched)
+	const bool touched = p.sel_mode == SEL_FINAL ? p.redo[sc] != 0 : k2_fmask_test(p, sc);
+	if (p.sel_mode == SEL_REPAIRED && !touched)
 		return;
-	const unsigned nwin = (p.sel_mode != 0 && touched) ? p.ctl[CTL_NWIN0 + sc] : 0u;
+	const unsigned nwin = (p.sel_mode != SEL_FIRST && touched) ? p.ctl[CTL_NWIN0(p) + sc] : 0u;
 	const int2 *win = p.win + (size_t)sc * VDL2_WIN_CAP;
-	unsigned n0 = p.ctl[CTL_NSEL0 + sc], n1 = (p.sel_mode != 0 && touched) ? p.ctl[CTL_NSEL1 + sc] : 0u;
+	unsigned n0 = p.ctl[CTL_NSEL0(p) + sc], n1 = (p.sel_mode != SEL_FIRST && touched) ? p.ctl[CTL_NSEL1(p) + sc] : 0u;
 	n0 = n0 > VDL2_SEL_CAP ? VDL2_SEL_CAP : n0;
 	n1 = n1 > VDL2_SEL_CAP ? VDL2_SEL_CAP : n1;
 	const unsigned *sel0 = p.sel_list + (size_t)sc * VDL2_SEL_CAP, *sel1 = p.sel_list2 + (size_t)sc * VDL2_SEL_CAP;
-	if (p.sel_mode == 1 && nwin != 0 && p.sel_reserved) {
+	if (p.sel_mode == SEL_REPAIRED && nwin != 0 && p.sel_reserved) {
 		/* the first pass's records of this channel lie in one piece from CTL_SELBASE0 on: tag what has become void */
-		const unsigned base0 = p.ctl[CTL_SELBASE0 + sc];
+		const unsigned base0 = p.ctl[CTL_SELBASE0(p) + sc];
 		for (unsigned i = blockIdx.x * K2D_NT + threadIdx.x; i < n0; i += gridDim.x * K2D_NT) {
 			if (base0 + i >= p.rec_cap)
 				break;
@@ -1447,11 +1447,11 @@ template <bool LEV, bool SOFT, bool CAR = false, bool FB = false> __device__ __f
 			}
 #endif
 			if (nwin == VDL2_WIN_ALL || k2_in_windows(p, win, nwin, rec->trig_dec - p.dec_base))	/* invariant (b) at CTL_NWIN0 */
-				rec->trig_sample = 2;
+				rec->trig_sample = REC_VOID;
 		}
 	}
 	/* the bursts this launch decodes for the channel: entries [0, na) of the first selection, then [0, n1) of the rounds' */
-	const unsigned na = p.sel_mode == 1 ? 0u : ((p.sel_mode == 2 && nwin == VDL2_WIN_ALL) ? 0u : n0);
+	const unsigned na = p.sel_mode == SEL_REPAIRED ? 0u : ((p.sel_mode == SEL_FINAL && nwin == VDL2_WIN_ALL) ? 0u : n0);
 	const unsigned n = na + n1;
 	if (blockIdx.x >= n)
 		return;
@@ -1467,12 +1467,12 @@ template <bool LEV, bool SOFT, bool CAR = false, bool FB = false> __device__ __f
 	}
 	__syncthreads();
 	/* reserved by K2c (first selection) and K2f (the rounds' selection, when it is final): K2d fills them without atomics */
-	const unsigned base0 = p.ctl[CTL_SELBASE0 + sc], base1 = p.ctl[CTL_SELBASE1 + sc];
+	const unsigned base0 = p.ctl[CTL_SELBASE0(p) + sc], base1 = p.ctl[CTL_SELBASE1(p) + sc];
 	for (unsigned i = blockIdx.x; i < n; i += gridDim.x) {
 		const bool second = i >= na;
 		const BurstDesc d = p.stage[second ? sel1[i - na] : sel0[i]];
 		/* (block-uniform) a burst of the first selection inside a repaired window: not on the chain any more */
-		if (!second && p.sel_mode == 2 && nwin != 0 && k2_in_windows(p, win, nwin, d.nstar - p.dec_base))
+		if (!second && p.sel_mode == SEL_FINAL && nwin != 0 && k2_in_windows(p, win, nwin, d.nstar - p.dec_base))
 			continue;
 #ifdef VDL2GPU_TESTHOOKS
 		{	/* invariant (b) at CTL_NWIN0: a cluster's first descriptor (static slot, burst 0) against its candidate */
@@ -1490,19 +1490,19 @@ template <bool LEV, bool SOFT, bool CAR = false, bool FB = false> __device__ __f
 		else {
 			__syncthreads();
 			if (threadIdx.x == 0)
-				s_slot = atomicAdd(p.outc, 1u);
+				s_slot = atomicAdd(&p.outc->records, 1u);
 			__syncthreads();
 			slot = s_slot;
 		}
 		if (slot >= p.rec_cap) {	/* ring full: counted, never silent */
 			if (threadIdx.x == 0)
-				atomicAdd(p.outc + 1, 1u);
+				atomicAdd(&p.outc->dropped, 1u);
 			slot = 0xffffffffu;
 		}
 		if (slot != 0xffffffffu) {
 			const int s = d.sc / VDL2_CS;
 			const float2 *x0 = p.dec + (size_t)d.sc * p.cap - p.dec_base;
-			burst_payload<K2D_NT, true>(p.recs + slot, x0, p.pn, d.nstar, d.clk0, d.df, d.nbrow, d.nlbyte, s, p.cfg[d.sc], sph, p.sel_mode == 0 ? 0 : 1, d.sc, s_tabs, p.pn8);
+			burst_payload<K2D_NT, true>(p.recs + slot, x0, p.pn, d.nstar, d.clk0, d.df, d.nbrow, d.nlbyte, s, p.cfg[d.sc], sph, p.sel_mode == SEL_FIRST ? REC_FIRST : REC_FINAL, d.sc, s_tabs, p.pn8);
 			if (LEV && threadIdx.x < 64)
 				burst_payload_levels(p.levels + slot, x0, d.nstar, d.clk0, d.nbrow, d.nlbyte, s_tabs, p.dec_base);
 			if (SOFT) {

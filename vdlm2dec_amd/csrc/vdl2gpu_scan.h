@@ -88,7 +88,7 @@ struct alignas(16) K2aShared {
 	unsigned it_used, it_limit;	/* items the workgroup has put into its private area; where the first group that did not fit would have begun */
 	unsigned short pend[K2A_THREADS / 64][K2A_TS / (K2A_THREADS / 64)];	/* per wavefront: the evaluations of a tile and sub-phase that passed the
 					 * first screen (instant within the tile | 0x8000: a non-finite phasor), appended as ONE group behind the screen passes */
-	unsigned long long prof[16];	/* diagnostics: stage cycle counters of the workgroup's first lane, added to p.dbg at the end
+	unsigned long long prof[K2A_ST_SLOTS];	/* diagnostics: stage cycle counters of the workgroup's first lane, added to p.dbg at the end
 					 * (a global atomic per stamp would sit in front of the tile's next s_waitcnt vmcnt) */
 };
 static_assert(K2A_WU1 % 2 == 0 && K2A_XS_LEN >= K2A_XMAX + 8 && (K2A_XMAX / 2 + 4) % 2 == 0, "16-byte reads of xs[] and wu[]");
@@ -160,16 +160,16 @@ template <class PR> __device__ __forceinline__ void k2a_emit(PR p, int sc, long 
 						  long long chk_lo, long long chk_hi, int *fail, int skip_r, int skip_par,
 						  float p2err, float perr, float err, float pfr, unsigned *cntp, unsigned *ovf, Cand *cl)
 {
-	if (mode >= 2 && perr < VDL2_SEED_ERR && err > perr) {
-		const unsigned kk = atomicAdd(p.ctl + CTL_NSEED0 + sc, 1u);
+	if (mode >= SURV_PROBE && perr < VDL2_SEED_ERR && err > perr) {
+		const unsigned kk = atomicAdd(p.ctl + CTL_NSEED0(p) + sc, 1u);
 		if (kk < VDL2_CAND_CAP)	/* surplus seeds are simply dropped: K2a-verify covers what they would have */
 			p.seeds[(size_t)sc * VDL2_CAND_CAP + kk] = (int)(n - dec_base);
 	}
-	if (mode == 3)	/* (no scan runs in this mode: see the legend above k2a_append) */
+	if (mode == SURV_SEEDS_NEVER_SET)	/* (no scan runs in this mode: see the legend above k2a_append) */
 		return;
 	if (!(perr < 4.0f && err > perr))
 		return;
-	if (mode == 0 || mode == 2) {
+	if (mode == SURV_CANDS || mode == SURV_PROBE) {
 		if (r == skip_r && (int)(n & 1) == skip_par)
 			return;	/* that class is the probe's: already in the table */
 		/* The free-running test fires at EVERY rising step while the previous error is below 4 -- two or three instants
@@ -239,10 +239,10 @@ __device__ __forceinline__ void k2a_tables(K2aShared &sh)
  * the other three waited at the barrier -- a third of the probe's time -- and the exact work's live registers on top of the
  * tile loop's capped the scan kernels at four wavefronts per SIMD; round 4 ran them as a kernel of its own behind every scan:
  * four more launches a push, 30 us each as they ran.  Behind the tile loop the exact work has the registers to itself.]
- * The scan modes (K2Params.surv_mode; host side: SURV_*) -- 0: append candidates (region scan, complete scan); 1: verify pass, report
- * hits in [chk_lo, chk_hi) to *fail and append them; 2: probe, candidates of its class and seeds for the region scan.
- * [Mode 3, seeds without candidates, was the probe at every fourth sample's (measured twice and dropped: DESIGN.md section 8.4).  No
- * host code sets it any more; k2a_emit's test for it and the `mode >= 2` there and in k2x_chunk are what is left, because `mode` is
+ * The scan modes (K2Params.surv_mode: SURV_*) -- SURV_CANDS: append candidates (region scan, complete scan); SURV_VERIFY: verify pass, report
+ * hits in [chk_lo, chk_hi) to *fail and append them; SURV_PROBE: probe, candidates of its class and seeds for the region scan.
+ * [SURV_SEEDS_NEVER_SET (3), seeds without candidates, was the probe at every fourth sample's (measured twice and dropped: DESIGN.md section 8.4).  No
+ * host code sets it any more; k2a_emit's test for it and the `mode >= SURV_PROBE` there and in k2x_chunk are what is left, because `mode` is
  * a run-time value in the sparse stages and the compiler allots the registers of all eight kernels that hold them differently
  * without the tests: taking them out is a change to measure, not a tidying.] */
 
@@ -267,12 +267,12 @@ __device__ __forceinline__ void k2a_append(K2aShared &sh, const K2Params &p, int
 			 * the common area behind the private ones, through the channel's counter in device memory */
 			atomicMin(&sh.it_limit, off);
 			const unsigned priv = (unsigned)p.surv_nwg * pch;
-			const unsigned off2 = atomicAdd(p.ctl + CTL_NSURV0 + p.surv_slot * p.nstreams * VDL2_CS + sc, cnt);
+			const unsigned off2 = atomicAdd(p.ctl + CTL_NSURV0(p) + p.surv_slot * p.nstreams * VDL2_CS + sc, cnt);
 			stride = p.item_cap - priv;
 			const unsigned room = (p.surv_common_cap > 0 && (unsigned)p.surv_common_cap < stride) ? (unsigned)p.surv_common_cap : stride;
 			base = (off2 + cnt <= room) ? priv * K2A_ITEM_WORDS + off2 : 0xffffffffu;
 			if (base == 0xffffffffu)	/* refused: the drain must not read the common area from here on (nothing was written there) */
-				atomicMax(p.ctl + CTL_NSURVLIM0 + p.surv_slot * p.nstreams * VDL2_CS + sc, ~off2);
+				atomicMax(p.ctl + CTL_NSURVLIM0(p) + p.surv_slot * p.nstreams * VDL2_CS + sc, ~off2);
 		}
 	}
 	const int lead = __builtin_ctzll(m);
@@ -292,10 +292,10 @@ __device__ __forceinline__ void k2a_append(K2aShared &sh, const K2Params &p, int
 				c[l].v = __builtin_amdgcn_cvt_pknorm_i16(uu[4 * w + l].x, uu[4 * w + l].y);
 			dst[(size_t)(1 + w) * stride] = make_float4(__int_as_float(c[0].i), __int_as_float(c[1].i), __int_as_float(c[2].i), __int_as_float(c[3].i));
 		}
-	} else if (mode == 1)
+	} else if (mode == SURV_VERIFY)
 		atomicMin(fail, 0);	/* the verify pass cannot vouch for the channel: it is re-resolved, in the end redone serially */
 	else
-		p.ctl[CTL_CAND0 + p.nstreams * VDL2_CS + sc] = 1u;	/* as if the candidate table had overflowed: the serial machine takes the channel */
+		p.ctl[CTL_CANDOVF0(p) + sc] = 1u;	/* as if the candidate table had overflowed: the serial machine takes the channel */
 }
 
 /* the fourth screen's fit error from the sixteen rotated phase-step phasors (see k2_fast_angle) */
@@ -362,7 +362,7 @@ __device__ __forceinline__ void k2x_chunk(K2xWork &sh, PR p, int sc, int mode, i
 	constexpr float C1 = 0.92387953251128674f, S1 = 0.38268343236508977f;
 	constexpr float rc[16] = {C1, -C1, -S1, -C1, C1, S1, S1, -C1, S1, C1, -S1, -S1, S1, -S1, C1, -C1};
 	constexpr float rs[16] = {-S1, -S1, -C1, S1, -S1, -C1, C1, S1, -C1, S1, -C1, C1, C1, C1, S1, -S1};
-	const float fit_limit = mode >= 2 ? VDL2_SEED_ERR + VDL2_FIT_MARGIN : 4.0f + VDL2_FIT_MARGIN;
+	const float fit_limit = mode >= SURV_PROBE ? VDL2_SEED_ERR + VDL2_FIT_MARGIN : 4.0f + VDL2_FIT_MARGIN;
 	int st = 0;
 	float erra = 0.0f;
 	K2aDef d{};
@@ -464,7 +464,7 @@ __device__ __forceinline__ void k2x_chunk(K2xWork &sh, PR p, int sc, int mode, i
 			pv = tid - 2;
 		if (nx >= 0 && sh.it_ea[nx] < erra - VDL2_NB_MARGIN)
 			st = 0;
-		const bool first_only = (mode == 0 || mode == 2) && p.round == 0 && !p.full_scan;	/* k2a_emit's condition */
+		const bool first_only = (mode == SURV_CANDS || mode == SURV_PROBE) && p.round == 0 && !p.full_scan;	/* k2a_emit's condition */
 		if (first_only && pv >= 0 && sh.it_ea[pv] < 4.0f - VDL2_NB_MARGIN && erra > sh.it_ea[pv] + VDL2_NB_MARGIN)
 			st = 0;
 	}
@@ -490,7 +490,7 @@ __device__ __forceinline__ void k2x_chunk(K2xWork &sh, PR p, int sc, int mode, i
 	int *fail = p.fail + sc;
 	const float2 *x0 = p.dec + (size_t)sc * p.cap;	/* x0[n] = sample at stream-relative time n */
 	unsigned *cntp = p.ctl + CTL_CAND0 + sc;
-	unsigned *ovf = p.ctl + CTL_CAND0 + p.nstreams * VDL2_CS + sc;
+	unsigned *ovf = p.ctl + CTL_CANDOVF0(p) + sc;
 	Cand *cl = p.cands + (size_t)sc * VDL2_CAND_CAP;
 	for (int b0 = 0; b0 < nd; b0 += K2X_WL) {
 		const int nb = (nd - b0 < K2X_WL) ? nd - b0 : K2X_WL;
@@ -606,9 +606,9 @@ template <int NT> __device__ void k2x_drain(K2xWork &w, const K2Params &p, int s
 		return;
 	const unsigned pch = (unsigned)p.drain_pch, priv = (unsigned)p.drain_nwg * pch;
 	const unsigned stride = p.item_cap - priv;
-	unsigned nc = p.ctl[CTL_NSURV0 + p.drain_slot * p.nstreams * VDL2_CS + sc];
+	unsigned nc = p.ctl[CTL_NSURV0(p) + p.drain_slot * p.nstreams * VDL2_CS + sc];
 	{
-		const unsigned lim = ~p.ctl[CTL_NSURVLIM0 + p.drain_slot * p.nstreams * VDL2_CS + sc];
+		const unsigned lim = ~p.ctl[CTL_NSURVLIM0(p) + p.drain_slot * p.nstreams * VDL2_CS + sc];
 		nc = nc > lim ? lim : nc;
 	}
 	nc = nc > stride ? stride : nc;	/* (a group that did not fit reserved past the end and wrote nothing: k2a_append; what lies below the first
@@ -716,7 +716,7 @@ template <int S> __device__ void k2a_tile(K2aShared &sh, const K2Params &p, int 
 	static_assert(K2A_POFF == S * PH, "phase history must be a whole number of instants");
 	float2 *const wu = (S != 1) ? sh.xs : sh.xs + K2A_WU1;	/* phase-step phasors (see K2aShared) */
 	const int nx = S * (cnt - 1) + 1 + K2A_XOFF;
-	const bool prof = p.dbg && (mode == 2 || (mode == 0 && S == 1 && !p.full_scan && !p.full_round)) && tid == 0 && (blockIdx.x & 7) == 0;	/* probe, region scan */
+	const bool prof = p.dbg && (mode == SURV_PROBE || (mode == SURV_CANDS && S == 1 && !p.full_scan && !p.full_round)) && tid == 0 && (blockIdx.x & 7) == 0;	/* probe, region scan */
 	long long tq = prof ? clock64() : 0;
 #define K2A_STAMP(slot) do { if (prof) { const long long tn = clock64(); sh.prof[slot] += (unsigned long long)(tn - tq); tq = tn; } } while (0)
 	/* park slots: sample i = tid + k * K2A_THREADS of the tile goes to xs[pbase + k * pstep] */
@@ -732,15 +732,15 @@ template <int S> __device__ void k2a_tile(K2aShared &sh, const K2Params &p, int 
 		for (int k = 0; k < NL; ++k)
 			if (tid + k * K2A_THREADS < nx)
 				v[k] = x[tid + k * K2A_THREADS];
-		K2A_STAMP(12);
+		K2A_STAMP(K2A_ST_TILES_OR_WAIT);
 #pragma unroll
 		for (int k = 0; k < NL; ++k)
 			if (tid + k * K2A_THREADS < nx)
 				sh.xs[pbase + k * pstep] = v[k];
 	}
-	K2A_STAMP(13);
+	K2A_STAMP(K2A_ST_PARK);
 	__syncthreads();
-	K2A_STAMP(0);
+	K2A_STAMP(K2A_ST_STAGE_IN);
 	const int npairs = (cnt + PH + 1) / 2;
 	const int wv = tid >> 6, ln = tid & 63;
 	const int src_lane = (ln - KH) * 4;	/* ds_bpermute address of the lane KH down (wraps for the first KH lanes: their result is not used) */
@@ -773,17 +773,17 @@ template <int S> __device__ void k2a_tile(K2aShared &sh, const K2Params &p, int 
 					       __fmaf_rn(w1.x, p1x, w1.y * p1y), __fmaf_rn(w1.y, p1x, -(w1.x * p1y)));
 			__builtin_amdgcn_sched_barrier(0);	/* one round's nineteen samples in registers at a time */
 		}
-		K2A_STAMP(1);
+		K2A_STAMP(K2A_ST_FIR_UNIT);
 		if (S != 1)
 			__syncthreads();	/* wu[] is xs[]: every wavefront is through with the samples */
-		K2A_STAMP(2);
+		K2A_STAMP(K2A_ST_BARRIER_SAMPLES);
 #pragma unroll
 		for (int it = 0; it < NIT; ++it) {
 			const int q0 = 2 * (it * PPI + wv * PPW + ln - KH);
 			if (ln >= KH && q0 >= LSTR && q0 < cnt + PH)	/* (the odd one out at the end lands in wu[]'s padding) */
 				*reinterpret_cast<float4 *>(&wu[q0]) = hold[it];
 		}
-		K2A_STAMP(3);
+		K2A_STAMP(K2A_ST_STEPS);
 		__syncthreads();
 		/* ---- first screen, of the evaluation that is the `perr` of instant i: j = i + E2.  What passes (2.7 % on noise: seven of a
 		 *      wavefront's 256 evaluations) is only NOTED here, two bytes in the wavefront's own queue; the items -- sixteen phasors
@@ -821,7 +821,7 @@ template <int S> __device__ void k2a_tile(K2aShared &sh, const K2Params &p, int 
 			const v2f acc = {__fmaf_rn(qa.x - qa.y, RH, pa.x), __fmaf_rn(qa.x + qa.y, RH, pa.y)};
 			const float r2 = __fmaf_rn(acc.x, acc.x, acc.y * acc.y);
 			bool pass = i < cnt && !(r2 <= VDL2_SCREEN_R2);
-			if (mode == 0 && r == skip_r && (int)((nbase + S * (j - E4)) & 1) == skip_par)
+			if (mode == SURV_CANDS && r == skip_r && (int)((nbase + S * (j - E4)) & 1) == skip_par)
 				pass = false;	/* region scan: that class is the probe's, its hits are in the table already */
 			const unsigned long long m = __ballot(pass);
 			if (m != 0) {
@@ -841,15 +841,15 @@ template <int S> __device__ void k2a_tile(K2aShared &sh, const K2Params &p, int 
 			for (int l = 0; l < 16; ++l)
 				uu[l] = uq[l * LSTR];
 			const long long n_abs = nbase + S * (j - E4);	/* the evaluation's instant */
-			k2a_append(sh, p, sc, on, (int)(n_abs - dec_base), r, (mode == 1) ? (int)(chk_lo - dec_base) : 0,
-				   (mode == 1) ? (int)(chk_hi - dec_base) : 0, uu, (e & 0x8000) != 0, mode, fail);
+			k2a_append(sh, p, sc, on, (int)(n_abs - dec_base), r, (mode == SURV_VERIFY) ? (int)(chk_lo - dec_base) : 0,
+				   (mode == SURV_VERIFY) ? (int)(chk_hi - dec_base) : 0, uu, (e & 0x8000) != 0, mode, fail);
 		}
-		K2A_STAMP(4);
-		K2A_STAMP(8);
+		K2A_STAMP(K2A_ST_SCREEN);
+		K2A_STAMP(K2A_ST_SCREEN_END);
 		__syncthreads();
-		K2A_STAMP(9);
+		K2A_STAMP(K2A_ST_BARRIER_TILE);
 		if (prof)
-			sh.prof[11] += 1ull;
+			sh.prof[K2A_ST_PASSES] += 1ull;
 	}
 #undef K2A_STAMP
 }
@@ -866,7 +866,7 @@ void k2a_probe(K2Params p)
 		return;
 	if (p.round > 0 && (!p.full_round || p.fail[sc] >= VDL2_VERIFIED))
 		return;		/* in a repair round the probe only runs as the complete scan of a failing channel */
-	if (threadIdx.x < 16)
+	if (threadIdx.x < K2A_ST_SLOTS)
 		sh.prof[threadIdx.x] = 0;
 	k2a_tables(sh);
 	/* each workgroup walks tiles blockIdx.x, blockIdx.x + gridDim.x, ... of its channel */
@@ -874,7 +874,7 @@ void k2a_probe(K2Params p)
 		const long long step = (long long)gridDim.x * K2A_TS;
 		for (long long n0 = p.scan_lo + (long long)blockIdx.x * K2A_TS; n0 < avail_end; n0 += step) {
 			const int nt = (int)((avail_end - n0 < K2A_TS) ? (avail_end - n0) : K2A_TS);
-			k2a_tile<1>(sh, p, sc, dec_base, n0, nt, 0xfu, 0, 0, 0, nullptr);
+			k2a_tile<1>(sh, p, sc, dec_base, n0, nt, 0xfu, SURV_CANDS, 0, 0, nullptr);
 		}
 		k2a_tail(sh, sc);
 		return;
@@ -887,11 +887,11 @@ void k2a_probe(K2Params p)
 	for (long long n0 = p.scan_lo + 2LL * blockIdx.x * K2A_TS; n0 < avail_end; n0 += step) {
 		const long long left = (avail_end - n0 + 1) / 2;
 		const int nt = (int)(left < K2A_TS ? left : K2A_TS);
-		k2a_tile<2>(sh, p, sc, dec_base, n0, nt, rmask, 2, 0, 0, nullptr);
+		k2a_tile<2>(sh, p, sc, dec_base, n0, nt, rmask, SURV_PROBE, 0, 0, nullptr);
 	}
 	k2a_tail(sh, sc);
-	if (p.dbg && threadIdx.x < 16 && sh.prof[threadIdx.x])
-		atomicAdd(p.dbg + 32 + threadIdx.x, sh.prof[threadIdx.x]);
+	if (p.dbg && threadIdx.x < K2A_ST_SLOTS && sh.prof[threadIdx.x])
+		atomicAdd(p.dbg + K2_DBG_PROBE_STAGE0 + threadIdx.x, sh.prof[threadIdx.x]);
 }
 
 /* ---- workgroup sort of up to VDL2_CAND_CAP 64-bit keys whose top bits are a time stamp.
@@ -1035,14 +1035,14 @@ void k2r_regions(K2Params p)
 		/* the channel's tables are made again from nothing, by a scan of every class at every instant */
 		if (tid == 0) {
 			p.ctl[CTL_CAND0 + sc] = 0;
-			p.ctl[CTL_CAND0 + p.nstreams * VDL2_CS + sc] = 0;
-			p.ctl[CTL_NCLUST0 + sc] = 0;
-			p.ctl[CTL_NREG0 + sc] = 0;
-			p.ctl[CTL_NSEED0 + sc] = 0;
+			p.ctl[CTL_CANDOVF0(p) + sc] = 0;
+			p.ctl[CTL_NCLUST0(p) + sc] = 0;
+			p.ctl[CTL_NREG0(p) + sc] = 0;
+			p.ctl[CTL_NSEED0(p) + sc] = 0;
 		}
 		return;
 	}
-	int ncand = (int)p.ctl[CTL_NSEED0 + sc];
+	int ncand = (int)p.ctl[CTL_NSEED0(p) + sc];
 	ncand = ncand > VDL2_CAND_CAP ? VDL2_CAND_CAP : ncand;
 	const int *seeds = p.seeds + (size_t)sc * VDL2_CAND_CAP;
 	for (int i = tid; i < ncand; i += K2R_NT)	/* the index makes equal instants distinct keys (the sort ranks keys) */
@@ -1107,10 +1107,10 @@ void k2r_regions(K2Params p)
 			const int n = s_nreg;
 			/* more regions than the list holds: the surplus is dropped -- regions are a cost decision, what a
 			 * missing one would have found the verify pass finds (and a repair round scans the channel completely) */
-			p.ctl[CTL_NREG0 + sc] = (unsigned)(n > K2_REG_LIM(p) ? K2_REG_LIM(p) : n);
+			p.ctl[CTL_NREG0(p) + sc] = (unsigned)(n > K2_REG_LIM(p) ? K2_REG_LIM(p) : n);
 			if (n > K2_REG_LIM(p))
 				K2_COUNT(p, K2_DBG_ESC_REG);
-			p.ctl[CTL_NSEED0 + sc] = 0;
+			p.ctl[CTL_NSEED0(p) + sc] = 0;
 		}
 	}
 }
@@ -1131,29 +1131,29 @@ void k2a_region(K2Params p)
 	if (p.test_noregion && p.round == 0)
 		return;
 #endif
-	const unsigned nreg = p.ctl[CTL_NREG0 + sc];	/* (round 0 only: a repair round re-resolves or re-scans completely, it scans no regions) */
+	const unsigned nreg = p.ctl[CTL_NREG0(p) + sc];	/* (round 0 only: a repair round re-resolves or re-scans completely, it scans no regions) */
 	if (blockIdx.x >= nreg)	/* nothing for this workgroup (64 channels x 128 workgroups, 40 regions each): not even the tables */
 		return;
 	const long long dec_base = p.dec_base;
 	const int2 *regs = p.regs + (size_t)sc * VDL2_REG_CAP;
 	const int skip_r = p.probe_r, skip_par = p.probe_par;
-	if (threadIdx.x < 16)
+	if (threadIdx.x < K2A_ST_SLOTS)
 		sh.prof[threadIdx.x] = 0;
 	k2a_tables(sh);
 	const bool prof = p.dbg && threadIdx.x == 0 && (blockIdx.x & 7) == 0;
 	const long long t0 = prof ? clock64() : 0;
 	for (unsigned k = blockIdx.x; k < nreg; k += gridDim.x) {
 		const int2 rg = regs[k];
-		k2a_tile<1>(sh, p, sc, dec_base, dec_base + rg.x, rg.y, 0xfu, 0, 0, 0, nullptr, skip_r, skip_par);
+		k2a_tile<1>(sh, p, sc, dec_base, dec_base + rg.x, rg.y, 0xfu, SURV_CANDS, 0, 0, nullptr, skip_r, skip_par);
 		if (prof)
-			sh.prof[15] += (unsigned long long)rg.y;	/* instants */
+			sh.prof[K2A_ST_INSTANTS] += (unsigned long long)rg.y;
 	}
 	const long long t1 = prof ? clock64() : 0;
 	if (prof)
-		sh.prof[12] += (unsigned long long)(t1 - t0);		/* all tiles */
+		sh.prof[K2A_ST_TILES_OR_WAIT] += (unsigned long long)(t1 - t0);	/* all tiles */
 	k2a_tail(sh, sc);
-	if (p.dbg && threadIdx.x < 16 && sh.prof[threadIdx.x])
-		atomicAdd(p.dbg + 48 + threadIdx.x, sh.prof[threadIdx.x]);
+	if (p.dbg && threadIdx.x < K2A_ST_SLOTS && sh.prof[threadIdx.x])
+		atomicAdd(p.dbg + K2_DBG_REGION_STAGE0 + threadIdx.x, sh.prof[threadIdx.x]);
 }
 
 /* The verify pass's work is the ordered list of a channel's PIECES: stretch k (Seg{lo, hi, r}) yields n_k = ceil(evaluations_k /
@@ -1265,7 +1265,7 @@ void k2a_verify(K2Params p)
 		return;
 	const long long dec_base = p.dec_base;
 	const int t_end = (int)(VDL2_CARRY_FRAMES + p.J);
-	int nseg = (int)p.ctl[CTL_NSEG0 + sc];
+	int nseg = (int)p.ctl[CTL_NSEG0(p) + sc];
 	if (tid == 0 && blockIdx.x == 0 && (nseg < 0 || nseg > K2_SEG_LIM(p)))
 		K2_COUNT(p, K2_DBG_ESC_SEG);
 	nseg = nseg < 0 || nseg > K2_SEG_LIM(p) ? K2_SEG_LIM(p) : nseg;	/* (the resolver counts the stretches the list did not hold as well) */
@@ -1298,10 +1298,10 @@ void k2a_verify(K2Params p)
 	for (;;) {
 		const int ni = b - a;
 		if (p.dbg && tid < ni)	/* slot 30 (free until round 10): evaluation instants of every piece scanned */
-			atomicAdd(p.dbg + 30, (unsigned long long)((s_item[tid].y - s_item[tid].x + 1) / 2));
+			atomicAdd(p.dbg + K2_DBG_VERIFY_INSTANTS, (unsigned long long)((s_item[tid].y - s_item[tid].x + 1) / 2));
 		for (int i = 0; i < ni; ++i) {
 			const int4 it = s_item[i];
-			k2a_tile<2>(sh, p, sc, dec_base, dec_base + it.x, (it.y - it.x + 1) / 2, 1u << it.z, 1, dec_base + it.x, dec_base + it.y,
+			k2a_tile<2>(sh, p, sc, dec_base, dec_base + it.x, (it.y - it.x + 1) / 2, 1u << it.z, SURV_VERIFY, dec_base + it.x, dec_base + it.y,
 				    p.fail + sc);
 		}
 		a = b;

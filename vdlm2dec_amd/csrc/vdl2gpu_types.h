@@ -14,7 +14,7 @@
 #endif
 #define VDL2_NRING VDL2_NSET	/* output rings (records, frames, counters) */
 #define VDL2_NSLAB (VDL2_NSET + 1)	/* page-locked slabs the records are exported to, used in turn */
-static_assert(VDL2_NSET >= 3 && VDL2_NSET <= 4, "d_outc[] has the per-ring counters in front of the running totals at [8]; three bits of a record handle name its slab");
+static_assert(VDL2_NSET >= 3 && VDL2_NSET <= 4, "three bits of a record handle name its slab");
 #define VDL2_HIST 160		/* frames of history kept: 17-tap FIR + 17 symbols x 8 + slack */
 #define VDL2_NPH 68		/* NBPH*D8DWN, vdlm2.h:54-55 */
 #define VDL2_STEADY 68		/* evaluations after which the detector forgot the last burst */
@@ -39,6 +39,46 @@ static_assert(VDL2_LONGEST_BURST >= 7 + 8 * ((25 + 8 * VDL2GPU_MAXROWS * VDL2GPU
 #ifndef M_PI
 #define M_PI 3.14159265358979323846
 #endif
+
+/* ---- the words host and kernels share: counter blocks, modes and tags, development counters (the control words: CTL_* below) ---- */
+struct RingCount {		/* records of one output ring's push */
+	unsigned records, dropped;	/* written; not written because the ring was full */
+};
+struct OutCounters {		/* vdl2gpu.d_outc, device memory */
+	RingCount ring[4];
+	struct Totals {
+		unsigned redo, repairs;	/* since the handle was made: serial redos (k2f_commit); channel-pushes that went through a repair round (k2_begin_repair) */
+	} total;
+	unsigned spare[6];
+};
+static_assert(sizeof(RingCount) == 2 * sizeof(unsigned) && sizeof(OutCounters) == 16 * sizeof(unsigned), "OutCounters is sixteen words");
+static_assert(VDL2_NRING <= sizeof(OutCounters::ring) / sizeof(RingCount), "the rings' counters lie in front of the running totals");
+struct FrameCounters {		/* vdl2gpu.d_fcnt[ring], device memory: the block path's output of one push (VDL2GPU_F_FRAMES) */
+	unsigned frames, dropped;	/* written (compact: to the arena); not written (buffer or arena full) */
+	unsigned arena_asked;	/* arena bytes asked for, failed allocations included */
+	unsigned arena_end;	/* where the arena's last written entry ends: its valid bytes */
+};
+static_assert(sizeof(FrameCounters) == 4 * sizeof(unsigned), "FrameCounters is four words");
+#define VDL2_FMASK_WORDS 16	/* the redo mask: a bit per (stream, channel slot) */
+#define VDL2_FMASK_SLOTS (32 * VDL2_FMASK_WORDS)
+struct PushCounters {		/* vdl2gpu.h_pin_cnt[ring], page-locked: what k3_rebase hands the host of a push */
+	RingCount rec;
+	OutCounters::Totals total;	/* the running totals as they stood behind this push */
+	unsigned frames, frames_dropped, arena_end;	/* FrameCounters without arena_asked; zero without the block path */
+	unsigned cand_ovf;	/* channels whose candidate tables overflowed in this push */
+	unsigned fmask[VDL2_FMASK_WORDS];	/* K2f's redo mask of this push */
+	unsigned cand_max;	/* most candidates of any channel */
+	unsigned spare[7];
+};
+static_assert(sizeof(PushCounters) == 32 * sizeof(unsigned), "PushCounters is the 32 words a ring's block takes");
+#define VDL2_WORD(T, m) ((int)(offsetof(T, m) / sizeof(unsigned)))	/* member m of a counter block, where the block is read as words (k3_rebase) */
+
+/* K2Params.surv_mode / drain_mode: what a detector hit among a scan's survivors means (the legend above k2a_append) */
+enum { SURV_CANDS = 0, SURV_VERIFY = 1, SURV_PROBE = 2, SURV_SEEDS_NEVER_SET = 3 /* no host code sets it; the kernels' tests for it stay (above k2a_append) */ };
+/* K2Params.sel_mode: which selection a payload launch decodes (k2d_run) */
+enum { SEL_FIRST = 0, SEL_REPAIRED = 1, SEL_FINAL = 2 };
+/* device-side tag of a record, in vdl2gpu_burst_t.trig_sample until the host fills that field in (collect_records) */
+enum { REC_FIRST = 0, REC_FINAL = 1, REC_VOID = 2 };
 
 struct StreamState {
 	long long dec_base;	/* stream time (84 kS/s index) of frame 0 of the current planes */
@@ -198,21 +238,20 @@ struct K2Params {
 	Cand *cands;		/* [S*8][CAND_CAP] */
 	Cluster *clusters;	/* [S*8][CAND_CAP] */
 	int2 *clhead;		/* [S*8][CAND_CAP] what the resolver needs of every cluster, 8 bytes: see cl_pack() */
-	unsigned *ctl;		/* [0]=out count [1]=out overflow [2]=stage count [3]=k2b ticket [4]=stage overflow
-				 * [8 + S*8 ...] cand counts, then cand overflow flags */
+	unsigned *ctl;		/* the push's control words: CTL_* below */
 	BurstDesc *stage;	/* burst descriptors of all clusters */
 	unsigned *sel_list;	/* descriptors on the real chain (K2c -> K2d) */
 	unsigned *sel_list2;	/* ... as the repair rounds re-resolved them (channels in fmask) */
-	int sel_mode;		/* K2d: 0 = the first selection of every channel (beside the verify pass: the mask is not final yet);
-				 * 1 = the repaired selection of the masked channels (second pass);
-				 * 2 = one pass behind the commit: the repaired selection for masked channels, the first for the others */
+	int sel_mode;		/* K2d: SEL_FIRST = the first selection of every channel (beside the verify pass: the mask is not final yet);
+				 * SEL_REPAIRED = the repaired selection of the masked channels (second pass);
+				 * SEL_FINAL = one pass behind the commit: the repaired selection for masked channels, the first for the others */
 	unsigned stage_cap;
 	vdl2gpu_burst_t *recs;	/* output ring of this push */
 	vdl2gpu_level_t *levels;	/* VDL2GPU_F_LEVELS: one level record per record slot of `recs`, else nullptr (nothing is measured) */
 	vdl2gpu_soft_t *soft;	/* VDL2GPU_F_SOFT_RS: one reliability map per record slot of `recs`, else nullptr */
-	unsigned *outc;		/* [0] = records written, [1] = records dropped (ring full) */
-	unsigned *outc_total_redo;	/* running count of serial redos (host adapts the number of repair rounds) */
-	unsigned *fmask;	/* [16] bit per (stream, channel slot) that a repair round re-resolved or K2f redid serially in this push */
+	RingCount *outc;	/* this push's ring */
+	OutCounters::Totals *outc_total;	/* running counts of serial redos and repairs (the host adapts the number of repair rounds by them) */
+	unsigned *fmask;	/* [VDL2_FMASK_WORDS] bit per (stream, channel slot) that a repair round re-resolved or K2f redid serially in this push */
 	int full_round;		/* this repair round scans the failing channels completely (all classes, every instant): no regions, no verify */
 	int mini_round;		/* this repair round re-resolves with what the verify pass found and appended to the tables, nothing else: no scan, no
 				 * clusters (the resolver replays the few new candidates itself) */
@@ -244,7 +283,7 @@ struct K2Params {
 	int surv_pch, surv_nwg;	/* items a private area holds (a multiple of 256), scan workgroups per channel (= private areas) */
 	int surv_common_cap;	/* test hook: the common area holds only so many items (0: all that is left of the list) */
 	int surv_slot;		/* which of the push's scans this is: its item counters are ctl[CTL_NSURV0 + slot * S*8 ...] (VDL2_SURV_*) */
-	int surv_mode;		/* sparse stages: what a detector hit among the survivors means (k2a_emit: 0 candidates, 1 verify, 2 probe; host side: SURV_*) */
+	int surv_mode;		/* sparse stages: what a detector hit among the survivors means (k2a_emit: SURV_*) */
 	int surv_skip;		/* sparse stages: hits in the probe's class are in the table already (region scan) */
 	/* the one-workgroup-per-channel kernel behind a scan drains that scan's common area first (k2x_drain): which scan, and how its list was laid out */
 	int drain_slot;		/* VDL2_SURV_* of the scan in front of this launch, -1: nothing to drain */
@@ -262,6 +301,47 @@ struct K2Params {
 	int lim_reg, lim_seg, lim_vis, lim_win, lim_merge, lim_slog;
 #endif
 };
+/* Development counters (K2Params.dbg, vdl2gpu_debug_counters: 96 words in a test build, 64 in the product; VDL2GPU_DEBUG_COUNTERS).  Every
+ * slot that anything outside the kernel that writes it reads has its name here; vdlm2dec_amd/lib.py (DBG) carries the same table for the
+ * tests and scripts, and tests/test_shared_words.py holds the two together.
+ * [0 .. 15] k2b_clusters, of every sixteenth cluster: 100 MHz ticks in the ring fill and in the rest, clusters sampled, their triggers,
+ *   evaluations, the longest rest, steady ends, rejects; ticks and clusters by the cluster's ordinal in its wavefront (+ 0 .. 3)
+ * [16 .. 20], [25 .. 29] k2c_resolve per call: ticks in its four phases, calls; replays of clusters K2b did not make, non-steady clusters
+ *   continued serially, candidates, visited-list entries, samples through the serial machine
+ * [24] channel-pushes that went through a repair round (k2_begin_repair)   [30] evaluation instants of every piece the verify passes scanned
+ * [32 .. 47], [48 .. 63] the probe's and the region scan's stage counters (K2A_ST_* below), of every eighth workgroup's first lane
+ * -- from here on in a test build only --
+ * [64 .. 70] escapes: how often a kernel took the branch for a full list --
+ *   64 regions (k2r_regions)  65 verify stretches (k2_emit_seg, k2p_patch, k2a_verify's clamp)  66 visited list (k2c_walk, k2c_resolve)
+ *   67 windows (k2p_patch)  68 merge (k2p_patch, k2s_merge: also in 75)  69 serial-stretch log (k2c_publish, k2p_patch)
+ *   70 descriptor pool or selection list full under a kernel that stages descriptors (k2b_clusters, k2c_resolve, k2p_patch: MachOut.badslot)
+ * [71 .. 74] violations of the two invariants at CTL_NWIN0 (every test reads zero) --
+ *   71 (b) k2b_clusters: a cluster's first descriptor whose nstar is not dec_base + its candidate's nrel
+ *   72 (b) k2d_run: the same, of every first descriptor of a cluster it decodes
+ *   73 (b) k2d_run, SEL_REPAIRED: a record whose trig_dec is not the nstar of the descriptor it was made from
+ *   74 (a) k2p_patch: a burst of the first selection triggered inside a window whose cluster's candidate is not marked in onchain[]
+ * [75] of the merge escapes, those of k2s_merge (a further round: the resolver takes the channel through the serial machine)
+ * [76] k2p_patch gave a repair up that it had begun (k2_begin_repair had run: more windows or stretches than the lists hold, or the pool full)
+ * [77 .. 80] how often the checks behind 71 .. 74 were made (a zero there says something only if these are not) */
+enum K2Dbg {
+	K2_DBG_K2B_RING_TICKS = 0, K2_DBG_K2B_REST_TICKS, K2_DBG_K2B_SAMPLED, K2_DBG_K2B_TRIG, K2_DBG_K2B_EVAL, K2_DBG_K2B_MAX_TICKS,
+	K2_DBG_K2B_STEADY, K2_DBG_K2B_REJ, K2_DBG_K2B_ORD_TICKS0 = 8, K2_DBG_K2B_ORD_COUNT0 = 12,
+	K2_DBG_K2C_LOAD_TICKS = 16, K2_DBG_K2C_TABLES_TICKS, K2_DBG_K2C_WALK_TICKS, K2_DBG_K2C_PUBLISH_TICKS, K2_DBG_K2C_CALLS,
+	K2_DBG_REPAIRED = 24, K2_DBG_K2C_REPLAYS, K2_DBG_K2C_NONSTEADY, K2_DBG_K2C_CANDS, K2_DBG_K2C_VISITED, K2_DBG_K2C_SERIAL_SAMPLES,
+	K2_DBG_VERIFY_INSTANTS = 30, K2_DBG_PROBE_STAGE0 = 32, K2_DBG_REGION_STAGE0 = 48,
+	K2_DBG_ESC_REG = 64, K2_DBG_ESC_SEG, K2_DBG_ESC_VIS, K2_DBG_ESC_WIN, K2_DBG_ESC_MERGE, K2_DBG_ESC_SLOG, K2_DBG_ESC_STAGE,
+	K2_DBG_INV_B_CLUSTER, K2_DBG_INV_B_DECODE, K2_DBG_INV_B_RECORD, K2_DBG_INV_A, K2_DBG_ESC_MERGE_SORT,
+	K2_DBG_ESC_PATCH_ABANDON, K2_DBG_CHK_B_CLUSTER, K2_DBG_CHK_B_DECODE, K2_DBG_CHK_B_RECORD, K2_DBG_CHK_A
+};
+/* the sixteen stage slots behind K2_DBG_PROBE_STAGE0 / K2_DBG_REGION_STAGE0 (K2aShared.prof; ticks unless said otherwise).  The probe stamps
+ * the tile's stages; the region scan counts its tile loop as a whole (TILES_OR_WAIT) and its instants.  UNUSED*: stages that have gone */
+enum K2aStage {
+	K2A_ST_STAGE_IN = 0, K2A_ST_FIR_UNIT, K2A_ST_BARRIER_SAMPLES, K2A_ST_STEPS, K2A_ST_SCREEN, K2A_ST_UNUSED5, K2A_ST_UNUSED6, K2A_ST_UNUSED7,
+	K2A_ST_SCREEN_END, K2A_ST_BARRIER_TILE, K2A_ST_UNUSED10, K2A_ST_PASSES /* a count */, K2A_ST_TILES_OR_WAIT, K2A_ST_PARK, K2A_ST_UNUSED14,
+	K2A_ST_INSTANTS /* a count */, K2A_ST_SLOTS
+};
+static_assert(K2A_ST_SLOTS == 16 && K2_DBG_REGION_STAGE0 == K2_DBG_PROBE_STAGE0 + K2A_ST_SLOTS && K2_DBG_ESC_REG == K2_DBG_REGION_STAGE0 + K2A_ST_SLOTS,
+	      "the two scans' stage slots lie between the resolver's counters and the test build's");
 /* What a list of the back stage holds: the compile-time size, in a test build the run-time value beside it (K2Params.lim_*).  Every
  * comparison against a size goes through its macro, so that a lowered limit is one limit everywhere. */
 #ifdef VDL2GPU_TESTHOOKS
@@ -271,22 +351,6 @@ struct K2Params {
 #define K2_WIN_LIM(p) ((p).lim_win)
 #define K2_MERGE_LIM(p) ((p).lim_merge)
 #define K2_SLOG_LIM(p) ((p).lim_slog)
-/* Development counters behind the kernels' cycle counters (K2Params.dbg, vdl2gpu_debug_counters: 96 words in a test build, 64 in the product).
- * [64 .. 70] escapes: how often a kernel took the branch for a full list --
- *   64 regions (k2r_regions)  65 verify stretches (k2_emit_seg, k2p_patch, k2a_verify's clamp)  66 visited list (k2c_walk, k2c_resolve)
- *   67 windows (k2p_patch)  68 merge (k2p_patch, k2s_merge: also in 75)  69 serial-stretch log (k2c_publish, k2p_patch)
- *   70 descriptor pool or selection list full under a kernel that stages descriptors (k2b_clusters, k2c_resolve, k2p_patch: MachOut.badslot)
- * [71 .. 74] violations of the two invariants at CTL_NWIN0 (every test reads zero) --
- *   71 (b) k2b_clusters: a cluster's first descriptor whose nstar is not dec_base + its candidate's nrel
- *   72 (b) k2d_run: the same, of every first descriptor of a cluster it decodes
- *   73 (b) k2d_run, sel_mode 1: a record whose trig_dec is not the nstar of the descriptor it was made from
- *   74 (a) k2p_patch: a burst of the first selection triggered inside a window whose cluster's candidate is not marked in onchain[]
- * [75] of the merge escapes, those of k2s_merge (a further round: the resolver takes the channel through the serial machine)
- * [76] k2p_patch gave a repair up that it had begun (k2_begin_repair had run: more windows or stretches than the lists hold, or the pool full)
- * [77 .. 80] how often the checks behind 71 .. 74 were made (a zero there says something only if these are not) */
-enum { K2_DBG_ESC_REG = 64, K2_DBG_ESC_SEG, K2_DBG_ESC_VIS, K2_DBG_ESC_WIN, K2_DBG_ESC_MERGE, K2_DBG_ESC_SLOG, K2_DBG_ESC_STAGE,
-       K2_DBG_INV_B_CLUSTER, K2_DBG_INV_B_DECODE, K2_DBG_INV_B_RECORD, K2_DBG_INV_A, K2_DBG_ESC_MERGE_SORT,
-       K2_DBG_ESC_PATCH_ABANDON, K2_DBG_CHK_B_CLUSTER, K2_DBG_CHK_B_DECODE, K2_DBG_CHK_B_RECORD, K2_DBG_CHK_A };
 #define VDL2_DBG_WORDS 96
 #define K2_COUNT(p, slot) do { if ((p).dbg) atomicAdd((p).dbg + (slot), 1ull); } while (0)
 #else
@@ -304,28 +368,36 @@ enum { K2_DBG_ESC_REG = 64, K2_DBG_ESC_SEG, K2_DBG_ESC_VIS, K2_DBG_ESC_WIN, K2_D
 #define CTL_STAGE 2
 #define CTL_TICKET 3
 #define CTL_STAGE_OVF 4
-#define CTL_CAND0 8		/* [S*8] candidate counts, [S*8] overflow flags, then: */
-#define CTL_NREG0 (CTL_CAND0 + 2 * p.nstreams * VDL2_CS)
-#define CTL_NSEG0 (CTL_CAND0 + 3 * p.nstreams * VDL2_CS)
-#define CTL_NSEL0 (CTL_CAND0 + 4 * p.nstreams * VDL2_CS)
-#define CTL_NPRIM0 (CTL_CAND0 + 5 * p.nstreams * VDL2_CS)
-#define CTL_NSEED0 (CTL_CAND0 + 6 * p.nstreams * VDL2_CS)
-#define CTL_NCLUST0 (CTL_CAND0 + 7 * p.nstreams * VDL2_CS)	/* candidates [0, n) had their clusters decided by the previous K2s/K2b of this push */
-#define CTL_NSURV0 (CTL_CAND0 + 8 * p.nstreams * VDL2_CS)	/* [VDL2_SURV_SLOTS][S*8] item counts, one set per scan of the push */
+/* ... and behind them blocks of a word per channel slot, [S*8] each: CTL_x0(p) is the first word of block x, p a parameter block with
+ * `nstreams` (K2Params, K3Params: the host uses the same macros) */
+#define CTL_CAND0 8		/* candidate counts */
+/* the scans of a push, each with item counters of its own (K2Params.surv_slot) */
 enum { VDL2_SURV_PROBE = 0, VDL2_SURV_REGION = 1, VDL2_SURV_VERIFY = 2 /* + repair round (1..4) */, VDL2_SURV_FULL = 7, VDL2_SURV_SLOTS = 8 };
-#define CTL_SELBASE0 (CTL_CAND0 + (8 + VDL2_SURV_SLOTS) * p.nstreams * VDL2_CS)	/* first output record of the channel's selected bursts (K2c reserves, K2d fills) */
+enum { CTL_B_CAND = 0, CTL_B_CANDOVF, CTL_B_NREG, CTL_B_NSEG, CTL_B_NSEL, CTL_B_NPRIM, CTL_B_NSEED, CTL_B_NCLUST,
+       CTL_B_NSURV, CTL_B_SELBASE = CTL_B_NSURV + VDL2_SURV_SLOTS, CTL_B_NSEL1, CTL_B_SELBASE1,
+       CTL_B_NSURVLIM, CTL_B_NWIN = CTL_B_NSURVLIM + VDL2_SURV_SLOTS, CTL_B_NSLOG, CTL_B_END };
+#define CTL_BLOCK(p, b) (CTL_CAND0 + (b) * (p).nstreams * VDL2_CS)
+#define CTL_CANDOVF0(p) CTL_BLOCK(p, CTL_B_CANDOVF)	/* bit 0: the candidate table overflowed, bit 1: unusable for another reason than its size */
+#define CTL_NREG0(p) CTL_BLOCK(p, CTL_B_NREG)
+#define CTL_NSEG0(p) CTL_BLOCK(p, CTL_B_NSEG)
+#define CTL_NSEL0(p) CTL_BLOCK(p, CTL_B_NSEL)
+#define CTL_NPRIM0(p) CTL_BLOCK(p, CTL_B_NPRIM)
+#define CTL_NSEED0(p) CTL_BLOCK(p, CTL_B_NSEED)
+#define CTL_NCLUST0(p) CTL_BLOCK(p, CTL_B_NCLUST)	/* candidates [0, n) had their clusters decided by the previous K2s/K2b of this push */
+#define CTL_NSURV0(p) CTL_BLOCK(p, CTL_B_NSURV)	/* [VDL2_SURV_SLOTS][S*8] item counts, one set per scan of the push */
+#define CTL_SELBASE0(p) CTL_BLOCK(p, CTL_B_SELBASE)	/* first output record of the channel's selected bursts (K2c reserves, K2d fills) */
 /* The selection exists twice: the first resolver pass writes sel_list / CTL_NSEL0 / CTL_SELBASE0, the repair rounds sel_list2 and
  * the words below -- the payload decode of the first selection runs beside the verify pass AND beside the repair round (on a
  * stream of its own), which therefore must not touch what it reads. */
-#define CTL_NSEL1 (CTL_CAND0 + (9 + VDL2_SURV_SLOTS) * p.nstreams * VDL2_CS)
-#define CTL_SELBASE1 (CTL_CAND0 + (10 + VDL2_SURV_SLOTS) * p.nstreams * VDL2_CS)
-#define CTL_NSURVLIM0 (CTL_CAND0 + (11 + VDL2_SURV_SLOTS) * p.nstreams * VDL2_CS)	/* [VDL2_SURV_SLOTS][S*8] ~(where the first group that the common area
+#define CTL_NSEL1(p) CTL_BLOCK(p, CTL_B_NSEL1)
+#define CTL_SELBASE1(p) CTL_BLOCK(p, CTL_B_SELBASE1)
+#define CTL_NSURVLIM0(p) CTL_BLOCK(p, CTL_B_NSURVLIM)	/* [VDL2_SURV_SLOTS][S*8] ~(where the first group that the common area
 											 * refused would have begun): 0 = none refused; items below it are complete */
-#define CTL_NWIN0 (CTL_CAND0 + (11 + 2 * VDL2_SURV_SLOTS) * p.nstreams * VDL2_CS)	/* [S*8] what the repair rounds made void of the channel's FIRST selection: 0 nothing,
+#define CTL_NWIN0(p) CTL_BLOCK(p, CTL_B_NWIN)	/* [S*8] what the repair rounds made void of the channel's FIRST selection: 0 nothing,
 											 * 1..VDL2_WIN_CAP: the bursts triggered inside so many windows of stream time (K2Params.win:
 											 * a local repair, k2p_patch), VDL2_WIN_ALL: all of it (the channel was resolved again from its
 											 * input state, or redone serially) */
-#define CTL_NSLOG0 (CTL_CAND0 + (12 + 2 * VDL2_SURV_SLOTS) * p.nstreams * VDL2_CS)	/* [S*8] entries of K2Params.slog the first resolver pass made (VDL2_SLOG_CAP + 1: more than it holds) */
+#define CTL_NSLOG0(p) CTL_BLOCK(p, CTL_B_NSLOG)	/* [S*8] entries of K2Params.slog the first resolver pass made (VDL2_SLOG_CAP + 1: more than it holds) */
 /* Two invariants the windows of CTL_NWIN0 stand on (both implicit in the code, held by the parity and soak tests alone):
  * (a) K2Params.onchain[] marks the candidates the first resolver pass met history-free: exactly the clusters whose bursts that pass
  *     selected and whose head it counted, and the candidates a walk stopped at without counting their head (CL_DEFER_FIRST, CL_INVALID:
@@ -334,9 +406,9 @@ enum { VDL2_SURV_PROBE = 0, VDL2_SURV_REGION = 1, VDL2_SURV_VERIFY = 2 /* + repa
  *     old chain, and k2p_old_counts takes the old chain's counts inside a window from these heads;
  * (b) a burst's trigger instant is the same number everywhere: BurstDesc.nstar of a cluster's first burst = dec_base + its candidate's
  *     nrel, and a record's trig_dec = its descriptor's nstar.  ESTABLISHED by k2b_clusters (st.pos = dec_base + nrel) and burst_payload;
- *     RELIED ON by k2_in_windows' callers in k2d_run, which test trig_dec (sel_mode 1) and nstar (sel_mode 2) against windows that
+ *     RELIED ON by k2_in_windows' callers in k2d_run, which test trig_dec (SEL_REPAIRED) and nstar (SEL_FINAL) against windows that
  *     k2p_patch made of candidate times. */
-#define VDL2_CTL_WORDS(nsc) (CTL_CAND0 + (13 + 2 * VDL2_SURV_SLOTS) * (size_t)(nsc))
+#define VDL2_CTL_WORDS(nsc) (CTL_CAND0 + CTL_B_END * (size_t)(nsc))	/* (nsc: channel slots, S*8) */
 #define VDL2_WIN_CAP 32
 #define VDL2_WIN_ALL 0xffffffffu
 #define VDL2_SLOG_CAP 16
@@ -349,11 +421,10 @@ struct K3Params {
 	long long J;
 	StreamState *ss;
 	const ChanState *cs;
-	const unsigned *outc;	/* device counters: [2*ring] records, [2*ring+1] dropped, [4] serial redos so far */
-	const unsigned *fmask;	/* K2f's redo mask of this push (16 words) */
-	const unsigned *fcnt;	/* block path in the pipeline (VDL2GPU_F_FRAMES): frames, dropped, arena bytes asked for, end of the last arena entry written; else nullptr */
-	unsigned *host_cnt;	/* the same, in pinned host memory, for this push's ring ([4..6]: frames, dropped, end of the last arena entry written; [7]: channels whose
-				 * candidate tables overflowed in this push) */
+	const OutCounters *outc;	/* device counters: every ring's and the running totals */
+	const unsigned *fmask;	/* K2f's redo mask of this push (VDL2_FMASK_WORDS) */
+	const FrameCounters *fcnt;	/* block path in the pipeline (VDL2GPU_F_FRAMES): this ring's; else nullptr */
+	PushCounters *host_cnt;	/* what the host reads of them, in pinned host memory, for this push's ring */
 	int ring;
 	const unsigned *ctl;	/* the push's control words */
 	int nstreams;
@@ -362,11 +433,11 @@ struct K3Params {
 struct KInitParams {		/* per-push reset of the demodulator's control words */
 	unsigned *ctl;
 	int ctl_words;
-	unsigned *outc;		/* 2 words of this push's ring */
+	RingCount *outc;	/* this push's ring */
 	int *fail, *redo;
 	int nsc;
-	unsigned *fmask;	/* 16 words */
-	unsigned *fcnt;		/* 4 words: this ring's block-path counters, or nullptr */
+	unsigned *fmask;	/* VDL2_FMASK_WORDS */
+	FrameCounters *fcnt;	/* this ring's block-path counters, or nullptr */
 };
 
 /* ---- constant data tables (d8psk.h:20-249) as bit patterns ------------- */

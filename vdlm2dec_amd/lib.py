@@ -36,6 +36,29 @@ F_FEEDBACK = 4096
 CL_STEADY, CL_DEFER_FIRST, CL_NONSTEADY = 0, 1, 2
 
 
+# vdl2gpu_debug_counters(): slot of every named development counter (enum K2Dbg in csrc/vdl2gpu_types.h without its K2_DBG_ prefix;
+# tests/test_shared_words.py holds the two together).  Slots from ESC_REG on exist in the test library only.
+DBG = {
+    "K2B_RING_TICKS": 0, "K2B_REST_TICKS": 1, "K2B_SAMPLED": 2, "K2B_TRIG": 3, "K2B_EVAL": 4, "K2B_MAX_TICKS": 5,
+    "K2B_STEADY": 6, "K2B_REJ": 7, "K2B_ORD_TICKS0": 8, "K2B_ORD_COUNT0": 12,
+    "K2C_LOAD_TICKS": 16, "K2C_TABLES_TICKS": 17, "K2C_WALK_TICKS": 18, "K2C_PUBLISH_TICKS": 19, "K2C_CALLS": 20,
+    "REPAIRED": 24, "K2C_REPLAYS": 25, "K2C_NONSTEADY": 26, "K2C_CANDS": 27, "K2C_VISITED": 28, "K2C_SERIAL_SAMPLES": 29,
+    "VERIFY_INSTANTS": 30, "PROBE_STAGE0": 32, "REGION_STAGE0": 48,
+    "ESC_REG": 64, "ESC_SEG": 65, "ESC_VIS": 66, "ESC_WIN": 67, "ESC_MERGE": 68, "ESC_SLOG": 69, "ESC_STAGE": 70,
+    "INV_B_CLUSTER": 71, "INV_B_DECODE": 72, "INV_B_RECORD": 73, "INV_A": 74, "ESC_MERGE_SORT": 75,
+    "ESC_PATCH_ABANDON": 76, "CHK_B_CLUSTER": 77, "CHK_B_DECODE": 78, "CHK_B_RECORD": 79, "CHK_A": 80,
+}
+# the sixteen stage slots behind PROBE_STAGE0 and REGION_STAGE0 (enum K2aStage without its K2A_ST_ prefix, lower case)
+DBG_STAGES = ("stage_in", "fir_unit", "barrier_samples", "steps", "screen", "unused5", "unused6", "unused7",
+              "screen_end", "barrier_tile", "unused10", "passes", "tiles_or_wait", "park", "unused14", "instants")
+DBG_WORDS, DBG_WORDS_TEST = 64, 96      # VDL2_DBG_WORDS of the product and of the test library
+
+
+def dbg_stages(counters, base):
+    """'name value, ...' of the stage slots that counted, base = DBG["PROBE_STAGE0"] or DBG["REGION_STAGE0"]"""
+    return ", ".join("%s %d" % (name, counters[base + i]) for i, name in enumerate(DBG_STAGES) if counters[base + i])
+
+
 def cl_unpack(packed):
     """(status, r_s, nslots, ntrig, nrej, nburst) of a cluster head's packed word, as the device's cl_*() accessors read it"""
     p = int(packed) & 0xffffffff
