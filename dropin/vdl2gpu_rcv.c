@@ -21,7 +21,8 @@
  * With -DVDL2GPU_FRAMES the block path runs on the GPU as well (vdl2gpu_decode_blocks: RS, HDLC
  * un-stuffing, FCS for a whole batch of bursts in one kernel) and the shim goes straight to
  * out(msgblk_t*, unsigned char *hdata, int l) (vdlm2.h:134, called by check_frame, vdlm2.c:60):
- * then vdlm2.c, rs.c and crc.c drop out of the build too.  At the rates the GPU front end
+ * then vdlm2.c, rs.c and crc.c drop out of the build too.  With VDL2GPU_RCV_ALL_FRAMES in the environment that build hands out() every
+ * frame of a burst that carries several (vdl2gpu_decode_blocks_ex, VDL2GPU_BLK_ALL_FRAMES), not only the first.  At the rates the GPU front end
  * demodulates at, the reference's single blk_thread cannot keep up.
  *
  * This file contains no DSP.  It is compiled against the reference's own vdlm2.h.
@@ -79,6 +80,9 @@ _Static_assert(NSTAMP >= BATCH_BLOCKS * 5 + 64, "the stamp ring must reach back 
 				 * at 2 MS/s, 3.3 ms at 10 MS/s); closer together the source is a replay and the slot fills first */
 static vdl2gpu_t *g_h;
 static long long g_last_ns;	/* when the previous hand-off came */
+#ifdef VDL2GPU_FRAMES
+static int g_all_frames;	/* VDL2GPU_RCV_ALL_FRAMES is set: deliver() asks for every frame of a burst */
+#endif
 static int g_null;		/* VDL2GPU_RCV_NULL=1: keep the barrier protocol, do nothing else (measures what the protocol alone allows) */
 static char *g_slot;		/* the slot being filled, or NULL */
 static size_t g_fill;		/* samples in it */
@@ -103,7 +107,10 @@ static void deliver(vdl2gpu_t *h, int wait)
 	static msgblk_t blk;	/* what out() reads of it: chn, Fr, tv, ppm, nbrow, nlbyte */
 	int n, nf, i, dropped = 0;
 	while ((n = wait ? vdl2gpu_poll(h, b, 64) : vdl2gpu_poll_ready(h, b, 64)) > 0) {
-		nf = vdl2gpu_decode_blocks(h, b, n, f, 128, &dropped);
+		/* VDL2GPU_RCV_ALL_FRAMES: every frame of a burst goes to out(), in (block, seq) order -- the reference's check_frame() can
+		 * only pass the first (include/vdl2gpu.h, VDL2GPU_F_ALL_FRAMES).  Unset: vdl2gpu_decode_blocks, as ever */
+		nf = g_all_frames ? vdl2gpu_decode_blocks_ex(h, b, NULL, NULL, n, f, 128, &dropped, NULL, VDL2GPU_BLK_ALL_FRAMES)
+				  : vdl2gpu_decode_blocks(h, b, n, f, 128, &dropped);
 		if (dropped)	/* more frames than the buffer holds (or than 12 in one burst): never silent */
 			fprintf(stderr, "vdl2gpu_decode_blocks: %d frame(s) dropped\n", dropped);
 		for (i = 0; i < nf; i++) {
@@ -238,6 +245,9 @@ void *rcv_thread(void *arg)
 			exit(1);
 		}
 		g_null = getenv("VDL2GPU_RCV_NULL") != NULL;
+#ifdef VDL2GPU_FRAMES
+		g_all_frames = getenv("VDL2GPU_RCV_ALL_FRAMES") != NULL;
+#endif
 		pthread_mutex_lock(&g_mu);
 		g_h = h;
 		pthread_mutex_unlock(&g_mu);

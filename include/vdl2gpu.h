@@ -411,6 +411,39 @@ typedef struct {
 	uint8_t reserved[8];				/* @2040 0 */
 } vdl2gpu_fb_t;		/* sizeof 2048 */
 
+/* ---- every frame of a burst (VDL2GPU_F_ALL_FRAMES; announced by VDL2GPU_HAVE_ALL_FRAMES, the ABI version is unchanged) ----
+ * A burst may carry several AVLC frames, one flag closing a frame and opening the next.  blk_thread() calls check_frame() at every 0x7e
+ * behind hdata[1], and check_frame() always runs the FCS from hdata[1] (vdlm2.c:52): its second candidate is "frame 1 + FCS + flag +
+ * frame 2", which cannot check, so only the first frame of a burst can pass.  The block path without this flag reproduces that.
+ * With VDL2GPU_F_ALL_FRAMES (which needs VDL2GPU_F_FRAMES: without it vdl2gpu_create returns VDL2GPU_EINVAL), and in
+ * vdl2gpu_decode_blocks_ex with VDL2GPU_BLK_ALL_FRAMES on any handle, the block path hands on every frame of the burst.
+ * Everything up to and including the flag hunt is unchanged: RS per row with the soft and feedback row rules, un-stuffing over all
+ * rows, flag_at, and m1 = hdata[1] = the first byte behind the first flag that is no 0x7e.  Let B[0..nb) be the whole un-stuffed bytes
+ * and q_0 < q_1 < ... the positions q >= m1 with B[q] == 0x7e.
+ *   segment j   starts at s_0 = m1, s_{j+1} = q_j + 1, and is closed by q_j
+ *   l_j         = q_j - s_j + 2: its length in the reference's terms -- opening flag, bytes, closing flag
+ *   l_j == 2    is an empty segment (flags side by side).  It is swallowed, as the reference swallows the flags behind the first one
+ *               (k == 1, vdlm2.c:134-135)
+ *   passes      iff l_j >= 13 and the FCS-16 (crc.c) run from 0xffff over B[s_j .. q_j - 1] leaves 0xf0b8
+ *   frame       each passing segment is one vdl2gpu_frame_t: data = 0x7e, B[s_j .. q_j], len = l_j; seq is its rank among the passing
+ *               segments of its burst in stream order; all other fields are the burst's
+ * Segment 0 is the reference's first candidate, so a burst of one frame gives the same frame with or without the flag.  The
+ * reference's FURTHER candidates (all of them starting at m1, passing only by an accident of 2^-16 each) are not formed in this mode.
+ * One thing follows from working on B, as the reference does: the un-stuffer hands a stuffed data byte 0x7e on as the byte 0x7e, and
+ * the rule takes it for a flag (so does check_frame()'s caller, vdlm2.c:143, where it only adds a candidate that fails).  A frame that
+ * holds a data byte 0x7e is therefore cut there in this mode and does not pass, not even as the first frame of its burst, which the
+ * block path without the flag delivers.  A consumer that must not lose those runs a handle without the flag beside one with it.
+ * As without the flag: at most 12 passing frames of a burst are kept, the first 12 in stream order, and further ones are counted in
+ * vdl2gpu_stats_t.frames_dropped / *dropped; bytes behind the last flag are ignored; nothing is re-aligned at bit level -- flags
+ * survive the un-stuffer and frames are whole bytes, so byte alignment holds across the frames of a burst.
+ * The block report (vdl2gpu_blockrep_t, layout unchanged) in this mode: cand keeps its meaning, every 0x7e behind hdata[1]; too_short
+ * counts l_j < 13, the empty segments of l_j = 2 included; bad_fcs counts l_j >= 13 with another residue; frames counts those that
+ * pass; cand == too_short + bad_fcs + frames still holds.
+ * Nothing else changes with the flag: burst records, their order and every column are what they are without it, and
+ * vdl2gpu_poll_frames keeps its order (end_dec, stream, chn, seq). */
+#define VDL2GPU_F_ALL_FRAMES 8192u
+#define VDL2GPU_HAVE_ALL_FRAMES 1
+
 typedef struct {
 	uint64_t samples_in;	/* per stream */
 	uint64_t dec_samples;	/* 84 kS/s samples produced per channel */
@@ -423,7 +456,8 @@ typedef struct {
 	uint64_t serial_redos;	/* channel-pushes redone serially because the verify pass found an unlisted event */
 	uint64_t serial_samples;	/* 84 kS/s samples handled by the serial machine (history-dependent stretches) */
 	uint64_t overflowed;	/* burst records dropped: device ring full, or host queue never drained */
-	uint64_t frames_dropped;	/* VDL2GPU_F_FRAMES: frames dropped (arena full, more than 12 frames in a burst, host queue never drained) */
+	uint64_t frames_dropped;	/* VDL2GPU_F_FRAMES: frames that checked and were not handed out: more than 12 in one burst (with VDL2GPU_F_ALL_FRAMES the
+				 * 13th passing segment onwards, in stream order), the device's frame arena full, or the host queue never drained */
 	uint64_t repairs;	/* channel-pushes a repair round re-resolved because the verify pass found an unlisted event (cheap; serial_redos
 				 * counts the ones no scheduled round could settle) */
 } vdl2gpu_stats_t;
@@ -608,6 +642,12 @@ int vdl2gpu_decode_blocks_report(vdl2gpu_t *h, const vdl2gpu_burst_t *blocks, co
  * the row rule of vdl2gpu_fb_t.  Works on any handle; soft and rep may each be NULL; fb == NULL: exactly vdl2gpu_decode_blocks_report. */
 int vdl2gpu_decode_blocks_feedback(vdl2gpu_t *h, const vdl2gpu_burst_t *blocks, const vdl2gpu_soft_t *soft, const vdl2gpu_fb_t *fb, int n,
 				   vdl2gpu_frame_t *frames, int max_frames, int *dropped, vdl2gpu_blockrep_t *rep);
+/* ... and with a mode word (announced by VDL2GPU_HAVE_ALL_FRAMES), so that a further mode needs no further name.
+ * VDL2GPU_BLK_ALL_FRAMES: every frame of a burst, by the rule at VDL2GPU_F_ALL_FRAMES.  Works on any handle; soft, fb and rep may each be
+ * NULL; mode == 0: exactly vdl2gpu_decode_blocks_feedback; any other bit: VDL2GPU_EINVAL before any device call. */
+#define VDL2GPU_BLK_ALL_FRAMES 1u
+int vdl2gpu_decode_blocks_ex(vdl2gpu_t *h, const vdl2gpu_burst_t *blocks, const vdl2gpu_soft_t *soft, const vdl2gpu_fb_t *fb, int n,
+			     vdl2gpu_frame_t *frames, int max_frames, int *dropped, vdl2gpu_blockrep_t *rep, uint32_t mode);
 /* With VDL2GPU_F_FRAMES the same kernel runs on every push's burst records where they lie in device
  * memory, right behind the demodulator.  Collect the frames of everything pushed so far (waits like
  * vdl2gpu_poll; the bursts themselves stay available through vdl2gpu_poll).  Frames come out ordered

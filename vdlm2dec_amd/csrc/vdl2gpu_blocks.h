@@ -17,6 +17,8 @@
  * the burst (K4Rep, in LDS) and writes it out as the record's vdl2gpu_blockrep_t (VDL2GPU_F_BLOCK_REPORT, include/vdl2gpu.h).
  * ... and over FB: k4_frames_fb / k4_frames_rep_fb try the record's decision-feedback row (K4Params.fb, VDL2GPU_F_FEEDBACK) behind a
  * row that rs() fails on (k4_fb_row), in front of the soft trials.
+ * ... and over ALL: the four kernels k4_frames_all* (vdl2gpu_allframes.hip) take every segment between two flags for a candidate frame,
+ * not only what follows the first flag (VDL2GPU_F_ALL_FRAMES): k4_fcs_scan_all in k4_fcs_scan's place, k4_emit with each frame's own start.
  */
 #ifndef VDL2GPU_BLOCKS_H
 #define VDL2GPU_BLOCKS_H
@@ -89,6 +91,9 @@ struct K4Shared {
 	int cand[4];		/* soft mode: the least reliable candidate positions, most doubtful first */
 };
 
+/* VDL2GPU_BLOCKS_DEVICE_ONLY: the translation unit wants the device functions and none of the kernels below (vdl2gpu_allframes.hip
+ * defines its own on k4_frames_body) */
+#ifndef VDL2GPU_BLOCKS_DEVICE_ONLY
 /* GF(256)/0x187 (rs.c:17-79) and FCS-16 reflected 0x8408 (crc.c) tables, built once per handle */
 __global__ void k4_tables(unsigned *out)
 {
@@ -118,6 +123,7 @@ __global__ void k4_tables(unsigned *out)
 	for (int i = threadIdx.x; i < K4_TABW; i += blockDim.x)
 		out[i] = reinterpret_cast<const unsigned *>(t)[i];
 }
+#endif
 
 __device__ __forceinline__ int k4_m255(int x)
 {
@@ -719,10 +725,114 @@ __device__ __forceinline__ int k4_flag_hunt(K4Shared &sh, int c0, int c1, int la
  * alongside.  Leaves the closing flags of the frames that check in sh.ends, in any order, and their number in sh.nfr.
  * REP: every lane also counts the 0x7e bytes it meets (B[m1] is none) and those of them that close a candidate of l < 13; the two
  * counts (at most K4_MAXBY < 65536 and at most 10: l < 13 ends at m1 + 10) are added up over the wave in one word and returned:
- * cand | too_short << 16.  The candidates of l >= 13 with the wrong FCS are the rest: cand - too_short - sh.nfr.  Without REP: 0. */
+ * cand | too_short << 16.  The candidates of l >= 13 with the wrong FCS are the rest: cand - too_short - sh.nfr.  Without REP: 0.
+ * ALL (VDL2GPU_F_ALL_FRAMES, include/vdl2gpu.h): every 0x7e at q >= m1 closes the segment that began behind the flag before it (s_0 = m1,
+ * s_{j+1} = q_j + 1, l_j = q_j - s_j + 2), and the FCS starts again from 0xffff behind it.  A lane whose bytes hold such a flag ends in a
+ * state that does not depend on the lanes before it -- the FCS from 0xffff over what follows its last flag -- so the scan's element is
+ * (reset, x) with (r_a, x_a) o (r_b, x_b) = r_b ? (1, x_b) : (r_a, A^n_b x_a ^ x_b): associative, and the advance map and its squaring
+ * are untouched.  The lane that holds m1 starts from 0xffff and is a reset by construction.  A maximum scan of the lanes' last flags gives
+ * every lane the start of the segment its first byte lies in.  sh.ends[] gets q << 16 | s of the segments that pass, in stream order
+ * (ranks from a prefix sum of the lanes' counts: the first K4_NCAND of the burst are the ones kept), sh.nfr their number; the counts
+ * follow the same rule: too_short is l_j < 13, flags side by side (l_j = 2) included. */
+/* segments that pass are 12 bytes apart at least (l >= 13), so a lane meets at most three closing flags of such */
+#define K4_ALL_LANE_MAX 3
+static_assert((K4_MAXBY + K4_NT - 1) / K4_NT <= 12 * K4_ALL_LANE_MAX, "a lane's span holds at most K4_ALL_LANE_MAX passing segments' ends");
+static_assert(K4_MAXBY < 65536, "a candidate's closing flag and start share a word");
+
 template <bool REP>
+__device__ __forceinline__ unsigned k4_fcs_scan_all(K4Shared &sh, int m1, int per, int c0, int c1, int lane)
+{
+	const uint8_t *B = reinterpret_cast<const uint8_t *>(sh.dst);
+	unsigned col = 0;	/* the advance map, one state bit per lane */
+	if (lane < 16) {
+		col = 1u << lane;
+		for (int i = 0; i < per; ++i)
+			col = (col >> 8) ^ sh.crc_tab[col & 0xffu];
+	}
+	const int L1 = m1 / per;	/* lane that holds m1 */
+	const int b0 = (lane == L1) ? m1 : c0;	/* the lane's first byte that counts */
+	unsigned x = 0;		/* FCS over the lane's own bytes: from 0xffff behind m1 and behind every flag, else from zero */
+	int reset = lane == L1;	/* ... which is then all there is to its end state */
+	int last = -1;		/* the lane's last flag */
+	if (lane >= L1) {
+		x = reset ? 0xffffu : 0u;
+		for (int i = b0; i < c1; ++i) {
+			const unsigned v = B[i];
+			if (v == 0x7eu) {
+				x = 0xffffu;
+				reset = 1;
+				last = i;
+			} else
+				x = (x >> 8) ^ sh.crc_tab[(x ^ v) & 0xffu];
+		}
+	}
+	for (int d = 1; d < K4_NT; d <<= 1) {
+		unsigned xl = __shfl_up(x, d, K4_NT);
+		int rl = __shfl_up(reset, d, K4_NT);
+		if (lane < d) {
+			xl = 0;
+			rl = 0;
+		}
+		unsigned y = 0, nc = 0;
+#pragma unroll
+		for (int b = 0; b < 16; ++b) {
+			const unsigned cb = (unsigned)__builtin_amdgcn_readlane((int)col, b);
+			y ^= (0u - ((xl >> b) & 1u)) & cb;
+			nc ^= (0u - ((col >> b) & 1u)) & cb;
+		}
+		if (!reset) {	/* exact for whole lanes; the last, partial lane's end state is not needed */
+			x ^= y;
+			reset = rl;
+		}
+		col = nc;
+	}
+	const unsigned crc_in = __shfl_up(x, 1, K4_NT);	/* state at the lane's first byte */
+	const int flag_in = __shfl_up(k4_scan(last, lane, [](int a, int b) { return a > b ? a : b; }), 1, K4_NT);	/* last flag in front of it */
+	unsigned counts = 0;
+	unsigned mine[K4_ALL_LANE_MAX] = {};	/* the segments that pass and end in this lane's bytes */
+	int npass = 0;
+	if (lane >= L1) {
+		unsigned c = (lane == L1) ? 0xffffu : crc_in;
+		int s = (lane == L1 || flag_in < 0) ? m1 : flag_in + 1;
+		for (int q = b0; q < c1; ++q) {
+			const unsigned v = B[q];
+			if (v == 0x7eu) {
+				const int l = q - s + 2;
+				if (l >= 13 && c == 0xf0b8u) {
+					const unsigned w = (unsigned)q << 16 | (unsigned)s;
+#pragma unroll
+					for (int k = 0; k < K4_ALL_LANE_MAX; ++k)
+						mine[k] = npass == k ? w : mine[k];
+					++npass;
+				}
+				if (REP)
+					counts += 1u + (l < 13 ? 1u << 16 : 0u);
+				c = 0xffffu;
+				s = q + 1;
+			} else
+				c = (c >> 8) ^ sh.crc_tab[(c ^ v) & 0xffu];
+		}
+	}
+	const int upto = k4_scan(npass, lane, [](int a, int b) { return a + b; });	/* passing segments up to and with this lane's */
+#pragma unroll
+	for (int k = 0; k < K4_ALL_LANE_MAX; ++k)
+		if (k < npass && upto - npass + k < K4_NCAND)
+			sh.ends[upto - npass + k] = (int)mine[k];
+	if (lane == K4_NT - 1)
+		sh.nfr = upto;
+	if (REP) {
+		for (int d = 32; d > 0; d >>= 1)
+			counts += __shfl_xor(counts, d, K4_NT);
+	}
+	K4_SYNC();
+	return counts;
+}
+
+template <bool REP, bool ALL = false>
 __device__ __forceinline__ unsigned k4_fcs_scan(K4Shared &sh, int m1, int per, int c0, int c1, int lane)
 {
+	if constexpr (ALL)
+		return k4_fcs_scan_all<REP>(sh, m1, per, c0, c1, lane);
 	const uint8_t *B = reinterpret_cast<const uint8_t *>(sh.dst);
 	unsigned col = 0;	/* the advance map, one state bit per lane */
 	if (lane < 16) {
@@ -820,14 +930,20 @@ __device__ __forceinline__ vdl2gpu_frame_t *k4_alloc(const K4Params &p, int len)
 	return nullptr;
 }
 
-/* the burst's frames: the first one into the record's slot when there is one (myslot) and it fits, the others where k4_alloc says */
+/* the burst's frames: the first one into the record's slot when there is one (myslot) and it fits, the others where k4_alloc says.
+ * ALL: a frame starts where its entry in sh.ends says (k4_fcs_scan), not at m1 */
+template <bool ALL = false>
 __device__ __forceinline__ void k4_emit(K4Shared &sh, const K4Params &p, vdl2gpu_frame_t *myslot, unsigned ib, int m1, int lane)
 {
 	const vdl2gpu_burst_t *const rec = reinterpret_cast<const vdl2gpu_burst_t *>(sh.recw);
 	const uint8_t *B = reinterpret_cast<const uint8_t *>(sh.dst);
 	const int nf = sh.nfr;
 	for (int f = 0; f < nf; ++f) {
-		const int len = sh.ends[f] - m1 + 2;
+		int start = m1, len = sh.ends[f] - m1 + 2;
+		if constexpr (ALL) {
+			start = sh.ends[f] & 0xffff;
+			len = (sh.ends[f] >> 16) - start + 2;
+		}
 		const bool inslot = myslot && f == 0 && k4_fits_slot(len);	/* uniform */
 		if (!inslot) {
 			if (lane == 0)
@@ -852,7 +968,7 @@ __device__ __forceinline__ void k4_emit(K4Shared &sh, const K4Params &p, vdl2gpu
 				fr->data[0] = 0x7e;
 			}
 			for (int i = lane; i < len - 1 && i + 1 < VDL2GPU_MAXFRAME; i += K4_NT)
-				fr->data[i + 1] = B[m1 + i];
+				fr->data[i + 1] = B[start + i];
 		}
 		K4_SYNC();
 	}
@@ -875,7 +991,8 @@ __device__ __forceinline__ void k4_rep_store(const K4Rep &rp, vdl2gpu_blockrep_t
 }
 
 /* FB: p.fb holds the records' decision-feedback rows for the row rule of vdl2gpu_fb_t */
-template <bool REP, bool FB = false>
+/* ALL: every segment between flags is a candidate frame (VDL2GPU_F_ALL_FRAMES), see k4_fcs_scan */
+template <bool REP, bool FB = false, bool ALL = false>
 __device__ __forceinline__ void k4_frames_body(const K4Params &p)
 {
 	__shared__ K4Shared sh;
@@ -942,7 +1059,7 @@ __device__ __forceinline__ void k4_frames_body(const K4Params &p)
 			K4_SYNC();
 			continue;
 		}
-		const unsigned counts = k4_fcs_scan<REP>(sh, m1, per, c0, c1, lane);
+		const unsigned counts = k4_fcs_scan<REP, ALL>(sh, m1, per, c0, c1, lane);
 		if (REP && lane == 0) {
 			const unsigned cand = counts & 0xffffu, too_short = counts >> 16, frames = (unsigned)sh.nfr;	/* (nfr: before k4_sort_candidates caps it) */
 			rp.r.cand = (uint16_t)cand;
@@ -951,12 +1068,13 @@ __device__ __forceinline__ void k4_frames_body(const K4Params &p)
 			rp.r.frames = (uint16_t)frames;
 		}
 		k4_sort_candidates(sh, &p.nframes->dropped, lane);
-		k4_emit(sh, p, myslot, ib, m1, lane);
+		k4_emit<ALL>(sh, p, myslot, ib, m1, lane);
 		if constexpr (REP)
 			k4_rep_store(rp, p.rep + ib, lane);
 	}
 }
 
+#ifndef VDL2GPU_BLOCKS_DEVICE_ONLY
 __global__ __launch_bounds__(K4_NT)
 void k4_frames(K4Params p)
 {
@@ -1017,5 +1135,13 @@ void k4_rs_debug(uint8_t *rows, int *eras, const int *no_eras, int *ret, const u
 	if (lane == 0)
 		ret[ib] = count;
 }
+
+/* VDL2GPU_F_ALL_FRAMES and vdl2gpu_decode_blocks_ex with VDL2GPU_BLK_ALL_FRAMES: the four kernels above with ALL, defined in
+ * vdl2gpu_allframes.hip (a translation unit of their own, so that this one compiles to what it was without them) */
+__global__ void k4_frames_all(K4Params p);
+__global__ void k4_frames_all_rep(K4Params p);
+__global__ void k4_frames_all_fb(K4Params p);
+__global__ void k4_frames_all_rep_fb(K4Params p);
+#endif	/* VDL2GPU_BLOCKS_DEVICE_ONLY */
 
 #endif

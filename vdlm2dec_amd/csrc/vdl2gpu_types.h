@@ -441,6 +441,8 @@ struct KInitParams {		/* per-push reset of the demodulator's control words */
 };
 
 /* ---- constant data tables (d8psk.h:20-249) as bit patterns ------------- */
+/* (defined once in the library: a second translation unit, vdl2gpu_allframes.hip, takes the types alone) */
+#ifndef VDL2GPU_TYPES_NO_TABLES
 #define VDL2_TABLE_BEGIN(name, n) __constant__ uint32_t c_##name[n] = {
 #define VDL2_F32(x) x,
 #define VDL2_TABLE_END };
@@ -453,5 +455,6 @@ struct KInitParams {		/* per-push reset of the demodulator's control words */
 __constant__ int c_hcol[25] = { 6, 7, 9, 10, 11, 12, 14, 15, 17, 19, 21, 22, 24, 25, 26, 27, 28, 29, 30, 31,
 	16, 8, 4, 2, 1
 };
+#endif	/* VDL2GPU_TYPES_NO_TABLES */
 
 #endif

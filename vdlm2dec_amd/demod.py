@@ -147,7 +147,8 @@ class Receiver:
                  max_bursts: int = 0, keep_dec: bool = False, serial: bool = False, full_scan: bool = False,
                  frames: bool = False, rtl_quirk: bool = False, flags: int = 0, testhooks: bool = False,
                  levels: bool = False, soft_rs: bool = False, exact_fo: bool = False, carrier: bool = False,
-                 block_report: bool = False, feedback: bool = False):
+                 block_report: bool = False, feedback: bool = False, all_frames: bool = False):
+        # all_frames: VDL2GPU_F_ALL_FRAMES (needs frames=True), the block path hands on every frame of a burst, not only the first
         # feedback: VDL2GPU_F_FEEDBACK, every burst's rows sliced a second time with decision feedback (Burst.fb); with frames=True the
         # block path takes a row the reference cannot decode from them
         # block_report: VDL2GPU_F_BLOCK_REPORT (needs frames=True), what the block path made of every burst (Burst.report)
@@ -181,11 +182,12 @@ class Receiver:
         cfg.max_bursts = max_bursts
         asked = dict(levels=levels, soft_rs=soft_rs, carrier=carrier, block_report=block_report, feedback=feedback)
         switches = [(keep_dec, _lib.F_KEEP_DEC), (serial, _lib.F_SERIAL), (full_scan, _lib.F_FULLSCAN), (frames, _lib.F_FRAMES),
-                    (rtl_quirk, _lib.F_RTL_QUIRK), (exact_fo, _lib.F_EXACT_FO)] + [(asked[kw], flag) for kw, flag, _, _ in _COLUMNS]
+                    (rtl_quirk, _lib.F_RTL_QUIRK), (exact_fo, _lib.F_EXACT_FO), (all_frames, _lib.F_ALL_FRAMES)] + [(asked[kw], flag) for kw, flag, _, _ in _COLUMNS]
         cfg.flags = flags | sum(flag for on, flag in switches if on)     # (one bit each)
         self.max_push = max_push
         for kw, flag, _, _ in _COLUMNS:     # self.levels, .soft_rs, .carrier, .block_report, .feedback: by keyword or by `flags`
             setattr(self, kw, bool(cfg.flags & flag))
+        self.all_frames = bool(cfg.flags & _lib.F_ALL_FRAMES)
         self.h = C.c_void_p()
         rc = self.L.vdl2gpu_create(C.byref(cfg), C.byref(self.h))
         if rc != 0:
@@ -305,14 +307,16 @@ class Receiver:
         return out
 
     # ------------------------------------------------------------------ block path
-    def decode_blocks(self, blocks: Sequence, max_frames: int = 0, soft=None, report: bool = False, fb=None):
+    def decode_blocks(self, blocks: Sequence, max_frames: int = 0, soft=None, report: bool = False, fb=None, all_frames: bool = False):
         """blk_thread for a batch (vdlm2.c:84-161): (index of the block, hdata) of every frame the
         reference would pass to out().  ``blocks``: Burst objects or (nbrow, nlbyte, data) tuples.
         ``soft``: one (8, 255) uint8 reliability map per block (Burst.soft): the soft row rule of include/vdl2gpu.h
         (vdl2gpu_decode_blocks_soft); None: the reference's block path.
         ``report``: return (frames, [BlockReport of every block]) (vdl2gpu_decode_blocks_report), on any handle.
         ``fb``: one (8, 255) uint8 array of decision-feedback rows per block (Burst.fb): a row the reference cannot decode is taken from
-        them if it decodes there (vdl2gpu_decode_blocks_feedback), on any handle; None: not."""
+        them if it decodes there (vdl2gpu_decode_blocks_feedback), on any handle; None: not.
+        ``all_frames``: every frame of a burst, by the rule of VDL2GPU_F_ALL_FRAMES (vdl2gpu_decode_blocks_ex with
+        VDL2GPU_BLK_ALL_FRAMES), on any handle; the frames of a block come in stream order."""
         n = len(blocks)
         if n == 0:
             return ([], []) if report else []
@@ -323,7 +327,7 @@ class Receiver:
             C.memmove(C.addressof(arr[i].data), bytes(data), min(len(data), 8 * 255))
             if hasattr(b, "chn"):
                 arr[i].stream, arr[i].chn, arr[i].Fr = b.stream, b.chn, b.Fr
-        cap = max_frames or 4 * n
+        cap = max_frames or (12 if all_frames else 4) * n
         out = (_lib.FrameT * cap)()
         dropped = C.c_int(0)
         sarr = None
@@ -345,7 +349,9 @@ class Receiver:
         rarr = (_lib.BlockRepT * n)() if report else None
         # (soft NULL: hard mode; rep NULL: exactly vdl2gpu_decode_blocks_soft, and with both exactly vdl2gpu_decode_blocks; fb NULL: the
         # library's vdl2gpu_decode_blocks_report, which the older calls go through as well)
-        if farr is None:
+        if all_frames:
+            nf = self._check(self.L.vdl2gpu_decode_blocks_ex(self.h, arr, sarr, farr, n, out, cap, C.byref(dropped), rarr, _lib.BLK_ALL_FRAMES))
+        elif farr is None:
             nf = self._check(self.L.vdl2gpu_decode_blocks_report(self.h, arr, sarr, n, out, cap, C.byref(dropped), rarr))
         else:
             nf = self._check(self.L.vdl2gpu_decode_blocks_feedback(self.h, arr, sarr, farr, n, out, cap, C.byref(dropped), rarr))

@@ -32,6 +32,8 @@ F_BLOCK_REPORT = 2048
 ROW_NONE, ROW_CLEAN, ROW_REF, ROW_SOFT2, ROW_SOFT4, ROW_FAIL = range(6)
 ROW_FEEDBACK = 6    # (VDL2GPU_F_FEEDBACK) the record's decision-feedback row replaced the row
 F_FEEDBACK = 4096
+F_ALL_FRAMES = 8192     # (VDL2GPU_F_ALL_FRAMES, needs F_FRAMES) the block path hands on every frame of a burst
+BLK_ALL_FRAMES = 1      # vdl2gpu_decode_blocks_ex's mode word (VDL2GPU_BLK_*)
 # status of a cluster head (vdl2gpu_debug_clheads()'s packed word: cl_pack() in csrc/vdl2gpu_types.h)
 CL_STEADY, CL_DEFER_FIRST, CL_NONSTEADY = 0, 1, 2
 
@@ -70,7 +72,7 @@ EXPORTS = (
     "vdl2gpu_abi_version", "vdl2gpu_create", "vdl2gpu_destroy", "vdl2gpu_push", "vdl2gpu_sync",
     "vdl2gpu_ring_init", "vdl2gpu_ring_acquire", "vdl2gpu_ring_commit",
     "vdl2gpu_poll", "vdl2gpu_poll_ready", "vdl2gpu_poll_levels", "vdl2gpu_poll_levels_ready", "vdl2gpu_poll_soft", "vdl2gpu_poll_soft_ready", "vdl2gpu_poll_carrier", "vdl2gpu_poll_carrier_ready", "vdl2gpu_poll_report", "vdl2gpu_poll_report_ready", "vdl2gpu_poll_feedback", "vdl2gpu_poll_feedback_ready", "vdl2gpu_pending", "vdl2gpu_inflight", "vdl2gpu_get_stats", "vdl2gpu_get_timing", "vdl2gpu_get_host_profile", "vdl2gpu_last_error",
-    "vdl2gpu_strerror", "vdl2gpu_burst_to_msgblk", "vdl2gpu_decode_blocks", "vdl2gpu_decode_blocks_soft", "vdl2gpu_decode_blocks_report", "vdl2gpu_decode_blocks_feedback", "vdl2gpu_poll_frames", "vdl2gpu_poll_frames_ready", "reversebits", "vdl2gpu_lo_len", "vdl2gpu_lo_table", "vdl2gpu_plan",
+    "vdl2gpu_strerror", "vdl2gpu_burst_to_msgblk", "vdl2gpu_decode_blocks", "vdl2gpu_decode_blocks_soft", "vdl2gpu_decode_blocks_report", "vdl2gpu_decode_blocks_feedback", "vdl2gpu_decode_blocks_ex", "vdl2gpu_poll_frames", "vdl2gpu_poll_frames_ready", "reversebits", "vdl2gpu_lo_len", "vdl2gpu_lo_table", "vdl2gpu_plan",
     "vdl2gpu_exact_fo_tables", "vdl2gpu_exact_fo_index", "vdl2gpu_carrier_from_sums",
     "vdl2gpu_choose_fc_rtl", "vdl2gpu_choose_fc_air",
     "vdl2gpu_debug_dec", "vdl2gpu_debug_k1", "vdl2gpu_debug_lo", "vdl2gpu_debug_atan2f", "vdl2gpu_debug_rs", "vdl2gpu_debug_counters", "vdl2gpu_debug_cands", "vdl2gpu_debug_clheads", "vdl2gpu_debug_fail", "vdl2gpu_debug_segs", "vdl2gpu_debug_heads",
@@ -246,6 +248,9 @@ def load(testhooks: bool = False):
     L.vdl2gpu_decode_blocks_feedback.restype = C.c_int
     L.vdl2gpu_decode_blocks_feedback.argtypes = [C.c_void_p, C.POINTER(BurstT), C.POINTER(SoftT), C.POINTER(FbT), C.c_int, C.POINTER(FrameT), C.c_int,
                                                  C.POINTER(C.c_int), C.POINTER(BlockRepT)]
+    L.vdl2gpu_decode_blocks_ex.restype = C.c_int
+    L.vdl2gpu_decode_blocks_ex.argtypes = [C.c_void_p, C.POINTER(BurstT), C.POINTER(SoftT), C.POINTER(FbT), C.c_int, C.POINTER(FrameT), C.c_int,
+                                           C.POINTER(C.c_int), C.POINTER(BlockRepT), C.c_uint32]
     L.vdl2gpu_poll_frames.restype = C.c_int
     L.vdl2gpu_poll_frames.argtypes = [C.c_void_p, C.POINTER(FrameT), C.c_int]
     L.vdl2gpu_poll_frames_ready.restype = C.c_int

@@ -134,24 +134,41 @@ def avlc_frame(info: bytes, src: int = (1 << 24) | 0x4CA2B1, dst: int = (2 << 24
 
 def hdlc_payload(frame: bytes) -> bytes:
     """0x7e | bit-stuffed(frame + FCS lo,hi) | 0x7e, zero padded to a byte boundary."""
+    return hdlc_payload_multi([frame])
+
+
+def hdlc_frame(frame: bytes) -> bytes:
+    """What out() is handed for ``frame``: 0x7e | frame + FCS lo,hi | 0x7e, not stuffed."""
     crc = fcs16(frame)
-    body = frame + bytes([crc & 0xFF, crc >> 8])
+    return b"\x7e" + frame + bytes([crc & 0xFF, crc >> 8]) + b"\x7e"
+
+
+def hdlc_payload_multi(frames: Sequence[bytes], flags_between: int = 1) -> bytes:
+    """Several frames in one burst: 0x7e | stuffed(frame + FCS) | 0x7e x flags_between | stuffed(frame + FCS) | ... | 0x7e, zero padded
+    to a byte boundary once, at the end.  With flags_between == 1 one flag closes a frame and opens the next."""
+    if not frames or flags_between < 1:
+        raise ValueError("at least one frame and one flag between two frames")
     bits: List[int] = []
     flag = [0, 1, 1, 1, 1, 1, 1, 0]
     bits += flag
-    ones = 0
-    for byte in body:
-        for n in range(8):
-            b = (byte >> n) & 1
-            bits.append(b)
-            if b:
-                ones += 1
-                if ones == 5:
-                    bits.append(0)
+    for j, frame in enumerate(frames):
+        if j:
+            bits += flag * (flags_between - 1)
+        crc = fcs16(frame)
+        body = bytes(frame) + bytes([crc & 0xFF, crc >> 8])
+        ones = 0
+        for byte in body:
+            for n in range(8):
+                b = (byte >> n) & 1
+                bits.append(b)
+                if b:
+                    ones += 1
+                    if ones == 5:
+                        bits.append(0)
+                        ones = 0
+                else:
                     ones = 0
-            else:
-                ones = 0
-    bits += flag
+        bits += flag
     while len(bits) % 8:
         bits.append(0)
     arr = np.array(bits, dtype=np.uint8).reshape(-1, 8)
@@ -309,11 +326,19 @@ class Burst:
     cfo: float = 0.0     # Hz carrier offset
     corrupt: Optional[dict] = None
     raw_payload: Optional[bytes] = None  # bypass AVLC/HDLC: bytes handed straight to burst_bits
+    infos: Optional[List[bytes]] = None  # several AVLC frames in this one burst, sharing single flags (`info` is then unused)
+
+    def frames(self) -> List[bytes]:
+        """the burst's AVLC frames as they stand between the flags, without FCS; frame j of several has its own src address"""
+        if self.infos is None:
+            return [avlc_frame(self.info, src=(1 << 24) | (0x400000 + self.chan * 0x111 + len(self.info)))]
+        return [avlc_frame(info, src=(1 << 24) | (0x400000 + self.chan * 0x111 + len(info) + 0x10000 * (j + 1)))
+                for j, info in enumerate(self.infos)]
 
     def payload(self) -> bytes:
         if self.raw_payload is not None:
             return self.raw_payload
-        return hdlc_payload(avlc_frame(self.info, src=(1 << 24) | (0x400000 + self.chan * 0x111 + len(self.info))))
+        return hdlc_payload_multi(self.frames())
 
     def n_symbols(self) -> int:
         return len(burst_increments(burst_bits(self.payload())))
@@ -383,8 +408,9 @@ DEFAULT_FO_8CH = (-450000, -350000, -250000, -150000, -50000, 100000, 200000, 30
 def random_scenario(rate: int, fo: Sequence[int], nsamples: int, seed: int,
                     bursts_per_s: float = 6.0, info_max: int = 300, noise: float = 1.7,
                     amp_range=(8.0, 60.0), cfo_max: float = 400.0,
-                    info_choices: Optional[Sequence[int]] = None) -> StreamSpec:
-    """Poisson-ish non-overlapping bursts per channel."""
+                    info_choices: Optional[Sequence[int]] = None, frames_per_burst: int = 1) -> StreamSpec:
+    """Poisson-ish non-overlapping bursts per channel.  frames_per_burst > 1: every burst carries so many AVLC
+    frames (Burst.infos), the first with the info field a burst of one frame would have had, the others drawn behind it."""
     rng = np.random.default_rng(seed ^ 0x5EED)
     dur = nsamples / rate
     bursts: List[Burst] = []
@@ -398,6 +424,9 @@ def random_scenario(rate: int, fo: Sequence[int], nsamples: int, seed: int,
             info = bytes(rng.integers(0, 256, n_info, dtype=np.uint8).tolist())
             b = Burst(chan=c, t0=t, info=info, amp=float(rng.uniform(*amp_range)),
                       cfo=float(rng.uniform(-cfo_max, cfo_max)))
+            if frames_per_burst > 1:
+                b.infos = [info] + [bytes(rng.integers(0, 256, int(rng.integers(1, len(info) + 1)), dtype=np.uint8).tolist())
+                                    for _ in range(frames_per_burst - 1)]
             d = b.duration()
             if t + d + 0.001 > dur:
                 break
@@ -426,18 +455,21 @@ def _cli(argv=None) -> int:
     ap.add_argument("--noise", type=float, default=1.7, help="AWGN sigma per component, LSB at cu8 scale")
     ap.add_argument("--cfo", type=float, default=400.0, help="carrier offsets uniform in +-CFO Hz")
     ap.add_argument("--seed", type=int, default=1)
+    ap.add_argument("--frames-per-burst", type=int, default=1, help="AVLC frames in every burst, one flag between two (a receiver needs "
+                    "VDL2GPU_F_ALL_FRAMES to see more than the first)")
     ap.add_argument("--truth", help="JSON file: every burst sent (channel, start, AVLC info, the frame out() must see, msgblk rows)")
     a = ap.parse_args(argv)
     ns = (int(a.seconds * a.rate) + 32767) // 32768 * 32768      # whole RTL hand-off blocks (vdlm2.h:35)
     spec = random_scenario(a.rate, a.fo, ns, seed=a.seed, bursts_per_s=a.bursts_per_s, info_max=a.info_max,
-                           noise=a.noise, amp_range=tuple(a.amp), cfo_max=a.cfo)
+                           noise=a.noise, amp_range=tuple(a.amp), cfo_max=a.cfo, frames_per_burst=a.frames_per_burst)
     synth_stream(spec, a.fmt).tofile(a.out)
     if a.truth:
         tr = []
         for b in sorted(spec.bursts, key=lambda b: b.t0):
             nbrow, nlbyte, rows = received_rows(b.payload())
             tr.append(dict(chan=b.chan, fo=int(a.fo[b.chan]), t0=b.t0, amp=b.amp, cfo=b.cfo, info=b.info.hex(),
-                           payload=b.payload().hex(), nbrow=nbrow, nlbyte=nlbyte, symbols=b.n_symbols()))
+                           payload=b.payload().hex(), nbrow=nbrow, nlbyte=nlbyte, symbols=b.n_symbols(),
+                           **({} if b.infos is None else dict(infos=[i.hex() for i in b.infos]))))
         json.dump(dict(rate=a.rate, fmt=a.fmt, fo=list(a.fo), nsamples=ns, noise=a.noise, seed=a.seed, bursts=tr), open(a.truth, "w"))
     print(f"{a.out}: {ns} samples @ {a.rate} S/s {a.fmt}, {len(a.fo)} channels, {len(spec.bursts)} bursts")
     return 0
