@@ -22,7 +22,8 @@
  * un-stuffing, FCS for a whole batch of bursts in one kernel) and the shim goes straight to
  * out(msgblk_t*, unsigned char *hdata, int l) (vdlm2.h:134, called by check_frame, vdlm2.c:60):
  * then vdlm2.c, rs.c and crc.c drop out of the build too.  With VDL2GPU_RCV_ALL_FRAMES in the environment that build hands out() every
- * frame of a burst that carries several (vdl2gpu_decode_blocks_ex, VDL2GPU_BLK_ALL_FRAMES), not only the first.  At the rates the GPU front end
+ * frame of a burst that carries several (vdl2gpu_decode_blocks_ex, VDL2GPU_BLK_ALL_FRAMES), not only the first; with VDL2GPU_RCV_RAW_FLAGS
+ * it does that and tells a stuffed data byte 0x7e from a flag (VDL2GPU_BLK_RAW_FLAGS), so frames that hold one arrive.  At the rates the GPU front end
  * demodulates at, the reference's single blk_thread cannot keep up.
  *
  * This file contains no DSP.  It is compiled against the reference's own vdlm2.h.
@@ -81,7 +82,8 @@ _Static_assert(NSTAMP >= BATCH_BLOCKS * 5 + 64, "the stamp ring must reach back 
 static vdl2gpu_t *g_h;
 static long long g_last_ns;	/* when the previous hand-off came */
 #ifdef VDL2GPU_FRAMES
-static int g_all_frames;	/* VDL2GPU_RCV_ALL_FRAMES is set: deliver() asks for every frame of a burst */
+static uint32_t g_blk_mode;	/* VDL2GPU_RCV_ALL_FRAMES is set: deliver() asks for every frame of a burst (VDL2GPU_BLK_ALL_FRAMES);
+				 * VDL2GPU_RCV_RAW_FLAGS: that, with VDL2GPU_BLK_RAW_FLAGS beside it */
 #endif
 static int g_null;		/* VDL2GPU_RCV_NULL=1: keep the barrier protocol, do nothing else (measures what the protocol alone allows) */
 static char *g_slot;		/* the slot being filled, or NULL */
@@ -108,9 +110,10 @@ static void deliver(vdl2gpu_t *h, int wait)
 	int n, nf, i, dropped = 0;
 	while ((n = wait ? vdl2gpu_poll(h, b, 64) : vdl2gpu_poll_ready(h, b, 64)) > 0) {
 		/* VDL2GPU_RCV_ALL_FRAMES: every frame of a burst goes to out(), in (block, seq) order -- the reference's check_frame() can
-		 * only pass the first (include/vdl2gpu.h, VDL2GPU_F_ALL_FRAMES).  Unset: vdl2gpu_decode_blocks, as ever */
-		nf = g_all_frames ? vdl2gpu_decode_blocks_ex(h, b, NULL, NULL, n, f, 128, &dropped, NULL, VDL2GPU_BLK_ALL_FRAMES)
-				  : vdl2gpu_decode_blocks(h, b, n, f, 128, &dropped);
+		 * only pass the first (include/vdl2gpu.h, VDL2GPU_F_ALL_FRAMES).  VDL2GPU_RCV_RAW_FLAGS: the same by the rule of
+		 * VDL2GPU_F_RAW_FLAGS.  Both unset: vdl2gpu_decode_blocks, as ever */
+		nf = g_blk_mode ? vdl2gpu_decode_blocks_ex(h, b, NULL, NULL, n, f, 128, &dropped, NULL, g_blk_mode)
+				: vdl2gpu_decode_blocks(h, b, n, f, 128, &dropped);
 		if (dropped)	/* more frames than the buffer holds (or than 12 in one burst): never silent */
 			fprintf(stderr, "vdl2gpu_decode_blocks: %d frame(s) dropped\n", dropped);
 		for (i = 0; i < nf; i++) {
@@ -246,7 +249,9 @@ void *rcv_thread(void *arg)
 		}
 		g_null = getenv("VDL2GPU_RCV_NULL") != NULL;
 #ifdef VDL2GPU_FRAMES
-		g_all_frames = getenv("VDL2GPU_RCV_ALL_FRAMES") != NULL;
+		g_blk_mode = getenv("VDL2GPU_RCV_ALL_FRAMES") != NULL ? VDL2GPU_BLK_ALL_FRAMES : 0u;
+		if (getenv("VDL2GPU_RCV_RAW_FLAGS") != NULL)	/* (implies every frame) */
+			g_blk_mode = VDL2GPU_BLK_ALL_FRAMES | VDL2GPU_BLK_RAW_FLAGS;
 #endif
 		pthread_mutex_lock(&g_mu);
 		g_h = h;

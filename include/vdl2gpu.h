@@ -432,7 +432,7 @@ typedef struct {
  * One thing follows from working on B, as the reference does: the un-stuffer hands a stuffed data byte 0x7e on as the byte 0x7e, and
  * the rule takes it for a flag (so does check_frame()'s caller, vdlm2.c:143, where it only adds a candidate that fails).  A frame that
  * holds a data byte 0x7e is therefore cut there in this mode and does not pass, not even as the first frame of its burst, which the
- * block path without the flag delivers.  A consumer that must not lose those runs a handle without the flag beside one with it.
+ * block path without the flag delivers.  A consumer that must not lose those sets VDL2GPU_F_RAW_FLAGS as well (below).
  * As without the flag: at most 12 passing frames of a burst are kept, the first 12 in stream order, and further ones are counted in
  * vdl2gpu_stats_t.frames_dropped / *dropped; bytes behind the last flag are ignored; nothing is re-aligned at bit level -- flags
  * survive the un-stuffer and frames are whole bytes, so byte alignment holds across the frames of a burst.
@@ -443,6 +443,30 @@ typedef struct {
  * vdl2gpu_poll_frames keeps its order (end_dec, stream, chn, seq). */
 #define VDL2GPU_F_ALL_FRAMES 8192u
 #define VDL2GPU_HAVE_ALL_FRAMES 1
+
+/* ---- a flag is six adjacent ones (VDL2GPU_F_RAW_FLAGS; announced by VDL2GPU_HAVE_RAW_FLAGS, the ABI version is unchanged) ----
+ * A mode of VDL2GPU_F_ALL_FRAMES (vdl2gpu_create returns VDL2GPU_EINVAL for this flag without that one), and in
+ * vdl2gpu_decode_blocks_ex VDL2GPU_BLK_RAW_FLAGS beside VDL2GPU_BLK_ALL_FRAMES on any handle.  It tells a flag from a stuffed data
+ * byte 0x7e, which the rule above cannot, by looking at the stuffed bit stream.
+ * The reference's un-stuffing loop (vdlm2.c:119-133) keeps t, the run of ones in front of the bit it reads; a zero read with t == 5 is
+ * dropped.  Every whole un-stuffed byte B[q] ends with its bit 7; where B[q] == 0x7e that bit is a zero that is kept.  Let t7[q] be t
+ * when that zero is read.
+ *   true flag     F[q] = (B[q] == 0x7e && t7[q] == 6): written "t == 6" -- the six ones are adjacent in the stuffed stream
+ *   data byte     a data byte 0x7e was sent as 0 11111 0 1 0; the zero behind its fifth one is dropped, so t7[q] == 1.  (The only place
+ *                 a zero can be dropped inside a byte that un-stuffs to 0x7e is between its bits 5 and 6: "a zero was dropped at
+ *                 un-stuffed bit offset 8q + 6" is the same statement as !F[q] for such a byte.)
+ * The rule of VDL2GPU_F_ALL_FRAMES then holds with F[q] in place of B[q] == 0x7e, in two places:
+ *   m1            is the first q > flag_at with !F[q] (not "the first byte that is no 0x7e": a frame that begins with a data byte 0x7e
+ *                 keeps that byte).  flag_at itself is unchanged, the prefix OR reaching 0x7e
+ *   segments      q_0 < q_1 < ... are the positions q >= m1 with F[q]; s_0, s_{j+1}, l_j, "passes", seq, the first 12 kept and
+ *                 frames_dropped are as above.  The frame is 0x7e, B[s_j .. q_j]: un-stuffed bytes, data bytes 0x7e among them
+ * The block report in this mode: cand counts the true flags at q >= m1; too_short, bad_fcs and frames follow those segments;
+ * cand == too_short + bad_fcs + frames still holds; every field in front of cand (the rows, stuffed, nbytes, flag_at, status) is what it
+ * is without the mode.
+ * A burst without a data byte 0x7e between its flags gives the same frames and the same report with and without this mode.  Nothing is
+ * re-aligned at bit level, as before: a flag that does not end on a byte boundary of B is not seen. */
+#define VDL2GPU_F_RAW_FLAGS 16384u
+#define VDL2GPU_HAVE_RAW_FLAGS 1
 
 typedef struct {
 	uint64_t samples_in;	/* per stream */
@@ -644,8 +668,12 @@ int vdl2gpu_decode_blocks_feedback(vdl2gpu_t *h, const vdl2gpu_burst_t *blocks, 
 				   vdl2gpu_frame_t *frames, int max_frames, int *dropped, vdl2gpu_blockrep_t *rep);
 /* ... and with a mode word (announced by VDL2GPU_HAVE_ALL_FRAMES), so that a further mode needs no further name.
  * VDL2GPU_BLK_ALL_FRAMES: every frame of a burst, by the rule at VDL2GPU_F_ALL_FRAMES.  Works on any handle; soft, fb and rep may each be
- * NULL; mode == 0: exactly vdl2gpu_decode_blocks_feedback; any other bit: VDL2GPU_EINVAL before any device call. */
+ * NULL; mode == 0: exactly vdl2gpu_decode_blocks_feedback.
+ * VDL2GPU_BLK_ALL_FRAMES | VDL2GPU_BLK_RAW_FLAGS (announced by VDL2GPU_HAVE_RAW_FLAGS): that with the rule at VDL2GPU_F_RAW_FLAGS.
+ * The mode word is 0, 1 or 5; every other value -- VDL2GPU_BLK_RAW_FLAGS alone, bit 1 (unassigned), any higher bit -- is VDL2GPU_EINVAL
+ * before any device call. */
 #define VDL2GPU_BLK_ALL_FRAMES 1u
+#define VDL2GPU_BLK_RAW_FLAGS 4u
 int vdl2gpu_decode_blocks_ex(vdl2gpu_t *h, const vdl2gpu_burst_t *blocks, const vdl2gpu_soft_t *soft, const vdl2gpu_fb_t *fb, int n,
 			     vdl2gpu_frame_t *frames, int max_frames, int *dropped, vdl2gpu_blockrep_t *rep, uint32_t mode);
 /* With VDL2GPU_F_FRAMES the same kernel runs on every push's burst records where they lie in device

@@ -1197,6 +1197,10 @@ extern "C" int vdl2gpu_create(const vdl2gpu_config_t *cfg, vdl2gpu_t **out)
 		create_err = "vdl2gpu_create: VDL2GPU_F_ALL_FRAMES needs VDL2GPU_F_FRAMES (the pipeline has no block path to take frames from)";
 		return VDL2GPU_EINVAL;
 	}
+	if ((cfg->flags & VDL2GPU_F_RAW_FLAGS) && !(cfg->flags & VDL2GPU_F_ALL_FRAMES)) {
+		create_err = "vdl2gpu_create: VDL2GPU_F_RAW_FLAGS needs VDL2GPU_F_ALL_FRAMES (it says what a flag is between the frames of a burst)";
+		return VDL2GPU_EINVAL;
+	}
 	const unsigned sdrclk = cfg->sdrclk ? cfg->sdrclk : cfg->sdrinrate / 4000;
 	if (sdrclk <= 21 || sdrclk > 1000000)
 		return VDL2GPU_EINVAL;
@@ -1605,11 +1609,14 @@ extern "C" int vdl2gpu_ring_commit(vdl2gpu_t *h, size_t nsamples)
 /* k4_frames on the records of output ring `ring` where they lie: compact entries, the record count from the device.  fmask: not
  * nullptr when K2d's second pass tags void records (see K4Params) */
 /* The block kernel on `grid` workgroups of stream s: with a report or without (rep), with the records' decision-feedback rows in the
- * row rule (k4.fb is given) or without; all: every segment between flags is a candidate frame (VDL2GPU_F_ALL_FRAMES) */
-static void launch_blocks(hipStream_t s, unsigned grid, const K4Params &k4, bool rep, bool all)
+ * row rule (k4.fb is given) or without; mode (VDL2GPU_BLK_*): 0, every segment between flags is a candidate frame (ALL_FRAMES), or that
+ * with a flag being six adjacent ones of the stuffed stream (ALL_FRAMES | RAW_FLAGS) */
+static void launch_blocks(hipStream_t s, unsigned grid, const K4Params &k4, bool rep, uint32_t mode)
 {
-	void (*const kernel)(K4Params) = all ? (k4.fb ? (rep ? k4_frames_all_rep_fb : k4_frames_all_fb) : (rep ? k4_frames_all_rep : k4_frames_all))
-					     : (k4.fb ? (rep ? k4_frames_rep_fb : k4_frames_fb) : (rep ? k4_frames_rep : k4_frames));
+	void (*const kernel)(K4Params) =
+		mode & VDL2GPU_BLK_RAW_FLAGS ? (k4.fb ? (rep ? k4_frames_raw_rep_fb : k4_frames_raw_fb) : (rep ? k4_frames_raw_rep : k4_frames_raw))
+		: mode & VDL2GPU_BLK_ALL_FRAMES ? (k4.fb ? (rep ? k4_frames_all_rep_fb : k4_frames_all_fb) : (rep ? k4_frames_all_rep : k4_frames_all))
+						: (k4.fb ? (rep ? k4_frames_rep_fb : k4_frames_fb) : (rep ? k4_frames_rep : k4_frames));
 	hipLaunchKernelGGL(kernel, dim3(grid), dim3(K4_NT), 0, s, k4);
 }
 
@@ -1786,7 +1793,7 @@ static int enqueue_back(vdl2gpu_t *h)
 		 * a latency-bound kernel like this one and the next push's scan slow each other down by
 		 * more than the overlap saves. */
 		launch_blocks(ts, (unsigned)h->n_cu * 16, k4_ring_params(h, ring, spec ? h->set[par].k2.fmask : nullptr), h->col_on[COL_REPORT],
-			      (h->cfg.flags & VDL2GPU_F_ALL_FRAMES) != 0);
+			      (h->cfg.flags & VDL2GPU_F_ALL_FRAMES ? VDL2GPU_BLK_ALL_FRAMES : 0u) | (h->cfg.flags & VDL2GPU_F_RAW_FLAGS ? VDL2GPU_BLK_RAW_FLAGS : 0u));
 		HIPCHK(h, hipGetLastError());
 	}
 	TRY(mark(h, pt, E_BLOCKS_END, ts));
@@ -2835,11 +2842,13 @@ extern "C" int vdl2gpu_decode_blocks_feedback(vdl2gpu_t *h, const vdl2gpu_burst_
 }
 
 /* rep: the reporting kernel, and its n reports come back beside the frames; fb: the kernel with the feedback row rule; mode:
- * VDL2GPU_BLK_ALL_FRAMES, the kernel that takes every segment between flags for a candidate (launch_blocks) */
+ * VDL2GPU_BLK_ALL_FRAMES, the kernel that takes every segment between flags for a candidate, with VDL2GPU_BLK_RAW_FLAGS the one that
+ * tells a flag from a stuffed data byte 0x7e (launch_blocks) */
 extern "C" int vdl2gpu_decode_blocks_ex(vdl2gpu_t *h, const vdl2gpu_burst_t *blocks, const vdl2gpu_soft_t *soft, const vdl2gpu_fb_t *fb, int n,
 					vdl2gpu_frame_t *frames, int max_frames, int *dropped, vdl2gpu_blockrep_t *rep, uint32_t mode)
 {
-	if (!h || n < 0 || max_frames < 0 || (n > 0 && !blocks) || (max_frames > 0 && !frames) || (mode & ~VDL2GPU_BLK_ALL_FRAMES))
+	if (!h || n < 0 || max_frames < 0 || (n > 0 && !blocks) || (max_frames > 0 && !frames) ||
+	    (mode != 0u && mode != VDL2GPU_BLK_ALL_FRAMES && mode != (VDL2GPU_BLK_ALL_FRAMES | VDL2GPU_BLK_RAW_FLAGS)))
 		return VDL2GPU_EINVAL;
 	if (dropped)
 		*dropped = 0;
@@ -2872,7 +2881,7 @@ extern "C" int vdl2gpu_decode_blocks_ex(vdl2gpu_t *h, const vdl2gpu_burst_t *blo
 		BLKCHK(hipMemcpyAsync(d.fb, fb, (size_t)n * sizeof(vdl2gpu_fb_t), hipMemcpyHostToDevice, h->copy_stream));
 	BLKCHK(hipMemsetAsync(d.cnt, 0, sizeof *d.cnt, h->copy_stream));
 	const unsigned grid = (unsigned)std::min<long long>(n, (long long)h->n_cu * 32);
-	launch_blocks(h->copy_stream, grid, k4_block_params(h, d, n, max_frames), rep != nullptr, (mode & VDL2GPU_BLK_ALL_FRAMES) != 0);
+	launch_blocks(h->copy_stream, grid, k4_block_params(h, d, n, max_frames), rep != nullptr, mode);
 	BLKCHK(hipGetLastError());
 	if (rep)	/* (no record is void here: every one of the n has been written) */
 		BLKCHK(hipMemcpyAsync(rep, d.rep, (size_t)n * sizeof(vdl2gpu_blockrep_t), hipMemcpyDeviceToHost, h->copy_stream));

@@ -19,6 +19,8 @@
  * row that rs() fails on (k4_fb_row), in front of the soft trials.
  * ... and over ALL: the four kernels k4_frames_all* (vdl2gpu_allframes.hip) take every segment between two flags for a candidate frame,
  * not only what follows the first flag (VDL2GPU_F_ALL_FRAMES): k4_fcs_scan_all in k4_fcs_scan's place, k4_emit with each frame's own start.
+ * ... and over RAW: the four kernels k4_frames_raw* (vdl2gpu_rawflags.hip) are those with VDL2GPU_F_RAW_FLAGS: k4_unstuff marks the bytes
+ * that lost a stuffed zero in front of their bit 6, and a byte 0x7e with that mark is data to k4_flag_hunt and k4_fcs_scan_all, no flag.
  */
 #ifndef VDL2GPU_BLOCKS_H
 #define VDL2GPU_BLOCKS_H
@@ -87,7 +89,8 @@ struct K4Shared {
 	/* Berlekamp-Massey work arrays live here, not in (scratch-backed) private arrays */
 	uint8_t lam[8], syn[8], omg[8], root[8], loc[8];
 	int rs_deg, rs_count, rs_fail;
-	uint8_t save[256];	/* soft mode and the report: the received row, for the trials and for row_changed */
+	uint8_t save[256];	/* soft mode and the report: the received row, for the trials and for row_changed.  Behind the rows (RAW): the
+				 * un-stuffer's marks, see k4_unstuff */
 	int cand[4];		/* soft mode: the least reliable candidate positions, most doubtful first */
 };
 
@@ -626,10 +629,31 @@ __device__ __forceinline__ unsigned k4_stuffed(unsigned v, int t)
 /* ones at the end of the stream after byte v, t of them in front of it: those above the byte's highest zero (bit 7 downwards) */
 __device__ __forceinline__ int k4_run_after(unsigned v, int t) { return v == 0xffu ? t + 8 : __clz((int)((~v & 0xffu) << 24)); }
 
-__device__ __forceinline__ int k4_unstuff(K4Shared &sh, int nby, int lane)
+/* RAW (VDL2GPU_F_RAW_FLAGS, include/vdl2gpu.h): the un-stuffer also leaves one bit per un-stuffed byte in marks[], bit q & 31 of word
+ * q >> 5: a zero was dropped in front of the byte's bit 6.  A byte that un-stuffs to 0x7e can have lost a zero nowhere else (its bit 0 is
+ * a kept zero, five ones follow), so for such a byte the mark says "the six ones were not adjacent in the stuffed stream": a data byte,
+ * no flag -- the reference's t is 1, not 6, at the byte's last bit.  The lane knows where each of its dropped zeros falls in the output. */
+#define K4_MARKW 64	/* words of marks: one bit for each of K4_MAXBY bytes, and a word behind them for k4_lane_marks */
+static_assert(K4_MAXBY <= 32 * (K4_MARKW - 1) && K4_MARKW == K4_NT, "one mark per un-stuffed byte; every lane clears one word");
+
+/* They live in sh.save: the received row is dead once k4_rs_rows is through, and the RAW kernels keep their siblings' LDS */
+static_assert(sizeof(K4Shared::save) >= 4 * K4_MARKW && offsetof(K4Shared, save) % 4 == 0, "the marks fit the saved row's place, as words");
+
+/* the marks of the lane's un-stuffed bytes [c0, c0 + 32): bit i - c0 is byte i's (a lane's span is 32 bytes at most) */
+static_assert((K4_MAXBY + K4_NT - 1) / K4_NT <= 32, "a lane's marks are one word");
+__device__ __forceinline__ unsigned k4_lane_marks(const unsigned *marks, int c0)
+{
+	const unsigned long long w = (unsigned long long)marks[(c0 >> 5) + 1] << 32 | marks[c0 >> 5];
+	return (unsigned)(w >> (c0 & 31));
+}
+
+template <bool RAW = false>
+__device__ __forceinline__ int k4_unstuff(K4Shared &sh, int nby, int lane, unsigned *marks = nullptr)
 {
 	for (int i = lane; i < nby / 4 + 2; i += K4_NT)
 		sh.dst[i] = 0u;
+	if constexpr (RAW)
+		marks[lane] = 0u;	/* (K4_MARKW == K4_NT) */
 	K4_SYNC();
 	int b0, b1;	/* lane owns bytes [b0, b1) */
 	k4_lane_span(nby, lane, &b0, &b1);
@@ -665,6 +689,11 @@ __device__ __forceinline__ int k4_unstuff(K4Shared &sh, int nby, int lane)
 				v = (v & ((1u << d) - 1u)) | ((v >> (d + 1)) << d);
 				dr &= ~(1u << d);
 				--nbits;
+				if constexpr (RAW) {
+					const int at = o + d - __popc(dr);	/* bits kept in front of this zero: those below it in v that stay */
+					if ((at & 7) == 6)
+						atomicOr(&marks[at >> 8], 1u << ((at >> 3) & 31));
+				}
 			}
 			acc |= (unsigned long long)v << (o & 31);
 			o += nbits;
@@ -683,8 +712,9 @@ __device__ __forceinline__ int k4_unstuff(K4Shared &sh, int nby, int lane)
 
 /* ---- first flag: the byte at which the OR of all bytes so far equals 0x7e (vdlm2.c:129-133); flags right behind the first one are
  * swallowed (k == 1, vdlm2.c:134-135).  The lane owns the un-stuffed bytes [c0, c1).  Returns the first byte behind the flags,
- * hdata[1], or K4_NONE: no flag, or nothing but flags behind it. */
-__device__ __forceinline__ int k4_flag_hunt(K4Shared &sh, int c0, int c1, int lane)
+ * hdata[1], or K4_NONE: no flag, or nothing but flags behind it.  RAW: only a true flag is swallowed (marks[], see k4_unstuff). */
+template <bool RAW = false>
+__device__ __forceinline__ int k4_flag_hunt(K4Shared &sh, int c0, int c1, int lane, const unsigned *marks = nullptr)
 {
 	const uint8_t *B = reinterpret_cast<const uint8_t *>(sh.dst);
 	unsigned lor = 0;	/* OR of all bytes in front of the lane's */
@@ -708,12 +738,17 @@ __device__ __forceinline__ int k4_flag_hunt(K4Shared &sh, int c0, int c1, int la
 	}
 	K4_SYNC();
 	const int m0 = sh.flag0;
+	unsigned data7e = 0;	/* RAW: a data byte 0x7e is hdata[1] like any other */
+	if constexpr (RAW)
+		data7e = k4_lane_marks(marks, c0);
 	if (m0 != K4_NONE)
-		for (int i = c0 > m0 + 1 ? c0 : m0 + 1; i < c1; ++i)
-			if (B[i] != 0x7eu) {
+		for (int i = c0 > m0 + 1 ? c0 : m0 + 1; i < c1; ++i) {
+			const bool flag = B[i] == 0x7eu && !(RAW && ((data7e >> (i - c0)) & 1u));
+			if (!flag) {
 				atomicMin(&sh.data0, i);
 				break;
 			}
+		}
 	K4_SYNC();
 	return sh.data0;
 }
@@ -733,16 +768,20 @@ __device__ __forceinline__ int k4_flag_hunt(K4Shared &sh, int c0, int c1, int la
  * are untouched.  The lane that holds m1 starts from 0xffff and is a reset by construction.  A maximum scan of the lanes' last flags gives
  * every lane the start of the segment its first byte lies in.  sh.ends[] gets q << 16 | s of the segments that pass, in stream order
  * (ranks from a prefix sum of the lanes' counts: the first K4_NCAND of the burst are the ones kept), sh.nfr their number; the counts
- * follow the same rule: too_short is l_j < 13, flags side by side (l_j = 2) included. */
+ * follow the same rule: too_short is l_j < 13, flags side by side (l_j = 2) included.
+ * RAW (VDL2GPU_F_RAW_FLAGS): "a flag" is a byte 0x7e without the un-stuffer's mark (k4_unstuff); a marked one is a data byte like any other. */
 /* segments that pass are 12 bytes apart at least (l >= 13), so a lane meets at most three closing flags of such */
 #define K4_ALL_LANE_MAX 3
 static_assert((K4_MAXBY + K4_NT - 1) / K4_NT <= 12 * K4_ALL_LANE_MAX, "a lane's span holds at most K4_ALL_LANE_MAX passing segments' ends");
 static_assert(K4_MAXBY < 65536, "a candidate's closing flag and start share a word");
 
-template <bool REP>
-__device__ __forceinline__ unsigned k4_fcs_scan_all(K4Shared &sh, int m1, int per, int c0, int c1, int lane)
+template <bool REP, bool RAW = false>
+__device__ __forceinline__ unsigned k4_fcs_scan_all(K4Shared &sh, int m1, int per, int c0, int c1, int lane, const unsigned *marks = nullptr)
 {
 	const uint8_t *B = reinterpret_cast<const uint8_t *>(sh.dst);
+	unsigned data7e = 0;	/* RAW: the lane's bytes that are no flag whatever their value, bit i - c0 (k4_lane_marks) */
+	if constexpr (RAW)
+		data7e = k4_lane_marks(marks, c0);
 	unsigned col = 0;	/* the advance map, one state bit per lane */
 	if (lane < 16) {
 		col = 1u << lane;
@@ -758,7 +797,7 @@ __device__ __forceinline__ unsigned k4_fcs_scan_all(K4Shared &sh, int m1, int pe
 		x = reset ? 0xffffu : 0u;
 		for (int i = b0; i < c1; ++i) {
 			const unsigned v = B[i];
-			if (v == 0x7eu) {
+			if (v == 0x7eu && !(RAW && ((data7e >> (i - c0)) & 1u))) {
 				x = 0xffffu;
 				reset = 1;
 				last = i;
@@ -796,7 +835,7 @@ __device__ __forceinline__ unsigned k4_fcs_scan_all(K4Shared &sh, int m1, int pe
 		int s = (lane == L1 || flag_in < 0) ? m1 : flag_in + 1;
 		for (int q = b0; q < c1; ++q) {
 			const unsigned v = B[q];
-			if (v == 0x7eu) {
+			if (v == 0x7eu && !(RAW && ((data7e >> (q - c0)) & 1u))) {
 				const int l = q - s + 2;
 				if (l >= 13 && c == 0xf0b8u) {
 					const unsigned w = (unsigned)q << 16 | (unsigned)s;
@@ -828,11 +867,12 @@ __device__ __forceinline__ unsigned k4_fcs_scan_all(K4Shared &sh, int m1, int pe
 	return counts;
 }
 
-template <bool REP, bool ALL = false>
-__device__ __forceinline__ unsigned k4_fcs_scan(K4Shared &sh, int m1, int per, int c0, int c1, int lane)
+template <bool REP, bool ALL = false, bool RAW = false>
+__device__ __forceinline__ unsigned k4_fcs_scan(K4Shared &sh, int m1, int per, int c0, int c1, int lane, const unsigned *marks = nullptr)
 {
+	static_assert(ALL || !RAW, "VDL2GPU_F_RAW_FLAGS is a mode of VDL2GPU_F_ALL_FRAMES");
 	if constexpr (ALL)
-		return k4_fcs_scan_all<REP>(sh, m1, per, c0, c1, lane);
+		return k4_fcs_scan_all<REP, RAW>(sh, m1, per, c0, c1, lane, marks);
 	const uint8_t *B = reinterpret_cast<const uint8_t *>(sh.dst);
 	unsigned col = 0;	/* the advance map, one state bit per lane */
 	if (lane < 16) {
@@ -992,11 +1032,13 @@ __device__ __forceinline__ void k4_rep_store(const K4Rep &rp, vdl2gpu_blockrep_t
 
 /* FB: p.fb holds the records' decision-feedback rows for the row rule of vdl2gpu_fb_t */
 /* ALL: every segment between flags is a candidate frame (VDL2GPU_F_ALL_FRAMES), see k4_fcs_scan */
-template <bool REP, bool FB = false, bool ALL = false>
+/* RAW: ... and a flag is six adjacent ones of the stuffed stream (VDL2GPU_F_RAW_FLAGS), see k4_unstuff */
+template <bool REP, bool FB = false, bool ALL = false, bool RAW = false>
 __device__ __forceinline__ void k4_frames_body(const K4Params &p)
 {
 	__shared__ K4Shared sh;
 	__shared__ K4Rep rp;	/* (REP; never touched without it) */
+	unsigned *const marks = RAW ? reinterpret_cast<unsigned *>(sh.save) : nullptr;	/* (behind k4_rs_rows: see k4_unstuff) */
 	const int lane = threadIdx.x;
 	/* Everything the first record needs from memory is asked for at once -- the tables, the record
 	 * count and the front of record blockIdx.x -- because this kernel runs beside the next push's
@@ -1043,11 +1085,11 @@ __device__ __forceinline__ void k4_frames_body(const K4Params &p)
 			continue;
 		k4_fetch_rows(sh, p.recs + ib, nbrow, lane);
 		const int nby = k4_rs_rows<REP, FB>(sh, p.soft ? p.soft + ib : nullptr, nbrow, nlbyte, sexp, lane, &rp.r, FB ? p.fb + ib : nullptr);
-		const int nbits = k4_unstuff(sh, nby, lane);
+		const int nbits = k4_unstuff<RAW>(sh, nby, lane, marks);
 		const int nb = nbits >> 3;	/* whole un-stuffed bytes */
 		int c0, c1;	/* of them, the lane's */
 		const int per = k4_lane_span(nb, lane, &c0, &c1);
-		const int m1 = k4_flag_hunt(sh, c0, c1, lane);
+		const int m1 = k4_flag_hunt<RAW>(sh, c0, c1, lane, marks);
 		if (REP && lane == 0) {
 			rp.r.stuffed = (uint16_t)(8 * nby - nbits);
 			rp.r.nbytes = (uint16_t)nb;
@@ -1059,7 +1101,7 @@ __device__ __forceinline__ void k4_frames_body(const K4Params &p)
 			K4_SYNC();
 			continue;
 		}
-		const unsigned counts = k4_fcs_scan<REP, ALL>(sh, m1, per, c0, c1, lane);
+		const unsigned counts = k4_fcs_scan<REP, ALL, RAW>(sh, m1, per, c0, c1, lane, marks);
 		if (REP && lane == 0) {
 			const unsigned cand = counts & 0xffffu, too_short = counts >> 16, frames = (unsigned)sh.nfr;	/* (nfr: before k4_sort_candidates caps it) */
 			rp.r.cand = (uint16_t)cand;
@@ -1142,6 +1184,11 @@ __global__ void k4_frames_all(K4Params p);
 __global__ void k4_frames_all_rep(K4Params p);
 __global__ void k4_frames_all_fb(K4Params p);
 __global__ void k4_frames_all_rep_fb(K4Params p);
+/* VDL2GPU_F_RAW_FLAGS and VDL2GPU_BLK_RAW_FLAGS: those four with RAW, defined in vdl2gpu_rawflags.hip for the same reason */
+__global__ void k4_frames_raw(K4Params p);
+__global__ void k4_frames_raw_rep(K4Params p);
+__global__ void k4_frames_raw_fb(K4Params p);
+__global__ void k4_frames_raw_rep_fb(K4Params p);
 #endif	/* VDL2GPU_BLOCKS_DEVICE_ONLY */
 
 #endif

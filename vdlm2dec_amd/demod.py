@@ -147,7 +147,8 @@ class Receiver:
                  max_bursts: int = 0, keep_dec: bool = False, serial: bool = False, full_scan: bool = False,
                  frames: bool = False, rtl_quirk: bool = False, flags: int = 0, testhooks: bool = False,
                  levels: bool = False, soft_rs: bool = False, exact_fo: bool = False, carrier: bool = False,
-                 block_report: bool = False, feedback: bool = False, all_frames: bool = False):
+                 block_report: bool = False, feedback: bool = False, all_frames: bool = False, raw_flags: bool = False):
+        # raw_flags: VDL2GPU_F_RAW_FLAGS (needs all_frames=True), a stuffed data byte 0x7e is told from a flag, so frames that hold one arrive
         # all_frames: VDL2GPU_F_ALL_FRAMES (needs frames=True), the block path hands on every frame of a burst, not only the first
         # feedback: VDL2GPU_F_FEEDBACK, every burst's rows sliced a second time with decision feedback (Burst.fb); with frames=True the
         # block path takes a row the reference cannot decode from them
@@ -155,6 +156,8 @@ class Receiver:
         # carrier: VDL2GPU_F_CARRIER, every burst's carrier offset and phase-error spread (Burst.carrier)
         # exact_fo: VDL2GPU_F_EXACT_FO, channel offsets off the 25 kHz grid with a phase-continuous oscillator (include/vdl2gpu.h)
         # testhooks: load libvdl2gpu_test.so, the build that honours F_TEST_NOREGION / VDL2GPU_PRIM_DROP / VDL2GPU_SPLIT_SAMPLES
+        if raw_flags and not all_frames:
+            raise ValueError("raw_flags=True needs all_frames=True")
         self.L = _lib.load(testhooks=testhooks or bool(flags & _lib.F_TEST_NOREGION))
         if channels and isinstance(channels[0], ThreadParam):
             channels = [list(channels)]
@@ -182,12 +185,14 @@ class Receiver:
         cfg.max_bursts = max_bursts
         asked = dict(levels=levels, soft_rs=soft_rs, carrier=carrier, block_report=block_report, feedback=feedback)
         switches = [(keep_dec, _lib.F_KEEP_DEC), (serial, _lib.F_SERIAL), (full_scan, _lib.F_FULLSCAN), (frames, _lib.F_FRAMES),
-                    (rtl_quirk, _lib.F_RTL_QUIRK), (exact_fo, _lib.F_EXACT_FO), (all_frames, _lib.F_ALL_FRAMES)] + [(asked[kw], flag) for kw, flag, _, _ in _COLUMNS]
+                    (rtl_quirk, _lib.F_RTL_QUIRK), (exact_fo, _lib.F_EXACT_FO), (all_frames, _lib.F_ALL_FRAMES),
+                    (raw_flags, _lib.F_RAW_FLAGS)] + [(asked[kw], flag) for kw, flag, _, _ in _COLUMNS]
         cfg.flags = flags | sum(flag for on, flag in switches if on)     # (one bit each)
         self.max_push = max_push
         for kw, flag, _, _ in _COLUMNS:     # self.levels, .soft_rs, .carrier, .block_report, .feedback: by keyword or by `flags`
             setattr(self, kw, bool(cfg.flags & flag))
         self.all_frames = bool(cfg.flags & _lib.F_ALL_FRAMES)
+        self.raw_flags = bool(cfg.flags & _lib.F_RAW_FLAGS)
         self.h = C.c_void_p()
         rc = self.L.vdl2gpu_create(C.byref(cfg), C.byref(self.h))
         if rc != 0:
@@ -307,7 +312,8 @@ class Receiver:
         return out
 
     # ------------------------------------------------------------------ block path
-    def decode_blocks(self, blocks: Sequence, max_frames: int = 0, soft=None, report: bool = False, fb=None, all_frames: bool = False):
+    def decode_blocks(self, blocks: Sequence, max_frames: int = 0, soft=None, report: bool = False, fb=None, all_frames: bool = False,
+                      raw_flags: bool = False):
         """blk_thread for a batch (vdlm2.c:84-161): (index of the block, hdata) of every frame the
         reference would pass to out().  ``blocks``: Burst objects or (nbrow, nlbyte, data) tuples.
         ``soft``: one (8, 255) uint8 reliability map per block (Burst.soft): the soft row rule of include/vdl2gpu.h
@@ -316,7 +322,10 @@ class Receiver:
         ``fb``: one (8, 255) uint8 array of decision-feedback rows per block (Burst.fb): a row the reference cannot decode is taken from
         them if it decodes there (vdl2gpu_decode_blocks_feedback), on any handle; None: not.
         ``all_frames``: every frame of a burst, by the rule of VDL2GPU_F_ALL_FRAMES (vdl2gpu_decode_blocks_ex with
-        VDL2GPU_BLK_ALL_FRAMES), on any handle; the frames of a block come in stream order."""
+        VDL2GPU_BLK_ALL_FRAMES), on any handle; the frames of a block come in stream order.
+        ``raw_flags`` (with ``all_frames``): the rule of VDL2GPU_F_RAW_FLAGS, a stuffed data byte 0x7e is no flag (VDL2GPU_BLK_RAW_FLAGS)."""
+        if raw_flags and not all_frames:
+            raise ValueError("raw_flags=True needs all_frames=True")
         n = len(blocks)
         if n == 0:
             return ([], []) if report else []
@@ -350,7 +359,8 @@ class Receiver:
         # (soft NULL: hard mode; rep NULL: exactly vdl2gpu_decode_blocks_soft, and with both exactly vdl2gpu_decode_blocks; fb NULL: the
         # library's vdl2gpu_decode_blocks_report, which the older calls go through as well)
         if all_frames:
-            nf = self._check(self.L.vdl2gpu_decode_blocks_ex(self.h, arr, sarr, farr, n, out, cap, C.byref(dropped), rarr, _lib.BLK_ALL_FRAMES))
+            nf = self._check(self.L.vdl2gpu_decode_blocks_ex(self.h, arr, sarr, farr, n, out, cap, C.byref(dropped), rarr,
+                                                             _lib.BLK_ALL_FRAMES | (_lib.BLK_RAW_FLAGS if raw_flags else 0)))
         elif farr is None:
             nf = self._check(self.L.vdl2gpu_decode_blocks_report(self.h, arr, sarr, n, out, cap, C.byref(dropped), rarr))
         else:

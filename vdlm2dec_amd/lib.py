@@ -34,6 +34,8 @@ ROW_FEEDBACK = 6    # (VDL2GPU_F_FEEDBACK) the record's decision-feedback row re
 F_FEEDBACK = 4096
 F_ALL_FRAMES = 8192     # (VDL2GPU_F_ALL_FRAMES, needs F_FRAMES) the block path hands on every frame of a burst
 BLK_ALL_FRAMES = 1      # vdl2gpu_decode_blocks_ex's mode word (VDL2GPU_BLK_*)
+F_RAW_FLAGS = 16384     # (VDL2GPU_F_RAW_FLAGS, needs F_ALL_FRAMES) a flag is six adjacent ones of the stuffed stream: a data byte 0x7e is data
+BLK_RAW_FLAGS = 4       # ... in the mode word, beside BLK_ALL_FRAMES
 # status of a cluster head (vdl2gpu_debug_clheads()'s packed word: cl_pack() in csrc/vdl2gpu_types.h)
 CL_STEADY, CL_DEFER_FIRST, CL_NONSTEADY = 0, 1, 2
 
