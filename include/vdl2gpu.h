@@ -468,6 +468,73 @@ typedef struct {
 #define VDL2GPU_F_RAW_FLAGS 16384u
 #define VDL2GPU_HAVE_RAW_FLAGS 1
 
+/* ---- symbol timing, clock drift and fine arrival time (VDL2GPU_F_SYMCLK; announced by VDL2GPU_HAVE_SYMCLK, the ABI version is unchanged) ----
+ * A burst record says when the burst arrived as trig_dec and the one-shot sub-phase of the 16 sync symbols: a quarter of an 84 kS/s
+ * sample, 3 us.  It says nothing of how fast the transmitter's symbol clock runs against the receiver's sample clock (VDL2 allows
+ * +-50 ppm, an uncorrected receiver adds 30 .. 100).  With VDL2GPU_F_SYMCLK the GPU measures both over the whole burst with the
+ * square-law (Oerder-Meyr) timing estimator at the plane's 8 samples per symbol.  It is not decision-directed and always uses
+ * sub-phase 0: the result does not depend on clk0, on the slicer or on any other flag, and nothing else changes with the flag.
+ * Notation as at vdl2gpu_level_t: S(n, c) the channel-filtered value at stream time n, sub-phase c.  For an accepted burst with header
+ * values nbrow, nlbyte and last symbol end_dec:
+ *   nsym            as at vdl2gpu_level_t (the byte schedule of d8psk.c:117-206: (25 + 8 (ND + NF) + 2) / 3 with ND, NF as at
+ *                   vdl2gpu_carrier_t), sym_first_dec = end_dec - 8 (nsym - 1), n_k = sym_first_dec + 8 k for k = 0 .. nsym - 1
+ *   segments        segment s holds the symbols k in [256 s, min(nsym, 256 s + 256)); nseg = ceil(nsym / 256), at most
+ *                   VDL2GPU_SYMCLK_SEGS = 22 (the longest burst has 5449 symbols)
+ *   sums            e[s][d] = sum over the segment's k of |S(n_k - d, 0)|^2, d = 0 .. 7, in float; e[s][] = 0 for s >= nseg.
+ *                   S is formed in float with the taps in ascending order (j = 0 .. 16, real and imaginary part each a chain of
+ *                   multiply, then add: no fused operation), |S|^2 = re * re + im * im.
+ *                   The oldest sample touched is sym_first_dec - 23, the newest end_dec: inside what the sync detector and the
+ *                   payload decode of the burst have read, never past end_dec -- the result cannot depend on where the stream was cut.
+ *   order           of the sum over k: value v[l] of symbol k = 256 s + l for l = 0 .. 255, 0.0f where k >= nsym; four groups of 64
+ *                   (l / 64); in each group the xor butterfly v[l] += v[l ^ 32], then ^ 16, 8, 4, 2, 1 (every l of the group ends
+ *                   with the same sum); e[s][d] = ((g0 + g1) + g2) + g3.  A burst therefore gets bit-identical sums whatever
+ *                   kernel, path or repair round decoded it and however the stream was cut into pushes.
+ * The host derives the rest in double precision (vdl2gpu_symclk_from_sums is that arithmetic, and what the library itself calls):
+ *   z_s       = sum_d e[s][d] * exp(+2 pi i d / 8)
+ *   tau_s     = -(4 / pi) * arg z_s (atan2; + 8 where that gives -4 or less), in 84 kS/s samples, in (-4, 4].  Positive: the symbol
+ *               centres lie LATER than the grid n_k.  For s >= 1 tau_s is then unwrapped: 8 is added or subtracted until
+ *               tau_s - tau_{s-1} lies in (-4, 4]
+ *   line      weighted least squares tau(k) = tau0 + slope * k through the points (c_s, tau_s), c_s = 256 s + (m_s - 1) / 2 the centre
+ *               symbol index and the weight m_s the symbol count of segment s
+ *   tau0      the line at k = 0;  clock_ppm = -slope / 8 * 1e6: POSITIVE when the transmitter's symbols come FASTER than 10 500 a
+ *               second as counted by the receiver's sample clock;  tau_rms = sqrt(sum m_s r_s^2 / sum m_s), r_s the segments'
+ *               residuals about the line.  With nseg == 1: tau0 = tau_0, clock_ppm and tau_rms are NaN
+ *   toa_sample = (sym_first_dec + tau0 - D + 0.5) * sdrinrate / 84000 - 0.5 (tau0 before it is narrowed to float): the time, in INPUT
+ *               samples of the stream, of the centre of symbol k = 0 -- the first symbol behind the 17 of the unique word (reference
+ *               symbol + 16), symbol 21 counted from a transmitter's first ramp symbol with 4 ramp symbols.
+ *               D = sum_j (16 - j) mflt[4 j] / sum_j mflt[4 j] (j = 0 .. 16) is the centroid delay of the sub-phase-0 taps; mflt is not
+ *               symmetric, D is 8.2509, not 8.  The linear map is the mean of the dump schedule (d8psk.c:374-381: output m averages
+ *               the inputs [m M, (m + 1) M), M = sdrinrate / 84000, so its centre is input (m + 0.5) M - 0.5).  With VDL2GPU_F_RTL_QUIRK
+ *               the map to input samples does NOT hold (every block of 32768 is shifted by one and loses a sample): toa_sample is then
+ *               a time in the quirk's own sample count.
+ * Accuracy, measured with these formulas in float64 on the CPU model's planes against a synthetic transmitter's truth (cs16 at 2 and
+ * 10 MS/s, cu8 at 2 MS/s; 24 bursts of 123 .. 4561 symbols at a random fraction of a symbol; noise 1.7; symbol clock 0, +50, -30 ppm;
+ * scripts/symclk_accuracy.py, profiles/r24_symclk_accuracy.txt):
+ *   toa_sample  within 0.527 us of the true centre of symbol k = 0.  The error is not centred: mean -0.222 us (a sixtieth of an 84 kS/s
+ *               sample; -0.29 / -0.12 / -0.25 us for the three inputs) against a standard deviation of 0.07 .. 0.14 us, with D derived as
+ *               above, not fitted -- stated, not absorbed.  Stations that compare arrival times of one burst share the offset
+ *   clock_ppm   within 0.319 ppm with nseg >= 10, within 1.386 ppm with 3 <= nseg < 10; with nseg == 2 the line goes through its two
+ *               points (tau_rms is 0) and the error reaches 19 ppm; with nseg == 1 there is none
+ * The GPU's plane is that model's bit for bit and its sums agree with float64 to 1e-5, so it inherits these errors; the tests bound it
+ * by twice the worst of that table (other seeds): 1.054 us, 0.638 ppm, 2.772 ppm.
+ * Memory: 744 bytes per record slot wherever a level record has 40 -- each device output ring, each host slab, and the host queue
+ * beside every burst record it holds. */
+#define VDL2GPU_F_SYMCLK 32768u
+#define VDL2GPU_HAVE_SYMCLK 1
+#define VDL2GPU_SYMCLK_SEG 256		/* symbols per segment */
+#define VDL2GPU_SYMCLK_SEGS 22		/* ceil(5449 / 256): covers a burst of VDL2GPU_MAXROWS rows */
+typedef struct {
+	int64_t sym_first_dec;	/* @0  stream time (84 kS/s) of the first symbol evaluation, n_0 */
+	int32_t nsym;		/* @8  symbols of the burst */
+	int32_t nseg;		/* @12 segments used, ceil(nsym / 256) */
+	double toa_sample;	/* @16 input-sample time of the centre of symbol k = 0 */
+	float tau0;		/* @24 the fitted line at k = 0, 84 kS/s samples */
+	float clock_ppm;	/* @28 symbol clock against the sample clock; NaN with nseg == 1 */
+	float tau_rms;		/* @32 weighted rms residual of the segments about the line; NaN with nseg == 1 */
+	int32_t reserved;	/* @36 0 */
+	float e[VDL2GPU_SYMCLK_SEGS][8];	/* @40 the sums; 40 + 22 * 32 = 744 is a multiple of 8: no padding */
+} vdl2gpu_symclk_t;		/* sizeof 744, alignment 8 */
+
 typedef struct {
 	uint64_t samples_in;	/* per stream */
 	uint64_t dec_samples;	/* 84 kS/s samples produced per channel */
@@ -595,6 +662,13 @@ int vdl2gpu_poll_feedback(vdl2gpu_t *h, vdl2gpu_burst_t *out, vdl2gpu_level_t *l
 			  vdl2gpu_fb_t *fb, int max);
 int vdl2gpu_poll_feedback_ready(vdl2gpu_t *h, vdl2gpu_burst_t *out, vdl2gpu_level_t *lv, vdl2gpu_soft_t *soft, vdl2gpu_carrier_t *car, vdl2gpu_blockrep_t *rep,
 				vdl2gpu_fb_t *fb, int max);
+/* ... and with the bursts' symbol-clock records: clk[i] belongs to out[i] (VDL2GPU_F_SYMCLK).  Same queue, order, waiting and threading
+ * as the other collectors; each of lv, soft, car, rep, fb and clk may be NULL (clk == NULL: exactly vdl2gpu_poll_feedback).  clk != NULL
+ * on a handle created without VDL2GPU_F_SYMCLK: VDL2GPU_EINVAL, and nothing is consumed; the others as above. */
+int vdl2gpu_poll_symclk(vdl2gpu_t *h, vdl2gpu_burst_t *out, vdl2gpu_level_t *lv, vdl2gpu_soft_t *soft, vdl2gpu_carrier_t *car, vdl2gpu_blockrep_t *rep,
+			vdl2gpu_fb_t *fb, vdl2gpu_symclk_t *clk, int max);
+int vdl2gpu_poll_symclk_ready(vdl2gpu_t *h, vdl2gpu_burst_t *out, vdl2gpu_level_t *lv, vdl2gpu_soft_t *soft, vdl2gpu_carrier_t *car, vdl2gpu_blockrep_t *rep,
+			      vdl2gpu_fb_t *fb, vdl2gpu_symclk_t *clk, int max);
 /* Number of bursts a poll would currently return (implies vdl2gpu_sync). */
 int vdl2gpu_pending(vdl2gpu_t *h);
 /* Pushes the GPU has not finished yet (0..3); never waits.  For a producer that is not bound to real time and wants to
@@ -712,6 +786,12 @@ int64_t vdl2gpu_exact_fo_index(uint64_t a, uint64_t e, unsigned sdrinrate, int f
  * (what the library's collector calls for every record).  df, Fr: the burst record's.  Fills all of *out (reserved = 0).
  * VDL2GPU_EINVAL for nsym <= 0, Fr == 0 or out == NULL. */
 int vdl2gpu_carrier_from_sums(float df, int Fr, int nsym, int sum_e, unsigned sum_e2, vdl2gpu_carrier_t *out);
+/* VDL2GPU_F_SYMCLK: the derived values of a symbol-clock record from its sums, the formulas at vdl2gpu_symclk_t in double precision
+ * (what the library's collector calls for every record).  e: the sums of the first ceil(nsym / 256) segments, 8 floats each (it may be
+ * out->e itself).  Fills all of *out: the two integers as given, nseg, the derived fields, reserved = 0, e copied and zero from segment
+ * nseg on.  tau_s: if not NULL, room for VDL2GPU_SYMCLK_SEGS doubles; the first nseg receive the segments' unwrapped tau_s.
+ * VDL2GPU_EINVAL for nsym <= 0 or above 256 * VDL2GPU_SYMCLK_SEGS, sdrinrate == 0, e == NULL or out == NULL. */
+int vdl2gpu_symclk_from_sums(int64_t sym_first_dec, int nsym, const float *e, unsigned sdrinrate, vdl2gpu_symclk_t *out, double *tau_s);
 /* Frequency planning: the tuner centre the reference picks for a list of channel
  * frequencies, and the per-channel mixer offsets Fo it derives (thread_param_t.Fo).
  *   rtl: chooseFc() of rtl.c:123-160 -- the highest Fc (1 Hz steps, downwards from max + 50 kHz) that keeps every

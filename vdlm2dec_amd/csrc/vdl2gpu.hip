@@ -16,6 +16,7 @@
  */
 #include "vdl2gpu_kernels.h"
 #include "vdl2gpu_blocks.h"
+#include "vdl2gpu_symclk.h"
 
 #include <algorithm>
 #include <cerrno>
@@ -94,14 +95,16 @@ struct LaterEvent {
 
 /* A burst record has side columns: entries at the record's index in the device rings, the slabs and the host queue, present when
  * the handle's flags ask for them.  A column is a name in the enum and a row of each of the two tables here. */
-enum { COL_LEVEL, COL_SOFT, COL_CARRIER, COL_REPORT, COL_FB, VDL2_NCOL };	/* (the order of the collectors' arguments: poll_impl) */
-static const size_t col_bytes[VDL2_NCOL] = { sizeof(vdl2gpu_level_t), sizeof(vdl2gpu_soft_t), sizeof(vdl2gpu_carrier_t), sizeof(vdl2gpu_blockrep_t), sizeof(vdl2gpu_fb_t) };
+enum { COL_LEVEL, COL_SOFT, COL_CARRIER, COL_REPORT, COL_FB, COL_SYMCLK, VDL2_NCOL };	/* (the order of the collectors' arguments: poll_impl) */
+static const size_t col_bytes[VDL2_NCOL] = { sizeof(vdl2gpu_level_t), sizeof(vdl2gpu_soft_t), sizeof(vdl2gpu_carrier_t), sizeof(vdl2gpu_blockrep_t), sizeof(vdl2gpu_fb_t),
+					      sizeof(vdl2gpu_symclk_t) };
 static const struct { unsigned flag; const char *flag_name, *arg; } col_info[VDL2_NCOL] = {	/* arg: what the collectors' error texts call the column */
 	{ VDL2GPU_F_LEVELS, "VDL2GPU_F_LEVELS", "lv" },			/* a level record */
 	{ VDL2GPU_F_SOFT_RS, "VDL2GPU_F_SOFT_RS", "soft" },		/* a reliability map (2048 bytes) */
 	{ VDL2GPU_F_CARRIER, "VDL2GPU_F_CARRIER", "car" },		/* a carrier record */
 	{ VDL2GPU_F_BLOCK_REPORT, "VDL2GPU_F_BLOCK_REPORT", "rep" },	/* a block report (vdl2gpu_create: only with VDL2GPU_F_FRAMES) */
 	{ VDL2GPU_F_FEEDBACK, "VDL2GPU_F_FEEDBACK", "fb" },		/* decision-feedback rows (2048 bytes; with or without VDL2GPU_F_FRAMES) */
+	{ VDL2GPU_F_SYMCLK, "VDL2GPU_F_SYMCLK", "clk" },		/* a symbol-clock record (744 bytes) */
 };
 
 /* A table set (push % VDL2_NSET): what a push's demodulator kernels work in, see alloc_sets. */
@@ -1797,6 +1800,26 @@ static int enqueue_back(vdl2gpu_t *h)
 		HIPCHK(h, hipGetLastError());
 	}
 	TRY(mark(h, pt, E_BLOCKS_END, ts));
+	if (h->col_on[COL_SYMCLK]) {
+		/* VDL2GPU_F_SYMCLK: the timing sums of every record of the push's ring, behind the last payload pass -- the records are final --
+		 * and on the tail's stream, where the second payload pass has just read the same planes: the set is the push's own until
+		 * k2_done below.  Record-driven: whichever kernel, pass or round made a record, this is the one place that measures it. */
+		KSymclkParams kc{};
+		kc.dec = k2.dec;
+		kc.cap = k2.cap;
+		kc.dec_base = k2.dec_base;
+		kc.frames = std::min<long long>(VDL2_CARRY_FRAMES + J, k2.cap);
+		kc.cfg = h->d_cfg;
+		kc.nbch = h->C;
+		kc.nstreams = h->S;
+		kc.recs = h->ring[ring].d_recs;
+		kc.count = &h->d_outc->ring[ring].records;
+		kc.rec_cap = h->rec_cap;
+		kc.out = h->ring[ring].col<vdl2gpu_symclk_t>(COL_SYMCLK);
+		symclk_taps(kc.taps);
+		hipLaunchKernelGGL(k_symclk_sums, dim3(VDL2GPU_SYMCLK_SEGS, std::min(h->rec_cap, 2u * (unsigned)h->n_cu)), dim3(KSC_NT), 0, ts, kc);
+		HIPCHK(h, hipGetLastError());
+	}
 	{
 		/* the push's records go to the host by the GPU's own hand: page-locked memory, coalesced 8-byte stores */
 		KExportParams ke{};
@@ -1819,6 +1842,11 @@ static int enqueue_back(vdl2gpu_t *h)
 		if (h->col_on[COL_FB]) {	/* the feedback rows beside them: a kernel of its own, k_export_records keeps its registers */
 			hipLaunchKernelGGL(k_export_feedback, dim3((unsigned)h->n_cu), dim3(256), 0, ts, ke.count, ke.cap,
 					   rg.col<const vdl2gpu_fb_t>(COL_FB), sl.col<vdl2gpu_fb_t>(COL_FB));
+			HIPCHK(h, hipGetLastError());
+		}
+		if (h->col_on[COL_SYMCLK]) {	/* ... and the symbol-clock records, likewise */
+			hipLaunchKernelGGL(k_export_symclk, dim3((unsigned)h->n_cu), dim3(256), 0, ts, ke.count, ke.cap,
+					   rg.col<const vdl2gpu_symclk_t>(COL_SYMCLK), sl.col<vdl2gpu_symclk_t>(COL_SYMCLK));
 			HIPCHK(h, hipGetLastError());
 		}
 		TRY(mark(h, pt, E_EXPORT_END, ts, true));
@@ -2562,6 +2590,13 @@ static int collect_records(vdl2gpu_t *h, int ring, unsigned n)
 			if (vdl2gpu_carrier_from_sums(b.df, b.Fr, c.nsym, c.sum_e, c.sum_e2, &c) == VDL2GPU_OK)	/* (a channel with Fr == 0: the sums alone) */
 				memcpy(at, &c, sizeof c);
 		}
+		if (h->col_on[COL_SYMCLK]) {
+			uint8_t *at = slot_of(h, handle).side[COL_SYMCLK];
+			vdl2gpu_symclk_t c;
+			memcpy(&c, at, sizeof c);
+			if (vdl2gpu_symclk_from_sums(c.sym_first_dec, c.nsym, &c.e[0][0], h->cfg.sdrinrate, &c, nullptr) == VDL2GPU_OK)	/* (a record that is none: zeros) */
+				memcpy(at, &c, sizeof c);
+		}
 		h->ready_idx.push_back(handle);
 	};
 	Slab &sl = h->slab[rg.slab];
@@ -2969,7 +3004,7 @@ extern "C" int vdl2gpu_inflight(vdl2gpu_t *h)
 	return n;
 }
 
-/* The twelve collectors.  side.p[k]: where the caller wants column k beside the records (nullptr: not).  who: the entry point as the
+/* The fourteen collectors.  side.p[k]: where the caller wants column k beside the records (nullptr: not).  who: the entry point as the
  * error texts name it.  When the handle was made without a column that is asked for, the first such column in the order of the
  * arguments is named: "who: arg needs FLAG" (named = false, the two collectors with one column: "who needs FLAG"). */
 struct PollCols {
@@ -3006,6 +3041,9 @@ extern "C" int vdl2gpu_poll_report(vdl2gpu_t *h, vdl2gpu_burst_t *out, vdl2gpu_l
 extern "C" int vdl2gpu_poll_report_ready(vdl2gpu_t *h, vdl2gpu_burst_t *out, vdl2gpu_level_t *lv, vdl2gpu_soft_t *soft, vdl2gpu_carrier_t *car, vdl2gpu_blockrep_t *rep, int max) { return poll_impl(h, out, max, {{lv, soft, car, rep}}, false, "vdl2gpu_poll_report"); }
 extern "C" int vdl2gpu_poll_feedback(vdl2gpu_t *h, vdl2gpu_burst_t *out, vdl2gpu_level_t *lv, vdl2gpu_soft_t *soft, vdl2gpu_carrier_t *car, vdl2gpu_blockrep_t *rep, vdl2gpu_fb_t *fb, int max) { return poll_impl(h, out, max, {{lv, soft, car, rep, fb}}, true, "vdl2gpu_poll_feedback"); }
 extern "C" int vdl2gpu_poll_feedback_ready(vdl2gpu_t *h, vdl2gpu_burst_t *out, vdl2gpu_level_t *lv, vdl2gpu_soft_t *soft, vdl2gpu_carrier_t *car, vdl2gpu_blockrep_t *rep, vdl2gpu_fb_t *fb, int max) { return poll_impl(h, out, max, {{lv, soft, car, rep, fb}}, false, "vdl2gpu_poll_feedback"); }
+
+extern "C" int vdl2gpu_poll_symclk(vdl2gpu_t *h, vdl2gpu_burst_t *out, vdl2gpu_level_t *lv, vdl2gpu_soft_t *soft, vdl2gpu_carrier_t *car, vdl2gpu_blockrep_t *rep, vdl2gpu_fb_t *fb, vdl2gpu_symclk_t *clk, int max) { return poll_impl(h, out, max, {{lv, soft, car, rep, fb, clk}}, true, "vdl2gpu_poll_symclk"); }
+extern "C" int vdl2gpu_poll_symclk_ready(vdl2gpu_t *h, vdl2gpu_burst_t *out, vdl2gpu_level_t *lv, vdl2gpu_soft_t *soft, vdl2gpu_carrier_t *car, vdl2gpu_blockrep_t *rep, vdl2gpu_fb_t *fb, vdl2gpu_symclk_t *clk, int max) { return poll_impl(h, out, max, {{lv, soft, car, rep, fb, clk}}, false, "vdl2gpu_poll_symclk"); }
 
 /* VDL2GPU_F_CARRIER: the derived values of a carrier record (include/vdl2gpu.h, vdl2gpu_carrier_t) -- the one statement of that
  * arithmetic: collect_records calls it for every record. */

@@ -87,6 +87,45 @@ class BlockReport:
                    v.stuffed, v.nbytes, v.flag_at, v.cand, v.too_short, v.bad_fcs, v.frames, v.status)
 
 
+@dataclass(frozen=True)
+class SymClock:
+    """vdl2gpu_symclk_t: the burst's symbol timing, clock drift and fine arrival time (Receiver(symclk=True); definitions in
+    include/vdl2gpu.h)."""
+    sym_first_dec: int
+    nsym: int
+    nseg: int
+    toa_sample: float          # input-sample time of the centre of the first symbol behind the unique word
+    tau0: float                # 84 kS/s samples; positive: the symbol centres lie later than the grid sym_first_dec + 8 k
+    clock_ppm: float           # positive: the transmitter's symbols come faster than 10 500 a second; NaN with nseg == 1
+    tau_rms: float             # NaN with nseg == 1
+    e: np.ndarray              # float32 (22, 8): the sums, zero from segment nseg on
+    tau_s: Tuple[float, ...]   # the nseg segments' unwrapped timing, derived from e as the library derives it
+
+    @classmethod
+    def from_c(cls, v, sdrinrate: int) -> "SymClock":
+        e = np.frombuffer(bytes(v.e), np.float32).reshape(_lib.SYMCLK_SEGS, 8).copy()
+        tau = ()
+        if v.nsym > 0:
+            tau = symclk_from_sums(v.sym_first_dec, v.nsym, e, sdrinrate).tau_s
+        return cls(v.sym_first_dec, v.nsym, v.nseg, v.toa_sample, v.tau0, v.clock_ppm, v.tau_rms, e, tau)
+
+
+def symclk_from_sums(sym_first_dec: int, nsym: int, e, sdrinrate: int) -> SymClock:
+    """vdl2gpu_symclk_from_sums: the derived values of a symbol-clock record, as the library computes them (no GPU needed).
+    e: the sums of at least the first ceil(nsym / 256) segments, (segments, 8)."""
+    nseg = (nsym + _lib.SYMCLK_SEG - 1) // _lib.SYMCLK_SEG
+    ee = np.ascontiguousarray(np.asarray(e, np.float32).reshape(-1, 8)[:max(nseg, 0)])
+    if nsym > 0 and ee.shape[0] < nseg:
+        raise ValueError("e holds fewer segments than nsym needs")
+    c = _lib.SymClkT()
+    tau = (C.c_double * _lib.SYMCLK_SEGS)()
+    rc = _lib.load().vdl2gpu_symclk_from_sums(sym_first_dec, nsym, ee.ctypes.data_as(C.POINTER(C.c_float)), sdrinrate, C.byref(c), tau)
+    if rc < 0:
+        raise _lib.Vdl2GpuError("vdl2gpu_symclk_from_sums failed")
+    return SymClock(c.sym_first_dec, c.nsym, c.nseg, c.toa_sample, c.tau0, c.clock_ppm, c.tau_rms,
+                    np.frombuffer(bytes(c.e), np.float32).reshape(_lib.SYMCLK_SEGS, 8).copy(), tuple(tau[:c.nseg]))
+
+
 def carrier_from_sums(df: float, Fr: int, nsym: int, sum_e: int, sum_e2: int) -> Carrier:
     """vdl2gpu_carrier_from_sums: the derived values of a carrier record, as the library computes them (no GPU needed)."""
     c = _lib.CarrierT()
@@ -116,6 +155,7 @@ class Burst:
     carrier: Optional[Carrier] = None   # Receiver(carrier=True) only; not part of key()
     report: Optional[BlockReport] = None   # Receiver(frames=True, block_report=True) only; not part of key()
     fb: Optional[np.ndarray] = None   # Receiver(feedback=True) only: uint8 (8, 255), the rows sliced with decision feedback; not part of key()
+    clock: Optional[SymClock] = None   # Receiver(symclk=True) only; not part of key()
 
     def key(self):
         return (self.stream, self.chn, self.nbrow, self.nlbyte, self.data)
@@ -133,6 +173,7 @@ _COLUMNS = (
     ("carrier", _lib.F_CARRIER, _lib.CarrierT, Carrier.from_c),
     ("block_report", _lib.F_BLOCK_REPORT, _lib.BlockRepT, BlockReport.from_c),
     ("feedback", _lib.F_FEEDBACK, _lib.FbT, lambda v: _rows(v.data)),
+    ("symclk", _lib.F_SYMCLK, _lib.SymClkT, None),     # (SymClock.from_c wants the receiver's rate: _collect)
 )
 
 
@@ -147,7 +188,9 @@ class Receiver:
                  max_bursts: int = 0, keep_dec: bool = False, serial: bool = False, full_scan: bool = False,
                  frames: bool = False, rtl_quirk: bool = False, flags: int = 0, testhooks: bool = False,
                  levels: bool = False, soft_rs: bool = False, exact_fo: bool = False, carrier: bool = False,
-                 block_report: bool = False, feedback: bool = False, all_frames: bool = False, raw_flags: bool = False):
+                 block_report: bool = False, feedback: bool = False, all_frames: bool = False, raw_flags: bool = False,
+                 symclk: bool = False):
+        # symclk: VDL2GPU_F_SYMCLK, every burst's symbol timing, clock drift and fine arrival time (Burst.clock)
         # raw_flags: VDL2GPU_F_RAW_FLAGS (needs all_frames=True), a stuffed data byte 0x7e is told from a flag, so frames that hold one arrive
         # all_frames: VDL2GPU_F_ALL_FRAMES (needs frames=True), the block path hands on every frame of a burst, not only the first
         # feedback: VDL2GPU_F_FEEDBACK, every burst's rows sliced a second time with decision feedback (Burst.fb); with frames=True the
@@ -183,13 +226,13 @@ class Receiver:
         cfg.max_push = max_push
         cfg.device = device
         cfg.max_bursts = max_bursts
-        asked = dict(levels=levels, soft_rs=soft_rs, carrier=carrier, block_report=block_report, feedback=feedback)
+        asked = dict(levels=levels, soft_rs=soft_rs, carrier=carrier, block_report=block_report, feedback=feedback, symclk=symclk)
         switches = [(keep_dec, _lib.F_KEEP_DEC), (serial, _lib.F_SERIAL), (full_scan, _lib.F_FULLSCAN), (frames, _lib.F_FRAMES),
                     (rtl_quirk, _lib.F_RTL_QUIRK), (exact_fo, _lib.F_EXACT_FO), (all_frames, _lib.F_ALL_FRAMES),
                     (raw_flags, _lib.F_RAW_FLAGS)] + [(asked[kw], flag) for kw, flag, _, _ in _COLUMNS]
         cfg.flags = flags | sum(flag for on, flag in switches if on)     # (one bit each)
         self.max_push = max_push
-        for kw, flag, _, _ in _COLUMNS:     # self.levels, .soft_rs, .carrier, .block_report, .feedback: by keyword or by `flags`
+        for kw, flag, _, _ in _COLUMNS:     # self.levels, .soft_rs, .carrier, .block_report, .feedback, .symclk: by keyword or by `flags`
             setattr(self, kw, bool(cfg.flags & flag))
         self.all_frames = bool(cfg.flags & _lib.F_ALL_FRAMES)
         self.raw_flags = bool(cfg.flags & _lib.F_RAW_FLAGS)
@@ -248,14 +291,15 @@ class Receiver:
         buf = (_lib.BurstT * max_bursts)()
         cols = [(typ * max_bursts)() if getattr(self, kw) else None for kw, _, typ, _ in _COLUMNS]
         # the widest collector serves every handle: a column the handle lacks is None, "not wanted" (include/vdl2gpu.h)
-        fn = self.L.vdl2gpu_poll_feedback_ready if ready else self.L.vdl2gpu_poll_feedback
+        fn = self.L.vdl2gpu_poll_symclk_ready if ready else self.L.vdl2gpu_poll_symclk
         while True:
             n = self._check(fn(self.h, buf, *cols, max_bursts))
             for i in range(n):
                 b = buf[i]
                 out.append(Burst(b.stream, b.chn, b.Fr, b.nbrow, b.nlbyte, b.df, b.ppm, b.trig_dec, b.end_dec,
                                  b.trig_sample, b.end_sample, bytes(b.data),
-                                 *[conv(v[i]) if v is not None else None for v, (_, _, _, conv) in zip(cols, _COLUMNS)]))
+                                 *[None if v is None else (conv(v[i]) if conv else SymClock.from_c(v[i], self.rate))
+                                   for v, (_, _, _, conv) in zip(cols, _COLUMNS)]))
             if n < max_bursts:
                 return out
 
@@ -271,7 +315,7 @@ class Receiver:
         fn = getattr(self.L, name + ("_ready" if ready else ""))
         return self._check(fn(self.h, buf, *cols, max_bursts))
 
-    # vdl2gpu_poll_levels / _soft / _carrier / _report / _feedback (and their _ready forms) into caller-owned arrays: buf a
+    # vdl2gpu_poll_levels / _soft / _carrier / _report / _feedback / _symclk (kv: a (lib.SymClkT * n) or None) (and their _ready forms) into caller-owned arrays: buf a
     # (lib.BurstT * n), lv / sv / cv / rv / fv a (lib.LevelT / SoftT / CarrierT / BlockRepT / FbT * n) or None
     def poll_levels_raw(self, buf, lv, max_bursts: int, ready: bool = False) -> int:
         return self._poll_cols_raw("vdl2gpu_poll_levels", ready, buf, (lv,), max_bursts)
@@ -287,6 +331,9 @@ class Receiver:
 
     def poll_feedback_raw(self, buf, lv, sv, cv, rv, fv, max_bursts: int, ready: bool = False) -> int:
         return self._poll_cols_raw("vdl2gpu_poll_feedback", ready, buf, (lv, sv, cv, rv, fv), max_bursts)
+
+    def poll_symclk_raw(self, buf, lv, sv, cv, rv, fv, kv, max_bursts: int, ready: bool = False) -> int:
+        return self._poll_cols_raw("vdl2gpu_poll_symclk", ready, buf, (lv, sv, cv, rv, fv, kv), max_bursts)
 
     def poll_ready_raw(self, buf, max_bursts: int) -> int:
         """vdl2gpu_poll_ready: bursts of pushes that have already finished; never waits."""

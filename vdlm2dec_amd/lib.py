@@ -36,6 +36,8 @@ F_ALL_FRAMES = 8192     # (VDL2GPU_F_ALL_FRAMES, needs F_FRAMES) the block path 
 BLK_ALL_FRAMES = 1      # vdl2gpu_decode_blocks_ex's mode word (VDL2GPU_BLK_*)
 F_RAW_FLAGS = 16384     # (VDL2GPU_F_RAW_FLAGS, needs F_ALL_FRAMES) a flag is six adjacent ones of the stuffed stream: a data byte 0x7e is data
 BLK_RAW_FLAGS = 4       # ... in the mode word, beside BLK_ALL_FRAMES
+F_SYMCLK = 32768        # (VDL2GPU_F_SYMCLK) every burst's symbol timing, clock drift and fine arrival time (vdl2gpu_symclk_t)
+SYMCLK_SEG, SYMCLK_SEGS = 256, 22      # VDL2GPU_SYMCLK_SEG symbols a segment, VDL2GPU_SYMCLK_SEGS segments a record
 # status of a cluster head (vdl2gpu_debug_clheads()'s packed word: cl_pack() in csrc/vdl2gpu_types.h)
 CL_STEADY, CL_DEFER_FIRST, CL_NONSTEADY = 0, 1, 2
 
@@ -73,9 +75,9 @@ def cl_unpack(packed):
 EXPORTS = (
     "vdl2gpu_abi_version", "vdl2gpu_create", "vdl2gpu_destroy", "vdl2gpu_push", "vdl2gpu_sync",
     "vdl2gpu_ring_init", "vdl2gpu_ring_acquire", "vdl2gpu_ring_commit",
-    "vdl2gpu_poll", "vdl2gpu_poll_ready", "vdl2gpu_poll_levels", "vdl2gpu_poll_levels_ready", "vdl2gpu_poll_soft", "vdl2gpu_poll_soft_ready", "vdl2gpu_poll_carrier", "vdl2gpu_poll_carrier_ready", "vdl2gpu_poll_report", "vdl2gpu_poll_report_ready", "vdl2gpu_poll_feedback", "vdl2gpu_poll_feedback_ready", "vdl2gpu_pending", "vdl2gpu_inflight", "vdl2gpu_get_stats", "vdl2gpu_get_timing", "vdl2gpu_get_host_profile", "vdl2gpu_last_error",
+    "vdl2gpu_poll", "vdl2gpu_poll_ready", "vdl2gpu_poll_levels", "vdl2gpu_poll_levels_ready", "vdl2gpu_poll_soft", "vdl2gpu_poll_soft_ready", "vdl2gpu_poll_carrier", "vdl2gpu_poll_carrier_ready", "vdl2gpu_poll_report", "vdl2gpu_poll_report_ready", "vdl2gpu_poll_feedback", "vdl2gpu_poll_feedback_ready", "vdl2gpu_poll_symclk", "vdl2gpu_poll_symclk_ready", "vdl2gpu_pending", "vdl2gpu_inflight", "vdl2gpu_get_stats", "vdl2gpu_get_timing", "vdl2gpu_get_host_profile", "vdl2gpu_last_error",
     "vdl2gpu_strerror", "vdl2gpu_burst_to_msgblk", "vdl2gpu_decode_blocks", "vdl2gpu_decode_blocks_soft", "vdl2gpu_decode_blocks_report", "vdl2gpu_decode_blocks_feedback", "vdl2gpu_decode_blocks_ex", "vdl2gpu_poll_frames", "vdl2gpu_poll_frames_ready", "reversebits", "vdl2gpu_lo_len", "vdl2gpu_lo_table", "vdl2gpu_plan",
-    "vdl2gpu_exact_fo_tables", "vdl2gpu_exact_fo_index", "vdl2gpu_carrier_from_sums",
+    "vdl2gpu_exact_fo_tables", "vdl2gpu_exact_fo_index", "vdl2gpu_carrier_from_sums", "vdl2gpu_symclk_from_sums",
     "vdl2gpu_choose_fc_rtl", "vdl2gpu_choose_fc_air",
     "vdl2gpu_debug_dec", "vdl2gpu_debug_k1", "vdl2gpu_debug_lo", "vdl2gpu_debug_atan2f", "vdl2gpu_debug_rs", "vdl2gpu_debug_counters", "vdl2gpu_debug_cands", "vdl2gpu_debug_clheads", "vdl2gpu_debug_fail", "vdl2gpu_debug_segs", "vdl2gpu_debug_heads",
 )
@@ -131,6 +133,14 @@ class FbT(C.Structure):
     """vdl2gpu_fb_t (VDL2GPU_F_FEEDBACK): 2048 bytes, the rows of the burst sliced a second time with decision feedback, laid out as the
     record's data[] (include/vdl2gpu.h)."""
     _fields_ = [("data", (C.c_uint8 * 255) * 8), ("reserved", C.c_uint8 * 8)]
+
+
+class SymClkT(C.Structure):
+    """vdl2gpu_symclk_t (VDL2GPU_F_SYMCLK): 744 bytes, the burst's square-law timing sums by segment of 256 symbols and the symbol timing,
+    clock drift and arrival time the host derives from them (include/vdl2gpu.h)."""
+    _fields_ = [("sym_first_dec", C.c_int64), ("nsym", C.c_int32), ("nseg", C.c_int32), ("toa_sample", C.c_double),
+                ("tau0", C.c_float), ("clock_ppm", C.c_float), ("tau_rms", C.c_float), ("reserved", C.c_int32),
+                ("e", (C.c_float * 8) * 22)]
 
 
 class FrameT(C.Structure):
@@ -224,6 +234,13 @@ def load(testhooks: bool = False):
     L.vdl2gpu_poll_feedback.argtypes = [C.c_void_p, C.POINTER(BurstT), C.POINTER(LevelT), C.POINTER(SoftT), C.POINTER(CarrierT), C.POINTER(BlockRepT), C.POINTER(FbT), C.c_int]
     L.vdl2gpu_poll_feedback_ready.restype = C.c_int
     L.vdl2gpu_poll_feedback_ready.argtypes = [C.c_void_p, C.POINTER(BurstT), C.POINTER(LevelT), C.POINTER(SoftT), C.POINTER(CarrierT), C.POINTER(BlockRepT), C.POINTER(FbT), C.c_int]
+    L.vdl2gpu_poll_symclk.restype = C.c_int
+    L.vdl2gpu_poll_symclk.argtypes = [C.c_void_p, C.POINTER(BurstT), C.POINTER(LevelT), C.POINTER(SoftT), C.POINTER(CarrierT), C.POINTER(BlockRepT), C.POINTER(FbT),
+                                      C.POINTER(SymClkT), C.c_int]
+    L.vdl2gpu_poll_symclk_ready.restype = C.c_int
+    L.vdl2gpu_poll_symclk_ready.argtypes = L.vdl2gpu_poll_symclk.argtypes
+    L.vdl2gpu_symclk_from_sums.restype = C.c_int
+    L.vdl2gpu_symclk_from_sums.argtypes = [C.c_int64, C.c_int, C.POINTER(C.c_float), C.c_uint, C.POINTER(SymClkT), C.POINTER(C.c_double)]
     L.vdl2gpu_carrier_from_sums.restype = C.c_int
     L.vdl2gpu_carrier_from_sums.argtypes = [C.c_float, C.c_int, C.c_int, C.c_int, C.c_uint, C.POINTER(CarrierT)]
     L.vdl2gpu_get_stats.restype = C.c_int

@@ -291,12 +291,13 @@ def rc_pulse(t_over_T: np.ndarray, alpha: float = 0.6) -> np.ndarray:
 
 
 def modulate_into(acc: np.ndarray, incr: np.ndarray, rate: float, t0: float, amp: float,
-                  freq_hz: float, real_lo: bool = False) -> None:
+                  freq_hz: float, real_lo: bool = False, sym_ppm: float = 0.0) -> None:
     """Add one burst (complex baseband at ``freq_hz``) into ``acc`` (complex128) in place.
 
-    ``t0`` is the time (s) of symbol 0's pulse centre.  Symbol k sits at t0 + k/10500.
+    ``t0`` is the time (s) of symbol 0's pulse centre.  Symbol k sits at t0 + k T, T = 1 / (10500 (1 + sym_ppm 1e-6)): a symbol
+    clock that runs sym_ppm parts in a million fast (the pulse scales with it); sym_ppm = 0 is T = 1 / 10500 to the bit.
     """
-    T = 1.0 / SYMRATE
+    T = 1.0 / (SYMRATE * (1.0 + sym_ppm * 1e-6))
     phases = np.cumsum(incr) * (np.pi / 4.0)
     a = np.exp(1j * phases)
     nsym = len(a)
@@ -327,6 +328,7 @@ class Burst:
     corrupt: Optional[dict] = None
     raw_payload: Optional[bytes] = None  # bypass AVLC/HDLC: bytes handed straight to burst_bits
     infos: Optional[List[bytes]] = None  # several AVLC frames in this one burst, sharing single flags (`info` is then unused)
+    sym_ppm: float = 0.0  # the transmitter's symbol clock, parts in a million above 10500 symbols a second (VDL2 allows +-50)
 
     def frames(self) -> List[bytes]:
         """the burst's AVLC frames as they stand between the flags, without FCS; frame j of several has its own src address"""
@@ -362,7 +364,7 @@ def synth_complex(spec: StreamSpec) -> np.ndarray:
     acc = np.zeros(spec.nsamples, dtype=np.complex128)
     for b in spec.bursts:
         incr = burst_increments(burst_bits(b.payload(), b.corrupt))
-        modulate_into(acc, incr, float(spec.rate), b.t0, b.amp, spec.fo[b.chan] + b.cfo)
+        modulate_into(acc, incr, float(spec.rate), b.t0, b.amp, spec.fo[b.chan] + b.cfo, sym_ppm=b.sym_ppm)
     if spec.noise > 0:
         acc += spec.noise * (rng.standard_normal(spec.nsamples) + 1j * rng.standard_normal(spec.nsamples))
     return acc
@@ -408,7 +410,7 @@ DEFAULT_FO_8CH = (-450000, -350000, -250000, -150000, -50000, 100000, 200000, 30
 def random_scenario(rate: int, fo: Sequence[int], nsamples: int, seed: int,
                     bursts_per_s: float = 6.0, info_max: int = 300, noise: float = 1.7,
                     amp_range=(8.0, 60.0), cfo_max: float = 400.0,
-                    info_choices: Optional[Sequence[int]] = None, frames_per_burst: int = 1) -> StreamSpec:
+                    info_choices: Optional[Sequence[int]] = None, frames_per_burst: int = 1, sym_ppm: float = 0.0) -> StreamSpec:
     """Poisson-ish non-overlapping bursts per channel.  frames_per_burst > 1: every burst carries so many AVLC
     frames (Burst.infos), the first with the info field a burst of one frame would have had, the others drawn behind it."""
     rng = np.random.default_rng(seed ^ 0x5EED)
@@ -427,6 +429,7 @@ def random_scenario(rate: int, fo: Sequence[int], nsamples: int, seed: int,
             if frames_per_burst > 1:
                 b.infos = [info] + [bytes(rng.integers(0, 256, int(rng.integers(1, len(info) + 1)), dtype=np.uint8).tolist())
                                     for _ in range(frames_per_burst - 1)]
+            b.sym_ppm = sym_ppm
             d = b.duration()
             if t + d + 0.001 > dur:
                 break
@@ -457,18 +460,20 @@ def _cli(argv=None) -> int:
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--frames-per-burst", type=int, default=1, help="AVLC frames in every burst, one flag between two (a receiver needs "
                     "VDL2GPU_F_ALL_FRAMES to see more than the first)")
+    ap.add_argument("--sym-ppm", type=float, default=0.0, help="every burst's symbol clock, parts in a million above 10500 symbols a second "
+                    "(a receiver with VDL2GPU_F_SYMCLK reports it as clock_ppm)")
     ap.add_argument("--truth", help="JSON file: every burst sent (channel, start, AVLC info, the frame out() must see, msgblk rows)")
     a = ap.parse_args(argv)
     ns = (int(a.seconds * a.rate) + 32767) // 32768 * 32768      # whole RTL hand-off blocks (vdlm2.h:35)
     spec = random_scenario(a.rate, a.fo, ns, seed=a.seed, bursts_per_s=a.bursts_per_s, info_max=a.info_max,
-                           noise=a.noise, amp_range=tuple(a.amp), cfo_max=a.cfo, frames_per_burst=a.frames_per_burst)
+                           noise=a.noise, amp_range=tuple(a.amp), cfo_max=a.cfo, frames_per_burst=a.frames_per_burst, sym_ppm=a.sym_ppm)
     synth_stream(spec, a.fmt).tofile(a.out)
     if a.truth:
         tr = []
         for b in sorted(spec.bursts, key=lambda b: b.t0):
             nbrow, nlbyte, rows = received_rows(b.payload())
             tr.append(dict(chan=b.chan, fo=int(a.fo[b.chan]), t0=b.t0, amp=b.amp, cfo=b.cfo, info=b.info.hex(),
-                           payload=b.payload().hex(), nbrow=nbrow, nlbyte=nlbyte, symbols=b.n_symbols(),
+                           payload=b.payload().hex(), nbrow=nbrow, nlbyte=nlbyte, symbols=b.n_symbols(), sym_ppm=b.sym_ppm,
                            **({} if b.infos is None else dict(infos=[i.hex() for i in b.infos]))))
         json.dump(dict(rate=a.rate, fmt=a.fmt, fo=list(a.fo), nsamples=ns, noise=a.noise, seed=a.seed, bursts=tr), open(a.truth, "w"))
     print(f"{a.out}: {ns} samples @ {a.rate} S/s {a.fmt}, {len(a.fo)} channels, {len(spec.bursts)} bursts")
