@@ -84,6 +84,8 @@ static long long g_last_ns;	/* when the previous hand-off came */
 #ifdef VDL2GPU_FRAMES
 static uint32_t g_blk_mode;	/* VDL2GPU_RCV_ALL_FRAMES is set: deliver() asks for every frame of a burst (VDL2GPU_BLK_ALL_FRAMES);
 				 * VDL2GPU_RCV_RAW_FLAGS: that, with VDL2GPU_BLK_RAW_FLAGS beside it */
+static int g_tracked;		/* VDL2GPU_RCV_TRACKED is set: the handle has VDL2GPU_F_TRACKED and deliver() hands the bursts' timing-tracked rows to
+				 * vdl2gpu_decode_blocks_tracked, which makes a second attempt for a burst that gave no frame */
 #endif
 static int g_null;		/* VDL2GPU_RCV_NULL=1: keep the barrier protocol, do nothing else (measures what the protocol alone allows) */
 static char *g_slot;		/* the slot being filled, or NULL */
@@ -106,13 +108,18 @@ static void deliver(vdl2gpu_t *h, int wait)
 {
 	static vdl2gpu_burst_t b[64];
 	static vdl2gpu_frame_t f[128];
+	static vdl2gpu_trk_t t[64];	/* (VDL2GPU_RCV_TRACKED) */
 	static msgblk_t blk;	/* what out() reads of it: chn, Fr, tv, ppm, nbrow, nlbyte */
 	int n, nf, i, dropped = 0;
-	while ((n = wait ? vdl2gpu_poll(h, b, 64) : vdl2gpu_poll_ready(h, b, 64)) > 0) {
+	while ((n = g_tracked ? (wait ? vdl2gpu_poll_tracked(h, b, NULL, NULL, NULL, NULL, NULL, NULL, t, 64)
+				      : vdl2gpu_poll_tracked_ready(h, b, NULL, NULL, NULL, NULL, NULL, NULL, t, 64))
+			      : (wait ? vdl2gpu_poll(h, b, 64) : vdl2gpu_poll_ready(h, b, 64))) > 0) {
 		/* VDL2GPU_RCV_ALL_FRAMES: every frame of a burst goes to out(), in (block, seq) order -- the reference's check_frame() can
 		 * only pass the first (include/vdl2gpu.h, VDL2GPU_F_ALL_FRAMES).  VDL2GPU_RCV_RAW_FLAGS: the same by the rule of
-		 * VDL2GPU_F_RAW_FLAGS.  Both unset: vdl2gpu_decode_blocks, as ever */
-		nf = g_blk_mode ? vdl2gpu_decode_blocks_ex(h, b, NULL, NULL, n, f, 128, &dropped, NULL, g_blk_mode)
+		 * VDL2GPU_F_RAW_FLAGS.  Both unset: vdl2gpu_decode_blocks, as ever.  VDL2GPU_RCV_TRACKED: any of these with the second attempt
+		 * of vdl2gpu_trk_t for a burst that gave no frame */
+		nf = g_tracked ? vdl2gpu_decode_blocks_tracked(h, b, NULL, NULL, t, n, f, 128, &dropped, NULL, g_blk_mode)
+		   : g_blk_mode ? vdl2gpu_decode_blocks_ex(h, b, NULL, NULL, n, f, 128, &dropped, NULL, g_blk_mode)
 				: vdl2gpu_decode_blocks(h, b, n, f, 128, &dropped);
 		if (dropped)	/* more frames than the buffer holds (or than 12 in one burst): never silent */
 			fprintf(stderr, "vdl2gpu_decode_blocks: %d frame(s) dropped\n", dropped);
@@ -237,6 +244,11 @@ void *rcv_thread(void *arg)
 		cfg.nstreams = 1;
 		cfg.chan = plan;
 		cfg.max_push = (size_t)BATCH_BLOCKS * (RTLINBUFSZ / 2);
+#ifdef VDL2GPU_FRAMES
+		g_tracked = getenv("VDL2GPU_RCV_TRACKED") != NULL;
+		if (g_tracked)
+			cfg.flags |= VDL2GPU_F_TRACKED;
+#endif
 		rc = vdl2gpu_create(&cfg, &h);
 		if (rc) {
 			fprintf(stderr, "vdl2gpu_create: %s\n", vdl2gpu_strerror(rc));

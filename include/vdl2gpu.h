@@ -362,7 +362,7 @@ typedef struct {
 	uint8_t row_changed[8];	/* @16 transmitted positions at which the decoded row differs from the received one */
 	uint16_t bytes_changed;	/* @24 sum of row_changed[] */
 	uint16_t rows_failed;	/* @26 rows with row_how == VDL2GPU_ROW_FAIL */
-	uint16_t rows_rescued;	/* @28 rows with row_how == VDL2GPU_ROW_SOFT2, _SOFT4 or _FEEDBACK */
+	uint16_t rows_rescued;	/* @28 rows with row_how == VDL2GPU_ROW_SOFT2, _SOFT4, _FEEDBACK or _TRACKED (vdl2gpu_trk_t, below) */
 	uint16_t stuffed;	/* @30 zeros the un-stuffer dropped */
 	uint16_t nbytes;	/* @32 whole un-stuffed bytes */
 	int16_t flag_at;	/* @34 index of the un-stuffed byte that completes the first flag, -1: never */
@@ -535,6 +535,59 @@ typedef struct {
 	float e[VDL2GPU_SYMCLK_SEGS][8];	/* @40 the sums; 40 + 22 * 32 = 744 is a multiple of 8: no padding */
 } vdl2gpu_symclk_t;		/* sizeof 744, alignment 8 */
 
+/* ---- timing-tracked rows (VDL2GPU_F_TRACKED; announced by VDL2GPU_HAVE_TRACKED, the ABI version is unchanged) ----
+ * The reference takes a burst's symbol timing once, from the 16 symbols of the unique word, and keeps it to the burst's last symbol
+ * (d8psk.c:281-319).  VDL Mode 2 allows a transmitter's symbol clock +-50 ppm and an uncorrected receiver adds its own: over the 5446
+ * symbols of the longest burst the sampling instant walks a quarter of a symbol, and since bursts are interleaved by column the damaged
+ * tail is the last columns of EVERY RS row.  With VDL2GPU_F_TRACKED the GPU slices every payload a second time, in segments of 256
+ * symbols whose sampling instant may move by a quarter of an 84 kS/s sample from one segment to the next, and keeps the bytes of that
+ * slice beside the record: the record's own data[], df and every other field and column stay the reference's.  The flag needs no other
+ * flag and changes nothing else.
+ * Notation as at vdl2gpu_carrier_t.  For an accepted record with nbrow, nlbyte, df, end_dec:
+ *   ND, NF       the data and FEC bytes, kmax = (25 + 8 (ND + NF) - 1) / 3; the payload symbols are k = 8 .. kmax, n = kmax - 7 of them;
+ *                symbol k lies at stream time t_k = end_dec - 8 (kmax - k) (that is trig_dec + j0 + 8 k)
+ *   positions    are counted in quarter samples.  P(u) is filteredphase() (d8psk.c:219-230) at stream time m = ceil(u / 4) and sub-phase
+ *                c = 4 m - u (taps mflt[c], mflt[c + 4], ... on the samples m - 16, m - 15, ...: float sums, oldest sample first, multiply
+ *                then add, then atan2f -- exactly as the payload decode forms its phases).  The reference's own slices are P(4 t_k - rb).
+ *                Samples at stream times GREATER THAN end_dec count as 0, whatever the stream holds there (only the burst's last symbol
+ *                can reach them, and only with d > 0): the record does not depend on where the stream was cut
+ *   segments     symbol index i = k - 8; segment s holds i in [256 s, min(n, 256 s + 256)); nseg = ceil(n / 256), at most 22
+ *   hypothesis   d of segment s: for each of its symbols idx_k(d) = the Grey table index (d8psk.c:213, 323-327, in 0..256) of
+ *                P(4 t_k + d) against P(4 t_{k-1} + d) with the record's df -- both phases with the same d, also for the segment's first
+ *                symbol; e = (idx & 31) - 16; the cost C_s(d) = sum of e^2 over the segment's symbols, an integer
+ *   choice       segment 0 tries d = 0, -1, -2, -3 in that order; segment s >= 1 tries d_{s-1}, d_{s-1} - 1, d_{s-1} + 1 in that order; a
+ *                later candidate wins only with a strictly smaller cost.  One step per 256 symbols follows up to 122 ppm
+ *   bytes        idx_k = idx_k(d_s) of the symbol's segment; payload bit q = 25 + 8 b + i of byte b is Grey_{q % 3}[idx_{q / 3}], descrambled
+ *                and compared with 0.5 exactly as the reference path does; the bytes are assembled and scattered to (row, col) exactly as
+ *                vdl2gpu_fb_t.data is.  Positions that carry no transmitted byte are 0
+ *   d_first, d_last, d_min, d_max   d_0, d_{nseg-1}, and the least and greatest d_s of the burst
+ * A record that is none has all zeros.  Everything chosen is an integer over bit-exact phases: a burst gets the same vdl2gpu_trk_t
+ * whatever kernel, path or repair round decoded it and however the stream was cut into pushes.
+ * The block path with tracked rows (the pipeline's with VDL2GPU_F_FRAMES | VDL2GPU_F_TRACKED; vdl2gpu_decode_blocks_tracked on any
+ * handle) makes a second attempt PER BURST, not per row: RS(255,249) with three correctable errors "decodes" a garbage row to a wrong
+ * codeword about one time in six, such a row would stay in place under a per-row rule, and the FCS then fails.
+ *   attempt A    the block path exactly as the other flags and the mode define it.  If one or more of its candidates pass, its frames and
+ *                its report are the result: no frame delivered without the flag is ever lost
+ *   attempt B    only when A passed none.  For each row r: rs() of trk.data[r] with the row's fixed erasures; if it returns >= 0 and
+ *                leaves all six syndromes zero, that row is taken (VDL2GPU_ROW_TRACKED), otherwise the row is what A's row rule left.
+ *                If no row is taken B ends here.  Then un-stuffing, the flag hunt and the FCS, as the mode says
+ *   result       if B passes one or more candidates: B's frames and B's whole report; otherwise A's -- no frames, and A's report.
+ * The report's layout is unchanged: row_roots stays the reference's run on the received row, row_changed counts against the received
+ * row, rows_rescued also counts VDL2GPU_ROW_TRACKED.  A second attempt gives the FCS's 2^-16 chance of passing a wrong candidate twice.
+ * Memory: 2048 bytes per record slot in each of the device output rings and each host slab, and in the host queue beside every
+ * burst record it holds. */
+#define VDL2GPU_F_TRACKED 65536u
+#define VDL2GPU_HAVE_TRACKED 1
+#define VDL2GPU_TRK_SEG 256		/* symbols per segment */
+#define VDL2GPU_TRK_SEGS 22		/* covers a burst of VDL2GPU_MAXROWS rows */
+#define VDL2GPU_ROW_TRACKED 7		/* block report, row_how: attempt B took the record's timing-tracked row; counted in rows_rescued */
+typedef struct {
+	uint8_t data[VDL2GPU_MAXROWS][VDL2GPU_ROWLEN];	/* @0    the rows of the tracked slice, laid out as the record's data[] */
+	int8_t d_first, d_last, d_min, d_max;		/* @2040 quarter samples: d_0, d_{nseg-1}, min and max over the segments */
+	uint8_t nseg;					/* @2044 segments used, ceil(n / 256) */
+	uint8_t reserved[3];				/* @2045 0 */
+} vdl2gpu_trk_t;		/* sizeof 2048 */
+
 typedef struct {
 	uint64_t samples_in;	/* per stream */
 	uint64_t dec_samples;	/* 84 kS/s samples produced per channel */
@@ -669,6 +722,13 @@ int vdl2gpu_poll_symclk(vdl2gpu_t *h, vdl2gpu_burst_t *out, vdl2gpu_level_t *lv,
 			vdl2gpu_fb_t *fb, vdl2gpu_symclk_t *clk, int max);
 int vdl2gpu_poll_symclk_ready(vdl2gpu_t *h, vdl2gpu_burst_t *out, vdl2gpu_level_t *lv, vdl2gpu_soft_t *soft, vdl2gpu_carrier_t *car, vdl2gpu_blockrep_t *rep,
 			      vdl2gpu_fb_t *fb, vdl2gpu_symclk_t *clk, int max);
+/* ... and with the bursts' timing-tracked rows: trk[i] belongs to out[i] (VDL2GPU_F_TRACKED).  Same queue, order, waiting and threading
+ * as the other collectors; each of lv, soft, car, rep, fb, clk and trk may be NULL (trk == NULL: exactly vdl2gpu_poll_symclk).  trk != NULL
+ * on a handle created without VDL2GPU_F_TRACKED: VDL2GPU_EINVAL, and nothing is consumed; the others as above. */
+int vdl2gpu_poll_tracked(vdl2gpu_t *h, vdl2gpu_burst_t *out, vdl2gpu_level_t *lv, vdl2gpu_soft_t *soft, vdl2gpu_carrier_t *car, vdl2gpu_blockrep_t *rep,
+			 vdl2gpu_fb_t *fb, vdl2gpu_symclk_t *clk, vdl2gpu_trk_t *trk, int max);
+int vdl2gpu_poll_tracked_ready(vdl2gpu_t *h, vdl2gpu_burst_t *out, vdl2gpu_level_t *lv, vdl2gpu_soft_t *soft, vdl2gpu_carrier_t *car, vdl2gpu_blockrep_t *rep,
+			       vdl2gpu_fb_t *fb, vdl2gpu_symclk_t *clk, vdl2gpu_trk_t *trk, int max);
 /* Number of bursts a poll would currently return (implies vdl2gpu_sync). */
 int vdl2gpu_pending(vdl2gpu_t *h);
 /* Pushes the GPU has not finished yet (0..3); never waits.  For a producer that is not bound to real time and wants to
@@ -750,6 +810,12 @@ int vdl2gpu_decode_blocks_feedback(vdl2gpu_t *h, const vdl2gpu_burst_t *blocks, 
 #define VDL2GPU_BLK_RAW_FLAGS 4u
 int vdl2gpu_decode_blocks_ex(vdl2gpu_t *h, const vdl2gpu_burst_t *blocks, const vdl2gpu_soft_t *soft, const vdl2gpu_fb_t *fb, int n,
 			     vdl2gpu_frame_t *frames, int max_frames, int *dropped, vdl2gpu_blockrep_t *rep, uint32_t mode);
+/* ... and with timing-tracked rows (announced by VDL2GPU_HAVE_TRACKED): trk[i] belongs to blocks[i] (vdl2gpu_poll_tracked), and a burst
+ * of which attempt A passes no candidate gets the second attempt defined at vdl2gpu_trk_t.  Works on any handle; soft, fb and rep may
+ * each be NULL; mode as above; trk == NULL: exactly vdl2gpu_decode_blocks_ex. */
+int vdl2gpu_decode_blocks_tracked(vdl2gpu_t *h, const vdl2gpu_burst_t *blocks, const vdl2gpu_soft_t *soft, const vdl2gpu_fb_t *fb,
+				  const vdl2gpu_trk_t *trk, int n, vdl2gpu_frame_t *frames, int max_frames, int *dropped, vdl2gpu_blockrep_t *rep,
+				  uint32_t mode);
 /* With VDL2GPU_F_FRAMES the same kernel runs on every push's burst records where they lie in device
  * memory, right behind the demodulator.  Collect the frames of everything pushed so far (waits like
  * vdl2gpu_poll; the bursts themselves stay available through vdl2gpu_poll).  Frames come out ordered

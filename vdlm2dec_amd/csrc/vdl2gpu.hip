@@ -17,6 +17,7 @@
 #include "vdl2gpu_kernels.h"
 #include "vdl2gpu_blocks.h"
 #include "vdl2gpu_symclk.h"
+#include "vdl2gpu_tracked.h"
 
 #include <algorithm>
 #include <cerrno>
@@ -95,9 +96,9 @@ struct LaterEvent {
 
 /* A burst record has side columns: entries at the record's index in the device rings, the slabs and the host queue, present when
  * the handle's flags ask for them.  A column is a name in the enum and a row of each of the two tables here. */
-enum { COL_LEVEL, COL_SOFT, COL_CARRIER, COL_REPORT, COL_FB, COL_SYMCLK, VDL2_NCOL };	/* (the order of the collectors' arguments: poll_impl) */
+enum { COL_LEVEL, COL_SOFT, COL_CARRIER, COL_REPORT, COL_FB, COL_SYMCLK, COL_TRK, VDL2_NCOL };	/* (the order of the collectors' arguments: poll_impl) */
 static const size_t col_bytes[VDL2_NCOL] = { sizeof(vdl2gpu_level_t), sizeof(vdl2gpu_soft_t), sizeof(vdl2gpu_carrier_t), sizeof(vdl2gpu_blockrep_t), sizeof(vdl2gpu_fb_t),
-					      sizeof(vdl2gpu_symclk_t) };
+					      sizeof(vdl2gpu_symclk_t), sizeof(vdl2gpu_trk_t) };
 static const struct { unsigned flag; const char *flag_name, *arg; } col_info[VDL2_NCOL] = {	/* arg: what the collectors' error texts call the column */
 	{ VDL2GPU_F_LEVELS, "VDL2GPU_F_LEVELS", "lv" },			/* a level record */
 	{ VDL2GPU_F_SOFT_RS, "VDL2GPU_F_SOFT_RS", "soft" },		/* a reliability map (2048 bytes) */
@@ -105,6 +106,7 @@ static const struct { unsigned flag; const char *flag_name, *arg; } col_info[VDL
 	{ VDL2GPU_F_BLOCK_REPORT, "VDL2GPU_F_BLOCK_REPORT", "rep" },	/* a block report (vdl2gpu_create: only with VDL2GPU_F_FRAMES) */
 	{ VDL2GPU_F_FEEDBACK, "VDL2GPU_F_FEEDBACK", "fb" },		/* decision-feedback rows (2048 bytes; with or without VDL2GPU_F_FRAMES) */
 	{ VDL2GPU_F_SYMCLK, "VDL2GPU_F_SYMCLK", "clk" },		/* a symbol-clock record (744 bytes) */
+	{ VDL2GPU_F_TRACKED, "VDL2GPU_F_TRACKED", "trk" },		/* timing-tracked rows (2048 bytes; with or without VDL2GPU_F_FRAMES) */
 };
 
 /* A table set (push % VDL2_NSET): what a push's demodulator kernels work in, see alloc_sets. */
@@ -1613,11 +1615,13 @@ extern "C" int vdl2gpu_ring_commit(vdl2gpu_t *h, size_t nsamples)
  * nullptr when K2d's second pass tags void records (see K4Params) */
 /* The block kernel on `grid` workgroups of stream s: with a report or without (rep), with the records' decision-feedback rows in the
  * row rule (k4.fb is given) or without; mode (VDL2GPU_BLK_*): 0, every segment between flags is a candidate frame (ALL_FRAMES), or that
- * with a flag being six adjacent ones of the stuffed stream (ALL_FRAMES | RAW_FLAGS) */
+ * with a flag being six adjacent ones of the stuffed stream (ALL_FRAMES | RAW_FLAGS); with the records' timing-tracked rows
+ * (k4.trk is given), each of these with the second attempt of vdl2gpu_trk_t */
 static void launch_blocks(hipStream_t s, unsigned grid, const K4Params &k4, bool rep, uint32_t mode)
 {
 	void (*const kernel)(K4Params) =
-		mode & VDL2GPU_BLK_RAW_FLAGS ? (k4.fb ? (rep ? k4_frames_raw_rep_fb : k4_frames_raw_fb) : (rep ? k4_frames_raw_rep : k4_frames_raw))
+		k4.trk ? k4_frames_trk_kernel(rep, k4.fb != nullptr, mode)	/* the records' timing-tracked rows are given: the kernels with the second attempt */
+		: mode & VDL2GPU_BLK_RAW_FLAGS ? (k4.fb ? (rep ? k4_frames_raw_rep_fb : k4_frames_raw_fb) : (rep ? k4_frames_raw_rep : k4_frames_raw))
 		: mode & VDL2GPU_BLK_ALL_FRAMES ? (k4.fb ? (rep ? k4_frames_all_rep_fb : k4_frames_all_fb) : (rep ? k4_frames_all_rep : k4_frames_all))
 						: (k4.fb ? (rep ? k4_frames_rep_fb : k4_frames_fb) : (rep ? k4_frames_rep : k4_frames));
 	hipLaunchKernelGGL(kernel, dim3(grid), dim3(K4_NT), 0, s, k4);
@@ -1638,6 +1642,7 @@ static K4Params k4_ring_params(vdl2gpu_t *h, int ring, const unsigned *fmask)
 	k4.soft = h->ring[ring].col<vdl2gpu_soft_t>(COL_SOFT);	/* (nullptr without VDL2GPU_F_SOFT_RS: the reference's block path) */
 	k4.rep = h->ring[ring].col<vdl2gpu_blockrep_t>(COL_REPORT);	/* (nullptr without VDL2GPU_F_BLOCK_REPORT, and k4_frames is launched, which does not look at it) */
 	k4.fb = h->ring[ring].col<vdl2gpu_fb_t>(COL_FB);	/* (nullptr without VDL2GPU_F_FEEDBACK: launch_blocks) */
+	k4.trk = h->ring[ring].col<vdl2gpu_trk_t>(COL_TRK);	/* (nullptr without VDL2GPU_F_TRACKED: launch_blocks) */
 	return k4;
 }
 
@@ -1791,6 +1796,26 @@ static int enqueue_back(vdl2gpu_t *h)
 		launch_payload(h, ts, k2, SEL_FINAL, ring);	/* one pass behind the commit: the repaired selection where there is one */
 	HIPCHK(h, hipGetLastError());
 	TRY(mark(h, pt, E_PAYLOAD2_END, ts, true));
+	if (h->col_on[COL_TRK]) {
+		/* VDL2GPU_F_TRACKED: the timing-tracked rows of every record of the push's ring, behind the last payload pass -- the records are
+		 * final -- and in front of the block path, which reads them; on the tail's stream, where the set is the push's own until k2_done
+		 * below.  Record-driven, like k_symclk_sums: whichever kernel, pass or round made a record, this is the one place that slices it. */
+		KTrackedParams kt{};
+		kt.dec = k2.dec;
+		kt.cap = (int)k2.cap;
+		kt.dec_base = k2.dec_base;
+		kt.frames = (int)std::min<long long>(VDL2_CARRY_FRAMES + J, k2.cap);
+		kt.cfg = h->d_cfg;
+		kt.nbch = h->C;
+		kt.nstreams = h->S;
+		kt.recs = h->ring[ring].d_recs;
+		kt.count = &h->d_outc->ring[ring].records;
+		kt.rec_cap = h->rec_cap;
+		kt.out = h->ring[ring].col<vdl2gpu_trk_t>(COL_TRK);
+		kt.pn8 = k2.pn8;
+		hipLaunchKernelGGL(k_tracked_rows, dim3(std::min(h->rec_cap, 4u * (unsigned)h->n_cu)), dim3(KTR_NT), 0, ts, kt);
+		HIPCHK(h, hipGetLastError());
+	}
 	if (h->frames_on) {
 		/* block path on the records where they lie (vdlm2.c:84-161).  In the chain, not beside it:
 		 * a latency-bound kernel like this one and the next push's scan slow each other down by
@@ -1842,6 +1867,11 @@ static int enqueue_back(vdl2gpu_t *h)
 		if (h->col_on[COL_FB]) {	/* the feedback rows beside them: a kernel of its own, k_export_records keeps its registers */
 			hipLaunchKernelGGL(k_export_feedback, dim3((unsigned)h->n_cu), dim3(256), 0, ts, ke.count, ke.cap,
 					   rg.col<const vdl2gpu_fb_t>(COL_FB), sl.col<vdl2gpu_fb_t>(COL_FB));
+			HIPCHK(h, hipGetLastError());
+		}
+		if (h->col_on[COL_TRK]) {	/* ... and the timing-tracked rows */
+			hipLaunchKernelGGL(k_export_tracked, dim3((unsigned)h->n_cu), dim3(256), 0, ts, ke.count, ke.cap,
+					   rg.col<const vdl2gpu_trk_t>(COL_TRK), sl.col<vdl2gpu_trk_t>(COL_TRK));
 			HIPCHK(h, hipGetLastError());
 		}
 		if (h->col_on[COL_SYMCLK]) {	/* ... and the symbol-clock records, likewise */
@@ -2829,6 +2859,7 @@ struct BlockTemps {
 	FrameCounters *cnt = nullptr;
 	vdl2gpu_blockrep_t *rep = nullptr;
 	vdl2gpu_fb_t *fb = nullptr;
+	vdl2gpu_trk_t *trk = nullptr;
 	~BlockTemps()
 	{
 		(void)hipFree(blk);
@@ -2837,6 +2868,7 @@ struct BlockTemps {
 		(void)hipFree(cnt);
 		(void)hipFree(rep);
 		(void)hipFree(fb);
+		(void)hipFree(trk);
 	}
 };
 
@@ -2855,6 +2887,7 @@ static K4Params k4_block_params(vdl2gpu_t *h, const BlockTemps &d, int n, int ma
 	k4.soft = d.soft;
 	k4.rep = d.rep;
 	k4.fb = d.fb;
+	k4.trk = d.trk;
 	return k4;
 }
 
@@ -2882,6 +2915,14 @@ extern "C" int vdl2gpu_decode_blocks_feedback(vdl2gpu_t *h, const vdl2gpu_burst_
 extern "C" int vdl2gpu_decode_blocks_ex(vdl2gpu_t *h, const vdl2gpu_burst_t *blocks, const vdl2gpu_soft_t *soft, const vdl2gpu_fb_t *fb, int n,
 					vdl2gpu_frame_t *frames, int max_frames, int *dropped, vdl2gpu_blockrep_t *rep, uint32_t mode)
 {
+	return vdl2gpu_decode_blocks_tracked(h, blocks, soft, fb, nullptr, n, frames, max_frames, dropped, rep, mode);
+}
+
+/* trk: the kernels with the second attempt of vdl2gpu_trk_t (launch_blocks) */
+extern "C" int vdl2gpu_decode_blocks_tracked(vdl2gpu_t *h, const vdl2gpu_burst_t *blocks, const vdl2gpu_soft_t *soft, const vdl2gpu_fb_t *fb,
+					     const vdl2gpu_trk_t *trk, int n, vdl2gpu_frame_t *frames, int max_frames, int *dropped,
+					     vdl2gpu_blockrep_t *rep, uint32_t mode)
+{
 	if (!h || n < 0 || max_frames < 0 || (n > 0 && !blocks) || (max_frames > 0 && !frames) ||
 	    (mode != 0u && mode != VDL2GPU_BLK_ALL_FRAMES && mode != (VDL2GPU_BLK_ALL_FRAMES | VDL2GPU_BLK_RAW_FLAGS)))
 		return VDL2GPU_EINVAL;
@@ -2907,6 +2948,8 @@ extern "C" int vdl2gpu_decode_blocks_ex(vdl2gpu_t *h, const vdl2gpu_burst_t *blo
 		BLKCHK(hipMalloc(&d.rep, (size_t)n * sizeof(vdl2gpu_blockrep_t)));
 	if (fb)
 		BLKCHK(hipMalloc(&d.fb, (size_t)n * sizeof(vdl2gpu_fb_t)));
+	if (trk)
+		BLKCHK(hipMalloc(&d.trk, (size_t)n * sizeof(vdl2gpu_trk_t)));
 	/* on the stream the kernel runs on: that stream does not wait for the legacy default stream, and a
 	 * plain hipMemset() that lands after the kernel's first atomics loses frames */
 	BLKCHK(hipMemcpyAsync(d.blk, blocks, (size_t)n * sizeof(vdl2gpu_burst_t), hipMemcpyHostToDevice, h->copy_stream));
@@ -2914,6 +2957,8 @@ extern "C" int vdl2gpu_decode_blocks_ex(vdl2gpu_t *h, const vdl2gpu_burst_t *blo
 		BLKCHK(hipMemcpyAsync(d.soft, soft, (size_t)n * sizeof(vdl2gpu_soft_t), hipMemcpyHostToDevice, h->copy_stream));
 	if (fb)
 		BLKCHK(hipMemcpyAsync(d.fb, fb, (size_t)n * sizeof(vdl2gpu_fb_t), hipMemcpyHostToDevice, h->copy_stream));
+	if (trk)
+		BLKCHK(hipMemcpyAsync(d.trk, trk, (size_t)n * sizeof(vdl2gpu_trk_t), hipMemcpyHostToDevice, h->copy_stream));
 	BLKCHK(hipMemsetAsync(d.cnt, 0, sizeof *d.cnt, h->copy_stream));
 	const unsigned grid = (unsigned)std::min<long long>(n, (long long)h->n_cu * 32);
 	launch_blocks(h->copy_stream, grid, k4_block_params(h, d, n, max_frames), rep != nullptr, mode);
@@ -3004,7 +3049,7 @@ extern "C" int vdl2gpu_inflight(vdl2gpu_t *h)
 	return n;
 }
 
-/* The fourteen collectors.  side.p[k]: where the caller wants column k beside the records (nullptr: not).  who: the entry point as the
+/* The sixteen collectors.  side.p[k]: where the caller wants column k beside the records (nullptr: not).  who: the entry point as the
  * error texts name it.  When the handle was made without a column that is asked for, the first such column in the order of the
  * arguments is named: "who: arg needs FLAG" (named = false, the two collectors with one column: "who needs FLAG"). */
 struct PollCols {
@@ -3044,6 +3089,9 @@ extern "C" int vdl2gpu_poll_feedback_ready(vdl2gpu_t *h, vdl2gpu_burst_t *out, v
 
 extern "C" int vdl2gpu_poll_symclk(vdl2gpu_t *h, vdl2gpu_burst_t *out, vdl2gpu_level_t *lv, vdl2gpu_soft_t *soft, vdl2gpu_carrier_t *car, vdl2gpu_blockrep_t *rep, vdl2gpu_fb_t *fb, vdl2gpu_symclk_t *clk, int max) { return poll_impl(h, out, max, {{lv, soft, car, rep, fb, clk}}, true, "vdl2gpu_poll_symclk"); }
 extern "C" int vdl2gpu_poll_symclk_ready(vdl2gpu_t *h, vdl2gpu_burst_t *out, vdl2gpu_level_t *lv, vdl2gpu_soft_t *soft, vdl2gpu_carrier_t *car, vdl2gpu_blockrep_t *rep, vdl2gpu_fb_t *fb, vdl2gpu_symclk_t *clk, int max) { return poll_impl(h, out, max, {{lv, soft, car, rep, fb, clk}}, false, "vdl2gpu_poll_symclk"); }
+
+extern "C" int vdl2gpu_poll_tracked(vdl2gpu_t *h, vdl2gpu_burst_t *out, vdl2gpu_level_t *lv, vdl2gpu_soft_t *soft, vdl2gpu_carrier_t *car, vdl2gpu_blockrep_t *rep, vdl2gpu_fb_t *fb, vdl2gpu_symclk_t *clk, vdl2gpu_trk_t *trk, int max) { return poll_impl(h, out, max, {{lv, soft, car, rep, fb, clk, trk}}, true, "vdl2gpu_poll_tracked"); }
+extern "C" int vdl2gpu_poll_tracked_ready(vdl2gpu_t *h, vdl2gpu_burst_t *out, vdl2gpu_level_t *lv, vdl2gpu_soft_t *soft, vdl2gpu_carrier_t *car, vdl2gpu_blockrep_t *rep, vdl2gpu_fb_t *fb, vdl2gpu_symclk_t *clk, vdl2gpu_trk_t *trk, int max) { return poll_impl(h, out, max, {{lv, soft, car, rep, fb, clk, trk}}, false, "vdl2gpu_poll_tracked"); }
 
 /* VDL2GPU_F_CARRIER: the derived values of a carrier record (include/vdl2gpu.h, vdl2gpu_carrier_t) -- the one statement of that
  * arithmetic: collect_records calls it for every record. */

@@ -21,6 +21,8 @@
  * not only what follows the first flag (VDL2GPU_F_ALL_FRAMES): k4_fcs_scan_all in k4_fcs_scan's place, k4_emit with each frame's own start.
  * ... and over RAW: the four kernels k4_frames_raw* (vdl2gpu_rawflags.hip) are those with VDL2GPU_F_RAW_FLAGS: k4_unstuff marks the bytes
  * that lost a stuffed zero in front of their bit 6, and a byte 0x7e with that mark is data to k4_flag_hunt and k4_fcs_scan_all, no flag.
+ * ... and over TRK: the kernels k4_frames_trk* (vdl2gpu_tracked.hip) make a second attempt with the record's timing-tracked rows
+ * (K4Params.trk, VDL2GPU_F_TRACKED) for a burst of which the first attempt passes no candidate: k4_trk_second, k4_trk_rows.
  */
 #ifndef VDL2GPU_BLOCKS_H
 #define VDL2GPU_BLOCKS_H
@@ -61,6 +63,8 @@ struct K4Params {
 					 * reads it (last: the other members keep their place) */
 	const vdl2gpu_fb_t *fb;		/* k4_frames_fb / k4_frames_rep_fb only (VDL2GPU_F_FEEDBACK): the records' decision-feedback rows, same
 					 * index: the row rule of vdl2gpu_fb_t.  The other two kernels never read it (last, for the same reason) */
+	const vdl2gpu_trk_t *trk;	/* k4_frames_trk* only (VDL2GPU_F_TRACKED): the records' timing-tracked rows, same index: the second attempt
+					 * of vdl2gpu_trk_t.  No other kernel reads it (last, for the same reason) */
 };
 
 #define K4_TABW ((512 + 256 + 512) / 4)
@@ -1030,14 +1034,114 @@ __device__ __forceinline__ void k4_rep_store(const K4Rep &rp, vdl2gpu_blockrep_t
 		reinterpret_cast<unsigned *>(g)[lane] = rp.w[lane];
 }
 
+/* ---- TRK: attempt B's rows (vdl2gpu.h, vdl2gpu_trk_t).  The rows in sh.recw are what attempt A's row rule left.  Row by row the
+ * record's tracked row goes to `trial` (sh.dst: dead between the attempts, the un-stuffer clears it), rs() runs on it with the row's fixed
+ * erasures, and if that returns >= 0 and leaves all six syndromes zero the row is taken.  REP: rep (in LDS, attempt A's report) gets
+ * VDL2GPU_ROW_TRACKED and row_changed against the RECEIVED row, which is read again from the record in memory (grec); the three sums
+ * are formed again from the rows' entries.  With a row taken sh.src is built again.  Returns the number of rows taken. */
+template <bool REP>
+__device__ __forceinline__ int k4_trk_rows(K4Shared &sh, const vdl2gpu_burst_t *grec, const vdl2gpu_trk_t *trk, int nbrow, int nlbyte,
+					   const unsigned (&sexp)[4][2], int lane, vdl2gpu_blockrep_t *rep)
+{
+	uint8_t *const rows = reinterpret_cast<uint8_t *>(sh.recw) + offsetof(vdl2gpu_burst_t, data);
+	uint8_t *const trial = reinterpret_cast<uint8_t *>(sh.dst);
+	int taken = 0;
+	for (int r = 0; r < nbrow; ++r) {
+		const int by = r == nbrow - 1 ? nlbyte : 249;
+		const int nera = k4_set_eras(sh, by, lane);
+		for (int i = lane; i < 255; i += K4_NT)
+			trial[i] = trk->data[r][i];
+		K4_SYNC();
+		bool ok = k4_rs_row(sh, trial, nera, sexp, lane);
+		if (ok) {
+			unsigned syn[6];
+			const unsigned any = k4_syndromes(sh, trial, sexp, syn, lane);
+			K4_SYNC();
+			ok = !any;
+		}
+		if (!ok)	/* (wave-uniform) */
+			continue;
+		++taken;
+		uint8_t *const row = rows + r * VDL2GPU_ROWLEN;
+		for (int i = lane; i < 255; i += K4_NT)
+			row[i] = trial[i];
+		K4_SYNC();
+		if constexpr (REP) {
+			const BurstGeom g = burst_geom(nbrow, nlbyte);
+			const int pr = r < g.nf_rows - 1 ? 6 : (r == g.nf_rows - 1 ? g.nf_last : 0);	/* the transmitted parity of row r */
+			unsigned nch = 0;
+#pragma unroll
+			for (int b = 0; b < 4; ++b) {
+				const int j = lane * 4 + b;
+				const bool sent = j < by || (j >= 249 && j < 249 + pr);
+				nch += (unsigned)__popcll(__ballot(sent && row[j < 255 ? j : 254] != grec->data[r][j < 255 ? j : 254]));
+			}
+			if (lane == 0) {
+				rep->row_how[r] = VDL2GPU_ROW_TRACKED;
+				rep->row_changed[r] = (uint8_t)nch;
+			}
+		}
+	}
+	if (taken) {
+		int nby = 0;
+		for (int r = 0; r < nbrow; ++r) {
+			const int by = r == nbrow - 1 ? nlbyte : 249;
+			for (int i = lane; i < by; i += K4_NT)
+				sh.src[nby + i] = rows[r * VDL2GPU_ROWLEN + i];
+			nby += by;
+		}
+		if (REP && lane == 0) {
+			unsigned changed = 0, failed = 0, rescued = 0;
+			for (int r = 0; r < nbrow; ++r) {
+				const unsigned how = rep->row_how[r];
+				changed += rep->row_changed[r];
+				failed += how == VDL2GPU_ROW_FAIL;
+				rescued += how == VDL2GPU_ROW_SOFT2 || how == VDL2GPU_ROW_SOFT4 || how == VDL2GPU_ROW_FEEDBACK || how == VDL2GPU_ROW_TRACKED;
+			}
+			rep->bytes_changed = (uint16_t)changed;
+			rep->rows_failed = (uint16_t)failed;
+			rep->rows_rescued = (uint16_t)rescued;
+		}
+	}
+	K4_SYNC();
+	return taken;
+}
+
+/* TRK: an attempt has passed no candidate -- is there another one to make?  Behind attempt A (second == false): yes if the record has
+ * tracked rows and k4_trk_rows takes one; attempt A's report is kept in rpa first.  Behind attempt B: no, and A's report comes back. */
+template <bool REP>
+__device__ __forceinline__ bool k4_trk_second(K4Shared &sh, const K4Params &p, unsigned ib, K4Rep &rp, K4Rep &rpa, int nbrow, int nlbyte,
+					      const unsigned (&sexp)[4][2], int lane, bool second)
+{
+	if (second || !p.trk) {
+		if (REP && second) {
+			K4_SYNC();
+			if (lane < (int)(sizeof(vdl2gpu_blockrep_t) / 4))
+				rp.w[lane] = rpa.w[lane];
+			K4_SYNC();
+		}
+		return false;
+	}
+	if constexpr (REP) {
+		K4_SYNC();
+		if (lane < (int)(sizeof(vdl2gpu_blockrep_t) / 4))
+			rpa.w[lane] = rp.w[lane];
+		K4_SYNC();
+	}
+	return k4_trk_rows<REP>(sh, p.recs + ib, p.trk + ib, nbrow, nlbyte, sexp, lane, &rp.r) > 0;
+}
+
 /* FB: p.fb holds the records' decision-feedback rows for the row rule of vdl2gpu_fb_t */
 /* ALL: every segment between flags is a candidate frame (VDL2GPU_F_ALL_FRAMES), see k4_fcs_scan */
 /* RAW: ... and a flag is six adjacent ones of the stuffed stream (VDL2GPU_F_RAW_FLAGS), see k4_unstuff */
-template <bool REP, bool FB = false, bool ALL = false, bool RAW = false>
+/* TRK: p.trk holds the records' timing-tracked rows: a burst of which the steps behind k4_rs_rows pass no candidate goes through them a
+ * second time with the rows k4_trk_rows takes (vdl2gpu.h, vdl2gpu_trk_t: attempts A and B).  Without TRK the loop below runs once */
+template <bool REP, bool FB = false, bool ALL = false, bool RAW = false, bool TRK = false>
 __device__ __forceinline__ void k4_frames_body(const K4Params &p)
 {
 	__shared__ K4Shared sh;
 	__shared__ K4Rep rp;	/* (REP; never touched without it) */
+	__shared__ K4Rep rpa;	/* (REP and TRK: attempt A's report while attempt B is under way) */
 	unsigned *const marks = RAW ? reinterpret_cast<unsigned *>(sh.save) : nullptr;	/* (behind k4_rs_rows: see k4_unstuff) */
 	const int lane = threadIdx.x;
 	/* Everything the first record needs from memory is asked for at once -- the tables, the record
@@ -1085,34 +1189,50 @@ __device__ __forceinline__ void k4_frames_body(const K4Params &p)
 			continue;
 		k4_fetch_rows(sh, p.recs + ib, nbrow, lane);
 		const int nby = k4_rs_rows<REP, FB>(sh, p.soft ? p.soft + ib : nullptr, nbrow, nlbyte, sexp, lane, &rp.r, FB ? p.fb + ib : nullptr);
-		const int nbits = k4_unstuff<RAW>(sh, nby, lane, marks);
-		const int nb = nbits >> 3;	/* whole un-stuffed bytes */
-		int c0, c1;	/* of them, the lane's */
-		const int per = k4_lane_span(nb, lane, &c0, &c1);
-		const int m1 = k4_flag_hunt<RAW>(sh, c0, c1, lane, marks);
-		if (REP && lane == 0) {
-			rp.r.stuffed = (uint16_t)(8 * nby - nbits);
-			rp.r.nbytes = (uint16_t)nb;
-			rp.r.flag_at = (int16_t)(sh.flag0 == K4_NONE ? -1 : sh.flag0);
-		}
-		if (m1 == K4_NONE) {
+		bool second = false, again;	/* (TRK) attempt B is under way; another attempt follows */
+		do {
+			again = false;
+			const int nbits = k4_unstuff<RAW>(sh, nby, lane, marks);
+			const int nb = nbits >> 3;	/* whole un-stuffed bytes */
+			int c0, c1;	/* of them, the lane's */
+			const int per = k4_lane_span(nb, lane, &c0, &c1);
+			const int m1 = k4_flag_hunt<RAW>(sh, c0, c1, lane, marks);
+			if (REP && lane == 0) {
+				rp.r.stuffed = (uint16_t)(8 * nby - nbits);
+				rp.r.nbytes = (uint16_t)nb;
+				rp.r.flag_at = (int16_t)(sh.flag0 == K4_NONE ? -1 : sh.flag0);
+			}
+			if (m1 == K4_NONE) {
+				if constexpr (TRK) {
+					if (k4_trk_second<REP>(sh, p, ib, rp, rpa, nbrow, nlbyte, sexp, lane, second)) {
+						second = again = true;
+						continue;
+					}
+				}
+				if constexpr (REP)
+					k4_rep_store(rp, p.rep + ib, lane);
+				K4_SYNC();
+				continue;
+			}
+			const unsigned counts = k4_fcs_scan<REP, ALL, RAW>(sh, m1, per, c0, c1, lane, marks);
+			if (REP && lane == 0) {
+				const unsigned cand = counts & 0xffffu, too_short = counts >> 16, frames = (unsigned)sh.nfr;	/* (nfr: before k4_sort_candidates caps it) */
+				rp.r.cand = (uint16_t)cand;
+				rp.r.too_short = (uint16_t)too_short;
+				rp.r.bad_fcs = (uint16_t)(cand - too_short - frames);	/* every 0x7e behind hdata[1] is one of the three */
+				rp.r.frames = (uint16_t)frames;
+			}
+			if constexpr (TRK) {
+				if (sh.nfr == 0 && k4_trk_second<REP>(sh, p, ib, rp, rpa, nbrow, nlbyte, sexp, lane, second)) {
+					second = again = true;
+					continue;
+				}
+			}
+			k4_sort_candidates(sh, &p.nframes->dropped, lane);
+			k4_emit<ALL>(sh, p, myslot, ib, m1, lane);
 			if constexpr (REP)
 				k4_rep_store(rp, p.rep + ib, lane);
-			K4_SYNC();
-			continue;
-		}
-		const unsigned counts = k4_fcs_scan<REP, ALL, RAW>(sh, m1, per, c0, c1, lane, marks);
-		if (REP && lane == 0) {
-			const unsigned cand = counts & 0xffffu, too_short = counts >> 16, frames = (unsigned)sh.nfr;	/* (nfr: before k4_sort_candidates caps it) */
-			rp.r.cand = (uint16_t)cand;
-			rp.r.too_short = (uint16_t)too_short;
-			rp.r.bad_fcs = (uint16_t)(cand - too_short - frames);	/* every 0x7e behind hdata[1] is one of the three */
-			rp.r.frames = (uint16_t)frames;
-		}
-		k4_sort_candidates(sh, &p.nframes->dropped, lane);
-		k4_emit<ALL>(sh, p, myslot, ib, m1, lane);
-		if constexpr (REP)
-			k4_rep_store(rp, p.rep + ib, lane);
+		} while (TRK && again);
 	}
 }
 

@@ -20,7 +20,7 @@
 #define K2B_NT 64		/* one wavefront per burst cluster */
 #define VDL2_XT 256		/* samples in the LDS tile: >= 152+1 (ring), 16+2*64+1 (window), 16+7+65 (header) */
 
-#include "vdl2gpu_geom.h"	/* BurstGeom, burst_geom: the receiver's byte schedule for a burst */
+#include "vdl2gpu_geom.h"	/* BurstGeom, burst_geom, burst_scatter: the receiver's byte schedule for a burst */
 
 __device__ __forceinline__ void burst_timing(int clk0, int *j0, int *rb)
 {
@@ -29,34 +29,6 @@ __device__ __forceinline__ void burst_timing(int clk0, int *j0, int *rb)
 		j = 1;
 	*j0 = j;
 	*rb = clk0 + 4 * j - 32;	/* sub-phase during and after the burst */
-}
-
-/* (row, col) of payload byte b: the column-major de-interleave (d8psk.c:127-147, 176-197) as a closed-form scatter */
-__device__ __forceinline__ void burst_scatter(const BurstGeom &g, int b, int *row, int *col)
-{
-	if (b < g.ND) {
-		const int full = g.nd_last * g.nd_rows;
-		if (b < full) {
-			*col = b / g.nd_rows;
-			*row = b % g.nd_rows;
-		} else {
-			const int bb = b - full;
-			*col = g.nd_last + bb / (g.nd_rows - 1);
-			*row = bb % (g.nd_rows - 1);
-		}
-	} else {
-		const int bf = b - g.ND;
-		const int full = g.nf_last * g.nf_rows;
-		if (bf < full) {
-			*col = bf / g.nf_rows;
-			*row = bf % g.nf_rows;
-		} else {
-			const int bb = bf - full;
-			*col = g.nf_last + bb / (g.nf_rows - 1);
-			*row = bb % (g.nf_rows - 1);
-		}
-		*col += 249;
-	}
 }
 
 /* VDL2GPU_F_LEVELS: |S|^2 of one evaluation, S formed exactly as k2_fir_phase_tab forms it before its atan2f (x[0..16] ends at the

@@ -126,6 +126,23 @@ def symclk_from_sums(sym_first_dec: int, nsym: int, e, sdrinrate: int) -> SymClo
                     np.frombuffer(bytes(c.e), np.float32).reshape(_lib.SYMCLK_SEGS, 8).copy(), tuple(tau[:c.nseg]))
 
 
+@dataclass(frozen=True)
+class Tracked:
+    """vdl2gpu_trk_t: the burst's rows sliced with a sampling instant tracked in segments of 256 symbols (Receiver(tracked=True);
+    definitions in include/vdl2gpu.h)."""
+    data: np.ndarray           # uint8 (8, 255), laid out as the record's data[]
+    d_first: int               # quarter samples: the first segment's offset ...
+    d_last: int                # ... the last segment's ...
+    d_min: int                 # ... and the least and greatest of the burst
+    d_max: int
+    nseg: int
+    raw: bytes                 # the 2048 bytes of the entry
+
+    @classmethod
+    def from_c(cls, v) -> "Tracked":
+        return cls(_rows(v.data), v.d_first, v.d_last, v.d_min, v.d_max, v.nseg, bytes(v))
+
+
 def carrier_from_sums(df: float, Fr: int, nsym: int, sum_e: int, sum_e2: int) -> Carrier:
     """vdl2gpu_carrier_from_sums: the derived values of a carrier record, as the library computes them (no GPU needed)."""
     c = _lib.CarrierT()
@@ -156,6 +173,7 @@ class Burst:
     report: Optional[BlockReport] = None   # Receiver(frames=True, block_report=True) only; not part of key()
     fb: Optional[np.ndarray] = None   # Receiver(feedback=True) only: uint8 (8, 255), the rows sliced with decision feedback; not part of key()
     clock: Optional[SymClock] = None   # Receiver(symclk=True) only; not part of key()
+    trk: Optional["Tracked"] = None   # Receiver(tracked=True) only: the rows sliced with a tracked sampling instant; not part of key()
 
     def key(self):
         return (self.stream, self.chn, self.nbrow, self.nlbyte, self.data)
@@ -175,6 +193,10 @@ _COLUMNS = (
     ("feedback", _lib.F_FEEDBACK, _lib.FbT, lambda v: _rows(v.data)),
     ("symclk", _lib.F_SYMCLK, _lib.SymClkT, None),     # (SymClock.from_c wants the receiver's rate: _collect)
 )
+# ... and the columns behind the symbol clock, in the order of vdl2gpu_poll_tracked's arguments (_COLUMNS is what vdl2gpu_poll_symclk takes)
+_ALL_COLUMNS = _COLUMNS + (
+    ("tracked", _lib.F_TRACKED, _lib.TrkT, Tracked.from_c),
+)
 
 
 def plan_channels(fc: int, offsets: Sequence[int]) -> List[ThreadParam]:
@@ -189,7 +211,9 @@ class Receiver:
                  frames: bool = False, rtl_quirk: bool = False, flags: int = 0, testhooks: bool = False,
                  levels: bool = False, soft_rs: bool = False, exact_fo: bool = False, carrier: bool = False,
                  block_report: bool = False, feedback: bool = False, all_frames: bool = False, raw_flags: bool = False,
-                 symclk: bool = False):
+                 symclk: bool = False, tracked: bool = False):
+        # tracked: VDL2GPU_F_TRACKED, every burst's rows sliced a second time with a tracked sampling instant (Burst.trk); with frames=True
+        # the block path makes a second attempt with them for a burst of which the first passes no candidate
         # symclk: VDL2GPU_F_SYMCLK, every burst's symbol timing, clock drift and fine arrival time (Burst.clock)
         # raw_flags: VDL2GPU_F_RAW_FLAGS (needs all_frames=True), a stuffed data byte 0x7e is told from a flag, so frames that hold one arrive
         # all_frames: VDL2GPU_F_ALL_FRAMES (needs frames=True), the block path hands on every frame of a burst, not only the first
@@ -226,13 +250,13 @@ class Receiver:
         cfg.max_push = max_push
         cfg.device = device
         cfg.max_bursts = max_bursts
-        asked = dict(levels=levels, soft_rs=soft_rs, carrier=carrier, block_report=block_report, feedback=feedback, symclk=symclk)
+        asked = dict(levels=levels, soft_rs=soft_rs, carrier=carrier, block_report=block_report, feedback=feedback, symclk=symclk, tracked=tracked)
         switches = [(keep_dec, _lib.F_KEEP_DEC), (serial, _lib.F_SERIAL), (full_scan, _lib.F_FULLSCAN), (frames, _lib.F_FRAMES),
                     (rtl_quirk, _lib.F_RTL_QUIRK), (exact_fo, _lib.F_EXACT_FO), (all_frames, _lib.F_ALL_FRAMES),
-                    (raw_flags, _lib.F_RAW_FLAGS)] + [(asked[kw], flag) for kw, flag, _, _ in _COLUMNS]
+                    (raw_flags, _lib.F_RAW_FLAGS)] + [(asked[kw], flag) for kw, flag, _, _ in _ALL_COLUMNS]
         cfg.flags = flags | sum(flag for on, flag in switches if on)     # (one bit each)
         self.max_push = max_push
-        for kw, flag, _, _ in _COLUMNS:     # self.levels, .soft_rs, .carrier, .block_report, .feedback, .symclk: by keyword or by `flags`
+        for kw, flag, _, _ in _ALL_COLUMNS:     # self.levels, .soft_rs, .carrier, .block_report, .feedback, .symclk, .tracked: by keyword or by `flags`
             setattr(self, kw, bool(cfg.flags & flag))
         self.all_frames = bool(cfg.flags & _lib.F_ALL_FRAMES)
         self.raw_flags = bool(cfg.flags & _lib.F_RAW_FLAGS)
@@ -289,9 +313,9 @@ class Receiver:
     def _collect(self, ready: bool, max_bursts: int) -> List[Burst]:
         out: List[Burst] = []
         buf = (_lib.BurstT * max_bursts)()
-        cols = [(typ * max_bursts)() if getattr(self, kw) else None for kw, _, typ, _ in _COLUMNS]
+        cols = [(typ * max_bursts)() if getattr(self, kw) else None for kw, _, typ, _ in _ALL_COLUMNS]
         # the widest collector serves every handle: a column the handle lacks is None, "not wanted" (include/vdl2gpu.h)
-        fn = self.L.vdl2gpu_poll_symclk_ready if ready else self.L.vdl2gpu_poll_symclk
+        fn = self.L.vdl2gpu_poll_tracked_ready if ready else self.L.vdl2gpu_poll_tracked
         while True:
             n = self._check(fn(self.h, buf, *cols, max_bursts))
             for i in range(n):
@@ -299,7 +323,7 @@ class Receiver:
                 out.append(Burst(b.stream, b.chn, b.Fr, b.nbrow, b.nlbyte, b.df, b.ppm, b.trig_dec, b.end_dec,
                                  b.trig_sample, b.end_sample, bytes(b.data),
                                  *[None if v is None else (conv(v[i]) if conv else SymClock.from_c(v[i], self.rate))
-                                   for v, (_, _, _, conv) in zip(cols, _COLUMNS)]))
+                                   for v, (_, _, _, conv) in zip(cols, _ALL_COLUMNS)]))
             if n < max_bursts:
                 return out
 
@@ -335,6 +359,9 @@ class Receiver:
     def poll_symclk_raw(self, buf, lv, sv, cv, rv, fv, kv, max_bursts: int, ready: bool = False) -> int:
         return self._poll_cols_raw("vdl2gpu_poll_symclk", ready, buf, (lv, sv, cv, rv, fv, kv), max_bursts)
 
+    def poll_tracked_raw(self, buf, lv, sv, cv, rv, fv, kv, tv, max_bursts: int, ready: bool = False) -> int:
+        return self._poll_cols_raw("vdl2gpu_poll_tracked", ready, buf, (lv, sv, cv, rv, fv, kv, tv), max_bursts)
+
     def poll_ready_raw(self, buf, max_bursts: int) -> int:
         """vdl2gpu_poll_ready: bursts of pushes that have already finished; never waits."""
         return self._check(self.L.vdl2gpu_poll_ready(self.h, buf, max_bursts))
@@ -360,7 +387,7 @@ class Receiver:
 
     # ------------------------------------------------------------------ block path
     def decode_blocks(self, blocks: Sequence, max_frames: int = 0, soft=None, report: bool = False, fb=None, all_frames: bool = False,
-                      raw_flags: bool = False):
+                      raw_flags: bool = False, trk=None):
         """blk_thread for a batch (vdlm2.c:84-161): (index of the block, hdata) of every frame the
         reference would pass to out().  ``blocks``: Burst objects or (nbrow, nlbyte, data) tuples.
         ``soft``: one (8, 255) uint8 reliability map per block (Burst.soft): the soft row rule of include/vdl2gpu.h
@@ -370,7 +397,9 @@ class Receiver:
         them if it decodes there (vdl2gpu_decode_blocks_feedback), on any handle; None: not.
         ``all_frames``: every frame of a burst, by the rule of VDL2GPU_F_ALL_FRAMES (vdl2gpu_decode_blocks_ex with
         VDL2GPU_BLK_ALL_FRAMES), on any handle; the frames of a block come in stream order.
-        ``raw_flags`` (with ``all_frames``): the rule of VDL2GPU_F_RAW_FLAGS, a stuffed data byte 0x7e is no flag (VDL2GPU_BLK_RAW_FLAGS)."""
+        ``raw_flags`` (with ``all_frames``): the rule of VDL2GPU_F_RAW_FLAGS, a stuffed data byte 0x7e is no flag (VDL2GPU_BLK_RAW_FLAGS).
+        ``trk``: one (8, 255) uint8 array of timing-tracked rows per block (Burst.trk.data): a block of which the first attempt passes no
+        candidate gets the second attempt of vdl2gpu_trk_t (vdl2gpu_decode_blocks_tracked), on any handle; None: not."""
         if raw_flags and not all_frames:
             raise ValueError("raw_flags=True needs all_frames=True")
         n = len(blocks)
@@ -402,10 +431,21 @@ class Receiver:
             for i, m in enumerate(fb):
                 m = np.ascontiguousarray(m, np.uint8).reshape(8, 255)
                 C.memmove(C.addressof(farr[i].data), m.ctypes.data, 8 * 255)
+        tarr = None
+        if trk is not None:
+            if len(trk) != n:
+                raise ValueError("one set of tracked rows per block")
+            tarr = (_lib.TrkT * n)()
+            for i, m in enumerate(trk):
+                m = np.ascontiguousarray(m, np.uint8).reshape(8, 255)
+                C.memmove(C.addressof(tarr[i].data), m.ctypes.data, 8 * 255)
         rarr = (_lib.BlockRepT * n)() if report else None
         # (soft NULL: hard mode; rep NULL: exactly vdl2gpu_decode_blocks_soft, and with both exactly vdl2gpu_decode_blocks; fb NULL: the
         # library's vdl2gpu_decode_blocks_report, which the older calls go through as well)
-        if all_frames:
+        if tarr is not None:
+            mode = (_lib.BLK_ALL_FRAMES | (_lib.BLK_RAW_FLAGS if raw_flags else 0)) if all_frames else 0
+            nf = self._check(self.L.vdl2gpu_decode_blocks_tracked(self.h, arr, sarr, farr, tarr, n, out, cap, C.byref(dropped), rarr, mode))
+        elif all_frames:
             nf = self._check(self.L.vdl2gpu_decode_blocks_ex(self.h, arr, sarr, farr, n, out, cap, C.byref(dropped), rarr,
                                                              _lib.BLK_ALL_FRAMES | (_lib.BLK_RAW_FLAGS if raw_flags else 0)))
         elif farr is None:

@@ -38,6 +38,9 @@ F_RAW_FLAGS = 16384     # (VDL2GPU_F_RAW_FLAGS, needs F_ALL_FRAMES) a flag is si
 BLK_RAW_FLAGS = 4       # ... in the mode word, beside BLK_ALL_FRAMES
 F_SYMCLK = 32768        # (VDL2GPU_F_SYMCLK) every burst's symbol timing, clock drift and fine arrival time (vdl2gpu_symclk_t)
 SYMCLK_SEG, SYMCLK_SEGS = 256, 22      # VDL2GPU_SYMCLK_SEG symbols a segment, VDL2GPU_SYMCLK_SEGS segments a record
+F_TRACKED = 65536       # (VDL2GPU_F_TRACKED) every burst's payload sliced a second time with a tracked sampling instant (vdl2gpu_trk_t)
+TRK_SEG, TRK_SEGS = 256, 22            # VDL2GPU_TRK_SEG, VDL2GPU_TRK_SEGS
+ROW_TRACKED = 7         # VDL2GPU_ROW_TRACKED: block report, row_how
 # status of a cluster head (vdl2gpu_debug_clheads()'s packed word: cl_pack() in csrc/vdl2gpu_types.h)
 CL_STEADY, CL_DEFER_FIRST, CL_NONSTEADY = 0, 1, 2
 
@@ -75,8 +78,8 @@ def cl_unpack(packed):
 EXPORTS = (
     "vdl2gpu_abi_version", "vdl2gpu_create", "vdl2gpu_destroy", "vdl2gpu_push", "vdl2gpu_sync",
     "vdl2gpu_ring_init", "vdl2gpu_ring_acquire", "vdl2gpu_ring_commit",
-    "vdl2gpu_poll", "vdl2gpu_poll_ready", "vdl2gpu_poll_levels", "vdl2gpu_poll_levels_ready", "vdl2gpu_poll_soft", "vdl2gpu_poll_soft_ready", "vdl2gpu_poll_carrier", "vdl2gpu_poll_carrier_ready", "vdl2gpu_poll_report", "vdl2gpu_poll_report_ready", "vdl2gpu_poll_feedback", "vdl2gpu_poll_feedback_ready", "vdl2gpu_poll_symclk", "vdl2gpu_poll_symclk_ready", "vdl2gpu_pending", "vdl2gpu_inflight", "vdl2gpu_get_stats", "vdl2gpu_get_timing", "vdl2gpu_get_host_profile", "vdl2gpu_last_error",
-    "vdl2gpu_strerror", "vdl2gpu_burst_to_msgblk", "vdl2gpu_decode_blocks", "vdl2gpu_decode_blocks_soft", "vdl2gpu_decode_blocks_report", "vdl2gpu_decode_blocks_feedback", "vdl2gpu_decode_blocks_ex", "vdl2gpu_poll_frames", "vdl2gpu_poll_frames_ready", "reversebits", "vdl2gpu_lo_len", "vdl2gpu_lo_table", "vdl2gpu_plan",
+    "vdl2gpu_poll", "vdl2gpu_poll_ready", "vdl2gpu_poll_levels", "vdl2gpu_poll_levels_ready", "vdl2gpu_poll_soft", "vdl2gpu_poll_soft_ready", "vdl2gpu_poll_carrier", "vdl2gpu_poll_carrier_ready", "vdl2gpu_poll_report", "vdl2gpu_poll_report_ready", "vdl2gpu_poll_feedback", "vdl2gpu_poll_feedback_ready", "vdl2gpu_poll_symclk", "vdl2gpu_poll_symclk_ready", "vdl2gpu_poll_tracked", "vdl2gpu_poll_tracked_ready", "vdl2gpu_pending", "vdl2gpu_inflight", "vdl2gpu_get_stats", "vdl2gpu_get_timing", "vdl2gpu_get_host_profile", "vdl2gpu_last_error",
+    "vdl2gpu_strerror", "vdl2gpu_burst_to_msgblk", "vdl2gpu_decode_blocks", "vdl2gpu_decode_blocks_soft", "vdl2gpu_decode_blocks_report", "vdl2gpu_decode_blocks_feedback", "vdl2gpu_decode_blocks_ex", "vdl2gpu_decode_blocks_tracked", "vdl2gpu_poll_frames", "vdl2gpu_poll_frames_ready", "reversebits", "vdl2gpu_lo_len", "vdl2gpu_lo_table", "vdl2gpu_plan",
     "vdl2gpu_exact_fo_tables", "vdl2gpu_exact_fo_index", "vdl2gpu_carrier_from_sums", "vdl2gpu_symclk_from_sums",
     "vdl2gpu_choose_fc_rtl", "vdl2gpu_choose_fc_air",
     "vdl2gpu_debug_dec", "vdl2gpu_debug_k1", "vdl2gpu_debug_lo", "vdl2gpu_debug_atan2f", "vdl2gpu_debug_rs", "vdl2gpu_debug_counters", "vdl2gpu_debug_cands", "vdl2gpu_debug_clheads", "vdl2gpu_debug_fail", "vdl2gpu_debug_segs", "vdl2gpu_debug_heads",
@@ -141,6 +144,13 @@ class SymClkT(C.Structure):
     _fields_ = [("sym_first_dec", C.c_int64), ("nsym", C.c_int32), ("nseg", C.c_int32), ("toa_sample", C.c_double),
                 ("tau0", C.c_float), ("clock_ppm", C.c_float), ("tau_rms", C.c_float), ("reserved", C.c_int32),
                 ("e", (C.c_float * 8) * 22)]
+
+
+class TrkT(C.Structure):
+    """vdl2gpu_trk_t (VDL2GPU_F_TRACKED): 2048 bytes, the rows of the timing-tracked slice laid out as the record's data[], and the
+    quarter-sample offsets the segments chose (include/vdl2gpu.h)."""
+    _fields_ = [("data", (C.c_uint8 * 255) * 8), ("d_first", C.c_int8), ("d_last", C.c_int8), ("d_min", C.c_int8), ("d_max", C.c_int8),
+                ("nseg", C.c_uint8), ("reserved", C.c_uint8 * 3)]
 
 
 class FrameT(C.Structure):
@@ -239,6 +249,11 @@ def load(testhooks: bool = False):
                                       C.POINTER(SymClkT), C.c_int]
     L.vdl2gpu_poll_symclk_ready.restype = C.c_int
     L.vdl2gpu_poll_symclk_ready.argtypes = L.vdl2gpu_poll_symclk.argtypes
+    L.vdl2gpu_poll_tracked.restype = C.c_int
+    L.vdl2gpu_poll_tracked.argtypes = [C.c_void_p, C.POINTER(BurstT), C.POINTER(LevelT), C.POINTER(SoftT), C.POINTER(CarrierT), C.POINTER(BlockRepT), C.POINTER(FbT),
+                                       C.POINTER(SymClkT), C.POINTER(TrkT), C.c_int]
+    L.vdl2gpu_poll_tracked_ready.restype = C.c_int
+    L.vdl2gpu_poll_tracked_ready.argtypes = L.vdl2gpu_poll_tracked.argtypes
     L.vdl2gpu_symclk_from_sums.restype = C.c_int
     L.vdl2gpu_symclk_from_sums.argtypes = [C.c_int64, C.c_int, C.POINTER(C.c_float), C.c_uint, C.POINTER(SymClkT), C.POINTER(C.c_double)]
     L.vdl2gpu_carrier_from_sums.restype = C.c_int
@@ -270,6 +285,9 @@ def load(testhooks: bool = False):
     L.vdl2gpu_decode_blocks_ex.restype = C.c_int
     L.vdl2gpu_decode_blocks_ex.argtypes = [C.c_void_p, C.POINTER(BurstT), C.POINTER(SoftT), C.POINTER(FbT), C.c_int, C.POINTER(FrameT), C.c_int,
                                            C.POINTER(C.c_int), C.POINTER(BlockRepT), C.c_uint32]
+    L.vdl2gpu_decode_blocks_tracked.restype = C.c_int
+    L.vdl2gpu_decode_blocks_tracked.argtypes = [C.c_void_p, C.POINTER(BurstT), C.POINTER(SoftT), C.POINTER(FbT), C.POINTER(TrkT), C.c_int, C.POINTER(FrameT),
+                                                C.c_int, C.POINTER(C.c_int), C.POINTER(BlockRepT), C.c_uint32]
     L.vdl2gpu_poll_frames.restype = C.c_int
     L.vdl2gpu_poll_frames.argtypes = [C.c_void_p, C.POINTER(FrameT), C.c_int]
     L.vdl2gpu_poll_frames_ready.restype = C.c_int
